@@ -13,17 +13,28 @@ collective); the only exchange is the RCCL all-reduce of the hit counter after e
 Other configs: --kind octree (config 3), --scene cathedral --domain 128 --rays 2097152 (config 4 shard),
 --scene cathedral --domain 128 --bounces 8 (config 5: device-resident specular bounce loop, value = casts/s),
 --kind kdtree --scene shoebox (KDTree.Shoot, a brute-force query in the reference: one measured line, profiles/).
-The default run (the driver's command, at ANY N) measures the headline workload first and then, in the same process(es), the rest
-of BASELINE's table at fewer steps, attached to the ONE JSON line as "configs": {...}, each entry with its own value, roofline,
-parity flag and (N = 1) cpu_baseline:
+
+A plain run (no --full) does only what the headline figure needs: set up, `warmup` untimed steps, exactly `steps` timed steps,
+the outputs of the last step if --dump-outputs DIR is given, and the ONE JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...; roofline, cpu_baseline and x_event_parity_vs_oracle are null).  --dump-outputs DIR writes the X_Event fields the
+timed path returned in its last step (rank 0's shard) as DIR/<field>.npy: hit and poly_id as float32, t x y z u v as float64,
+`counters.npy` = [rays, hits] of one step summed over every rank, `shard.npy` = [first ray, rays, ranks]: which rays of the burst
+the fields are (at N = 1 the whole batch); a batch whose records would pass 64 MB is cut to a fixed seeded sample of rays, whose
+indices (into the shard) go to `ray_index.npy`.  The rays are a fixed burst, so two builds given the same arguments can be compared field by field.
+
+--full adds everything else the line has carried: the oracle pass after the timed region (parity, roofline, cpu_baseline), the
+host-buffer legs, the two-stream figure, the per-launch event pairs, the device-copy bandwidth and, for the default workload (at
+ANY N), the rest of BASELINE's table at fewer steps, attached to the ONE JSON line as "configs": {...}, each entry with its own
+value, roofline, parity flag and (N = 1) cpu_baseline:
     c4, c5                   configs 4 and 5 as stated: ONE 16 777 216-ray burst / ONE 8 388 608-ray burst x 8 specular bounces into
                              the 1M-triangle cathedral, contiguous shards over the N ranks ("scaling": "strong"), hit counters
                              all-reduced (RCCL), max-over-ranks timing, every rank's X_Events checked against the oracle
     c3, c4_shard, c5_shard   N = 1 only: config 3, and one GPU's share of configs 4 / 5 at N = 8 (2M rays; 1M rays x 8)
     c2_quads                 N = 1 only: the headline workload on `hall_quads` -- the hall with its flat lattices un-split, 39k planar
                              quadrilaterals + 22k triangles: the quadrilateral build of the voxel kernel (hare_voxel_pool_quad)
-(--no-extra-configs skips them).  --force-dist runs the torch.distributed code path (init, per-step async all-reduce of
-the counters, all-gather of the timings) even at N = 1, so that the RCCL branch can be exercised on a one-GPU box.
+(--no-extra-configs skips them; --extra-configs, --inproc-scenes K and --bounce-api batch refine --full and need it).
+--force-dist runs the torch.distributed code path (init, per-step async all-reduce of the counters, all-gather of the timings)
+even at N = 1, so that the RCCL branch can be exercised on a one-GPU box.
 
 Prints ONE JSON line on rank 0.  `roofline.achieved` = algorithmic bytes per launch (SURVEY.md 8(d):
 104 + 8*C + 4*L + 96*T per ray for the grid, 64*C for the octree, + 28 B per bounce; C/L/T counted exactly
@@ -80,8 +91,24 @@ def parse_args(argv=None):
                          "N = 1; 0: off; K > 0: K scenes (a one-GPU box runs it with two scenes on its one device)")
     ap.add_argument("--bounce-api", default="device", choices=["device", "batch"],
                     help="--bounces > 1: 'device' = hare_shoot_device + hare_reflect_device on resident buffers (the timed loop); "
-                         "'batch' additionally times hare_bounce_batch from host buffers (PCIe-inclusive, reported beside it)")
-    return ap.parse_args(argv)
+                         "'batch' additionally times hare_bounce_batch from host buffers (PCIe-inclusive, reported beside it; needs --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: oracle parity, roofline, CPU baseline, host-buffer "
+                         "legs, two streams, per-launch event pairs, the appended configs and the in-process sharded leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the X_Events of the last timed step (rank 0's shard, named in shard.npy) as DIR/<field>.npy, float32 / float64, "
+                         "at most 64 MB")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    if not args.full:
+        for flag, given in (("--extra-configs", args.extra_configs), ("--inproc-scenes", args.inproc_scenes > 0),
+                            ("--bounce-api batch", args.bounce_api == "batch")):
+            if given:
+                ap.error(f"{flag} is measured by --full; add --full")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ N > 1 launcher
@@ -177,6 +204,44 @@ def load_traffic(workload_key: str):
         return e
     except Exception:
         return None
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs: what one run may write in all
+DUMP_SEED = 20240607      # the fixed sample of rays when a batch's records would pass DUMP_BYTES
+
+
+def write_outputs(out_dir: str, ev, rays: int, hits: int, shard=None) -> None:
+    """--dump-outputs: the X_Events of the last timed step as out_dir/<field>.npy (hit and poly_id as float32 -- exact for the integers
+    a scene here can hold -- the six FP64 fields as float64) and counters.npy = [rays, hits] of one step (over every rank),
+    shard.npy = [first ray, rays, ranks]: the part of the burst `ev` holds (default: all of it, one rank).  A batch whose fields would
+    pass DUMP_BYTES is cut to a fixed seeded sample of rays, ascending, whose indices into `ev` go to ray_index.npy."""
+    import numpy as np
+
+    per_ray = 2 * 4 + 6 * 8
+    if shard is None:
+        shard = (0, len(ev), 1)
+    m = len(ev)
+    idx = None
+    if m * per_ray > DUMP_BYTES - 4096:
+        m = (DUMP_BYTES - 4096) // (per_ray + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(len(ev), m, replace=False))
+        ev = ev[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"counters": np.array([rays, hits], dtype=np.float64),
+              "shard": np.array(shard, dtype=np.float64)}
+    for f in ("hit", "poly_id"):
+        a = ev[f].astype(np.float32)
+        if not np.array_equal(a.astype(np.int64), ev[f]):
+            raise ValueError(f"--dump-outputs: X_Event.{f} does not fit float32 exactly")
+        arrays[f] = a
+    for f in ("t", "x", "y", "z", "u", "v"):
+        arrays[f] = np.ascontiguousarray(ev[f], dtype=np.float64)
+    if idx is not None:
+        arrays["ray_index"] = idx.astype(np.float64)
+    elif os.path.exists(os.path.join(out_dir, "ray_index.npy")):
+        os.remove(os.path.join(out_dir, "ray_index.npy"))          # an earlier, sampled dump's: these fields are the whole batch
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 N_SIMDS = 1024            # 256 CUs x 4 SIMDs
@@ -369,6 +434,10 @@ def measure(w, env):
     fence()
     wall = time.perf_counter() - t_start
     dev_ms = ev0.elapsed_time(ev1)
+    # what the last timed step returned, taken before anything else is cast into the buffers (--dump-outputs)
+    last_events = None
+    if w.get("dump") and rank == 0:
+        last_events = (out_sets[state["set"]] if B == 1 else d_out)[:n * 56].cpu().numpy().view(H.capi.XEVENT_DTYPE)
     walls = [wall]
     if dist is not None:
         tw = torch.tensor([wall, dev_ms], dtype=torch.float64)
@@ -390,16 +459,22 @@ def measure(w, env):
         rays_total = int(last[0])
         ranks_seen = int(last[7])
 
-    # shoot-kernel duration: HIP events around each shoot launch on the launch stream (the stream the kernel runs on)
-    nrep = max(1, min(steps, 30))
-    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(2 * B)] for _ in range(nrep)]
-    cast_pass(0)
-    torch.cuda.synchronize()
-    for r in range(nrep):
-        cast_pass(0, evs[r])
-    torch.cuda.synchronize()
-    loop_ms = sum(evs[r][0].elapsed_time(evs[r][1]) for r in range(nrep)) / nrep      # one shoot launch, or the whole bounce loop
-    kern_ms_pairs = loop_ms / B               # average per cast; an event pair around every call
+    if last_events is not None:
+        write_outputs(w["dump"], last_events, rays_total, hits_total, shard=(lo, n, world))
+
+    # shoot-kernel duration: HIP events around each shoot launch on the launch stream (the stream the kernel runs on) -- launches of
+    # their own after the timed region, so only with --full; a plain run has the timed region's own estimator (one rank, one cast) or none
+    loop_ms = kern_ms_pairs = None
+    if w.get("kernel_pairs", True):
+        nrep = max(1, min(steps, 30))
+        evs = [[torch.cuda.Event(enable_timing=True) for _ in range(2 * B)] for _ in range(nrep)]
+        cast_pass(0)
+        torch.cuda.synchronize()
+        for r in range(nrep):
+            cast_pass(0, evs[r])
+        torch.cuda.synchronize()
+        loop_ms = sum(evs[r][0].elapsed_time(evs[r][1]) for r in range(nrep)) / nrep      # one shoot launch, or the whole bounce loop
+        kern_ms_pairs = loop_ms / B               # average per cast; an event pair around every call
     # ONE estimator of the kernel's duration, stated in the line (ADVICE, round 4: not the smaller of two):
     #   one rank, one cast per step: a timed step IS one shoot launch and nothing else (the counters run on, no reset kernel), so the two
     #   HIP events around the K timed launches give the average launch duration over the timed region itself -- what the contract asks
@@ -409,8 +484,7 @@ def measure(w, env):
         kern_ms, kern_src = dev_ms / steps, "timed region / steps (HIP events)"
     else:
         kern_ms, kern_src = kern_ms_pairs, "event pair per call (HIP events)"
-    per_cast_ms = [kern_ms] * B
-    events_dev = out_sets[state["set"]].cpu().numpy().tobytes() if B == 1 else None   # the bench buffers themselves, for the parity check
+    events_dev = out_sets[state["set"]].cpu().numpy().tobytes() if B == 1 and w["cpu_baseline"] else None   # the bench buffers themselves, for the parity check
 
     # Beside the contract's figure (steps on ONE stream, so that a launch's duration is that of an undisturbed launch): what a caller that
     # streams batches over TWO HIP streams gets -- one launch's drain runs under the next one's ramp (DESIGN.md 6 "Two streams").  Same
@@ -735,7 +809,7 @@ def measure(w, env):
                    "buffer_sets": n_sets,
                    "backend": ("none" if dist is None else ("rccl" if backend == "nccl" else "gloo (rehearsal)"))},
         "ms_per_step_per_rank": {"max": round(max(walls) * 1e3 / steps, 4), "min": round(min(walls) * 1e3 / steps, 4)},
-        "device_ms_per_step": round(dev_ms / steps, 4), "kernel_only_mrays_s": round(n / kern_ms / 1e3, 2),
+        "device_ms_per_step": round(dev_ms / steps, 4), "kernel_only_mrays_s": None if kern_ms is None else round(n / kern_ms / 1e3, 2),
         "end_to_end_mrays_s": None if e2e is None else round(e2e, 1),
         "hits": hits_total, "rays": rays_total, "build_s": round(build_s, 3),
         "x_event_parity_vs_oracle": parity if parity_ranks is None else bool(all(parity_ranks)),
@@ -990,12 +1064,14 @@ def main() -> None:
 
     env = Env(args, rank, local_rank, world, dist, device)
     head = {"scene": args.scene, "kind": args.kind, "domain": args.domain, "rays": args.rays, "bounces": args.bounces,
-            "steps": args.steps, "warmup": args.warmup, "cpu_baseline": not args.no_cpu_baseline, "e2e": not args.no_e2e,
-            "bounce_api": args.bounce_api, "two_streams": True}
+            "steps": args.steps, "warmup": args.warmup, "bounce_api": args.bounce_api, "dump": args.dump_outputs,
+            # a plain run: the timed steps and nothing else; --full: every check and figure beside them
+            "cpu_baseline": args.full and not args.no_cpu_baseline, "e2e": args.full and not args.no_e2e,
+            "two_streams": args.full, "copy_bw": args.full, "kernel_pairs": args.full}
     line = measure(head, env)
 
     default_workload = (args.scene == "hall" and args.kind == "voxel" and args.domain == 64 and args.rays == 1 << 20 and args.bounces == 1)
-    extras = (default_workload and not args.no_extra_configs) or args.extra_configs
+    extras = args.full and ((default_workload and not args.no_extra_configs) or args.extra_configs)
     if extras and not args.no_cpu_baseline:
         # the rest of BASELINE's table in the same process(es), driver-observed like the headline; fewer steps, one oracle pass.
         # Every rank takes part: the strong-scaled configs 4 and 5 shard over all of them
@@ -1028,7 +1104,7 @@ def main() -> None:
     k_scenes = args.inproc_scenes
     if k_scenes < 0:
         k_scenes = ndev if world > 1 else 0
-    if rank == 0 and k_scenes > 0 and not args.no_cpu_baseline:
+    if rank == 0 and k_scenes > 0 and args.full and not args.no_cpu_baseline:
         line["inproc_sharded"] = inproc_sharded(env, k_scenes, args.rays * world, args.domain if args.kind == "voxel" else 64)
     if rank == 0:
         print(fit_line(line), flush=True)

@@ -16,9 +16,11 @@ OCTREE_KERNEL = "hare_octree_group"      # what hare_shoot_kernel_name reports f
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*args):
+def _bench(*args, full=True):
+    """One bench.py run; `full`: with --full, which the oracle checks, roofline, CPU baseline and appended configs asserted here need."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *(("--full",) if full else ()), *args], capture_output=True, text=True,
+                       timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -53,9 +55,9 @@ def _oracle_hits(n_total, scene="hall", domain=64, bounces=1):
     return hits
 
 
-def test_bench_two_ranks_started_by_bench_itself():
+def test_bench_two_ranks_started_by_bench_itself(tmp_path):
     n = 65536
-    j = _bench("--gpus", "2", "--backend", "gloo", "--rays", str(n), "--steps", "3", "--warmup", "1")
+    j = _bench("--gpus", "2", "--backend", "gloo", "--rays", str(n), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
     assert j["n_gpus"] == 2 and j["scaling"] == "weak"
     assert j["rays"] == 2 * n                                   # both ranks' counters reached the reduce
     assert j["hits"] == _oracle_hits(2 * n)                     # ... and they cast the two halves of ONE 2n-ray burst
@@ -64,6 +66,9 @@ def test_bench_two_ranks_started_by_bench_itself():
     assert j["cpu_baseline"] is None                            # reported at N = 1 only
     assert j["roofline"]["kernel"] == "hare_voxel_pool_tri" and j["roofline"]["frac"] > 0
     assert j["ranks_seen_in_reduce"] == 2 and j["parity_per_rank"] == [True, True]
+    # the dump holds rank 0's shard and says so; its counters are the line's, summed over both ranks
+    assert np.load(tmp_path / "shard.npy").tolist() == [0, n, 2] and np.load(tmp_path / "hit.npy").shape == (n,)
+    assert np.load(tmp_path / "counters.npy").tolist() == [2 * n, j["hits"]]
 
 
 def test_bench_two_ranks_print_configs_4_and_5_strong_scaled():
@@ -168,3 +173,26 @@ def test_bench_inproc_sharded_leg_with_two_scenes_on_this_box_one_gpu():
     assert s["parity_vs_oracle"] is True
     k = _bench("--rays", str(n), "--steps", "2", "--warmup", "1", "--no-extra-configs", "--no-e2e")
     assert "inproc_sharded" not in k                       # off by default at N = 1
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_what_they_returned(tmp_path):
+    """The plain run (no --full): exactly --steps timed steps, the headline fields, none of the --full checks, and with --dump-outputs the
+    X_Events of the last step, which must be the oracle's for the same burst, field for field."""
+    from oracle import pyoracle as po
+    n = 65536
+    j = _bench("--rays", str(n), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path), full=False)
+    assert j["metric"].startswith("Mrays/s") and j["unit"] == "Mrays/s" and j["higher_is_better"] is True and j["dtype"] == "f64"
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0
+    assert abs(j["value"] - n / (j["ms_per_step"] * 1e3)) <= 0.01 * j["value"]        # value and ms_per_step speak of the same steps
+    assert j["roofline"] is None and j["cpu_baseline"] is None and j["x_event_parity_vs_oracle"] is None
+    assert "configs" not in j and "two_streams" not in j and "inproc_sharded" not in j and j["end_to_end_mrays_s"] is None
+    mesh = H.scenes.SCENES["hall"]()
+    rays = H.scenes.burst_rays(n, mesh.size)
+    ref, _ = po.VoxelGrid([po.Topology(mesh.verts, mesh.nverts)], domain=64).shoot(rays, nthreads=8)
+    assert not (tmp_path / "ray_index.npy").exists()
+    for f in ("hit", "poly_id", "t", "x", "y", "z", "u", "v"):
+        a = np.load(tmp_path / f"{f}.npy")
+        assert a.dtype == (np.float32 if f in ("hit", "poly_id") else np.float64) and a.shape == (n,), f
+        assert np.array_equal(a, ref[f].astype(a.dtype)), f
+    assert np.load(tmp_path / "counters.npy").tolist() == [n, j["hits"]] and j["hits"] == int(ref["hit"].sum())
+    assert np.load(tmp_path / "shard.npy").tolist() == [0, n, 1]

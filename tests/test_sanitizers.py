@@ -13,6 +13,11 @@ def test_oracle_under_asan_ubsan():
 
 
 def test_host_library_under_asan_ubsan():
-    out = subprocess.run(["make", "-C", os.path.join(ROOT, "hare_amd", "csrc"), "-s", "asan-test"], capture_output=True, text=True)
+    # where a GPU is visible the selftest's shoots run on it, and ROCm's runtime keeps a few allocations until exit.  tests/lsan_rocm.supp
+    # makes LeakSanitizer skip every leaked block with a frame of ROCm's runtime libraries in its allocation stack: those blocks, but also
+    # a runtime object the library would create and never release (a stream, an event, ...).  Leaks of memory the project allocates
+    # itself (new, malloc, containers) are still errors; a leaked runtime object is not caught here on a machine with a GPU
+    env = dict(os.environ, LSAN_OPTIONS="suppressions=" + os.path.join(ROOT, "tests", "lsan_rocm.supp"))
+    out = subprocess.run(["make", "-C", os.path.join(ROOT, "hare_amd", "csrc"), "-s", "asan-test"], capture_output=True, text=True, env=env)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "0 failures" in out.stdout and "ERROR" not in out.stderr

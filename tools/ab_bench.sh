@@ -4,7 +4,7 @@ export HARE_DEV=1   # developer overrides (HARE_VOXEL_KERNEL, HARE_TICKET, ...) 
 for k in persist pool; do
   for cfg in "--steps 20 --warmup 3" "--rays 2097152 --steps 10 --warmup 2" "--rays 4194304 --steps 6 --warmup 2" "--scene cathedral --domain 128 --rays 2097152 --steps 8 --warmup 2" "--scene cathedral --domain 128 --bounces 8 --steps 4 --warmup 1"; do
     echo "== $k $cfg"
-    HARE_VOXEL_KERNEL=$k timeout -k 10 400 python bench.py $cfg | python -c "
+    HARE_VOXEL_KERNEL=$k timeout -k 10 400 python bench.py --full $cfg | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 ROUND=${ROUND:-r06}
 O=$R/gpurun_out/${ROUND}lines
 mkdir -p $O
-run() { tag=$1; shift; echo "[$tag]" >> $O/progress.log; timeout -k 10 400 python3 $R/bench.py "$@" --no-extra-configs > $O/${ROUND}_${tag}_bench.json 2> $O/${tag}.err || echo "  failed" >> $O/progress.log; }
+run() { tag=$1; shift; echo "[$tag]" >> $O/progress.log; timeout -k 10 400 python3 $R/bench.py --full "$@" --no-extra-configs > $O/${ROUND}_${tag}_bench.json 2> $O/${tag}.err || echo "  failed" >> $O/progress.log; }
 want() { [ -z "$ONLY" ] || [[ " $ONLY " == *" $1 "* ]]; }
 want c2 && run c2 --steps 20 --warmup 3
 want c2_4M && run c2_4M --rays 4194304 --steps 8 --warmup 2
@@ -18,5 +18,5 @@ want kd && run kd --kind kdtree --scene shoebox --rays 1048576 --steps 5 --warmu
 want kd_hall && run kd_hall --kind kdtree --scene hall --rays 1048576 --steps 5 --warmup 1
 want c4 && run c4 --scene cathedral --domain 128 --rays 16777216 --steps 3 --warmup 1
 want c5full && run c5full --scene cathedral --domain 128 --rays 8388608 --bounces 8 --steps 2 --warmup 1
-if want default; then echo "[default]" >> $O/progress.log; timeout -k 10 600 python3 $R/bench.py > $O/${ROUND}_default_bench.json 2> $O/default.err || echo "  failed" >> $O/progress.log; fi
+if want default; then echo "[default]" >> $O/progress.log; timeout -k 10 600 python3 $R/bench.py --full > $O/${ROUND}_default_bench.json 2> $O/default.err || echo "  failed" >> $O/progress.log; fi
 cat $O/progress.log

@@ -4,9 +4,10 @@ export HARE_DEV=1   # developer overrides (HARE_VOXEL_KERNEL, HARE_TICKET, ...) 
 # same rays, so the two `roofline.frac` values compare per algorithmic byte.  One step after another; nothing is retried.
 R=$GRAFT_REPO_ROOT
 cd $R
-timeout -k 10 280 python3 bench.py --scene hall --domain 64 --bounces 8 --steps 5 --warmup 1 --no-e2e > gpurun_out/r2_b8_hall.json 2> gpurun_out/r2_b8_hall.err &&
-timeout -k 10 280 python3 bench.py --scene cathedral --domain 128 --bounces 8 --steps 5 --warmup 1 --no-e2e > gpurun_out/r2_b8_cath.json 2> gpurun_out/r2_b8_cath.err
+O=${OUT:-${TMPDIR:-/tmp}/hare_b8}; mkdir -p $O
+timeout -k 10 280 python3 bench.py --full --scene hall --domain 64 --bounces 8 --steps 5 --warmup 1 --no-e2e > $O/b8_hall.json 2> $O/b8_hall.err &&
+timeout -k 10 280 python3 bench.py --full --scene cathedral --domain 128 --bounces 8 --steps 5 --warmup 1 --no-e2e > $O/b8_cath.json 2> $O/b8_cath.err
 rc=$?
-tail -n 2 gpurun_out/r2_b8_hall.json gpurun_out/r2_b8_cath.json
-tail -n 3 gpurun_out/r2_b8_hall.err gpurun_out/r2_b8_cath.err
+tail -n 2 $O/b8_hall.json $O/b8_cath.json
+tail -n 3 $O/b8_hall.err $O/b8_cath.err
 exit $rc

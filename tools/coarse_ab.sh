@@ -11,8 +11,8 @@ mkdir -p $O
 SCENE=cathedral DOMAIN=128 RAYS=1048576,2097152 timeout -k 10 500 python3 tools/ab_pool.py pool:default pool:$L persist:default persist:$L > $O/voxel.log 2>&1 || { cut -c1-300 $O/voxel.log; exit 1; }
 for lib in default $V; do
   if [ $lib = default ]; then unset HARE_LIB; else export HARE_LIB=$R/$L; fi
-  timeout -k 10 250 python3 bench.py --scene cathedral --domain 128 --bounces 8 --steps 5 --warmup 1 --no-e2e > $O/b8_cath_$lib.json 2> $O/b8_cath_$lib.err || exit 1
-  timeout -k 10 250 python3 bench.py --scene cathedral --domain 128 --rays 2097152 --steps 10 --warmup 2 --no-e2e > $O/c4_$lib.json 2> $O/c4_$lib.err || exit 1
+  timeout -k 10 250 python3 bench.py --full --scene cathedral --domain 128 --bounces 8 --steps 5 --warmup 1 --no-e2e > $O/b8_cath_$lib.json 2> $O/b8_cath_$lib.err || exit 1
+  timeout -k 10 250 python3 bench.py --full --scene cathedral --domain 128 --rays 2097152 --steps 10 --warmup 2 --no-e2e > $O/c4_$lib.json 2> $O/c4_$lib.err || exit 1
 done
 cut -c1-330 $O/voxel.log
 python3 - $O <<'PY'

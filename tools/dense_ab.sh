@@ -11,9 +11,9 @@ RAYS=1048576,4194304 timeout -k 10 400 python3 tools/ab_pool.py persist:default 
 timeout -k 10 400 python3 tools/ab_oct.py persist:default persist:$D > $O/octree.log 2>&1 &&
 for lib in default dense; do
   if [ $lib = dense ]; then export HARE_LIB=$R/$D; else unset HARE_LIB; fi
-  timeout -k 10 250 python3 bench.py --scene cathedral --domain 128 --bounces 8 --steps 5 --warmup 1 --no-e2e > $O/b8_cath_$lib.json 2> $O/b8_cath_$lib.err || exit 1
-  HARE_VOXEL_KERNEL=pool timeout -k 10 250 python3 bench.py --scene hall --domain 64 --bounces 8 --steps 5 --warmup 1 --no-e2e > $O/b8_hall_pool_$lib.json 2> $O/b8_hall_pool_$lib.err || exit 1
-  timeout -k 10 250 python3 bench.py --scene cathedral --domain 128 --rays 2097152 --steps 10 --warmup 2 --no-e2e > $O/c4_$lib.json 2> $O/c4_$lib.err || exit 1
+  timeout -k 10 250 python3 bench.py --full --scene cathedral --domain 128 --bounces 8 --steps 5 --warmup 1 --no-e2e > $O/b8_cath_$lib.json 2> $O/b8_cath_$lib.err || exit 1
+  HARE_VOXEL_KERNEL=pool timeout -k 10 250 python3 bench.py --full --scene hall --domain 64 --bounces 8 --steps 5 --warmup 1 --no-e2e > $O/b8_hall_pool_$lib.json 2> $O/b8_hall_pool_$lib.err || exit 1
+  timeout -k 10 250 python3 bench.py --full --scene cathedral --domain 128 --rays 2097152 --steps 10 --warmup 2 --no-e2e > $O/c4_$lib.json 2> $O/c4_$lib.err || exit 1
 done
 rc=$?
 cut -c1-400 $O/voxel.log $O/octree.log

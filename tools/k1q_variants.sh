@@ -12,7 +12,7 @@ RAYS=1048576,4194304 timeout -k 10 500 python3 tools/ab_pool.py $specs > $O/hall
 SCENE=cathedral DOMAIN=128 RAYS=1048576,2097152 timeout -k 10 500 python3 tools/ab_pool.py $specs > $O/cath.log 2>&1 || { cut -c1-300 $O/cath.log; exit 1; }
 for lib in default "$@"; do
   if [ $lib = default ]; then unset HARE_LIB; else export HARE_LIB=$R/hare_amd/libhare_hip_$lib.so; fi
-  timeout -k 10 250 python3 bench.py --scene cathedral --domain 128 --bounces 8 --steps 5 --warmup 1 --no-e2e > $O/b8_$lib.json 2> $O/b8_$lib.err || exit 1
+  timeout -k 10 250 python3 bench.py --full --scene cathedral --domain 128 --bounces 8 --steps 5 --warmup 1 --no-e2e > $O/b8_$lib.json 2> $O/b8_$lib.err || exit 1
 done
 echo "hall D=64"; cut -c1-44,118-330 $O/hall.log
 echo "cathedral D=128"; cut -c1-44,118-330 $O/cath.log

@@ -7,7 +7,7 @@ one() {  # label, rays, extra bench args, env...
   env HARE_DEV=1 "$@" timeout -k 10 120 python bench.py --kind octree --rays $n --steps 5 --warmup 2 --no-e2e $BARGS 2>>"${ERRLOG:=${GRAFT_REPO_ROOT:-.}/gpurun_out/tools_stderr.log}" |
     python -c "import sys,json; j=json.loads(sys.stdin.read()); print('$label n=$n', j['value'], j['ms_per_step'], j['kernel_only_mrays_s'], j['x_event_parity_vs_oracle'])" || { echo "$label n=$n FAILED -- stderr tail:"; tail -n 8 "${ERRLOG:=${GRAFT_REPO_ROOT:-.}/gpurun_out/tools_stderr.log}"; }
 }
-BARGS=""
+BARGS="--full"                 # the oracle pass: parity in the line
 for sh in 150 250 350 450; do one "hybrid share=$sh" 1048576 HARE_OCTREE_KERNEL=hybrid HARE_HYBRID_SHARE=$sh; done
 BARGS="--no-cpu-baseline"
 for n in 65536 262144 524288 2097152 4194304; do

@@ -7,7 +7,7 @@ one() {  # label, rays, env...
   env HARE_DEV=1 HARE_OCTREE_KERNEL=persist "$@" timeout -k 10 120 python bench.py --kind octree --rays $n --steps 5 --warmup 2 --no-e2e $BARGS 2>>"${ERRLOG:=${GRAFT_REPO_ROOT:-.}/gpurun_out/tools_stderr.log}" |
     python -c "import sys,json; j=json.loads(sys.stdin.read()); print('$label n=$n', j['value'], j['ms_per_step'], j['kernel_only_mrays_s'], j['x_event_parity_vs_oracle'])" || { echo "$label n=$n FAILED -- stderr tail:"; tail -n 8 "${ERRLOG:=${GRAFT_REPO_ROOT:-.}/gpurun_out/tools_stderr.log}"; }
 }
-BARGS=""
+BARGS="--full"                 # the oracle pass: parity in the line
 one "K2t (16,64)" 1048576 HARE_OCTREE_TAIL=1
 one "K2g-tail all at drain" 1048576 HARE_OCTREE_TAIL=2
 BARGS="--no-cpu-baseline"

@@ -29,7 +29,7 @@ prof() {  # tag, bench args...
     pmc $tag F64 SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 -- "$@"
   fi
   # the bench line of the same command, un-profiled, with the oracle (roofline, cpu_baseline, parity)
-  python3 $R/bench.py "$@" --no-extra-configs > $O/${tag}_bench.json 2> $O/${tag}_bench.err
+  python3 $R/bench.py --full "$@" --no-extra-configs > $O/${tag}_bench.json 2> $O/${tag}_bench.err
 }
 want() { [ -z "$ONLY" ] || [[ " $ONLY " == *" $1 "* ]]; }      # ONLY="c2 c3": a subset (one gpurun call holds ~3 configurations)
 want c2 && prof c2 --steps 20 --warmup 3

@@ -1,6 +1,6 @@
 #!/bin/bash
 mkdir -p "${GRAFT_REPO_ROOT:-.}/gpurun_out"   # the failing command's stderr is kept there (ERRLOG)
-# Developer A/B: the subtree tight boxes of K2d / K2p (scene option octree_tight) on and off over batch sizes, with parity.  GPU box.
+# Developer A/B: the subtree tight boxes of K2d / K2p (scene option octree_tight) on and off over batch sizes; EXTRA=--full adds the oracle pass (parity).  GPU box.
 cd "$(dirname "$0")/.."
 for t in 1 0 1 0; do
   for n in ${RAYS:-262144 1048576 4194304}; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 mkdir -p "${GRAFT_REPO_ROOT:-.}/gpurun_out"   # the failing command's stderr is kept there (ERRLOG)
 # Developer A/B: the voxels' tight boxes of K1q (scene option voxel_tight) on and off: C2, 4M rays, C4 shard, the hall's and the
-# cathedral's 8-bounce loops, with parity.  GPU box.
+# cathedral's 8-bounce loops; EXTRA=--full adds the oracle pass (parity, roofline).  GPU box.
 cd "$(dirname "$0")/.."
 run() { local label=$1; shift
   for t in 1 0 1 0; do
