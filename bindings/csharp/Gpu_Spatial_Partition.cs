@@ -234,6 +234,48 @@ namespace Hare
                 return (long)ctr.hits;
             }
 
+            /// <summary>Receivers of every scene of this partition (hare_scene_set_receivers): centers K x 3, radii K.</summary>
+            public void SetReceivers(double[] centers, double[] radii)
+            {
+                if (centers == null || radii == null || centers.Length != 3 * radii.Length) throw new ArgumentException("centers must hold 3 x radii.Length values");
+                foreach (IntPtr s in scenes) HareHip.Check(HareHip.hare_scene_set_receivers(s, radii.Length, centers, radii));
+            }
+
+            /// <summary>Absorption table of Model[top_index] (hare_scene_set_absorption): alpha[p * bands + b] in [0, 1].</summary>
+            public void SetAbsorption(int top_index, int bands, double[] alpha)
+            {
+                if (top_index < 0 || top_index >= Model.Length) throw new ArgumentException("bad top_index");
+                if (bands < 1 || alpha == null || alpha.LongLength != (long)Model[top_index].Polygon_Count * bands)
+                    throw new ArgumentException("alpha must hold Polygon_Count x bands values");
+                foreach (IntPtr s in scenes) HareHip.Check(HareHip.hare_scene_set_absorption(s, top_index, bands, alpha));
+            }
+
+            /// <summary>B of Model[top_index]'s absorption table (1 without one): hist holds K x n_bins x B values, state (1 + B) x n.</summary>
+            public int Bands(int top_index)
+            {
+                return (int)GetOption("bands:" + top_index);
+            }
+
+            /// <summary>The bounce loop with the receiver step between its casts (hare_receive_batch_sharded): what a Pachyderm-style
+            /// caller keeps of a burst -- the energy passing each receiver, binned by arrival time -- without downloading any X_Event.
+            /// hist receives K x n_bins x B fixed-point sums (scale 2^-frac_bits), detections 2 K counts (binned, outside the bins);
+            /// state (optional, (1 + B) x rays.Length: L, then E per band) is read when state_in is true and receives the final state.
+            /// Returns the number of hits over all casts.</summary>
+            public long Receive(hare_ray[] rays, int top_index, int bounces, int n_bins, double bin_len, int frac_bits, ulong[] hist,
+                                ulong[] detections, double[] state = null, bool state_in = false)
+            {
+                if (bounces < 1) throw new ArgumentException("bounces must be at least 1");
+                long K = GetOption("receivers"), B = Bands(top_index);
+                if (hist == null || hist.LongLength < K * n_bins * B) throw new ArgumentException("hist must hold receivers x n_bins x Bands(top_index) values");
+                if (detections == null || detections.LongLength < 2 * K) throw new ArgumentException("detections must hold 2 x receivers values");
+                if (state != null && state.LongLength < (1 + B) * rays.LongLength) throw new ArgumentException("state must hold (1 + Bands(top_index)) x rays.Length values");
+                if (state_in && state == null) throw new ArgumentException("state_in needs a state array");
+                hare_counters ctr;
+                HareHip.Check(HareHip.hare_receive_batch_sharded(scenes, scenes.Length, Kind, top_index, rays.LongLength, rays, null, null, bounces, 0u,
+                                                                 n_bins, bin_len, frac_bits, state_in ? state : null, state, hist, detections, out ctr));
+                return (long)ctr.hits;
+            }
+
             /// <summary>The same on managed objects: result[b][i] is the X_Event of ray i in cast b (X_Event() once the ray has
             /// left the model).  rays[] is not modified.</summary>
             public X_Event[][] Bounce(Ray[] rays, int top_index, int bounces)

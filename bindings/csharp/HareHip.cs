@@ -210,6 +210,26 @@ namespace Hare
                                                         int bounces, uint flags, IntPtr d_work, IntPtr d_events_all, IntPtr d_events_last,
                                                         IntPtr d_counters, IntPtr d_counters_per_cast, IntPtr stream);
 
+            // Receivers: energy-time histograms from the bounce loop (include/hare_hip.h, "receivers")
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_scene_set_receivers(IntPtr scene, int K, [In] double[] centers, [In] double[] radii);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_scene_set_absorption(IntPtr scene, int top_index, int B, [In] double[] alpha);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_receive_batch(IntPtr scene, int kind, int top_index, long n, [In] hare_ray[] rays, int[] excl1, int[] excl2,
+                                                        int bounces, uint flags, int n_bins, double bin_len, int frac_bits, [In] double[] state_in,
+                                                        [Out] double[] state_out, [Out] ulong[] hist, [Out] ulong[] detections, out hare_counters ctr);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_receive_batch_sharded([In] IntPtr[] scenes, int n_scenes, int kind, int top_index, long n, [In] hare_ray[] rays,
+                                                                int[] excl1, int[] excl2, int bounces, uint flags, int n_bins, double bin_len,
+                                                                int frac_bits, [In] double[] state_in, [Out] double[] state_out, [Out] ulong[] hist,
+                                                                [Out] ulong[] detections, out hare_counters ctr);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_receive_device(IntPtr scene, int kind, int top_index, long n, IntPtr d_rays, IntPtr d_excl1, IntPtr d_excl2,
+                                                         int bounces, uint flags, int n_bins, double bin_len, int frac_bits, IntPtr d_state,
+                                                         IntPtr d_work, IntPtr d_events_last, IntPtr d_hist, IntPtr d_detections, IntPtr d_counters,
+                                                         IntPtr stream);
+
             public static void Check(int rc)
             {
                 if (rc == 0) return;

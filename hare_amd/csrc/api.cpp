@@ -173,6 +173,7 @@ void hare_scene_destroy(hare_scene* s)
         for (void*& p : s->d_kd_tight) dev_free(H, p);
         for (void*& p : s->d_kd_dev) dev_free(H, p);
         free_bounce_buffers(H, *s);
+        free_receivers(H, *s);
         for (Scene::BatchCtx& c : s->ctx) {
             for (hipStream_t& x : c.st)
                 if (x) { (void)H->StreamSynchronize(x); (void)H->StreamDestroy(x); x = nullptr; }
@@ -895,6 +896,7 @@ const OptionEntry kOptionTable[] = {
         {"bounce_pack", &SceneOptions::bounce_pack, 0, 1},
         {"voxel_walk", &SceneOptions::voxel_walk, 0, 1},
         {"voxel_skip", &SceneOptions::voxel_skip, 0, 1},
+        {"receive_aggregate", &SceneOptions::receive_aggregate, 0, 1},
 };
 }  // namespace
 
@@ -918,6 +920,24 @@ int hare_scene_get_option(const hare_scene* s, const char* name, int64_t* value)
     }
     if (strcmp(name, "hip_malloc_calls") == 0 || strcmp(name, "hip_free_calls") == 0 || strcmp(name, "hip_sync_calls") == 0) {
         *value = (int64_t)hip_call_count(name[4] == 'm' ? 0 : (name[4] == 'f' ? 1 : 2));
+        return HARE_OK;
+    }
+    if (strcmp(name, "receivers") == 0) {             // hare_scene_set_receivers: K (0: none set)
+        *value = (int64_t)(s->rcv.size() / 4);
+        return HARE_OK;
+    }
+    if (strcmp(name, "bands") == 0) {                 // hare_scene_set_absorption: B of topology 0 (1: no table)
+        *value = scene_bands(*s, 0);
+        return HARE_OK;
+    }
+    if (strncmp(name, "bands:", 6) == 0) {            // ... of topology <top>: what a receive call's histogram and state are sized by
+        char* end = nullptr;
+        const long top = strtol(name + 6, &end, 10);
+        if (end == name + 6 || *end != '\0' || top < 0 || top >= (long)s->topos.size()) {
+            set_error(std::string("hare_scene_get_option: bad topology in ") + name);
+            return HARE_E_INVALID;
+        }
+        *value = scene_bands(*s, (int32_t)top);
         return HARE_OK;
     }
     if (strcmp(name, "octree_scratch_bytes") == 0) {

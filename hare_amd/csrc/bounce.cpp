@@ -41,10 +41,12 @@ void free_bounce_buffers(const HipApi* H, Scene& s)
         Scene::BounceBuf& b = c.bounce;
         if (b.copy_st) { (void)H->StreamSynchronize(b.copy_st); (void)H->StreamDestroy(b.copy_st); b.copy_st = nullptr; }
         for (void** p : {&b.rays[0], &b.rays[1], &b.excl[0], &b.excl[1], &b.excl2, &b.idx[0], &b.idx[1], &b.ev[0], &b.ev[1], &b.full,
-                         &b.tiles, &b.ctr})
+                         &b.tiles, &b.ctr, &b.state, &b.hist})
             dev_free(H, *p);
         b.cap = 0;
         b.ctr_cap = 0;
+        b.state_cap = 0;
+        b.hist_cap = 0;
     }
 }
 
@@ -213,6 +215,73 @@ int bounce_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind,
     return HARE_OK;
 }
 
+// hare_receive_batch: what one scene's share of the rays computes, into host buffers.  The state planes of the caller's arrays are
+// `stride` doubles apart (the whole batch's n); hist / det are this scene's own (written).
+struct ReceiveJob {
+    int32_t n_bins = 1;
+    double bin_len = 1;
+    int32_t frac_bits = 0;
+    const double* state_in = nullptr;
+    double* state_out = nullptr;
+    int64_t stride = 0;
+    uint64_t* hist = nullptr;
+    uint64_t* det = nullptr;
+};
+
+// The receive loop for one scene: rays, exclusions and state go up, the loop is enqueued ONCE (a launch per cast, hare_receive_reflect
+// behind each), histogram, detections, final state and per-cast counters come down, one synchronisation -- hare_bounce_batch's
+// last-cast-only path.  No events are downloaded.
+int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind, int32_t top, int64_t n, const hare_ray* rays,
+                     const int32_t* excl1, const int32_t* excl2, int32_t bounces, uint32_t flags, const ReceiveJob& job, hare_counters* per_cast)
+{
+    Scene::BounceBuf& b = c.bounce;
+    if (int rc = ensure_bounce_buffers(H, b, n, bounces)) return rc;
+    const int32_t B = scene_bands(s, top);
+    const size_t K = s.rcv.size() / 4;
+    const size_t state_bytes = (size_t)n * (size_t)(1 + B) * sizeof(double);
+    const size_t hist_words = K * (size_t)job.n_bins * (size_t)B, hist_bytes = (hist_words + 2 * K) * sizeof(uint64_t);
+    if (state_bytes > b.state_cap) {
+        dev_free(H, b.state);
+        b.state_cap = 0;
+        HIP_TRY(H->Malloc(&b.state, state_bytes));
+        b.state_cap = state_bytes;
+    }
+    if (hist_bytes > b.hist_cap) {
+        dev_free(H, b.hist);
+        b.hist_cap = 0;
+        HIP_TRY(H->Malloc(&b.hist, hist_bytes));
+        b.hist_cap = hist_bytes;
+    }
+    if (!c.st[0]) HIP_TRY(H->StreamCreate(&c.st[0]));
+    hipStream_t st = c.st[0];
+    uint64_t* const d_hist = (uint64_t*)b.hist;
+    uint64_t* const d_det = d_hist + hist_words;
+    double* const d_state = (double*)b.state;
+    HIP_TRY(H->MemcpyAsync(b.rays[0], rays, (size_t)n * sizeof(hare_ray), hipMemcpyHostToDevice, st));
+    if (excl1) HIP_TRY(H->MemcpyAsync(b.excl[0], excl1, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (excl2) HIP_TRY(H->MemcpyAsync(b.excl2, excl2, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (job.state_in)
+        for (int32_t p = 0; p <= B; ++p)
+            HIP_TRY(H->MemcpyAsync(d_state + (size_t)p * (size_t)n, job.state_in + (size_t)p * (size_t)job.stride, (size_t)n * sizeof(double),
+                                   hipMemcpyHostToDevice, st));
+    HIP_TRY(H->MemsetAsync(b.hist, 0, hist_bytes, st));
+    HIP_TRY(H->MemsetAsync(b.ctr, 0, (size_t)bounces * sizeof(hare_counters), st));
+    ReceiveArgs ra;
+    if (int rc = receive_args(s, top, job.n_bins, job.bin_len, job.frac_bits, d_state, d_hist, d_det, job.state_in == nullptr, ra)) return rc;
+    if (int rc = bounce_device_impl(s, H, kind, top, n, b.rays[0], excl1 ? b.excl[0] : nullptr, excl2 ? b.excl2 : nullptr, bounces, flags, b.ev[1],
+                                    nullptr, b.ev[0], nullptr, b.ctr, st, &ra))
+        return rc;
+    HIP_TRY(H->MemcpyAsync(job.hist, d_hist, hist_words * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(H->MemcpyAsync(job.det, d_det, 2 * K * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (job.state_out)
+        for (int32_t p = 0; p <= B; ++p)
+            HIP_TRY(H->MemcpyAsync(job.state_out + (size_t)p * (size_t)job.stride, d_state + (size_t)p * (size_t)n, (size_t)n * sizeof(double),
+                                   hipMemcpyDeviceToHost, st));
+    HIP_TRY(H->MemcpyAsync(per_cast, b.ctr, (size_t)bounces * sizeof(hare_counters), hipMemcpyDeviceToHost, st));
+    HIP_TRY(H->StreamSynchronize(st));
+    return HARE_OK;
+}
+
 int check_args(const char* who, int64_t n, const hare_ray* rays, int32_t bounces, hare_xevent* events_all, hare_xevent* events_last)
 {
     if (n < 0 || bounces < 1 || bounces > 4096 || (n > 0 && !rays)) {
@@ -225,7 +294,8 @@ int check_args(const char* who, int64_t n, const hare_ray* rays, int32_t bounces
 }
 
 int bounce_one(hare_scene* s, int32_t kind, int32_t top, int64_t n, const hare_ray* rays, const int32_t* excl1, const int32_t* excl2,
-               int32_t bounces, uint32_t flags, hare_xevent* events_all, int64_t stride, hare_xevent* events_last, hare_counters* per_cast)
+               int32_t bounces, uint32_t flags, hare_xevent* events_all, int64_t stride, hare_xevent* events_last, hare_counters* per_cast,
+               const ReceiveJob* job = nullptr)
 {
     if (top < 0 || top >= (int32_t)s->topos.size()) {
         set_error("hare_bounce_batch: bad top_index");
@@ -243,6 +313,7 @@ int bounce_one(hare_scene* s, int32_t kind, int32_t top, int64_t n, const hare_r
         if (rc) return rc;
         rc = upload_polys(*s, H);
         if (rc) return rc;
+        if (job && (rc = receive_ready(*s, H, "hare_receive_batch"))) return rc;
         if (n == 0) return HARE_OK;
         s->cv.wait(lk, [&] { for (Scene::BatchCtx& x : s->ctx) if (!x.busy) return true; return false; });
         for (Scene::BatchCtx& x : s->ctx)
@@ -256,7 +327,8 @@ int bounce_one(hare_scene* s, int32_t kind, int32_t top, int64_t n, const hare_r
         hare_scene* s; Scene::BatchCtx* c;
         ~Release() { { std::lock_guard<std::mutex> lk(s->mu); c->busy = false; } s->cv.notify_one(); }
     } release{s, c};
-    const int rc = bounce_on_scene(*s, H, *c, kind, top, n, rays, excl1, excl2, bounces, flags, events_all, stride, events_last, per_cast);
+    const int rc = job ? receive_on_scene(*s, H, *c, kind, top, n, rays, excl1, excl2, bounces, flags, *job, per_cast)
+                       : bounce_on_scene(*s, H, *c, kind, top, n, rays, excl1, excl2, bounces, flags, events_all, stride, events_last, per_cast);
     if (rc != HARE_OK) {          // copies into the caller's buffers may still be in flight: drain before the error returns
         if (c->st[0]) (void)H->StreamSynchronize(c->st[0]);
         if (c->bounce.copy_st) (void)H->StreamSynchronize(c->bounce.copy_st);
@@ -373,6 +445,104 @@ int hare_bounce_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int32
             if (ctr) add_counters(*ctr, pcs[(size_t)k][(size_t)b]);
             if (ctr_per_cast) add_counters(ctr_per_cast[b], pcs[(size_t)k][(size_t)b]);
         }
+    return HARE_OK;
+    GUARD_END
+}
+
+int hare_receive_batch(hare_scene* s, int32_t kind, int32_t top_index, int64_t n, const hare_ray* rays, const int32_t* excl1,
+                       const int32_t* excl2, int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits,
+                       const double* state_in, double* state_out, uint64_t* hist, uint64_t* detections, hare_counters* ctr)
+{
+    hare_scene* const one[1] = {s};
+    return hare_receive_batch_sharded(one, 1, kind, top_index, n, rays, excl1, excl2, bounces, flags, n_bins, bin_len, frac_bits, state_in,
+                                      state_out, hist, detections, ctr);
+}
+
+int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int32_t kind, int32_t top_index, int64_t n, const hare_ray* rays,
+                               const int32_t* excl1, const int32_t* excl2, int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len,
+                               int32_t frac_bits, const double* state_in, double* state_out, uint64_t* hist, uint64_t* detections,
+                               hare_counters* ctr)
+{
+    const char* who = n_scenes == 1 ? "hare_receive_batch" : "hare_receive_batch_sharded";
+    if (!scenes || n_scenes < 1 || n_scenes > 64) {
+        set_error(std::string(who) + ": need 1..64 scenes");
+        return HARE_E_INVALID;
+    }
+    for (int32_t k = 0; k < n_scenes; ++k)
+        if (!scenes[k]) {
+            set_error("null scene");
+            return HARE_E_INVALID;
+        }
+    hare_scene* const s0 = scenes[0];
+    if (int rc = receive_check_args(who, *s0, kind, top_index, n, bounces, n_bins, bin_len, frac_bits)) return rc;
+    if ((n > 0 && !rays) || !hist || !detections) {
+        set_error(std::string(who) + ": null rays, histogram or detections");
+        return HARE_E_INVALID;
+    }
+    for (int32_t k = 1; k < n_scenes; ++k)       // the shards must compute the same thing
+        if (scenes[k]->rcv != s0->rcv || scene_bands(*scenes[k], top_index) != scene_bands(*s0, top_index) ||
+            (top_index < (int32_t)scenes[k]->topos.size() ? scenes[k]->topos[(size_t)top_index].P : -1) != s0->topos[(size_t)top_index].P) {
+            set_error(std::string(who) + ": the scenes differ in receivers, bands or polygons");
+            return HARE_E_INVALID;
+        }
+    GUARD_BEGIN
+    const int G = n_scenes;
+    const size_t K = s0->rcv.size() / 4, hist_words = K * (size_t)n_bins * (size_t)scene_bands(*s0, top_index);
+    memset(hist, 0, hist_words * sizeof(uint64_t));
+    memset(detections, 0, 2 * K * sizeof(uint64_t));
+    if (ctr) memset(ctr, 0, sizeof *ctr);
+    std::vector<int> rcs((size_t)G, HARE_OK);
+    std::vector<std::string> errs((size_t)G);
+    std::vector<std::vector<hare_counters>> pcs((size_t)G, std::vector<hare_counters>((size_t)bounces));
+    std::vector<std::vector<uint64_t>> hists((size_t)G), dets((size_t)G);    // shard 0 writes the caller's arrays
+    for (int k = 1; k < G; ++k) {
+        hists[(size_t)k].assign(hist_words, 0);
+        dets[(size_t)k].assign(2 * K, 0);
+    }
+    auto shard = [&](int k) {
+        const int64_t lo = (int64_t)((__int128)n * k / G), hi = (int64_t)((__int128)n * (k + 1) / G);
+        memset(pcs[(size_t)k].data(), 0, (size_t)bounces * sizeof(hare_counters));
+        ReceiveJob job;
+        job.n_bins = n_bins;
+        job.bin_len = bin_len;
+        job.frac_bits = frac_bits;
+        job.state_in = state_in ? state_in + lo : nullptr;
+        job.state_out = state_out ? state_out + lo : nullptr;
+        job.stride = n;
+        job.hist = k == 0 ? hist : hists[(size_t)k].data();
+        job.det = k == 0 ? detections : dets[(size_t)k].data();
+        try {
+            rcs[(size_t)k] = bounce_one(scenes[k], kind, top_index, hi - lo, rays ? rays + lo : nullptr, excl1 ? excl1 + lo : nullptr,
+                                        excl2 ? excl2 + lo : nullptr, bounces, flags, nullptr, n, nullptr, pcs[(size_t)k].data(), &job);
+        } catch (...) {
+            rcs[(size_t)k] = HARE_E_NOMEM;
+            set_error(std::string(who) + ": exception in a shard");
+        }
+        if (rcs[(size_t)k] != HARE_OK) errs[(size_t)k] = hare_last_error();
+    };
+    std::vector<std::thread> workers;
+    workers.reserve((size_t)G);
+    for (int k = 1; k < G; ++k) {
+        try {
+            workers.emplace_back(shard, k);
+        } catch (...) {
+            shard(k);
+        }
+    }
+    shard(0);
+    for (auto& w : workers) w.join();
+    for (int k = 0; k < G; ++k)
+        if (rcs[(size_t)k] != HARE_OK) {
+            set_error(G == 1 ? errs[0] : "shard " + std::to_string(k) + ": " + errs[(size_t)k]);
+            return rcs[(size_t)k];
+        }
+    for (int k = 1; k < G; ++k) {                 // integer sums (mod 2^64): the order of the shards does not matter
+        for (size_t w = 0; w < hist_words; ++w) hist[w] += hists[(size_t)k][w];
+        for (size_t w = 0; w < 2 * K; ++w) detections[w] += dets[(size_t)k][w];
+    }
+    if (ctr)
+        for (int k = 0; k < G; ++k)
+            for (int32_t b = 0; b < bounces; ++b) add_counters(*ctr, pcs[(size_t)k][(size_t)b]);
     return HARE_OK;
     GUARD_END
 }

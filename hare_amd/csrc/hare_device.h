@@ -473,6 +473,32 @@ struct ShootIO {
     int32_t oct_spill_cap;
 };
 
+// hare_receive_reflect (receive.hip): the receiver step + state update + reflection of one cast of the receive loop (launch.cpp)
+constexpr int kMaxBands = 8;
+constexpr int kMaxReceivers = 256;
+struct ReceiveArgs {
+    const PolyRec* polys;      // Model[top]
+    RayRec* rays;              // n rays, the ray each lane's cast received; overwritten by the reflection (not in the last cast)
+    const XEventRec* ev;       // the cast's n events
+    int32_t* excl;             // marks / next exclusions (the loop's work array; -2: retired)
+    unsigned char* block_live; // nullable: a byte per 64 rays, as hare_reflect writes it
+    double* state;             // (1 + bands) planes of n doubles: L, E[0 .. bands-1]
+    const double* alpha;       // nullable: P x bands absorption coefficients of Model[top]
+    const double* rcv;         // n_rcv x 4: cx, cy, cz, r * r
+    unsigned long long* hist;  // n_rcv x n_bins x bands, accumulated
+    unsigned long long* det;   // 2 n_rcv, accumulated
+    long long n;
+    double bin_len;            // > 0
+    double scale;              // 2^frac_bits
+    int32_t bands;             // 1 .. kMaxBands
+    int32_t n_rcv;             // 1 .. kMaxReceivers
+    int32_t n_bins;
+    int32_t marks_valid;       // excl holds the previous reflection's marks (every cast after the first)
+    int32_t last;              // 1: the loop's last cast -- no reflection
+    int32_t aggregate;         // 1: one atomic per distinct (receiver, bin) per wave; 0: one per detecting lane (scene option "receive_aggregate")
+    int32_t init_state;        // first cast only: every ray starts at L = 0, E = 1 (state is written, not read: hare_receive_batch without state_in)
+};
+
 #if defined(__HIPCC__)
 // Every kernel argument as a scalar of its OWN (round 6).  The compiler fetches the 720-byte argument block in tuples of 8 and 16 SGPRs and,
 // short of SGPRs in these kernels, spills and reloads them AS tuples: a block that needs the rays' pointer reloaded sixteen registers to get

@@ -13,6 +13,7 @@
 //   hare_kdtree_shoot*          KDTree.Shoot (visits every leaf, like the reference)
 //   hare_reflect           K3   specular bounce between casts (harness-defined); hare_live_count / hare_scan_tiles /
 //                               hare_reflect_compact / hare_events_*: the same with the survivors packed (hare_bounce_batch)
+//   hare_receive_reflect        hare_reflect plus the receiver step of the receive loop (receive.hip: energy-time histograms)
 //   hare_cull_audit             tests only: FP32 cull vs exact test on every ray x polygon pair
 //   hare_vb_*, hare_scan_*, hare_ob_*  Voxel_Grid / Octree construction (build_kernels.hip, included at the end)
 //
@@ -1743,15 +1744,10 @@ __global__ __launch_bounds__(256) void hare_kdtree_shoot_count(KdArgs g, ShootIO
 // that missed are marked dead (-2).  Returns whether the ray lives on.
 // marks_valid (the bounce loop from its second reflection on): excl_out already holds the previous reflection's marks, and a ray marked -2 is
 // retired -- its event is a miss record whatever it says, so neither the event (56 B) nor anything else of it is read.
-__device__ __forceinline__ bool reflect_one(const PolyRec* polys, RayRec* rays, const XEventRec* ev, int32_t* excl_out, int64_t i, bool marks_valid)
+// The reflection of a ray that hit, in ONE place: hare_reflect, hare_reflect_compact and hare_receive_reflect (receive.hip) must all give
+// the oracle's bits, so none of them spells the arithmetic out on its own.
+__device__ __forceinline__ RayRec reflect_hit(const PolyRec* polys, const RayRec& r, const XEventRec& e)
 {
-    if (marks_valid && excl_out[i] == -2) return false;
-    const XEventRec e = ev[i];
-    if (!e.hit) {
-        excl_out[i] = -2;
-        return false;
-    }
-    const RayRec r = rays[i];
     const PolyRec& p = polys[e.poly_id];
     const double dn = dot3(r.dx, r.dy, r.dz, p.n[0], p.n[1], p.n[2]);
     const double k = 2.0 * dn;
@@ -1760,7 +1756,17 @@ __device__ __forceinline__ bool reflect_one(const PolyRec* polys, RayRec* rays, 
     o.dx = r.dx - k * p.n[0];
     o.dy = r.dy - k * p.n[1];
     o.dz = r.dz - k * p.n[2];
-    rays[i] = o;
+    return o;
+}
+__device__ __forceinline__ bool reflect_one(const PolyRec* polys, RayRec* rays, const XEventRec* ev, int32_t* excl_out, int64_t i, bool marks_valid)
+{
+    if (marks_valid && excl_out[i] == -2) return false;
+    const XEventRec e = ev[i];
+    if (!e.hit) {
+        excl_out[i] = -2;
+        return false;
+    }
+    rays[i] = reflect_hit(polys, rays[i], e);
     excl_out[i] = e.poly_id;
     return true;
 }
@@ -1868,16 +1874,7 @@ __global__ __launch_bounds__(256) void hare_reflect_compact(const PolyRec* polys
         run += wc[0] + wc[1] + wc[2] + wc[3];
         __syncthreads();
         if (live) {
-            const RayRec r = rays_in[i];
-            const PolyRec& p = polys[e.poly_id];
-            const double dn = dot3(r.dx, r.dy, r.dz, p.n[0], p.n[1], p.n[2]);
-            const double kk = 2.0 * dn;
-            RayRec o;
-            o.x = e.x; o.y = e.y; o.z = e.z;
-            o.dx = r.dx - kk * p.n[0];
-            o.dy = r.dy - kk * p.n[1];
-            o.dz = r.dz - kk * p.n[2];
-            rays_out[off] = o;
+            rays_out[off] = reflect_hit(polys, rays_in[i], e);
             excl_out[off] = e.poly_id;
             idx_out[off] = idx_in ? idx_in[i] : (int32_t)i;
         }
@@ -1948,6 +1945,7 @@ __global__ __launch_bounds__(256) void hare_occlusion(const XEventRec* ev, const
 
 }  // extern "C"
 
+#include "receive.hip"         // hare_receive_reflect: the receiver step of hare_receive_device's loop
 #include "voxel_pool.hip"
 #include "octree_pool.hip"
 #include "octree_group.hip"

@@ -454,7 +454,8 @@ static void fill_voxel_args(const Scene& s, int32_t top, VoxelArgs& g)
 //   d_all    nullable: casts x n events, cast-major;  d_last: nullable when d_all is given: the last cast's n events
 //   d_ctr    nullable: totals, accumulated (rays = casts with a live ray);  d_ctr_casts: nullable, `casts` blocks, accumulated
 int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, void* d_rays, const void* d_e1, const void* d_e2,
-                       int32_t casts, uint32_t flags, void* d_work, void* d_all, void* d_last, void* d_ctr, void* d_ctr_casts, hipStream_t st)
+                       int32_t casts, uint32_t flags, void* d_work, void* d_all, void* d_last, void* d_ctr, void* d_ctr_casts, hipStream_t st,
+                       const ReceiveArgs* rcv)
 {
     if (n < 0 || casts < 1 || casts > 4096 || top < 0 || top >= (int32_t)s.topos.size()) {
         set_error("hare_bounce: bad n, bounces or top_index");
@@ -474,12 +475,12 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
     hare_xevent* const all = (hare_xevent*)d_all;
     hare_xevent* const last = d_last ? (hare_xevent*)d_last : all + (size_t)(casts - 1) * (size_t)n;
     int32_t* const work = (int32_t*)d_work;
-    if (!M.reflect || !M.events_fill_miss) {
+    if (!M.reflect || !M.events_fill_miss || (rcv && !M.receive_reflect)) {
         set_error("hare_bounce: bounce kernels missing from code object");
         return HARE_E_STATE;
     }
-    // ---- one launch?
-    if (kind == HARE_KIND_VOXEL && casts <= kBounceMaxCasts && flags == 0 && s.vox.built && !s.d_cells.empty()) {
+    // ---- one launch?  (never for the receive loop: its receiver step runs between the casts)
+    if (!rcv && kind == HARE_KIND_VOXEL && casts <= kBounceMaxCasts && flags == 0 && s.vox.built && !s.d_cells.empty()) {
         const KernChoice kc = choose_kernel(s, &M, kind, (size_t)top, n, 0u);
         const bool quads = s.topos[top].has_quads, coarse = s.occ_shift > 0;
         hipFunction_t f = !coarse ? (quads ? M.voxel_bounce_quad : M.voxel_bounce_tri) : (quads ? M.voxel_bounce_quad_g : M.voxel_bounce_tri_g);
@@ -539,13 +540,16 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
     // second only serves the one-launch loop): n / 64 bytes, n / 64 words, the count.  A closed room, where nothing dies, pays the one-workgroup launch per cast (~1 %; scene option "bounce_pack" 0 switches it off).  Events and counters are those of the plain loop
     // (tests: every cast against the oracle's loop, open soups and closed rooms).  Voxel_Grid batches the pool kernel serves only; other
     // kernels cast all n rays and skip the retired ones as before.
+    // The bytes start on a 16-byte boundary (hare_live_blocks reads them sixteen at a time): work + n is one only when n % 4 == 0 (and the
+    // caller's array is aligned), so the pad in front of them counts against the second half's n * 4 bytes.
     const int64_t nblk = (n + 63) / 64;
-    unsigned char* const blk_live = (unsigned char*)(work + n);
+    const size_t blk_pad = (size_t)((16u - ((uintptr_t)(work + n) & 15u)) & 15u);
+    unsigned char* const blk_live = (unsigned char*)(work + n) + blk_pad;
     uint32_t* const blk_list = (uint32_t*)(blk_live + ((nblk + 15) & ~(int64_t)15));
     uint32_t* const blk_words = blk_list + nblk;          // {list length, epoch of the last dead block, epoch whose list is ready}
     // (Not with a buffer per cast, `all`: there every slot of every cast is written, a retired ray's with its miss record.)
     const bool use_blocks = !all && kind == HARE_KIND_VOXEL && M.live_blocks != nullptr && s.opt.bounce_pack != 0 && n >= 4096 && nblk <= 0x7FFFFFF0ll &&
-                            (size_t)((nblk + 15) & ~(int64_t)15) + (size_t)(nblk + 4) * 4u <= (size_t)n * 4u &&
+                            blk_pad + (size_t)((nblk + 15) & ~(int64_t)15) + (size_t)(nblk + 4) * 4u <= (size_t)n * 4u &&
                             choose_kernel(s, &M, kind, (size_t)top, n, flags | HARE_SHOOT_RETIRED_RAYS).k == Kern::VoxelPool;
     if (int rc = sum_counters(-1)) return rc;            // the per-cast blocks are accumulated into: the totals get what THIS loop adds
     // From here on the caller's totals have the per-cast blocks SUBTRACTED: whatever ends the loop early (a cast whose kernel has no counting
@@ -566,7 +570,30 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
         extra.internal_flags = (c > 0 && !all) ? (uint32_t)SHOOT_RETIRED_SILENT : 0u;
         if (c > 0 && use_blocks) { extra.blocks = blk_list; extra.blk_words = blk_words; }
         if (int rc = shoot_device_impl(s, H, kind, top, n, d_rays, c == 0 ? d_e1 : work, c == 0 ? d_e2 : nullptr, f, out_c, ctr_c, st, nullptr, nullptr, &extra)) return fail(rc);
-        if (c + 1 < casts) {
+        if (rcv) {
+            // the receiver step, the state update and (but behind the last cast) the reflection: hare_receive_reflect in hare_reflect's place
+            const bool last_cast = c + 1 == casts;
+            ReceiveArgs ra = *rcv;
+            ra.polys = (const PolyRec*)s.d_polys[(size_t)top];
+            ra.rays = (RayRec*)d_rays;
+            ra.ev = (const XEventRec*)out_c;
+            ra.excl = work;
+            ra.block_live = (use_blocks && !last_cast) ? blk_live : nullptr;
+            ra.n = n;
+            ra.marks_valid = c > 0 ? 1 : 0;
+            ra.last = last_cast ? 1 : 0;
+            ra.init_state = c == 0 ? rcv->init_state : 0;      // the starting state is the first cast's business only
+            void* a[] = {&ra};
+            if (int rc = launch(H, M.receive_reflect, (unsigned)((n + 255) / 256), 256, 0, st, a)) return fail(rc);
+            if (use_blocks && !last_cast) {
+                uint32_t nb = (uint32_t)nblk;
+                const unsigned char* blc = blk_live;
+                uint32_t* lst = blk_list;
+                uint32_t* cnt = blk_words;
+                void* a2[] = {&blc, &nb, &lst, &cnt};
+                if (int rc = launch(H, M.live_blocks, 1, 1024, 0, st, a2)) return fail(rc);
+            }
+        } else if (c + 1 < casts) {
             const void* polys = s.d_polys[(size_t)top];
             const void* ev = out_c;
             void* ex = work;

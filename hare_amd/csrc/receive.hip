@@ -1,0 +1,149 @@
+// receive.hip -- hare_receive_reflect: the receiver step of the receive loop (include/hare_hip.h, "receivers"), #included from kernels.hip.
+//
+// One lane per ray, in place of hare_reflect behind every cast of hare_receive_device's loop (launch.cpp: bounce_device_impl with a
+// ReceiveArgs).  A live ray reads its ray, its event and its state once; runs through every receiver sphere in ascending order with the
+// FP64 test of the header (no contraction: -ffp-contract=off); updates its state; and, except in the last cast, is reflected exactly as
+// hare_reflect does it (the same function, reflect_hit; the same marks and live-block byte).  A retired ray (-2) costs one 4-byte load; a
+// workgroup whose rays are all retired also passes one barrier and stages no receivers.
+//
+// The receivers (at most 256 x 32 B) are staged in LDS once per workgroup and read with wave-uniform addresses (the loop index is uniform):
+// one broadcast ds_read per receiver.  (Read straight from the device array they compiled to vector loads: the atomics in the loop keep
+// the compiler from proving the array unchanged, so it does not use scalar loads.)
+// No pre-cull: the test is a handful of FP64 operations per receiver and the exact test decides anyway.
+// Histogram adds are uint64 fixed point, so their order does not matter.  A detection is rare except in the direct sound of a burst,
+// where a wave's rays that pass a receiver near the source land in one or two bins: with `aggregate` the wave sums its lanes' adds
+// per distinct bin first and issues ONE atomic instruction per (receiver, bin), lanes 0 .. B-1 adding the B bands (8 B contiguous bytes).
+
+static __device__ __forceinline__ unsigned long long wave_allsum_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;  // every lane
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect(ReceiveArgs a)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int B = a.bands;
+    __shared__ double rcv[kMaxReceivers * 4];                        // the receivers: uniform LDS reads (broadcast) in the loop below
+    bool live = i < a.n;
+    if (live && a.marks_valid && a.excl[i] == -2) live = false;
+    // a workgroup whose 256 rays are all retired stages nothing: its rays cost their 4-byte mark and this one barrier (it still writes
+    // its live-block bytes, below)
+    if (!__syncthreads_or(live ? 1 : 0)) {
+        if (a.block_live && lane == 0) {
+            const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+            if (blk * 64 < a.n) a.block_live[blk] = 0;
+        }
+        return;
+    }
+    for (int k = threadIdx.x; k < a.n_rcv * 4; k += blockDim.x) rcv[k] = a.rcv[k];
+    __syncthreads();
+    XEventRec e;
+    RayRec r;
+    double L = 0;
+    double E[kMaxBands];
+#pragma unroll
+    for (int b = 0; b < kMaxBands; ++b) E[b] = 0;
+    if (live) {
+        e = a.ev[i];
+        r = a.rays[i];
+        if (a.init_state) {
+#pragma unroll
+            for (int b = 0; b < kMaxBands; ++b) E[b] = 1.0;
+        } else {
+            L = a.state[i];
+#pragma unroll
+            for (int b = 0; b < kMaxBands; ++b)
+                if (b < B) E[b] = a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i];
+        }
+    }
+    // ---- receivers
+    if (__ballot(live) != 0ull) {
+        const double t_end = (live && e.hit) ? e.t : __builtin_inf();
+        const double nb = (double)a.n_bins;
+        for (int k = 0; k < a.n_rcv; ++k) {
+            const double cx = rcv[4 * k + 0], cy = rcv[4 * k + 1], cz = rcv[4 * k + 2], r2 = rcv[4 * k + 3];
+            bool det = false, binned = false;
+            int bin = 0;
+            if (live) {
+                const double wx = cx - r.x, wy = cy - r.y, wz = cz - r.z;
+                const double s = ((wx * r.dx + wy * r.dy) + wz * r.dz) / ((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
+                const double qx = (r.x + r.dx * s) - cx, qy = (r.y + r.dy * s) - cy, qz = (r.z + r.dz * s) - cz;
+                det = s >= 0 && s < t_end && ((qx * qx + qy * qy) + qz * qz) < r2;
+                if (det) {
+                    const double x = (L + s) / a.bin_len;
+                    binned = x >= 0 && x < nb;
+                    if (binned) bin = (int)floor(x);
+                }
+            }
+            const unsigned long long dm = __ballot(det);
+            if (dm == 0ull) continue;                                       // the common case: nobody passed receiver k
+            const unsigned long long bm = __ballot(binned);
+            if (lane == 0) {
+                if (bm) atomicAdd(&a.det[2 * k], (unsigned long long)__popcll(bm));
+                if (dm & ~bm) atomicAdd(&a.det[2 * k + 1], (unsigned long long)__popcll(dm & ~bm));
+            }
+            if (bm == 0ull) continue;
+            unsigned long long q[kMaxBands];
+#pragma unroll
+            for (int b = 0; b < kMaxBands; ++b) {
+                q[b] = 0;
+                if (b < B && binned) {
+                    double v = E[b] * a.scale;
+                    if (!(v > 0)) v = 0;
+                    v = v < 9223372036854775808.0 ? v : 9223372036854775808.0;     // min(q, 2^63)
+                    q[b] = (unsigned long long)rint(v);
+                }
+            }
+            unsigned long long* const row = a.hist + (size_t)k * (size_t)a.n_bins * (size_t)B;
+            if (!a.aggregate) {                                              // naive form (A/B): every detecting lane adds its own bands
+                if (binned)
+                    for (int b = 0; b < B; ++b) atomicAdd(&row[(size_t)bin * B + b], q[b]);
+                continue;
+            }
+            unsigned long long todo = bm;
+            while (todo) {                                                   // one round per distinct bin among the wave's detections
+                const int leader = __ffsll((long long)todo) - 1;
+                const int lb = __shfl(bin, leader, 64);
+                const bool mine = binned && bin == lb;
+                todo &= ~__ballot(mine);
+                unsigned long long mysum = 0;
+#pragma unroll
+                for (int b = 0; b < kMaxBands; ++b) {
+                    if (b < B) {
+                        const unsigned long long sb = wave_allsum_u64(mine ? q[b] : 0ull);
+                        if (lane == b) mysum = sb;
+                    }
+                }
+                if (lane < B) atomicAdd(&row[(size_t)lb * B + lane], mysum);     // B contiguous 8-byte adds: one instruction
+            }
+        }
+    }
+    // ---- state update, reflection (hare_reflect's arithmetic and marks)
+    bool lives_on = false;
+    if (live) {
+        if (e.hit || a.init_state) {               // a miss leaves its state as it is (init_state: as it starts)
+            const double* al = (e.hit && a.alpha) ? a.alpha + (size_t)e.poly_id * (size_t)B : nullptr;
+            a.state[i] = e.hit ? L + e.t : L;
+#pragma unroll
+            for (int b = 0; b < kMaxBands; ++b)
+                if (b < B) a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i] = al ? E[b] * (1.0 - al[b]) : E[b];      // no table: alpha = 0
+        }
+        if (e.hit) {
+            if (!a.last) {
+                a.rays[i] = reflect_hit(a.polys, r, e);         // kernels.hip: hare_reflect's arithmetic, shared
+                a.excl[i] = e.poly_id;
+                lives_on = true;
+            }
+        } else if (!a.last) {
+            a.excl[i] = -2;
+        }
+    }
+    if (a.block_live) {
+        const unsigned long long lm = __ballot(lives_on);
+        const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+        if (lane == 0 && blk * 64 < a.n) a.block_live[blk] = lm != 0ull ? 1 : 0;
+    }
+}

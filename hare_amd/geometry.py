@@ -363,6 +363,87 @@ class Spatial_Partition:
                                             ptr(ev_all), ptr(ev_last), C.addressof(ctr), None))
         return (ev_all if all_casts else ev_last), ctr.as_dict()
 
+    # ---- receivers: energy-time histograms from the bounce loop (include/hare_hip.h, "receivers")
+    def set_receivers(self, centers, radii):
+        """hare_scene_set_receivers: K spheres, centers [K, 3], radii [K] (replaces the scene's receivers)."""
+        c = np.ascontiguousarray(centers, np.float64).reshape(-1, 3)
+        r = np.ascontiguousarray(radii, np.float64).reshape(-1)
+        if r.shape[0] != c.shape[0]:
+            raise ValueError("one radius per center")
+        check(lib.hare_scene_set_receivers(self._h, c.shape[0], ptr(c), ptr(r)))
+        return self
+
+    def set_absorption(self, alpha, top_index: int = 0):
+        """hare_scene_set_absorption: alpha [P, B] in [0, 1] for Model[top_index] (B = 1 .. 8 bands)."""
+        a = np.ascontiguousarray(alpha, np.float64)
+        if a.ndim != 2:
+            raise ValueError("alpha must be [polygons, bands]")
+        check(lib.hare_scene_set_absorption(self._h, int(top_index), a.shape[1], ptr(a)))
+        return self
+
+    def _receive_shape(self, top_index: int, n_bins: int):
+        return self.get_option("receivers"), int(n_bins), self._bands(top_index)
+
+    def _bands(self, top_index: int) -> int:
+        return self.get_option("bands:%d" % int(top_index))          # the scene's own record, whoever set the table
+
+    def Receive_batch(self, rays, bounces: int, n_bins: int, bin_len: float, energy=None, frac_bits: int = 40, top_index: int = 0,
+                      poly_origin1=None, poly_origin2=None, out=None):
+        """The bounce loop with the receiver step between its casts, from host buffers (hare_receive_batch).
+        energy: None (every ray starts at L = 0, E = 1) or the state [1 + B, n] (row 0: L, rows 1..B: E).
+        Returns (hist [K, n_bins, B] uint64, hist * 2^-frac_bits as float64, detections [K, 2] uint64, final state [1 + B, n],
+        counters).  out (optional): the caller's uint64 histogram array [K, n_bins, B], as in Shoot_batch."""
+        return Spatial_Partition._receive([self], rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1,
+                                          poly_origin2, out)
+
+    @staticmethod
+    def Receive_batch_sharded(partitions, rays, bounces: int, n_bins: int, bin_len: float, energy=None, frac_bits: int = 40,
+                              top_index: int = 0, poly_origin1=None, poly_origin2=None, out=None):
+        """hare_receive_batch_sharded: Receive_batch over several partitions (contiguous ray shards, histograms summed); byte-identical."""
+        return Spatial_Partition._receive(list(partitions), rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1,
+                                          poly_origin2, out)
+
+    @staticmethod
+    def _receive(parts, rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1, poly_origin2, out):
+        if not parts or any(p._kind != parts[0]._kind for p in parts):
+            raise ValueError("need one or more partitions of the same kind")
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+        n = rays.shape[0]
+        K, nb, B = parts[0]._receive_shape(top_index, n_bins)
+        e1 = None if poly_origin1 is None else np.ascontiguousarray(poly_origin1, np.int32)
+        e2 = None if poly_origin2 is None else np.ascontiguousarray(poly_origin2, np.int32)
+        for e in (e1, e2):
+            if e is not None and e.shape != (n,):
+                raise ValueError("poly_origin arrays must have one entry per ray")
+        state_in = None
+        if energy is not None:
+            state_in = np.ascontiguousarray(energy, np.float64)
+            if state_in.shape != (1 + B, n):
+                raise ValueError("energy must be the state [1 + B, n] = [%d, %d]" % (1 + B, n))
+        hist = _result_array(out, (max(K, 0), nb, B), np.uint64)
+        det = np.zeros((max(K, 0), 2), np.uint64)
+        state_out = np.empty((1 + B, n), np.float64)
+        ctr = capi.Counters()
+        if len(parts) == 1:
+            rc = lib.hare_receive_batch(parts[0]._h, parts[0]._kind, int(top_index), n, ptr(rays), ptr(e1), ptr(e2), int(bounces), 0, nb,
+                                        float(bin_len), int(frac_bits), ptr(state_in), ptr(state_out), ptr(hist), ptr(det), C.addressof(ctr))
+        else:
+            handles = (C.c_void_p * len(parts))(*[p._h for p in parts])
+            rc = lib.hare_receive_batch_sharded(handles, len(parts), parts[0]._kind, int(top_index), n, ptr(rays), ptr(e1), ptr(e2),
+                                                int(bounces), 0, nb, float(bin_len), int(frac_bits), ptr(state_in), ptr(state_out),
+                                                ptr(hist), ptr(det), C.addressof(ctr))
+        check(rc)
+        return hist, hist.astype(np.float64) * 2.0 ** -int(frac_bits), det, state_out, ctr.as_dict()
+
+    def receive_device(self, n: int, d_rays: int, bounces: int, n_bins: int, bin_len: float, frac_bits: int, d_state: int, d_work: int,
+                       d_events_last: int, d_hist: int, d_detections: int, top_index: int = 0, d_excl1: int = 0, d_excl2: int = 0,
+                       d_counters: int = 0, stream: int = 0, flags: int = 0):
+        """hare_receive_device on raw device addresses (e.g. torch.Tensor.data_ptr()) + a hipStream_t: d_state (1 + B) x n doubles is read
+        and overwritten, d_hist (K x n_bins x B uint64) and d_detections (2 K uint64) are accumulated into.  Stream-ordered."""
+        check(lib.hare_receive_device(self._h, self._kind, int(top_index), int(n), d_rays or None, d_excl1 or None, d_excl2 or None,
+                                      int(bounces), int(flags), int(n_bins), float(bin_len), int(frac_bits), d_state or None, d_work or None,
+                                      d_events_last or None, d_hist or None, d_detections or None, d_counters or None, stream or None))
+
     def shoot_device(self, n: int, d_rays: int, d_out: int, top_index: int = 0, d_excl1: int = 0, d_excl2: int = 0,
                      d_counters: int = 0, stream: int = 0, flags: int = 0):
         """Device-resident shoot: raw device addresses (e.g. torch.Tensor.data_ptr()) + a hipStream_t."""

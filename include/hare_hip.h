@@ -218,6 +218,8 @@ HARE_API void hare_scene_destroy(hare_scene *s);
  *                     under capture, or a failed reservation runs in the caller's order (same results).  0: no ring
  *   "voxel_tight_max_mb"  budget for those boxes in MiB (0, the default: none).  Over budget -- or out of device memory -- the grid is
  *                     built and traced without them: never an error, never a different result
+ *   "receive_aggregate"  1 (default): hare_receive_reflect sums a wave's histogram adds per distinct (receiver, bin) before ONE atomic
+ *                     instruction; 0: an atomic per detecting lane and band (A/B).  Results never depend on it
  *   "dev"             1: developer flag bits of hare_shoot_* (timeline, phase profile, cull audit) pass
  * Single-caller like the build calls: not to be changed while shoots are in flight on the scene. */
 HARE_API int hare_scene_set_option(hare_scene *s, const char *name, int64_t value);
@@ -233,6 +235,8 @@ HARE_API int hare_scene_set_option(hare_scene *s, const char *name, int64_t valu
  *                           entry points to "none of these"
  *   "octree_scratch_bytes"  device bytes of the octree kernels' scratch ring (hand-over records and stack spill; 0 before the first
  *                           octree launch that needs one)
+ *   "receivers", "bands"    K of hare_scene_set_receivers (0: none set) and B of topology 0's absorption table (1: none);
+ *   "bands:<top>"           B of topology <top> (e.g. "bands:1"; HARE_E_INVALID for a topology the scene does not have)
  * No reference counterpart: Hare has no device memory to account for. */
 HARE_API int hare_scene_get_option(const hare_scene *s, const char *name, int64_t *value);
 
@@ -427,6 +431,76 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
                                        const hare_ray *rays, const int32_t *excl1, const int32_t *excl2, int32_t bounces,
                                        uint32_t flags, hare_xevent *events_all, hare_xevent *events_last, hare_counters *ctr,
                                        hare_counters *ctr_per_cast);
+
+/* ---- receivers: energy-time histograms from the bounce loop (harness-defined; the reference has no receivers -- Pachyderm, its
+ * caller, intersects every reflected segment with its receivers on the host) ----
+ * The scene holds receivers: K spheres (center c_k, radius r_k), with 1 <= K <= 256.  For each topology it may also hold an
+ * absorption table: alpha[p][b], one value in [0, 1] per polygon p and band b, with 1 <= B <= 8 bands.  A topology with no table
+ * acts as B = 1 with every alpha = 0.
+ *
+ * Every ray carries a state: a path parameter L and band energies E[0..B-1].  The loop is the bounce loop's: shoot, reflect about
+ * Normal(Poly_id), exclude the polygon just left, and retire a ray that misses.  One step is added after each cast c (the last
+ * cast included) and before that cast's reflection.  For every ray still live in cast c, it runs the ray through every receiver k
+ * in ascending order.  Here o, d are the ray as cast c received it, e is its X_Event, and t_end = e.hit ? e.t : +inf (a miss is a
+ * half-line).  All of it is FP64 with no contraction, in exactly this order:
+ *
+ *   wx = cx - ox; wy = cy - oy; wz = cz - oz
+ *   s  = ((wx*dx + wy*dy) + wz*dz) / ((dx*dx + dy*dy) + dz*dz)
+ *   qx = (ox + dx*s) - cx;  (same for y, z)
+ *   detected  iff  s >= 0  &&  s < t_end  &&  ((qx*qx + qy*qy) + qz*qz) < r*r
+ *   x   = (L + s) / bin_len            binned iff x >= 0 && x < n_bins (compared as doubles); bin = (int)floor(x)
+ *   q_b = E[b] * 2^frac_bits; 0 unless q_b > 0; min(q_b, 2^63); rint -> uint64
+ *   hist[(k*n_bins + bin)*B + b] += q_b            (uint64, wraps mod 2^64: the caller sizes frac_bits)
+ *   detections[2k] += 1 if binned, detections[2k+1] += 1 otherwise
+ *
+ * After the receiver step, a ray that hit updates its state: E[b] = E[b] * (1.0 - alpha[Poly_id][b]) and L = L + e.t (in the last
+ * cast too).  Then it is reflected as in the bounce loop (not behind the last cast).  A ray that missed is retired and its state is
+ * left as it is.
+ *
+ * The histogram is fixed point in uint64: integer sums do not depend on the order of the adds, so the result is bit-identical from
+ * run to run, between the one-device and the sharded call, and against a restatement on the host.  (r*r is formed once, when the
+ * receivers are set: the same FP64 product.)
+ *
+ * Setters: single-caller, like the build calls.  They validate, keep a host copy, and upload it when a device is present (as a build
+ * pushes its partition; on a GPU-less host the copy goes up with the first receive call).  No receive call allocates for them.
+ *   hare_scene_set_receivers    replaces the receivers: centers K x 3, radii K.  HARE_E_INVALID for K outside 1..256, a non-finite
+ *                               center, or a radius that is not finite and > 0
+ *   hare_scene_set_absorption   alpha: P x B of Model[top_index] (row per polygon).  HARE_E_INVALID for a bad top_index, B outside 1..8,
+ *                               or any alpha outside [0, 1] or NaN
+ * hare_scene_get_option reads back "receivers" (K; 0 before the first set), "bands" (B of topology 0) and "bands:<top>" (B of topology
+ * <top>): the sizes of a receive call's histogram (K x n_bins x B) and state ((1 + B) x n) for that topology.  The library cannot check the
+ * size of a caller's host buffer: the bindings size theirs from these. */
+HARE_API int hare_scene_set_receivers(hare_scene *s, int32_t K, const double *centers, const double *radii);
+HARE_API int hare_scene_set_absorption(hare_scene *s, int32_t top_index, int32_t B, const double *alpha);
+
+/* The receive loop on DEVICE buffers: stream-ordered like hare_shoot_device -- no allocation, no free, no wait ("hip_malloc_calls" ...).
+ * Always a launch per cast (the scene option "bounce_fused" does not apply; results are the same either way).
+ *   d_rays, d_excl1, d_excl2, d_work (2 n int32), d_events_last   as in hare_bounce_device
+ *   d_state        (1 + B) planes of n doubles: plane 0 is L, planes 1..B are E.  Read and overwritten
+ *   d_hist         K x n_bins x B uint64, ACCUMULATED;  d_detections: 2 K uint64, ACCUMULATED
+ *   d_counters     nullable: totals, ACCUMULATED (as hare_bounce_device's)
+ *   flags          HARE_SHOOT_COUNT_WORK / HARE_SHOOT_SIMPLE_KERNEL only
+ * Arguments are checked before anything runs (HARE_E_INVALID): kind, top_index, 0 <= n <= 2^31 - 256, 1 <= bounces <= 4096,
+ * n_bins >= 1, bin_len finite and > 0, 0 <= frac_bits <= 62, K x n_bins x B <= 2^27, null or overlapping buffers.  Then
+ * HARE_E_NODEVICE, then HARE_E_STATE (no receivers set; partition not built). */
+HARE_API int hare_receive_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, void *d_rays, const void *d_excl1,
+                                 const void *d_excl2, int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len,
+                                 int32_t frac_bits, void *d_state, void *d_work, void *d_events_last, void *d_hist,
+                                 void *d_detections, void *d_counters, void *stream);
+/* The same from host buffers (threading and staging as hare_bounce_batch's last-cast-only path: one enqueue, one synchronisation; no
+ * events are downloaded).  state_in nullable (every ray starts at L = 0, E = 1); state_out nullable ((1 + B) x n, as d_state).
+ * hist (K x n_bins x B) and detections (2 K) are WRITTEN, not accumulated; ctr nullable: counters summed over the casts. */
+HARE_API int hare_receive_batch(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, const hare_ray *rays,
+                                const int32_t *excl1, const int32_t *excl2, int32_t bounces, uint32_t flags, int32_t n_bins,
+                                double bin_len, int32_t frac_bits, const double *state_in, double *state_out, uint64_t *hist,
+                                uint64_t *detections, hare_counters *ctr);
+/* Over several devices: rays [n*k/G, n*(k+1)/G) go to scenes[k] (as hare_bounce_batch_sharded), the histograms and detections are
+ * summed.  Byte-identical to the one-device call.  The scenes must hold the same receivers and bands (HARE_E_INVALID otherwise). */
+HARE_API int hare_receive_batch_sharded(hare_scene *const *scenes, int32_t n_scenes, int32_t kind, int32_t top_index, int64_t n,
+                                        const hare_ray *rays, const int32_t *excl1, const int32_t *excl2, int32_t bounces,
+                                        uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits,
+                                        const double *state_in, double *state_out, uint64_t *hist, uint64_t *detections,
+                                        hare_counters *ctr);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,117 @@
+"""Cost of the receiver step (include/hare_hip.h, "receivers"; kernel hare_receive_reflect, receive.hip): hare_receive_device against
+hare_bounce_device (last cast only) on the same burst, device-resident, HIP events on the launch stream; K = 1 / 8 / 64 receivers,
+B = 1 / 8 bands, 4 000 bins; receiver 0 is the direct-sound case (a 1 m sphere 2 m from the source: ~7 % of the rays cross it in cast 0,
+into one or two bins), timed with the wave-aggregated atomics and with the naive ones.  With --host, also the host alternative a caller
+has without the feature: Bounce_batch(all_casts=True) and the numpy restatement of the step (tests/receiver_ref.py) on every cast.
+Prints ONE JSON line.  usage: python tools/receiver_rate.py [hall|cathedral] [--rays N] [--bounces B] [--reps R] [--host] [--quick]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+import hare_amd as H
+
+ap = argparse.ArgumentParser()
+ap.add_argument("scene", nargs="?", default="hall", choices=["hall", "cathedral"])
+ap.add_argument("--rays", type=int, default=1 << 20)
+ap.add_argument("--bounces", type=int, default=8)
+ap.add_argument("--reps", type=int, default=10)
+ap.add_argument("--host", action="store_true", help="also time Bounce_batch(all_casts=True) + the numpy step (K = 8, B = 8)")
+ap.add_argument("--quick", action="store_true", help="K = 8, B = 8 only (a profiling run)")
+a = ap.parse_args()
+if not torch.cuda.is_available():
+    sys.exit("receiver_rate: no GPU -- nothing to measure")
+
+D = 64 if a.scene == "hall" else 128
+mesh = H.scenes.SCENES[a.scene]()
+T = H.Topology(mesh.verts, mesh.nverts)
+g = H.Voxel_Grid([T], D)
+n, nb, N_BINS, BIN_LEN, FRAC = a.rays, a.bounces, 4000, 0.05, 32
+rays = H.scenes.burst_rays(n, mesh.size)
+st = torch.cuda.current_stream().cuda_stream
+d_src = torch.from_numpy(rays).cuda()
+d_rays = torch.empty_like(d_src)
+d_work = torch.zeros(2 * n, dtype=torch.int32, device="cuda")
+d_last = torch.zeros(n * 56, dtype=torch.uint8, device="cuda")
+S = np.array([0.31, 0.42, 0.37]) * np.asarray(mesh.size)
+
+
+def receivers(K):
+    rng = np.random.default_rng(K)
+    c = [S + np.array([2.0, 0.0, 0.0])]                                 # the direct sound: r = 1 m at 2 m
+    c += list(rng.uniform(0.1, 0.9, (K - 1, 3)) * np.asarray(mesh.size))
+    return np.array(c), np.concatenate([[1.0], rng.uniform(0.3, 1.0, K - 1)])
+
+
+def timed(fn, reps):
+    fn(); torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+        d_rays.copy_(d_src)                                              # both loops overwrite their rays: the copy is outside the window
+        e0.record()
+        fn()
+        e1.record(); torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return float(np.median(ms))
+
+
+def bounce():
+    g.bounce_device(n, d_rays.data_ptr(), nb, d_work.data_ptr(), d_events_last=d_last.data_ptr(), stream=st)
+
+
+ms_bounce = timed(bounce, a.reps)
+out = {"scene": a.scene, "domain": D, "rays": n, "bounces": nb, "n_bins": N_BINS, "bounce_ms": round(ms_bounce, 3),
+       "bounce_Mcasts_s": round(n * nb / ms_bounce / 1e3, 1), "receive": []}
+cases = [(8, 8)] if a.quick else [(K, B) for K in (1, 8, 64) for B in (1, 8)]
+for K, B in cases:
+    c, r = receivers(K)
+    g.set_receivers(c, r)
+    g.set_absorption(np.random.default_rng(B).uniform(0.02, 0.3, (T.Polygon_Count, B)))
+    d_state = torch.empty((1 + B, n), dtype=torch.float64, device="cuda")
+    init = torch.cat([torch.zeros((1, n), dtype=torch.float64, device="cuda"), torch.ones((B, n), dtype=torch.float64, device="cuda")])
+    d_hist = torch.zeros(K * N_BINS * B, dtype=torch.int64, device="cuda")
+    d_det = torch.zeros(2 * K, dtype=torch.int64, device="cuda")
+
+    def receive():
+        g.receive_device(n, d_rays.data_ptr(), nb, N_BINS, BIN_LEN, FRAC, d_state.data_ptr(), d_work.data_ptr(), d_last.data_ptr(),
+                         d_hist.data_ptr(), d_det.data_ptr(), stream=st)
+    row = {"K": K, "B": B}
+    for agg in ((1, 0) if K == 8 and B == 8 else (1,)):
+        g.set_option("receive_aggregate", agg)
+        d_hist.zero_(); d_det.zero_()
+        d_state.copy_(init)
+        ms = timed(lambda: (d_state.copy_(init), receive()), a.reps)
+        ms_copy = timed(lambda: d_state.copy_(init), a.reps)          # the state reset inside the window, timed alone
+        key = "ms" if agg else "ms_naive"
+        row[key] = round(ms - ms_copy, 3)
+        row[key.replace("ms", "over_bounce_pct")] = round(100.0 * (ms - ms_copy - ms_bounce) / ms_bounce, 1)
+    g.set_option("receive_aggregate", 1)
+    d_hist.zero_(); d_det.zero_(); d_rays.copy_(d_src); d_state.copy_(init)
+    receive(); torch.cuda.synchronize()
+    det = d_det.cpu().numpy().reshape(K, 2)
+    row["direct_frac_cast_sum"] = round(float(det[0].sum()) / n, 4)     # detections of receiver 0 (all casts) per ray
+    row["detections"] = int(det.sum())
+    out["receive"].append(row)
+    print(json.dumps(row), file=sys.stderr, flush=True)
+
+if a.host:
+    from tests.receiver_ref import receive_loop
+    from oracle import pyoracle as po
+    K, B = 8, 8
+    c, r = receivers(K)
+    alpha = np.random.default_rng(B).uniform(0.02, 0.3, (T.Polygon_Count, B))
+    t0 = time.perf_counter()
+    ev, _ = g.Bounce_batch(rays, nb, all_casts=True)
+    t1 = time.perf_counter()
+    To = po.Topology(mesh.verts, mesh.nverts)
+    receive_loop(po, To, rays, ev, c, r, N_BINS, BIN_LEN, FRAC, alpha=alpha)
+    t2 = time.perf_counter()
+    out["host_alternative"] = {"K": K, "B": B, "bounce_all_casts_ms": round((t1 - t0) * 1e3, 1), "numpy_step_ms": round((t2 - t1) * 1e3, 1),
+                               "events_bytes": int(ev.nbytes)}
+print(json.dumps(out))
