@@ -167,6 +167,16 @@ public:
             throw std::invalid_argument("SetAbsorption: alpha must hold Polygon_Count x bands values");
         check(hare_scene_set_absorption(scene_, top_index, bands, alpha.data()));
     }
+    // scattering table of Model[top_index] (hare_scene_set_scattering): Polygon_Count x bands values in [0, 1], the same bands as its absorption
+    // table if it has one; the receive loop then scatters diffusely (seed: SetOption("scatter_seed", ...)).  ClearScattering removes it.
+    void SetScattering(int top_index, int bands, const std::vector<double>& sigma)
+    {
+        if (top_index < 0 || (size_t)top_index >= Model.size()) throw std::invalid_argument("SetScattering: bad top_index");
+        if (bands < 1 || sigma.size() != (size_t)Model[(size_t)top_index]->Polygon_Count() * (size_t)bands)
+            throw std::invalid_argument("SetScattering: sigma must hold Polygon_Count x bands values");
+        check(hare_scene_set_scattering(scene_, top_index, bands, sigma.data()));
+    }
+    void ClearScattering(int top_index) { check(hare_scene_set_scattering(scene_, top_index, 0, nullptr)); }
     int64_t Bands(int top_index) const { return GetOption(("bands:" + std::to_string(top_index)).c_str()); }
     uint64_t Receive(const std::vector<hare_ray>& rays, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
                      std::vector<uint64_t>& hist, std::vector<uint64_t>& detections, const std::vector<double>* state_in = nullptr,

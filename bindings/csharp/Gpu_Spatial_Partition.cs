@@ -250,6 +250,22 @@ namespace Hare
                 foreach (IntPtr s in scenes) HareHip.Check(HareHip.hare_scene_set_absorption(s, top_index, bands, alpha));
             }
 
+            /// <summary>Scattering table of Model[top_index] (hare_scene_set_scattering): sigma[p * bands + b] in [0, 1], the same bands as
+            /// its absorption table if it has one.  Receive then scatters diffusely, seeded by the option "scatter_seed" (the same on every
+            /// scene of the partition: set it with SetOption).  sigma null removes the table.</summary>
+            public void SetScattering(int top_index, int bands, double[] sigma)
+            {
+                if (top_index < 0 || top_index >= Model.Length) throw new ArgumentException("bad top_index");
+                if (sigma == null)
+                {
+                    foreach (IntPtr s in scenes) HareHip.Check(HareHip.hare_scene_set_scattering(s, top_index, 0, null));
+                    return;
+                }
+                if (bands < 1 || sigma.LongLength != (long)Model[top_index].Polygon_Count * bands)
+                    throw new ArgumentException("sigma must hold Polygon_Count x bands values");
+                foreach (IntPtr s in scenes) HareHip.Check(HareHip.hare_scene_set_scattering(s, top_index, bands, sigma));
+            }
+
             /// <summary>B of Model[top_index]'s absorption table (1 without one): hist holds K x n_bins x B values, state (1 + B) x n.</summary>
             public int Bands(int top_index)
             {

@@ -215,6 +215,9 @@ namespace Hare
             public static extern int hare_scene_set_receivers(IntPtr scene, int K, [In] double[] centers, [In] double[] radii);
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_scene_set_absorption(IntPtr scene, int top_index, int B, [In] double[] alpha);
+            /// <summary>Scattering table of a topology (sigma P x B in [0, 1], the absorption table's B); B = 0 with sigma null removes it.</summary>
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_scene_set_scattering(IntPtr scene, int top_index, int B, [In] double[] sigma);
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_receive_batch(IntPtr scene, int kind, int top_index, long n, [In] hare_ray[] rays, int[] excl1, int[] excl2,
                                                         int bounces, uint flags, int n_bins, double bin_len, int frac_bits, [In] double[] state_in,

@@ -926,7 +926,7 @@ int hare_scene_get_option(const hare_scene* s, const char* name, int64_t* value)
         *value = (int64_t)(s->rcv.size() / 4);
         return HARE_OK;
     }
-    if (strcmp(name, "bands") == 0) {                 // hare_scene_set_absorption: B of topology 0 (1: no table)
+    if (strcmp(name, "bands") == 0) {                 // hare_scene_set_absorption / _scattering: B of topology 0 (1: no table)
         *value = scene_bands(*s, 0);
         return HARE_OK;
     }
@@ -938,6 +938,10 @@ int hare_scene_get_option(const hare_scene* s, const char* name, int64_t* value)
             return HARE_E_INVALID;
         }
         *value = scene_bands(*s, (int32_t)top);
+        return HARE_OK;
+    }
+    if (strcmp(name, "scatter_seed") == 0) {
+        *value = (int64_t)s->opt.scatter_seed;
         return HARE_OK;
     }
     if (strcmp(name, "octree_scratch_bytes") == 0) {
@@ -961,6 +965,10 @@ int hare_scene_set_option(hare_scene* s, const char* name, int64_t value)
     }
     if (strcmp(name, "dev_order_ptr") == 0) {       // developer experiments: see SceneOptions::dev_order_ptr
         s->opt.dev_order_ptr = (long long)value;
+        return HARE_OK;
+    }
+    if (strcmp(name, "scatter_seed") == 0) {        // any int64: the scattering RNG reads its bits as uint64
+        s->opt.scatter_seed = (long long)value;
         return HARE_OK;
     }
     for (const OptionEntry& t : kOptionTable)

@@ -226,6 +226,7 @@ struct ReceiveJob {
     int64_t stride = 0;
     uint64_t* hist = nullptr;
     uint64_t* det = nullptr;
+    int64_t ray_base = 0;      // this shard's first ray in the whole batch (the scattering RNG's global ray index)
 };
 
 // The receive loop for one scene: rays, exclusions and state go up, the loop is enqueued ONCE (a launch per cast, hare_receive_reflect
@@ -267,7 +268,8 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
     HIP_TRY(H->MemsetAsync(b.hist, 0, hist_bytes, st));
     HIP_TRY(H->MemsetAsync(b.ctr, 0, (size_t)bounces * sizeof(hare_counters), st));
     ReceiveArgs ra;
-    if (int rc = receive_args(s, top, job.n_bins, job.bin_len, job.frac_bits, d_state, d_hist, d_det, job.state_in == nullptr, ra)) return rc;
+    if (int rc = receive_args(s, top, job.n_bins, job.bin_len, job.frac_bits, d_state, d_hist, d_det, job.state_in == nullptr, job.ray_base, ra))
+        return rc;
     if (int rc = bounce_device_impl(s, H, kind, top, n, b.rays[0], excl1 ? b.excl[0] : nullptr, excl2 ? b.excl2 : nullptr, bounces, flags, b.ev[1],
                                     nullptr, b.ev[0], nullptr, b.ctr, st, &ra))
         return rc;
@@ -479,12 +481,22 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
         set_error(std::string(who) + ": null rays, histogram or detections");
         return HARE_E_INVALID;
     }
-    for (int32_t k = 1; k < n_scenes; ++k)       // the shards must compute the same thing
+    auto sigma_of = [&](const Scene& s) -> const std::vector<double>* {
+        return scene_has_scattering(s, top_index) ? &s.sigma[(size_t)top_index] : nullptr;
+    };
+    for (int32_t k = 1; k < n_scenes; ++k) {     // the shards must compute the same thing
+        const std::vector<double>* sk = sigma_of(*scenes[k]);
+        const std::vector<double>* s0s = sigma_of(*s0);
         if (scenes[k]->rcv != s0->rcv || scene_bands(*scenes[k], top_index) != scene_bands(*s0, top_index) ||
             (top_index < (int32_t)scenes[k]->topos.size() ? scenes[k]->topos[(size_t)top_index].P : -1) != s0->topos[(size_t)top_index].P) {
             set_error(std::string(who) + ": the scenes differ in receivers, bands or polygons");
             return HARE_E_INVALID;
         }
+        if ((sk == nullptr) != (s0s == nullptr) || (sk && *sk != *s0s) || (s0s && scenes[k]->opt.scatter_seed != s0->opt.scatter_seed)) {
+            set_error(std::string(who) + ": the scenes differ in scattering tables or scatter_seed");
+            return HARE_E_INVALID;
+        }
+    }
     GUARD_BEGIN
     const int G = n_scenes;
     const size_t K = s0->rcv.size() / 4, hist_words = K * (size_t)n_bins * (size_t)scene_bands(*s0, top_index);
@@ -511,6 +523,7 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
         job.stride = n;
         job.hist = k == 0 ? hist : hists[(size_t)k].data();
         job.det = k == 0 ? detections : dets[(size_t)k].data();
+        job.ray_base = lo;
         try {
             rcs[(size_t)k] = bounce_one(scenes[k], kind, top_index, hi - lo, rays ? rays + lo : nullptr, excl1 ? excl1 + lo : nullptr,
                                         excl2 ? excl2 + lo : nullptr, bounces, flags, nullptr, n, nullptr, pcs[(size_t)k].data(), &job);

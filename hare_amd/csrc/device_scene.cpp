@@ -95,6 +95,7 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_kdtree_shoot_count", &m->kdtree_count},
         {"hare_reflect", &m->reflect},
         {"hare_receive_reflect", &m->receive_reflect},
+        {"hare_receive_scatter", &m->receive_scatter},
         {"hare_occlusion", &m->occlusion},
         {"hare_voxel_occl_tri", &m->voxel_occl_tri},
         {"hare_voxel_occl_quad", &m->voxel_occl_quad},

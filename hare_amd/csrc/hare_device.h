@@ -473,7 +473,7 @@ struct ShootIO {
     int32_t oct_spill_cap;
 };
 
-// hare_receive_reflect (receive.hip): the receiver step + state update + reflection of one cast of the receive loop (launch.cpp)
+// hare_receive_reflect / hare_receive_scatter (receive.hip): the receiver step + state update + reflection of one cast of the receive loop (launch.cpp)
 constexpr int kMaxBands = 8;
 constexpr int kMaxReceivers = 256;
 struct ReceiveArgs {
@@ -497,6 +497,11 @@ struct ReceiveArgs {
     int32_t last;              // 1: the loop's last cast -- no reflection
     int32_t aggregate;         // 1: one atomic per distinct (receiver, bin) per wave; 0: one per detecting lane (scene option "receive_aggregate")
     int32_t init_state;        // first cast only: every ray starts at L = 0, E = 1 (state is written, not read: hare_receive_batch without state_in)
+    int32_t cast;              // c, this cast's number in the call (0 .. bounces - 1): the scattering RNG's counter
+    // hare_receive_scatter only (the topology has a scattering table, launch.cpp chooses that kernel):
+    const double* sigma;       // P x bands scattering coefficients of Model[top] (null: hare_receive_reflect)
+    unsigned long long seed;   // scene option "scatter_seed"
+    long long ray_base;        // global index of ray 0 of this call (the shard's offset in hare_receive_batch_sharded): g = ray_base + i
 };
 
 #if defined(__HIPCC__)

@@ -14,6 +14,7 @@
 //   hare_reflect           K3   specular bounce between casts (harness-defined); hare_live_count / hare_scan_tiles /
 //                               hare_reflect_compact / hare_events_*: the same with the survivors packed (hare_bounce_batch)
 //   hare_receive_reflect        hare_reflect plus the receiver step of the receive loop (receive.hip: energy-time histograms)
+//   hare_receive_scatter        the same with diffuse (Lambertian) scattering where the topology has a scattering table (receive.hip)
 //   hare_cull_audit             tests only: FP32 cull vs exact test on every ray x polygon pair
 //   hare_vb_*, hare_scan_*, hare_ob_*  Voxel_Grid / Octree construction (build_kernels.hip, included at the end)
 //
@@ -1746,17 +1747,21 @@ __global__ __launch_bounds__(256) void hare_kdtree_shoot_count(KdArgs g, ShootIO
 // retired -- its event is a miss record whatever it says, so neither the event (56 B) nor anything else of it is read.
 // The reflection of a ray that hit, in ONE place: hare_reflect, hare_reflect_compact and hare_receive_reflect (receive.hip) must all give
 // the oracle's bits, so none of them spells the arithmetic out on its own.
-__device__ __forceinline__ RayRec reflect_hit(const PolyRec* polys, const RayRec& r, const XEventRec& e)
+__device__ __forceinline__ RayRec reflect_about(double nx, double ny, double nz, const RayRec& r, const XEventRec& e)     // n = Normal(Poly_id)
 {
-    const PolyRec& p = polys[e.poly_id];
-    const double dn = dot3(r.dx, r.dy, r.dz, p.n[0], p.n[1], p.n[2]);
+    const double dn = dot3(r.dx, r.dy, r.dz, nx, ny, nz);
     const double k = 2.0 * dn;
     RayRec o;
     o.x = e.x; o.y = e.y; o.z = e.z;
-    o.dx = r.dx - k * p.n[0];
-    o.dy = r.dy - k * p.n[1];
-    o.dz = r.dz - k * p.n[2];
+    o.dx = r.dx - k * nx;
+    o.dy = r.dy - k * ny;
+    o.dz = r.dz - k * nz;
     return o;
+}
+__device__ __forceinline__ RayRec reflect_hit(const PolyRec* polys, const RayRec& r, const XEventRec& e)
+{
+    const PolyRec& p = polys[e.poly_id];
+    return reflect_about(p.n[0], p.n[1], p.n[2], r, e);
 }
 __device__ __forceinline__ bool reflect_one(const PolyRec* polys, RayRec* rays, const XEventRec* ev, int32_t* excl_out, int64_t i, bool marks_valid)
 {
@@ -1945,7 +1950,7 @@ __global__ __launch_bounds__(256) void hare_occlusion(const XEventRec* ev, const
 
 }  // extern "C"
 
-#include "receive.hip"         // hare_receive_reflect: the receiver step of hare_receive_device's loop
+#include "receive.hip"         // hare_receive_reflect / _scatter: the receiver step of hare_receive_device's loop
 #include "voxel_pool.hip"
 #include "octree_pool.hip"
 #include "octree_group.hip"

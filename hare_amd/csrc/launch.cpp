@@ -475,7 +475,7 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
     hare_xevent* const all = (hare_xevent*)d_all;
     hare_xevent* const last = d_last ? (hare_xevent*)d_last : all + (size_t)(casts - 1) * (size_t)n;
     int32_t* const work = (int32_t*)d_work;
-    if (!M.reflect || !M.events_fill_miss || (rcv && !M.receive_reflect)) {
+    if (!M.reflect || !M.events_fill_miss || (rcv && !(rcv->sigma ? M.receive_scatter : M.receive_reflect))) {
         set_error("hare_bounce: bounce kernels missing from code object");
         return HARE_E_STATE;
     }
@@ -571,7 +571,8 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
         if (c > 0 && use_blocks) { extra.blocks = blk_list; extra.blk_words = blk_words; }
         if (int rc = shoot_device_impl(s, H, kind, top, n, d_rays, c == 0 ? d_e1 : work, c == 0 ? d_e2 : nullptr, f, out_c, ctr_c, st, nullptr, nullptr, &extra)) return fail(rc);
         if (rcv) {
-            // the receiver step, the state update and (but behind the last cast) the reflection: hare_receive_reflect in hare_reflect's place
+            // the receiver step, the state update and (but behind the last cast) the reflection: hare_receive_reflect in hare_reflect's place,
+            // hare_receive_scatter where Model[top] has a scattering table
             const bool last_cast = c + 1 == casts;
             ReceiveArgs ra = *rcv;
             ra.polys = (const PolyRec*)s.d_polys[(size_t)top];
@@ -583,8 +584,9 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
             ra.marks_valid = c > 0 ? 1 : 0;
             ra.last = last_cast ? 1 : 0;
             ra.init_state = c == 0 ? rcv->init_state : 0;      // the starting state is the first cast's business only
+            ra.cast = c;
             void* a[] = {&ra};
-            if (int rc = launch(H, M.receive_reflect, (unsigned)((n + 255) / 256), 256, 0, st, a)) return fail(rc);
+            if (int rc = launch(H, rcv->sigma ? M.receive_scatter : M.receive_reflect, (unsigned)((n + 255) / 256), 256, 0, st, a)) return fail(rc);
             if (use_blocks && !last_cast) {
                 uint32_t nb = (uint32_t)nblk;
                 const unsigned char* blc = blk_live;

@@ -1,4 +1,4 @@
-// receive.cpp -- receivers and absorption of a scene (hare_scene_set_receivers / hare_scene_set_absorption) and hare_receive_device,
+// receive.cpp -- receivers, absorption and scattering of a scene (hare_scene_set_receivers / _absorption / _scattering) and hare_receive_device,
 // the bounce loop with the receiver step between its casts (include/hare_hip.h, "receivers"; the kernel: receive.hip).  The host-buffer
 // calls hare_receive_batch / _sharded are in bounce.cpp, beside the loop they share with hare_bounce_batch.
 //
@@ -28,7 +28,7 @@ bool device_present(const HipApi*& H)
 
 }  // namespace
 
-// The host copies to the device: fixed-size receiver block (never reallocated), an absorption table per topology.  Called by the setters
+// The host copies to the device: fixed-size receiver block (never reallocated), an absorption and a scattering table per topology.  Called by the setters
 // when a device is present -- as a build pushes its partition -- and by a receive call only for what a setter could not upload.
 int upload_receivers(Scene& s, const HipApi* H)
 {
@@ -44,6 +44,13 @@ int upload_receivers(Scene& s, const HipApi* H)
         if (int rc = upload(H, &s.d_alpha[m], s.alpha[m].data(), s.alpha[m].size() * sizeof(double))) return rc;
         s.alpha_on_device[m] = 1;
     }
+    s.d_sigma.resize(s.topos.size(), nullptr);
+    s.sigma_on_device.resize(s.topos.size(), 0);
+    for (size_t m = 0; m < s.sigma.size(); ++m) {
+        if (s.sigma[m].empty() || s.sigma_on_device[m]) continue;
+        if (int rc = upload(H, &s.d_sigma[m], s.sigma[m].data(), s.sigma[m].size() * sizeof(double))) return rc;
+        s.sigma_on_device[m] = 1;
+    }
     return HARE_OK;
 }
 
@@ -51,6 +58,12 @@ void free_receivers(const HipApi* H, Scene& s)
 {
     dev_free(H, s.d_rcv);
     for (void*& p : s.d_alpha) dev_free(H, p);
+    for (void*& p : s.d_sigma) dev_free(H, p);
+}
+
+bool scene_has_scattering(const Scene& s, int32_t top)
+{
+    return top >= 0 && (size_t)top < s.sigma.size() && !s.sigma[(size_t)top].empty();
 }
 
 int32_t scene_bands(const Scene& s, int32_t top)
@@ -81,7 +94,7 @@ int receive_check_args(const char* who, const Scene& s, int32_t kind, int32_t to
 
 // The ReceiveArgs of one call (the loop fills in rays, events, marks per cast); receivers and tables must be on the device
 int receive_args(const Scene& s, int32_t top, int32_t n_bins, double bin_len, int32_t frac_bits, void* d_state, void* d_hist, void* d_det,
-                 bool init_state, ReceiveArgs& ra)
+                 bool init_state, int64_t ray_base, ReceiveArgs& ra)
 {
     memset(&ra, 0, sizeof ra);
     const int32_t B = scene_bands(s, top);
@@ -97,6 +110,13 @@ int receive_args(const Scene& s, int32_t top, int32_t n_bins, double bin_len, in
     ra.n_bins = n_bins;
     ra.aggregate = s.opt.receive_aggregate;
     ra.init_state = init_state ? 1 : 0;
+    ra.sigma = ((size_t)top < s.d_sigma.size() && scene_has_scattering(s, top)) ? (const double*)s.d_sigma[(size_t)top] : nullptr;
+    ra.seed = (unsigned long long)s.opt.scatter_seed;
+    ra.ray_base = (long long)ray_base;
+    if (ra.sigma == nullptr && scene_has_scattering(s, top)) {
+        set_error("receive: scattering table not on the device");
+        return HARE_E_STATE;
+    }
     if (ra.alpha == nullptr && !s.alpha.empty() && (size_t)top < s.alpha.size() && !s.alpha[(size_t)top].empty()) {
         set_error("receive: absorption table not on the device");
         return HARE_E_STATE;
@@ -192,6 +212,10 @@ int hare_scene_set_absorption(hare_scene* s, int32_t top_index, int32_t B, const
             set_error("hare_scene_set_absorption: alpha[" + std::to_string(k) + "] outside [0, 1]");
             return HARE_E_INVALID;
         }
+    if (scene_has_scattering(*s, top_index) && B != scene_bands(*s, top_index)) {
+        set_error("hare_scene_set_absorption: B differs from the topology's scattering table (" + std::to_string(scene_bands(*s, top_index)) + " bands)");
+        return HARE_E_INVALID;
+    }
     GUARD_BEGIN
     s->alpha.resize(s->topos.size());
     s->bands.resize(s->topos.size(), 1);
@@ -201,6 +225,67 @@ int hare_scene_set_absorption(hare_scene* s, int32_t top_index, int32_t B, const
     s->alpha[(size_t)top_index].swap(a);
     s->bands[(size_t)top_index] = B;
     s->alpha_on_device[(size_t)top_index] = 0;
+    const HipApi* H = nullptr;
+    if (!device_present(H)) return HARE_OK;
+    DeviceGuard dev_guard(H, s->device);
+    if (int rc = ensure_device(*s, H)) return rc;
+    return upload_receivers(*s, H);
+    GUARD_END
+}
+
+int hare_scene_set_scattering(hare_scene* s, int32_t top_index, int32_t B, const double* sigma)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    if (top_index < 0 || top_index >= (int32_t)s->topos.size()) {
+        set_error("hare_scene_set_scattering: bad top_index");
+        return HARE_E_INVALID;
+    }
+    const bool remove = B == 0 && !sigma;
+    if (!remove && (B < 1 || B > kMaxBands)) {
+        set_error("hare_scene_set_scattering: bands out of range (1 .. 8; 0 with a null table removes it)");
+        return HARE_E_INVALID;
+    }
+    const size_t cnt = remove ? 0 : (size_t)s->topos[(size_t)top_index].P * (size_t)B;
+    if (!remove && cnt > 0 && !sigma) {
+        set_error("hare_scene_set_scattering: null sigma");
+        return HARE_E_INVALID;
+    }
+    for (size_t k = 0; k < cnt; ++k)
+        if (!(sigma[k] >= 0.0 && sigma[k] <= 1.0)) {
+            set_error("hare_scene_set_scattering: sigma[" + std::to_string(k) + "] outside [0, 1]");
+            return HARE_E_INVALID;
+        }
+    const bool has_alpha = (size_t)top_index < s->alpha.size() && !s->alpha[(size_t)top_index].empty();
+    if (!remove && has_alpha && B != scene_bands(*s, top_index)) {
+        set_error("hare_scene_set_scattering: B differs from the topology's absorption table (" + std::to_string(scene_bands(*s, top_index)) + " bands)");
+        return HARE_E_INVALID;
+    }
+    GUARD_BEGIN
+    s->sigma.resize(s->topos.size());
+    s->bands.resize(s->topos.size(), 1);
+    s->sigma_on_device.resize(s->topos.size(), 0);
+    s->d_sigma.resize(s->topos.size(), nullptr);
+    if (remove) {
+        s->sigma[(size_t)top_index].clear();
+        if (!has_alpha) s->bands[(size_t)top_index] = 1;
+        s->sigma_on_device[(size_t)top_index] = 0;
+        if (s->d_sigma[(size_t)top_index]) {
+            const HipApi* H = hip_api(nullptr);
+            if (H) {
+                DeviceGuard dev_guard(H, s->device);
+                dev_free(H, s->d_sigma[(size_t)top_index]);
+            }
+        }
+        return HARE_OK;
+    }
+    std::vector<double> t(sigma, sigma + cnt);
+    if (t.empty()) t.assign((size_t)B, 0.0);       // a topology without polygons: a table of one row no ray reads
+    s->sigma[(size_t)top_index].swap(t);
+    s->bands[(size_t)top_index] = B;
+    s->sigma_on_device[(size_t)top_index] = 0;
     const HipApi* H = nullptr;
     if (!device_present(H)) return HARE_OK;
     DeviceGuard dev_guard(H, s->device);
@@ -255,7 +340,7 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
     if (int rc = receive_ready(*s, H, "hare_receive_device")) return rc;
     if (n == 0) return HARE_OK;
     ReceiveArgs ra;
-    if (int rc = receive_args(*s, top_index, n_bins, bin_len, frac_bits, d_state, d_hist, d_detections, false, ra)) return rc;
+    if (int rc = receive_args(*s, top_index, n_bins, bin_len, frac_bits, d_state, d_hist, d_detections, false, 0, ra)) return rc;
     flags &= HARE_SHOOT_COUNT_WORK | HARE_SHOOT_SIMPLE_KERNEL;
     return bounce_device_impl(*s, H, kind, top_index, n, d_rays, d_excl1, d_excl2, bounces, flags, d_work, nullptr, d_events_last, d_counters,
                               nullptr, (hipStream_t)stream, &ra);

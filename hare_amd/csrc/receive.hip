@@ -1,4 +1,5 @@
-// receive.hip -- hare_receive_reflect: the receiver step of the receive loop (include/hare_hip.h, "receivers"), #included from kernels.hip.
+// receive.hip -- hare_receive_reflect / hare_receive_scatter: the receiver step of the receive loop (include/hare_hip.h, "receivers"),
+// #included from kernels.hip.  One body (receive_body), two kernels: the scattering variant is a compile-time switch.
 //
 // One lane per ray, in place of hare_reflect behind every cast of hare_receive_device's loop (launch.cpp: bounce_device_impl with a
 // ReceiveArgs).  A live ray reads its ray, its event and its state once; runs through every receiver sphere in ascending order with the
@@ -21,7 +22,64 @@ static __device__ __forceinline__ unsigned long long wave_allsum_u64(unsigned lo
     return v;  // every lane
 }
 
-extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect(ReceiveArgs a)
+// hare_receive_scatter (SCATTER): the same, and a ray that hit in a cast that is not the last chooses diffuse or specular (the counter-based
+// RNG of the header, "receivers": SplitMix64's finaliser on (seed, global ray index, cast, word)), weights its band energies and, when diffuse,
+// leaves along a cosine-distributed direction (Malley's method in Duff et al.'s branchless basis) instead of reflect_hit's.  Only a lane that
+// went diffuse runs the rejection loop, drawing its words as it goes (about 1.27 tries).  Integer ops, + - * /, sqrt and copysign only, FP64,
+// no contraction: bit-exact with tests/scatter_ref.py.  sqrt is LLVM's correctly rounded FP64 expansion (v_rsq_f64 + refinement), as numpy's.
+static __device__ __forceinline__ unsigned long long scatter_mix(unsigned long long z)
+{
+    z ^= z >> 30;
+    z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27;
+    z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z;
+}
+constexpr unsigned long long kScatterGamma = 0x9E3779B97F4A7C15ull;
+// u_j of the header: (double)(mix(base + ((c << 8) | j) * G) >> 11) * 2^-53, in [0, 1)
+static __device__ __forceinline__ double scatter_u(unsigned long long base, unsigned long long c8, unsigned j)
+{
+    return (double)(scatter_mix(base + (c8 | (unsigned long long)j) * kScatterGamma) >> 11) * 0x1p-53;
+}
+// the diffuse direction of a ray r that hit a polygon of normal n at e (|d_out| = |d|): the header's operations in the header's order
+static __device__ __forceinline__ RayRec scatter_hit(double nx, double ny, double nz, const RayRec& r, const XEventRec& e,
+                                                     unsigned long long base, unsigned long long c8)
+{
+    if (dot3(r.dx, r.dy, r.dz, nx, ny, nz) > 0) {          // back into the half-space the ray came from
+        nx = -nx;
+        ny = -ny;
+        nz = -nz;
+    }
+    double x = 0, y = 0, r2 = 0;
+    for (unsigned t = 0; t < 32; ++t) {
+        const double xt = 2.0 * scatter_u(base, c8, 1 + 2 * t) - 1.0;
+        const double yt = 2.0 * scatter_u(base, c8, 2 + 2 * t) - 1.0;
+        const double rt = xt * xt + yt * yt;
+        if (rt < 1.0) {
+            x = xt;
+            y = yt;
+            r2 = rt;
+            break;
+        }
+    }
+    const double z = sqrt(1.0 - r2);
+    const double sg = copysign(1.0, nz);
+    const double ia = -1.0 / (sg + nz);
+    const double ib = (nx * ny) * ia;
+    const double t1x = 1.0 + ((sg * nx) * nx) * ia, t1y = sg * ib, t1z = -(sg * nx);
+    const double t2x = ib, t2y = sg + (ny * ny) * ia, t2z = -ny;
+    const double len = sqrt((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
+    RayRec o;
+    o.x = e.x; o.y = e.y; o.z = e.z;
+    o.dx = ((x * t1x + y * t2x) + z * nx) * len;
+    o.dy = ((x * t1y + y * t2y) + z * ny) * len;
+    o.dz = ((x * t1z + y * t2z) + z * nz) * len;
+    return o;
+}
+
+template <bool SCATTER>
+static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
@@ -124,16 +182,55 @@ extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect(ReceiveAr
     // ---- state update, reflection (hare_reflect's arithmetic and marks)
     bool lives_on = false;
     if (live) {
+        bool diffuse = false;
+        unsigned long long base = 0, c8 = 0;
+        double nx = 0, ny = 0, nz = 0;
         if (e.hit || a.init_state) {               // a miss leaves its state as it is (init_state: as it starts)
             const double* al = (e.hit && a.alpha) ? a.alpha + (size_t)e.poly_id * (size_t)B : nullptr;
-            a.state[i] = e.hit ? L + e.t : L;
+            if constexpr (SCATTER) {
+                // every load (absorption, scattering and normal of the polygon) ahead of the first store to the state, which the compiler
+                // must assume may alias them: issued together, their latencies overlap
+                const bool scat = e.hit && !a.last;            // the choice and its weights: only a ray that will be reflected
+                const double* sg = a.sigma + (size_t)(scat ? e.poly_id : 0) * (size_t)B;
+                double sig[kMaxBands];
 #pragma unroll
-            for (int b = 0; b < kMaxBands; ++b)
-                if (b < B) a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i] = al ? E[b] * (1.0 - al[b]) : E[b];      // no table: alpha = 0
+                for (int b = 0; b < kMaxBands; ++b) sig[b] = (scat && b < B) ? sg[b] : 0.0;
+                if (scat) {
+                    const PolyRec& pr = a.polys[e.poly_id];
+                    nx = pr.n[0]; ny = pr.n[1]; nz = pr.n[2];
+                }
+#pragma unroll
+                for (int b = 0; b < kMaxBands; ++b)
+                    if (b < B && al) E[b] = E[b] * (1.0 - al[b]);
+                if (scat) {
+                    double p = sig[0];
+#pragma unroll
+                    for (int b = 1; b < kMaxBands; ++b)
+                        if (b < B) p = p + sig[b];
+                    p = p / (double)B;
+                    base = scatter_mix(scatter_mix(a.seed + kScatterGamma) ^ (unsigned long long)(a.ray_base + i));
+                    c8 = (unsigned long long)a.cast << 8;
+                    diffuse = scatter_u(base, c8, 0) < p;
+                    const double den = diffuse ? p : 1.0 - p;                  // one division per band: sigma / p or (1 - sigma) / (1 - p)
+#pragma unroll
+                    for (int b = 0; b < kMaxBands; ++b)
+                        if (b < B) E[b] = E[b] * ((diffuse ? sig[b] : 1.0 - sig[b]) / den);
+                }
+                a.state[i] = e.hit ? L + e.t : L;
+#pragma unroll
+                for (int b = 0; b < kMaxBands; ++b)
+                    if (b < B) a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i] = E[b];
+            } else {
+                a.state[i] = e.hit ? L + e.t : L;
+#pragma unroll
+                for (int b = 0; b < kMaxBands; ++b)
+                    if (b < B) a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i] = al ? E[b] * (1.0 - al[b]) : E[b];      // no table: alpha = 0
+            }
         }
         if (e.hit) {
             if (!a.last) {
-                a.rays[i] = reflect_hit(a.polys, r, e);         // kernels.hip: hare_reflect's arithmetic, shared
+                if constexpr (SCATTER) a.rays[i] = diffuse ? scatter_hit(nx, ny, nz, r, e, base, c8) : reflect_about(nx, ny, nz, r, e);
+                else a.rays[i] = reflect_hit(a.polys, r, e);         // kernels.hip: hare_reflect's arithmetic, shared
                 a.excl[i] = e.poly_id;
                 lives_on = true;
             }
@@ -146,4 +243,14 @@ extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect(ReceiveAr
         const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
         if (lane == 0 && blk * 64 < a.n) a.block_live[blk] = lm != 0ull ? 1 : 0;
     }
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect(ReceiveArgs a)
+{
+    receive_body<false>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter(ReceiveArgs a)
+{
+    receive_body<true>(a);
 }

@@ -60,6 +60,7 @@ struct SceneOptions {
                                // more one-workgroup launch per cast) and the next cast walks the list: open scenes; 0: off (a closed room saves ~1 %)
     int wide_drain = 1;        // 1: K1q's wide cull / wide walk in the drain of a launch (voxel_pool.hip); 0: the pool's ordinary phases to the end (A/B)
     int receive_aggregate = 1; // 1: hare_receive_reflect sums a wave's histogram adds per distinct (receiver, bin) before one atomic; 0: an atomic per detecting lane (A/B).  Same results
+    long long scatter_seed = 0;    // the scattering RNG's seed S (hare_receive_scatter; read as uint64 bits)
     long long dev_order_ptr = 0;   // developer experiments (a `dev` scene only): a device array of n uint32, the order K1q takes the rays in (ShootIO::order)
     int tune[5] = {0, 0, 0, 0, 0};   // HARE_TUNE: steps,refill,chunk,blocks_per_cu,exact (profiling build; blocks_per_cu: K1p)
 };
@@ -116,7 +117,7 @@ struct DeviceModule {
     hipFunction_t octree = nullptr, octree_count = nullptr, octree_persist = nullptr, octree_pool = nullptr, octree_tail = nullptr, octree_group = nullptr, octree_group_tail = nullptr, octree_dense = nullptr;
     hipFunction_t kdtree = nullptr, kdtree_count = nullptr;
     hipFunction_t reflect = nullptr, occlusion = nullptr;
-    hipFunction_t receive_reflect = nullptr;                               // receive.hip: hare_receive_reflect
+    hipFunction_t receive_reflect = nullptr, receive_scatter = nullptr;    // receive.hip: hare_receive_reflect, hare_receive_scatter
     hipFunction_t voxel_occl_tri = nullptr, voxel_occl_quad = nullptr, voxel_occl_tri_g = nullptr, voxel_occl_quad_g = nullptr, octree_occl = nullptr, octree_occl_any = nullptr;
     hipFunction_t events_pack_slim = nullptr;
     hipFunction_t block_occ = nullptr;                                     // build_kernels.hip: hare_block_occ
@@ -285,9 +286,12 @@ struct Scene {
     void* d_rcv = nullptr;
     bool rcv_on_device = false;
     std::vector<std::vector<double>> alpha;      // per topology: P x bands, or empty (no table: B = 1, every alpha 0)
-    std::vector<int32_t> bands;                  // per topology: B (1 without a table)
+    std::vector<int32_t> bands;                  // per topology: B of its tables (1 without one); the first table set fixes it for the other
     std::vector<void*> d_alpha;                  // per topology: device copy of alpha, or null
     std::vector<char> alpha_on_device;
+    std::vector<std::vector<double>> sigma;      // per topology: P x bands scattering coefficients, or empty (no table: specular only)
+    std::vector<void*> d_sigma;                  // per topology: device copy of sigma, or null
+    std::vector<char> sigma_on_device;
 };
 void free_host_mirror(Scene& s);             // host_trace.cpp
 void make_poly_records(const Topo& T, std::vector<PolyRec>& rec, std::vector<QuadRec>& quads);   // device_scene.cpp
@@ -309,7 +313,8 @@ struct ShootExtra {
     const uint32_t* blocks = nullptr;
     const uint32_t* blk_words = nullptr;
 };
-// rcv non-null (hare_receive_*): always a launch per cast, hare_receive_reflect behind every cast (the last included) instead of hare_reflect;
+// rcv non-null (hare_receive_*): always a launch per cast, hare_receive_reflect (hare_receive_scatter where rcv->sigma is set) behind every
+// cast (the last included) instead of hare_reflect;
 // rcv supplies the receivers, state, histogram and switches, the loop fills in the rest per cast
 int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, void* d_rays, const void* d_e1, const void* d_e2,
                        int32_t casts, uint32_t flags, void* d_work, void* d_all, void* d_last, void* d_ctr, void* d_ctr_casts, hipStream_t st,
@@ -320,11 +325,13 @@ void free_bounce_buffers(const HipApi* H, Scene& s);          // bounce.cpp
 // receivers (receive.cpp)
 int upload_receivers(Scene& s, const HipApi* H);
 void free_receivers(const HipApi* H, Scene& s);
-int32_t scene_bands(const Scene& s, int32_t top);             // B of Model[top]'s absorption table (1 without one)
+int32_t scene_bands(const Scene& s, int32_t top);             // B of Model[top]'s absorption / scattering tables (1 without one)
 int receive_check_args(const char* who, const Scene& s, int32_t kind, int32_t top, int64_t n, int32_t bounces, int32_t n_bins, double bin_len,
                        int32_t frac_bits);
+bool scene_has_scattering(const Scene& s, int32_t top);       // Model[top] has a scattering table (hare_receive_scatter)
+// ray_base: the global index of the call's ray 0 (the scattering RNG's g = ray_base + i)
 int receive_args(const Scene& s, int32_t top, int32_t n_bins, double bin_len, int32_t frac_bits, void* d_state, void* d_hist, void* d_det,
-                 bool init_state, ReceiveArgs& ra);
+                 bool init_state, int64_t ray_base, ReceiveArgs& ra);
 int receive_ready(Scene& s, const HipApi* H, const char* who);
 
 // device plumbing (device_scene.cpp) shared with api.cpp, launch.cpp and build_gpu.cpp

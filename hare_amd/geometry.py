@@ -381,6 +381,18 @@ class Spatial_Partition:
         check(lib.hare_scene_set_absorption(self._h, int(top_index), a.shape[1], ptr(a)))
         return self
 
+    def set_scattering(self, sigma, top_index: int = 0):
+        """hare_scene_set_scattering: sigma [P, B] in [0, 1] for Model[top_index] (the same B as its absorption table, if any): the receive
+        loop scatters diffusely (seed: option "scatter_seed").  sigma None removes the table (specular reflection only)."""
+        if sigma is None:
+            check(lib.hare_scene_set_scattering(self._h, int(top_index), 0, None))
+            return self
+        s = np.ascontiguousarray(sigma, np.float64)
+        if s.ndim != 2:
+            raise ValueError("sigma must be [polygons, bands]")
+        check(lib.hare_scene_set_scattering(self._h, int(top_index), s.shape[1], ptr(s)))
+        return self
+
     def _receive_shape(self, top_index: int, n_bins: int):
         return self.get_option("receivers"), int(n_bins), self._bands(top_index)
 

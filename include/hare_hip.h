@@ -220,6 +220,7 @@ HARE_API void hare_scene_destroy(hare_scene *s);
  *                     built and traced without them: never an error, never a different result
  *   "receive_aggregate"  1 (default): hare_receive_reflect sums a wave's histogram adds per distinct (receiver, bin) before ONE atomic
  *                     instruction; 0: an atomic per detecting lane and band (A/B).  Results never depend on it
+ *   "scatter_seed"    any int64 (default 0), read as uint64 bits: the seed S of the receive loop's scattering RNG ("receivers" below)
  *   "dev"             1: developer flag bits of hare_shoot_* (timeline, phase profile, cull audit) pass
  * Single-caller like the build calls: not to be changed while shoots are in flight on the scene. */
 HARE_API int hare_scene_set_option(hare_scene *s, const char *name, int64_t value);
@@ -235,7 +236,7 @@ HARE_API int hare_scene_set_option(hare_scene *s, const char *name, int64_t valu
  *                           entry points to "none of these"
  *   "octree_scratch_bytes"  device bytes of the octree kernels' scratch ring (hand-over records and stack spill; 0 before the first
  *                           octree launch that needs one)
- *   "receivers", "bands"    K of hare_scene_set_receivers (0: none set) and B of topology 0's absorption table (1: none);
+ *   "receivers", "bands"    K of hare_scene_set_receivers (0: none set) and B of topology 0's absorption / scattering tables (1: none);
  *   "bands:<top>"           B of topology <top> (e.g. "bands:1"; HARE_E_INVALID for a topology the scene does not have)
  * No reference counterpart: Hare has no device memory to account for. */
 HARE_API int hare_scene_get_option(const hare_scene *s, const char *name, int64_t *value);
@@ -457,6 +458,38 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * cast too).  Then it is reflected as in the bounce loop (not behind the last cast).  A ray that missed is retired and its state is
  * left as it is.
  *
+ * Scattering (diffuse, Lambertian).  A topology may also hold a scattering table: sigma[p][b], one value in [0, 1] per polygon and band.
+ * It shares B with the topology's absorption table: whichever of the two is set first fixes B, and setting the other with a different B
+ * is HARE_E_INVALID (absorption alone may still be replaced with a different B).  A topology with no scattering table reflects
+ * specularly, as above.  With one, a ray that hit in cast c and will be reflected (never behind the last cast) chooses, after its
+ * absorption update, between specular and diffuse.  FP64, no contraction; g is the ray's index in the call's `rays` (in the sharded call
+ * the GLOBAL index, not the index in its shard), S the scene option "scatter_seed".  Integer arithmetic is uint64, wrapping mod 2^64:
+ *
+ *   G       = 0x9E3779B97F4A7C15
+ *   mix(z)  = z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31   (SplitMix64's finaliser)
+ *   base    = mix(mix(S + G) ^ g)
+ *   u_j     = (double)(mix(base + (((uint64)c << 8) | j) * G) >> 11) * 2^-53          j = 0 .. 64, in [0, 1)
+ *   p       = (((sigma[0] + sigma[1]) + ...) + sigma[B-1]) / (double)B                (left to right; sigma = sigma[Poly_id])
+ *   diffuse = u_0 < p
+ *   E[b]    = E[b] * (sigma[b] / p)                   if diffuse
+ *   E[b]    = E[b] * ((1.0 - sigma[b]) / (1.0 - p))   otherwise
+ *
+ * (c < 4096 and j < 256: the word of each (c, j) is distinct.)  Each band's energy is unbiased in expectation; at p = 0 (an all-zero
+ * row) no ray goes diffuse and every weight is exactly 1.  A specular ray is reflected as above.  A diffuse ray takes a cosine-distributed
+ * direction (Malley's method in the branchless orthonormal basis of Duff et al. 2017):
+ *
+ *   n  = Normal(Poly_id); n' = dot3(d, n) > 0 ? -n : n                 (the side the ray came from: polygons are two-sided)
+ *   for t = 0 .. 31: x = 2.0*u_{1+2t} - 1.0; y = 2.0*u_{2+2t} - 1.0; r2 = x*x + y*y; take the first with r2 < 1.0
+ *                    (none taken: x = y = r2 = 0)
+ *   z  = sqrt(1.0 - r2)
+ *   sg = copysign(1.0, n'z); a = -1.0 / (sg + n'z); b = (n'x * n'y) * a
+ *   t1 = (1.0 + ((sg * n'x) * n'x) * a,  sg * b,  -(sg * n'x));  t2 = (b,  sg + (n'y * n'y) * a,  -n'y)
+ *   w_i = (x * t1_i + y * t2_i) + z * n'_i;  len = sqrt((dx*dx + dy*dy) + dz*dz);  d_out = (wx * len, wy * len, wz * len)
+ *
+ * from the X_Point, excluding Poly_id, as a specular ray does (|d_out| = |d|: L keeps its meaning).  The plain bounce loop is not affected.
+ * Every call restarts c at 0: a device caller that splits one burst over several calls varies "scatter_seed" from call to call, or the
+ * calls draw the same numbers.
+ *
  * The histogram is fixed point in uint64: integer sums do not depend on the order of the adds, so the result is bit-identical from
  * run to run, between the one-device and the sharded call, and against a restatement on the host.  (r*r is formed once, when the
  * receivers are set: the same FP64 product.)
@@ -466,12 +499,15 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  *   hare_scene_set_receivers    replaces the receivers: centers K x 3, radii K.  HARE_E_INVALID for K outside 1..256, a non-finite
  *                               center, or a radius that is not finite and > 0
  *   hare_scene_set_absorption   alpha: P x B of Model[top_index] (row per polygon).  HARE_E_INVALID for a bad top_index, B outside 1..8,
- *                               or any alpha outside [0, 1] or NaN
+ *                               any alpha outside [0, 1] or NaN, or a B other than that of the topology's scattering table
+ *   hare_scene_set_scattering   sigma: P x B of Model[top_index], checked as alpha is (and against the absorption table's B); B = 0 with
+ *                               sigma NULL removes the table
  * hare_scene_get_option reads back "receivers" (K; 0 before the first set), "bands" (B of topology 0) and "bands:<top>" (B of topology
  * <top>): the sizes of a receive call's histogram (K x n_bins x B) and state ((1 + B) x n) for that topology.  The library cannot check the
  * size of a caller's host buffer: the bindings size theirs from these. */
 HARE_API int hare_scene_set_receivers(hare_scene *s, int32_t K, const double *centers, const double *radii);
 HARE_API int hare_scene_set_absorption(hare_scene *s, int32_t top_index, int32_t B, const double *alpha);
+HARE_API int hare_scene_set_scattering(hare_scene *s, int32_t top_index, int32_t B, const double *sigma);
 
 /* The receive loop on DEVICE buffers: stream-ordered like hare_shoot_device -- no allocation, no free, no wait ("hip_malloc_calls" ...).
  * Always a launch per cast (the scene option "bounce_fused" does not apply; results are the same either way).
@@ -495,7 +531,8 @@ HARE_API int hare_receive_batch(hare_scene *s, int32_t kind, int32_t top_index, 
                                 double bin_len, int32_t frac_bits, const double *state_in, double *state_out, uint64_t *hist,
                                 uint64_t *detections, hare_counters *ctr);
 /* Over several devices: rays [n*k/G, n*(k+1)/G) go to scenes[k] (as hare_bounce_batch_sharded), the histograms and detections are
- * summed.  Byte-identical to the one-device call.  The scenes must hold the same receivers and bands (HARE_E_INVALID otherwise). */
+ * summed.  Byte-identical to the one-device call.  The scenes must hold the same receivers, bands, scattering table and (with one)
+ * "scatter_seed" (HARE_E_INVALID otherwise). */
 HARE_API int hare_receive_batch_sharded(hare_scene *const *scenes, int32_t n_scenes, int32_t kind, int32_t top_index, int64_t n,
                                         const hare_ray *rays, const int32_t *excl1, const int32_t *excl2, int32_t bounces,
                                         uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits,

@@ -3,7 +3,11 @@ hare_bounce_device (last cast only) on the same burst, device-resident, HIP even
 B = 1 / 8 bands, 4 000 bins; receiver 0 is the direct-sound case (a 1 m sphere 2 m from the source: ~7 % of the rays cross it in cast 0,
 into one or two bins), timed with the wave-aggregated atomics and with the naive ones.  With --host, also the host alternative a caller
 has without the feature: Bounce_batch(all_casts=True) and the numpy restatement of the step (tests/receiver_ref.py) on every cast.
-Prints ONE JSON line.  usage: python tools/receiver_rate.py [hall|cathedral] [--rays N] [--bounces B] [--reps R] [--host] [--quick]"""
+With --scatter SIGMA (K = 8, B = 8 only), the same loop again with a scattering table of SIGMA on every polygon and band (hare_receive_scatter
+in place of hare_receive_reflect; SIGMA 0 runs that kernel on exactly the rays the specular loop has); run it under rocprofv3 --kernel-trace
+for the two kernels' per-cast times.
+Prints ONE JSON line.  usage: python tools/receiver_rate.py [hall|cathedral] [--rays N] [--bounces B] [--reps R] [--host] [--quick]
+                                                          [--scatter SIGMA]"""
 import argparse
 import json
 import os
@@ -23,6 +27,8 @@ ap.add_argument("--bounces", type=int, default=8)
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--host", action="store_true", help="also time Bounce_batch(all_casts=True) + the numpy step (K = 8, B = 8)")
 ap.add_argument("--quick", action="store_true", help="K = 8, B = 8 only (a profiling run)")
+ap.add_argument("--scatter", type=float, default=None, metavar="SIGMA",
+                help="K = 8, B = 8 only, and the loop again with a scattering table of SIGMA everywhere (scene option scatter_seed 1)")
 a = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("receiver_rate: no GPU -- nothing to measure")
@@ -68,7 +74,7 @@ def bounce():
 ms_bounce = timed(bounce, a.reps)
 out = {"scene": a.scene, "domain": D, "rays": n, "bounces": nb, "n_bins": N_BINS, "bounce_ms": round(ms_bounce, 3),
        "bounce_Mcasts_s": round(n * nb / ms_bounce / 1e3, 1), "receive": []}
-cases = [(8, 8)] if a.quick else [(K, B) for K in (1, 8, 64) for B in (1, 8)]
+cases = [(8, 8)] if (a.quick or a.scatter is not None) else [(K, B) for K in (1, 8, 64) for B in (1, 8)]
 for K, B in cases:
     c, r = receivers(K)
     g.set_receivers(c, r)
@@ -82,7 +88,7 @@ for K, B in cases:
         g.receive_device(n, d_rays.data_ptr(), nb, N_BINS, BIN_LEN, FRAC, d_state.data_ptr(), d_work.data_ptr(), d_last.data_ptr(),
                          d_hist.data_ptr(), d_det.data_ptr(), stream=st)
     row = {"K": K, "B": B}
-    for agg in ((1, 0) if K == 8 and B == 8 else (1,)):
+    for agg in ((1, 0) if K == 8 and B == 8 and a.scatter is None else (1,)):
         g.set_option("receive_aggregate", agg)
         d_hist.zero_(); d_det.zero_()
         d_state.copy_(init)
@@ -97,6 +103,16 @@ for K, B in cases:
     det = d_det.cpu().numpy().reshape(K, 2)
     row["direct_frac_cast_sum"] = round(float(det[0].sum()) / n, 4)     # detections of receiver 0 (all casts) per ray
     row["detections"] = int(det.sum())
+    if a.scatter is not None:                                            # the same loop with diffuse scattering
+        g.set_scattering(np.full((T.Polygon_Count, B), a.scatter)).set_option("scatter_seed", 1)
+        ms = timed(lambda: (d_state.copy_(init), receive()), a.reps)
+        row["scatter_sigma"] = a.scatter
+        row["scatter_ms"] = round(ms - ms_copy, 3)
+        row["scatter_over_specular_pct"] = round(100.0 * (ms - ms_copy - row["ms"]) / row["ms"], 1)
+        d_hist.zero_(); d_det.zero_(); d_rays.copy_(d_src); d_state.copy_(init)
+        receive(); torch.cuda.synchronize()
+        row["scatter_detections"] = int(d_det.cpu().numpy().sum())
+        g.set_scattering(None)
     out["receive"].append(row)
     print(json.dumps(row), file=sys.stderr, flush=True)
 
