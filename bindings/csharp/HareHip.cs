@@ -99,6 +99,7 @@ namespace Hare
             public const uint HARE_SHOOT_COUNT_OWN = 64;     // measurement: the production kernel's counting build (its own cells / entries / pre-culls / tests)
             public const uint HARE_SHOOT_BOUNCE_LOOP = 32;   // hare_shoot_kernel_name only
             public const uint HARE_SHOOT_SLIM_EVENTS = 16;   // host-buffer batches: hare_slim_event records come back (16 B per ray, not 56)
+            public const uint HARE_RECEIVE_DIFFUSE_RAIN = 128;   // receive calls: diffuse rain where the topology has a scattering table
 
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr hare_last_error();
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int hare_device_count(out int count);

@@ -41,12 +41,13 @@ void free_bounce_buffers(const HipApi* H, Scene& s)
         Scene::BounceBuf& b = c.bounce;
         if (b.copy_st) { (void)H->StreamSynchronize(b.copy_st); (void)H->StreamDestroy(b.copy_st); b.copy_st = nullptr; }
         for (void** p : {&b.rays[0], &b.rays[1], &b.excl[0], &b.excl[1], &b.excl2, &b.idx[0], &b.idx[1], &b.ev[0], &b.ev[1], &b.full,
-                         &b.tiles, &b.ctr, &b.state, &b.hist})
+                         &b.tiles, &b.ctr, &b.state, &b.hist, &b.rain})
             dev_free(H, *p);
         b.cap = 0;
         b.ctr_cap = 0;
         b.state_cap = 0;
         b.hist_cap = 0;
+        b.rain_cap = 0;
     }
 }
 
@@ -227,6 +228,7 @@ struct ReceiveJob {
     uint64_t* hist = nullptr;
     uint64_t* det = nullptr;
     int64_t ray_base = 0;      // this shard's first ray in the whole batch (the scattering RNG's global ray index)
+    bool rain = false;         // HARE_RECEIVE_DIFFUSE_RAIN
 };
 
 // The receive loop for one scene: rays, exclusions and state go up, the loop is enqueued ONCE (a launch per cast, hare_receive_reflect
@@ -253,6 +255,14 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
         HIP_TRY(H->Malloc(&b.hist, hist_bytes));
         b.hist_cap = hist_bytes;
     }
+    const bool rain = job.rain && scene_has_scattering(s, top);     // rain needs a scattering table: without one the flag changes nothing
+    const size_t rain_bytes = (size_t)HARE_RECEIVE_RAIN_WORK_BYTES(n);
+    if (rain && rain_bytes > b.rain_cap) {
+        dev_free(H, b.rain);
+        b.rain_cap = 0;
+        HIP_TRY(H->Malloc(&b.rain, rain_bytes));
+        b.rain_cap = rain_bytes;
+    }
     if (!c.st[0]) HIP_TRY(H->StreamCreate(&c.st[0]));
     hipStream_t st = c.st[0];
     uint64_t* const d_hist = (uint64_t*)b.hist;
@@ -270,8 +280,14 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
     ReceiveArgs ra;
     if (int rc = receive_args(s, top, job.n_bins, job.bin_len, job.frac_bits, d_state, d_hist, d_det, job.state_in == nullptr, job.ray_base, ra))
         return rc;
-    if (int rc = bounce_device_impl(s, H, kind, top, n, b.rays[0], excl1 ? b.excl[0] : nullptr, excl2 ? b.excl2 : nullptr, bounces, flags, b.ev[1],
-                                    nullptr, b.ev[0], nullptr, b.ctr, st, &ra))
+    void* const work = rain ? b.rain : b.ev[1];         // b.ev[1] holds the loop's 2 n int32; with rain, a buffer of its own holds them and the rain's scratch
+    RainWork rw;
+    if (rain) {
+        rw = rain_work(work, n);
+        ra.rain_flag = rw.flag;
+    }
+    if (int rc = bounce_device_impl(s, H, kind, top, n, b.rays[0], excl1 ? b.excl[0] : nullptr, excl2 ? b.excl2 : nullptr, bounces, flags, work,
+                                    nullptr, b.ev[0], nullptr, b.ctr, st, &ra, rain ? &rw : nullptr))
         return rc;
     HIP_TRY(H->MemcpyAsync(job.hist, d_hist, hist_words * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(H->MemcpyAsync(job.det, d_det, 2 * K * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -524,6 +540,7 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
         job.hist = k == 0 ? hist : hists[(size_t)k].data();
         job.det = k == 0 ? detections : dets[(size_t)k].data();
         job.ray_base = lo;
+        job.rain = (flags & HARE_RECEIVE_DIFFUSE_RAIN) != 0;
         try {
             rcs[(size_t)k] = bounce_one(scenes[k], kind, top_index, hi - lo, rays ? rays + lo : nullptr, excl1 ? excl1 + lo : nullptr,
                                         excl2 ? excl2 + lo : nullptr, bounces, flags, nullptr, n, nullptr, pcs[(size_t)k].data(), &job);

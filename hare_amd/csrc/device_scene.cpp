@@ -96,6 +96,8 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_reflect", &m->reflect},
         {"hare_receive_reflect", &m->receive_reflect},
         {"hare_receive_scatter", &m->receive_scatter},
+        {"hare_receive_scatter_rain", &m->receive_scatter_rain},
+        {"hare_rain_step", &m->rain_step},
         {"hare_occlusion", &m->occlusion},
         {"hare_voxel_occl_tri", &m->voxel_occl_tri},
         {"hare_voxel_occl_quad", &m->voxel_occl_quad},

@@ -502,6 +502,37 @@ struct ReceiveArgs {
     const double* sigma;       // P x bands scattering coefficients of Model[top] (null: hare_receive_reflect)
     unsigned long long seed;   // scene option "scatter_seed"
     long long ray_base;        // global index of ray 0 of this call (the shard's offset in hare_receive_batch_sharded): g = ray_base + i
+    // hare_receive_scatter_rain only (HARE_RECEIVE_DIFFUSE_RAIN; last, so that the fields above keep their offsets):
+    int32_t* rain_flag;        // n flags: 1 when the ray's reflection in the previous cast was diffuse (its segment is rained, not detected)
+};
+
+// hare_rain_step (receive.hip): diffuse rain between the shoot and the receive kernel of a cast -- the deposit of receiver k_dep's
+// visibility query (its flags in `socc`) and the emission of receiver k_emit's.  Reads what hare_receive_scatter_rain reads before it
+// updates anything (ray, event, state), so both compute the same bits.
+struct RainArgs {
+    const PolyRec* polys;      // Model[top]
+    const RayRec* rays;        // n rays, the ray each lane's cast received
+    const XEventRec* ev;       // the cast's n events
+    const int32_t* marks;      // the loop's marks (-2: retired), when marks_valid
+    const double* state;       // (1 + bands) planes of n doubles: L, E before this cast's update
+    const double* alpha;       // nullable: P x bands
+    const double* sigma;       // P x bands
+    const double* rcv;         // n_rcv x 4: cx, cy, cz, r * r
+    unsigned long long* hist;  // n_rcv x n_bins x bands, accumulated
+    unsigned long long* det;   // 2 n_rcv, accumulated
+    RayRec* srays;             // n shadow rays: origin X_Point, direction c_k - X_Point
+    double* stmax;             // n t_max (1.0)
+    int32_t* sexcl;            // n: Poly_id for an eligible slot, -2 (retired: no traversal, not occluded) for the others
+    const int32_t* socc;       // n occlusion flags of receiver k_dep's query
+    long long n;
+    double bin_len;
+    double scale;              // 2^frac_bits
+    int32_t bands;
+    int32_t n_bins;
+    int32_t marks_valid;
+    int32_t init_state;
+    int32_t k_dep;             // receiver whose query is deposited (-1: none)
+    int32_t k_emit;            // receiver whose query is emitted (-1: none)
 };
 
 #if defined(__HIPCC__)

@@ -149,6 +149,8 @@ constexpr uint32_t kFlagAnyHit = 0x40000u;         // internal (set below, never
 constexpr uint32_t kPublicFlags = HARE_SHOOT_WRITEBACK_ORIGIN | HARE_SHOOT_COUNT_WORK | HARE_SHOOT_SIMPLE_KERNEL | HARE_SHOOT_RETIRED_RAYS | HARE_SHOOT_SLIM_EVENTS |
                                  HARE_SHOOT_COUNT_OWN;
 static_assert((kPublicFlags & HARE_SHOOT_BOUNCE_LOOP) == 0, "the kernel-name query bit never reaches a kernel");
+static_assert((HARE_RECEIVE_DIFFUSE_RAIN & (kPublicFlags | HARE_SHOOT_BOUNCE_LOOP | 0xF000u | kFlagAnyHit | SHOOT_RETIRED_SILENT)) == 0,
+              "the receive calls' rain bit is a bit of its own");
 uint32_t sanitize_flags(const Scene& s, uint32_t flags)
 {
     return flags & (kPublicFlags | (s.opt.dev ? 0xF000u : 0u));
@@ -455,7 +457,7 @@ static void fill_voxel_args(const Scene& s, int32_t top, VoxelArgs& g)
 //   d_ctr    nullable: totals, accumulated (rays = casts with a live ray);  d_ctr_casts: nullable, `casts` blocks, accumulated
 int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, void* d_rays, const void* d_e1, const void* d_e2,
                        int32_t casts, uint32_t flags, void* d_work, void* d_all, void* d_last, void* d_ctr, void* d_ctr_casts, hipStream_t st,
-                       const ReceiveArgs* rcv)
+                       const ReceiveArgs* rcv, const RainWork* rain)
 {
     if (n < 0 || casts < 1 || casts > 4096 || top < 0 || top >= (int32_t)s.topos.size()) {
         set_error("hare_bounce: bad n, bounces or top_index");
@@ -475,10 +477,13 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
     hare_xevent* const all = (hare_xevent*)d_all;
     hare_xevent* const last = d_last ? (hare_xevent*)d_last : all + (size_t)(casts - 1) * (size_t)n;
     int32_t* const work = (int32_t*)d_work;
-    if (!M.reflect || !M.events_fill_miss || (rcv && !(rcv->sigma ? M.receive_scatter : M.receive_reflect))) {
+    if (rain && !(rcv && rcv->sigma && rcv->rain_flag)) rain = nullptr;
+    hipFunction_t const receive_fn = !rcv ? nullptr : (!rcv->sigma ? M.receive_reflect : (rain ? M.receive_scatter_rain : M.receive_scatter));
+    if (!M.reflect || !M.events_fill_miss || (rcv && !receive_fn) || (rain && !M.rain_step)) {
         set_error("hare_bounce: bounce kernels missing from code object");
         return HARE_E_STATE;
     }
+    if (rain) HIP_TRY(H->MemsetAsync(rain->flag, 0, (size_t)n * sizeof(int32_t), st));      // no segment of this call has been rained yet
     // ---- one launch?  (never for the receive loop: its receiver step runs between the casts)
     if (!rcv && kind == HARE_KIND_VOXEL && casts <= kBounceMaxCasts && flags == 0 && s.vox.built && !s.d_cells.empty()) {
         const KernChoice kc = choose_kernel(s, &M, kind, (size_t)top, n, 0u);
@@ -585,8 +590,45 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
             ra.last = last_cast ? 1 : 0;
             ra.init_state = c == 0 ? rcv->init_state : 0;      // the starting state is the first cast's business only
             ra.cast = c;
+            if (rain && !last_cast) {
+                // diffuse rain (receive.hip: hare_rain_step), before the receive kernel overwrites rays and state: receiver k's query is
+                // emitted, answered by the flags-only occlusion kernel of this partition, and deposited by the launch that emits k + 1's
+                RainArgs g;
+                memset(&g, 0, sizeof g);
+                g.polys = ra.polys;
+                g.rays = ra.rays;
+                g.ev = ra.ev;
+                g.marks = work;
+                g.state = ra.state;
+                g.alpha = ra.alpha;
+                g.sigma = ra.sigma;
+                g.rcv = ra.rcv;
+                g.hist = ra.hist;
+                g.det = ra.det;
+                g.srays = rain->rays;
+                g.stmax = rain->tmax;
+                g.sexcl = rain->excl;
+                g.socc = rain->occ;
+                g.n = n;
+                g.bin_len = ra.bin_len;
+                g.scale = ra.scale;
+                g.bands = ra.bands;
+                g.n_bins = ra.n_bins;
+                g.marks_valid = ra.marks_valid;
+                g.init_state = ra.init_state;
+                for (int32_t k = 0; k <= ra.n_rcv; ++k) {
+                    g.k_dep = k - 1;
+                    g.k_emit = k < ra.n_rcv ? k : -1;
+                    void* ga[] = {&g};
+                    if (int rc = launch(H, M.rain_step, (unsigned)((n + 255) / 256), 256, 0, st, ga)) return fail(rc);
+                    if (k == ra.n_rcv) break;
+                    if (int rc = shoot_device_impl(s, H, kind, top, n, rain->rays, rain->excl, nullptr, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st,
+                                                   rain->tmax, rain->occ))
+                        return fail(rc);
+                }
+            }
             void* a[] = {&ra};
-            if (int rc = launch(H, rcv->sigma ? M.receive_scatter : M.receive_reflect, (unsigned)((n + 255) / 256), 256, 0, st, a)) return fail(rc);
+            if (int rc = launch(H, receive_fn, (unsigned)((n + 255) / 256), 256, 0, st, a)) return fail(rc);
             if (use_blocks && !last_cast) {
                 uint32_t nb = (uint32_t)nblk;
                 const unsigned char* blc = blk_live;

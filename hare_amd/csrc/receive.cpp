@@ -1,5 +1,5 @@
 // receive.cpp -- receivers, absorption and scattering of a scene (hare_scene_set_receivers / _absorption / _scattering) and hare_receive_device,
-// the bounce loop with the receiver step between its casts (include/hare_hip.h, "receivers"; the kernel: receive.hip).  The host-buffer
+// the bounce loop with the receiver step (and, on request, diffuse rain) between its casts (include/hare_hip.h, "receivers"; the kernel: receive.hip).  The host-buffer
 // calls hare_receive_batch / _sharded are in bounce.cpp, beside the loop they share with hare_bounce_batch.
 //
 // Harness-defined: the reference has no receivers (Pachyderm, its caller, detects them on the host per ray).
@@ -122,6 +122,19 @@ int receive_args(const Scene& s, int32_t top, int32_t n_bins, double bin_len, in
         return HARE_E_STATE;
     }
     return HARE_OK;
+}
+
+// The rain's scratch in a receive call's work array: behind the loop's 2 n int32, from a 16-byte boundary: n shadow rays (48 B), n t_max,
+// n exclusions, n occlusion flags, n suppression flags: 76 n bytes in all and at most 15 of padding, within HARE_RECEIVE_RAIN_WORK_BYTES(n)
+RainWork rain_work(void* d_work, int64_t n)
+{
+    RainWork w;
+    w.rays = (RayRec*)(((uintptr_t)d_work + (uintptr_t)n * 8u + 15u) & ~(uintptr_t)15u);
+    w.tmax = (double*)(w.rays + n);
+    w.excl = (int32_t*)(w.tmax + n);
+    w.occ = w.excl + n;
+    w.flag = w.occ + n;
+    return w;
 }
 
 // After the device checks: receivers set, and on the device (uploads only what a setter run without a device left behind)
@@ -305,6 +318,7 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
     if (int rc = receive_check_args("hare_receive_device", *s, kind, top_index, n, bounces, n_bins, bin_len, frac_bits)) return rc;
     const int64_t K = std::max<int64_t>(1, (int64_t)(s->rcv.size() / 4));
     const int32_t B = scene_bands(*s, top_index);
+    const bool rain = (flags & HARE_RECEIVE_DIFFUSE_RAIN) != 0;
     if (n > 0) {
         if (!d_rays || !d_state || !d_work || !d_events_last || !d_hist || !d_detections) {
             set_error("hare_receive_device: null rays / state / work array / events / histogram / detections");
@@ -313,7 +327,7 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
         struct Buf { const void* p; size_t bytes; bool written; };
         const Buf bufs[] = {{d_rays, (size_t)n * sizeof(hare_ray), true},
                             {d_state, (size_t)n * (size_t)(1 + B) * sizeof(double), true},
-                            {d_work, (size_t)n * 2 * sizeof(int32_t), true},
+                            {d_work, rain ? (size_t)HARE_RECEIVE_RAIN_WORK_BYTES(n) : (size_t)n * 2 * sizeof(int32_t), true},
                             {d_events_last, (size_t)n * sizeof(hare_xevent), true},
                             {d_hist, (size_t)K * (size_t)n_bins * (size_t)B * sizeof(uint64_t), true},
                             {d_detections, (size_t)K * 2 * sizeof(uint64_t), true},
@@ -342,8 +356,13 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
     ReceiveArgs ra;
     if (int rc = receive_args(*s, top_index, n_bins, bin_len, frac_bits, d_state, d_hist, d_detections, false, 0, ra)) return rc;
     flags &= HARE_SHOOT_COUNT_WORK | HARE_SHOOT_SIMPLE_KERNEL;
+    RainWork rw;
+    if (rain && ra.sigma) {                 // rain needs a scattering table: without one the flag changes nothing
+        rw = rain_work(d_work, n);
+        ra.rain_flag = rw.flag;
+    }
     return bounce_device_impl(*s, H, kind, top_index, n, d_rays, d_excl1, d_excl2, bounces, flags, d_work, nullptr, d_events_last, d_counters,
-                              nullptr, (hipStream_t)stream, &ra);
+                              nullptr, (hipStream_t)stream, &ra, ra.rain_flag ? &rw : nullptr);
     GUARD_END
 }
 

@@ -1,5 +1,6 @@
-// receive.hip -- hare_receive_reflect / hare_receive_scatter: the receiver step of the receive loop (include/hare_hip.h, "receivers"),
-// #included from kernels.hip.  One body (receive_body), two kernels: the scattering variant is a compile-time switch.
+// receive.hip -- hare_receive_reflect / hare_receive_scatter / hare_receive_scatter_rain: the receiver step of the receive loop (include/hare_hip.h,
+// "receivers"), #included from kernels.hip.  One body (receive_body), three kernels: scattering and rain are compile-time switches.  And
+// hare_rain_step, diffuse rain's emit and deposit (below).
 //
 // One lane per ray, in place of hare_reflect behind every cast of hare_receive_device's loop (launch.cpp: bounce_device_impl with a
 // ReceiveArgs).  A live ray reads its ray, its event and its state once; runs through every receiver sphere in ascending order with the
@@ -78,7 +79,9 @@ static __device__ __forceinline__ RayRec scatter_hit(double nx, double ny, doubl
     return o;
 }
 
-template <bool SCATTER>
+// RAIN (hare_receive_scatter_rain, HARE_RECEIVE_DIFFUSE_RAIN): a ray whose reflection in the previous cast was diffuse (ReceiveArgs::rain_flag)
+// skips the receiver step -- hare_rain_step has deposited that segment -- and every reflected ray writes the flag after its choice.
+template <bool SCATTER, bool RAIN = false>
 static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -104,9 +107,11 @@ static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
     double E[kMaxBands];
 #pragma unroll
     for (int b = 0; b < kMaxBands; ++b) E[b] = 0;
+    bool rained = false;
     if (live) {
         e = a.ev[i];
         r = a.rays[i];
+        if constexpr (RAIN) rained = a.rain_flag[i] != 0;
         if (a.init_state) {
 #pragma unroll
             for (int b = 0; b < kMaxBands; ++b) E[b] = 1.0;
@@ -118,14 +123,15 @@ static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
         }
     }
     // ---- receivers
-    if (__ballot(live) != 0ull) {
+    const bool seen = live && !rained;
+    if (__ballot(seen) != 0ull) {
         const double t_end = (live && e.hit) ? e.t : __builtin_inf();
         const double nb = (double)a.n_bins;
         for (int k = 0; k < a.n_rcv; ++k) {
             const double cx = rcv[4 * k + 0], cy = rcv[4 * k + 1], cz = rcv[4 * k + 2], r2 = rcv[4 * k + 3];
             bool det = false, binned = false;
             int bin = 0;
-            if (live) {
+            if (seen) {
                 const double wx = cx - r.x, wy = cy - r.y, wz = cz - r.z;
                 const double s = ((wx * r.dx + wy * r.dy) + wz * r.dz) / ((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
                 const double qx = (r.x + r.dx * s) - cx, qy = (r.y + r.dy * s) - cy, qz = (r.z + r.dz * s) - cz;
@@ -232,6 +238,7 @@ static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
                 if constexpr (SCATTER) a.rays[i] = diffuse ? scatter_hit(nx, ny, nz, r, e, base, c8) : reflect_about(nx, ny, nz, r, e);
                 else a.rays[i] = reflect_hit(a.polys, r, e);         // kernels.hip: hare_reflect's arithmetic, shared
                 a.excl[i] = e.poly_id;
+                if constexpr (RAIN) a.rain_flag[i] = diffuse ? 1 : 0;
                 lives_on = true;
             }
         } else if (!a.last) {
@@ -253,4 +260,123 @@ extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect(ReceiveAr
 extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter(ReceiveArgs a)
 {
     receive_body<true>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_rain(ReceiveArgs a)
+{
+    receive_body<true, true>(a);
+}
+
+// ---- diffuse rain (HARE_RECEIVE_DIFFUSE_RAIN; the header's "receivers", "Diffuse rain")
+// hare_rain_step runs between a cast's shoot and hare_receive_scatter_rain, which overwrites the rays and the state: a lane per ray reads what
+// that kernel reads and recomputes E after absorption and L' = L + e.t with the same FP64 operations.  One launch deposits receiver k_dep
+// (the flags the occlusion kernel left for the query the previous launch emitted) and emits receiver k_emit's query, so K receivers cost
+// K + 1 launches of this kernel and K occlusion launches per cast (launch.cpp).  A slot without a query is marked -2, which the occlusion
+// kernels skip under HARE_SHOOT_RETIRED_RAYS (no traversal, flag 0).  The deposit adds per lane, not per distinct bin of a wave as the
+// receiver step does: nearly every visible ray deposits and their bins are spread, so the wave's rounds over distinct bins cost more than
+// they save (hall, 1M rays, K = 8, B = 8: the rain loop 94.5 ms aggregated, 79.5 ms per lane; the same histogram).
+extern "C" __global__ __launch_bounds__(256) void hare_rain_step(RainArgs a)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int B = a.bands;
+    const bool in = i < a.n;
+    const bool vis = in && a.k_dep >= 0 && a.sexcl[i] != -2 && a.socc[i] == 0;     // eligible for receiver k_dep and not occluded
+    // a ray takes part when it is live, hit and its polygon's row mean p > 0 (the loop launches this kernel only in casts that reflect);
+    // vis implies it: the previous launch found the same
+    bool part = false;
+    XEventRec e;
+    double sig[kMaxBands];
+#pragma unroll
+    for (int b = 0; b < kMaxBands; ++b) sig[b] = 0;
+    if (in && (a.k_emit >= 0 || vis) && !(a.marks_valid && a.marks[i] == -2)) {
+        e = a.ev[i];
+        if (e.hit) {
+            const double* sg = a.sigma + (size_t)e.poly_id * (size_t)B;
+#pragma unroll
+            for (int b = 0; b < kMaxBands; ++b)
+                if (b < B) sig[b] = sg[b];
+            double p = sig[0];
+#pragma unroll
+            for (int b = 1; b < kMaxBands; ++b)
+                if (b < B) p = p + sig[b];
+            part = p / (double)B > 0;
+        }
+    }
+    double nx = 0, ny = 0, nz = 0, len = 1;
+    if (part) {
+        const RayRec r = a.rays[i];
+        const PolyRec& pr = a.polys[e.poly_id];
+        nx = pr.n[0]; ny = pr.n[1]; nz = pr.n[2];
+        if (dot3(r.dx, r.dy, r.dz, nx, ny, nz) > 0) {      // n': the side the ray came from
+            nx = -nx;
+            ny = -ny;
+            nz = -nz;
+        }
+        len = sqrt((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
+    }
+    // ---- deposit: receiver k_dep, the eligible rays its query found unoccluded
+    if (a.k_dep >= 0 && __ballot(vis) != 0ull) {
+        const int k = a.k_dep;
+        bool binned = false;
+        int bin = 0;
+        unsigned long long q[kMaxBands];
+#pragma unroll
+        for (int b = 0; b < kMaxBands; ++b) q[b] = 0;
+        if (vis) {
+            const double cx = a.rcv[4 * k + 0], cy = a.rcv[4 * k + 1], cz = a.rcv[4 * k + 2], rr = a.rcv[4 * k + 3];
+            const double vx = cx - e.x, vy = cy - e.y, vz = cz - e.z;
+            const double d2 = (vx * vx + vy * vy) + vz * vz;
+            const double cs = (vx * nx + vy * ny) + vz * nz;
+            const double dist = sqrt(d2);
+            const double w = (cs / dist) * (rr / d2);
+            const double L = a.init_state ? 0.0 : a.state[i];
+            const double x = ((L + e.t) + dist / len) / a.bin_len;
+            binned = x >= 0 && x < (double)a.n_bins;
+            if (binned) {
+                bin = (int)floor(x);
+                const double* al = a.alpha ? a.alpha + (size_t)e.poly_id * (size_t)B : nullptr;
+#pragma unroll
+                for (int b = 0; b < kMaxBands; ++b) {
+                    if (b < B) {
+                        const double E = a.init_state ? 1.0 : a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i];
+                        const double Ea = al ? E * (1.0 - al[b]) : E;
+                        double v = ((Ea * sig[b]) * w) * a.scale;
+                        if (!(v > 0)) v = 0;
+                        v = v < 9223372036854775808.0 ? v : 9223372036854775808.0;     // min(q, 2^63)
+                        q[b] = (unsigned long long)rint(v);
+                    }
+                }
+            }
+        }
+        const unsigned long long dm = __ballot(vis), bm = __ballot(binned);
+        if (lane == 0) {
+            if (bm) atomicAdd(&a.det[2 * k], (unsigned long long)__popcll(bm));
+            if (dm & ~bm) atomicAdd(&a.det[2 * k + 1], (unsigned long long)__popcll(dm & ~bm));
+        }
+        if (binned) {                                                   // per lane: rain's bins are spread, see above
+            unsigned long long* const row = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B;
+            for (int b = 0; b < B; ++b) atomicAdd(&row[b], q[b]);
+        }
+    }
+    // ---- emit: receiver k_emit's query
+    if (a.k_emit >= 0 && in) {
+        const int k = a.k_emit;
+        bool elig = false;
+        if (part) {
+            const double cx = a.rcv[4 * k + 0], cy = a.rcv[4 * k + 1], cz = a.rcv[4 * k + 2], rr = a.rcv[4 * k + 3];
+            const double vx = cx - e.x, vy = cy - e.y, vz = cz - e.z;
+            const double d2 = (vx * vx + vy * vy) + vz * vz;
+            const double cs = (vx * nx + vy * ny) + vz * nz;
+            elig = d2 > rr && cs > 0;
+            if (elig) {
+                RayRec s;
+                s.x = e.x; s.y = e.y; s.z = e.z;
+                s.dx = vx; s.dy = vy; s.dz = vz;
+                a.srays[i] = s;
+                a.stmax[i] = 1.0;
+            }
+        }
+        a.sexcl[i] = elig ? e.poly_id : -2;
+    }
 }

@@ -118,6 +118,7 @@ struct DeviceModule {
     hipFunction_t kdtree = nullptr, kdtree_count = nullptr;
     hipFunction_t reflect = nullptr, occlusion = nullptr;
     hipFunction_t receive_reflect = nullptr, receive_scatter = nullptr;    // receive.hip: hare_receive_reflect, hare_receive_scatter
+    hipFunction_t receive_scatter_rain = nullptr, rain_step = nullptr;     // receive.hip: diffuse rain (hare_receive_scatter_rain, hare_rain_step)
     hipFunction_t voxel_occl_tri = nullptr, voxel_occl_quad = nullptr, voxel_occl_tri_g = nullptr, voxel_occl_quad_g = nullptr, octree_occl = nullptr, octree_occl_any = nullptr;
     hipFunction_t events_pack_slim = nullptr;
     hipFunction_t block_occ = nullptr;                                     // build_kernels.hip: hare_block_occ
@@ -240,7 +241,8 @@ struct Scene {
         void* ctr = nullptr;            // hare_counters per cast (+ one word for the packed count)
         void* state = nullptr;          // hare_receive_batch: (1 + B) x n doubles, the histogram and the detections
         void* hist = nullptr;
-        size_t state_cap = 0, hist_cap = 0;     // bytes
+        void* rain = nullptr;           // hare_receive_batch with HARE_RECEIVE_DIFFUSE_RAIN: the loop's work array with the rain's scratch
+        size_t state_cap = 0, hist_cap = 0, rain_cap = 0;     // bytes
         int64_t cap = 0;
         int32_t ctr_cap = 0;
         hipStream_t copy_st = nullptr;
@@ -313,12 +315,23 @@ struct ShootExtra {
     const uint32_t* blocks = nullptr;
     const uint32_t* blk_words = nullptr;
 };
+// HARE_RECEIVE_DIFFUSE_RAIN: the rain's scratch, behind the loop's 2 n int32 in a receive call's work array (receive.cpp: rain_work;
+// HARE_RECEIVE_RAIN_WORK_BYTES(n) in all)
+struct RainWork {
+    RayRec* rays = nullptr;     // n shadow rays
+    double* tmax = nullptr;     // n t_max
+    int32_t* excl = nullptr;    // n poly_origin1 (-2: no query)
+    int32_t* occ = nullptr;     // n occlusion flags
+    int32_t* flag = nullptr;    // n suppression flags (ReceiveArgs::rain_flag)
+};
+RainWork rain_work(void* d_work, int64_t n);
 // rcv non-null (hare_receive_*): always a launch per cast, hare_receive_reflect (hare_receive_scatter where rcv->sigma is set) behind every
 // cast (the last included) instead of hare_reflect;
-// rcv supplies the receivers, state, histogram and switches, the loop fills in the rest per cast
+// rcv supplies the receivers, state, histogram and switches, the loop fills in the rest per cast.  rain non-null (with rcv->sigma and
+// rcv->rain_flag): diffuse rain before the receive kernel of every cast but the last, hare_receive_scatter_rain in hare_receive_scatter's place
 int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, void* d_rays, const void* d_e1, const void* d_e2,
                        int32_t casts, uint32_t flags, void* d_work, void* d_all, void* d_last, void* d_ctr, void* d_ctr_casts, hipStream_t st,
-                       const ReceiveArgs* rcv = nullptr);
+                       const ReceiveArgs* rcv = nullptr, const RainWork* rain = nullptr);
 uint32_t sanitize_flags(const Scene& s, uint32_t flags);
 int dev_free(const HipApi* H, void*& p);
 void free_bounce_buffers(const HipApi* H, Scene& s);          // bounce.cpp

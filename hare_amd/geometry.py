@@ -400,23 +400,24 @@ class Spatial_Partition:
         return self.get_option("bands:%d" % int(top_index))          # the scene's own record, whoever set the table
 
     def Receive_batch(self, rays, bounces: int, n_bins: int, bin_len: float, energy=None, frac_bits: int = 40, top_index: int = 0,
-                      poly_origin1=None, poly_origin2=None, out=None):
+                      poly_origin1=None, poly_origin2=None, out=None, rain: bool = False):
         """The bounce loop with the receiver step between its casts, from host buffers (hare_receive_batch).
         energy: None (every ray starts at L = 0, E = 1) or the state [1 + B, n] (row 0: L, rows 1..B: E).
         Returns (hist [K, n_bins, B] uint64, hist * 2^-frac_bits as float64, detections [K, 2] uint64, final state [1 + B, n],
-        counters).  out (optional): the caller's uint64 histogram array [K, n_bins, B], as in Shoot_batch."""
+        counters).  out (optional): the caller's uint64 histogram array [K, n_bins, B], as in Shoot_batch.  rain: diffuse rain
+        (HARE_RECEIVE_DIFFUSE_RAIN) where the topology has a scattering table."""
         return Spatial_Partition._receive([self], rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1,
-                                          poly_origin2, out)
+                                          poly_origin2, out, rain)
 
     @staticmethod
     def Receive_batch_sharded(partitions, rays, bounces: int, n_bins: int, bin_len: float, energy=None, frac_bits: int = 40,
-                              top_index: int = 0, poly_origin1=None, poly_origin2=None, out=None):
+                              top_index: int = 0, poly_origin1=None, poly_origin2=None, out=None, rain: bool = False):
         """hare_receive_batch_sharded: Receive_batch over several partitions (contiguous ray shards, histograms summed); byte-identical."""
         return Spatial_Partition._receive(list(partitions), rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1,
-                                          poly_origin2, out)
+                                          poly_origin2, out, rain)
 
     @staticmethod
-    def _receive(parts, rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1, poly_origin2, out):
+    def _receive(parts, rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1, poly_origin2, out, rain=False):
         if not parts or any(p._kind != parts[0]._kind for p in parts):
             raise ValueError("need one or more partitions of the same kind")
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
@@ -436,22 +437,31 @@ class Spatial_Partition:
         det = np.zeros((max(K, 0), 2), np.uint64)
         state_out = np.empty((1 + B, n), np.float64)
         ctr = capi.Counters()
+        flags = capi.RECEIVE_DIFFUSE_RAIN if rain else 0
         if len(parts) == 1:
-            rc = lib.hare_receive_batch(parts[0]._h, parts[0]._kind, int(top_index), n, ptr(rays), ptr(e1), ptr(e2), int(bounces), 0, nb,
+            rc = lib.hare_receive_batch(parts[0]._h, parts[0]._kind, int(top_index), n, ptr(rays), ptr(e1), ptr(e2), int(bounces), flags, nb,
                                         float(bin_len), int(frac_bits), ptr(state_in), ptr(state_out), ptr(hist), ptr(det), C.addressof(ctr))
         else:
             handles = (C.c_void_p * len(parts))(*[p._h for p in parts])
             rc = lib.hare_receive_batch_sharded(handles, len(parts), parts[0]._kind, int(top_index), n, ptr(rays), ptr(e1), ptr(e2),
-                                                int(bounces), 0, nb, float(bin_len), int(frac_bits), ptr(state_in), ptr(state_out),
+                                                int(bounces), flags, nb, float(bin_len), int(frac_bits), ptr(state_in), ptr(state_out),
                                                 ptr(hist), ptr(det), C.addressof(ctr))
         check(rc)
         return hist, hist.astype(np.float64) * 2.0 ** -int(frac_bits), det, state_out, ctr.as_dict()
 
+    @staticmethod
+    def receive_work_bytes(n: int, rain: bool = False) -> int:
+        """Bytes of receive_device's d_work for n rays: 2 n int32, or HARE_RECEIVE_RAIN_WORK_BYTES(n) with rain."""
+        return 80 * int(n) + 256 if rain else 8 * int(n)
+
     def receive_device(self, n: int, d_rays: int, bounces: int, n_bins: int, bin_len: float, frac_bits: int, d_state: int, d_work: int,
                        d_events_last: int, d_hist: int, d_detections: int, top_index: int = 0, d_excl1: int = 0, d_excl2: int = 0,
-                       d_counters: int = 0, stream: int = 0, flags: int = 0):
+                       d_counters: int = 0, stream: int = 0, flags: int = 0, rain: bool = False):
         """hare_receive_device on raw device addresses (e.g. torch.Tensor.data_ptr()) + a hipStream_t: d_state (1 + B) x n doubles is read
-        and overwritten, d_hist (K x n_bins x B uint64) and d_detections (2 K uint64) are accumulated into.  Stream-ordered."""
+        and overwritten, d_hist (K x n_bins x B uint64) and d_detections (2 K uint64) are accumulated into.  Stream-ordered.  rain: diffuse
+        rain (HARE_RECEIVE_DIFFUSE_RAIN); d_work then holds receive_work_bytes(n, rain=True) bytes."""
+        if rain:
+            flags |= capi.RECEIVE_DIFFUSE_RAIN
         check(lib.hare_receive_device(self._h, self._kind, int(top_index), int(n), d_rays or None, d_excl1 or None, d_excl2 or None,
                                       int(bounces), int(flags), int(n_bins), float(bin_len), int(frac_bits), d_state or None, d_work or None,
                                       d_events_last or None, d_hist or None, d_detections or None, d_counters or None, stream or None))

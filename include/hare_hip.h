@@ -80,6 +80,7 @@ extern "C" {
                                        /* the REFERENCE algorithm's work with a diagnostic kernel.)  HARE_E_UNSUPPORTED for a batch another        */
                                        /* kernel would serve.  No reference counterpart                                                            */
 #define HARE_SHOOT_BOUNCE_LOOP 32u     /* hare_shoot_kernel_name only: name the kernel hare_bounce_device (<= 16 casts) launches for n rays           */
+#define HARE_RECEIVE_DIFFUSE_RAIN 128u /* hare_receive_device / _batch / _batch_sharded only: diffuse rain ("receivers", "Diffuse rain", below)    */
 
 /* Hare.Geometry.Ray (Hare_Geometry_Primitives.cs:393-429): origin + direction.  Ray_ID/ThreadID
  * only serve the reference's mailbox pool and are not needed here. 48 bytes. */
@@ -490,6 +491,34 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * Every call restarts c at 0: a device caller that splits one burst over several calls varies "scatter_seed" from call to call, or the
  * calls draw the same numbers.
  *
+ * Diffuse rain (flag HARE_RECEIVE_DIFFUSE_RAIN; Heinz's diffuse rain, a form of next-event estimation).  Opt-in per call, and only on a
+ * topology with a scattering table: without one the flag changes nothing.  At every hit that may go diffuse, the scattered share of the
+ * energy goes straight to each receiver the hit point sees.  A ray takes part in cast c when it hit in cast c, c < bounces - 1 (it will be
+ * reflected) and p > 0 (p as above).  Its rain comes after the receiver step and the absorption update, before the choice, with
+ * x = X_Point, Ea[b] = E[b] after absorption, sg = sigma[Poly_id], n' the side normal above, len = sqrt((dx*dx + dy*dy) + dz*dz) of the
+ * incoming direction, L' = L + e.t and rr the stored r*r; for each receiver k in ascending order, FP64, no contraction:
+ *
+ *   vx = cx - x.x; vy = cy - x.y; vz = cz - x.z
+ *   d2 = (vx*vx + vy*vy) + vz*vz;  cs = (vx*n'x + vy*n'y) + vz*n'z
+ *   eligible  iff  d2 > rr && cs > 0
+ *   occluded  = the hare_occluded predicate on the shadow ray (origin x, direction v, poly_origin1 = Poly_id, t_max = 1.0):
+ *               the closest hit has t < 1.0
+ *   if eligible && !occluded:
+ *     dist = sqrt(d2);  w = (cs / dist) * (rr / d2)
+ *     xb   = (L' + dist / len) / bin_len                binned as in the receiver step
+ *     q_b  = ((Ea[b] * sg[b]) * w) * 2^frac_bits        0 unless q_b > 0; min(q_b, 2^63); rint -> uint64
+ *     hist[(k*n_bins + bin)*B + b] += q_b;  detections[2k] += 1 if binned, detections[2k+1] += 1 otherwise
+ *
+ * w is the sphere's projected solid angle over pi, the chance that a cosine-distributed direction from x passes through it.  It is exact
+ * when the sphere lies wholly in front of the polygon's plane; for a sphere the plane cuts (near the horizon) it is an approximation.
+ * Visibility is tested to the center only.  Suppression: a ray whose reflection in the previous cast was diffuse skips the receiver step
+ * in this cast (no add, no detection) -- the rain has accounted for that segment.  Specular segments, and cast 0, detect as before.  The
+ * flag is kept per ray in the rain's scratch and cleared at the start of every call; as the last cast of a call is never reflected, no
+ * diffuse segment crosses from one call into the next.  Rain changes deposits only: the draws, choices, weights, directions, the final
+ * state and rays are those of the call without it.  In a convex room whose receivers are clear of every wall plane by more than r, the
+ * expected histogram total per band is the same with and without rain (the diffuse segment's hit probability there is exactly w); its
+ * spread is smaller.  Cost: each reflecting cast runs K flags-only occlusion queries of n rays.
+ *
  * The histogram is fixed point in uint64: integer sums do not depend on the order of the adds, so the result is bit-identical from
  * run to run, between the one-device and the sharded call, and against a restatement on the host.  (r*r is formed once, when the
  * receivers are set: the same FP64 product.)
@@ -514,18 +543,21 @@ HARE_API int hare_scene_set_scattering(hare_scene *s, int32_t top_index, int32_t
  *   d_rays, d_excl1, d_excl2, d_work (2 n int32), d_events_last   as in hare_bounce_device
  *   d_state        (1 + B) planes of n doubles: plane 0 is L, planes 1..B are E.  Read and overwritten
  *   d_hist         K x n_bins x B uint64, ACCUMULATED;  d_detections: 2 K uint64, ACCUMULATED
- *   d_counters     nullable: totals, ACCUMULATED (as hare_bounce_device's)
- *   flags          HARE_SHOOT_COUNT_WORK / HARE_SHOOT_SIMPLE_KERNEL only
+ *   d_counters     nullable: totals, ACCUMULATED (as hare_bounce_device's; the rain's occlusion queries are not counted)
+ *   flags          HARE_SHOOT_COUNT_WORK / HARE_SHOOT_SIMPLE_KERNEL (the casts) and HARE_RECEIVE_DIFFUSE_RAIN; other bits are ignored.  With
+ *                  HARE_RECEIVE_DIFFUSE_RAIN d_work holds HARE_RECEIVE_RAIN_WORK_BYTES(n) bytes: the 2 n int32, then the rain's scratch
  * Arguments are checked before anything runs (HARE_E_INVALID): kind, top_index, 0 <= n <= 2^31 - 256, 1 <= bounces <= 4096,
  * n_bins >= 1, bin_len finite and > 0, 0 <= frac_bits <= 62, K x n_bins x B <= 2^27, null or overlapping buffers.  Then
  * HARE_E_NODEVICE, then HARE_E_STATE (no receivers set; partition not built). */
+#define HARE_RECEIVE_RAIN_WORK_BYTES(n) (80 * (int64_t)(n) + 256)
 HARE_API int hare_receive_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, void *d_rays, const void *d_excl1,
                                  const void *d_excl2, int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len,
                                  int32_t frac_bits, void *d_state, void *d_work, void *d_events_last, void *d_hist,
                                  void *d_detections, void *d_counters, void *stream);
 /* The same from host buffers (threading and staging as hare_bounce_batch's last-cast-only path: one enqueue, one synchronisation; no
  * events are downloaded).  state_in nullable (every ray starts at L = 0, E = 1); state_out nullable ((1 + B) x n, as d_state).
- * hist (K x n_bins x B) and detections (2 K) are WRITTEN, not accumulated; ctr nullable: counters summed over the casts. */
+ * hist (K x n_bins x B) and detections (2 K) are WRITTEN, not accumulated; ctr nullable: counters summed over the casts.  flags as
+ * hare_receive_device's (the call sizes the rain's scratch itself). */
 HARE_API int hare_receive_batch(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, const hare_ray *rays,
                                 const int32_t *excl1, const int32_t *excl2, int32_t bounces, uint32_t flags, int32_t n_bins,
                                 double bin_len, int32_t frac_bits, const double *state_in, double *state_out, uint64_t *hist,

@@ -6,8 +6,11 @@ has without the feature: Bounce_batch(all_casts=True) and the numpy restatement 
 With --scatter SIGMA (K = 8, B = 8 only), the same loop again with a scattering table of SIGMA on every polygon and band (hare_receive_scatter
 in place of hare_receive_reflect; SIGMA 0 runs that kernel on exactly the rays the specular loop has); run it under rocprofv3 --kernel-trace
 for the two kernels' per-cast times.
+With --rain (B = 8, K = 1 and 8; SIGMA from --scatter, default 0.3), the scattering loop with and without diffuse rain
+(HARE_RECEIVE_DIFFUSE_RAIN), and a noise figure: the relative spread, over 8 scatter seeds, of the energy the receivers get from 60 m of
+path on (summed over receivers and bands), with rain and without.
 Prints ONE JSON line.  usage: python tools/receiver_rate.py [hall|cathedral] [--rays N] [--bounces B] [--reps R] [--host] [--quick]
-                                                          [--scatter SIGMA]"""
+                                                          [--scatter SIGMA] [--rain]"""
 import argparse
 import json
 import os
@@ -29,7 +32,10 @@ ap.add_argument("--host", action="store_true", help="also time Bounce_batch(all_
 ap.add_argument("--quick", action="store_true", help="K = 8, B = 8 only (a profiling run)")
 ap.add_argument("--scatter", type=float, default=None, metavar="SIGMA",
                 help="K = 8, B = 8 only, and the loop again with a scattering table of SIGMA everywhere (scene option scatter_seed 1)")
+ap.add_argument("--rain", action="store_true", help="K = 1 and 8, B = 8: the scattering loop with and without diffuse rain, and its noise")
 a = ap.parse_args()
+if a.rain and a.scatter is None:
+    a.scatter = 0.3
 if not torch.cuda.is_available():
     sys.exit("receiver_rate: no GPU -- nothing to measure")
 
@@ -74,7 +80,8 @@ def bounce():
 ms_bounce = timed(bounce, a.reps)
 out = {"scene": a.scene, "domain": D, "rays": n, "bounces": nb, "n_bins": N_BINS, "bounce_ms": round(ms_bounce, 3),
        "bounce_Mcasts_s": round(n * nb / ms_bounce / 1e3, 1), "receive": []}
-cases = [(8, 8)] if (a.quick or a.scatter is not None) else [(K, B) for K in (1, 8, 64) for B in (1, 8)]
+cases = [(1, 8), (8, 8)] if a.rain else ([(8, 8)] if (a.quick or a.scatter is not None) else [(K, B) for K in (1, 8, 64) for B in (1, 8)])
+d_work_rain = torch.zeros(H.Voxel_Grid.receive_work_bytes(n, rain=True), dtype=torch.uint8, device="cuda") if a.rain else None
 for K, B in cases:
     c, r = receivers(K)
     g.set_receivers(c, r)
@@ -84,11 +91,11 @@ for K, B in cases:
     d_hist = torch.zeros(K * N_BINS * B, dtype=torch.int64, device="cuda")
     d_det = torch.zeros(2 * K, dtype=torch.int64, device="cuda")
 
-    def receive():
-        g.receive_device(n, d_rays.data_ptr(), nb, N_BINS, BIN_LEN, FRAC, d_state.data_ptr(), d_work.data_ptr(), d_last.data_ptr(),
-                         d_hist.data_ptr(), d_det.data_ptr(), stream=st)
+    def receive(rain=False):
+        g.receive_device(n, d_rays.data_ptr(), nb, N_BINS, BIN_LEN, FRAC, d_state.data_ptr(), (d_work_rain if rain else d_work).data_ptr(),
+                         d_last.data_ptr(), d_hist.data_ptr(), d_det.data_ptr(), stream=st, rain=rain)
     row = {"K": K, "B": B}
-    for agg in ((1, 0) if K == 8 and B == 8 and a.scatter is None else (1,)):
+    for agg in ((1, 0) if K == 8 and B == 8 and a.scatter is None and not a.rain else (1,)):
         g.set_option("receive_aggregate", agg)
         d_hist.zero_(); d_det.zero_()
         d_state.copy_(init)
@@ -112,6 +119,21 @@ for K, B in cases:
         d_hist.zero_(); d_det.zero_(); d_rays.copy_(d_src); d_state.copy_(init)
         receive(); torch.cuda.synchronize()
         row["scatter_detections"] = int(d_det.cpu().numpy().sum())
+        if a.rain:                                                       # the same loop with diffuse rain
+            ms = timed(lambda: (d_state.copy_(init), receive(True)), a.reps)
+            row["rain_ms"] = round(ms - ms_copy, 3)
+            row["rain_over_scatter"] = round((ms - ms_copy) / row["scatter_ms"], 2)
+            late = int(60.0 / BIN_LEN)
+            for rain in (False, True):
+                e = []
+                for seed in range(8):
+                    g.set_option("scatter_seed", 100 + seed)
+                    d_hist.zero_(); d_det.zero_(); d_rays.copy_(d_src); d_state.copy_(init)
+                    receive(rain); torch.cuda.synchronize()
+                    h = d_hist.cpu().numpy().view(np.uint64).reshape(K, N_BINS, B)
+                    e.append(float(h[:, late:, :].astype(np.float64).sum()) * 2.0 ** -FRAC)
+                row["late_spread_rain" if rain else "late_spread"] = round(float(np.std(e, ddof=1) / np.mean(e)), 5)
+            g.set_option("scatter_seed", 1)
         g.set_scattering(None)
     out["receive"].append(row)
     print(json.dumps(row), file=sys.stderr, flush=True)
