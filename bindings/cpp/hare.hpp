@@ -154,7 +154,8 @@ public:
     // receivers (include/hare_hip.h, "receivers"): K spheres, an absorption table per topology, and the bounce loop with the receiver
     // step between its casts.  hist: K x n_bins x B fixed-point sums (scale 2^-frac_bits), B = Bands(top_index); detections: 2 K;
     // state: (1 + B) x rays.size() (L, then E per band); rain: diffuse rain (HARE_RECEIVE_DIFFUSE_RAIN).  Returns the hits over all casts.  Sizes are checked here: the library reads and
-    // writes as many values as the scene says, whatever the vectors hold.
+    // writes as many values as the scene says, whatever the vectors hold.  directional (HARE_RECEIVE_DIRECTIONAL): hist is K x n_bins x B x 4,
+    // channel innermost: W (the omni word), then X, Y, Z as int64 in two's complement (positive for sound arriving from +x, +y, +z).
     void SetReceivers(const std::vector<double>& centers, const std::vector<double>& radii)
     {
         if (centers.size() != 3 * radii.size()) throw std::invalid_argument("SetReceivers: centers must hold 3 x radii.size() values");
@@ -180,17 +181,17 @@ public:
     int64_t Bands(int top_index) const { return GetOption(("bands:" + std::to_string(top_index)).c_str()); }
     uint64_t Receive(const std::vector<hare_ray>& rays, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
                      std::vector<uint64_t>& hist, std::vector<uint64_t>& detections, const std::vector<double>* state_in = nullptr,
-                     std::vector<double>* state_out = nullptr, bool rain = false)
+                     std::vector<double>* state_out = nullptr, bool rain = false, bool directional = false)
     {
         const int64_t K = GetOption("receivers"), B = Bands(top_index);
         const size_t n_state = (size_t)(1 + B) * rays.size();
         if (state_in && state_in->size() != n_state) throw std::invalid_argument("Receive: state_in must hold (1 + B) x rays.size() values");
-        hist.assign((size_t)(K * (n_bins > 0 ? n_bins : 0) * B), 0);
+        hist.assign((size_t)(K * (n_bins > 0 ? n_bins : 0) * B * (directional ? 4 : 1)), 0);
         detections.assign((size_t)(2 * K), 0);
         if (state_out) state_out->assign(n_state, 0.0);
         hare_counters c{};
         check(hare_receive_batch(scene_, kind_, top_index, (int64_t)rays.size(), rays.data(), nullptr, nullptr, bounces,
-                                 rain ? HARE_RECEIVE_DIFFUSE_RAIN : 0u, n_bins, bin_len,
+                                 (rain ? HARE_RECEIVE_DIFFUSE_RAIN : 0u) | (directional ? HARE_RECEIVE_DIRECTIONAL : 0u), n_bins, bin_len,
                                  frac_bits, state_in ? state_in->data() : nullptr, state_out ? state_out->data() : nullptr, hist.data(),
                                  detections.data(), &c));
         return c.hits;

@@ -302,6 +302,26 @@ namespace Hare
                 return (long)ctr.hits;
             }
 
+            /// <summary>Receive with directional channels on request (HARE_RECEIVE_DIRECTIONAL; include/hare_hip.h, "Directional"): hist then
+            /// holds K x n_bins x B x 4 words, channel innermost: W (the omni word of the other overloads), then X, Y, Z, which are
+            /// two's-complement sums (read them as unchecked((long)word)), positive for sound arriving from +x, +y, +z in world axes.
+            /// frac_bits must leave a sign bit of headroom.  Combines with rain.</summary>
+            public long Receive(hare_ray[] rays, int top_index, int bounces, int n_bins, double bin_len, int frac_bits, ulong[] hist,
+                                ulong[] detections, double[] state, bool state_in, bool rain, bool directional)
+            {
+                if (bounces < 1) throw new ArgumentException("bounces must be at least 1");
+                long K = GetOption("receivers"), B = Bands(top_index), C = directional ? 4 : 1;
+                if (hist == null || hist.LongLength < K * n_bins * B * C) throw new ArgumentException("hist must hold receivers x n_bins x Bands(top_index) values (x 4 when directional)");
+                if (detections == null || detections.LongLength < 2 * K) throw new ArgumentException("detections must hold 2 x receivers values");
+                if (state != null && state.LongLength < (1 + B) * rays.LongLength) throw new ArgumentException("state must hold (1 + Bands(top_index)) x rays.Length values");
+                if (state_in && state == null) throw new ArgumentException("state_in needs a state array");
+                hare_counters ctr;
+                uint flags = (rain ? HareHip.HARE_RECEIVE_DIFFUSE_RAIN : 0u) | (directional ? HareHip.HARE_RECEIVE_DIRECTIONAL : 0u);
+                HareHip.Check(HareHip.hare_receive_batch_sharded(scenes, scenes.Length, Kind, top_index, rays.LongLength, rays, null, null, bounces, flags,
+                                                                 n_bins, bin_len, frac_bits, state_in ? state : null, state, hist, detections, out ctr));
+                return (long)ctr.hits;
+            }
+
             /// <summary>The same on managed objects: result[b][i] is the X_Event of ray i in cast b (X_Event() once the ray has
             /// left the model).  rays[] is not modified.</summary>
             public X_Event[][] Bounce(Ray[] rays, int top_index, int bounces)

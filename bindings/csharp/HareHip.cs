@@ -100,6 +100,7 @@ namespace Hare
             public const uint HARE_SHOOT_BOUNCE_LOOP = 32;   // hare_shoot_kernel_name only
             public const uint HARE_SHOOT_SLIM_EVENTS = 16;   // host-buffer batches: hare_slim_event records come back (16 B per ray, not 56)
             public const uint HARE_RECEIVE_DIFFUSE_RAIN = 128;   // receive calls: diffuse rain where the topology has a scattering table
+            public const uint HARE_RECEIVE_DIRECTIONAL = 256;    // receive calls: four channels per histogram word (W, X, Y, Z)
 
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr hare_last_error();
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int hare_device_count(out int count);

@@ -19,6 +19,7 @@ KIND_VOXEL, KIND_OCTREE, KIND_KDTREE = 0, 1, 2
 SHOOT_WRITEBACK_ORIGIN, SHOOT_COUNT_WORK, SHOOT_SIMPLE_KERNEL, SHOOT_RETIRED_RAYS, SHOOT_SLIM_EVENTS, SHOOT_BOUNCE_LOOP = 1, 2, 4, 8, 16, 32
 SHOOT_COUNT_OWN = 64
 RECEIVE_DIFFUSE_RAIN = 128          # hare_receive_*: diffuse rain (include/hare_hip.h)
+RECEIVE_DIRECTIONAL = 256           # hare_receive_*: four channels per histogram word, W X Y Z (include/hare_hip.h)
 
 RAY_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("dx", "<f8"), ("dy", "<f8"), ("dz", "<f8")])
 XEVENT_DTYPE = np.dtype(

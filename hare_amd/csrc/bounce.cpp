@@ -229,6 +229,7 @@ struct ReceiveJob {
     uint64_t* det = nullptr;
     int64_t ray_base = 0;      // this shard's first ray in the whole batch (the scattering RNG's global ray index)
     bool rain = false;         // HARE_RECEIVE_DIFFUSE_RAIN
+    bool directional = false;  // HARE_RECEIVE_DIRECTIONAL: four channels per histogram word
 };
 
 // The receive loop for one scene: rays, exclusions and state go up, the loop is enqueued ONCE (a launch per cast, hare_receive_reflect
@@ -242,7 +243,7 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
     const int32_t B = scene_bands(s, top);
     const size_t K = s.rcv.size() / 4;
     const size_t state_bytes = (size_t)n * (size_t)(1 + B) * sizeof(double);
-    const size_t hist_words = K * (size_t)job.n_bins * (size_t)B, hist_bytes = (hist_words + 2 * K) * sizeof(uint64_t);
+    const size_t hist_words = K * (size_t)job.n_bins * (size_t)B * (job.directional ? 4u : 1u), hist_bytes = (hist_words + 2 * K) * sizeof(uint64_t);
     if (state_bytes > b.state_cap) {
         dev_free(H, b.state);
         b.state_cap = 0;
@@ -287,7 +288,7 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
         ra.rain_flag = rw.flag;
     }
     if (int rc = bounce_device_impl(s, H, kind, top, n, b.rays[0], excl1 ? b.excl[0] : nullptr, excl2 ? b.excl2 : nullptr, bounces, flags, work,
-                                    nullptr, b.ev[0], nullptr, b.ctr, st, &ra, rain ? &rw : nullptr))
+                                    nullptr, b.ev[0], nullptr, b.ctr, st, &ra, rain ? &rw : nullptr, job.directional))
         return rc;
     HIP_TRY(H->MemcpyAsync(job.hist, d_hist, hist_words * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(H->MemcpyAsync(job.det, d_det, 2 * K * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -492,7 +493,7 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
             return HARE_E_INVALID;
         }
     hare_scene* const s0 = scenes[0];
-    if (int rc = receive_check_args(who, *s0, kind, top_index, n, bounces, n_bins, bin_len, frac_bits)) return rc;
+    if (int rc = receive_check_args(who, *s0, flags, kind, top_index, n, bounces, n_bins, bin_len, frac_bits)) return rc;
     if ((n > 0 && !rays) || !hist || !detections) {
         set_error(std::string(who) + ": null rays, histogram or detections");
         return HARE_E_INVALID;
@@ -515,7 +516,8 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
     }
     GUARD_BEGIN
     const int G = n_scenes;
-    const size_t K = s0->rcv.size() / 4, hist_words = K * (size_t)n_bins * (size_t)scene_bands(*s0, top_index);
+    const bool directional = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
+    const size_t K = s0->rcv.size() / 4, hist_words = K * (size_t)n_bins * (size_t)scene_bands(*s0, top_index) * (directional ? 4u : 1u);
     memset(hist, 0, hist_words * sizeof(uint64_t));
     memset(detections, 0, 2 * K * sizeof(uint64_t));
     if (ctr) memset(ctr, 0, sizeof *ctr);
@@ -541,6 +543,7 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
         job.det = k == 0 ? detections : dets[(size_t)k].data();
         job.ray_base = lo;
         job.rain = (flags & HARE_RECEIVE_DIFFUSE_RAIN) != 0;
+        job.directional = directional;
         try {
             rcs[(size_t)k] = bounce_one(scenes[k], kind, top_index, hi - lo, rays ? rays + lo : nullptr, excl1 ? excl1 + lo : nullptr,
                                         excl2 ? excl2 + lo : nullptr, bounces, flags, nullptr, n, nullptr, pcs[(size_t)k].data(), &job);
@@ -566,7 +569,7 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
             set_error(G == 1 ? errs[0] : "shard " + std::to_string(k) + ": " + errs[(size_t)k]);
             return rcs[(size_t)k];
         }
-    for (int k = 1; k < G; ++k) {                 // integer sums (mod 2^64): the order of the shards does not matter
+    for (int k = 1; k < G; ++k) {                 // integer sums (mod 2^64, so right for the signed channels too): the order of the shards does not matter
         for (size_t w = 0; w < hist_words; ++w) hist[w] += hists[(size_t)k][w];
         for (size_t w = 0; w < 2 * K; ++w) detections[w] += dets[(size_t)k][w];
     }

@@ -98,6 +98,10 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_receive_scatter", &m->receive_scatter},
         {"hare_receive_scatter_rain", &m->receive_scatter_rain},
         {"hare_rain_step", &m->rain_step},
+        {"hare_receive_reflect_dir", &m->receive_reflect_dir},
+        {"hare_receive_scatter_dir", &m->receive_scatter_dir},
+        {"hare_receive_scatter_rain_dir", &m->receive_scatter_rain_dir},
+        {"hare_rain_step_dir", &m->rain_step_dir},
         {"hare_occlusion", &m->occlusion},
         {"hare_voxel_occl_tri", &m->voxel_occl_tri},
         {"hare_voxel_occl_quad", &m->voxel_occl_quad},

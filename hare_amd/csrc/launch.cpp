@@ -151,6 +151,9 @@ constexpr uint32_t kPublicFlags = HARE_SHOOT_WRITEBACK_ORIGIN | HARE_SHOOT_COUNT
 static_assert((kPublicFlags & HARE_SHOOT_BOUNCE_LOOP) == 0, "the kernel-name query bit never reaches a kernel");
 static_assert((HARE_RECEIVE_DIFFUSE_RAIN & (kPublicFlags | HARE_SHOOT_BOUNCE_LOOP | 0xF000u | kFlagAnyHit | SHOOT_RETIRED_SILENT)) == 0,
               "the receive calls' rain bit is a bit of its own");
+static_assert((HARE_RECEIVE_DIRECTIONAL & (kPublicFlags | HARE_SHOOT_BOUNCE_LOOP | HARE_RECEIVE_DIFFUSE_RAIN | 0xF000u | kFlagAnyHit | SHOOT_RETIRED_SILENT)) == 0 &&
+                  (HARE_RECEIVE_DIRECTIONAL & (HARE_RECEIVE_DIRECTIONAL - 1u)) == 0,
+              "the receive calls' directional bit is a bit of its own");
 uint32_t sanitize_flags(const Scene& s, uint32_t flags)
 {
     return flags & (kPublicFlags | (s.opt.dev ? 0xF000u : 0u));
@@ -457,7 +460,7 @@ static void fill_voxel_args(const Scene& s, int32_t top, VoxelArgs& g)
 //   d_ctr    nullable: totals, accumulated (rays = casts with a live ray);  d_ctr_casts: nullable, `casts` blocks, accumulated
 int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, void* d_rays, const void* d_e1, const void* d_e2,
                        int32_t casts, uint32_t flags, void* d_work, void* d_all, void* d_last, void* d_ctr, void* d_ctr_casts, hipStream_t st,
-                       const ReceiveArgs* rcv, const RainWork* rain)
+                       const ReceiveArgs* rcv, const RainWork* rain, bool directional)
 {
     if (n < 0 || casts < 1 || casts > 4096 || top < 0 || top >= (int32_t)s.topos.size()) {
         set_error("hare_bounce: bad n, bounces or top_index");
@@ -478,8 +481,13 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
     hare_xevent* const last = d_last ? (hare_xevent*)d_last : all + (size_t)(casts - 1) * (size_t)n;
     int32_t* const work = (int32_t*)d_work;
     if (rain && !(rcv && rcv->sigma && rcv->rain_flag)) rain = nullptr;
-    hipFunction_t const receive_fn = !rcv ? nullptr : (!rcv->sigma ? M.receive_reflect : (rain ? M.receive_scatter_rain : M.receive_scatter));
-    if (!M.reflect || !M.events_fill_miss || (rcv && !receive_fn) || (rain && !M.rain_step)) {
+    if (!rcv) directional = false;
+    // HARE_RECEIVE_DIRECTIONAL: the _dir kernels (four channels per histogram word) in place of each of the four
+    hipFunction_t const receive_fn = !rcv             ? nullptr
+                                     : directional ? (!rcv->sigma ? M.receive_reflect_dir : (rain ? M.receive_scatter_rain_dir : M.receive_scatter_dir))
+                                                   : (!rcv->sigma ? M.receive_reflect : (rain ? M.receive_scatter_rain : M.receive_scatter));
+    hipFunction_t const rain_fn = directional ? M.rain_step_dir : M.rain_step;
+    if (!M.reflect || !M.events_fill_miss || (rcv && !receive_fn) || (rain && !rain_fn)) {
         set_error("hare_bounce: bounce kernels missing from code object");
         return HARE_E_STATE;
     }
@@ -620,7 +628,7 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
                     g.k_dep = k - 1;
                     g.k_emit = k < ra.n_rcv ? k : -1;
                     void* ga[] = {&g};
-                    if (int rc = launch(H, M.rain_step, (unsigned)((n + 255) / 256), 256, 0, st, ga)) return fail(rc);
+                    if (int rc = launch(H, rain_fn, (unsigned)((n + 255) / 256), 256, 0, st, ga)) return fail(rc);
                     if (k == ra.n_rcv) break;
                     if (int rc = shoot_device_impl(s, H, kind, top, n, rain->rays, rain->excl, nullptr, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st,
                                                    rain->tmax, rain->occ))

@@ -73,7 +73,7 @@ int32_t scene_bands(const Scene& s, int32_t top)
 
 // Everything a receive call checks before anything runs (HARE_E_INVALID); K is the scene's receiver count (0: unset, counted as 1 here --
 // "no receivers" is HARE_E_STATE, after the device checks)
-int receive_check_args(const char* who, const Scene& s, int32_t kind, int32_t top, int64_t n, int32_t bounces, int32_t n_bins, double bin_len,
+int receive_check_args(const char* who, const Scene& s, uint32_t flags, int32_t kind, int32_t top, int64_t n, int32_t bounces, int32_t n_bins, double bin_len,
                        int32_t frac_bits)
 {
     auto bad = [&](const char* what) {
@@ -89,6 +89,8 @@ int receive_check_args(const char* who, const Scene& s, int32_t kind, int32_t to
     if (frac_bits < 0 || frac_bits > 62) return bad("frac_bits out of range (0 .. 62)");
     const int64_t K = std::max<int64_t>(1, (int64_t)(s.rcv.size() / 4));
     if (K * (int64_t)n_bins * (int64_t)scene_bands(s, top) > ((int64_t)1 << 27)) return bad("receivers x n_bins x bands exceeds 2^27");
+    if ((flags & HARE_RECEIVE_DIRECTIONAL) && K * (int64_t)n_bins * (int64_t)scene_bands(s, top) * 4 > ((int64_t)1 << 27))
+        return bad("receivers x n_bins x bands x 4 channels (HARE_RECEIVE_DIRECTIONAL) exceeds 2^27");
     return HARE_OK;
 }
 
@@ -315,10 +317,11 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
         set_error("null scene");
         return HARE_E_INVALID;
     }
-    if (int rc = receive_check_args("hare_receive_device", *s, kind, top_index, n, bounces, n_bins, bin_len, frac_bits)) return rc;
+    if (int rc = receive_check_args("hare_receive_device", *s, flags, kind, top_index, n, bounces, n_bins, bin_len, frac_bits)) return rc;
     const int64_t K = std::max<int64_t>(1, (int64_t)(s->rcv.size() / 4));
     const int32_t B = scene_bands(*s, top_index);
     const bool rain = (flags & HARE_RECEIVE_DIFFUSE_RAIN) != 0;
+    const bool directional = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;      // four channels per histogram word
     if (n > 0) {
         if (!d_rays || !d_state || !d_work || !d_events_last || !d_hist || !d_detections) {
             set_error("hare_receive_device: null rays / state / work array / events / histogram / detections");
@@ -329,7 +332,7 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
                             {d_state, (size_t)n * (size_t)(1 + B) * sizeof(double), true},
                             {d_work, rain ? (size_t)HARE_RECEIVE_RAIN_WORK_BYTES(n) : (size_t)n * 2 * sizeof(int32_t), true},
                             {d_events_last, (size_t)n * sizeof(hare_xevent), true},
-                            {d_hist, (size_t)K * (size_t)n_bins * (size_t)B * sizeof(uint64_t), true},
+                            {d_hist, (size_t)K * (size_t)n_bins * (size_t)B * (directional ? 4u : 1u) * sizeof(uint64_t), true},
                             {d_detections, (size_t)K * 2 * sizeof(uint64_t), true},
                             {d_counters, sizeof(hare_counters), true},
                             {d_excl1, (size_t)n * sizeof(int32_t), false},
@@ -362,7 +365,7 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
         ra.rain_flag = rw.flag;
     }
     return bounce_device_impl(*s, H, kind, top_index, n, d_rays, d_excl1, d_excl2, bounces, flags, d_work, nullptr, d_events_last, d_counters,
-                              nullptr, (hipStream_t)stream, &ra, ra.rain_flag ? &rw : nullptr);
+                              nullptr, (hipStream_t)stream, &ra, ra.rain_flag ? &rw : nullptr, directional);
     GUARD_END
 }
 

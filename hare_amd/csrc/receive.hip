@@ -1,4 +1,4 @@
-// receive.hip -- hare_receive_reflect / hare_receive_scatter / hare_receive_scatter_rain: the receiver step of the receive loop (include/hare_hip.h,
+// receive.hip -- hare_receive_reflect / hare_receive_scatter / hare_receive_scatter_rain (and their _dir forms): the receiver step of the receive loop (include/hare_hip.h,
 // "receivers"), #included from kernels.hip.  One body (receive_body), three kernels: scattering and rain are compile-time switches.  And
 // hare_rain_step, diffuse rain's emit and deposit (below).
 //
@@ -79,9 +79,47 @@ static __device__ __forceinline__ RayRec scatter_hit(double nx, double ny, doubl
     return o;
 }
 
+// ---- directional receivers (HARE_RECEIVE_DIRECTIONAL; the header's "receivers", "Directional"): four words per (receiver, bin, band),
+// channel innermost: W (the omni word, unchanged) and X, Y, Z, the add weighted by the unit vector towards where the sound came from, as
+// int64 in two's complement.  They are added with the same wrapping uint64 adds, so every sum stays an exact integer sum.
+// m_b of the header: the double that q_b is the rint of
+static __device__ __forceinline__ double dir_m(double v)
+{
+    if (!(v > 0)) v = 0;
+    return v < 9223372036854775808.0 ? v : 9223372036854775808.0;     // min(m, 2^63)
+}
+// s_i of the header as a two's-complement word: m * a_i, 0 for NaN, clamped to +-2^62, rint
+static __device__ __forceinline__ unsigned long long dir_q(double m, double ai)
+{
+    double v = m * ai;
+    if (!(v == v)) v = 0;
+    v = v > -4611686018427387904.0 ? v : -4611686018427387904.0;
+    v = v < 4611686018427387904.0 ? v : 4611686018427387904.0;
+    return (unsigned long long)(long long)rint(v);
+}
+// The wave's sums of four words per lane (W, X, Y, Z of one band) in 7 exchanges instead of 4 x 6: the first two steps halve what a lane
+// holds (lanes 32.. keep Y, Z and pass W, X on; then bit 4 of the lane picks one of the two), the last four are the plain butterfly.
+// Returns, in every lane, the wave's sum of channel lane >> 4.  Wrapping uint64 adds only: exact whatever the order.
+static __device__ __forceinline__ unsigned long long wave_sum4_u64(unsigned long long w, unsigned long long x, unsigned long long y,
+                                                                   unsigned long long z, int lane)
+{
+    const bool hi = (lane & 32) != 0, b4 = (lane & 16) != 0;
+    unsigned long long k0 = hi ? y : w, k1 = hi ? z : x;
+    k0 += __shfl_xor(hi ? w : y, 32, 64);
+    k1 += __shfl_xor(hi ? x : z, 32, 64);
+    unsigned long long v = (b4 ? k1 : k0) + __shfl_xor(b4 ? k0 : k1, 16, 64);
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
 // RAIN (hare_receive_scatter_rain, HARE_RECEIVE_DIFFUSE_RAIN): a ray whose reflection in the previous cast was diffuse (ReceiveArgs::rain_flag)
 // skips the receiver step -- hare_rain_step has deposited that segment -- and every reflected ray writes the flag after its choice.
-template <bool SCATTER, bool RAIN = false>
+// DIR (the _dir kernels, HARE_RECEIVE_DIRECTIONAL): four channels per histogram word.  The arrival vector is one per ray and cast; it costs a
+// sqrt and three divisions, so it is formed behind the first ballot that found a binned detection, not for every ray of every cast.  The
+// quantised words are formed inside the band loop (4 x 8 of them held per lane would be 64 VGPRs).  Aggregated, lanes 16 ch + b add the
+// 4 B contiguous words of a bin (at most 256 B) in one atomic instruction.
+template <bool SCATTER, bool RAIN = false, bool DIR = false>
 static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -127,6 +165,8 @@ static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
     if (__ballot(seen) != 0ull) {
         const double t_end = (live && e.hit) ? e.t : __builtin_inf();
         const double nb = (double)a.n_bins;
+        [[maybe_unused]] double ax = 0, ay = 0, az = 0;
+        [[maybe_unused]] bool have_a = false;                               // wave-uniform
         for (int k = 0; k < a.n_rcv; ++k) {
             const double cx = rcv[4 * k + 0], cy = rcv[4 * k + 1], cz = rcv[4 * k + 2], r2 = rcv[4 * k + 3];
             bool det = false, binned = false;
@@ -150,6 +190,50 @@ static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
                 if (dm & ~bm) atomicAdd(&a.det[2 * k + 1], (unsigned long long)__popcll(dm & ~bm));
             }
             if (bm == 0ull) continue;
+            if constexpr (DIR) {
+                if (!have_a) {
+                    have_a = true;
+                    if (seen) {
+                        const double len = sqrt((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
+                        ax = -(r.dx / len);
+                        ay = -(r.dy / len);
+                        az = -(r.dz / len);
+                    }
+                }
+                unsigned long long* const row = a.hist + (size_t)k * (size_t)a.n_bins * (size_t)B * 4;
+                if (!a.aggregate) {                                          // naive form (A/B): every detecting lane adds its own words
+                    if (binned)
+                        for (int b = 0; b < B; ++b) {
+                            const double m = dir_m(E[b] * a.scale);
+                            unsigned long long* const w = &row[((size_t)bin * B + b) * 4];
+                            atomicAdd(&w[0], (unsigned long long)rint(m));
+                            atomicAdd(&w[1], dir_q(m, ax));
+                            atomicAdd(&w[2], dir_q(m, ay));
+                            atomicAdd(&w[3], dir_q(m, az));
+                        }
+                    continue;
+                }
+                unsigned long long todo = bm;
+                while (todo) {                                               // one round per distinct bin among the wave's detections
+                    const int leader = __ffsll((long long)todo) - 1;
+                    const int lb = __shfl(bin, leader, 64);
+                    const bool mine = binned && bin == lb;
+                    todo &= ~__ballot(mine);
+                    unsigned long long mysum = 0;
+#pragma unroll
+                    for (int b = 0; b < kMaxBands; ++b) {
+                        if (b < B) {
+                            const double m = mine ? dir_m(E[b] * a.scale) : 0.0;     // m = 0 quantises to four zero words
+                            const unsigned long long sb =
+                                wave_sum4_u64((unsigned long long)rint(m), dir_q(m, ax), dir_q(m, ay), dir_q(m, az), lane);
+                            if ((lane & 15) == b) mysum = sb;
+                        }
+                    }
+                    // lane 16 ch + b holds channel ch of band b: 4 B contiguous 8-byte adds, one instruction
+                    if ((lane & 15) < B) atomicAdd(&row[((size_t)lb * B + (lane & 15)) * 4 + (lane >> 4)], mysum);
+                }
+                continue;
+            }
             unsigned long long q[kMaxBands];
 #pragma unroll
             for (int b = 0; b < kMaxBands; ++b) {
@@ -267,6 +351,21 @@ extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_rain(Rece
     receive_body<true, true>(a);
 }
 
+extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect_dir(ReceiveArgs a)
+{
+    receive_body<false, false, true>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_dir(ReceiveArgs a)
+{
+    receive_body<true, false, true>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_rain_dir(ReceiveArgs a)
+{
+    receive_body<true, true, true>(a);
+}
+
 // ---- diffuse rain (HARE_RECEIVE_DIFFUSE_RAIN; the header's "receivers", "Diffuse rain")
 // hare_rain_step runs between a cast's shoot and hare_receive_scatter_rain, which overwrites the rays and the state: a lane per ray reads what
 // that kernel reads and recomputes E after absorption and L' = L + e.t with the same FP64 operations.  One launch deposits receiver k_dep
@@ -275,7 +374,9 @@ extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_rain(Rece
 // kernels skip under HARE_SHOOT_RETIRED_RAYS (no traversal, flag 0).  The deposit adds per lane, not per distinct bin of a wave as the
 // receiver step does: nearly every visible ray deposits and their bins are spread, so the wave's rounds over distinct bins cost more than
 // they save (hall, 1M rays, K = 8, B = 8: the rain loop 94.5 ms aggregated, 79.5 ms per lane; the same histogram).
-extern "C" __global__ __launch_bounds__(256) void hare_rain_step(RainArgs a)
+// DIR (hare_rain_step_dir, HARE_RECEIVE_DIRECTIONAL): the deposit adds four words per band, weighted by -(v / dist).
+template <bool DIR>
+static __device__ __forceinline__ void rain_body(const RainArgs& a)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
@@ -323,6 +424,12 @@ extern "C" __global__ __launch_bounds__(256) void hare_rain_step(RainArgs a)
         unsigned long long q[kMaxBands];
 #pragma unroll
         for (int b = 0; b < kMaxBands; ++b) q[b] = 0;
+        [[maybe_unused]] double mq[kMaxBands];                          // DIR: m_b, quantised where it is added
+        [[maybe_unused]] double ax = 0, ay = 0, az = 0;
+        if constexpr (DIR) {
+#pragma unroll
+            for (int b = 0; b < kMaxBands; ++b) mq[b] = 0;
+        }
         if (vis) {
             const double cx = a.rcv[4 * k + 0], cy = a.rcv[4 * k + 1], cz = a.rcv[4 * k + 2], rr = a.rcv[4 * k + 3];
             const double vx = cx - e.x, vy = cy - e.y, vz = cz - e.z;
@@ -336,6 +443,11 @@ extern "C" __global__ __launch_bounds__(256) void hare_rain_step(RainArgs a)
             if (binned) {
                 bin = (int)floor(x);
                 const double* al = a.alpha ? a.alpha + (size_t)e.poly_id * (size_t)B : nullptr;
+                if constexpr (DIR) {
+                    ax = -(vx / dist);
+                    ay = -(vy / dist);
+                    az = -(vz / dist);
+                }
 #pragma unroll
                 for (int b = 0; b < kMaxBands; ++b) {
                     if (b < B) {
@@ -344,7 +456,8 @@ extern "C" __global__ __launch_bounds__(256) void hare_rain_step(RainArgs a)
                         double v = ((Ea * sig[b]) * w) * a.scale;
                         if (!(v > 0)) v = 0;
                         v = v < 9223372036854775808.0 ? v : 9223372036854775808.0;     // min(q, 2^63)
-                        q[b] = (unsigned long long)rint(v);
+                        if constexpr (DIR) mq[b] = v;
+                        else q[b] = (unsigned long long)rint(v);
                     }
                 }
             }
@@ -354,7 +467,20 @@ extern "C" __global__ __launch_bounds__(256) void hare_rain_step(RainArgs a)
             if (bm) atomicAdd(&a.det[2 * k], (unsigned long long)__popcll(bm));
             if (dm & ~bm) atomicAdd(&a.det[2 * k + 1], (unsigned long long)__popcll(dm & ~bm));
         }
-        if (binned) {                                                   // per lane: rain's bins are spread, see above
+        if constexpr (DIR) {
+            if (binned) {                                               // per lane, the four words of a band one by one
+                unsigned long long* const row = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B * 4;
+#pragma unroll
+                for (int b = 0; b < kMaxBands; ++b) {
+                    if (b < B) {
+                        atomicAdd(&row[4 * b + 0], (unsigned long long)rint(mq[b]));
+                        atomicAdd(&row[4 * b + 1], dir_q(mq[b], ax));
+                        atomicAdd(&row[4 * b + 2], dir_q(mq[b], ay));
+                        atomicAdd(&row[4 * b + 3], dir_q(mq[b], az));
+                    }
+                }
+            }
+        } else if (binned) {                                            // per lane: rain's bins are spread, see above
             unsigned long long* const row = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B;
             for (int b = 0; b < B; ++b) atomicAdd(&row[b], q[b]);
         }
@@ -379,4 +505,14 @@ extern "C" __global__ __launch_bounds__(256) void hare_rain_step(RainArgs a)
         }
         a.sexcl[i] = elig ? e.poly_id : -2;
     }
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_rain_step(RainArgs a)
+{
+    rain_body<false>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_rain_step_dir(RainArgs a)
+{
+    rain_body<true>(a);
 }

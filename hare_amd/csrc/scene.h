@@ -119,6 +119,8 @@ struct DeviceModule {
     hipFunction_t reflect = nullptr, occlusion = nullptr;
     hipFunction_t receive_reflect = nullptr, receive_scatter = nullptr;    // receive.hip: hare_receive_reflect, hare_receive_scatter
     hipFunction_t receive_scatter_rain = nullptr, rain_step = nullptr;     // receive.hip: diffuse rain (hare_receive_scatter_rain, hare_rain_step)
+    hipFunction_t receive_reflect_dir = nullptr, receive_scatter_dir = nullptr, receive_scatter_rain_dir = nullptr,
+                  rain_step_dir = nullptr;                                 // receive.hip: HARE_RECEIVE_DIRECTIONAL's forms of the four above
     hipFunction_t voxel_occl_tri = nullptr, voxel_occl_quad = nullptr, voxel_occl_tri_g = nullptr, voxel_occl_quad_g = nullptr, octree_occl = nullptr, octree_occl_any = nullptr;
     hipFunction_t events_pack_slim = nullptr;
     hipFunction_t block_occ = nullptr;                                     // build_kernels.hip: hare_block_occ
@@ -328,10 +330,11 @@ RainWork rain_work(void* d_work, int64_t n);
 // rcv non-null (hare_receive_*): always a launch per cast, hare_receive_reflect (hare_receive_scatter where rcv->sigma is set) behind every
 // cast (the last included) instead of hare_reflect;
 // rcv supplies the receivers, state, histogram and switches, the loop fills in the rest per cast.  rain non-null (with rcv->sigma and
-// rcv->rain_flag): diffuse rain before the receive kernel of every cast but the last, hare_receive_scatter_rain in hare_receive_scatter's place
+// rcv->rain_flag): diffuse rain before the receive kernel of every cast but the last, hare_receive_scatter_rain in hare_receive_scatter's place.
+// directional (HARE_RECEIVE_DIRECTIONAL): rcv->hist has four channels per word and the _dir kernels run
 int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, void* d_rays, const void* d_e1, const void* d_e2,
                        int32_t casts, uint32_t flags, void* d_work, void* d_all, void* d_last, void* d_ctr, void* d_ctr_casts, hipStream_t st,
-                       const ReceiveArgs* rcv = nullptr, const RainWork* rain = nullptr);
+                       const ReceiveArgs* rcv = nullptr, const RainWork* rain = nullptr, bool directional = false);
 uint32_t sanitize_flags(const Scene& s, uint32_t flags);
 int dev_free(const HipApi* H, void*& p);
 void free_bounce_buffers(const HipApi* H, Scene& s);          // bounce.cpp
@@ -339,7 +342,7 @@ void free_bounce_buffers(const HipApi* H, Scene& s);          // bounce.cpp
 int upload_receivers(Scene& s, const HipApi* H);
 void free_receivers(const HipApi* H, Scene& s);
 int32_t scene_bands(const Scene& s, int32_t top);             // B of Model[top]'s absorption / scattering tables (1 without one)
-int receive_check_args(const char* who, const Scene& s, int32_t kind, int32_t top, int64_t n, int32_t bounces, int32_t n_bins, double bin_len,
+int receive_check_args(const char* who, const Scene& s, uint32_t flags, int32_t kind, int32_t top, int64_t n, int32_t bounces, int32_t n_bins, double bin_len,
                        int32_t frac_bits);
 bool scene_has_scattering(const Scene& s, int32_t top);       // Model[top] has a scattering table (hare_receive_scatter)
 // ray_base: the global index of the call's ray 0 (the scattering RNG's g = ray_base + i)

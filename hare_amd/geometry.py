@@ -393,36 +393,51 @@ class Spatial_Partition:
         check(lib.hare_scene_set_scattering(self._h, int(top_index), s.shape[1], ptr(s)))
         return self
 
-    def _receive_shape(self, top_index: int, n_bins: int):
-        return self.get_option("receivers"), int(n_bins), self._bands(top_index)
+    def _receive_shape(self, top_index: int, n_bins: int, directional: bool = False):
+        shape = (self.get_option("receivers"), int(n_bins), self._bands(top_index))
+        return shape + (4,) if directional else shape
+
+    @staticmethod
+    def directional_signed(hist):
+        """The signed channels of a directional histogram [K, n_bins, B, 4]: X, Y, Z as int64 [K, n_bins, B, 3] (a view, no copy).
+        Channel 0 is W, the omni word a call without `directional` returns; channels 1, 2, 3 are X, Y, Z in world axes, positive for
+        sound ARRIVING FROM +x, +y, +z (the ambisonic sign convention), in two's complement at the same scale 2^-frac_bits."""
+        hist = np.asarray(hist)
+        if hist.dtype != np.uint64 or hist.ndim < 1 or hist.shape[-1] != 4:
+            raise ValueError("need a directional histogram: uint64 [..., 4]")
+        return hist[..., 1:].view(np.int64)
 
     def _bands(self, top_index: int) -> int:
         return self.get_option("bands:%d" % int(top_index))          # the scene's own record, whoever set the table
 
     def Receive_batch(self, rays, bounces: int, n_bins: int, bin_len: float, energy=None, frac_bits: int = 40, top_index: int = 0,
-                      poly_origin1=None, poly_origin2=None, out=None, rain: bool = False):
+                      poly_origin1=None, poly_origin2=None, out=None, rain: bool = False, directional: bool = False):
         """The bounce loop with the receiver step between its casts, from host buffers (hare_receive_batch).
         energy: None (every ray starts at L = 0, E = 1) or the state [1 + B, n] (row 0: L, rows 1..B: E).
         Returns (hist [K, n_bins, B] uint64, hist * 2^-frac_bits as float64, detections [K, 2] uint64, final state [1 + B, n],
         counters).  out (optional): the caller's uint64 histogram array [K, n_bins, B], as in Shoot_batch.  rain: diffuse rain
-        (HARE_RECEIVE_DIFFUSE_RAIN) where the topology has a scattering table."""
+        (HARE_RECEIVE_DIFFUSE_RAIN) where the topology has a scattering table.  directional (HARE_RECEIVE_DIRECTIONAL): the histogram
+        (and `out`) is [K, n_bins, B, 4], channels W, X, Y, Z (directional_signed gives X, Y, Z as int64); frac_bits must leave a sign
+        bit of headroom."""
         return Spatial_Partition._receive([self], rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1,
-                                          poly_origin2, out, rain)
+                                          poly_origin2, out, rain, directional)
 
     @staticmethod
     def Receive_batch_sharded(partitions, rays, bounces: int, n_bins: int, bin_len: float, energy=None, frac_bits: int = 40,
-                              top_index: int = 0, poly_origin1=None, poly_origin2=None, out=None, rain: bool = False):
+                              top_index: int = 0, poly_origin1=None, poly_origin2=None, out=None, rain: bool = False,
+                              directional: bool = False):
         """hare_receive_batch_sharded: Receive_batch over several partitions (contiguous ray shards, histograms summed); byte-identical."""
         return Spatial_Partition._receive(list(partitions), rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1,
-                                          poly_origin2, out, rain)
+                                          poly_origin2, out, rain, directional)
 
     @staticmethod
-    def _receive(parts, rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1, poly_origin2, out, rain=False):
+    def _receive(parts, rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1, poly_origin2, out, rain=False, directional=False):
         if not parts or any(p._kind != parts[0]._kind for p in parts):
             raise ValueError("need one or more partitions of the same kind")
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
         n = rays.shape[0]
-        K, nb, B = parts[0]._receive_shape(top_index, n_bins)
+        shape = parts[0]._receive_shape(top_index, n_bins, bool(directional))      # [K, n_bins, B], and the four channels with the flag
+        K, nb, B = shape[:3]
         e1 = None if poly_origin1 is None else np.ascontiguousarray(poly_origin1, np.int32)
         e2 = None if poly_origin2 is None else np.ascontiguousarray(poly_origin2, np.int32)
         for e in (e1, e2):
@@ -433,11 +448,11 @@ class Spatial_Partition:
             state_in = np.ascontiguousarray(energy, np.float64)
             if state_in.shape != (1 + B, n):
                 raise ValueError("energy must be the state [1 + B, n] = [%d, %d]" % (1 + B, n))
-        hist = _result_array(out, (max(K, 0), nb, B), np.uint64)
+        hist = _result_array(out, (max(K, 0),) + shape[1:], np.uint64)
         det = np.zeros((max(K, 0), 2), np.uint64)
         state_out = np.empty((1 + B, n), np.float64)
         ctr = capi.Counters()
-        flags = capi.RECEIVE_DIFFUSE_RAIN if rain else 0
+        flags = (capi.RECEIVE_DIFFUSE_RAIN if rain else 0) | (capi.RECEIVE_DIRECTIONAL if directional else 0)
         if len(parts) == 1:
             rc = lib.hare_receive_batch(parts[0]._h, parts[0]._kind, int(top_index), n, ptr(rays), ptr(e1), ptr(e2), int(bounces), flags, nb,
                                         float(bin_len), int(frac_bits), ptr(state_in), ptr(state_out), ptr(hist), ptr(det), C.addressof(ctr))
@@ -456,12 +471,15 @@ class Spatial_Partition:
 
     def receive_device(self, n: int, d_rays: int, bounces: int, n_bins: int, bin_len: float, frac_bits: int, d_state: int, d_work: int,
                        d_events_last: int, d_hist: int, d_detections: int, top_index: int = 0, d_excl1: int = 0, d_excl2: int = 0,
-                       d_counters: int = 0, stream: int = 0, flags: int = 0, rain: bool = False):
+                       d_counters: int = 0, stream: int = 0, flags: int = 0, rain: bool = False, directional: bool = False):
         """hare_receive_device on raw device addresses (e.g. torch.Tensor.data_ptr()) + a hipStream_t: d_state (1 + B) x n doubles is read
         and overwritten, d_hist (K x n_bins x B uint64) and d_detections (2 K uint64) are accumulated into.  Stream-ordered.  rain: diffuse
-        rain (HARE_RECEIVE_DIFFUSE_RAIN); d_work then holds receive_work_bytes(n, rain=True) bytes."""
+        rain (HARE_RECEIVE_DIFFUSE_RAIN); d_work then holds receive_work_bytes(n, rain=True) bytes.  directional
+        (HARE_RECEIVE_DIRECTIONAL): d_hist is K x n_bins x B x 4 uint64, channels W, X, Y, Z."""
         if rain:
             flags |= capi.RECEIVE_DIFFUSE_RAIN
+        if directional:
+            flags |= capi.RECEIVE_DIRECTIONAL
         check(lib.hare_receive_device(self._h, self._kind, int(top_index), int(n), d_rays or None, d_excl1 or None, d_excl2 or None,
                                       int(bounces), int(flags), int(n_bins), float(bin_len), int(frac_bits), d_state or None, d_work or None,
                                       d_events_last or None, d_hist or None, d_detections or None, d_counters or None, stream or None))

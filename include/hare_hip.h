@@ -81,6 +81,7 @@ extern "C" {
                                        /* kernel would serve.  No reference counterpart                                                            */
 #define HARE_SHOOT_BOUNCE_LOOP 32u     /* hare_shoot_kernel_name only: name the kernel hare_bounce_device (<= 16 casts) launches for n rays           */
 #define HARE_RECEIVE_DIFFUSE_RAIN 128u /* hare_receive_device / _batch / _batch_sharded only: diffuse rain ("receivers", "Diffuse rain", below)    */
+#define HARE_RECEIVE_DIRECTIONAL 256u  /* the same three calls only: four channels per histogram word, W X Y Z ("receivers", "Directional", below) */
 
 /* Hare.Geometry.Ray (Hare_Geometry_Primitives.cs:393-429): origin + direction.  Ray_ID/ThreadID
  * only serve the reference's mailbox pool and are not needed here. 48 bytes. */
@@ -519,6 +520,29 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * expected histogram total per band is the same with and without rain (the diffuse segment's hit probability there is exactly w); its
  * spread is smaller.  Cost: each reflecting cast runs K flags-only occlusion queries of n rays.
  *
+ * Directional (flag HARE_RECEIVE_DIRECTIONAL; first-order, B-format).  Opt-in per call; it combines freely with HARE_RECEIVE_DIFFUSE_RAIN.
+ * With the flag the histogram has four channels, channel innermost:
+ *
+ *   hist[((k*n_bins + bin)*B + b)*4 + ch]        ch 0 = W (omni), 1 = X, 2 = Y, 3 = Z        (K x n_bins x B x 4 uint64 words)
+ *
+ * Channel 0 is exactly the word the call writes without the flag.  Channels 1..3 are int64 in two's complement, added with the same
+ * wrapping uint64 add.  For every add of the receiver step and of the rain above, with q_b as defined there and m_b the double that q_b
+ * is the rint of (E[b] * 2^frac_bits, or in rain ((Ea[b] * sg[b]) * w) * 2^frac_bits; then 0 unless > 0; then min(., 2^63)), FP64, no
+ * contraction:
+ *
+ *   receiver step:   len = sqrt((dx*dx + dy*dy) + dz*dz);   a = ( -(dx / len), -(dy / len), -(dz / len) )
+ *   rain deposit:    a = ( -(vx / dist), -(vy / dist), -(vz / dist) )               (v, dist as in "Diffuse rain")
+ *   v_i = m_b * a_i;   v_i = 0 unless v_i == v_i (NaN);   v_i = min(max(v_i, -2^62), 2^62);   s_i = (int64) rint(v_i)
+ *   hist[... + 0] += q_b;   hist[... + 1 + i] += (uint64) s_i            i = 0, 1, 2
+ *
+ * a is the unit vector from the receiver towards where the sound came from, so a wave arriving from +x gives X > 0 (the ambisonic sign
+ * convention); the channels are in world axes.  In the receiver step a is one vector per ray and cast, the same for every receiver.
+ * sqrt and / are the correctly rounded FP64 ones.  What the caller has to know: frac_bits must leave a sign bit of headroom (the sums of
+ * the signed channels must stay inside +-2^63, so size frac_bits for half the range the omni word alone would allow);
+ * |hist[..., 1 + i]| as int64 never exceeds hist[..., 0] by more than the number of adds into that word (each rint moves a value by at most
+ * 1/2); detections keep their shape and values; nothing about draws, choices, rays, state, suppression or detections changes.  d_hist of
+ * the device call and hist of the host calls are four times as large, and the bound on the histogram becomes K x n_bins x B x 4 <= 2^27.
+ *
  * The histogram is fixed point in uint64: integer sums do not depend on the order of the adds, so the result is bit-identical from
  * run to run, between the one-device and the sharded call, and against a restatement on the host.  (r*r is formed once, when the
  * receivers are set: the same FP64 product.)
@@ -542,12 +566,13 @@ HARE_API int hare_scene_set_scattering(hare_scene *s, int32_t top_index, int32_t
  * Always a launch per cast (the scene option "bounce_fused" does not apply; results are the same either way).
  *   d_rays, d_excl1, d_excl2, d_work (2 n int32), d_events_last   as in hare_bounce_device
  *   d_state        (1 + B) planes of n doubles: plane 0 is L, planes 1..B are E.  Read and overwritten
- *   d_hist         K x n_bins x B uint64, ACCUMULATED;  d_detections: 2 K uint64, ACCUMULATED
+ *   d_hist         K x n_bins x B uint64 (x 4 with HARE_RECEIVE_DIRECTIONAL), ACCUMULATED;  d_detections: 2 K uint64, ACCUMULATED
  *   d_counters     nullable: totals, ACCUMULATED (as hare_bounce_device's; the rain's occlusion queries are not counted)
- *   flags          HARE_SHOOT_COUNT_WORK / HARE_SHOOT_SIMPLE_KERNEL (the casts) and HARE_RECEIVE_DIFFUSE_RAIN; other bits are ignored.  With
+ *   flags          HARE_SHOOT_COUNT_WORK / HARE_SHOOT_SIMPLE_KERNEL (the casts), HARE_RECEIVE_DIFFUSE_RAIN and HARE_RECEIVE_DIRECTIONAL; other bits are ignored.  With
  *                  HARE_RECEIVE_DIFFUSE_RAIN d_work holds HARE_RECEIVE_RAIN_WORK_BYTES(n) bytes: the 2 n int32, then the rain's scratch
  * Arguments are checked before anything runs (HARE_E_INVALID): kind, top_index, 0 <= n <= 2^31 - 256, 1 <= bounces <= 4096,
- * n_bins >= 1, bin_len finite and > 0, 0 <= frac_bits <= 62, K x n_bins x B <= 2^27, null or overlapping buffers.  Then
+ * n_bins >= 1, bin_len finite and > 0, 0 <= frac_bits <= 62, K x n_bins x B <= 2^27 (K x n_bins x B x 4 <= 2^27 with
+ * HARE_RECEIVE_DIRECTIONAL), null or overlapping buffers (d_hist at the size the flags give it).  Then
  * HARE_E_NODEVICE, then HARE_E_STATE (no receivers set; partition not built). */
 #define HARE_RECEIVE_RAIN_WORK_BYTES(n) (80 * (int64_t)(n) + 256)
 HARE_API int hare_receive_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, void *d_rays, const void *d_excl1,
@@ -556,7 +581,7 @@ HARE_API int hare_receive_device(hare_scene *s, int32_t kind, int32_t top_index,
                                  void *d_detections, void *d_counters, void *stream);
 /* The same from host buffers (threading and staging as hare_bounce_batch's last-cast-only path: one enqueue, one synchronisation; no
  * events are downloaded).  state_in nullable (every ray starts at L = 0, E = 1); state_out nullable ((1 + B) x n, as d_state).
- * hist (K x n_bins x B) and detections (2 K) are WRITTEN, not accumulated; ctr nullable: counters summed over the casts.  flags as
+ * hist (K x n_bins x B, x 4 with HARE_RECEIVE_DIRECTIONAL) and detections (2 K) are WRITTEN, not accumulated; ctr nullable: counters summed over the casts.  flags as
  * hare_receive_device's (the call sizes the rain's scratch itself). */
 HARE_API int hare_receive_batch(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, const hare_ray *rays,
                                 const int32_t *excl1, const int32_t *excl2, int32_t bounces, uint32_t flags, int32_t n_bins,

@@ -9,8 +9,11 @@ for the two kernels' per-cast times.
 With --rain (B = 8, K = 1 and 8; SIGMA from --scatter, default 0.3), the scattering loop with and without diffuse rain
 (HARE_RECEIVE_DIFFUSE_RAIN), and a noise figure: the relative spread, over 8 scatter seeds, of the energy the receivers get from 60 m of
 path on (summed over receivers and bands), with rain and without.
+With --directional (B = 8; K = 8 and 64, or K = 1 and 8 with --rain; combinable with --scatter and --rain), every loop of the run is timed
+again with HARE_RECEIVE_DIRECTIONAL in the same run (the _dir kernels, a four-fold histogram): dir_ms, scatter_dir_ms, rain_dir_ms and
+their cost over the same loop without the flag.
 Prints ONE JSON line.  usage: python tools/receiver_rate.py [hall|cathedral] [--rays N] [--bounces B] [--reps R] [--host] [--quick]
-                                                          [--scatter SIGMA] [--rain]"""
+                                                          [--scatter SIGMA] [--rain] [--directional]"""
 import argparse
 import json
 import os
@@ -33,6 +36,7 @@ ap.add_argument("--quick", action="store_true", help="K = 8, B = 8 only (a profi
 ap.add_argument("--scatter", type=float, default=None, metavar="SIGMA",
                 help="K = 8, B = 8 only, and the loop again with a scattering table of SIGMA everywhere (scene option scatter_seed 1)")
 ap.add_argument("--rain", action="store_true", help="K = 1 and 8, B = 8: the scattering loop with and without diffuse rain, and its noise")
+ap.add_argument("--directional", action="store_true", help="B = 8: every loop again with HARE_RECEIVE_DIRECTIONAL, in the same run")
 a = ap.parse_args()
 if a.rain and a.scatter is None:
     a.scatter = 0.3
@@ -80,7 +84,7 @@ def bounce():
 ms_bounce = timed(bounce, a.reps)
 out = {"scene": a.scene, "domain": D, "rays": n, "bounces": nb, "n_bins": N_BINS, "bounce_ms": round(ms_bounce, 3),
        "bounce_Mcasts_s": round(n * nb / ms_bounce / 1e3, 1), "receive": []}
-cases = [(1, 8), (8, 8)] if a.rain else ([(8, 8)] if (a.quick or a.scatter is not None) else [(K, B) for K in (1, 8, 64) for B in (1, 8)])
+cases = [(1, 8), (8, 8)] if a.rain else [(8, 8), (64, 8)] if a.directional else ([(8, 8)] if (a.quick or a.scatter is not None) else [(K, B) for K in (1, 8, 64) for B in (1, 8)])
 d_work_rain = torch.zeros(H.Voxel_Grid.receive_work_bytes(n, rain=True), dtype=torch.uint8, device="cuda") if a.rain else None
 for K, B in cases:
     c, r = receivers(K)
@@ -90,12 +94,20 @@ for K, B in cases:
     init = torch.cat([torch.zeros((1, n), dtype=torch.float64, device="cuda"), torch.ones((B, n), dtype=torch.float64, device="cuda")])
     d_hist = torch.zeros(K * N_BINS * B, dtype=torch.int64, device="cuda")
     d_det = torch.zeros(2 * K, dtype=torch.int64, device="cuda")
+    d_hist4 = torch.zeros(K * N_BINS * B * 4, dtype=torch.int64, device="cuda") if a.directional else None
 
-    def receive(rain=False):
+    def receive(rain=False, directional=False):
         g.receive_device(n, d_rays.data_ptr(), nb, N_BINS, BIN_LEN, FRAC, d_state.data_ptr(), (d_work_rain if rain else d_work).data_ptr(),
-                         d_last.data_ptr(), d_hist.data_ptr(), d_det.data_ptr(), stream=st, rain=rain)
+                         d_last.data_ptr(), (d_hist4 if directional else d_hist).data_ptr(), d_det.data_ptr(), stream=st, rain=rain,
+                         directional=directional)
+
+    def timed_dir(row, key, base_key, rain=False):                       # the same loop with the flag, against row[base_key]
+        ms = timed(lambda: (d_state.copy_(init), receive(rain, True)), a.reps)
+        row[key] = round(ms - ms_copy, 3)
+        row[key.replace("ms", "over_pct")] = round(100.0 * (ms - ms_copy - row[base_key]) / row[base_key], 1)
+        row[key.replace("ms", "over_bounce_pct")] = round(100.0 * (ms - ms_copy - ms_bounce) / ms_bounce, 1)
     row = {"K": K, "B": B}
-    for agg in ((1, 0) if K == 8 and B == 8 and a.scatter is None and not a.rain else (1,)):
+    for agg in ((1, 0) if K == 8 and B == 8 and a.scatter is None and not a.rain and not a.directional else (1,)):
         g.set_option("receive_aggregate", agg)
         d_hist.zero_(); d_det.zero_()
         d_state.copy_(init)
@@ -105,6 +117,11 @@ for K, B in cases:
         row[key] = round(ms - ms_copy, 3)
         row[key.replace("ms", "over_bounce_pct")] = round(100.0 * (ms - ms_copy - ms_bounce) / ms_bounce, 1)
     g.set_option("receive_aggregate", 1)
+    if a.directional:
+        timed_dir(row, "dir_ms", "ms")
+        g.set_option("receive_aggregate", 0)
+        timed_dir(row, "dir_naive_ms", "ms")
+        g.set_option("receive_aggregate", 1)
     d_hist.zero_(); d_det.zero_(); d_rays.copy_(d_src); d_state.copy_(init)
     receive(); torch.cuda.synchronize()
     det = d_det.cpu().numpy().reshape(K, 2)
@@ -116,6 +133,8 @@ for K, B in cases:
         row["scatter_sigma"] = a.scatter
         row["scatter_ms"] = round(ms - ms_copy, 3)
         row["scatter_over_specular_pct"] = round(100.0 * (ms - ms_copy - row["ms"]) / row["ms"], 1)
+        if a.directional:
+            timed_dir(row, "scatter_dir_ms", "scatter_ms")
         d_hist.zero_(); d_det.zero_(); d_rays.copy_(d_src); d_state.copy_(init)
         receive(); torch.cuda.synchronize()
         row["scatter_detections"] = int(d_det.cpu().numpy().sum())
@@ -123,6 +142,8 @@ for K, B in cases:
             ms = timed(lambda: (d_state.copy_(init), receive(True)), a.reps)
             row["rain_ms"] = round(ms - ms_copy, 3)
             row["rain_over_scatter"] = round((ms - ms_copy) / row["scatter_ms"], 2)
+            if a.directional:
+                timed_dir(row, "rain_dir_ms", "rain_ms", rain=True)
             late = int(60.0 / BIN_LEN)
             for rain in (False, True):
                 e = []
