@@ -228,8 +228,7 @@ struct ReceiveJob {
     uint64_t* hist = nullptr;
     uint64_t* det = nullptr;
     int64_t ray_base = 0;      // this shard's first ray in the whole batch (the scattering RNG's global ray index)
-    bool rain = false;         // HARE_RECEIVE_DIFFUSE_RAIN
-    bool directional = false;  // HARE_RECEIVE_DIRECTIONAL: four channels per histogram word
+    uint32_t flags = 0;        // the call's HARE_RECEIVE_* bits
 };
 
 // The receive loop for one scene: rays, exclusions and state go up, the loop is enqueued ONCE (a launch per cast, hare_receive_reflect
@@ -243,7 +242,7 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
     const int32_t B = scene_bands(s, top);
     const size_t K = s.rcv.size() / 4;
     const size_t state_bytes = (size_t)n * (size_t)(1 + B) * sizeof(double);
-    const size_t hist_words = K * (size_t)job.n_bins * (size_t)B * (job.directional ? 4u : 1u), hist_bytes = (hist_words + 2 * K) * sizeof(uint64_t);
+    const size_t hist_words = receive_hist_words(s, top, job.n_bins, job.flags), hist_bytes = (hist_words + 2 * K) * sizeof(uint64_t);
     if (state_bytes > b.state_cap) {
         dev_free(H, b.state);
         b.state_cap = 0;
@@ -256,7 +255,7 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
         HIP_TRY(H->Malloc(&b.hist, hist_bytes));
         b.hist_cap = hist_bytes;
     }
-    const bool rain = job.rain && scene_has_scattering(s, top);     // rain needs a scattering table: without one the flag changes nothing
+    const bool rain = receive_rains(s, top, job.flags);
     const size_t rain_bytes = (size_t)HARE_RECEIVE_RAIN_WORK_BYTES(n);
     if (rain && rain_bytes > b.rain_cap) {
         dev_free(H, b.rain);
@@ -278,17 +277,13 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
                                    hipMemcpyHostToDevice, st));
     HIP_TRY(H->MemsetAsync(b.hist, 0, hist_bytes, st));
     HIP_TRY(H->MemsetAsync(b.ctr, 0, (size_t)bounces * sizeof(hare_counters), st));
-    ReceiveArgs ra;
-    if (int rc = receive_args(s, top, job.n_bins, job.bin_len, job.frac_bits, d_state, d_hist, d_det, job.state_in == nullptr, job.ray_base, ra))
-        return rc;
     void* const work = rain ? b.rain : b.ev[1];         // b.ev[1] holds the loop's 2 n int32; with rain, a buffer of its own holds them and the rain's scratch
-    RainWork rw;
-    if (rain) {
-        rw = rain_work(work, n);
-        ra.rain_flag = rw.flag;
-    }
+    ReceivePlan plan;
+    if (int rc = receive_plan(s, top, job.flags, n, job.n_bins, job.bin_len, job.frac_bits, d_state, d_hist, d_det, work, job.state_in == nullptr,
+                              job.ray_base, plan))
+        return rc;
     if (int rc = bounce_device_impl(s, H, kind, top, n, b.rays[0], excl1 ? b.excl[0] : nullptr, excl2 ? b.excl2 : nullptr, bounces, flags, work,
-                                    nullptr, b.ev[0], nullptr, b.ctr, st, &ra, rain ? &rw : nullptr, job.directional))
+                                    nullptr, b.ev[0], nullptr, b.ctr, st, &plan))
         return rc;
     HIP_TRY(H->MemcpyAsync(job.hist, d_hist, hist_words * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(H->MemcpyAsync(job.det, d_det, 2 * K * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -499,7 +494,7 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
         return HARE_E_INVALID;
     }
     auto sigma_of = [&](const Scene& s) -> const std::vector<double>* {
-        return scene_has_scattering(s, top_index) ? &s.sigma[(size_t)top_index] : nullptr;
+        return scene_has_scattering(s, top_index) ? &s.sigma[(size_t)top_index].host : nullptr;
     };
     for (int32_t k = 1; k < n_scenes; ++k) {     // the shards must compute the same thing
         const std::vector<double>* sk = sigma_of(*scenes[k]);
@@ -516,8 +511,7 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
     }
     GUARD_BEGIN
     const int G = n_scenes;
-    const bool directional = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
-    const size_t K = s0->rcv.size() / 4, hist_words = K * (size_t)n_bins * (size_t)scene_bands(*s0, top_index) * (directional ? 4u : 1u);
+    const size_t K = s0->rcv.size() / 4, hist_words = receive_hist_words(*s0, top_index, n_bins, flags);
     memset(hist, 0, hist_words * sizeof(uint64_t));
     memset(detections, 0, 2 * K * sizeof(uint64_t));
     if (ctr) memset(ctr, 0, sizeof *ctr);
@@ -542,8 +536,7 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
         job.hist = k == 0 ? hist : hists[(size_t)k].data();
         job.det = k == 0 ? detections : dets[(size_t)k].data();
         job.ray_base = lo;
-        job.rain = (flags & HARE_RECEIVE_DIFFUSE_RAIN) != 0;
-        job.directional = directional;
+        job.flags = flags;
         try {
             rcs[(size_t)k] = bounce_one(scenes[k], kind, top_index, hi - lo, rays ? rays + lo : nullptr, excl1 ? excl1 + lo : nullptr,
                                         excl2 ? excl2 + lo : nullptr, bounces, flags, nullptr, n, nullptr, pcs[(size_t)k].data(), &job);

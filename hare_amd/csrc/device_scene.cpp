@@ -94,14 +94,6 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_kdtree_occl", &m->kdtree_occl},
         {"hare_kdtree_shoot_count", &m->kdtree_count},
         {"hare_reflect", &m->reflect},
-        {"hare_receive_reflect", &m->receive_reflect},
-        {"hare_receive_scatter", &m->receive_scatter},
-        {"hare_receive_scatter_rain", &m->receive_scatter_rain},
-        {"hare_rain_step", &m->rain_step},
-        {"hare_receive_reflect_dir", &m->receive_reflect_dir},
-        {"hare_receive_scatter_dir", &m->receive_scatter_dir},
-        {"hare_receive_scatter_rain_dir", &m->receive_scatter_rain_dir},
-        {"hare_rain_step_dir", &m->rain_step_dir},
         {"hare_occlusion", &m->occlusion},
         {"hare_voxel_occl_tri", &m->voxel_occl_tri},
         {"hare_voxel_occl_quad", &m->voxel_occl_quad},
@@ -138,6 +130,12 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         hipError_t e = H->ModuleGetFunction(t.fn, m->mod, t.name);
         if (e != hipSuccess) *t.fn = nullptr;   // optional kernels may be absent in a given build
     }
+    const char* const receive_names[4] = {"hare_receive_reflect", "hare_receive_scatter", "hare_receive_scatter_rain", "hare_rain_step"};
+    for (int f = 0; f < 4; ++f)
+        for (int dir = 0; dir < 2; ++dir) {
+            hipFunction_t* fn = f < 3 ? &m->receive[f][dir] : &m->rain_step[dir];
+            if (H->ModuleGetFunction(fn, m->mod, (std::string(receive_names[f]) + (dir ? "_dir" : "")).c_str()) != hipSuccess) *fn = nullptr;
+        }
     (void)H->GetLastError();   // a failed lookup must not stay behind as the host's "last error"
     if (!m->voxel_tri || !m->voxel_quad) {
         set_error("embedded code object lacks hare_voxel_shoot_* (not a gfx950 device?)");

@@ -460,7 +460,7 @@ static void fill_voxel_args(const Scene& s, int32_t top, VoxelArgs& g)
 //   d_ctr    nullable: totals, accumulated (rays = casts with a live ray);  d_ctr_casts: nullable, `casts` blocks, accumulated
 int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, void* d_rays, const void* d_e1, const void* d_e2,
                        int32_t casts, uint32_t flags, void* d_work, void* d_all, void* d_last, void* d_ctr, void* d_ctr_casts, hipStream_t st,
-                       const ReceiveArgs* rcv, const RainWork* rain, bool directional)
+                       const ReceivePlan* rcv)
 {
     if (n < 0 || casts < 1 || casts > 4096 || top < 0 || top >= (int32_t)s.topos.size()) {
         set_error("hare_bounce: bad n, bounces or top_index");
@@ -480,18 +480,12 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
     hare_xevent* const all = (hare_xevent*)d_all;
     hare_xevent* const last = d_last ? (hare_xevent*)d_last : all + (size_t)(casts - 1) * (size_t)n;
     int32_t* const work = (int32_t*)d_work;
-    if (rain && !(rcv && rcv->sigma && rcv->rain_flag)) rain = nullptr;
-    if (!rcv) directional = false;
-    // HARE_RECEIVE_DIRECTIONAL: the _dir kernels (four channels per histogram word) in place of each of the four
-    hipFunction_t const receive_fn = !rcv             ? nullptr
-                                     : directional ? (!rcv->sigma ? M.receive_reflect_dir : (rain ? M.receive_scatter_rain_dir : M.receive_scatter_dir))
-                                                   : (!rcv->sigma ? M.receive_reflect : (rain ? M.receive_scatter_rain : M.receive_scatter));
-    hipFunction_t const rain_fn = directional ? M.rain_step_dir : M.rain_step;
-    if (!M.reflect || !M.events_fill_miss || (rcv && !receive_fn) || (rain && !rain_fn)) {
+    if (!M.reflect || !M.events_fill_miss || (rcv && !M.receive[receive_form(*rcv)][rcv->directional]) ||
+        (rcv && rcv->rain && !M.rain_step[rcv->directional])) {
         set_error("hare_bounce: bounce kernels missing from code object");
         return HARE_E_STATE;
     }
-    if (rain) HIP_TRY(H->MemsetAsync(rain->flag, 0, (size_t)n * sizeof(int32_t), st));      // no segment of this call has been rained yet
+    if (rcv && rcv->rain) HIP_TRY(H->MemsetAsync(rcv->work.flag, 0, (size_t)n * sizeof(int32_t), st));      // no segment of this call has been rained yet
     // ---- one launch?  (never for the receive loop: its receiver step runs between the casts)
     if (!rcv && kind == HARE_KIND_VOXEL && casts <= kBounceMaxCasts && flags == 0 && s.vox.built && !s.d_cells.empty()) {
         const KernChoice kc = choose_kernel(s, &M, kind, (size_t)top, n, 0u);
@@ -583,69 +577,11 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
         extra.internal_flags = (c > 0 && !all) ? (uint32_t)SHOOT_RETIRED_SILENT : 0u;
         if (c > 0 && use_blocks) { extra.blocks = blk_list; extra.blk_words = blk_words; }
         if (int rc = shoot_device_impl(s, H, kind, top, n, d_rays, c == 0 ? d_e1 : work, c == 0 ? d_e2 : nullptr, f, out_c, ctr_c, st, nullptr, nullptr, &extra)) return fail(rc);
+        const bool last_cast = c + 1 == casts;
         if (rcv) {
-            // the receiver step, the state update and (but behind the last cast) the reflection: hare_receive_reflect in hare_reflect's place,
-            // hare_receive_scatter where Model[top] has a scattering table
-            const bool last_cast = c + 1 == casts;
-            ReceiveArgs ra = *rcv;
-            ra.polys = (const PolyRec*)s.d_polys[(size_t)top];
-            ra.rays = (RayRec*)d_rays;
-            ra.ev = (const XEventRec*)out_c;
-            ra.excl = work;
-            ra.block_live = (use_blocks && !last_cast) ? blk_live : nullptr;
-            ra.n = n;
-            ra.marks_valid = c > 0 ? 1 : 0;
-            ra.last = last_cast ? 1 : 0;
-            ra.init_state = c == 0 ? rcv->init_state : 0;      // the starting state is the first cast's business only
-            ra.cast = c;
-            if (rain && !last_cast) {
-                // diffuse rain (receive.hip: hare_rain_step), before the receive kernel overwrites rays and state: receiver k's query is
-                // emitted, answered by the flags-only occlusion kernel of this partition, and deposited by the launch that emits k + 1's
-                RainArgs g;
-                memset(&g, 0, sizeof g);
-                g.polys = ra.polys;
-                g.rays = ra.rays;
-                g.ev = ra.ev;
-                g.marks = work;
-                g.state = ra.state;
-                g.alpha = ra.alpha;
-                g.sigma = ra.sigma;
-                g.rcv = ra.rcv;
-                g.hist = ra.hist;
-                g.det = ra.det;
-                g.srays = rain->rays;
-                g.stmax = rain->tmax;
-                g.sexcl = rain->excl;
-                g.socc = rain->occ;
-                g.n = n;
-                g.bin_len = ra.bin_len;
-                g.scale = ra.scale;
-                g.bands = ra.bands;
-                g.n_bins = ra.n_bins;
-                g.marks_valid = ra.marks_valid;
-                g.init_state = ra.init_state;
-                for (int32_t k = 0; k <= ra.n_rcv; ++k) {
-                    g.k_dep = k - 1;
-                    g.k_emit = k < ra.n_rcv ? k : -1;
-                    void* ga[] = {&g};
-                    if (int rc = launch(H, rain_fn, (unsigned)((n + 255) / 256), 256, 0, st, ga)) return fail(rc);
-                    if (k == ra.n_rcv) break;
-                    if (int rc = shoot_device_impl(s, H, kind, top, n, rain->rays, rain->excl, nullptr, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st,
-                                                   rain->tmax, rain->occ))
-                        return fail(rc);
-                }
-            }
-            void* a[] = {&ra};
-            if (int rc = launch(H, receive_fn, (unsigned)((n + 255) / 256), 256, 0, st, a)) return fail(rc);
-            if (use_blocks && !last_cast) {
-                uint32_t nb = (uint32_t)nblk;
-                const unsigned char* blc = blk_live;
-                uint32_t* lst = blk_list;
-                uint32_t* cnt = blk_words;
-                void* a2[] = {&blc, &nb, &lst, &cnt};
-                if (int rc = launch(H, M.live_blocks, 1, 1024, 0, st, a2)) return fail(rc);
-            }
-        } else if (c + 1 < casts) {
+            if (int rc = receive_step(s, H, kind, top, n, *rcv, d_rays, out_c, work, (use_blocks && !last_cast) ? blk_live : nullptr, c, last_cast, st))
+                return fail(rc);
+        } else if (!last_cast) {
             const void* polys = s.d_polys[(size_t)top];
             const void* ev = out_c;
             void* ex = work;
@@ -654,14 +590,14 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
             unsigned char* bl = use_blocks ? blk_live : nullptr;
             void* a[] = {&polys, &d_rays, &ev, &ex, &mm, &marks_valid, &bl};
             if (int rc = launch(H, M.reflect, (unsigned)((n + 255) / 256), 256, 0, st, a)) return fail(rc);
-            if (use_blocks) {
-                uint32_t nb = (uint32_t)nblk;
-                const unsigned char* blc = blk_live;
-                uint32_t* lst = blk_list;
-                uint32_t* cnt = blk_words;
-                void* a2[] = {&blc, &nb, &lst, &cnt};
-                if (int rc = launch(H, M.live_blocks, 1, 1024, 0, st, a2)) return fail(rc);
-            }
+        }
+        if (use_blocks && !last_cast) {
+            uint32_t nb = (uint32_t)nblk;
+            const unsigned char* blc = blk_live;
+            uint32_t* lst = blk_list;
+            uint32_t* cnt = blk_words;
+            void* a2[] = {&blc, &nb, &lst, &cnt};
+            if (int rc = launch(H, M.live_blocks, 1, 1024, 0, st, a2)) return fail(rc);
         }
     }
     if (all && d_last) HIP_TRY(H->MemcpyAsync(d_last, all + (size_t)(casts - 1) * (size_t)n, (size_t)n * sizeof(hare_xevent), hipMemcpyDeviceToDevice, st));

@@ -1,6 +1,7 @@
-// receive.cpp -- receivers, absorption and scattering of a scene (hare_scene_set_receivers / _absorption / _scattering) and hare_receive_device,
-// the bounce loop with the receiver step (and, on request, diffuse rain) between its casts (include/hare_hip.h, "receivers"; the kernel: receive.hip).  The host-buffer
-// calls hare_receive_batch / _sharded are in bounce.cpp, beside the loop they share with hare_bounce_batch.
+// receive.cpp -- receivers, absorption and scattering of a scene (hare_scene_set_receivers / _absorption / _scattering), the receive loop's plan
+// and its per-cast step (receive_plan, receive_step: what bounce_device_impl, launch.cpp, runs between its casts) and hare_receive_device
+// (include/hare_hip.h, "receivers"; the kernels: receive.hip).  The host-buffer calls hare_receive_batch / _sharded are in bounce.cpp, beside
+// the loop they share with hare_bounce_batch.
 //
 // Harness-defined: the reference has no receivers (Pachyderm, its caller, detects them on the host per ray).
 // Product code; nothing from oracle/.
@@ -37,33 +38,35 @@ int upload_receivers(Scene& s, const HipApi* H)
         HIP_TRY(H->Memcpy(s.d_rcv, s.rcv.data(), s.rcv.size() * sizeof(double), hipMemcpyHostToDevice));
         s.rcv_on_device = true;
     }
-    s.d_alpha.resize(s.topos.size(), nullptr);
-    s.alpha_on_device.resize(s.topos.size(), 0);
-    for (size_t m = 0; m < s.alpha.size(); ++m) {
-        if (s.alpha[m].empty() || s.alpha_on_device[m]) continue;
-        if (int rc = upload(H, &s.d_alpha[m], s.alpha[m].data(), s.alpha[m].size() * sizeof(double))) return rc;
-        s.alpha_on_device[m] = 1;
-    }
-    s.d_sigma.resize(s.topos.size(), nullptr);
-    s.sigma_on_device.resize(s.topos.size(), 0);
-    for (size_t m = 0; m < s.sigma.size(); ++m) {
-        if (s.sigma[m].empty() || s.sigma_on_device[m]) continue;
-        if (int rc = upload(H, &s.d_sigma[m], s.sigma[m].data(), s.sigma[m].size() * sizeof(double))) return rc;
-        s.sigma_on_device[m] = 1;
-    }
+    for (std::vector<Scene::BandTable>* tables : {&s.alpha, &s.sigma})
+        for (Scene::BandTable& t : *tables) {
+            if (t.host.empty() || t.on_device) continue;
+            if (int rc = upload(H, &t.dev, t.host.data(), t.host.size() * sizeof(double))) return rc;
+            t.on_device = true;
+        }
     return HARE_OK;
 }
 
 void free_receivers(const HipApi* H, Scene& s)
 {
     dev_free(H, s.d_rcv);
-    for (void*& p : s.d_alpha) dev_free(H, p);
-    for (void*& p : s.d_sigma) dev_free(H, p);
+    for (std::vector<Scene::BandTable>* tables : {&s.alpha, &s.sigma})
+        for (Scene::BandTable& t : *tables) dev_free(H, t.dev);
+}
+
+static bool has_table(const std::vector<Scene::BandTable>& tables, int32_t top)
+{
+    return top >= 0 && (size_t)top < tables.size() && !tables[(size_t)top].host.empty();
 }
 
 bool scene_has_scattering(const Scene& s, int32_t top)
 {
-    return top >= 0 && (size_t)top < s.sigma.size() && !s.sigma[(size_t)top].empty();
+    return has_table(s.sigma, top);
+}
+
+bool receive_rains(const Scene& s, int32_t top, uint32_t flags)
+{
+    return (flags & HARE_RECEIVE_DIFFUSE_RAIN) && scene_has_scattering(s, top);
 }
 
 int32_t scene_bands(const Scene& s, int32_t top)
@@ -71,8 +74,13 @@ int32_t scene_bands(const Scene& s, int32_t top)
     return (top >= 0 && (size_t)top < s.bands.size() && s.bands[(size_t)top] > 0) ? s.bands[(size_t)top] : 1;
 }
 
-// Everything a receive call checks before anything runs (HARE_E_INVALID); K is the scene's receiver count (0: unset, counted as 1 here --
-// "no receivers" is HARE_E_STATE, after the device checks)
+size_t receive_hist_words(const Scene& s, int32_t top, int32_t n_bins, uint32_t flags, size_t min_K)
+{
+    const size_t K = std::max<size_t>(min_K, s.rcv.size() / 4);
+    return K * (size_t)n_bins * (size_t)scene_bands(s, top) * ((flags & HARE_RECEIVE_DIRECTIONAL) ? 4u : 1u);
+}
+
+// Everything a receive call checks before anything runs (HARE_E_INVALID); "no receivers" is HARE_E_STATE, after the device checks
 int receive_check_args(const char* who, const Scene& s, uint32_t flags, int32_t kind, int32_t top, int64_t n, int32_t bounces, int32_t n_bins, double bin_len,
                        int32_t frac_bits)
 {
@@ -87,48 +95,15 @@ int receive_check_args(const char* who, const Scene& s, uint32_t flags, int32_t 
     if (n_bins < 1) return bad("n_bins must be >= 1");
     if (!(std::isfinite(bin_len) && bin_len > 0)) return bad("bin_len must be finite and > 0");
     if (frac_bits < 0 || frac_bits > 62) return bad("frac_bits out of range (0 .. 62)");
-    const int64_t K = std::max<int64_t>(1, (int64_t)(s.rcv.size() / 4));
-    if (K * (int64_t)n_bins * (int64_t)scene_bands(s, top) > ((int64_t)1 << 27)) return bad("receivers x n_bins x bands exceeds 2^27");
-    if ((flags & HARE_RECEIVE_DIRECTIONAL) && K * (int64_t)n_bins * (int64_t)scene_bands(s, top) * 4 > ((int64_t)1 << 27))
+    if (receive_hist_words(s, top, n_bins, 0, 1) > ((size_t)1 << 27)) return bad("receivers x n_bins x bands exceeds 2^27");
+    if (receive_hist_words(s, top, n_bins, flags, 1) > ((size_t)1 << 27))
         return bad("receivers x n_bins x bands x 4 channels (HARE_RECEIVE_DIRECTIONAL) exceeds 2^27");
-    return HARE_OK;
-}
-
-// The ReceiveArgs of one call (the loop fills in rays, events, marks per cast); receivers and tables must be on the device
-int receive_args(const Scene& s, int32_t top, int32_t n_bins, double bin_len, int32_t frac_bits, void* d_state, void* d_hist, void* d_det,
-                 bool init_state, int64_t ray_base, ReceiveArgs& ra)
-{
-    memset(&ra, 0, sizeof ra);
-    const int32_t B = scene_bands(s, top);
-    ra.state = (double*)d_state;
-    ra.alpha = ((size_t)top < s.d_alpha.size() && (size_t)top < s.alpha.size() && !s.alpha[(size_t)top].empty()) ? (const double*)s.d_alpha[(size_t)top] : nullptr;
-    ra.rcv = (const double*)s.d_rcv;
-    ra.hist = (unsigned long long*)d_hist;
-    ra.det = (unsigned long long*)d_det;
-    ra.bin_len = bin_len;
-    ra.scale = ldexp(1.0, frac_bits);
-    ra.bands = B;
-    ra.n_rcv = (int32_t)(s.rcv.size() / 4);
-    ra.n_bins = n_bins;
-    ra.aggregate = s.opt.receive_aggregate;
-    ra.init_state = init_state ? 1 : 0;
-    ra.sigma = ((size_t)top < s.d_sigma.size() && scene_has_scattering(s, top)) ? (const double*)s.d_sigma[(size_t)top] : nullptr;
-    ra.seed = (unsigned long long)s.opt.scatter_seed;
-    ra.ray_base = (long long)ray_base;
-    if (ra.sigma == nullptr && scene_has_scattering(s, top)) {
-        set_error("receive: scattering table not on the device");
-        return HARE_E_STATE;
-    }
-    if (ra.alpha == nullptr && !s.alpha.empty() && (size_t)top < s.alpha.size() && !s.alpha[(size_t)top].empty()) {
-        set_error("receive: absorption table not on the device");
-        return HARE_E_STATE;
-    }
     return HARE_OK;
 }
 
 // The rain's scratch in a receive call's work array: behind the loop's 2 n int32, from a 16-byte boundary: n shadow rays (48 B), n t_max,
 // n exclusions, n occlusion flags, n suppression flags: 76 n bytes in all and at most 15 of padding, within HARE_RECEIVE_RAIN_WORK_BYTES(n)
-RainWork rain_work(void* d_work, int64_t n)
+static RainWork rain_work(void* d_work, int64_t n)
 {
     RainWork w;
     w.rays = (RayRec*)(((uintptr_t)d_work + (uintptr_t)n * 8u + 15u) & ~(uintptr_t)15u);
@@ -139,6 +114,107 @@ RainWork rain_work(void* d_work, int64_t n)
     return w;
 }
 
+int receive_plan(const Scene& s, int32_t top, uint32_t flags, int64_t n, int32_t n_bins, double bin_len, int32_t frac_bits, void* d_state,
+                 void* d_hist, void* d_det, void* d_work, bool init_state, int64_t ray_base, ReceivePlan& p)
+{
+    ReceiveArgs& ra = p.args;
+    memset(&ra, 0, sizeof ra);
+    ra.state = (double*)d_state;
+    ra.alpha = has_table(s.alpha, top) ? (const double*)s.alpha[(size_t)top].dev : nullptr;
+    ra.rcv = (const double*)s.d_rcv;
+    ra.hist = (unsigned long long*)d_hist;
+    ra.det = (unsigned long long*)d_det;
+    ra.bin_len = bin_len;
+    ra.scale = ldexp(1.0, frac_bits);
+    ra.bands = scene_bands(s, top);
+    ra.n_rcv = (int32_t)(s.rcv.size() / 4);
+    ra.n_bins = n_bins;
+    ra.aggregate = s.opt.receive_aggregate;
+    ra.init_state = init_state ? 1 : 0;
+    ra.sigma = has_table(s.sigma, top) ? (const double*)s.sigma[(size_t)top].dev : nullptr;
+    ra.seed = (unsigned long long)s.opt.scatter_seed;
+    ra.ray_base = (long long)ray_base;
+    if (ra.sigma == nullptr && has_table(s.sigma, top)) {
+        set_error("receive: scattering table not on the device");
+        return HARE_E_STATE;
+    }
+    if (ra.alpha == nullptr && has_table(s.alpha, top)) {
+        set_error("receive: absorption table not on the device");
+        return HARE_E_STATE;
+    }
+    p.directional = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
+    p.rain = receive_rains(s, top, flags);
+    p.work = p.rain ? rain_work(d_work, n) : RainWork();
+    ra.rain_flag = p.work.flag;
+    return HARE_OK;
+}
+
+// hare_rain_step reads what the receive kernel of the same cast reads, before that kernel overwrites rays and state
+static RainArgs rain_args(const ReceiveArgs& ra, const RainWork& w)
+{
+    RainArgs g;
+    memset(&g, 0, sizeof g);
+    g.polys = ra.polys;
+    g.rays = ra.rays;
+    g.ev = ra.ev;
+    g.marks = ra.excl;
+    g.state = ra.state;
+    g.alpha = ra.alpha;
+    g.sigma = ra.sigma;
+    g.rcv = ra.rcv;
+    g.hist = ra.hist;
+    g.det = ra.det;
+    g.srays = w.rays;
+    g.stmax = w.tmax;
+    g.sexcl = w.excl;
+    g.socc = w.occ;
+    g.n = ra.n;
+    g.bin_len = ra.bin_len;
+    g.scale = ra.scale;
+    g.bands = ra.bands;
+    g.n_bins = ra.n_bins;
+    g.marks_valid = ra.marks_valid;
+    g.init_state = ra.init_state;
+    return g;
+}
+
+// The receiver step, the state update and (but behind the last cast) the reflection: hare_receive_reflect in hare_reflect's place,
+// hare_receive_scatter where Model[top] has a scattering table, hare_receive_scatter_rain behind the rain
+int receive_step(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, const ReceivePlan& p, void* d_rays, const void* d_ev,
+                 int32_t* marks, unsigned char* block_live, int32_t cast, bool last_cast, hipStream_t st)
+{
+    const DeviceModule& M = *s.module;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    ReceiveArgs ra = p.args;
+    ra.polys = (const PolyRec*)s.d_polys[(size_t)top];
+    ra.rays = (RayRec*)d_rays;
+    ra.ev = (const XEventRec*)d_ev;
+    ra.excl = marks;
+    ra.block_live = block_live;
+    ra.n = n;
+    ra.marks_valid = cast > 0 ? 1 : 0;
+    ra.last = last_cast ? 1 : 0;
+    ra.init_state = cast == 0 ? p.args.init_state : 0;      // the starting state is the first cast's business only
+    ra.cast = cast;
+    if (p.rain && !last_cast) {
+        // diffuse rain (receive.hip: hare_rain_step): receiver k's query is emitted, answered by the flags-only occlusion kernel of this
+        // partition, and deposited by the launch that emits k + 1's
+        RainArgs g = rain_args(ra, p.work);
+        for (int32_t k = 0; k <= ra.n_rcv; ++k) {
+            g.k_dep = k - 1;
+            g.k_emit = k < ra.n_rcv ? k : -1;
+            void* ga[] = {&g};
+            if (int rc = launch(H, M.rain_step[p.directional], grid, 256, 0, st, ga)) return rc;
+            if (k == ra.n_rcv) break;
+            if (int rc = shoot_device_impl(s, H, kind, top, n, p.work.rays, p.work.excl, nullptr, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st,
+                                           p.work.tmax, p.work.occ))
+                return rc;
+        }
+    }
+    void* a[] = {&ra};
+    return launch(H, M.receive[receive_form(p)][p.directional], grid, 256, 0, st, a);
+}
+
 // After the device checks: receivers set, and on the device (uploads only what a setter run without a device left behind)
 int receive_ready(Scene& s, const HipApi* H, const char* who)
 {
@@ -146,6 +222,35 @@ int receive_ready(Scene& s, const HipApi* H, const char* who)
         set_error(std::string(who) + ": no receivers set (hare_scene_set_receivers)");
         return HARE_E_STATE;
     }
+    return upload_receivers(s, H);
+}
+
+// hare_scene_set_absorption / _scattering behind their own checks of top_index and B: P x B coefficients in [0, 1] become Model[top]'s
+// table `mine` (`name` in the messages), with the B of the topology's other table where it has one
+static int set_band_table(Scene& s, const char* who, const char* name, std::vector<Scene::BandTable>& mine, const std::vector<Scene::BandTable>& other,
+                   const char* other_name, int32_t top, int32_t B, const double* v)
+{
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    const size_t cnt = (size_t)s.topos[(size_t)top].P * (size_t)B;
+    if (cnt > 0 && !v) return bad(std::string("null ") + name);
+    for (size_t k = 0; k < cnt; ++k)
+        if (!(v[k] >= 0.0 && v[k] <= 1.0)) return bad(std::string(name) + "[" + std::to_string(k) + "] outside [0, 1]");
+    if (has_table(other, top) && B != scene_bands(s, top))
+        return bad(std::string("B differs from the topology's ") + other_name + " table (" + std::to_string(scene_bands(s, top)) + " bands)");
+    mine.resize(s.topos.size());
+    s.bands.resize(s.topos.size(), 1);
+    std::vector<double> t(v, v + cnt);
+    if (t.empty()) t.assign((size_t)B, 0.0);       // a topology without polygons: a table of one row no ray reads
+    mine[(size_t)top].host.swap(t);
+    mine[(size_t)top].on_device = false;
+    s.bands[(size_t)top] = B;
+    const HipApi* H = nullptr;
+    if (!device_present(H)) return HARE_OK;
+    DeviceGuard dev_guard(H, s.device);
+    if (int rc = ensure_device(s, H)) return rc;
     return upload_receivers(s, H);
 }
 
@@ -217,34 +322,8 @@ int hare_scene_set_absorption(hare_scene* s, int32_t top_index, int32_t B, const
         set_error("hare_scene_set_absorption: bad top_index or bands (1 .. 8)");
         return HARE_E_INVALID;
     }
-    const size_t cnt = (size_t)s->topos[(size_t)top_index].P * (size_t)B;
-    if (cnt > 0 && !alpha) {
-        set_error("hare_scene_set_absorption: null alpha");
-        return HARE_E_INVALID;
-    }
-    for (size_t k = 0; k < cnt; ++k)
-        if (!(alpha[k] >= 0.0 && alpha[k] <= 1.0)) {
-            set_error("hare_scene_set_absorption: alpha[" + std::to_string(k) + "] outside [0, 1]");
-            return HARE_E_INVALID;
-        }
-    if (scene_has_scattering(*s, top_index) && B != scene_bands(*s, top_index)) {
-        set_error("hare_scene_set_absorption: B differs from the topology's scattering table (" + std::to_string(scene_bands(*s, top_index)) + " bands)");
-        return HARE_E_INVALID;
-    }
     GUARD_BEGIN
-    s->alpha.resize(s->topos.size());
-    s->bands.resize(s->topos.size(), 1);
-    s->alpha_on_device.resize(s->topos.size(), 0);
-    std::vector<double> a(alpha, alpha + cnt);
-    if (a.empty()) a.assign((size_t)B, 0.0);       // a topology without polygons: a table of one row no ray reads
-    s->alpha[(size_t)top_index].swap(a);
-    s->bands[(size_t)top_index] = B;
-    s->alpha_on_device[(size_t)top_index] = 0;
-    const HipApi* H = nullptr;
-    if (!device_present(H)) return HARE_OK;
-    DeviceGuard dev_guard(H, s->device);
-    if (int rc = ensure_device(*s, H)) return rc;
-    return upload_receivers(*s, H);
+    return set_band_table(*s, "hare_scene_set_absorption", "alpha", s->alpha, s->sigma, "scattering", top_index, B, alpha);
     GUARD_END
 }
 
@@ -258,54 +337,25 @@ int hare_scene_set_scattering(hare_scene* s, int32_t top_index, int32_t B, const
         set_error("hare_scene_set_scattering: bad top_index");
         return HARE_E_INVALID;
     }
-    const bool remove = B == 0 && !sigma;
-    if (!remove && (B < 1 || B > kMaxBands)) {
-        set_error("hare_scene_set_scattering: bands out of range (1 .. 8; 0 with a null table removes it)");
-        return HARE_E_INVALID;
-    }
-    const size_t cnt = remove ? 0 : (size_t)s->topos[(size_t)top_index].P * (size_t)B;
-    if (!remove && cnt > 0 && !sigma) {
-        set_error("hare_scene_set_scattering: null sigma");
-        return HARE_E_INVALID;
-    }
-    for (size_t k = 0; k < cnt; ++k)
-        if (!(sigma[k] >= 0.0 && sigma[k] <= 1.0)) {
-            set_error("hare_scene_set_scattering: sigma[" + std::to_string(k) + "] outside [0, 1]");
-            return HARE_E_INVALID;
-        }
-    const bool has_alpha = (size_t)top_index < s->alpha.size() && !s->alpha[(size_t)top_index].empty();
-    if (!remove && has_alpha && B != scene_bands(*s, top_index)) {
-        set_error("hare_scene_set_scattering: B differs from the topology's absorption table (" + std::to_string(scene_bands(*s, top_index)) + " bands)");
-        return HARE_E_INVALID;
-    }
-    GUARD_BEGIN
-    s->sigma.resize(s->topos.size());
-    s->bands.resize(s->topos.size(), 1);
-    s->sigma_on_device.resize(s->topos.size(), 0);
-    s->d_sigma.resize(s->topos.size(), nullptr);
-    if (remove) {
-        s->sigma[(size_t)top_index].clear();
-        if (!has_alpha) s->bands[(size_t)top_index] = 1;
-        s->sigma_on_device[(size_t)top_index] = 0;
-        if (s->d_sigma[(size_t)top_index]) {
-            const HipApi* H = hip_api(nullptr);
-            if (H) {
-                DeviceGuard dev_guard(H, s->device);
-                dev_free(H, s->d_sigma[(size_t)top_index]);
-            }
+    if (B == 0 && !sigma) {                          // removal
+        if (!has_table(s->sigma, top_index)) return HARE_OK;
+        Scene::BandTable& t = s->sigma[(size_t)top_index];
+        t.host.clear();
+        t.on_device = false;
+        if (!has_table(s->alpha, top_index)) s->bands[(size_t)top_index] = 1;
+        const HipApi* H = t.dev ? hip_api(nullptr) : nullptr;
+        if (H) {
+            DeviceGuard dev_guard(H, s->device);
+            dev_free(H, t.dev);
         }
         return HARE_OK;
     }
-    std::vector<double> t(sigma, sigma + cnt);
-    if (t.empty()) t.assign((size_t)B, 0.0);       // a topology without polygons: a table of one row no ray reads
-    s->sigma[(size_t)top_index].swap(t);
-    s->bands[(size_t)top_index] = B;
-    s->sigma_on_device[(size_t)top_index] = 0;
-    const HipApi* H = nullptr;
-    if (!device_present(H)) return HARE_OK;
-    DeviceGuard dev_guard(H, s->device);
-    if (int rc = ensure_device(*s, H)) return rc;
-    return upload_receivers(*s, H);
+    if (B < 1 || B > kMaxBands) {
+        set_error("hare_scene_set_scattering: bands out of range (1 .. 8; 0 with a null table removes it)");
+        return HARE_E_INVALID;
+    }
+    GUARD_BEGIN
+    return set_band_table(*s, "hare_scene_set_scattering", "sigma", s->sigma, s->alpha, "absorption", top_index, B, sigma);
     GUARD_END
 }
 
@@ -318,10 +368,9 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
         return HARE_E_INVALID;
     }
     if (int rc = receive_check_args("hare_receive_device", *s, flags, kind, top_index, n, bounces, n_bins, bin_len, frac_bits)) return rc;
-    const int64_t K = std::max<int64_t>(1, (int64_t)(s->rcv.size() / 4));
+    const size_t K = std::max<size_t>(1, s->rcv.size() / 4);
     const int32_t B = scene_bands(*s, top_index);
     const bool rain = (flags & HARE_RECEIVE_DIFFUSE_RAIN) != 0;
-    const bool directional = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;      // four channels per histogram word
     if (n > 0) {
         if (!d_rays || !d_state || !d_work || !d_events_last || !d_hist || !d_detections) {
             set_error("hare_receive_device: null rays / state / work array / events / histogram / detections");
@@ -332,8 +381,8 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
                             {d_state, (size_t)n * (size_t)(1 + B) * sizeof(double), true},
                             {d_work, rain ? (size_t)HARE_RECEIVE_RAIN_WORK_BYTES(n) : (size_t)n * 2 * sizeof(int32_t), true},
                             {d_events_last, (size_t)n * sizeof(hare_xevent), true},
-                            {d_hist, (size_t)K * (size_t)n_bins * (size_t)B * (directional ? 4u : 1u) * sizeof(uint64_t), true},
-                            {d_detections, (size_t)K * 2 * sizeof(uint64_t), true},
+                            {d_hist, receive_hist_words(*s, top_index, n_bins, flags, 1) * sizeof(uint64_t), true},
+                            {d_detections, K * 2 * sizeof(uint64_t), true},
                             {d_counters, sizeof(hare_counters), true},
                             {d_excl1, (size_t)n * sizeof(int32_t), false},
                             {d_excl2, (size_t)n * sizeof(int32_t), false}};
@@ -356,16 +405,11 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
     if (int rc = upload_polys(*s, H)) return rc;
     if (int rc = receive_ready(*s, H, "hare_receive_device")) return rc;
     if (n == 0) return HARE_OK;
-    ReceiveArgs ra;
-    if (int rc = receive_args(*s, top_index, n_bins, bin_len, frac_bits, d_state, d_hist, d_detections, false, 0, ra)) return rc;
+    ReceivePlan plan;
+    if (int rc = receive_plan(*s, top_index, flags, n, n_bins, bin_len, frac_bits, d_state, d_hist, d_detections, d_work, false, 0, plan)) return rc;
     flags &= HARE_SHOOT_COUNT_WORK | HARE_SHOOT_SIMPLE_KERNEL;
-    RainWork rw;
-    if (rain && ra.sigma) {                 // rain needs a scattering table: without one the flag changes nothing
-        rw = rain_work(d_work, n);
-        ra.rain_flag = rw.flag;
-    }
     return bounce_device_impl(*s, H, kind, top_index, n, d_rays, d_excl1, d_excl2, bounces, flags, d_work, nullptr, d_events_last, d_counters,
-                              nullptr, (hipStream_t)stream, &ra, ra.rain_flag ? &rw : nullptr, directional);
+                              nullptr, (hipStream_t)stream, &plan);
     GUARD_END
 }
 

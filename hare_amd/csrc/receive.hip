@@ -2,8 +2,8 @@
 // "receivers"), #included from kernels.hip.  One body (receive_body), three kernels: scattering and rain are compile-time switches.  And
 // hare_rain_step, diffuse rain's emit and deposit (below).
 //
-// One lane per ray, in place of hare_reflect behind every cast of hare_receive_device's loop (launch.cpp: bounce_device_impl with a
-// ReceiveArgs).  A live ray reads its ray, its event and its state once; runs through every receiver sphere in ascending order with the
+// One lane per ray, in place of hare_reflect behind every cast of hare_receive_device's loop (receive.cpp: receive_step, which
+// bounce_device_impl runs behind every cast).  A live ray reads its ray, its event and its state once; runs through every receiver sphere in ascending order with the
 // FP64 test of the header (no contraction: -ffp-contract=off); updates its state; and, except in the last cast, is reflected exactly as
 // hare_reflect does it (the same function, reflect_hit; the same marks and live-block byte).  A retired ray (-2) costs one 4-byte load; a
 // workgroup whose rays are all retired also passes one barrier and stages no receivers.
@@ -15,6 +15,13 @@
 // Histogram adds are uint64 fixed point, so their order does not matter.  A detection is rare except in the direct sound of a burst,
 // where a wave's rays that pass a receiver near the source land in one or two bins: with `aggregate` the wave sums its lanes' adds
 // per distinct bin first and issues ONE atomic instruction per (receiver, bin), lanes 0 .. B-1 adding the B bands (8 B contiguous bytes).
+
+// m_b of the header, the double that the histogram word q_b is the rint of: v = energy * 2^frac_bits; 0 unless > 0; min(., 2^63)
+static __device__ __forceinline__ double quant_m(double v)
+{
+    if (!(v > 0)) v = 0;
+    return v < 9223372036854775808.0 ? v : 9223372036854775808.0;
+}
 
 static __device__ __forceinline__ unsigned long long wave_allsum_u64(unsigned long long v)
 {
@@ -82,12 +89,6 @@ static __device__ __forceinline__ RayRec scatter_hit(double nx, double ny, doubl
 // ---- directional receivers (HARE_RECEIVE_DIRECTIONAL; the header's "receivers", "Directional"): four words per (receiver, bin, band),
 // channel innermost: W (the omni word, unchanged) and X, Y, Z, the add weighted by the unit vector towards where the sound came from, as
 // int64 in two's complement.  They are added with the same wrapping uint64 adds, so every sum stays an exact integer sum.
-// m_b of the header: the double that q_b is the rint of
-static __device__ __forceinline__ double dir_m(double v)
-{
-    if (!(v > 0)) v = 0;
-    return v < 9223372036854775808.0 ? v : 9223372036854775808.0;     // min(m, 2^63)
-}
 // s_i of the header as a two's-complement word: m * a_i, 0 for NaN, clamped to +-2^62, rint
 static __device__ __forceinline__ unsigned long long dir_q(double m, double ai)
 {
@@ -204,7 +205,7 @@ static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
                 if (!a.aggregate) {                                          // naive form (A/B): every detecting lane adds its own words
                     if (binned)
                         for (int b = 0; b < B; ++b) {
-                            const double m = dir_m(E[b] * a.scale);
+                            const double m = quant_m(E[b] * a.scale);
                             unsigned long long* const w = &row[((size_t)bin * B + b) * 4];
                             atomicAdd(&w[0], (unsigned long long)rint(m));
                             atomicAdd(&w[1], dir_q(m, ax));
@@ -223,7 +224,7 @@ static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
 #pragma unroll
                     for (int b = 0; b < kMaxBands; ++b) {
                         if (b < B) {
-                            const double m = mine ? dir_m(E[b] * a.scale) : 0.0;     // m = 0 quantises to four zero words
+                            const double m = mine ? quant_m(E[b] * a.scale) : 0.0;     // m = 0 quantises to four zero words
                             const unsigned long long sb =
                                 wave_sum4_u64((unsigned long long)rint(m), dir_q(m, ax), dir_q(m, ay), dir_q(m, az), lane);
                             if ((lane & 15) == b) mysum = sb;
@@ -238,12 +239,7 @@ static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
 #pragma unroll
             for (int b = 0; b < kMaxBands; ++b) {
                 q[b] = 0;
-                if (b < B && binned) {
-                    double v = E[b] * a.scale;
-                    if (!(v > 0)) v = 0;
-                    v = v < 9223372036854775808.0 ? v : 9223372036854775808.0;     // min(q, 2^63)
-                    q[b] = (unsigned long long)rint(v);
-                }
+                if (b < B && binned) q[b] = (unsigned long long)rint(quant_m(E[b] * a.scale));
             }
             unsigned long long* const row = a.hist + (size_t)k * (size_t)a.n_bins * (size_t)B;
             if (!a.aggregate) {                                              // naive form (A/B): every detecting lane adds its own bands
@@ -370,7 +366,7 @@ extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_rain_dir(
 // hare_rain_step runs between a cast's shoot and hare_receive_scatter_rain, which overwrites the rays and the state: a lane per ray reads what
 // that kernel reads and recomputes E after absorption and L' = L + e.t with the same FP64 operations.  One launch deposits receiver k_dep
 // (the flags the occlusion kernel left for the query the previous launch emitted) and emits receiver k_emit's query, so K receivers cost
-// K + 1 launches of this kernel and K occlusion launches per cast (launch.cpp).  A slot without a query is marked -2, which the occlusion
+// K + 1 launches of this kernel and K occlusion launches per cast (receive.cpp: receive_step).  A slot without a query is marked -2, which the occlusion
 // kernels skip under HARE_SHOOT_RETIRED_RAYS (no traversal, flag 0).  The deposit adds per lane, not per distinct bin of a wave as the
 // receiver step does: nearly every visible ray deposits and their bins are spread, so the wave's rounds over distinct bins cost more than
 // they save (hall, 1M rays, K = 8, B = 8: the rain loop 94.5 ms aggregated, 79.5 ms per lane; the same histogram).
@@ -453,9 +449,7 @@ static __device__ __forceinline__ void rain_body(const RainArgs& a)
                     if (b < B) {
                         const double E = a.init_state ? 1.0 : a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i];
                         const double Ea = al ? E * (1.0 - al[b]) : E;
-                        double v = ((Ea * sig[b]) * w) * a.scale;
-                        if (!(v > 0)) v = 0;
-                        v = v < 9223372036854775808.0 ? v : 9223372036854775808.0;     // min(q, 2^63)
+                        const double v = quant_m(((Ea * sig[b]) * w) * a.scale);
                         if constexpr (DIR) mq[b] = v;
                         else q[b] = (unsigned long long)rint(v);
                     }

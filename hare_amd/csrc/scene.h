@@ -117,10 +117,9 @@ struct DeviceModule {
     hipFunction_t octree = nullptr, octree_count = nullptr, octree_persist = nullptr, octree_pool = nullptr, octree_tail = nullptr, octree_group = nullptr, octree_group_tail = nullptr, octree_dense = nullptr;
     hipFunction_t kdtree = nullptr, kdtree_count = nullptr;
     hipFunction_t reflect = nullptr, occlusion = nullptr;
-    hipFunction_t receive_reflect = nullptr, receive_scatter = nullptr;    // receive.hip: hare_receive_reflect, hare_receive_scatter
-    hipFunction_t receive_scatter_rain = nullptr, rain_step = nullptr;     // receive.hip: diffuse rain (hare_receive_scatter_rain, hare_rain_step)
-    hipFunction_t receive_reflect_dir = nullptr, receive_scatter_dir = nullptr, receive_scatter_rain_dir = nullptr,
-                  rain_step_dir = nullptr;                                 // receive.hip: HARE_RECEIVE_DIRECTIONAL's forms of the four above
+    // receive.hip, [directional]: hare_receive_reflect / _scatter / _scatter_rain (no table / a scattering table / with diffuse rain),
+    // hare_rain_step, and HARE_RECEIVE_DIRECTIONAL's _dir forms
+    hipFunction_t receive[3][2] = {}, rain_step[2] = {};
     hipFunction_t voxel_occl_tri = nullptr, voxel_occl_quad = nullptr, voxel_occl_tri_g = nullptr, voxel_occl_quad_g = nullptr, octree_occl = nullptr, octree_occl_any = nullptr;
     hipFunction_t events_pack_slim = nullptr;
     hipFunction_t block_occ = nullptr;                                     // build_kernels.hip: hare_block_occ
@@ -289,13 +288,14 @@ struct Scene {
     std::vector<double> rcv;                     // K x 4: cx, cy, cz, r * r (hare_receive_reflect's layout)
     void* d_rcv = nullptr;
     bool rcv_on_device = false;
-    std::vector<std::vector<double>> alpha;      // per topology: P x bands, or empty (no table: B = 1, every alpha 0)
+    struct BandTable {
+        std::vector<double> host;                // P x bands coefficients, or empty (no table)
+        void* dev = nullptr;                     // device copy, or null
+        bool on_device = false;
+    };
+    std::vector<BandTable> alpha;                // per topology: absorption (no table: B = 1, every alpha 0)
+    std::vector<BandTable> sigma;                // per topology: scattering (no table: specular only)
     std::vector<int32_t> bands;                  // per topology: B of its tables (1 without one); the first table set fixes it for the other
-    std::vector<void*> d_alpha;                  // per topology: device copy of alpha, or null
-    std::vector<char> alpha_on_device;
-    std::vector<std::vector<double>> sigma;      // per topology: P x bands scattering coefficients, or empty (no table: specular only)
-    std::vector<void*> d_sigma;                  // per topology: device copy of sigma, or null
-    std::vector<char> sigma_on_device;
 };
 void free_host_mirror(Scene& s);             // host_trace.cpp
 void make_poly_records(const Topo& T, std::vector<PolyRec>& rec, std::vector<QuadRec>& quads);   // device_scene.cpp
@@ -326,15 +326,20 @@ struct RainWork {
     int32_t* occ = nullptr;     // n occlusion flags
     int32_t* flag = nullptr;    // n suppression flags (ReceiveArgs::rain_flag)
 };
-RainWork rain_work(void* d_work, int64_t n);
-// rcv non-null (hare_receive_*): always a launch per cast, hare_receive_reflect (hare_receive_scatter where rcv->sigma is set) behind every
-// cast (the last included) instead of hare_reflect;
-// rcv supplies the receivers, state, histogram and switches, the loop fills in the rest per cast.  rain non-null (with rcv->sigma and
-// rcv->rain_flag): diffuse rain before the receive kernel of every cast but the last, hare_receive_scatter_rain in hare_receive_scatter's place.
-// directional (HARE_RECEIVE_DIRECTIONAL): rcv->hist has four channels per word and the _dir kernels run
+// The receive loop of one call (receive.cpp: receive_plan), host side only
+struct ReceivePlan {
+    ReceiveArgs args;           // receivers, state, histogram and switches; the loop fills in rays, events and marks per cast
+    RainWork work;              // rain only
+    bool rain = false;          // HARE_RECEIVE_DIFFUSE_RAIN on a topology with a scattering table (args.sigma, args.rain_flag set)
+    bool directional = false;   // HARE_RECEIVE_DIRECTIONAL: args.hist has four channels per word and the _dir kernels run
+};
+inline int receive_form(const ReceivePlan& p) { return !p.args.sigma ? 0 : (p.rain ? 2 : 1); }      // DeviceModule::receive's first index
+// rcv non-null (hare_receive_*): always a launch per cast, hare_receive_reflect (hare_receive_scatter where rcv->args.sigma is set) behind
+// every cast (the last included) instead of hare_reflect.  rcv->rain: diffuse rain before the receive kernel of every cast but the last,
+// hare_receive_scatter_rain in hare_receive_scatter's place.
 int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, void* d_rays, const void* d_e1, const void* d_e2,
                        int32_t casts, uint32_t flags, void* d_work, void* d_all, void* d_last, void* d_ctr, void* d_ctr_casts, hipStream_t st,
-                       const ReceiveArgs* rcv = nullptr, const RainWork* rain = nullptr, bool directional = false);
+                       const ReceivePlan* rcv = nullptr);
 uint32_t sanitize_flags(const Scene& s, uint32_t flags);
 int dev_free(const HipApi* H, void*& p);
 void free_bounce_buffers(const HipApi* H, Scene& s);          // bounce.cpp
@@ -345,9 +350,17 @@ int32_t scene_bands(const Scene& s, int32_t top);             // B of Model[top]
 int receive_check_args(const char* who, const Scene& s, uint32_t flags, int32_t kind, int32_t top, int64_t n, int32_t bounces, int32_t n_bins, double bin_len,
                        int32_t frac_bits);
 bool scene_has_scattering(const Scene& s, int32_t top);       // Model[top] has a scattering table (hare_receive_scatter)
-// ray_base: the global index of the call's ray 0 (the scattering RNG's g = ray_base + i)
-int receive_args(const Scene& s, int32_t top, int32_t n_bins, double bin_len, int32_t frac_bits, void* d_state, void* d_hist, void* d_det,
-                 bool init_state, int64_t ray_base, ReceiveArgs& ra);
+bool receive_rains(const Scene& s, int32_t top, uint32_t flags);      // rain needs a scattering table: without one the flag changes nothing
+// K x n_bins x B (x 4: HARE_RECEIVE_DIRECTIONAL) with K the scene's receiver count, or min_K where fewer are set (the checks that run before
+// "no receivers" is found count one)
+size_t receive_hist_words(const Scene& s, int32_t top, int32_t n_bins, uint32_t flags, size_t min_K = 0);
+// flags: the call's HARE_RECEIVE_* bits; d_work: the loop's work array (with rain: HARE_RECEIVE_RAIN_WORK_BYTES(n));
+// ray_base: the global index of the call's ray 0 (the scattering RNG's g = ray_base + i).  Receivers and tables must be on the device
+int receive_plan(const Scene& s, int32_t top, uint32_t flags, int64_t n, int32_t n_bins, double bin_len, int32_t frac_bits, void* d_state,
+                 void* d_hist, void* d_det, void* d_work, bool init_state, int64_t ray_base, ReceivePlan& p);
+// One cast's receive step on the stream: the rain's launches (p.rain, but behind the last cast), then the receive kernel
+int receive_step(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, const ReceivePlan& p, void* d_rays, const void* d_ev,
+                 int32_t* marks, unsigned char* block_live, int32_t cast, bool last_cast, hipStream_t st);
 int receive_ready(Scene& s, const HipApi* H, const char* who);
 
 // device plumbing (device_scene.cpp) shared with api.cpp, launch.cpp and build_gpu.cpp

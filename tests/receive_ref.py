@@ -1,16 +1,13 @@
-"""numpy restatement of the directional receivers (include/hare_hip.h, "receivers", "Directional"), operation for operation in FP64:
-the receiver step and the rain deposit with four channels per histogram word -- W, the omni word of tests/receiver_ref.py and
-tests/rain_ref.py, and X, Y, Z, the add weighted by the unit vector towards where the sound came from, as int64 in two's complement --
-inside one cast-by-cast loop that serves the three receive loops: specular (no table), scattering (tests/scatter_ref.py's choice, weights
-and directions, called unchanged) and diffuse rain (tests/rain_ref.py's eligibility, shadow queries and suppression, restated here
-because the deposit sits inside its step).  numpy evaluates every product, quotient and sum on its own (no contraction) and its sqrt and
-division are correctly rounded, so the library's results must match it bit for bit."""
+"""numpy restatement of the receive loop (include/hare_hip.h, "receivers"), operation for operation in FP64: the receiver step, the rain
+step ("Diffuse rain"), the deposit in its omni and its directional ("Directional") form, and the one cast-by-cast loop that serves every
+mode -- specular (no table), scattering (tests/scatter_ref.py's RNG, choice, weights and directions) and diffuse rain, each with one word
+or four channels per band.  numpy evaluates every product, quotient and sum on its own (no contraction), in the order written here, and
+its sqrt and division are correctly rounded, so the library's results must match it bit for bit."""
 import numpy as np
 
-from tests.rain_ref import side_normals
-from tests.receiver_ref import TWO63
 from tests.scatter_ref import choose, normals_of, ray_base, scatter_rays, uniform, weights
 
+TWO63 = 9223372036854775808.0
 TWO62 = 4611686018427387904.0
 
 
@@ -22,6 +19,11 @@ def magnitude(v, frac_bits):
         return np.minimum(m, TWO63)
 
 
+def quantise(E, frac_bits):
+    """q_b = rint(m_b) -> uint64."""
+    return np.rint(magnitude(E, frac_bits)).astype(np.uint64)
+
+
 def signed_words(m, a):
     """s_i = (int64) rint(min(max(m * a_i, -2^62), 2^62)), 0 for NaN, as the uint64 word that is added."""
     with np.errstate(invalid="ignore", over="ignore"):
@@ -31,21 +33,30 @@ def signed_words(m, a):
     return np.rint(v).astype(np.int64).view(np.uint64)
 
 
-def add_words(hist, k, bins, m, a, counts=None):
-    """hist[k, bin, b, :] += (rint(m_b), s_0, s_1, s_2) for every add: m [B, m'], a three arrays [m'] (the arrival vector).
+def deposit(hist, k, bins, v, frac_bits, arrival, counts=None):
+    """The one thing the omni and the directional form differ in.  v [B, m'] is the energy of every add.
+    hist [K, n_bins, B]: hist[k, bin, b] += q_b.  hist [K, n_bins, B, 4]: hist[k, bin, b, :] += (q_b, s_0, s_1, s_2) with
+    arrival() -> three arrays [m'], the unit vector towards where the sound came from (not evaluated for the omni form).
     counts [K, n_bins] (optional) collects the number of adds into each (receiver, bin): the same for every band and channel."""
     if counts is not None:
         np.add.at(counts[k], bins, 1)
+    m = magnitude(v, frac_bits)
+    a = arrival() if hist.ndim == 4 else None
     with np.errstate(over="ignore"):
         for b in range(hist.shape[2]):
+            if a is None:
+                np.add.at(hist[k, :, b], bins, np.rint(m[b]).astype(np.uint64))
+                continue
             np.add.at(hist[k, :, b, 0], bins, np.rint(m[b]).astype(np.uint64))
             for i in range(3):
                 np.add.at(hist[k, :, b, 1 + i], bins, signed_words(m[b], a[i]))
 
 
-def receiver_step_dir(o, d, t_end, L, E, centers, radii, n_bins, bin_len, frac_bits, hist, det, counts=None):
-    """tests/receiver_ref.py's receiver_step with the four channels: hist [K, n_bins, B, 4].  a is one vector per ray, the same for
-    every receiver: len = sqrt((dx*dx + dy*dy) + dz*dz), a = (-(dx / len), -(dy / len), -(dz / len))."""
+def receiver_step(o, d, t_end, L, E, centers, radii, n_bins, bin_len, frac_bits, hist, det, counts=None):
+    """One cast's receiver step for the live rays given: o, d [m, 3]; t_end [m] (+inf for a miss); L [m]; E [B, m].
+    hist [K, n_bins, B] or [K, n_bins, B, 4] and det [K, 2] (uint64) are accumulated into (wrapping mod 2^64).  The arrival vector of
+    the directional form is one per ray, the same for every receiver: len = sqrt((dx*dx + dy*dy) + dz*dz),
+    a = (-(dx / len), -(dy / len), -(dz / len))."""
     o = np.asarray(o, np.float64).reshape(-1, 3)
     d = np.asarray(d, np.float64).reshape(-1, 3)
     E = np.asarray(E, np.float64).reshape(hist.shape[2], -1)
@@ -55,8 +66,6 @@ def receiver_step_dir(o, d, t_end, L, E, centers, radii, n_bins, bin_len, frac_b
     dx, dy, dz = d[:, 0], d[:, 1], d[:, 2]
     with np.errstate(all="ignore"):
         dd = (dx * dx + dy * dy) + dz * dz
-        ln = np.sqrt(dd)
-        a = (-(dx / ln), -(dy / ln), -(dz / ln))
         for k in range(centers.shape[0]):
             cx, cy, cz = centers[k]
             wx = cx - ox
@@ -73,12 +82,30 @@ def receiver_step_dir(o, d, t_end, L, E, centers, radii, n_bins, bin_len, frac_b
             det[k, 1] += np.uint64(np.count_nonzero(detected & ~binned))
             if binned.any():
                 bins = np.floor(x[binned]).astype(np.int64)
-                add_words(hist, k, bins, magnitude(E[:, binned], frac_bits), [c[binned] for c in a], counts)
+
+                def arrival():
+                    ln = np.sqrt(dd[binned])
+                    return -(dx[binned] / ln), -(dy[binned] / ln), -(dz[binned] / ln)
+                deposit(hist, k, bins, E[:, binned], frac_bits, arrival, counts)
 
 
-def rain_step_dir(part, x, nprime, pid, length, Lp, Ea, sg, centers, radii, n_bins, bin_len, frac_bits, hist, det, stats=None, nthreads=16,
-                  counts=None):
-    """tests/rain_ref.py's rain_step with the four channels: a = (-(vx / dist), -(vy / dist), -(vz / dist)) per deposit."""
+receiver_step_dir = receiver_step           # the directional form is chosen by hist's shape
+
+
+def side_normals(d, n):
+    """n' = dot3(d, n) > 0 ? -n : n (the side the ray came from)."""
+    d = np.asarray(d, np.float64).reshape(-1, 3)
+    n = np.asarray(n, np.float64).reshape(-1, 3)
+    dn = (d[:, 0] * n[:, 0] + d[:, 1] * n[:, 1]) + d[:, 2] * n[:, 2]
+    return np.where((dn > 0)[:, None], -n, n)
+
+
+def rain_step(part, x, nprime, pid, length, Lp, Ea, sg, centers, radii, n_bins, bin_len, frac_bits, hist, det, stats=None, nthreads=16,
+              counts=None):
+    """The rain of m rays that take part: X_Points x [m, 3], side normals n' [m, 3], Poly_id [m], len [m], L' [m], Ea [B, m] and
+    sg [B, m] (the sigma rows).  The shadow queries run through the oracle partition's shoot (poly_origin1 = Poly_id; occluded =
+    hit && t < 1.0).  hist and det are accumulated into as in receiver_step; the arrival vector of the directional form is
+    a = (-(vx / dist), -(vy / dist), -(vz / dist)) per deposit.  stats (dict, optional) counts the eligible and the occluded queries."""
     centers = np.asarray(centers, np.float64).reshape(-1, 3)
     rr = np.asarray(radii, np.float64) * np.asarray(radii, np.float64)
     with np.errstate(all="ignore"):
@@ -108,17 +135,23 @@ def rain_step_dir(part, x, nprime, pid, length, Lp, Ea, sg, centers, radii, n_bi
             if binned.any():
                 bins = np.floor(xb[binned]).astype(np.int64)
                 sel = vis[binned]
-                m = magnitude((Ea[:, sel] * sg[:, sel]) * w[binned], frac_bits)      # ((Ea * sg) * w) * 2^frac_bits
-                db = dist[binned]
-                add_words(hist, k, bins, m, (-(vx[sel] / db), -(vy[sel] / db), -(vz[sel] / db)), counts)
+
+                def arrival():
+                    db = dist[binned]
+                    return -(vx[sel] / db), -(vy[sel] / db), -(vz[sel] / db)
+                deposit(hist, k, bins, (Ea[:, sel] * sg[:, sel]) * w[binned], frac_bits, arrival, counts)   # ((Ea * sg) * w) * 2^frac_bits
 
 
-def directional_receive_loop(po, topo, part, rays, bounces, centers, radii, n_bins, bin_len, frac_bits, alpha=None, sigma=None, seed=0,
-                             state_in=None, g0=0, rain=False, stats=None, nthreads=16, counts=None):
-    """The receive loop with HARE_RECEIVE_DIRECTIONAL, cast by cast with part.shoot (an oracle partition): specular without a table,
-    scattering with one, diffuse rain with rain=True (which, as in the library, changes nothing without a table).
-    counts: an int64 array [K, n_bins] that collects the adds per (receiver, bin), or None.
-    Returns (hist [K, n_bins, B, 4] uint64, det [K, 2], state [1 + B, n], the final rays [n, 6])."""
+def receive_loop(po, topo, part, rays, bounces, centers, radii, n_bins, bin_len, frac_bits, alpha=None, sigma=None, seed=0, state_in=None,
+                 g0=0, rain=False, directional=False, keep_rays_after=None, stats=None, counts=None, nthreads=16, events=None):
+    """The receive loop, cast by cast: part.shoot (an oracle partition) on the live rays, the receiver step, the state update, then (but
+    behind the last cast) the choice, the rain, the weights and the reflection -- specular rays with the oracle's reflection, diffuse
+    ones with tests/scatter_ref.py's.  sigma: the scattering table (None: specular).  rain: diffuse rain, with the receiver step skipped
+    for the segment behind a diffuse reflection (as in the library, it changes nothing without a table).  directional: four channels
+    per band.  g0: the global index of ray 0.  counts: an int64 array [K, n_bins] that collects the adds per (receiver, bin), or None.
+    events [bounces, n] (e.g. tests.helpers.oracle_bounce_loop): replay these recorded events of every cast instead of shooting.
+    Returns (hist [K, n_bins, B] or [K, n_bins, B, 4] uint64, det [K, 2], state [1 + B, n], the rays [n, 6] behind cast
+    `keep_rays_after`, or the final ones)."""
     rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
     n = rays.shape[0]
     B = 1
@@ -126,7 +159,7 @@ def directional_receive_loop(po, topo, part, rays, bounces, centers, radii, n_bi
         if t is not None:
             B = np.asarray(t).shape[1]
     K = np.asarray(centers).reshape(-1, 3).shape[0]
-    hist = np.zeros((K, n_bins, B, 4), np.uint64)
+    hist = np.zeros((K, n_bins, B, 4) if directional else (K, n_bins, B), np.uint64)
     det = np.zeros((K, 2), np.uint64)
     if state_in is None:
         L, E = np.zeros(n), np.ones((B, n))
@@ -139,18 +172,18 @@ def directional_receive_loop(po, topo, part, rays, bounces, centers, radii, n_bi
     e1 = np.full(n, -1, np.int32)
     live = np.ones(n, bool)
     rained = np.zeros(n, bool)              # the segment behind a diffuse reflection: deposited by the rain, not detected
+    kept = None
     for c in range(bounces):
         ev = np.zeros(n, po.XEVENT_DTYPE)
         ev["poly_id"] = -1
         if live.any():
-            ev_live, _ = part.shoot(cur[live], excl1=e1[live], nthreads=nthreads)
-            ev[live] = ev_live
+            ev[live] = events[c][live] if events is not None else part.shoot(cur[live], excl1=e1[live], nthreads=nthreads)[0]
         hit = ev["hit"] == 1
         t_end = np.where(hit, ev["t"], np.inf)
         seen = live & ~rained
         if seen.any():
-            receiver_step_dir(cur[seen, :3], cur[seen, 3:], t_end[seen], L[seen], E[:, seen], centers, radii, n_bins, bin_len, frac_bits,
-                              hist, det, counts)
+            receiver_step(cur[seen, :3], cur[seen, 3:], t_end[seen], L[seen], E[:, seen], centers, radii, n_bins, bin_len, frac_bits,
+                          hist, det, counts)
         upd = live & hit
         if alpha is not None:
             a = np.asarray(alpha, np.float64)[ev["poly_id"][upd]].T          # [B, m]
@@ -171,15 +204,23 @@ def directional_receive_loop(po, topo, part, rays, bounces, centers, radii, n_bi
                         d = cur[ti, 3:]
                         length = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
                         x = np.stack([ev["x"][ti], ev["y"][ti], ev["z"][ti]], axis=1)
-                        rain_step_dir(part, x, side_normals(d, normals[pid[t]]), pid[t], length, L[ti], E[:, ti], srow[t].T, centers, radii,
-                                      n_bins, bin_len, frac_bits, hist, det, stats=stats, nthreads=nthreads, counts=counts)
+                        rain_step(part, x, side_normals(d, normals[pid[t]]), pid[t], length, L[ti], E[:, ti], srow[t].T, centers, radii,
+                                  n_bins, bin_len, frac_bits, hist, det, stats=stats, nthreads=nthreads, counts=counts)
                     rained[idx[diff]] = True
                 E[:, idx] = E[:, idx] * weights(srow, p, diff).T
                 di = idx[diff]
                 if di.size:
                     nxt[di] = scatter_rays(cur[di], ev[di], normals, base[di], c)
             cur = nxt
+            if keep_rays_after == c:
+                kept = cur.copy()
         e1 = np.where(upd, ev["poly_id"], -2).astype(np.int32)
         live = upd
-    return hist, det, np.concatenate([L[None], E], axis=0), cur
+    return hist, det, np.concatenate([L[None], E], axis=0), cur if keep_rays_after is None else kept
 
+
+def replay_loop(po, topo, rays, events, centers, radii, n_bins, bin_len, frac_bits, alpha=None, state_in=None):
+    """The specular receive loop from the bounce loop's recorded events of every cast (events [bounces, n]): receive_loop with nothing
+    shot.  Returns (hist [K, n_bins, B], det [K, 2], state [1 + B, n])."""
+    return receive_loop(po, topo, None, rays, events.shape[0], centers, radii, n_bins, bin_len, frac_bits, alpha=alpha, state_in=state_in,
+                        events=events)[:3]

@@ -1,11 +1,8 @@
 """numpy restatement of the receive loop's diffuse scattering (include/hare_hip.h, "receivers", "Scattering"): the counter-based RNG, the
 diffuse / specular choice, the band weights and the cosine-distributed direction, operation for operation in FP64 (numpy evaluates every
-product and sum on its own: no contraction), and a cast-by-cast receive loop that shoots with the oracle's partition, runs the receiver step
-of tests/receiver_ref.py and reflects specular rays with the oracle's reflection, diffuse ones with this restatement.  The library's
-results must match it bit for bit."""
+product and sum on its own: no contraction).  tests/receive_ref.py's cast-by-cast loop calls these; the library's results must match it
+bit for bit."""
 import numpy as np
-
-from tests.receiver_ref import receiver_step
 
 G = np.uint64(0x9E3779B97F4A7C15)
 M1 = np.uint64(0xBF58476D1CE4E5B9)
@@ -117,61 +114,3 @@ def scatter_rays(rays, ev, normals, base, c):
 def normals_of(topo):
     """PolyRec::n of every polygon: the normals the oracle's reflection uses (Topology.Normal)."""
     return np.asarray(topo.normals, np.float64).reshape(-1, 3)
-
-
-def scatter_receive_loop(po, topo, part, rays, bounces, centers, radii, n_bins, bin_len, frac_bits, alpha=None, sigma=None, seed=0,
-                         state_in=None, g0=0, keep_rays_after=None, nthreads=16):
-    """The receive loop with scattering, cast by cast: part.shoot (an oracle partition) on the live rays, the receiver step, the state
-    update, then (but behind the last cast) the choice, the weights and the reflection.  g0: the global index of ray 0.
-    Returns (hist [K, n_bins, B], det [K, 2], state [1 + B, n], rays after cast `keep_rays_after` or None)."""
-    rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
-    n = rays.shape[0]
-    B = 1
-    for t in (alpha, sigma):
-        if t is not None:
-            B = np.asarray(t).shape[1]
-    K = np.asarray(centers).reshape(-1, 3).shape[0]
-    hist = np.zeros((K, n_bins, B), np.uint64)
-    det = np.zeros((K, 2), np.uint64)
-    if state_in is None:
-        L, E = np.zeros(n), np.ones((B, n))
-    else:
-        st = np.array(state_in, np.float64).reshape(1 + B, n)
-        L, E = st[0].copy(), st[1:].copy()
-    normals = normals_of(topo)
-    base = ray_base(seed, np.arange(g0, g0 + n, dtype=np.uint64))
-    cur = rays.copy()
-    e1 = np.full(n, -1, np.int32)
-    live = np.ones(n, bool)
-    kept = None
-    for c in range(bounces):
-        ev = np.zeros(n, po.XEVENT_DTYPE)
-        ev["poly_id"] = -1
-        if live.any():
-            ev_live, _ = part.shoot(cur[live], excl1=e1[live], nthreads=nthreads)
-            ev[live] = ev_live
-        hit = ev["hit"] == 1
-        t_end = np.where(hit, ev["t"], np.inf)
-        if live.any():
-            receiver_step(cur[live, :3], cur[live, 3:], t_end[live], L[live], E[:, live], centers, radii, n_bins, bin_len, frac_bits, hist, det)
-        upd = live & hit
-        if alpha is not None:
-            a = np.asarray(alpha, np.float64)[ev["poly_id"][upd]].T          # [B, m]
-            E[:, upd] = E[:, upd] * (1.0 - a)
-        L[upd] = L[upd] + ev["t"][upd]
-        if c + 1 < bounces:
-            nxt = po.reflect_batch(topo, cur, ev)
-            if sigma is not None and upd.any():
-                idx = np.nonzero(upd)[0]
-                srow = np.asarray(sigma, np.float64)[ev["poly_id"][idx]]
-                p, diff = choose(srow, uniform(base[idx], c, 0))
-                E[:, idx] = E[:, idx] * weights(srow, p, diff).T
-                di = idx[diff]
-                if di.size:
-                    nxt[di] = scatter_rays(cur[di], ev[di], normals, base[di], c)
-            cur = nxt
-            if keep_rays_after == c:
-                kept = cur.copy()
-        e1 = np.where(upd, ev["poly_id"], -2).astype(np.int32)
-        live = upd
-    return hist, det, np.concatenate([L[None], E], axis=0), kept

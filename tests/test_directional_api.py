@@ -1,5 +1,5 @@
 """Directional receivers (include/hare_hip.h, "receivers", "Directional") without a GPU: the flag is a bit of its own and every binding
-repeats it; the numpy restatement the GPU tests compare against (tests/directional_ref.py) gives the hand-worked words for two rays and
+repeats it; the numpy restatement the GPU tests compare against (tests/receive_ref.py) gives the hand-worked words for two rays and
 one rain deposit, its channel 0 is the omni restatements' histogram word for word and its signed channels stay within channel 0 plus
 the adds; the argument checks that need no device see the four-fold histogram; the C++ mirror passes the flag."""
 import os
@@ -11,11 +11,8 @@ import numpy as np
 import hare_amd as H
 from hare_amd import capi
 from oracle import pyoracle as po
-from tests.directional_ref import directional_receive_loop, receiver_step_dir
 from tests.helpers import oracle_bounce_loop
-from tests.rain_ref import rain_receive_loop
-from tests.receiver_ref import receive_loop
-from tests.scatter_ref import scatter_receive_loop
+from tests.receive_ref import receive_loop, receiver_step_dir, replay_loop
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "hare_hip.h")
@@ -103,8 +100,8 @@ def test_one_rain_deposit_by_hand():
     sigma = np.ones((2, 1))
     n_bins, bin_len, frac = 16, 0.5, 40
     stats = {}
-    hist, det, state, _ = directional_receive_loop(po, To, part, ray, 2, c, r, n_bins, bin_len, frac, sigma=sigma, seed=5, rain=True,
-                                                   stats=stats, nthreads=1)
+    hist, det, state, _ = receive_loop(po, To, part, ray, 2, c, r, n_bins, bin_len, frac, sigma=sigma, seed=5, rain=True, directional=True,
+                                       stats=stats, nthreads=1)
     assert stats == {"eligible": 1, "occluded": 0} and det.tolist() == [[1, 0]]
     # v = (0, 3, 4), dist = 5, w = (4 / 5) * (0.25 / 25) = 0.008, bin (0.5 + 5 / 2) / 0.5 = 6 (tests/test_rain_api.py); the energy comes
     # from the receiver's side of the X_Point, so it arrives from -v / dist = (-0, -0.6, -0.8)
@@ -114,7 +111,7 @@ def test_one_rain_deposit_by_hand():
     want = np.zeros((1, n_bins, 1, 4), np.int64)
     want[0, 6, 0] = [w, 0, y, z]
     assert np.array_equal(hist.view(np.int64), want)
-    omni, det0, state0, _ = rain_receive_loop(po, To, part, ray, 2, c, r, n_bins, bin_len, frac, sigma=sigma, seed=5, nthreads=1)
+    omni, det0, state0, _ = receive_loop(po, To, part, ray, 2, c, r, n_bins, bin_len, frac, sigma=sigma, seed=5, rain=True, nthreads=1)
     assert np.array_equal(hist[..., 0], omni) and np.array_equal(det, det0) and state.tobytes() == state0.tobytes()
 
 
@@ -130,13 +127,13 @@ def test_channel_0_is_the_omni_restatement_and_the_signed_channels_are_bounded()
     sigma, alpha = rng.uniform(0, 1, (To.P, 3)), rng.uniform(0, 0.5, (To.P, 3))
     casts, n_bins, bin_len, frac = 4, 200, 0.1, 30
     ev, _ = oracle_bounce_loop(po, To, o, rays, casts)
-    omni = {"specular": receive_loop(po, To, rays, ev, c, r, n_bins, bin_len, frac, alpha=alpha),
-            "scatter": scatter_receive_loop(po, To, o, rays, casts, c, r, n_bins, bin_len, frac, alpha=alpha, sigma=sigma, seed=3)[:3],
-            "rain": rain_receive_loop(po, To, o, rays, casts, c, r, n_bins, bin_len, frac, alpha=alpha, sigma=sigma, seed=3)[:3]}
+    omni = {"specular": replay_loop(po, To, rays, ev, c, r, n_bins, bin_len, frac, alpha=alpha),
+            "scatter": receive_loop(po, To, o, rays, casts, c, r, n_bins, bin_len, frac, alpha=alpha, sigma=sigma, seed=3)[:3],
+            "rain": receive_loop(po, To, o, rays, casts, c, r, n_bins, bin_len, frac, alpha=alpha, sigma=sigma, seed=3, rain=True)[:3]}
     for what, (h0, d0, s0) in omni.items():
         counts = np.zeros((3, n_bins), np.int64)
-        h, d, s, _ = directional_receive_loop(po, To, o, rays, casts, c, r, n_bins, bin_len, frac, alpha=alpha,
-                                              sigma=None if what == "specular" else sigma, seed=3, rain=what == "rain", counts=counts)
+        h, d, s, _ = receive_loop(po, To, o, rays, casts, c, r, n_bins, bin_len, frac, alpha=alpha, sigma=None if what == "specular" else sigma,
+                                  seed=3, rain=what == "rain", directional=True, counts=counts)
         assert h.shape == (3, n_bins, 3, 4) and h0.sum() > 0, what
         assert np.array_equal(h[..., 0], h0), what
         assert np.array_equal(d, d0) and s.tobytes() == s0.tobytes(), what

@@ -1,5 +1,5 @@
 """Directional receivers on the MI355X (include/hare_hip.h, "receivers", "Directional"): with HARE_RECEIVE_DIRECTIONAL the four channels
-of the histogram, the detections, the final state and the rays equal, byte for byte, the numpy restatement (tests/directional_ref.py)
+of the histogram, the detections, the final state and the rays equal, byte for byte, the numpy restatement (tests/receive_ref.py)
 -- the shoebox under the three partitions, the hall, the room whose interior wall occludes some of the rain's queries; one band and
 eight; the live-block list on and off; the aggregated and the naive add; with no table, with a scattering table, with table and rain.
 Channel 0, detections, state and rays are those of the call without the flag; the sharded call is the one-device call; the device call
@@ -9,7 +9,7 @@ import pytest
 
 import hare_amd as H
 from oracle import pyoracle as po
-from tests.directional_ref import directional_receive_loop
+from tests.receive_ref import receive_loop
 from tests.test_gpu_rain import partition_room, partitions
 from tests.test_gpu_receivers import alpha_table, receivers, source
 from tests.test_gpu_scattering import sigma_table
@@ -58,8 +58,8 @@ def check_directional(part, To, o, rays, centers, radii, B, seed, mode, what, pa
     alpha, sigma = setup(part, To.P, centers, radii, B, seed, mode)
     rain = mode == "rain"
     stats = {}
-    want_h, want_d, want_s, _ = directional_receive_loop(po, To, o, rays, BOUNCES, centers, radii, N_BINS, BIN_LEN, FRAC, alpha=alpha,
-                                                         sigma=sigma, seed=seed, rain=rain, stats=stats)
+    want_h, want_d, want_s, _ = receive_loop(po, To, o, rays, BOUNCES, centers, radii, N_BINS, BIN_LEN, FRAC, alpha=alpha, sigma=sigma, seed=seed,
+                                            rain=rain, directional=True, stats=stats)
     assert want_d[:, 0].sum() > 0 and np.any(want_h[..., 1:] != 0), what
     if rain:
         assert stats["eligible"] > 0, what
@@ -79,8 +79,8 @@ def check_directional(part, To, o, rays, centers, radii, B, seed, mode, what, pa
     part.set_option("bounce_pack", 1).set_option("receive_aggregate", 1)
     if device:
         # the rays: two casts (every ray of the burst is reflected once), through the device call, with and without the flag
-        *_, want_rays = directional_receive_loop(po, To, o, rays, 2, centers, radii, N_BINS, BIN_LEN, FRAC, alpha=alpha, sigma=sigma,
-                                                 seed=seed, rain=rain)
+        *_, want_rays = receive_loop(po, To, o, rays, 2, centers, radii, N_BINS, BIN_LEN, FRAC, alpha=alpha, sigma=sigma, seed=seed, rain=rain,
+                                     directional=True)
         a, _, _ = device_run(torch, part, rays, 2, B, rain, True)
         b, _, _ = device_run(torch, part, rays, 2, B, rain, False)
         assert a["d_rays"].tobytes() == want_rays.tobytes(), (what, mode, np.argwhere(a["d_rays"] != want_rays)[:5])

@@ -1,5 +1,5 @@
 """Diffuse rain in the receive loop on the MI355X (include/hare_hip.h, "receivers", "Diffuse rain"): with HARE_RECEIVE_DIFFUSE_RAIN the
-histogram, detections and final state equal, byte for byte, the numpy restatement (tests/rain_ref.py) whose shadow queries run through
+histogram, detections and final state equal, byte for byte, the numpy restatement (tests/receive_ref.py) whose shadow queries run through
 the oracle's partition -- the shoebox, the hall and a room with an interior wall that occludes some of them; the three partitions; one band
 and eight; one receiver, three and seventeen; the live-block list on and off.  Rain changes deposits only (rays and state are the call's
 without it); without a scattering table, or with an all-zero one, it changes nothing; the sharded call is the one-device call; in a convex
@@ -10,7 +10,7 @@ import pytest
 
 import hare_amd as H
 from oracle import pyoracle as po
-from tests.rain_ref import rain_receive_loop
+from tests.receive_ref import receive_loop
 from tests.test_gpu_receivers import alpha_table, receivers
 from tests.test_gpu_scattering import sigma_table
 
@@ -47,8 +47,8 @@ def check_rain(part, To, o, rays, centers, radii, B, seed, what, packs=(1, 0)):
     part.set_scattering(sigma)
     part.set_option("scatter_seed", seed)
     stats = {}
-    want_h, want_d, want_s, _ = rain_receive_loop(po, To, o, rays, BOUNCES, centers, radii, N_BINS, BIN_LEN, FRAC, alpha=alpha, sigma=sigma,
-                                                  seed=seed, stats=stats)
+    want_h, want_d, want_s, _ = receive_loop(po, To, o, rays, BOUNCES, centers, radii, N_BINS, BIN_LEN, FRAC, alpha=alpha, sigma=sigma, seed=seed,
+                                            rain=True, stats=stats)
     assert stats["eligible"] > 0 and want_d[:, 0].sum() > 0, what
     for pack in packs:
         part.set_option("bounce_pack", pack)

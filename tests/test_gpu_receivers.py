@@ -1,5 +1,5 @@
 """Receivers on the MI355X (include/hare_hip.h, "receivers"): the energy-time histogram, the detections and the final ray state of the
-receive loop must equal, bit for bit, the numpy restatement (tests/receiver_ref.py) run on the oracle's bounce loop (every cast's events
+receive loop must equal, bit for bit, the numpy restatement (tests/receive_ref.py) run on the oracle's bounce loop (every cast's events
 from tests.helpers.oracle_bounce_loop, every cast's rays rebuilt with the oracle's reflection).  Closed rooms (the shoebox, the hall) with
 receivers near and far from a burst source, an open soup where rays escape and half-lines count; the three partitions; one band and
 eight; the live-block list on and off; the fused-loop option on and off (the receive loop never fuses); batch sizes that are not a
@@ -10,7 +10,7 @@ import pytest
 import hare_amd as H
 from oracle import pyoracle as po
 from tests.helpers import oracle_bounce_loop, soup, soup_rays
-from tests.receiver_ref import receive_loop
+from tests.receive_ref import replay_loop
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +46,7 @@ def check_receive(part, To, o, rays, centers, radii, B, what, combos, state_in=N
     part.set_receivers(centers, radii)
     if alpha is not None:
         part.set_absorption(alpha)
-    want_h, want_d, want_s = receive_loop(po, To, rays, ref_ev, centers, radii, N_BINS, BIN_LEN, FRAC, alpha=alpha, state_in=state_in)
+    want_h, want_d, want_s = replay_loop(po, To, rays, ref_ev, centers, radii, N_BINS, BIN_LEN, FRAC, alpha=alpha, state_in=state_in)
     assert want_d[:, 0].sum() > 0, what                              # the case detects something
     for pack, fused in combos:
         part.set_option("bounce_pack", pack)
@@ -117,7 +117,7 @@ def test_sharded_call_is_byte_identical_and_state_in_is_read():
     assert one[4]["hits"] == two[4]["hits"]
     To, o = po.Topology(m.verts, m.nverts), po.VoxelGrid([po.Topology(m.verts, m.nverts)], domain=8)
     ref_ev, _ = oracle_bounce_loop(po, To, o, rays, BOUNCES)
-    want_h, want_d, want_s = receive_loop(po, To, rays, ref_ev, c, r, N_BINS, BIN_LEN, FRAC, alpha=a, state_in=st)
+    want_h, want_d, want_s = replay_loop(po, To, rays, ref_ev, c, r, N_BINS, BIN_LEN, FRAC, alpha=a, state_in=st)
     assert np.array_equal(one[0], want_h) and np.array_equal(one[2], want_d) and one[3].tobytes() == want_s.tobytes()
     out = np.zeros_like(one[0])
     again = parts[1].Receive_batch(rays, BOUNCES, N_BINS, BIN_LEN, energy=st, frac_bits=FRAC, out=out)
@@ -164,7 +164,7 @@ def test_device_call_accumulates_on_a_torch_stream_and_allocates_nothing():
     assert states[0].tobytes() == one_s.tobytes() and states[1].tobytes() == one_s.tobytes()
     assert int(d_ctr.cpu().numpy()[1]) == 2 * ctr["hits"]
     ref_ev, _ = oracle_bounce_loop(po, To, po.VoxelGrid([To], domain=64), rays, BOUNCES)
-    want_h, want_d, _ = receive_loop(po, To, rays, ref_ev, c, r, N_BINS, BIN_LEN, FRAC, alpha=a)
+    want_h, want_d, _ = replay_loop(po, To, rays, ref_ev, c, r, N_BINS, BIN_LEN, FRAC, alpha=a)
     assert np.array_equal(one, want_h) and np.array_equal(one_d, want_d)
     last = np.frombuffer(d_last.cpu().numpy().tobytes(), H.capi.XEVENT_DTYPE)
     assert last.tobytes() == ref_ev[BOUNCES - 1].tobytes()

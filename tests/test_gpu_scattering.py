@@ -1,5 +1,5 @@
 """Diffuse scattering in the receive loop on the MI355X (include/hare_hip.h, "receivers", "Scattering"): hare_receive_scatter's histogram,
-detections and final ray state must equal, byte for byte, the numpy restatement (tests/scatter_ref.py) run cast by cast on the oracle's
+detections and final ray state must equal, byte for byte, the numpy restatement (tests/receive_ref.py) run cast by cast on the oracle's
 partition -- closed rooms and an open soup, the three partitions, one band and eight with rows of 0 and 1, the live-block list on and off,
 batch sizes that are not a multiple of 4.  An all-zero table is no table; the scattered rays themselves match and obey the cosine law;
 the same seed gives the same bytes and another seed another histogram; the sharded call is the one-device call; the device call allocates,
@@ -10,7 +10,8 @@ import pytest
 import hare_amd as H
 from oracle import pyoracle as po
 from tests.helpers import soup, soup_rays
-from tests.scatter_ref import normals_of, scatter_receive_loop
+from tests.receive_ref import receive_loop
+from tests.scatter_ref import normals_of
 from tests.test_gpu_receivers import alpha_table, receivers
 
 pytestmark = pytest.mark.gpu
@@ -38,8 +39,7 @@ def check_scatter(part, To, o, rays, centers, radii, B, seed, what, packs=(1, 0)
         part.set_absorption(alpha)
     part.set_scattering(sigma)
     part.set_option("scatter_seed", seed)
-    want_h, want_d, want_s, _ = scatter_receive_loop(po, To, o, rays, BOUNCES, centers, radii, N_BINS, BIN_LEN, FRAC, alpha=alpha, sigma=sigma,
-                                                     seed=seed)
+    want_h, want_d, want_s, _ = receive_loop(po, To, o, rays, BOUNCES, centers, radii, N_BINS, BIN_LEN, FRAC, alpha=alpha, sigma=sigma, seed=seed)
     assert want_d[:, 0].sum() > 0, what
     for pack in packs:
         part.set_option("bounce_pack", pack)
@@ -122,8 +122,7 @@ def test_scattered_rays_match_and_follow_the_cosine_law():
     g.set_receivers(c, r)
     for sigma, seed in ((sigma_table(T.Polygon_Count, B), 5), (np.ones((T.Polygon_Count, B)), -77)):
         g.set_scattering(sigma).set_option("scatter_seed", seed)
-        _, _, want_s, want_rays = scatter_receive_loop(po, To, o, rays, 2, c, r, N_BINS, BIN_LEN, FRAC, sigma=sigma, seed=seed,
-                                                       keep_rays_after=0)
+        _, _, want_s, want_rays = receive_loop(po, To, o, rays, 2, c, r, N_BINS, BIN_LEN, FRAC, sigma=sigma, seed=seed, keep_rays_after=0)
         b = device_buffers(torch, n, len(c), B)
         b["d_rays"].copy_(torch.from_numpy(rays))
         b["d_state"].copy_(torch.from_numpy(np.concatenate([np.zeros((1, n)), np.ones((B, n))])))
@@ -178,8 +177,8 @@ def test_sharded_call_is_byte_identical_and_refuses_differing_scenes():
     for x, y in zip(one[:4], two[:4]):
         assert x.tobytes() == y.tobytes()
     To = po.Topology(m.verts, m.nverts)
-    want_h, want_d, want_s, _ = scatter_receive_loop(po, To, po.VoxelGrid([To], domain=8), rays, BOUNCES, c, r, N_BINS, BIN_LEN, FRAC,
-                                                     alpha=a, sigma=s, seed=-9)
+    want_h, want_d, want_s, _ = receive_loop(po, To, po.VoxelGrid([To], domain=8), rays, BOUNCES, c, r, N_BINS, BIN_LEN, FRAC, alpha=a, sigma=s,
+                                            seed=-9)
     assert np.array_equal(one[0], want_h) and np.array_equal(one[2], want_d) and one[3].tobytes() == want_s.tobytes()
     # the scenes must scatter alike: another seed, another table, no table
     for change, undo in ((lambda: parts[1].set_option("scatter_seed", 3), lambda: parts[1].set_option("scatter_seed", -9)),

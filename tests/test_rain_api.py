@@ -1,7 +1,7 @@
 """Diffuse rain (include/hare_hip.h, "receivers", "Diffuse rain") without a GPU: the flag's value is a bit of its own and every binding
 repeats it; the enlarged work array of hare_receive_device is what the header's formula says and what the overlap check holds a caller
-to; the numpy restatement the GPU tests compare against (tests/rain_ref.py) gives the hand-worked answer on one ray over a floor, and
-without rain it is tests/scatter_ref.py's loop."""
+to; the numpy restatement the GPU tests compare against (tests/receive_ref.py) gives the hand-worked answer on one ray over a floor, and
+without rain it is the scattering loop."""
 import os
 import re
 import subprocess
@@ -12,8 +12,7 @@ import pytest
 import hare_amd as H
 from hare_amd import capi
 from oracle import pyoracle as po
-from tests.rain_ref import rain_receive_loop
-from tests.scatter_ref import scatter_receive_loop
+from tests.receive_ref import receive_loop
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "hare_hip.h")
@@ -130,7 +129,7 @@ def test_rain_of_one_ray_over_a_floor_by_hand():
     ev, _ = part.shoot(np.array([[0.0, 0.0, 0.0, 0.0, 3.0, 4.0]]), excl1=np.array([0], np.int32))
     assert ev["hit"][0] == 1 and ev["poly_id"][0] == 1 and ev["t"][0] == 2.5
     stats = {}
-    hist, det, state, _ = rain_receive_loop(po, To, part, ray, 2, c, r, n_bins, bin_len, frac, sigma=sigma, seed=5, stats=stats, nthreads=1)
+    hist, det, state, _ = receive_loop(po, To, part, ray, 2, c, r, n_bins, bin_len, frac, sigma=sigma, seed=5, rain=True, stats=stats, nthreads=1)
     # v = (0, 3, 4), d2 = 25, n' = (0, 0, 1) (the ray came from above), cs = 4: eligible (25 > 0.25, 4 > 0) and not occluded
     w = (4.0 / 5.0) * (0.25 / 25.0)                                    # cos / dist * r^2 / d2: 0.008
     assert abs(w - 0.008) < 1e-17
@@ -143,12 +142,12 @@ def test_rain_of_one_ray_over_a_floor_by_hand():
     assert np.array_equal(hist, want) and det.tolist() == [[1, 0]]
     assert x == 6.0 and q == 8796093022
     # the state is the scattered one: L = 0.5 + t of cast 1, E = 1 (weight sigma / p = 1)
-    _, _, state_plain, _ = rain_receive_loop(po, To, part, ray, 2, c, r, n_bins, bin_len, frac, sigma=sigma, seed=5, rain=False, nthreads=1)
+    _, _, state_plain, _ = receive_loop(po, To, part, ray, 2, c, r, n_bins, bin_len, frac, sigma=sigma, seed=5, rain=False, nthreads=1)
     assert state.tobytes() == state_plain.tobytes() and state[1, 0] == 1.0
     # a receiver behind the floor's plane (cs < 0) or one the point is inside (d2 <= r^2) gets nothing
     for cc in ([[0.0, 3.0, -4.0]], [[0.0, 0.3, 0.1]]):
         s2 = {}
-        rain_receive_loop(po, To, part, ray, 2, np.array(cc), r, n_bins, bin_len, frac, sigma=sigma, seed=5, stats=s2, nthreads=1)
+        receive_loop(po, To, part, ray, 2, np.array(cc), r, n_bins, bin_len, frac, sigma=sigma, seed=5, rain=True, stats=s2, nthreads=1)
         assert s2 == {}, cc
 
 
@@ -160,11 +159,11 @@ def test_restatement_without_rain_is_the_scatter_loop():
     c, r = np.array([[4.0, 3.5, 2.0], [7.0, 2.0, 1.5]]), np.array([0.6, 0.4])
     rng = np.random.default_rng(1)
     sigma, alpha = rng.uniform(0, 1, (To.P, 3)), rng.uniform(0, 0.5, (To.P, 3))
-    a = scatter_receive_loop(po, To, o, rays, 4, c, r, 200, 0.1, 30, alpha=alpha, sigma=sigma, seed=3)
-    b = rain_receive_loop(po, To, o, rays, 4, c, r, 200, 0.1, 30, alpha=alpha, sigma=sigma, seed=3, rain=False)
+    a = receive_loop(po, To, o, rays, 4, c, r, 200, 0.1, 30, alpha=alpha, sigma=sigma, seed=3)
+    b = receive_loop(po, To, o, rays, 4, c, r, 200, 0.1, 30, alpha=alpha, sigma=sigma, seed=3, rain=False)
     for x, y in zip(a[:3], b[:3]):
         assert x.tobytes() == y.tobytes()
     # with rain: the same state, another histogram
     stats = {}
-    h, d, s, _ = rain_receive_loop(po, To, o, rays, 4, c, r, 200, 0.1, 30, alpha=alpha, sigma=sigma, seed=3, stats=stats)
+    h, d, s, _ = receive_loop(po, To, o, rays, 4, c, r, 200, 0.1, 30, alpha=alpha, sigma=sigma, seed=3, rain=True, stats=stats)
     assert s.tobytes() == a[2].tobytes() and not np.array_equal(h, a[0]) and stats["eligible"] > 1000 and stats["occluded"] == 0

@@ -1,12 +1,12 @@
 """Receivers (include/hare_hip.h, "receivers") without a GPU: the new exports are bound, every bad argument is HARE_E_INVALID before
 anything runs, the setters work on a GPU-less scene and read back, a receive call without a device is HARE_E_NODEVICE, and the numpy
-restatement the GPU tests compare against (tests/receiver_ref.py) gives the hand-worked answers on the edge cases of the definition."""
+restatement the GPU tests compare against (tests/receive_ref.py) gives the hand-worked answers on the edge cases of the definition."""
 import numpy as np
 import pytest
 
 import hare_amd as H
 from hare_amd import capi
-from tests.receiver_ref import quantise, receiver_step
+from tests.receive_ref import quantise, receiver_step
 
 NEW = ("hare_scene_set_receivers", "hare_scene_set_absorption", "hare_receive_device", "hare_receive_batch", "hare_receive_batch_sharded")
 

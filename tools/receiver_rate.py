@@ -2,7 +2,7 @@
 hare_bounce_device (last cast only) on the same burst, device-resident, HIP events on the launch stream; K = 1 / 8 / 64 receivers,
 B = 1 / 8 bands, 4 000 bins; receiver 0 is the direct-sound case (a 1 m sphere 2 m from the source: ~7 % of the rays cross it in cast 0,
 into one or two bins), timed with the wave-aggregated atomics and with the naive ones.  With --host, also the host alternative a caller
-has without the feature: Bounce_batch(all_casts=True) and the numpy restatement of the step (tests/receiver_ref.py) on every cast.
+has without the feature: Bounce_batch(all_casts=True) and the numpy restatement of the step (tests/receive_ref.py) on every cast.
 With --scatter SIGMA (K = 8, B = 8 only), the same loop again with a scattering table of SIGMA on every polygon and band (hare_receive_scatter
 in place of hare_receive_reflect; SIGMA 0 runs that kernel on exactly the rays the specular loop has); run it under rocprofv3 --kernel-trace
 for the two kernels' per-cast times.
@@ -160,7 +160,7 @@ for K, B in cases:
     print(json.dumps(row), file=sys.stderr, flush=True)
 
 if a.host:
-    from tests.receiver_ref import receive_loop
+    from tests.receive_ref import replay_loop
     from oracle import pyoracle as po
     K, B = 8, 8
     c, r = receivers(K)
@@ -169,7 +169,7 @@ if a.host:
     ev, _ = g.Bounce_batch(rays, nb, all_casts=True)
     t1 = time.perf_counter()
     To = po.Topology(mesh.verts, mesh.nverts)
-    receive_loop(po, To, rays, ev, c, r, N_BINS, BIN_LEN, FRAC, alpha=alpha)
+    replay_loop(po, To, rays, ev, c, r, N_BINS, BIN_LEN, FRAC, alpha=alpha)
     t2 = time.perf_counter()
     out["host_alternative"] = {"K": K, "B": B, "bounce_all_casts_ms": round((t1 - t0) * 1e3, 1), "numpy_step_ms": round((t2 - t1) * 1e3, 1),
                                "events_bytes": int(ev.nbytes)}
