@@ -895,6 +895,7 @@ const OptionEntry kOptionTable[] = {
         {"wide_drain", &SceneOptions::wide_drain, 0, 1},
         {"bounce_pack", &SceneOptions::bounce_pack, 0, 1},
         {"voxel_walk", &SceneOptions::voxel_walk, 0, 1},
+        {"voxel_overlap", &SceneOptions::voxel_overlap, 0, 1},
         {"voxel_skip", &SceneOptions::voxel_skip, 0, 1},
         {"receive_aggregate", &SceneOptions::receive_aggregate, 0, 1},
 };

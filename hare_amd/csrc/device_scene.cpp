@@ -69,6 +69,10 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_voxel_pool_quad", &m->voxel_pool_quad},
         {"hare_voxel_pool_tri_g", &m->voxel_pool_tri_g},
         {"hare_voxel_pool_quad_g", &m->voxel_pool_quad_g},
+        {"hare_voxel_pool_tri_ov", &m->voxel_pool_tri_ov},
+        {"hare_voxel_pool_quad_ov", &m->voxel_pool_quad_ov},
+        {"hare_voxel_pool_tri_g_ov", &m->voxel_pool_tri_g_ov},
+        {"hare_voxel_pool_quad_g_ov", &m->voxel_pool_quad_g_ov},
         {"hare_voxel_pool_tri_own", &m->voxel_pool_tri_own},
         {"hare_voxel_pool_quad_own", &m->voxel_pool_quad_own},
         {"hare_voxel_pool_tri_g_own", &m->voxel_pool_tri_g_own},

@@ -174,6 +174,7 @@ void read_env_options(SceneOptions& o)
     if (const char* t = getenv("HARE_OCTREE_TIGHT")) o.octree_tight = atoi(t) != 0;
     if (const char* t = getenv("HARE_VOXEL_TIGHT")) o.voxel_tight = atoi(t) != 0;
     if (const char* t = getenv("HARE_VOXEL_WALK")) o.voxel_walk = atoi(t) != 0;
+    if (const char* t = getenv("HARE_VOXEL_OVERLAP")) o.voxel_overlap = atoi(t) != 0;
     if (const char* t = getenv("HARE_VOXEL_SKIP")) o.voxel_skip = atoi(t) != 0;
     if (const char* t = getenv("HARE_BOUNCE_PACK")) o.bounce_pack = atoi(t) != 0;
     if (const char* t = getenv("HARE_VOXEL_ORDER")) o.voxel_order = std::max(0, std::min(2, atoi(t)));
@@ -310,6 +311,12 @@ KernChoice choose_kernel(const Scene& s, const DeviceModule* M, int32_t kind, si
         if (pool_wanted && pool_fits && have(pf)) {
             pick(Kern::VoxelPool, !coarse ? (quads ? "hare_voxel_pool_quad" : "hare_voxel_pool_tri")
                                           : (quads ? "hare_voxel_pool_quad_g" : "hare_voxel_pool_tri_g"), pf);
+            if (s.opt.voxel_overlap && !own) {      // scene option "voxel_overlap": the build with the fused round, same launch geometry
+                hipFunction_t DeviceModule::*vf = !coarse ? (quads ? &DeviceModule::voxel_pool_quad_ov : &DeviceModule::voxel_pool_tri_ov)
+                                                           : (quads ? &DeviceModule::voxel_pool_quad_g_ov : &DeviceModule::voxel_pool_tri_g_ov);
+                pick(Kern::VoxelPool, !coarse ? (quads ? "hare_voxel_pool_quad_ov" : "hare_voxel_pool_tri_ov")
+                                              : (quads ? "hare_voxel_pool_quad_g_ov" : "hare_voxel_pool_tri_g_ov"), vf);
+            }
             if (own) {         // HARE_SHOOT_COUNT_OWN: the counting build of the SAME kernel, same launch geometry
                 hipFunction_t DeviceModule::*of = !coarse ? (quads ? &DeviceModule::voxel_pool_quad_own : &DeviceModule::voxel_pool_tri_own)
                                                            : (quads ? &DeviceModule::voxel_pool_quad_g_own : &DeviceModule::voxel_pool_tri_g_own);

@@ -56,6 +56,8 @@ struct SceneOptions {
     int voxel_skip = 0;        // 1: K1q's walk crosses an EMPTY aligned block of 4^3 voxels in one operation -- the exact closed-form skip (voxel_pool.hip); bit-identical
                                // results, and slower than the hand-written step: off by default, kept as a tested option
     int voxel_walk = 1;        // 1: K1q's DDA step loop as written by hand for gfx950 (voxel_walk.h: per-axis updates under EXEC masks); 0: the compiler's loop (A/B)
+    int voxel_overlap = 0;     // 1: a bulk round of K1q may run a cull task and a walk task together, the cull's list entries requested
+                               // before the walk's step loops and consumed behind them (voxel_pool.hip); 0 (default): one phase per round -- the fused round is slower.  Chooses the kernel: hare_voxel_pool_*_ov.  Results never depend on it
     int bounce_pack = 1;       // 1: the launch-per-cast bounce loop of a Voxel_Grid lists the blocks of 64 rays in which a ray still lives behind every reflection (one
                                // more one-workgroup launch per cast) and the next cast walks the list: open scenes; 0: off (a closed room saves ~1 %)
     int wide_drain = 1;        // 1: K1q's wide cull / wide walk in the drain of a launch (voxel_pool.hip); 0: the pool's ordinary phases to the end (A/B)
@@ -109,6 +111,7 @@ struct DeviceModule {
     hipFunction_t voxel_persist_tri_g = nullptr, voxel_persist_quad_g = nullptr;
     hipFunction_t voxel_pool_tri = nullptr, voxel_pool_quad = nullptr, voxel_pool_tri_g = nullptr, voxel_pool_quad_g = nullptr;
     // counting builds of the production kernels (HARE_SHOOT_COUNT_OWN)
+    hipFunction_t voxel_pool_tri_ov = nullptr, voxel_pool_quad_ov = nullptr, voxel_pool_tri_g_ov = nullptr, voxel_pool_quad_g_ov = nullptr;   // scene option "voxel_overlap"
     hipFunction_t voxel_pool_tri_own = nullptr, voxel_pool_quad_own = nullptr, voxel_pool_tri_g_own = nullptr, voxel_pool_quad_g_own = nullptr;
     hipFunction_t octree_dense_own = nullptr;
     hipFunction_t cost_order = nullptr;                                    // order_kernels.hip

@@ -87,6 +87,13 @@
 #ifndef HARE_K1Q_HAND_WALK
 #define HARE_K1Q_HAND_WALK 1      // the DDA step loop of the walk phases as written by hand (voxel_walk.h); 0: the compiler's (A/B)
 #endif
+#ifndef HARE_K1Q_FUSE_CULL_MIN
+#define HARE_K1Q_FUSE_CULL_MIN 16  // a bulk round runs a cull task AND a walk task (the fused round, below) when the cull queue holds this many rays ...
+#define HARE_K1Q_FUSE_WALK_MIN 16  // ... and the walk queue this many (8 / 8 ... 32 / 32 swept: nothing outside the noise)
+#endif
+#ifndef HARE_K1Q_ENTRIES_GLOBAL
+#define HARE_K1Q_ENTRIES_GLOBAL 1  // the cull task's list-entry gathers as global_load (0: flat_load, as the compiler writes them through the pinned arguments; A/B)
+#endif
 #ifndef HARE_K1Q_REFILL_MIN
 #define HARE_K1Q_REFILL_MIN 64    // set up new rays when this many slots are free (a full wave of set-ups)
 #endif
@@ -112,7 +119,10 @@ constexpr bool kK1qStats = false;
 // OWN (hare_voxel_pool_*_own, round 5; flag HARE_SHOOT_COUNT_OWN): the same kernel counting ITS OWN work per lane -- voxels it walked into,
 // list entries it scanned, candidates it pre-culled, exact tests it made -- into words 2 .. 5 of the counters block: the numerator of
 // bench.py's `roofline.own` (the reference-priced figure counts voxels, entries and tests this kernel skips).  Events are identical.
-template <bool QUADS, bool COARSE, bool BOUNCE = false, bool OWN = false>
+// FUSE (hare_voxel_pool_*_ov, round 7; scene option "voxel_overlap"): the same kernel whose bulk rounds may run a cull task and a walk task together
+// ("the FUSED round", below).  A build of its own, chosen by the host: the registers held across the walk task cost the one-phase kernel 16 VGPRs
+// even where no round was fused, and 2 % at 262 144 rays.
+template <bool QUADS, bool COARSE, bool BOUNCE = false, bool OWN = false, bool FUSE = false>
 __device__ __forceinline__ void voxel_pool_body(const VoxelArgs& g_in, const ShootIO& io_in)
 {
     VoxelArgs g = g_in;
@@ -195,6 +205,10 @@ __device__ __forceinline__ void voxel_pool_body(const VoxelArgs& g_in, const Sho
     // bookkeeping -- queue choice, refill rule, fences; [7]: the step loop inside walk tasks)
     unsigned long long kq_t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, kq_last_t = __builtin_amdgcn_s_memtime();
     int kq_last_i = 9;
+    // fused rounds (a cull task and a walk task in one round: both are counted in their own slots as well).  The clock of a fused round: stage A is
+    // booked to the cull (K1Q_STAT(2) starts its interval), the walk task to the walk -- including its segment-end wait, which now also waits for
+    // the cull's gathers (loads return in issue order) -- and stage B to the cull again.
+    unsigned long long kq_fused = 0;
     // (static indices under wave-uniform compares, and a second stamp when the bookkeeping is done: the clock's own cost is in no interval)
 #define K1Q_CLOCK(i) { const unsigned long long d_ = __builtin_amdgcn_s_memtime() - kq_last_t; _Pragma("unroll") for (int k_ = 0; k_ < 10; ++k_) if (kq_last_i == k_) kq_t[k_] += d_; \
                        kq_last_i = (i); kq_last_t = __builtin_amdgcn_s_memtime(); }
@@ -359,6 +373,50 @@ __device__ __forceinline__ void voxel_pool_body(const VoxelArgs& g_in, const Sho
         } else {
             store_miss(ray);
             freed = true;
+        }
+    };
+
+    // ---- the sequential cull task's FIRST ROUND TRIP, on its own (stage A): pop the task's slots, read from LDS what addresses the loads, and
+    // REQUEST the task's list entries (HARE_K1Q_CULL_AHEAD's four 8-byte gathers) -- the loads the task's NEXT round trip, the pre-cull
+    // records, depends on.  Nothing here waits for a load: the results stay in registers (8 VGPRs, the list window and the slot) until the
+    // cull block consumes them.  A one-phase round consumes them at once -- the task as it always was; the fused round runs the walk task
+    // in between.  The ray record, the exclusions and t_start of a moved origin are NOT held: nothing is addressed by them, so the cull block
+    // requests them together with its first four records, where they cost no round trip of their own; held across the walk task (27 VGPRs
+    // in all) they pushed every build into scratch.
+    struct CullReq {
+        unsigned slot, q, qe_word;
+        unsigned long long W[HARE_K1Q_CULL_PAIRS];      // two list entries each: the first in the low word
+        bool act;
+    };
+    typedef unsigned long long ItemPair __attribute__((aligned(4)));      // 4-byte aligned is all the hardware asks of an 8-byte gather
+    auto cull_request = [&](CullReq& c) __attribute__((always_inline)) {
+        c.slot = pop(Q_cull, hC, nC, c.act);
+        K1Q_STAT(2, c.act)
+        c.q = 0; c.qe_word = 0;
+#pragma unroll
+        for (int m = 0; m < HARE_K1Q_CULL_PAIRS; ++m) c.W[m] = 0ull;
+        if (c.act) {
+            c.q = L_q[c.slot];
+            c.qe_word = L_qe[c.slot];
+#if HARE_K1Q_CULL_AHEAD
+            // the task's list entries 2 .. 2 PAIRS + 1 (entries 0 and 1 are in the slot state): 8-byte gathers whose window slides back at the
+            // end of the list so that it stays inside it
+            const unsigned qe = c.qe_word & ~QE_HERE;
+            if (qe - c.q >= 2u) {
+#pragma unroll
+                for (int m = 0; m < HARE_K1Q_CULL_PAIRS; ++m) {
+                    const unsigned k0 = 2u + 2u * (unsigned)m;
+                    const unsigned a = c.q + k0 + 1u < qe ? c.q + k0 : qe - 2u;         // the pair's window, inside [q, qe)
+                    // a GLOBAL load, said so: through the pinned argument the compiler sees a generic pointer and would write flat_load, which
+                    // counts on lgkmcnt as well -- and the walk's first LDS wait (lgkmcnt(0)) would then wait for these gathers
+#if HARE_K1Q_ENTRIES_GLOBAL
+                    c.W[m] = *(const __attribute__((address_space(1))) ItemPair*)(g.items + a);
+#else
+                    c.W[m] = *(const ItemPair*)(g.items + a);
+#endif
+                }
+            }
+#endif
         }
     };
 
@@ -540,6 +598,34 @@ __device__ __forceinline__ void voxel_pool_body(const VoxelArgs& g_in, const Sho
         const int sel = (nE >= (unsigned)HARE_K1Q_EXACT_MIN || (big == 0 && nP == 0)) ? 0
                         : ((nP >= (unsigned)HARE_K1Q_PEND_MIN || big == 0) ? 1 : (nC >= nW ? 2 : 3));
         HARE_K1Q_PHASE_FENCE();      // the set-up's scratch stores, before any phase reads them
+        // ------------------------------------------------------------------ the FUSED round (round 7; scene option "voxel_overlap")
+        // A one-phase round is a chain of dependent round trips with nothing else of the wave's in flight: the cull task waits for its slot
+        // state, then for the ray record + exclusions + list entries, then twice for four pre-cull records; the walk task's step loops touch
+        // only LDS and the VALU.  When BOTH queues are worth a task, the round runs both: the cull's list entries are requested (stage A,
+        // cull_request above), the walk task runs as it is while those loads are in flight, and the cull consumes them behind it (stage B):
+        // its records are requested at once, the ray record and exclusions beside them -- one dependent round trip less per fused round.
+        // No load is added and none is issued twice; per ray the operations and their order are what they were.
+        //  * The two tasks' slots are disjoint (a slot is in one queue), so neither sees the other's LDS or scratch writes: the walk writes the
+        //    slot state of ITS slots and the miss record of rays that leave the grid; stage A reads the state of the CULL's slots and the list,
+        //    which no kernel writes.
+        //  * The walk pushes into Q_cull behind the head stage A's pop has already moved: those rays wait for the next round.
+        //  * The fence between the walk block and the cull block stays and still matters: stage B reads the ray record and t_start, which the
+        //    set-up stored -- behind the fence above and this one.  Stage A reads nothing a phase stores to, so no fence concerns it.
+        // Loads return in issue order: the walk's segment-end loads (cell record, tight box, ray record) wait for stage A's as well, which by
+        // then have had the step loop's time; stage B's first wait leaves nothing of the walk outstanding but its stores.
+        // Not built for the BOUNCE and the counting (OWN) kernels: they sit at the 168 VGPRs of three waves per SIMD already, and the eight
+        // held registers put them into scratch (bounce tri 4 -> 14 spilled VGPRs, quad 14 -> 44; counting builds 0 -> 4; compile-time
+        // figures -- no timing was taken of those builds with it).
+        static_assert(!FUSE || (!BOUNCE && !OWN), "the fused round exists in the plain pool kernels only");
+        constexpr unsigned fuse_cull_min = HARE_K1Q_FUSE_CULL_MIN, fuse_walk_min = HARE_K1Q_FUSE_WALK_MIN;
+        const bool fuse = FUSE && !tail && !wide && (sel == 2 || sel == 3) && nC >= fuse_cull_min && nW >= fuse_walk_min;
+        CullReq creq;
+        if (fuse) {
+#ifdef HARE_K1Q_STATS
+            kq_fused++;
+#endif
+            cull_request(creq);
+        }
         if (HARE_K1Q_WIDE_WALK && wide && nW > 0) {
             K1Q_STAT(5, true)
             // -------------------------------------------------------------- the WIDE walk of the drain: several occupied voxels ahead
@@ -687,7 +773,7 @@ __device__ __forceinline__ void voxel_pool_body(const VoxelArgs& g_in, const Sho
             push(Q_walk, hW, nW, lead && !exited, slot);
             push(Q_exact, hE, nE, writer, slot);
             push(Q_free, hF, nF, lead && exited, slot);
-        } else if (tail ? nW > 0 : sel == 3) {
+        } else if (tail ? nW > 0 : (sel == 3 || fuse)) {
             // -------------------------------------------------------------- DDA walk over empty voxels (no hit pending)
             bool act;
             const unsigned slot = pop(Q_walk, hW, nW, act);
@@ -931,17 +1017,19 @@ __device__ __forceinline__ void voxel_pool_body(const VoxelArgs& g_in, const Sho
             push(Q_cull, hC, nC, lead && !found && !exhausted, slot);
             push(Q_exact, hE, nE, lead && found, slot);
             push(Q_pend, hP, nP, lead && exhausted && (xf & F_HIT) != 0u, slot);
-        } else if (tail ? nC > 0 : sel == 2) {
+        } else if (tail ? nC > 0 : (sel == 2 || fuse)) {
             // -------------------------------------------------------------- FP32 pre-cull, 2 x CULL_PAIRS candidates per ray at most
-            bool act;
-            const unsigned slot = pop(Q_cull, hC, nC, act);
-            K1Q_STAT(2, act)
+            // (stage B: what stage A requested -- just now, or in front of the walk task in a fused round -- is consumed here)
+            if (!fuse) cull_request(creq);
+            else { K1Q_CLOCK(2) }
+            const bool act = creq.act;
+            const unsigned slot = creq.slot;
             bool to_walk = false, to_cull = false, to_exact = false, to_pend = false, done_here = false;
             int share_idx = -1;
             if (act) {
                 const unsigned ray = L_ray[slot];
-                unsigned q = L_q[slot];
-                const unsigned qe_word = L_qe[slot];
+                unsigned q = creq.q;
+                const unsigned qe_word = creq.qe_word;
                 const unsigned qe = qe_word & ~QE_HERE;
                 int idx = L_idx[slot], nexti = L_nexti[slot], done1 = L_d1[slot];
                 const uint32_t xf = L_xyzf[slot];
@@ -959,9 +1047,9 @@ __device__ __forceinline__ void voxel_pool_body(const VoxelArgs& g_in, const Sho
                 share_idx = idx;
 #if HARE_K1Q_CULL_AHEAD
                 // All of the task's list entries FIRST (idx, nexti are here; the eight after them in four 8-byte gathers, their window
-                // sliding back at the end of the list so that it stays inside it), then all eight pre-cull records, then the
-                // sequential scan on the eight results: three rounds of dependent loads per task (slot state -> ray record + entries ->
-                // records) where the pair-by-pair form below had six.  The same gathers as before -- the straight-line pairs
+                // sliding back at the end of the list so that it stays inside it: cull_request, above), then all eight pre-cull records --
+                // the ray record, exclusions and t_start beside the first four -- then the sequential scan on the eight results: three
+                // rounds of dependent loads per task (slot state -> entries -> records + ray record) where the pair-by-pair form below had six.  The same gathers as before -- the straight-line pairs
                 // requested theirs whether or not the scan had ended -- and the same candidates, in the same order, kept or dropped by
                 // the same rules.
                 constexpr int NC = 2 * HARE_K1Q_CULL_PAIRS;
@@ -974,8 +1062,7 @@ __device__ __forceinline__ void voxel_pool_body(const VoxelArgs& g_in, const Sho
                     for (int m = 0; m < NC / 2; ++m) {
                         const unsigned k0 = 2u + 2u * (unsigned)m;              // entries k0, k0 + 1 of the task
                         if (left >= 2u) {
-                            const unsigned a = q + k0 + 1u < qe ? q + k0 : qe - 2u;     // the pair's window, inside [q, qe)
-                            const int2 w = *reinterpret_cast<const int2*>(g.items + a);
+                            const int2 w = make_int2((int)(unsigned)creq.W[m], (int)(unsigned)(creq.W[m] >> 32));     // requested in stage A: the pair's window, slid back at the list's end
                             E[k0] = (q + k0 + 1u == qe) ? w.y : w.x;            // window slid back by one: the entry wanted is its second
                             E[k0 + 1] = w.y;
                         } else {
@@ -1341,6 +1428,7 @@ __device__ __forceinline__ void voxel_pool_body(const VoxelArgs& g_in, const Sho
     if (lane == 0 && io.prof) {
         for (int k = 0; k < 8; ++k) { atomicAdd(&io.prof[2 * k], kq_n[k]); atomicAdd(&io.prof[2 * k + 1], kq_l[k]); }
         atomicAdd(&io.prof[16], (unsigned long long)rounds_done);
+        atomicAdd(&io.prof[17], kq_fused);
         atomicAdd(&io.prof[18], kq_n[8]); atomicAdd(&io.prof[19], kq_l[8]);
         K1Q_CLOCK(9)
         for (int k = 0; k < 10; ++k) atomicAdd(&io.prof[20 + k], kq_t[k]);
@@ -1368,6 +1456,11 @@ __global__ __launch_bounds__(64 * HARE_K1Q_WAVES) void hare_voxel_pool_tri(Voxel
 __global__ __launch_bounds__(64 * HARE_K1Q_WAVES) void hare_voxel_pool_quad(VoxelArgs g, ShootIO io) { voxel_pool_body<true, false>(g, io); }
 __global__ __launch_bounds__(64 * HARE_K1Q_WAVES) void hare_voxel_pool_tri_g(VoxelArgs g, ShootIO io) { voxel_pool_body<false, true>(g, io); }
 __global__ __launch_bounds__(64 * HARE_K1Q_WAVES) void hare_voxel_pool_quad_g(VoxelArgs g, ShootIO io) { voxel_pool_body<true, true>(g, io); }
+// scene option "voxel_overlap": the same kernels with the fused round (FUSE, above)
+__global__ __launch_bounds__(64 * HARE_K1Q_WAVES) void hare_voxel_pool_tri_ov(VoxelArgs g, ShootIO io) { voxel_pool_body<false, false, false, false, true>(g, io); }
+__global__ __launch_bounds__(64 * HARE_K1Q_WAVES) void hare_voxel_pool_quad_ov(VoxelArgs g, ShootIO io) { voxel_pool_body<true, false, false, false, true>(g, io); }
+__global__ __launch_bounds__(64 * HARE_K1Q_WAVES) void hare_voxel_pool_tri_g_ov(VoxelArgs g, ShootIO io) { voxel_pool_body<false, true, false, false, true>(g, io); }
+__global__ __launch_bounds__(64 * HARE_K1Q_WAVES) void hare_voxel_pool_quad_g_ov(VoxelArgs g, ShootIO io) { voxel_pool_body<true, true, false, false, true>(g, io); }
 // the counting builds (HARE_SHOOT_COUNT_OWN): the same events, plus the kernel's own voxels / list entries / pre-culls / exact tests
 __global__ __launch_bounds__(64 * HARE_K1Q_WAVES) void hare_voxel_pool_tri_own(VoxelArgs g, ShootIO io) { voxel_pool_body<false, false, false, true>(g, io); }
 __global__ __launch_bounds__(64 * HARE_K1Q_WAVES) void hare_voxel_pool_quad_own(VoxelArgs g, ShootIO io) { voxel_pool_body<true, false, false, true>(g, io); }

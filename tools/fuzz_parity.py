@@ -62,6 +62,12 @@ def main():
             bad = same(g.Shoot_batch(rays)[0], ref); checks += 1
             if bad: print("MISMATCH seed %d voxel D=%d n=%d hand-written loop, wide_drain 0" % (seed, D, n), bad); return 1
         g.set_option("wide_drain", 1)
+        # ... and the fused round (scene option voxel_overlap: a cull task's list entries in flight under a walk task's step loops)
+        g.set_option("voxel_overlap", 1)
+        for what, got, want in (("plain", g.Shoot_batch(rays)[0], ref), ("excl", g.Shoot_batch(rays, poly_origin1=e1, poly_origin2=e2)[0], refx)):
+            bad = same(got, want); checks += 1
+            if bad: print("MISMATCH seed %d voxel D=%d n=%d voxel_overlap %s" % (seed, D, n, what), bad); return 1
+        g.set_option("voxel_overlap", 0)
         if seed % 2 == 0:       # ... and the exact multi-voxel skip (scene option voxel_skip: empty 4^3 blocks crossed in one operation)
             g.set_option("voxel_skip", 1)
             for what, got, want in (("plain", g.Shoot_batch(rays)[0], ref), ("excl", g.Shoot_batch(rays, poly_origin1=e1, poly_origin2=e2)[0], refx)):

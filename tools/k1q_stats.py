@@ -34,6 +34,8 @@ for k, nm in enumerate(names):
     ex, ln = c[8 + 2 * k], c[8 + 2 * k + 1]
     if ex:
         print("%-32s executions per ray %.4f   lanes per execution %.1f   lane-tasks per ray %.2f" % (nm, ex / r, ln / ex, ln / r))
+if c[8 + 17]:
+    print("%-32s per ray %.4f   (a cull task and a walk task in one round, each counted above; scene option voxel_overlap)" % ("fused rounds", c[8 + 17] / r))
 ex, ln = c[8 + 18], c[8 + 19]
 if ex:
     print("%-32s executions per ray %.4f   lanes per execution %.1f   lane-tasks per ray %.2f" % ("pend step (inside pend walks)", ex / r, ln / ex, ln / r))
