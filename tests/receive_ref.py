@@ -33,15 +33,51 @@ def signed_words(m, a):
     return np.rint(v).astype(np.int64).view(np.uint64)
 
 
-def deposit(hist, k, bins, v, frac_bits, arrival, counts=None):
+TALLIES = ("saturated", "zeroed", "zeroed_nan", "zeroed_negative", "zeroed_zero", "zeroed_negative_zero", "ties", "round_to_zero",
+           "dir_clamped", "dir_nan", "wrapped")
+
+
+def tally(tallies, hist, k, bins, v, m, a, frac_bits):
+    """The classes of the definition's edge cases that one deposit call went through, added to the dict `tallies` (TALLIES): adds with
+    m == 2^63 (saturated); adds whose product v * 2^frac_bits was NaN, < 0, +0.0 or -0.0 and became 0 (zeroed, and each on its own);
+    ties (m - floor(m) == 0.5); products > 0 that round to 0; directional words clamped at +-2^62 and zeroed for NaN; and, counted
+    before the adds are made, the omni words whose sum with this call's adds passes 2^64 (wrapped)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        raw = np.asarray(v, np.float64) * np.float64(2.0 ** int(frac_bits))
+        new = {"saturated": m == TWO63, "zeroed": ~(raw > 0), "zeroed_nan": raw != raw, "zeroed_negative": raw < 0,
+               "zeroed_zero": (raw == 0) & ~np.signbit(raw), "zeroed_negative_zero": (raw == 0) & np.signbit(raw),
+               "ties": m - np.floor(m) == 0.5, "round_to_zero": (raw > 0) & (np.rint(m) == 0)}
+        if a is not None:
+            w = np.stack([m * a[i] for i in range(3)])
+            new["dir_clamped"] = np.abs(w) > TWO62
+            new["dir_nan"] = w != w
+    for name in TALLIES:
+        tallies[name] = tallies.get(name, 0) + int(np.count_nonzero(new.get(name, False)))
+    # exact sums in two 32-bit halves (fewer than 2^31 adds per call): does old + adds reach 2^64?
+    ub, inv = np.unique(bins, return_inverse=True)
+    lo32 = np.uint64(0xFFFFFFFF)
+    for b in range(hist.shape[2]):
+        q = np.rint(m[b]).astype(np.uint64)
+        hi, lo = np.zeros(ub.size, np.uint64), np.zeros(ub.size, np.uint64)
+        np.add.at(hi, inv, q >> np.uint64(32))
+        np.add.at(lo, inv, q & lo32)
+        old = hist[k, ub, b, 0] if hist.ndim == 4 else hist[k, ub, b]
+        top = (old >> np.uint64(32)) + hi + (((old & lo32) + lo) >> np.uint64(32))
+        tallies["wrapped"] += int(np.count_nonzero(top >> np.uint64(32)))
+
+
+def deposit(hist, k, bins, v, frac_bits, arrival, counts=None, tallies=None):
     """The one thing the omni and the directional form differ in.  v [B, m'] is the energy of every add.
     hist [K, n_bins, B]: hist[k, bin, b] += q_b.  hist [K, n_bins, B, 4]: hist[k, bin, b, :] += (q_b, s_0, s_1, s_2) with
     arrival() -> three arrays [m'], the unit vector towards where the sound came from (not evaluated for the omni form).
-    counts [K, n_bins] (optional) collects the number of adds into each (receiver, bin): the same for every band and channel."""
+    counts [K, n_bins] (optional) collects the number of adds into each (receiver, bin): the same for every band and channel.
+    tallies (dict, optional) collects how many adds went through each edge case of the definition (tally, above)."""
     if counts is not None:
         np.add.at(counts[k], bins, 1)
     m = magnitude(v, frac_bits)
     a = arrival() if hist.ndim == 4 else None
+    if tallies is not None:
+        tally(tallies, hist, k, bins, v, m, a, frac_bits)
     with np.errstate(over="ignore"):
         for b in range(hist.shape[2]):
             if a is None:
@@ -52,7 +88,7 @@ def deposit(hist, k, bins, v, frac_bits, arrival, counts=None):
                 np.add.at(hist[k, :, b, 1 + i], bins, signed_words(m[b], a[i]))
 
 
-def receiver_step(o, d, t_end, L, E, centers, radii, n_bins, bin_len, frac_bits, hist, det, counts=None):
+def receiver_step(o, d, t_end, L, E, centers, radii, n_bins, bin_len, frac_bits, hist, det, counts=None, tallies=None):
     """One cast's receiver step for the live rays given: o, d [m, 3]; t_end [m] (+inf for a miss); L [m]; E [B, m].
     hist [K, n_bins, B] or [K, n_bins, B, 4] and det [K, 2] (uint64) are accumulated into (wrapping mod 2^64).  The arrival vector of
     the directional form is one per ray, the same for every receiver: len = sqrt((dx*dx + dy*dy) + dz*dz),
@@ -86,7 +122,7 @@ def receiver_step(o, d, t_end, L, E, centers, radii, n_bins, bin_len, frac_bits,
                 def arrival():
                     ln = np.sqrt(dd[binned])
                     return -(dx[binned] / ln), -(dy[binned] / ln), -(dz[binned] / ln)
-                deposit(hist, k, bins, E[:, binned], frac_bits, arrival, counts)
+                deposit(hist, k, bins, E[:, binned], frac_bits, arrival, counts, tallies)
 
 
 receiver_step_dir = receiver_step           # the directional form is chosen by hist's shape
@@ -101,7 +137,7 @@ def side_normals(d, n):
 
 
 def rain_step(part, x, nprime, pid, length, Lp, Ea, sg, centers, radii, n_bins, bin_len, frac_bits, hist, det, stats=None, nthreads=16,
-              counts=None):
+              counts=None, tallies=None):
     """The rain of m rays that take part: X_Points x [m, 3], side normals n' [m, 3], Poly_id [m], len [m], L' [m], Ea [B, m] and
     sg [B, m] (the sigma rows).  The shadow queries run through the oracle partition's shoot (poly_origin1 = Poly_id; occluded =
     hit && t < 1.0).  hist and det are accumulated into as in receiver_step; the arrival vector of the directional form is
@@ -139,17 +175,21 @@ def rain_step(part, x, nprime, pid, length, Lp, Ea, sg, centers, radii, n_bins, 
                 def arrival():
                     db = dist[binned]
                     return -(vx[sel] / db), -(vy[sel] / db), -(vz[sel] / db)
-                deposit(hist, k, bins, (Ea[:, sel] * sg[:, sel]) * w[binned], frac_bits, arrival, counts)   # ((Ea * sg) * w) * 2^frac_bits
+                deposit(hist, k, bins, (Ea[:, sel] * sg[:, sel]) * w[binned], frac_bits, arrival, counts,
+                        tallies)                                        # ((Ea * sg) * w) * 2^frac_bits
 
 
 def receive_loop(po, topo, part, rays, bounces, centers, radii, n_bins, bin_len, frac_bits, alpha=None, sigma=None, seed=0, state_in=None,
-                 g0=0, rain=False, directional=False, keep_rays_after=None, stats=None, counts=None, nthreads=16, events=None):
+                 g0=0, rain=False, directional=False, keep_rays_after=None, stats=None, counts=None, nthreads=16, events=None,
+                 tallies=None, excl1=None, excl2=None, last_events=None):
     """The receive loop, cast by cast: part.shoot (an oracle partition) on the live rays, the receiver step, the state update, then (but
     behind the last cast) the choice, the rain, the weights and the reflection -- specular rays with the oracle's reflection, diffuse
     ones with tests/scatter_ref.py's.  sigma: the scattering table (None: specular).  rain: diffuse rain, with the receiver step skipped
     for the segment behind a diffuse reflection (as in the library, it changes nothing without a table).  directional: four channels
     per band.  g0: the global index of ray 0.  counts: an int64 array [K, n_bins] that collects the adds per (receiver, bin), or None.
     events [bounces, n] (e.g. tests.helpers.oracle_bounce_loop): replay these recorded events of every cast instead of shooting.
+    tallies: deposit's dict of edge-case classes, or None.  excl1, excl2 [n]: poly_origin1 / poly_origin2 of the first cast (default:
+    none).  last_events: a list that receives the last cast's events [n] (a miss record for a retired ray), or None.
     Returns (hist [K, n_bins, B] or [K, n_bins, B, 4] uint64, det [K, 2], state [1 + B, n], the rays [n, 6] behind cast
     `keep_rays_after`, or the final ones)."""
     rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
@@ -169,7 +209,8 @@ def receive_loop(po, topo, part, rays, bounces, centers, radii, n_bins, bin_len,
     normals = normals_of(topo)
     base = ray_base(seed, np.arange(g0, g0 + n, dtype=np.uint64))
     cur = rays.copy()
-    e1 = np.full(n, -1, np.int32)
+    e1 = np.full(n, -1, np.int32) if excl1 is None else np.asarray(excl1, np.int32).copy()
+    e2 = None if excl2 is None else np.asarray(excl2, np.int32).copy()
     live = np.ones(n, bool)
     rained = np.zeros(n, bool)              # the segment behind a diffuse reflection: deposited by the rain, not detected
     kept = None
@@ -177,17 +218,19 @@ def receive_loop(po, topo, part, rays, bounces, centers, radii, n_bins, bin_len,
         ev = np.zeros(n, po.XEVENT_DTYPE)
         ev["poly_id"] = -1
         if live.any():
-            ev[live] = events[c][live] if events is not None else part.shoot(cur[live], excl1=e1[live], nthreads=nthreads)[0]
+            ev[live] = events[c][live] if events is not None else part.shoot(cur[live], excl1=e1[live], excl2=None if e2 is None else e2[live],
+                                                                             nthreads=nthreads)[0]
         hit = ev["hit"] == 1
         t_end = np.where(hit, ev["t"], np.inf)
         seen = live & ~rained
         if seen.any():
             receiver_step(cur[seen, :3], cur[seen, 3:], t_end[seen], L[seen], E[:, seen], centers, radii, n_bins, bin_len, frac_bits,
-                          hist, det, counts)
+                          hist, det, counts, tallies)
         upd = live & hit
         if alpha is not None:
             a = np.asarray(alpha, np.float64)[ev["poly_id"][upd]].T          # [B, m]
-            E[:, upd] = E[:, upd] * (1.0 - a)
+            with np.errstate(invalid="ignore"):                              # inf * 0
+                E[:, upd] = E[:, upd] * (1.0 - a)
         L[upd] = L[upd] + ev["t"][upd]
         rained = np.zeros(n, bool)
         if c + 1 < bounces:
@@ -205,9 +248,10 @@ def receive_loop(po, topo, part, rays, bounces, centers, radii, n_bins, bin_len,
                         length = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
                         x = np.stack([ev["x"][ti], ev["y"][ti], ev["z"][ti]], axis=1)
                         rain_step(part, x, side_normals(d, normals[pid[t]]), pid[t], length, L[ti], E[:, ti], srow[t].T, centers, radii,
-                                  n_bins, bin_len, frac_bits, hist, det, stats=stats, nthreads=nthreads, counts=counts)
+                                  n_bins, bin_len, frac_bits, hist, det, stats=stats, nthreads=nthreads, counts=counts, tallies=tallies)
                     rained[idx[diff]] = True
-                E[:, idx] = E[:, idx] * weights(srow, p, diff).T
+                with np.errstate(invalid="ignore", over="ignore"):
+                    E[:, idx] = E[:, idx] * weights(srow, p, diff).T
                 di = idx[diff]
                 if di.size:
                     nxt[di] = scatter_rays(cur[di], ev[di], normals, base[di], c)
@@ -215,7 +259,10 @@ def receive_loop(po, topo, part, rays, bounces, centers, radii, n_bins, bin_len,
             if keep_rays_after == c:
                 kept = cur.copy()
         e1 = np.where(upd, ev["poly_id"], -2).astype(np.int32)
+        e2 = None
         live = upd
+        if last_events is not None and c + 1 == bounces:
+            last_events.append(ev)
     return hist, det, np.concatenate([L[None], E], axis=0), cur if keep_rays_after is None else kept
 
 
