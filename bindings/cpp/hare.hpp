@@ -156,6 +156,11 @@ public:
     // state: (1 + B) x rays.size() (L, then E per band); rain: diffuse rain (HARE_RECEIVE_DIFFUSE_RAIN).  Returns the hits over all casts.  Sizes are checked here: the library reads and
     // writes as many values as the scene says, whatever the vectors hold.  directional (HARE_RECEIVE_DIRECTIONAL): hist is K x n_bins x B x 4,
     // channel innermost: W (the omni word), then X, Y, Z as int64 in two's complement (positive for sound arriving from +x, +y, +z).
+    // Termination (the header's section of that name).  HARE_RECEIVE_TIME_LIMIT (512u, a flag of hare_receive_batch on native(); Receive
+    // below does not set it): a ray whose path L has reached n_bins * bin_len after a hit is retired; hist and detections[2k] are
+    // those of the call without it, detections[2k + 1] and the final state differ.  The energy
+    // floor is the scene's: SetOption("receive_floor_bits", f) retires a ray whose largest band lies under 2^-f (0: off; biased by
+    // design), SetOption("receive_roulette", 1) lets it survive with probability ps = m / F, divided by ps (expectation kept).
     void SetReceivers(const std::vector<double>& centers, const std::vector<double>& radii)
     {
         if (centers.size() != 3 * radii.size()) throw std::invalid_argument("SetReceivers: centers must hold 3 x radii.size() values");

@@ -101,6 +101,12 @@ namespace Hare
             public const uint HARE_SHOOT_SLIM_EVENTS = 16;   // host-buffer batches: hare_slim_event records come back (16 B per ray, not 56)
             public const uint HARE_RECEIVE_DIFFUSE_RAIN = 128;   // receive calls: diffuse rain where the topology has a scattering table
             public const uint HARE_RECEIVE_DIRECTIONAL = 256;    // receive calls: four channels per histogram word (W, X, Y, Z)
+            // receive calls: a ray whose path L has reached n_bins * bin_len after a hit is retired (include/hare_hip.h, "Termination"):
+            // histogram and detections[2k] are those of the call without the flag; detections[2k + 1], the final state and the counters
+            // differ.  The energy floor is a scene option: "receive_floor_bits" f (0: off; F = 2^-f, a ray whose largest band lies under
+            // F is retired -- biased by design) and "receive_roulette" 1 (such a ray survives with probability ps = m / F and is then
+            // divided by ps: every band's expected energy is kept).  The same values on every scene of a sharded call.
+            public const uint HARE_RECEIVE_TIME_LIMIT = 512;
 
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr hare_last_error();
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int hare_device_count(out int count);

@@ -20,6 +20,7 @@ SHOOT_WRITEBACK_ORIGIN, SHOOT_COUNT_WORK, SHOOT_SIMPLE_KERNEL, SHOOT_RETIRED_RAY
 SHOOT_COUNT_OWN = 64
 RECEIVE_DIFFUSE_RAIN = 128          # hare_receive_*: diffuse rain (include/hare_hip.h)
 RECEIVE_DIRECTIONAL = 256           # hare_receive_*: four channels per histogram word, W X Y Z (include/hare_hip.h)
+RECEIVE_TIME_LIMIT = 512            # hare_receive_*: retire a ray whose path has passed the histogram's end (include/hare_hip.h, "Termination")
 
 RAY_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("dx", "<f8"), ("dy", "<f8"), ("dz", "<f8")])
 XEVENT_DTYPE = np.dtype(

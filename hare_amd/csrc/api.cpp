@@ -898,6 +898,8 @@ const OptionEntry kOptionTable[] = {
         {"voxel_overlap", &SceneOptions::voxel_overlap, 0, 1},
         {"voxel_skip", &SceneOptions::voxel_skip, 0, 1},
         {"receive_aggregate", &SceneOptions::receive_aggregate, 0, 1},
+        {"receive_floor_bits", &SceneOptions::receive_floor_bits, 0, 1000},
+        {"receive_roulette", &SceneOptions::receive_roulette, 0, 1},
 };
 }  // namespace
 

@@ -508,6 +508,12 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
             set_error(std::string(who) + ": the scenes differ in scattering tables or scatter_seed");
             return HARE_E_INVALID;
         }
+        const bool roulette = s0->opt.receive_floor_bits > 0 && s0->opt.receive_roulette != 0;      // draws from "scatter_seed" without a table too
+        if (scenes[k]->opt.receive_floor_bits != s0->opt.receive_floor_bits || scenes[k]->opt.receive_roulette != s0->opt.receive_roulette ||
+            (roulette && scenes[k]->opt.scatter_seed != s0->opt.scatter_seed)) {
+            set_error(std::string(who) + ": the scenes differ in receive_floor_bits, receive_roulette or (with roulette) scatter_seed");
+            return HARE_E_INVALID;
+        }
     }
     GUARD_BEGIN
     const int G = n_scenes;

@@ -479,7 +479,7 @@ constexpr int kMaxReceivers = 256;
 struct ReceiveArgs {
     const PolyRec* polys;      // Model[top]
     RayRec* rays;              // n rays, the ray each lane's cast received; overwritten by the reflection (not in the last cast)
-    const XEventRec* ev;       // the cast's n events
+    XEventRec* ev;             // the cast's n events; written only for a ray a termination rule retires (its miss record)
     int32_t* excl;             // marks / next exclusions (the loop's work array; -2: retired)
     unsigned char* block_live; // nullable: a byte per 64 rays, as hare_reflect writes it
     double* state;             // (1 + bands) planes of n doubles: L, E[0 .. bands-1]
@@ -504,7 +504,13 @@ struct ReceiveArgs {
     long long ray_base;        // global index of ray 0 of this call (the shard's offset in hare_receive_batch_sharded): g = ray_base + i
     // hare_receive_scatter_rain only (HARE_RECEIVE_DIFFUSE_RAIN; last, so that the fields above keep their offsets):
     int32_t* rain_flag;        // n flags: 1 when the ray's reflection in the previous cast was diffuse (its segment is rained, not detected)
+    // termination (include/hare_hip.h, "Termination"; last again): read under one wave-uniform branch on `cut`
+    double floor;              // F = 2^-"receive_floor_bits" (kCutFloor)
+    int32_t cut;               // kCut* bits; 0: no rule, the kernels behave as they did without them
 };
+constexpr int32_t kCutTime = 1;      // HARE_RECEIVE_TIME_LIMIT
+constexpr int32_t kCutFloor = 2;     // "receive_floor_bits" > 0
+constexpr int32_t kCutRoulette = 4;  // ... with "receive_roulette" 1
 
 // hare_rain_step (receive.hip): diffuse rain between the shoot and the receive kernel of a cast -- the deposit of receiver k_dep's
 // visibility query (its flags in `socc`) and the emission of receiver k_emit's.  Reads what hare_receive_scatter_rain reads before it

@@ -154,6 +154,10 @@ static_assert((HARE_RECEIVE_DIFFUSE_RAIN & (kPublicFlags | HARE_SHOOT_BOUNCE_LOO
 static_assert((HARE_RECEIVE_DIRECTIONAL & (kPublicFlags | HARE_SHOOT_BOUNCE_LOOP | HARE_RECEIVE_DIFFUSE_RAIN | 0xF000u | kFlagAnyHit | SHOOT_RETIRED_SILENT)) == 0 &&
                   (HARE_RECEIVE_DIRECTIONAL & (HARE_RECEIVE_DIRECTIONAL - 1u)) == 0,
               "the receive calls' directional bit is a bit of its own");
+static_assert((HARE_RECEIVE_TIME_LIMIT & (kPublicFlags | HARE_SHOOT_BOUNCE_LOOP | HARE_RECEIVE_DIFFUSE_RAIN | HARE_RECEIVE_DIRECTIONAL | 0xF000u | kFlagAnyHit |
+                                          SHOOT_RETIRED_SILENT)) == 0 &&
+                  (HARE_RECEIVE_TIME_LIMIT & (HARE_RECEIVE_TIME_LIMIT - 1u)) == 0,
+              "the receive calls' time-limit bit is a bit of its own");
 uint32_t sanitize_flags(const Scene& s, uint32_t flags)
 {
     return flags & (kPublicFlags | (s.opt.dev ? 0xF000u : 0u));

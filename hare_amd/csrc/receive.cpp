@@ -142,6 +142,10 @@ int receive_plan(const Scene& s, int32_t top, uint32_t flags, int64_t n, int32_t
         set_error("receive: absorption table not on the device");
         return HARE_E_STATE;
     }
+    // termination (the header's "Termination"): the flag and the two scene options, as the kernels' one field
+    ra.cut = ((flags & HARE_RECEIVE_TIME_LIMIT) ? kCutTime : 0) |
+             (s.opt.receive_floor_bits > 0 ? (kCutFloor | (s.opt.receive_roulette ? kCutRoulette : 0)) : 0);
+    ra.floor = ldexp(1.0, -s.opt.receive_floor_bits);
     p.directional = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
     p.rain = receive_rains(s, top, flags);
     p.work = p.rain ? rain_work(d_work, n) : RainWork();
@@ -180,7 +184,7 @@ static RainArgs rain_args(const ReceiveArgs& ra, const RainWork& w)
 
 // The receiver step, the state update and (but behind the last cast) the reflection: hare_receive_reflect in hare_reflect's place,
 // hare_receive_scatter where Model[top] has a scattering table, hare_receive_scatter_rain behind the rain
-int receive_step(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, const ReceivePlan& p, void* d_rays, const void* d_ev,
+int receive_step(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, const ReceivePlan& p, void* d_rays, void* d_ev,
                  int32_t* marks, unsigned char* block_live, int32_t cast, bool last_cast, hipStream_t st)
 {
     const DeviceModule& M = *s.module;
@@ -188,7 +192,7 @@ int receive_step(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n
     ReceiveArgs ra = p.args;
     ra.polys = (const PolyRec*)s.d_polys[(size_t)top];
     ra.rays = (RayRec*)d_rays;
-    ra.ev = (const XEventRec*)d_ev;
+    ra.ev = (XEventRec*)d_ev;
     ra.excl = marks;
     ra.block_live = block_live;
     ra.n = n;

@@ -6,7 +6,8 @@
 // bounce_device_impl runs behind every cast).  A live ray reads its ray, its event and its state once; runs through every receiver sphere in ascending order with the
 // FP64 test of the header (no contraction: -ffp-contract=off); updates its state; and, except in the last cast, is reflected exactly as
 // hare_reflect does it (the same function, reflect_hit; the same marks and live-block byte).  A retired ray (-2) costs one 4-byte load; a
-// workgroup whose rays are all retired also passes one barrier and stages no receivers.
+// workgroup whose rays are all retired also passes one barrier and stages no receivers.  The termination rules of the header (time limit,
+// energy floor, roulette: ReceiveArgs::cut) retire a ray behind its state update with the mark and the live-block byte of a miss.
 //
 // The receivers (at most 256 x 32 B) are staged in LDS once per workgroup and read with wave-uniform addresses (the loop index is uniform):
 // one broadcast ds_read per receiver.  (Read straight from the device array they compiled to vector loads: the atomics in the loop keep
@@ -265,18 +266,19 @@ static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
             }
         }
     }
-    // ---- state update, reflection (hare_reflect's arithmetic and marks)
+    // ---- state update, termination, reflection (hare_reflect's arithmetic and marks)
     bool lives_on = false;
     if (live) {
         bool diffuse = false;
+        bool cut = false;                              // a termination rule retires the ray (the header's "Termination")
         unsigned long long base = 0, c8 = 0;
         double nx = 0, ny = 0, nz = 0;
         if (e.hit || a.init_state) {               // a miss leaves its state as it is (init_state: as it starts)
             const double* al = (e.hit && a.alpha) ? a.alpha + (size_t)e.poly_id * (size_t)B : nullptr;
+            const bool scat = e.hit && !a.last;                // the choice, its weights and the rules: only a ray that will be reflected
             if constexpr (SCATTER) {
                 // every load (absorption, scattering and normal of the polygon) ahead of the first store to the state, which the compiler
                 // must assume may alias them: issued together, their latencies overlap
-                const bool scat = e.hit && !a.last;            // the choice and its weights: only a ray that will be reflected
                 const double* sg = a.sigma + (size_t)(scat ? e.poly_id : 0) * (size_t)B;
                 double sig[kMaxBands];
 #pragma unroll
@@ -302,19 +304,50 @@ static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
                     for (int b = 0; b < kMaxBands; ++b)
                         if (b < B) E[b] = E[b] * ((diffuse ? sig[b] : 1.0 - sig[b]) / den);
                 }
-                a.state[i] = e.hit ? L + e.t : L;
-#pragma unroll
-                for (int b = 0; b < kMaxBands; ++b)
-                    if (b < B) a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i] = E[b];
             } else {
-                a.state[i] = e.hit ? L + e.t : L;
 #pragma unroll
                 for (int b = 0; b < kMaxBands; ++b)
-                    if (b < B) a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i] = al ? E[b] * (1.0 - al[b]) : E[b];      // no table: alpha = 0
+                    if (b < B && al) E[b] = E[b] * (1.0 - al[b]);              // no table: alpha = 0
             }
+            const double Lp = e.hit ? L + e.t : L;
+            if (a.cut != 0 && scat) {                          // a.cut is uniform: a call without a rule pays this one scalar test
+                if ((a.cut & kCutTime) && Lp / a.bin_len >= (double)a.n_bins) {
+                    cut = true;
+                } else if (a.cut & kCutFloor) {
+                    double m = E[0];
+#pragma unroll
+                    for (int b = 1; b < kMaxBands; ++b)
+                        if (b < B) m = (E[b] > m) ? E[b] : m;
+                    if (m < a.floor) {
+                        cut = true;
+                        if (a.cut & kCutRoulette) {
+                            if constexpr (!SCATTER) {
+                                base = scatter_mix(scatter_mix(a.seed + kScatterGamma) ^ (unsigned long long)(a.ray_base + i));
+                                c8 = (unsigned long long)a.cast << 8;
+                            }
+                            const double ps = m / a.floor;
+                            if (scatter_u(base, c8, 65) < ps) {                // the survivor carries what the casualties held
+                                cut = false;
+#pragma unroll
+                                for (int b = 0; b < kMaxBands; ++b)
+                                    if (b < B) E[b] = E[b] / ps;
+                            }
+                        }
+                    }
+                }
+            }
+            a.state[i] = Lp;
+#pragma unroll
+            for (int b = 0; b < kMaxBands; ++b)
+                if (b < B) a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i] = E[b];
         }
         if (e.hit) {
-            if (!a.last) {
+            if (cut) {                                 // as a miss: no reflection, the mark, and the miss record later casts leave in place
+                a.excl[i] = -2;
+                XEventRec me;
+                set_miss(me);
+                a.ev[i] = me;
+            } else if (!a.last) {
                 if constexpr (SCATTER) a.rays[i] = diffuse ? scatter_hit(nx, ny, nz, r, e, base, c8) : reflect_about(nx, ny, nz, r, e);
                 else a.rays[i] = reflect_hit(a.polys, r, e);         // kernels.hip: hare_reflect's arithmetic, shared
                 a.excl[i] = e.poly_id;

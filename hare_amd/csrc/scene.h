@@ -62,6 +62,8 @@ struct SceneOptions {
                                // more one-workgroup launch per cast) and the next cast walks the list: open scenes; 0: off (a closed room saves ~1 %)
     int wide_drain = 1;        // 1: K1q's wide cull / wide walk in the drain of a launch (voxel_pool.hip); 0: the pool's ordinary phases to the end (A/B)
     int receive_aggregate = 1; // 1: hare_receive_reflect sums a wave's histogram adds per distinct (receiver, bin) before one atomic; 0: an atomic per detecting lane (A/B).  Same results
+    int receive_floor_bits = 0;    // f: the receive loop's energy floor F = 2^-f (0: off; include/hare_hip.h, "Termination")
+    int receive_roulette = 0;      // 1: a ray under the floor plays Russian roulette (word 65 of the scattering RNG)
     long long scatter_seed = 0;    // the scattering RNG's seed S (hare_receive_scatter; read as uint64 bits)
     long long dev_order_ptr = 0;   // developer experiments (a `dev` scene only): a device array of n uint32, the order K1q takes the rays in (ShootIO::order)
     int tune[5] = {0, 0, 0, 0, 0};   // HARE_TUNE: steps,refill,chunk,blocks_per_cu,exact (profiling build; blocks_per_cu: K1p)
@@ -362,7 +364,7 @@ size_t receive_hist_words(const Scene& s, int32_t top, int32_t n_bins, uint32_t 
 int receive_plan(const Scene& s, int32_t top, uint32_t flags, int64_t n, int32_t n_bins, double bin_len, int32_t frac_bits, void* d_state,
                  void* d_hist, void* d_det, void* d_work, bool init_state, int64_t ray_base, ReceivePlan& p);
 // One cast's receive step on the stream: the rain's launches (p.rain, but behind the last cast), then the receive kernel
-int receive_step(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, const ReceivePlan& p, void* d_rays, const void* d_ev,
+int receive_step(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, const ReceivePlan& p, void* d_rays, void* d_ev,
                  int32_t* marks, unsigned char* block_live, int32_t cast, bool last_cast, hipStream_t st);
 int receive_ready(Scene& s, const HipApi* H, const char* who);
 

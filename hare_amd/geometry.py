@@ -411,27 +411,31 @@ class Spatial_Partition:
         return self.get_option("bands:%d" % int(top_index))          # the scene's own record, whoever set the table
 
     def Receive_batch(self, rays, bounces: int, n_bins: int, bin_len: float, energy=None, frac_bits: int = 40, top_index: int = 0,
-                      poly_origin1=None, poly_origin2=None, out=None, rain: bool = False, directional: bool = False):
+                      poly_origin1=None, poly_origin2=None, out=None, rain: bool = False, directional: bool = False, time_limit: bool = False):
         """The bounce loop with the receiver step between its casts, from host buffers (hare_receive_batch).
         energy: None (every ray starts at L = 0, E = 1) or the state [1 + B, n] (row 0: L, rows 1..B: E).
         Returns (hist [K, n_bins, B] uint64, hist * 2^-frac_bits as float64, detections [K, 2] uint64, final state [1 + B, n],
         counters).  out (optional): the caller's uint64 histogram array [K, n_bins, B], as in Shoot_batch.  rain: diffuse rain
         (HARE_RECEIVE_DIFFUSE_RAIN) where the topology has a scattering table.  directional (HARE_RECEIVE_DIRECTIONAL): the histogram
         (and `out`) is [K, n_bins, B, 4], channels W, X, Y, Z (directional_signed gives X, Y, Z as int64); frac_bits must leave a sign
-        bit of headroom."""
+        bit of headroom.  time_limit (HARE_RECEIVE_TIME_LIMIT): a ray whose path L has reached n_bins * bin_len after a hit is retired;
+        histogram and detections[:, 0] stay as they are without it.  The energy floor is the scene's: options "receive_floor_bits"
+        (F = 2^-f) and "receive_roulette" (include/hare_hip.h, "Termination")."""
         return Spatial_Partition._receive([self], rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1,
-                                          poly_origin2, out, rain, directional)
+                                          poly_origin2, out, rain, directional, time_limit)
 
     @staticmethod
     def Receive_batch_sharded(partitions, rays, bounces: int, n_bins: int, bin_len: float, energy=None, frac_bits: int = 40,
                               top_index: int = 0, poly_origin1=None, poly_origin2=None, out=None, rain: bool = False,
-                              directional: bool = False):
-        """hare_receive_batch_sharded: Receive_batch over several partitions (contiguous ray shards, histograms summed); byte-identical."""
+                              directional: bool = False, time_limit: bool = False):
+        """hare_receive_batch_sharded: Receive_batch over several partitions (contiguous ray shards, histograms summed); byte-identical.
+        The partitions must agree in "receive_floor_bits" and "receive_roulette" (and, with roulette, in "scatter_seed")."""
         return Spatial_Partition._receive(list(partitions), rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1,
-                                          poly_origin2, out, rain, directional)
+                                          poly_origin2, out, rain, directional, time_limit)
 
     @staticmethod
-    def _receive(parts, rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1, poly_origin2, out, rain=False, directional=False):
+    def _receive(parts, rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1, poly_origin2, out, rain=False, directional=False,
+                 time_limit=False):
         if not parts or any(p._kind != parts[0]._kind for p in parts):
             raise ValueError("need one or more partitions of the same kind")
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
@@ -452,7 +456,8 @@ class Spatial_Partition:
         det = np.zeros((max(K, 0), 2), np.uint64)
         state_out = np.empty((1 + B, n), np.float64)
         ctr = capi.Counters()
-        flags = (capi.RECEIVE_DIFFUSE_RAIN if rain else 0) | (capi.RECEIVE_DIRECTIONAL if directional else 0)
+        flags = ((capi.RECEIVE_DIFFUSE_RAIN if rain else 0) | (capi.RECEIVE_DIRECTIONAL if directional else 0) |
+                 (capi.RECEIVE_TIME_LIMIT if time_limit else 0))
         if len(parts) == 1:
             rc = lib.hare_receive_batch(parts[0]._h, parts[0]._kind, int(top_index), n, ptr(rays), ptr(e1), ptr(e2), int(bounces), flags, nb,
                                         float(bin_len), int(frac_bits), ptr(state_in), ptr(state_out), ptr(hist), ptr(det), C.addressof(ctr))
@@ -471,11 +476,15 @@ class Spatial_Partition:
 
     def receive_device(self, n: int, d_rays: int, bounces: int, n_bins: int, bin_len: float, frac_bits: int, d_state: int, d_work: int,
                        d_events_last: int, d_hist: int, d_detections: int, top_index: int = 0, d_excl1: int = 0, d_excl2: int = 0,
-                       d_counters: int = 0, stream: int = 0, flags: int = 0, rain: bool = False, directional: bool = False):
+                       d_counters: int = 0, stream: int = 0, flags: int = 0, rain: bool = False, directional: bool = False,
+                       time_limit: bool = False):
         """hare_receive_device on raw device addresses (e.g. torch.Tensor.data_ptr()) + a hipStream_t: d_state (1 + B) x n doubles is read
         and overwritten, d_hist (K x n_bins x B uint64) and d_detections (2 K uint64) are accumulated into.  Stream-ordered.  rain: diffuse
         rain (HARE_RECEIVE_DIFFUSE_RAIN); d_work then holds receive_work_bytes(n, rain=True) bytes.  directional
-        (HARE_RECEIVE_DIRECTIONAL): d_hist is K x n_bins x B x 4 uint64, channels W, X, Y, Z."""
+        (HARE_RECEIVE_DIRECTIONAL): d_hist is K x n_bins x B x 4 uint64, channels W, X, Y, Z.  time_limit (HARE_RECEIVE_TIME_LIMIT): as
+        in Receive_batch; a retired ray keeps the ray and the state of the cast that retired it."""
+        if time_limit:
+            flags |= capi.RECEIVE_TIME_LIMIT
         if rain:
             flags |= capi.RECEIVE_DIFFUSE_RAIN
         if directional:

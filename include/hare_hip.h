@@ -82,6 +82,7 @@ extern "C" {
 #define HARE_SHOOT_BOUNCE_LOOP 32u     /* hare_shoot_kernel_name only: name the kernel hare_bounce_device (<= 16 casts) launches for n rays           */
 #define HARE_RECEIVE_DIFFUSE_RAIN 128u /* hare_receive_device / _batch / _batch_sharded only: diffuse rain ("receivers", "Diffuse rain", below)    */
 #define HARE_RECEIVE_DIRECTIONAL 256u  /* the same three calls only: four channels per histogram word, W X Y Z ("receivers", "Directional", below) */
+#define HARE_RECEIVE_TIME_LIMIT 512u   /* the same three calls only: a ray whose path has passed the histogram's end is retired ("receivers", "Termination")  */
 
 /* Hare.Geometry.Ray (Hare_Geometry_Primitives.cs:393-429): origin + direction.  Ray_ID/ThreadID
  * only serve the reference's mailbox pool and are not needed here. 48 bytes. */
@@ -226,6 +227,8 @@ HARE_API void hare_scene_destroy(hare_scene *s);
  *   "receive_aggregate"  1 (default): hare_receive_reflect sums a wave's histogram adds per distinct (receiver, bin) before ONE atomic
  *                     instruction; 0: an atomic per detecting lane and band (A/B).  Results never depend on it
  *   "scatter_seed"    any int64 (default 0), read as uint64 bits: the seed S of the receive loop's scattering RNG ("receivers" below)
+ *   "receive_floor_bits"  f = 0 (default: off) .. 1000: the receive loop's energy floor F = 2^-f ("receivers", "Termination", below)
+ *   "receive_roulette"    0 (default) / 1: a ray under the floor plays Russian roulette instead of being retired outright (the same section)
  *   "dev"             1: developer flag bits of hare_shoot_* (timeline, phase profile, cull audit) pass
  * Single-caller like the build calls: not to be changed while shoots are in flight on the scene. */
 HARE_API int hare_scene_set_option(hare_scene *s, const char *name, int64_t value);
@@ -546,6 +549,34 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * 1/2); detections keep their shape and values; nothing about draws, choices, rays, state, suppression or detections changes.  d_hist of
  * the device call and hist of the host calls are four times as large, and the bound on the histogram becomes K x n_bins x B x 4 <= 2^27.
  *
+ * Termination (flag HARE_RECEIVE_TIME_LIMIT; scene options "receive_floor_bits" and "receive_roulette").  Two opt-in rules that retire a
+ * ray before the call's `bounces` are spent.  Without the flag and with "receive_floor_bits" 0 nothing in this section applies.  Both are
+ * decided in cast c for a ray that hit in cast c and would be reflected (c < bounces - 1), AFTER that cast's state update: after the
+ * absorption update and, with a scattering table, after the scattering weights (and after the cast's rain, which deposits as before).
+ * With L' = L + e.t and E[b] as that update leaves them, FP64, no contraction, in this order:
+ *
+ *   time limit (the flag):      retire  iff  (L' / bin_len) >= (double)n_bins          one division; a NaN L' is not retired
+ *   energy floor (f > 0):       F = 2^-f (ldexp: exact)
+ *     m = E[0];  for b = 1 .. B-1:  m = (E[b] > m) ? E[b] : m                          a NaN E[b] never replaces m; m = NaN: not below F
+ *     if m < F:
+ *       "receive_roulette" 0:   retire
+ *       "receive_roulette" 1:   ps = m / F;  u = u_65 of the RNG above (cast c, word j = 65, base = mix(mix(S + G) ^ g) with g the GLOBAL
+ *                               ray index and S = "scatter_seed" -- also on a topology without a scattering table)
+ *                               u < ps:   the ray survives, E[b] = E[b] / ps for every b, and THAT is the state stored
+ *                               else:     retire (the state stored is the undivided one)
+ *
+ * m <= 0 gives ps <= 0: such a ray never survives.  Word 65 is free (scattering draws j = 0 .. 64 and reserves j < 256).  The time limit
+ * is tested first and a ray it retires draws nothing; as draws are per (g, c, j) this cannot be observed.
+ * A ray a rule retires is treated as a ray that missed, but that its state update has happened and is stored: it is not reflected
+ * (rays[i] stays as cast c received it), its mark becomes -2, its block counts as not live, its rain flag is not written, it takes part in
+ * no later cast, and events_last holds the miss record for it, as for any ray retired before the last cast.
+ * What the caller has to know.  Time limit: x = (L + s) / bin_len with s >= 0 only grows with L and rounding is monotone, so for hits
+ * with t >= 0 every later x of a retired ray (the rain's xb too) is >= n_bins -- the histogram and detections[2k] are BYTE-IDENTICAL to
+ * those of the same call without the flag, and as the RNG is per ray no other ray is affected.  Only detections[2k + 1], the final state,
+ * the final rays, events_last and the counters differ.  Floor with roulette: every band's expected energy is kept (a ray survives with
+ * probability ps and is then worth 1 / ps), at the price of variance in the late tail.  The plain floor is BIASED by design: it drops
+ * what lies under F, at most F per ray and band.  Later casts run over the rays still live; the call makes no host round trip.
+ *
  * The histogram is fixed point in uint64: integer sums do not depend on the order of the adds, so the result is bit-identical from
  * run to run, between the one-device and the sharded call, and against a restatement on the host.  (r*r is formed once, when the
  * receivers are set: the same FP64 product.)
@@ -571,7 +602,8 @@ HARE_API int hare_scene_set_scattering(hare_scene *s, int32_t top_index, int32_t
  *   d_state        (1 + B) planes of n doubles: plane 0 is L, planes 1..B are E.  Read and overwritten
  *   d_hist         K x n_bins x B uint64 (x 4 with HARE_RECEIVE_DIRECTIONAL), ACCUMULATED;  d_detections: 2 K uint64, ACCUMULATED
  *   d_counters     nullable: totals, ACCUMULATED (as hare_bounce_device's; the rain's occlusion queries are not counted)
- *   flags          HARE_SHOOT_COUNT_WORK / HARE_SHOOT_SIMPLE_KERNEL (the casts), HARE_RECEIVE_DIFFUSE_RAIN and HARE_RECEIVE_DIRECTIONAL; other bits are ignored.  With
+ *   flags          HARE_SHOOT_COUNT_WORK / HARE_SHOOT_SIMPLE_KERNEL (the casts), HARE_RECEIVE_DIFFUSE_RAIN, HARE_RECEIVE_DIRECTIONAL and
+ *                  HARE_RECEIVE_TIME_LIMIT; other bits are ignored.  With
  *                  HARE_RECEIVE_DIFFUSE_RAIN d_work holds HARE_RECEIVE_RAIN_WORK_BYTES(n) bytes: the 2 n int32, then the rain's scratch
  * Arguments are checked before anything runs (HARE_E_INVALID): kind, top_index, 0 <= n <= 2^31 - 256, 1 <= bounces <= 4096,
  * n_bins >= 1, bin_len finite and > 0, 0 <= frac_bits <= 62, K x n_bins x B <= 2^27 (K x n_bins x B x 4 <= 2^27 with
@@ -591,8 +623,8 @@ HARE_API int hare_receive_batch(hare_scene *s, int32_t kind, int32_t top_index, 
                                 double bin_len, int32_t frac_bits, const double *state_in, double *state_out, uint64_t *hist,
                                 uint64_t *detections, hare_counters *ctr);
 /* Over several devices: rays [n*k/G, n*(k+1)/G) go to scenes[k] (as hare_bounce_batch_sharded), the histograms and detections are
- * summed.  Byte-identical to the one-device call.  The scenes must hold the same receivers, bands, scattering table and (with one)
- * "scatter_seed" (HARE_E_INVALID otherwise). */
+ * summed.  Byte-identical to the one-device call.  The scenes must hold the same receivers, bands, scattering table, "receive_floor_bits",
+ * "receive_roulette" and (with a table, or with roulette) "scatter_seed" (HARE_E_INVALID otherwise). */
 HARE_API int hare_receive_batch_sharded(hare_scene *const *scenes, int32_t n_scenes, int32_t kind, int32_t top_index, int64_t n,
                                         const hare_ray *rays, const int32_t *excl1, const int32_t *excl2, int32_t bounces,
                                         uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits,

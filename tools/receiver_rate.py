@@ -12,8 +12,12 @@ path on (summed over receivers and bands), with rain and without.
 With --directional (B = 8; K = 8 and 64, or K = 1 and 8 with --rain; combinable with --scatter and --rain), every loop of the run is timed
 again with HARE_RECEIVE_DIRECTIONAL in the same run (the _dir kernels, a four-fold histogram): dir_ms, scatter_dir_ms, rain_dir_ms and
 their cost over the same loop without the flag.
+With --time-limit and / or --floor-bits N [--roulette] (the header's "Termination"), the specular loop of every (K, B) again with the time
+limit, with the energy floor 2^-N, and with both where both are given: cut_*_ms against ms of the same row, and the share of the rays
+still live -- over all casts (the loop's ray counter over n x bounces) and in the casts 1, 2, 4, 8, ... (the counter's difference between
+two calls that differ by one cast).
 Prints ONE JSON line.  usage: python tools/receiver_rate.py [hall|cathedral] [--rays N] [--bounces B] [--reps R] [--host] [--quick]
-                                                          [--scatter SIGMA] [--rain] [--directional]"""
+                                                          [--scatter SIGMA] [--rain] [--directional] [--time-limit] [--floor-bits N [--roulette]]"""
 import argparse
 import json
 import os
@@ -37,6 +41,9 @@ ap.add_argument("--scatter", type=float, default=None, metavar="SIGMA",
                 help="K = 8, B = 8 only, and the loop again with a scattering table of SIGMA everywhere (scene option scatter_seed 1)")
 ap.add_argument("--rain", action="store_true", help="K = 1 and 8, B = 8: the scattering loop with and without diffuse rain, and its noise")
 ap.add_argument("--directional", action="store_true", help="B = 8: every loop again with HARE_RECEIVE_DIRECTIONAL, in the same run")
+ap.add_argument("--time-limit", action="store_true", help="the loop again with HARE_RECEIVE_TIME_LIMIT")
+ap.add_argument("--floor-bits", type=int, default=0, metavar="N", help="the loop again with the energy floor 2^-N (scene option receive_floor_bits)")
+ap.add_argument("--roulette", action="store_true", help="with --floor-bits: Russian roulette under the floor (scene option receive_roulette)")
 a = ap.parse_args()
 if a.rain and a.scatter is None:
     a.scatter = 0.3
@@ -96,10 +103,26 @@ for K, B in cases:
     d_det = torch.zeros(2 * K, dtype=torch.int64, device="cuda")
     d_hist4 = torch.zeros(K * N_BINS * B * 4, dtype=torch.int64, device="cuda") if a.directional else None
 
-    def receive(rain=False, directional=False):
-        g.receive_device(n, d_rays.data_ptr(), nb, N_BINS, BIN_LEN, FRAC, d_state.data_ptr(), (d_work_rain if rain else d_work).data_ptr(),
+    def receive(rain=False, directional=False, time_limit=False, casts=nb, d_counters=0):
+        g.receive_device(n, d_rays.data_ptr(), casts, N_BINS, BIN_LEN, FRAC, d_state.data_ptr(), (d_work_rain if rain else d_work).data_ptr(),
                          d_last.data_ptr(), (d_hist4 if directional else d_hist).data_ptr(), d_det.data_ptr(), stream=st, rain=rain,
-                         directional=directional)
+                         directional=directional, time_limit=time_limit, d_counters=d_counters)
+
+    def timed_cut(row, key, time_limit, floor_bits):                     # the specular loop under a rule, against row["ms"]
+        g.set_option("receive_floor_bits", floor_bits).set_option("receive_roulette", int(a.roulette and floor_bits > 0))
+        ms = timed(lambda: (d_state.copy_(init), receive(time_limit=time_limit)), a.reps)
+        row[key + "_ms"] = round(ms - ms_copy, 3)
+        row[key + "_of_plain"] = round((ms - ms_copy) / row["ms"], 3)
+        d_ctr = torch.zeros(8, dtype=torch.int64, device="cuda")
+
+        def cast_rays(casts):                                            # rays cast by a call of `casts` casts, over all of them
+            d_ctr.zero_(); d_rays.copy_(d_src); d_state.copy_(init)
+            receive(time_limit=time_limit, casts=casts, d_counters=d_ctr.data_ptr()); torch.cuda.synchronize()
+            return int(d_ctr[0].item())
+        row[key + "_live_share"] = round(cast_rays(nb) / (n * nb), 4)
+        at = [c for c in (1, 2, 4, 8, 16, 32, 64, 128, 255) if c < nb]
+        row[key + "_live_in_cast"] = {c: round((cast_rays(c + 1) - cast_rays(c)) / n, 4) for c in at}
+        g.set_option("receive_floor_bits", 0).set_option("receive_roulette", 0)
 
     def timed_dir(row, key, base_key, rain=False):                       # the same loop with the flag, against row[base_key]
         ms = timed(lambda: (d_state.copy_(init), receive(rain, True)), a.reps)
@@ -122,6 +145,12 @@ for K, B in cases:
         g.set_option("receive_aggregate", 0)
         timed_dir(row, "dir_naive_ms", "ms")
         g.set_option("receive_aggregate", 1)
+    if a.time_limit:
+        timed_cut(row, "cut_time", True, 0)
+    if a.floor_bits:
+        timed_cut(row, "cut_floor", False, a.floor_bits)
+    if a.time_limit and a.floor_bits:
+        timed_cut(row, "cut_both", True, a.floor_bits)
     d_hist.zero_(); d_det.zero_(); d_rays.copy_(d_src); d_state.copy_(init)
     receive(); torch.cuda.synchronize()
     det = d_det.cpu().numpy().reshape(K, 2)
