@@ -201,6 +201,34 @@ public:
                                  detections.data(), &c));
         return c.hits;
     }
+    // the point source (include/hare_hip.h, "receivers", "Source"; hare_scene_set_source): a position, a power per band (power.size() = B),
+    // and optionally a directivity table gain[6][R][R][B] (band innermost) read in the frame (9 values, row-major; empty: identity).  Seed:
+    // SetOption("source_seed", ...).  ReceiveSource is Receive with the rays first_ray .. first_ray + n - 1 and their state emitted on the
+    // device: nothing but the count goes up, and calls over [0, k) and [k, n) sum to the histogram of the one call.
+    void SetSource(const std::array<double, 3>& pos, const std::vector<double>& power, const std::vector<double>& frame = {}, int R = 0,
+                   const std::vector<double>& gain = {})
+    {
+        if (!frame.empty() && frame.size() != 9) throw std::invalid_argument("SetSource: frame must hold 9 values (or none)");
+        if (R < 0 || gain.size() != (size_t)6 * (size_t)R * (size_t)R * power.size())
+            throw std::invalid_argument("SetSource: gain must hold 6 x R x R x power.size() values");
+        check(hare_scene_set_source(scene_, pos.data(), (int32_t)power.size(), power.data(), frame.empty() ? nullptr : frame.data(), R,
+                                    R > 0 ? gain.data() : nullptr));
+    }
+    uint64_t ReceiveSource(int64_t n, int64_t first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
+                           std::vector<uint64_t>& hist, std::vector<uint64_t>& detections, std::vector<double>* state_out = nullptr,
+                           bool rain = false, bool directional = false)
+    {
+        if (n < 0) throw std::invalid_argument("ReceiveSource: n must be >= 0");
+        const int64_t K = GetOption("receivers"), B = Bands(top_index);
+        hist.assign((size_t)(K * (n_bins > 0 ? n_bins : 0) * B * (directional ? 4 : 1)), 0);
+        detections.assign((size_t)(2 * K), 0);
+        if (state_out) state_out->assign((size_t)(1 + B) * (size_t)n, 0.0);
+        hare_counters c{};
+        check(hare_receive_source(scene_, kind_, top_index, n, first_ray, bounces,
+                                  (rain ? HARE_RECEIVE_DIFFUSE_RAIN : 0u) | (directional ? HARE_RECEIVE_DIRECTIONAL : 0u), n_bins, bin_len, frac_bits,
+                                  state_out ? state_out->data() : nullptr, hist.data(), detections.data(), &c));
+        return c.hits;
+    }
     void SetOption(const char* name, int64_t value) { check(hare_scene_set_option(scene_, name, value)); }
     int64_t GetOption(const char* name) const { int64_t v = 0; check(hare_scene_get_option(scene_, name, &v)); return v; }
     hare_scene* native() const { return scene_; }

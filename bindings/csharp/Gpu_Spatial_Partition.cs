@@ -322,6 +322,38 @@ namespace Hare
                 return (long)ctr.hits;
             }
 
+            /// <summary>The point source of every scene of this partition (hare_scene_set_source; include/hare_hip.h, "Source"): pos 3
+            /// values; power one value per band; frame 9 values, row-major (null: identity); gain 6 x R x R x power.Length values, band
+            /// innermost, a nearest-texel cube map read in the frame (null with R = 0: omnidirectional).  Seed: SetOption("source_seed").</summary>
+            public void SetSource(double[] pos, double[] power, double[] frame = null, int R = 0, double[] gain = null)
+            {
+                if (pos == null || pos.Length != 3) throw new ArgumentException("pos must hold 3 values");
+                if (power == null || power.Length < 1) throw new ArgumentException("power must hold one value per band");
+                if (frame != null && frame.Length != 9) throw new ArgumentException("frame must hold 9 values (or be null)");
+                if (R < 0 || (R == 0) != (gain == null) || (gain != null && gain.LongLength != 6L * R * R * power.Length))
+                    throw new ArgumentException("gain must hold 6 x R x R x power.Length values (null with R = 0)");
+                foreach (IntPtr s in scenes) HareHip.Check(HareHip.hare_scene_set_source(s, pos, power.Length, power, frame, R, gain));
+            }
+
+            /// <summary>Receive with the rays first_ray .. first_ray + n - 1 and their state emitted on the device by the source
+            /// (hare_receive_source_sharded): nothing but the count goes up.  Calls over [0, k) and [k, n) sum to the histogram and the
+            /// detections of the one call.  hist, detections and state (optional, (1 + B) x n: the final state) as in Receive.</summary>
+            public long ReceiveSource(long n, long first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits, ulong[] hist,
+                                      ulong[] detections, double[] state = null, bool rain = false, bool directional = false)
+            {
+                if (n < 0) throw new ArgumentException("n must be at least 0");
+                if (bounces < 1) throw new ArgumentException("bounces must be at least 1");
+                long K = GetOption("receivers"), B = Bands(top_index), C = directional ? 4 : 1;
+                if (hist == null || hist.LongLength < K * n_bins * B * C) throw new ArgumentException("hist must hold receivers x n_bins x Bands(top_index) values (x 4 when directional)");
+                if (detections == null || detections.LongLength < 2 * K) throw new ArgumentException("detections must hold 2 x receivers values");
+                if (state != null && state.LongLength < (1 + B) * n) throw new ArgumentException("state must hold (1 + Bands(top_index)) x n values");
+                hare_counters ctr;
+                uint flags = (rain ? HareHip.HARE_RECEIVE_DIFFUSE_RAIN : 0u) | (directional ? HareHip.HARE_RECEIVE_DIRECTIONAL : 0u);
+                HareHip.Check(HareHip.hare_receive_source_sharded(scenes, scenes.Length, Kind, top_index, n, first_ray, bounces, flags, n_bins, bin_len,
+                                                                  frac_bits, state, hist, detections, out ctr));
+                return (long)ctr.hits;
+            }
+
             /// <summary>The same on managed objects: result[b][i] is the X_Event of ray i in cast b (X_Event() once the ray has
             /// left the model).  rays[] is not modified.</summary>
             public X_Event[][] Bounce(Ray[] rays, int top_index, int bounces)

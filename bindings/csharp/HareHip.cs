@@ -241,6 +241,23 @@ namespace Hare
                                                          IntPtr d_work, IntPtr d_events_last, IntPtr d_hist, IntPtr d_detections, IntPtr d_counters,
                                                          IntPtr stream);
 
+            // The point source (include/hare_hip.h, "receivers", "Source"): pos 3; power B (null: 1.0); frame 9 (null: identity);
+            // gain 6 x R x R x B (null iff R == 0)
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_scene_set_source(IntPtr scene, [In] double[] pos, int B, [In] double[] power, [In] double[] frame, int R,
+                                                           [In] double[] gain);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_emit_device(IntPtr scene, long n, long first_ray, IntPtr d_rays, IntPtr d_state, IntPtr stream);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_receive_source(IntPtr scene, int kind, int top_index, long n, long first_ray, int bounces, uint flags,
+                                                         int n_bins, double bin_len, int frac_bits, [Out] double[] state_out, [Out] ulong[] hist,
+                                                         [Out] ulong[] detections, out hare_counters ctr);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_receive_source_sharded([In] IntPtr[] scenes, int n_scenes, int kind, int top_index, long n, long first_ray,
+                                                                 int bounces, uint flags, int n_bins, double bin_len, int frac_bits,
+                                                                 [Out] double[] state_out, [Out] ulong[] hist, [Out] ulong[] detections,
+                                                                 out hare_counters ctr);
+
             public static void Check(int rc)
             {
                 if (rc == 0) return;

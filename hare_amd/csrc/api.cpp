@@ -947,6 +947,14 @@ int hare_scene_get_option(const hare_scene* s, const char* name, int64_t* value)
         *value = (int64_t)s->opt.scatter_seed;
         return HARE_OK;
     }
+    if (strcmp(name, "source_seed") == 0) {
+        *value = (int64_t)s->opt.source_seed;
+        return HARE_OK;
+    }
+    if (strcmp(name, "source") == 0 || strcmp(name, "source_bands") == 0 || strcmp(name, "source_res") == 0) {     // hare_scene_set_source
+        *value = name[6] == '\0' ? (s->src.set ? 1 : 0) : (name[7] == 'b' ? s->src.B : s->src.R);
+        return HARE_OK;
+    }
     if (strcmp(name, "octree_scratch_bytes") == 0) {
         *value = s->d_oct_tail ? (int64_t)Scene::kOctTailRing * (int64_t)s->oct_tail_block_bytes : 0;
         return HARE_OK;
@@ -972,6 +980,10 @@ int hare_scene_set_option(hare_scene* s, const char* name, int64_t value)
     }
     if (strcmp(name, "scatter_seed") == 0) {        // any int64: the scattering RNG reads its bits as uint64
         s->opt.scatter_seed = (long long)value;
+        return HARE_OK;
+    }
+    if (strcmp(name, "source_seed") == 0) {         // any int64, as "scatter_seed": the point source's seed
+        s->opt.source_seed = (long long)value;
         return HARE_OK;
     }
     for (const OptionEntry& t : kOptionTable)

@@ -229,11 +229,13 @@ struct ReceiveJob {
     uint64_t* det = nullptr;
     int64_t ray_base = 0;      // this shard's first ray in the whole batch (the scattering RNG's global ray index)
     uint32_t flags = 0;        // the call's HARE_RECEIVE_* bits
+    bool from_source = false;  // hare_receive_source: rays and state come from hare_emit_source (rays from ray_base on), not from the caller
+    const char* who = "hare_receive_batch";
 };
 
 // The receive loop for one scene: rays, exclusions and state go up, the loop is enqueued ONCE (a launch per cast, hare_receive_reflect
 // behind each), histogram, detections, final state and per-cast counters come down, one synchronisation -- hare_bounce_batch's
-// last-cast-only path.  No events are downloaded.
+// last-cast-only path.  No events are downloaded.  job.from_source: nothing goes up -- the scene's source emits rays and state on the stream.
 int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind, int32_t top, int64_t n, const hare_ray* rays,
                      const int32_t* excl1, const int32_t* excl2, int32_t bounces, uint32_t flags, const ReceiveJob& job, hare_counters* per_cast)
 {
@@ -268,7 +270,11 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
     uint64_t* const d_hist = (uint64_t*)b.hist;
     uint64_t* const d_det = d_hist + hist_words;
     double* const d_state = (double*)b.state;
-    HIP_TRY(H->MemcpyAsync(b.rays[0], rays, (size_t)n * sizeof(hare_ray), hipMemcpyHostToDevice, st));
+    if (job.from_source) {
+        if (int rc = emit_source(s, H, n, job.ray_base, b.rays[0], d_state, st)) return rc;
+    } else {
+        HIP_TRY(H->MemcpyAsync(b.rays[0], rays, (size_t)n * sizeof(hare_ray), hipMemcpyHostToDevice, st));
+    }
     if (excl1) HIP_TRY(H->MemcpyAsync(b.excl[0], excl1, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (excl2) HIP_TRY(H->MemcpyAsync(b.excl2, excl2, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (job.state_in)
@@ -279,8 +285,8 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
     HIP_TRY(H->MemsetAsync(b.ctr, 0, (size_t)bounces * sizeof(hare_counters), st));
     void* const work = rain ? b.rain : b.ev[1];         // b.ev[1] holds the loop's 2 n int32; with rain, a buffer of its own holds them and the rain's scratch
     ReceivePlan plan;
-    if (int rc = receive_plan(s, top, job.flags, n, job.n_bins, job.bin_len, job.frac_bits, d_state, d_hist, d_det, work, job.state_in == nullptr,
-                              job.ray_base, plan))
+    if (int rc = receive_plan(s, top, job.flags, n, job.n_bins, job.bin_len, job.frac_bits, d_state, d_hist, d_det, work,
+                              job.state_in == nullptr && !job.from_source, job.ray_base, plan))
         return rc;
     if (int rc = bounce_device_impl(s, H, kind, top, n, b.rays[0], excl1 ? b.excl[0] : nullptr, excl2 ? b.excl2 : nullptr, bounces, flags, work,
                                     nullptr, b.ev[0], nullptr, b.ctr, st, &plan))
@@ -327,7 +333,8 @@ int bounce_one(hare_scene* s, int32_t kind, int32_t top, int64_t n, const hare_r
         if (rc) return rc;
         rc = upload_polys(*s, H);
         if (rc) return rc;
-        if (job && (rc = receive_ready(*s, H, "hare_receive_batch"))) return rc;
+        if (job && (rc = receive_ready(*s, H, job->who))) return rc;
+        if (job && job->from_source && (rc = source_ready(*s, H, job->who))) return rc;
         if (n == 0) return HARE_OK;
         s->cv.wait(lk, [&] { for (Scene::BatchCtx& x : s->ctx) if (!x.busy) return true; return false; });
         for (Scene::BatchCtx& x : s->ctx)
@@ -463,21 +470,15 @@ int hare_bounce_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int32
     GUARD_END
 }
 
-int hare_receive_batch(hare_scene* s, int32_t kind, int32_t top_index, int64_t n, const hare_ray* rays, const int32_t* excl1,
-                       const int32_t* excl2, int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits,
-                       const double* state_in, double* state_out, uint64_t* hist, uint64_t* detections, hare_counters* ctr)
-{
-    hare_scene* const one[1] = {s};
-    return hare_receive_batch_sharded(one, 1, kind, top_index, n, rays, excl1, excl2, bounces, flags, n_bins, bin_len, frac_bits, state_in,
-                                      state_out, hist, detections, ctr);
-}
+}  // extern "C"
 
-int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int32_t kind, int32_t top_index, int64_t n, const hare_ray* rays,
-                               const int32_t* excl1, const int32_t* excl2, int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len,
-                               int32_t frac_bits, const double* state_in, double* state_out, uint64_t* hist, uint64_t* detections,
-                               hare_counters* ctr)
+// hare_receive_batch / _sharded and, with first_ray non-null, hare_receive_source / _sharded: the same call with the upload of rays and
+// state replaced by the source's emission (shard k emits the rays from *first_ray + lo on)
+static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n_scenes, int32_t kind, int32_t top_index, int64_t n,
+                           const hare_ray* rays, const int32_t* excl1, const int32_t* excl2, int32_t bounces, uint32_t flags, int32_t n_bins,
+                           double bin_len, int32_t frac_bits, const double* state_in, double* state_out, uint64_t* hist, uint64_t* detections,
+                           hare_counters* ctr, const int64_t* first_ray)
 {
-    const char* who = n_scenes == 1 ? "hare_receive_batch" : "hare_receive_batch_sharded";
     if (!scenes || n_scenes < 1 || n_scenes > 64) {
         set_error(std::string(who) + ": need 1..64 scenes");
         return HARE_E_INVALID;
@@ -489,9 +490,22 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
         }
     hare_scene* const s0 = scenes[0];
     if (int rc = receive_check_args(who, *s0, flags, kind, top_index, n, bounces, n_bins, bin_len, frac_bits)) return rc;
-    if ((n > 0 && !rays) || !hist || !detections) {
+    if ((n > 0 && !rays && !first_ray) || !hist || !detections) {
         set_error(std::string(who) + ": null rays, histogram or detections");
         return HARE_E_INVALID;
+    }
+    if (first_ray) {
+        if (int rc = source_check_range(who, n, *first_ray)) return rc;
+        if (s0->src.set && s0->src.B != scene_bands(*s0, top_index)) {
+            set_error(std::string(who) + ": the source has " + std::to_string(s0->src.B) + " bands, the topology " +
+                      std::to_string(scene_bands(*s0, top_index)));
+            return HARE_E_INVALID;
+        }
+        for (int32_t k = 1; k < n_scenes; ++k)
+            if (!scenes[k]->src.same_as(s0->src) || scenes[k]->opt.source_seed != s0->opt.source_seed) {
+                set_error(std::string(who) + ": the scenes differ in source or source_seed");
+                return HARE_E_INVALID;
+            }
     }
     auto sigma_of = [&](const Scene& s) -> const std::vector<double>* {
         return scene_has_scattering(s, top_index) ? &s.sigma[(size_t)top_index].host : nullptr;
@@ -541,8 +555,10 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
         job.stride = n;
         job.hist = k == 0 ? hist : hists[(size_t)k].data();
         job.det = k == 0 ? detections : dets[(size_t)k].data();
-        job.ray_base = lo;
+        job.ray_base = (first_ray ? *first_ray : 0) + lo;
         job.flags = flags;
+        job.from_source = first_ray != nullptr;
+        job.who = who;
         try {
             rcs[(size_t)k] = bounce_one(scenes[k], kind, top_index, hi - lo, rays ? rays + lo : nullptr, excl1 ? excl1 + lo : nullptr,
                                         excl2 ? excl2 + lo : nullptr, bounces, flags, nullptr, n, nullptr, pcs[(size_t)k].data(), &job);
@@ -577,6 +593,43 @@ int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int3
             for (int32_t b = 0; b < bounces; ++b) add_counters(*ctr, pcs[(size_t)k][(size_t)b]);
     return HARE_OK;
     GUARD_END
+}
+
+extern "C" {
+
+int hare_receive_batch(hare_scene* s, int32_t kind, int32_t top_index, int64_t n, const hare_ray* rays, const int32_t* excl1,
+                       const int32_t* excl2, int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits,
+                       const double* state_in, double* state_out, uint64_t* hist, uint64_t* detections, hare_counters* ctr)
+{
+    hare_scene* const one[1] = {s};
+    return receive_sharded("hare_receive_batch", one, 1, kind, top_index, n, rays, excl1, excl2, bounces, flags, n_bins, bin_len, frac_bits,
+                           state_in, state_out, hist, detections, ctr, nullptr);
+}
+
+int hare_receive_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int32_t kind, int32_t top_index, int64_t n, const hare_ray* rays,
+                               const int32_t* excl1, const int32_t* excl2, int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len,
+                               int32_t frac_bits, const double* state_in, double* state_out, uint64_t* hist, uint64_t* detections,
+                               hare_counters* ctr)
+{
+    return receive_sharded(n_scenes == 1 ? "hare_receive_batch" : "hare_receive_batch_sharded", scenes, n_scenes, kind, top_index, n, rays, excl1,
+                           excl2, bounces, flags, n_bins, bin_len, frac_bits, state_in, state_out, hist, detections, ctr, nullptr);
+}
+
+int hare_receive_source(hare_scene* s, int32_t kind, int32_t top_index, int64_t n, int64_t first_ray, int32_t bounces, uint32_t flags,
+                        int32_t n_bins, double bin_len, int32_t frac_bits, double* state_out, uint64_t* hist, uint64_t* detections,
+                        hare_counters* ctr)
+{
+    hare_scene* const one[1] = {s};
+    return receive_sharded("hare_receive_source", one, 1, kind, top_index, n, nullptr, nullptr, nullptr, bounces, flags, n_bins, bin_len,
+                           frac_bits, nullptr, state_out, hist, detections, ctr, &first_ray);
+}
+
+int hare_receive_source_sharded(hare_scene* const* scenes, int32_t n_scenes, int32_t kind, int32_t top_index, int64_t n, int64_t first_ray,
+                                int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits, double* state_out,
+                                uint64_t* hist, uint64_t* detections, hare_counters* ctr)
+{
+    return receive_sharded(n_scenes == 1 ? "hare_receive_source" : "hare_receive_source_sharded", scenes, n_scenes, kind, top_index, n, nullptr,
+                           nullptr, nullptr, bounces, flags, n_bins, bin_len, frac_bits, nullptr, state_out, hist, detections, ctr, &first_ray);
 }
 
 }  // extern "C"

@@ -129,6 +129,7 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_vb_fill_big", &m->vb_fill_big},
         {"hare_ob_count", &m->ob_count},
         {"hare_ob_fill", &m->ob_fill},
+        {"hare_emit_source", &m->emit_source},
     };
     for (auto& t : table) {
         hipError_t e = H->ModuleGetFunction(t.fn, m->mod, t.name);

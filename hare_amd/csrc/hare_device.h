@@ -541,6 +541,24 @@ struct RainArgs {
     int32_t k_emit;            // receiver whose query is emitted (-1: none)
 };
 
+// hare_emit_source (source.hip): the scene's point source (include/hare_hip.h, "receivers", "Source") -- n rays from `pos` with directions
+// uniform on the sphere, and their starting state L = 0, E[b] = power[b] * gain_b(d).  Position, power and frame by value; the table by pointer
+constexpr unsigned kSourceCounter = 4096;     // the RNG counter c of the emission: the casts use c < 4096
+constexpr int kMaxSourceRes = 64;
+struct SourceArgs {
+    RayRec* rays;              // n rays, written
+    double* state;             // (1 + bands) planes of n doubles, written: L, E[0 .. bands-1]
+    const double* gain;        // 6 x res x res x bands, band innermost (null iff res == 0: every gain 1.0)
+    long long n;
+    long long first_ray;       // g = first_ray + i
+    unsigned long long seed;   // scene option "source_seed"
+    double pos[3];
+    double power[kMaxBands];
+    double frame[9];           // M, row-major: the lookup is in l = M d
+    int32_t bands;             // 1 .. kMaxBands
+    int32_t res;               // R: 0 (no table) .. kMaxSourceRes
+};
+
 #if defined(__HIPCC__)
 // Every kernel argument as a scalar of its OWN (round 6).  The compiler fetches the 720-byte argument block in tuples of 8 and 16 SGPRs and,
 // short of SGPRs in these kernels, spills and reloads them AS tuples: a block that needs the rays' pointer reloaded sixteen registers to get

@@ -1,7 +1,8 @@
 // receive.cpp -- receivers, absorption and scattering of a scene (hare_scene_set_receivers / _absorption / _scattering), the receive loop's plan
 // and its per-cast step (receive_plan, receive_step: what bounce_device_impl, launch.cpp, runs between its casts) and hare_receive_device
-// (include/hare_hip.h, "receivers"; the kernels: receive.hip).  The host-buffer calls hare_receive_batch / _sharded are in bounce.cpp, beside
-// the loop they share with hare_bounce_batch.
+// (include/hare_hip.h, "receivers"; the kernels: receive.hip); the point source (hare_scene_set_source, hare_emit_device; the kernel:
+// source.hip).  The host-buffer calls hare_receive_batch / _sharded and hare_receive_source / _sharded are in bounce.cpp, beside the loop
+// they share with hare_bounce_batch.
 //
 // Harness-defined: the reference has no receivers (Pachyderm, its caller, detects them on the host per ray).
 // Product code; nothing from oracle/.
@@ -50,6 +51,7 @@ int upload_receivers(Scene& s, const HipApi* H)
 void free_receivers(const HipApi* H, Scene& s)
 {
     dev_free(H, s.d_rcv);
+    dev_free(H, s.src.d_gain);
     for (std::vector<Scene::BandTable>* tables : {&s.alpha, &s.sigma})
         for (Scene::BandTable& t : *tables) dev_free(H, t.dev);
 }
@@ -229,6 +231,70 @@ int receive_ready(Scene& s, const HipApi* H, const char* who)
     return upload_receivers(s, H);
 }
 
+// ---- the point source (include/hare_hip.h, "receivers", "Source")
+bool Scene::Source::same_as(const Source& o) const
+{
+    return set == o.set && B == o.B && R == o.R && memcmp(pos, o.pos, sizeof pos) == 0 && memcmp(power, o.power, sizeof power) == 0 &&
+           memcmp(frame, o.frame, sizeof frame) == 0 && gain == o.gain;
+}
+
+int source_check_range(const char* who, int64_t n, int64_t first_ray)
+{
+    if (first_ray < 0 || n < 0 || first_ray > ((int64_t)1 << 62) - n) {
+        set_error(std::string(who) + ": first_ray out of range (first_ray >= 0, first_ray + n <= 2^62)");
+        return HARE_E_INVALID;
+    }
+    return HARE_OK;
+}
+
+static int upload_source(Scene& s, const HipApi* H)
+{
+    Scene::Source& src = s.src;
+    if (!src.set || src.gain.empty() || src.on_device) return HARE_OK;
+    if (int rc = upload(H, &src.d_gain, src.gain.data(), src.gain.size() * sizeof(double))) return rc;
+    src.on_device = true;
+    return HARE_OK;
+}
+
+// After the device checks: a source set, and its table on the device (uploads only what a setter run without a device left behind)
+int source_ready(Scene& s, const HipApi* H, const char* who)
+{
+    if (!s.src.set) {
+        set_error(std::string(who) + ": no source set (hare_scene_set_source)");
+        return HARE_E_STATE;
+    }
+    return upload_source(s, H);
+}
+
+int emit_source(const Scene& s, const HipApi* H, int64_t n, int64_t first_ray, void* d_rays, void* d_state, hipStream_t st)
+{
+    const Scene::Source& src = s.src;
+    if (!s.module || !s.module->emit_source) {
+        set_error("hare_emit_source missing from code object");
+        return HARE_E_STATE;
+    }
+    if (n == 0) return HARE_OK;
+    SourceArgs a;
+    memset(&a, 0, sizeof a);
+    a.rays = (RayRec*)d_rays;
+    a.state = (double*)d_state;
+    a.gain = src.R > 0 ? (const double*)src.d_gain : nullptr;
+    a.n = n;
+    a.first_ray = first_ray;
+    a.seed = (unsigned long long)s.opt.source_seed;
+    memcpy(a.pos, src.pos, sizeof a.pos);
+    memcpy(a.power, src.power, sizeof a.power);
+    memcpy(a.frame, src.frame, sizeof a.frame);
+    a.bands = src.B;
+    a.res = src.R;
+    if (src.R > 0 && !a.gain) {
+        set_error("source: directivity table not on the device");
+        return HARE_E_STATE;
+    }
+    void* args[] = {&a};
+    return launch(H, s.module->emit_source, (unsigned)((n + 255) / 256), 256, 0, st, args);
+}
+
 // hare_scene_set_absorption / _scattering behind their own checks of top_index and B: P x B coefficients in [0, 1] become Model[top]'s
 // table `mine` (`name` in the messages), with the B of the topology's other table where it has one
 static int set_band_table(Scene& s, const char* who, const char* name, std::vector<Scene::BandTable>& mine, const std::vector<Scene::BandTable>& other,
@@ -360,6 +426,87 @@ int hare_scene_set_scattering(hare_scene* s, int32_t top_index, int32_t B, const
     }
     GUARD_BEGIN
     return set_band_table(*s, "hare_scene_set_scattering", "sigma", s->sigma, s->alpha, "absorption", top_index, B, sigma);
+    GUARD_END
+}
+
+int hare_scene_set_source(hare_scene* s, const double pos[3], int32_t B, const double* power, const double* frame, int32_t R, const double* gain)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    auto bad = [&](const std::string& what) {
+        set_error("hare_scene_set_source: " + what);
+        return HARE_E_INVALID;
+    };
+    if (!pos || !(std::isfinite(pos[0]) && std::isfinite(pos[1]) && std::isfinite(pos[2]))) return bad("need a finite position");
+    if (B < 1 || B > kMaxBands) return bad("bands out of range (1 .. 8)");
+    if (R < 0 || R > kMaxSourceRes) return bad("table resolution out of range (0 .. 64)");
+    if ((R == 0) != (gain == nullptr)) return bad("a directivity table needs R >= 1, and R >= 1 a table");
+    if (frame)
+        for (int k = 0; k < 9; ++k)
+            if (!std::isfinite(frame[k])) return bad("non-finite frame");
+    if (power)
+        for (int32_t b = 0; b < B; ++b)
+            if (!(std::isfinite(power[b]) && power[b] >= 0)) return bad("power[" + std::to_string(b) + "] must be finite and >= 0");
+    const size_t cnt = (size_t)6 * (size_t)R * (size_t)R * (size_t)B;
+    for (size_t k = 0; k < cnt; ++k)
+        if (!(std::isfinite(gain[k]) && gain[k] >= 0)) return bad("gain[" + std::to_string(k) + "] must be finite and >= 0");
+    GUARD_BEGIN
+    std::vector<double> g(gain, gain + cnt);
+    Scene::Source& src = s->src;
+    memcpy(src.pos, pos, sizeof src.pos);
+    src.B = B;
+    for (int32_t b = 0; b < kMaxBands; ++b) src.power[b] = b < B ? (power ? power[b] : 1.0) : 0.0;
+    for (int k = 0; k < 9; ++k) src.frame[k] = frame ? frame[k] : (k % 4 == 0 ? 1.0 : 0.0);
+    src.R = R;
+    src.gain.swap(g);
+    src.on_device = false;
+    src.set = true;
+    const HipApi* H = nullptr;
+    if (!device_present(H)) return HARE_OK;          // GPU-less: the table goes up with the first call that emits
+    DeviceGuard dev_guard(H, s->device);
+    if (int rc = ensure_device(*s, H)) return rc;
+    if (src.gain.empty()) {                          // a table replaced by none
+        dev_free(H, src.d_gain);
+        return HARE_OK;
+    }
+    return upload_source(*s, H);
+    GUARD_END
+}
+
+int hare_emit_device(hare_scene* s, int64_t n, int64_t first_ray, void* d_rays, void* d_state, void* stream)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    if (n < 0 || n > 0x7FFFFF00ll) {
+        set_error("hare_emit_device: n out of range (0 .. 2^31 - 256)");
+        return HARE_E_INVALID;
+    }
+    if (int rc = source_check_range("hare_emit_device", n, first_ray)) return rc;
+    if (n > 0) {
+        const int32_t B = s->src.set ? s->src.B : 1;
+        if (!d_rays || !d_state) {
+            set_error("hare_emit_device: null rays / state");
+            return HARE_E_INVALID;
+        }
+        if (ranges_overlap(d_rays, (size_t)n * sizeof(hare_ray), d_state, (size_t)n * (size_t)(1 + B) * sizeof(double))) {
+            set_error("hare_emit_device: rays and state must not overlap");
+            return HARE_E_INVALID;
+        }
+    }
+    GUARD_BEGIN
+    const HipApi* H = api_or_err();
+    if (!H) return HARE_E_NODEVICE;
+    DeviceGuard dev_guard(H, s->device);
+    if (!s->module) {
+        int rc = ensure_device(*s, H);
+        if (rc) return rc;
+    }
+    if (int rc = source_ready(*s, H, "hare_emit_device")) return rc;
+    return emit_source(*s, H, n, first_ray, d_rays, d_state, (hipStream_t)stream);
     GUARD_END
 }
 

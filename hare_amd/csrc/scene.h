@@ -65,6 +65,7 @@ struct SceneOptions {
     int receive_floor_bits = 0;    // f: the receive loop's energy floor F = 2^-f (0: off; include/hare_hip.h, "Termination")
     int receive_roulette = 0;      // 1: a ray under the floor plays Russian roulette (word 65 of the scattering RNG)
     long long scatter_seed = 0;    // the scattering RNG's seed S (hare_receive_scatter; read as uint64 bits)
+    long long source_seed = 0;     // the point source's seed S (hare_emit_source; read as uint64 bits)
     long long dev_order_ptr = 0;   // developer experiments (a `dev` scene only): a device array of n uint32, the order K1q takes the rays in (ShootIO::order)
     int tune[5] = {0, 0, 0, 0, 0};   // HARE_TUNE: steps,refill,chunk,blocks_per_cu,exact (profiling build; blocks_per_cu: K1p)
 };
@@ -125,6 +126,7 @@ struct DeviceModule {
     // receive.hip, [directional]: hare_receive_reflect / _scatter / _scatter_rain (no table / a scattering table / with diffuse rain),
     // hare_rain_step, and HARE_RECEIVE_DIRECTIONAL's _dir forms
     hipFunction_t receive[3][2] = {}, rain_step[2] = {};
+    hipFunction_t emit_source = nullptr;                                   // source.hip
     hipFunction_t voxel_occl_tri = nullptr, voxel_occl_quad = nullptr, voxel_occl_tri_g = nullptr, voxel_occl_quad_g = nullptr, octree_occl = nullptr, octree_occl_any = nullptr;
     hipFunction_t events_pack_slim = nullptr;
     hipFunction_t block_occ = nullptr;                                     // build_kernels.hip: hare_block_occ
@@ -301,6 +303,20 @@ struct Scene {
     std::vector<BandTable> alpha;                // per topology: absorption (no table: B = 1, every alpha 0)
     std::vector<BandTable> sigma;                // per topology: scattering (no table: specular only)
     std::vector<int32_t> bands;                  // per topology: B of its tables (1 without one); the first table set fixes it for the other
+    // the point source (hare_scene_set_source, receive.cpp): kept and uploaded as the receivers are
+    struct Source {
+        bool set = false;
+        double pos[3] = {0, 0, 0};
+        int32_t B = 0;                           // 1 .. kMaxBands
+        double power[kMaxBands] = {};
+        double frame[9] = {};
+        int32_t R = 0;                           // 0: no directivity table
+        std::vector<double> gain;                // 6 x R x R x B, band innermost
+        void* d_gain = nullptr;
+        bool on_device = false;                  // the table (a source without one has nothing to upload)
+        bool same_as(const Source& o) const;     // what the sharded call compares
+    };
+    Source src;
 };
 void free_host_mirror(Scene& s);             // host_trace.cpp
 void make_poly_records(const Topo& T, std::vector<PolyRec>& rec, std::vector<QuadRec>& quads);   // device_scene.cpp
@@ -367,6 +383,11 @@ int receive_plan(const Scene& s, int32_t top, uint32_t flags, int64_t n, int32_t
 int receive_step(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, const ReceivePlan& p, void* d_rays, void* d_ev,
                  int32_t* marks, unsigned char* block_live, int32_t cast, bool last_cast, hipStream_t st);
 int receive_ready(Scene& s, const HipApi* H, const char* who);
+// the point source (receive.cpp).  source_check_range: 0 <= first_ray, first_ray + n <= 2^62 (HARE_E_INVALID); source_ready: a source is set
+// (HARE_E_STATE) and its table on the device; emit_source: hare_emit_source on the stream -- n rays from first_ray and their (1 + B) x n state
+int source_check_range(const char* who, int64_t n, int64_t first_ray);
+int source_ready(Scene& s, const HipApi* H, const char* who);
+int emit_source(const Scene& s, const HipApi* H, int64_t n, int64_t first_ray, void* d_rays, void* d_state, hipStream_t st);
 
 // device plumbing (device_scene.cpp) shared with api.cpp, launch.cpp and build_gpu.cpp
 const HipApi* api_or_err();

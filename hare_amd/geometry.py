@@ -393,6 +393,72 @@ class Spatial_Partition:
         check(lib.hare_scene_set_scattering(self._h, int(top_index), s.shape[1], ptr(s)))
         return self
 
+    def set_source(self, pos, power=None, frame=None, gain=None):
+        """hare_scene_set_source: the scene's point source (include/hare_hip.h, "receivers", "Source").  pos [3]; power [B] per band (None:
+        1.0 in each of the B bands of `gain`, or of topology 0 without a table); frame [3, 3] (None: identity); gain [6, R, R, B], the
+        directivity as a nearest-texel cube map read in the source's frame (None: omnidirectional).  Seed: option "source_seed"."""
+        p = np.ascontiguousarray(pos, np.float64).reshape(-1)
+        if p.shape != (3,):
+            raise ValueError("pos must be [3]")
+        g = None if gain is None else np.ascontiguousarray(gain, np.float64)
+        if g is not None and not (g.ndim == 4 and g.shape[0] == 6 and g.shape[1] == g.shape[2]):
+            raise ValueError("gain must be [6, R, R, B]")
+        w = None if power is None else np.ascontiguousarray(power, np.float64).reshape(-1)
+        B = w.shape[0] if w is not None else (g.shape[3] if g is not None else self._bands(0))
+        if g is not None and g.shape[3] != B:
+            raise ValueError("power and gain must have the same number of bands")
+        f = None if frame is None else np.ascontiguousarray(frame, np.float64).reshape(-1)
+        if f is not None and f.shape != (9,):
+            raise ValueError("frame must be [3, 3]")
+        check(lib.hare_scene_set_source(self._h, ptr(p), int(B), ptr(w), ptr(f), 0 if g is None else g.shape[1], ptr(g)))
+        return self
+
+    def emit_device(self, n: int, d_rays: int, d_state: int, first_ray: int = 0, stream: int = 0):
+        """hare_emit_device on raw device addresses + a hipStream_t: the source's rays first_ray .. first_ray + n - 1 into d_rays (n x 48 B)
+        and their state into d_state ((1 + B) x n doubles, B = get_option("source_bands")).  Stream-ordered."""
+        check(lib.hare_emit_device(self._h, int(n), int(first_ray), d_rays or None, d_state or None, stream or None))
+
+    def Receive_source(self, n: int, bounces: int, n_bins: int, bin_len: float, first_ray: int = 0, frac_bits: int = 40, top_index: int = 0,
+                       out=None, rain: bool = False, directional: bool = False, time_limit: bool = False):
+        """hare_receive_source: Receive_batch with the rays and their state emitted on the device by the scene's source (set_source) --
+        the rays first_ray .. first_ray + n - 1; nothing but the count goes up.  Returns what Receive_batch returns.  Calls over
+        [0, k) and [k, n) sum to the histogram and detections of the one call."""
+        return Spatial_Partition._receive_source([self], n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain, directional,
+                                                 time_limit)
+
+    @staticmethod
+    def Receive_source_sharded(partitions, n: int, bounces: int, n_bins: int, bin_len: float, first_ray: int = 0, frac_bits: int = 40,
+                               top_index: int = 0, out=None, rain: bool = False, directional: bool = False, time_limit: bool = False):
+        """hare_receive_source_sharded: Receive_source over several partitions (contiguous ray shards, histograms summed); byte-identical.
+        The partitions must hold the same source and "source_seed"."""
+        return Spatial_Partition._receive_source(list(partitions), n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain,
+                                                 directional, time_limit)
+
+    @staticmethod
+    def _receive_source(parts, n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain, directional, time_limit):
+        if not parts or any(p._kind != parts[0]._kind for p in parts):
+            raise ValueError("need one or more partitions of the same kind")
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        shape = parts[0]._receive_shape(top_index, n_bins, bool(directional))
+        K, nb, B = shape[:3]
+        hist = _result_array(out, (max(K, 0),) + shape[1:], np.uint64)
+        det = np.zeros((max(K, 0), 2), np.uint64)
+        state_out = np.empty((1 + B, n), np.float64)
+        ctr = capi.Counters()
+        flags = ((capi.RECEIVE_DIFFUSE_RAIN if rain else 0) | (capi.RECEIVE_DIRECTIONAL if directional else 0) |
+                 (capi.RECEIVE_TIME_LIMIT if time_limit else 0))
+        if len(parts) == 1:
+            rc = lib.hare_receive_source(parts[0]._h, parts[0]._kind, int(top_index), n, int(first_ray), int(bounces), flags, nb, float(bin_len),
+                                         int(frac_bits), ptr(state_out), ptr(hist), ptr(det), C.addressof(ctr))
+        else:
+            handles = (C.c_void_p * len(parts))(*[p._h for p in parts])
+            rc = lib.hare_receive_source_sharded(handles, len(parts), parts[0]._kind, int(top_index), n, int(first_ray), int(bounces), flags, nb,
+                                                 float(bin_len), int(frac_bits), ptr(state_out), ptr(hist), ptr(det), C.addressof(ctr))
+        check(rc)
+        return hist, hist.astype(np.float64) * 2.0 ** -int(frac_bits), det, state_out, ctr.as_dict()
+
     def _receive_shape(self, top_index: int, n_bins: int, directional: bool = False):
         shape = (self.get_option("receivers"), int(n_bins), self._bands(top_index))
         return shape + (4,) if directional else shape

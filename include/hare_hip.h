@@ -227,6 +227,7 @@ HARE_API void hare_scene_destroy(hare_scene *s);
  *   "receive_aggregate"  1 (default): hare_receive_reflect sums a wave's histogram adds per distinct (receiver, bin) before ONE atomic
  *                     instruction; 0: an atomic per detecting lane and band (A/B).  Results never depend on it
  *   "scatter_seed"    any int64 (default 0), read as uint64 bits: the seed S of the receive loop's scattering RNG ("receivers" below)
+ *   "source_seed"     any int64 (default 0), read as uint64 bits: the seed S of the point source's directions ("receivers", "Source", below)
  *   "receive_floor_bits"  f = 0 (default: off) .. 1000: the receive loop's energy floor F = 2^-f ("receivers", "Termination", below)
  *   "receive_roulette"    0 (default) / 1: a ray under the floor plays Russian roulette instead of being retired outright (the same section)
  *   "dev"             1: developer flag bits of hare_shoot_* (timeline, phase profile, cull audit) pass
@@ -246,6 +247,7 @@ HARE_API int hare_scene_set_option(hare_scene *s, const char *name, int64_t valu
  *                           octree launch that needs one)
  *   "receivers", "bands"    K of hare_scene_set_receivers (0: none set) and B of topology 0's absorption / scattering tables (1: none);
  *   "bands:<top>"           B of topology <top> (e.g. "bands:1"; HARE_E_INVALID for a topology the scene does not have)
+ *   "source", "source_bands", "source_res"   1 when hare_scene_set_source has set a source (0: none), its B and its table's R (0: no table)
  * No reference counterpart: Hare has no device memory to account for. */
 HARE_API int hare_scene_get_option(const hare_scene *s, const char *name, int64_t *value);
 
@@ -577,6 +579,37 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * probability ps and is then worth 1 / ps), at the price of variance in the late tail.  The plain floor is BIASED by design: it drops
  * what lies under F, at most F per ray and band.  Later casts run over the rays still live; the call makes no host round trip.
  *
+ * Source (hare_scene_set_source; hare_emit_device, hare_receive_source / _sharded).  The scene may hold one point source: a position, a
+ * power per band (B bands), and optionally a directivity table with the frame it is read in.  The source's rays and their starting state are
+ * drawn on the device from a ray COUNT, bit-exact with a restatement on the host like everything else in the loop.  FP64, no contraction;
+ * integers are uint64 and wrap; mix, G and u_j are those of "Scattering" above.  g = first_ray + i is the global index of ray i of a call, S
+ * the scene option "source_seed" (any int64, default 0, read as uint64 bits like "scatter_seed"), and the counter is c = 4096 -- the casts
+ * use c < 4096, so no word is shared with them even when both seeds are equal:
+ *
+ *   base = mix(mix(S + G) ^ g)
+ *   for t = 0 .. 31: x = 2.0*u_{1+2t} - 1.0; y = 2.0*u_{2+2t} - 1.0; s = x*x + y*y; take the first with s < 1.0   (none taken: x = y = s = 0)
+ *   h = sqrt(1.0 - s)
+ *   d = ((2.0*x)*h, (2.0*y)*h, 1.0 - 2.0*s)            (Marsaglia 1972: uniform on the sphere; |d| = 1 up to rounding, not renormalised)
+ *   ray = (pos, d);  L = 0;  E[b] = power[b] * gain_b(d)
+ *
+ * gain_b is 1.0 without a table.  With one it is a nearest-texel cube map of resolution R: table[6][R][R][B], band innermost, read in the
+ * source's frame M (3 x 3, row-major; it need not be orthonormal):
+ *
+ *   l_i = (M[i][0]*dx + M[i][1]*dy) + M[i][2]*dz;  a_i = |l_i|                        i = 0, 1, 2
+ *   f = 0; if (a_1 > a_f) f = 1; if (a_2 > a_f) f = 2                                 (ties and NaN keep the lower index)
+ *   F = 2f + (l_f < 0 ? 1 : 0);  the texel axes are u = (f + 1) % 3 and v = (f + 2) % 3
+ *   su = l_u / a_f;  tu = (su + 1.0) * (0.5 * R);  iu = tu >= 0 ? (tu < R ? (int)floor(tu) : R - 1) : 0      (NaN -> 0); iv likewise from l_v
+ *   gain_b = table[((F*R + iv)*R + iu)*B + b]
+ *
+ * so face 0 / 1 is +x / -x of the frame, 2 / 3 is +y / -y, 4 / 5 is +z / -z (a zero frame gives 0 / 0: texel 0 of face 0).  Counter-based
+ * means: rays [k, n) of a call with first_ray = a are the rays of a call with first_ray = a + k; and as hare_receive_source's scattering
+ * and roulette draws use the same g = first_ray + i (with S = "scatter_seed"), a burst split into chunks gives, summed, the histogram and
+ * detections of the one call -- no seed needs changing.
+ *   hare_scene_set_source   a setter like those below.  pos: 3; power: B values, NULL for 1.0 in every band; frame: 9 values, NULL for the
+ *                           identity; gain: 6 x R x R x B values, NULL iff R == 0.  HARE_E_INVALID for a non-finite pos or frame, B outside
+ *                           1..8, R outside 0..64, R and gain disagreeing, any power or gain that is not finite and >= 0.
+ *                           hare_scene_get_option reads "source" (0 / 1), "source_bands" and "source_res"
+ *
  * The histogram is fixed point in uint64: integer sums do not depend on the order of the adds, so the result is bit-identical from
  * run to run, between the one-device and the sharded call, and against a restatement on the host.  (r*r is formed once, when the
  * receivers are set: the same FP64 product.)
@@ -595,6 +628,14 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
 HARE_API int hare_scene_set_receivers(hare_scene *s, int32_t K, const double *centers, const double *radii);
 HARE_API int hare_scene_set_absorption(hare_scene *s, int32_t top_index, int32_t B, const double *alpha);
 HARE_API int hare_scene_set_scattering(hare_scene *s, int32_t top_index, int32_t B, const double *sigma);
+HARE_API int hare_scene_set_source(hare_scene *s, const double pos[3], int32_t B, const double *power /* B, nullable */,
+                                   const double *frame /* 9, nullable */, int32_t R, const double *gain /* 6 R R B, NULL iff R == 0 */);
+
+/* The source's rays on DEVICE buffers: n hare_ray into d_rays and the (1 + B) x n doubles of their state into d_state (plane 0: L, planes
+ * 1..B: E; B the source's), for the rays first_ray .. first_ray + n - 1 ("Source" above).  Stream-ordered like hare_shoot_device: no
+ * allocation, no free, no wait.  HARE_E_INVALID unless 0 <= n <= 2^31 - 256, first_ray >= 0 and first_ray + n <= 2^62; for null or
+ * overlapping buffers; then HARE_E_NODEVICE; then HARE_E_STATE when no source is set. */
+HARE_API int hare_emit_device(hare_scene *s, int64_t n, int64_t first_ray, void *d_rays, void *d_state, void *stream);
 
 /* The receive loop on DEVICE buffers: stream-ordered like hare_shoot_device -- no allocation, no free, no wait ("hip_malloc_calls" ...).
  * Always a launch per cast (the scene option "bounce_fused" does not apply; results are the same either way).
@@ -630,6 +671,18 @@ HARE_API int hare_receive_batch_sharded(hare_scene *const *scenes, int32_t n_sce
                                         uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits,
                                         const double *state_in, double *state_out, uint64_t *hist, uint64_t *detections,
                                         hare_counters *ctr);
+
+/* hare_receive_batch / _sharded with the upload of rays and state replaced by the source's emission on the loop's stream: the rays
+ * first_ray .. first_ray + n - 1 of the scene's source ("Source" above), no exclusions.  In the sharded call the shard that starts at ray lo
+ * emits from first_ray + lo.  Flags, checks and outputs as hare_receive_batch's, and HARE_E_INVALID when first_ray < 0 or
+ * first_ray + n > 2^62, or when the source's B is not the band count of Model[top_index]; HARE_E_STATE when no source is set.  The sharded
+ * call also refuses scenes whose source or "source_seed" differ. */
+HARE_API int hare_receive_source(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, int64_t first_ray, int32_t bounces,
+                                 uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits, double *state_out, uint64_t *hist,
+                                 uint64_t *detections, hare_counters *ctr);
+HARE_API int hare_receive_source_sharded(hare_scene *const *scenes, int32_t n_scenes, int32_t kind, int32_t top_index, int64_t n,
+                                         int64_t first_ray, int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len,
+                                         int32_t frac_bits, double *state_out, uint64_t *hist, uint64_t *detections, hare_counters *ctr);
 
 #ifdef __cplusplus
 }

@@ -16,8 +16,13 @@ With --time-limit and / or --floor-bits N [--roulette] (the header's "Terminatio
 limit, with the energy floor 2^-N, and with both where both are given: cut_*_ms against ms of the same row, and the share of the rays
 still live -- over all casts (the loop's ray counter over n x bounces) and in the casts 1, 2, 4, 8, ... (the counter's difference between
 two calls that differ by one cast).
+With --source (K = 8, B = 8 only; nothing else of the above runs), the host wall time of hare_receive_source against hare_receive_batch
+given the same rays (the source's own, downloaded once), without and with state_in: the three calls interleaved, the median of --reps
+runs (default there: 9) after a warm-up, and the spread (min, max) of each; and hare_emit_source alone between HIP events, beside the
+120 B per ray it writes at B = 8.  Run it under rocprofv3 --kernel-trace --stats for the kernel's own time.
 Prints ONE JSON line.  usage: python tools/receiver_rate.py [hall|cathedral] [--rays N] [--bounces B] [--reps R] [--host] [--quick]
-                                                          [--scatter SIGMA] [--rain] [--directional] [--time-limit] [--floor-bits N [--roulette]]"""
+                                                          [--scatter SIGMA] [--rain] [--directional] [--time-limit] [--floor-bits N [--roulette]]
+                                                          [--source]"""
 import argparse
 import json
 import os
@@ -34,7 +39,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("scene", nargs="?", default="hall", choices=["hall", "cathedral"])
 ap.add_argument("--rays", type=int, default=1 << 20)
 ap.add_argument("--bounces", type=int, default=8)
-ap.add_argument("--reps", type=int, default=10)
+ap.add_argument("--reps", type=int, default=None, help="timed runs per figure (default 10; 9 with --source)")
 ap.add_argument("--host", action="store_true", help="also time Bounce_batch(all_casts=True) + the numpy step (K = 8, B = 8)")
 ap.add_argument("--quick", action="store_true", help="K = 8, B = 8 only (a profiling run)")
 ap.add_argument("--scatter", type=float, default=None, metavar="SIGMA",
@@ -44,7 +49,10 @@ ap.add_argument("--directional", action="store_true", help="B = 8: every loop ag
 ap.add_argument("--time-limit", action="store_true", help="the loop again with HARE_RECEIVE_TIME_LIMIT")
 ap.add_argument("--floor-bits", type=int, default=0, metavar="N", help="the loop again with the energy floor 2^-N (scene option receive_floor_bits)")
 ap.add_argument("--roulette", action="store_true", help="with --floor-bits: Russian roulette under the floor (scene option receive_roulette)")
+ap.add_argument("--source", action="store_true", help="K = 8, B = 8: hare_receive_source against hare_receive_batch from host rays, wall time")
 a = ap.parse_args()
+if a.reps is None:
+    a.reps = 9 if a.source else 10
 if a.rain and a.scatter is None:
     a.scatter = 0.3
 if not torch.cuda.is_available():
@@ -69,6 +77,50 @@ def receivers(K):
     c = [S + np.array([2.0, 0.0, 0.0])]                                 # the direct sound: r = 1 m at 2 m
     c += list(rng.uniform(0.1, 0.9, (K - 1, 3)) * np.asarray(mesh.size))
     return np.array(c), np.concatenate([[1.0], rng.uniform(0.3, 1.0, K - 1)])
+
+
+def source_run():
+    """hare_receive_source against hare_receive_batch on the same rays, host wall time (what a caller with host buffers sees)."""
+    K, B = 8, 8
+    c, r = receivers(K)
+    g.set_receivers(c, r).set_absorption(np.random.default_rng(B).uniform(0.02, 0.3, (T.Polygon_Count, B)))
+    g.set_source(S, power=np.ones(B)).set_option("source_seed", 1)
+    d_r = torch.empty((n, 6), dtype=torch.float64, device="cuda")
+    d_s = torch.empty((1 + B, n), dtype=torch.float64, device="cuda")
+    ms = []
+    for _ in range(a.reps + 1):
+        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.emit_device(n, d_r.data_ptr(), d_s.data_ptr(), stream=st)
+        e1.record(); torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    emit_ms = float(np.median(ms[1:]))
+    src_rays, src_state = d_r.cpu().numpy(), d_s.cpu().numpy()
+    calls = {"source": lambda: g.Receive_source(n, nb, N_BINS, BIN_LEN, frac_bits=FRAC),
+             "batch": lambda: g.Receive_batch(src_rays, nb, N_BINS, BIN_LEN, frac_bits=FRAC),
+             "batch_state_in": lambda: g.Receive_batch(src_rays, nb, N_BINS, BIN_LEN, energy=src_state, frac_bits=FRAC)}
+    res = {k: f() for k, f in calls.items()}                              # the warm-up; and the three compute the same
+    same = all(res["source"][i].tobytes() == res["batch_state_in"][i].tobytes() for i in (0, 2, 3))
+    wall = {k: [] for k in calls}
+    for _ in range(a.reps):                                               # interleaved: drift of the host or the link meets all three alike
+        for k, f in calls.items():
+            t0 = time.perf_counter()
+            f()
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+    row = {"scene": a.scene, "domain": D, "rays": n, "bounces": nb, "K": K, "B": B, "reps": a.reps, "same_bytes": bool(same),
+           "emit_ms": round(emit_ms, 4), "emit_bytes_per_ray": 48 + 8 * (1 + B), "emit_GBps": round(n * (48 + 8 * (1 + B)) / emit_ms / 1e6, 1),
+           "emit_Mrays_s": round(n / emit_ms / 1e3, 1)}
+    for k, v in wall.items():
+        row[k + "_ms"] = round(float(np.median(v)), 3)
+        row[k + "_min_max_ms"] = [round(min(v), 3), round(max(v), 3)]
+    row["source_over_batch"] = round(row["source_ms"] / row["batch_ms"], 3)
+    row["source_over_batch_state_in"] = round(row["source_ms"] / row["batch_state_in_ms"], 3)
+    print(json.dumps(row))
+
+
+if a.source:
+    source_run()
+    sys.exit(0)
 
 
 def timed(fn, reps):
