@@ -166,6 +166,13 @@ public:
         if (centers.size() != 3 * radii.size()) throw std::invalid_argument("SetReceivers: centers must hold 3 x radii.size() values");
         check(hare_scene_set_receivers(scene_, (int32_t)radii.size(), centers.data(), radii.data()));
     }
+    // A receiver map (hare_scene_set_receiver_map): up to 65 536 receivers found through a uniform grid over their centers; cell 0: twice
+    // the largest radius.  Diffuse rain does not combine with a map; SetReceivers afterwards returns the scene to the linear loop.
+    void SetReceiverMap(const std::vector<double>& centers, const std::vector<double>& radii, double cell = 0.0)
+    {
+        if (centers.size() != 3 * radii.size()) throw std::invalid_argument("SetReceiverMap: centers must hold 3 x radii.size() values");
+        check(hare_scene_set_receiver_map(scene_, (int32_t)radii.size(), centers.data(), radii.data(), cell));
+    }
     void SetAbsorption(int top_index, int bands, const std::vector<double>& alpha)
     {
         if (top_index < 0 || (size_t)top_index >= Model.size()) throw std::invalid_argument("SetAbsorption: bad top_index");

@@ -241,6 +241,15 @@ namespace Hare
                 foreach (IntPtr s in scenes) HareHip.Check(HareHip.hare_scene_set_receivers(s, radii.Length, centers, radii));
             }
 
+            /// <summary>A receiver map for every scene of this partition (hare_scene_set_receiver_map): up to 65 536 receivers, centers K x 3,
+            /// radii K, found through a uniform grid (cell 0: twice the largest radius).  Diffuse rain does not combine with a map;
+            /// SetReceivers afterwards returns to the linear loop.</summary>
+            public void SetReceiverMap(double[] centers, double[] radii, double cell = 0.0)
+            {
+                if (centers == null || radii == null || centers.Length != 3 * radii.Length) throw new ArgumentException("centers must hold 3 x radii.Length values");
+                foreach (IntPtr s in scenes) HareHip.Check(HareHip.hare_scene_set_receiver_map(s, radii.Length, centers, radii, cell));
+            }
+
             /// <summary>Absorption table of Model[top_index] (hare_scene_set_absorption): alpha[p * bands + b] in [0, 1].</summary>
             public void SetAbsorption(int top_index, int bands, double[] alpha)
             {

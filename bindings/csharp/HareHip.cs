@@ -221,6 +221,12 @@ namespace Hare
             // Receivers: energy-time histograms from the bounce loop (include/hare_hip.h, "receivers")
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_scene_set_receivers(IntPtr scene, int K, [In] double[] centers, [In] double[] radii);
+            /// <summary>Receiver map: up to 65 536 receivers found through a uniform grid over their centers; cell 0: twice the largest radius.</summary>
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_scene_set_receiver_map(IntPtr scene, int K, [In] double[] centers, [In] double[] radii, double cell);
+            /// <summary>The map's grid: geom (lower corner, cell edge, pad: 5), dims (3), CSR offsets (cells + 1) and items (K); each nullable.</summary>
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_scene_get_receiver_map(IntPtr scene, [Out] double[] geom, [Out] int[] dims, [Out] uint[] cell_start, [Out] uint[] cell_items);
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_scene_set_absorption(IntPtr scene, int top_index, int B, [In] double[] alpha);
             /// <summary>Scattering table of a topology (sigma P x B in [0, 1], the absorption table's B); B = 0 with sigma null removes it.</summary>

@@ -103,6 +103,8 @@ SYMBOLS = {
     "hare_occluded_batch": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     "hare_occluded_batch_sharded": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     "hare_scene_set_receivers": (C.c_int, [_vp, _i32, _vp, _vp]),
+    "hare_scene_set_receiver_map": (C.c_int, [_vp, _i32, _vp, _vp, C.c_double]),
+    "hare_scene_get_receiver_map": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "hare_scene_set_absorption": (C.c_int, [_vp, _i32, _i32, _vp]),
     "hare_scene_set_scattering": (C.c_int, [_vp, _i32, _i32, _vp]),
     "hare_receive_device": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _i32, _u32, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp,

@@ -929,6 +929,20 @@ int hare_scene_get_option(const hare_scene* s, const char* name, int64_t* value)
         *value = (int64_t)(s->rcv.size() / 4);
         return HARE_OK;
     }
+    if (strcmp(name, "receiver_map") == 0) {          // hare_scene_set_receiver_map: 1 while a map is set
+        *value = s->rmap.set ? 1 : 0;
+        return HARE_OK;
+    }
+    if (strcmp(name, "receiver_map_cells") == 0) {    // ... its grid's cell count (0: no map)
+        *value = s->rmap.set ? (int64_t)s->rmap.start.size() - 1 : 0;
+        return HARE_OK;
+    }
+    if (strcmp(name, "receiver_map_cell") == 0) {     // ... and its cell edge, as the bits of the double (0: no map)
+        int64_t bits = 0;
+        if (s->rmap.set) memcpy(&bits, &s->rmap.h, sizeof bits);
+        *value = bits;
+        return HARE_OK;
+    }
     if (strcmp(name, "bands") == 0) {                 // hare_scene_set_absorption / _scattering: B of topology 0 (1: no table)
         *value = scene_bands(*s, 0);
         return HARE_OK;

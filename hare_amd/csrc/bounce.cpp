@@ -513,7 +513,9 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
     for (int32_t k = 1; k < n_scenes; ++k) {     // the shards must compute the same thing
         const std::vector<double>* sk = sigma_of(*scenes[k]);
         const std::vector<double>* s0s = sigma_of(*s0);
-        if (scenes[k]->rcv != s0->rcv || scene_bands(*scenes[k], top_index) != scene_bands(*s0, top_index) ||
+        const Scene::ReceiverMap &mk = scenes[k]->rmap, &m0 = s0->rmap;      // the same receivers through the same loop: a map's grid too
+        if (scenes[k]->rcv != s0->rcv || mk.set != m0.set || (m0.set && (mk.h != m0.h || mk.start != m0.start || mk.items != m0.items)) ||
+            scene_bands(*scenes[k], top_index) != scene_bands(*s0, top_index) ||
             (top_index < (int32_t)scenes[k]->topos.size() ? scenes[k]->topos[(size_t)top_index].P : -1) != s0->topos[(size_t)top_index].P) {
             set_error(std::string(who) + ": the scenes differ in receivers, bands or polygons");
             return HARE_E_INVALID;

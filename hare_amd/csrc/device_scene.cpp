@@ -135,10 +135,11 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         hipError_t e = H->ModuleGetFunction(t.fn, m->mod, t.name);
         if (e != hipSuccess) *t.fn = nullptr;   // optional kernels may be absent in a given build
     }
-    const char* const receive_names[4] = {"hare_receive_reflect", "hare_receive_scatter", "hare_receive_scatter_rain", "hare_rain_step"};
-    for (int f = 0; f < 4; ++f)
+    const char* const receive_names[6] = {"hare_receive_reflect", "hare_receive_scatter", "hare_receive_scatter_rain", "hare_receive_reflect_map",
+                                          "hare_receive_scatter_map", "hare_rain_step"};
+    for (int f = 0; f < 6; ++f)
         for (int dir = 0; dir < 2; ++dir) {
-            hipFunction_t* fn = f < 3 ? &m->receive[f][dir] : &m->rain_step[dir];
+            hipFunction_t* fn = f < 5 ? &m->receive[f][dir] : &m->rain_step[dir];
             if (H->ModuleGetFunction(fn, m->mod, (std::string(receive_names[f]) + (dir ? "_dir" : "")).c_str()) != hipSuccess) *fn = nullptr;
         }
     (void)H->GetLastError();   // a failed lookup must not stay behind as the host's "last error"

@@ -491,7 +491,7 @@ struct ReceiveArgs {
     double bin_len;            // > 0
     double scale;              // 2^frac_bits
     int32_t bands;             // 1 .. kMaxBands
-    int32_t n_rcv;             // 1 .. kMaxReceivers
+    int32_t n_rcv;             // 1 .. kMaxReceivers (the _map kernels: 1 .. kMaxMapReceivers)
     int32_t n_bins;
     int32_t marks_valid;       // excl holds the previous reflection's marks (every cast after the first)
     int32_t last;              // 1: the loop's last cast -- no reflection
@@ -508,6 +508,18 @@ struct ReceiveArgs {
     double floor;              // F = 2^-"receive_floor_bits" (kCutFloor)
     int32_t cut;               // kCut* bits; 0: no rule, the kernels behave as they did without them
 };
+// The _map kernels (hare_scene_set_receiver_map): ReceiveArgs with the grid behind it, so that the kernels above keep their arguments,
+// byte for byte.  n_rcv is up to kMaxMapReceivers and rcv is not staged in LDS
+struct ReceiveMapArgs : ReceiveArgs {
+    const uint32_t* map_start; // CSR over the cells, x fastest: cells + 1 offsets into map_items
+    const uint32_t* map_items; // n_rcv receiver indices, each receiver once, in the cell of its center
+    double map_org[3];         // the grid's lower corner
+    double map_h;              // cell edge h
+    double map_pad;            // P = (r_max + h / 8) / h: the pad in cell units
+    int32_t map_n[3];          // the grid's cells per axis (their product <= kMaxMapCells)
+};
+constexpr int kMaxMapReceivers = 65536;
+constexpr int kMaxMapCells = 1 << 21;
 constexpr int32_t kCutTime = 1;      // HARE_RECEIVE_TIME_LIMIT
 constexpr int32_t kCutFloor = 2;     // "receive_floor_bits" > 0
 constexpr int32_t kCutRoulette = 4;  // ... with "receive_roulette" 1

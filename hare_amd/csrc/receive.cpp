@@ -30,10 +30,21 @@ bool device_present(const HipApi*& H)
 
 }  // namespace
 
-// The host copies to the device: fixed-size receiver block (never reallocated), an absorption and a scattering table per topology.  Called by the setters
-// when a device is present -- as a build pushes its partition -- and by a receive call only for what a setter could not upload.
+// The host copies to the device: the linear loop's fixed-size receiver block (allocated once, never reallocated), a map's three blocks (its
+// receivers, cell_start, cell_items: sized by the map, so upload() frees and allocates them again for every hare_scene_set_receiver_map),
+// an absorption and a scattering table per topology.  Called by the setters when a device is present -- as a build pushes its partition --
+// and by a receive call only for what a setter could not upload: no receive call reallocates anything a setter has uploaded.
+// hare_scene_set_receivers behind a map leaves the map's device blocks where they are, unused, until the next map replaces them or
+// free_receivers frees them with the scene.
 int upload_receivers(Scene& s, const HipApi* H)
 {
+    if (s.rmap.set && !s.rcv.empty() && !s.rcv_on_device) {      // a map: a block of its own size, and the grid next to it
+        Scene::ReceiverMap& m = s.rmap;
+        if (int rc = upload(H, &m.d_rcv, s.rcv.data(), s.rcv.size() * sizeof(double))) return rc;
+        if (int rc = upload(H, &m.d_start, m.start.data(), m.start.size() * sizeof(uint32_t))) return rc;
+        if (int rc = upload(H, &m.d_items, m.items.data(), m.items.size() * sizeof(uint32_t))) return rc;
+        s.rcv_on_device = true;
+    }
     if (!s.rcv.empty() && !s.rcv_on_device) {
         if (!s.d_rcv) HIP_TRY(H->Malloc(&s.d_rcv, (size_t)kMaxReceivers * 4 * sizeof(double)));
         HIP_TRY(H->Memcpy(s.d_rcv, s.rcv.data(), s.rcv.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -51,6 +62,9 @@ int upload_receivers(Scene& s, const HipApi* H)
 void free_receivers(const HipApi* H, Scene& s)
 {
     dev_free(H, s.d_rcv);
+    dev_free(H, s.rmap.d_rcv);
+    dev_free(H, s.rmap.d_start);
+    dev_free(H, s.rmap.d_items);
     dev_free(H, s.src.d_gain);
     for (std::vector<Scene::BandTable>* tables : {&s.alpha, &s.sigma})
         for (Scene::BandTable& t : *tables) dev_free(H, t.dev);
@@ -100,6 +114,8 @@ int receive_check_args(const char* who, const Scene& s, uint32_t flags, int32_t 
     if (receive_hist_words(s, top, n_bins, 0, 1) > ((size_t)1 << 27)) return bad("receivers x n_bins x bands exceeds 2^27");
     if (receive_hist_words(s, top, n_bins, flags, 1) > ((size_t)1 << 27))
         return bad("receivers x n_bins x bands x 4 channels (HARE_RECEIVE_DIRECTIONAL) exceeds 2^27");
+    if (s.rmap.set && receive_rains(s, top, flags))
+        return bad("HARE_RECEIVE_DIFFUSE_RAIN does not combine with a receiver map (hare_scene_set_receiver_map)");
     return HARE_OK;
 }
 
@@ -119,11 +135,11 @@ static RainWork rain_work(void* d_work, int64_t n)
 int receive_plan(const Scene& s, int32_t top, uint32_t flags, int64_t n, int32_t n_bins, double bin_len, int32_t frac_bits, void* d_state,
                  void* d_hist, void* d_det, void* d_work, bool init_state, int64_t ray_base, ReceivePlan& p)
 {
-    ReceiveArgs& ra = p.args;
-    memset(&ra, 0, sizeof ra);
+    ReceiveMapArgs& ra = p.args;
+    memset((void*)&ra, 0, sizeof ra);
     ra.state = (double*)d_state;
     ra.alpha = has_table(s.alpha, top) ? (const double*)s.alpha[(size_t)top].dev : nullptr;
-    ra.rcv = (const double*)s.d_rcv;
+    ra.rcv = (const double*)(s.rmap.set ? s.rmap.d_rcv : s.d_rcv);
     ra.hist = (unsigned long long*)d_hist;
     ra.det = (unsigned long long*)d_det;
     ra.bin_len = bin_len;
@@ -148,6 +164,22 @@ int receive_plan(const Scene& s, int32_t top, uint32_t flags, int64_t n, int32_t
     ra.cut = ((flags & HARE_RECEIVE_TIME_LIMIT) ? kCutTime : 0) |
              (s.opt.receive_floor_bits > 0 ? (kCutFloor | (s.opt.receive_roulette ? kCutRoulette : 0)) : 0);
     ra.floor = ldexp(1.0, -s.opt.receive_floor_bits);
+    p.map = s.rmap.set;
+    if (p.map) {
+        const Scene::ReceiverMap& m = s.rmap;
+        if (!m.d_rcv || !m.d_start || !m.d_items) {
+            set_error("receive: receiver map not on the device");
+            return HARE_E_STATE;
+        }
+        ra.map_start = (const uint32_t*)m.d_start;
+        ra.map_items = (const uint32_t*)m.d_items;
+        for (int k = 0; k < 3; ++k) {
+            ra.map_n[k] = m.n[k];
+            ra.map_org[k] = m.org[k];
+        }
+        ra.map_h = m.h;
+        ra.map_pad = m.pad;
+    }
     p.directional = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
     p.rain = receive_rains(s, top, flags);
     p.work = p.rain ? rain_work(d_work, n) : RainWork();
@@ -191,7 +223,7 @@ int receive_step(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n
 {
     const DeviceModule& M = *s.module;
     const unsigned grid = (unsigned)((n + 255) / 256);
-    ReceiveArgs ra = p.args;
+    ReceiveMapArgs ra = p.args;                             // the kernels without a map read its ReceiveArgs, which lies in front
     ra.polys = (const PolyRec*)s.d_polys[(size_t)top];
     ra.rays = (RayRec*)d_rays;
     ra.ev = (XEventRec*)d_ev;
@@ -324,6 +356,103 @@ static int set_band_table(Scene& s, const char* who, const char* name, std::vect
     return upload_receivers(s, H);
 }
 
+// what both receiver setters check, and the K x 4 block (cx, cy, cz, r * r) they keep
+static int check_receivers(const char* who, int32_t K, int32_t K_max, const double* centers, const double* radii)
+{
+    if (K < 1 || K > K_max || !centers || !radii) {
+        set_error(std::string(who) + ": need 1 .. " + std::to_string(K_max) + " receivers, centers and radii");
+        return HARE_E_INVALID;
+    }
+    for (int32_t k = 0; k < K; ++k) {
+        if (!std::isfinite(centers[3 * k]) || !std::isfinite(centers[3 * k + 1]) || !std::isfinite(centers[3 * k + 2])) {
+            set_error(std::string(who) + ": receiver " + std::to_string(k) + " has a non-finite center");
+            return HARE_E_INVALID;
+        }
+        if (!(std::isfinite(radii[k]) && radii[k] > 0)) {
+            set_error(std::string(who) + ": receiver " + std::to_string(k) + " needs a finite radius > 0");
+            return HARE_E_INVALID;
+        }
+    }
+    return HARE_OK;
+}
+
+static std::vector<double> receiver_block(int32_t K, const double* centers, const double* radii)
+{
+    std::vector<double> r((size_t)K * 4);
+    for (int32_t k = 0; k < K; ++k) {
+        r[4 * (size_t)k + 0] = centers[3 * k];
+        r[4 * (size_t)k + 1] = centers[3 * k + 1];
+        r[4 * (size_t)k + 2] = centers[3 * k + 2];
+        r[4 * (size_t)k + 3] = radii[k] * radii[k];
+    }
+    return r;
+}
+
+// the receivers are replaced (host copies): up they go when a device is present
+static int push_receivers(hare_scene* s)
+{
+    s->rcv_on_device = false;
+    const HipApi* H = nullptr;
+    if (!device_present(H)) return HARE_OK;          // GPU-less: the host copy goes up with the first receive call
+    DeviceGuard dev_guard(H, s->device);
+    if (int rc = ensure_device(*s, H)) return rc;
+    if (!s->rmap.set) {                              // back to the linear loop: the map's device copies go
+        dev_free(H, s->rmap.d_rcv);
+        dev_free(H, s->rmap.d_start);
+        dev_free(H, s->rmap.d_items);
+    }
+    return upload_receivers(*s, H);
+}
+
+// The grid of a receiver map (include/hare_hip.h, "Receiver maps"): FP64, no contraction, in the header's order
+static void build_receiver_map(Scene::ReceiverMap& m, int32_t K, const double* centers, const double* radii, double cell)
+{
+    double r_max = radii[0], lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) lo[a] = hi[a] = centers[a];
+    for (int32_t k = 1; k < K; ++k) {
+        r_max = radii[k] > r_max ? radii[k] : r_max;
+        for (int a = 0; a < 3; ++a) {
+            const double c = centers[3 * k + a];
+            lo[a] = c < lo[a] ? c : lo[a];
+            hi[a] = c > hi[a] ? c : hi[a];
+        }
+    }
+    double h = cell > 0 ? cell : 2.0 * r_max;
+    int64_t n[3];
+    for (;;) {
+        for (int a = 0; a < 3; ++a) {
+            const double q = (hi[a] - lo[a]) / h;
+            n[a] = (q >= 0 && q < (double)kMaxMapCells) ? (int64_t)floor(q) + 1 : (q != q ? 1 : (int64_t)kMaxMapCells + 1);
+        }
+        if (n[0] <= kMaxMapCells && n[1] <= kMaxMapCells && n[0] * n[1] <= kMaxMapCells && n[0] * n[1] * n[2] <= kMaxMapCells) break;
+        h = h * 2.0;
+    }
+    m.h = h;
+    m.R = r_max + h / 8.0;
+    m.pad = m.R / h;
+    for (int a = 0; a < 3; ++a) {
+        m.org[a] = lo[a];
+        m.n[a] = (int32_t)n[a];
+    }
+    const size_t cells = (size_t)(n[0] * n[1] * n[2]);
+    std::vector<uint32_t> cell_of((size_t)K);
+    m.start.assign(cells + 1, 0);
+    for (int32_t k = 0; k < K; ++k) {
+        int64_t i[3];
+        for (int a = 0; a < 3; ++a) {
+            const double u = (centers[3 * k + a] - lo[a]) / h;
+            i[a] = u >= 0 ? (u < (double)n[a] ? (int64_t)floor(u) : n[a] - 1) : 0;      // clamped as a double; NaN -> 0
+        }
+        cell_of[(size_t)k] = (uint32_t)((i[2] * n[1] + i[1]) * n[0] + i[0]);
+        ++m.start[cell_of[(size_t)k] + 1];
+    }
+    for (size_t c = 0; c < cells; ++c) m.start[c + 1] += m.start[c];
+    std::vector<uint32_t> at(m.start.begin(), m.start.end() - 1);
+    m.items.assign((size_t)K, 0);
+    for (int32_t k = 0; k < K; ++k) m.items[at[cell_of[(size_t)k]]++] = (uint32_t)k;          // ascending k within a cell
+    m.set = true;
+}
+
 }  // namespace hare
 
 using namespace hare;
@@ -350,36 +479,62 @@ int hare_scene_set_receivers(hare_scene* s, int32_t K, const double* centers, co
         set_error("null scene");
         return HARE_E_INVALID;
     }
-    if (K < 1 || K > kMaxReceivers || !centers || !radii) {
-        set_error("hare_scene_set_receivers: need 1 .. 256 receivers, centers and radii");
+    if (int rc = check_receivers("hare_scene_set_receivers", K, kMaxReceivers, centers, radii)) return rc;
+    GUARD_BEGIN
+    std::vector<double> r = receiver_block(K, centers, radii);
+    s->rcv.swap(r);
+    s->rmap.set = false;
+    s->rmap.start.clear();
+    s->rmap.items.clear();
+    return push_receivers(s);
+    GUARD_END
+}
+
+int hare_scene_set_receiver_map(hare_scene* s, int32_t K, const double* centers, const double* radii, double cell)
+{
+    if (!s) {
+        set_error("null scene");
         return HARE_E_INVALID;
     }
-    for (int32_t k = 0; k < K; ++k) {
-        if (!std::isfinite(centers[3 * k]) || !std::isfinite(centers[3 * k + 1]) || !std::isfinite(centers[3 * k + 2])) {
-            set_error("hare_scene_set_receivers: receiver " + std::to_string(k) + " has a non-finite center");
-            return HARE_E_INVALID;
-        }
-        if (!(std::isfinite(radii[k]) && radii[k] > 0)) {
-            set_error("hare_scene_set_receivers: receiver " + std::to_string(k) + " needs a finite radius > 0");
-            return HARE_E_INVALID;
-        }
+    if (int rc = check_receivers("hare_scene_set_receiver_map", K, kMaxMapReceivers, centers, radii)) return rc;
+    if (!(cell >= 0 && std::isfinite(cell))) {
+        set_error("hare_scene_set_receiver_map: cell must be finite and >= 0 (0: 2 r_max)");
+        return HARE_E_INVALID;
     }
     GUARD_BEGIN
-    std::vector<double> r((size_t)K * 4);
-    for (int32_t k = 0; k < K; ++k) {
-        r[4 * (size_t)k + 0] = centers[3 * k];
-        r[4 * (size_t)k + 1] = centers[3 * k + 1];
-        r[4 * (size_t)k + 2] = centers[3 * k + 2];
-        r[4 * (size_t)k + 3] = radii[k] * radii[k];
-    }
+    std::vector<double> r = receiver_block(K, centers, radii);
+    Scene::ReceiverMap m;
+    build_receiver_map(m, K, centers, radii, cell);
+    m.d_rcv = s->rmap.d_rcv;                         // the device copies are replaced by the upload
+    m.d_start = s->rmap.d_start;
+    m.d_items = s->rmap.d_items;
     s->rcv.swap(r);
-    s->rcv_on_device = false;
-    const HipApi* H = nullptr;
-    if (!device_present(H)) return HARE_OK;          // GPU-less: the host copy goes up with the first receive call
-    DeviceGuard dev_guard(H, s->device);
-    if (int rc = ensure_device(*s, H)) return rc;
-    return upload_receivers(*s, H);
+    s->rmap = std::move(m);
+    return push_receivers(s);
     GUARD_END
+}
+
+int hare_scene_get_receiver_map(const hare_scene* s, double* geom, int32_t* dims, uint32_t* cell_start, uint32_t* cell_items)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    if (!s->rmap.set) {
+        set_error("hare_scene_get_receiver_map: no receiver map set (hare_scene_set_receiver_map)");
+        return HARE_E_STATE;
+    }
+    const Scene::ReceiverMap& m = s->rmap;
+    if (geom) {
+        for (int a = 0; a < 3; ++a) geom[a] = m.org[a];
+        geom[3] = m.h;
+        geom[4] = m.R;
+    }
+    if (dims)
+        for (int a = 0; a < 3; ++a) dims[a] = m.n[a];
+    if (cell_start) memcpy(cell_start, m.start.data(), m.start.size() * sizeof(uint32_t));
+    if (cell_items) memcpy(cell_items, m.items.data(), m.items.size() * sizeof(uint32_t));
+    return HARE_OK;
 }
 
 int hare_scene_set_absorption(hare_scene* s, int32_t top_index, int32_t B, const double* alpha)

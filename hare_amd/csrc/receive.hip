@@ -115,19 +115,140 @@ static __device__ __forceinline__ unsigned long long wave_sum4_u64(unsigned long
     return v;
 }
 
+// ---- receiver maps (hare_scene_set_receiver_map; the header's "receivers", "Receiver maps"): the _map kernels run a ray through its
+// CANDIDATES only, the receivers listed in the grid cells its segment visits, with the test, the binning and the adds of the loop above.
+// The receivers (up to 65 536 x 32 B) are not staged: every lane walks its own cells and reads its own candidates with vector loads;
+// the grid's offsets and items and the receivers are L2-resident (2.5 MiB at most, 8 MiB of offsets for the largest grid).  The receiver
+// index is per lane, so nothing is summed over a wave: a detecting lane adds its own B (4 B) words and its own detection count.  A map's
+// detections are spread over many receivers, so those adds rarely meet.
+// The visit rule, operation by operation as the header states it (FP64, no contraction); every double is clamped AS A DOUBLE before it
+// becomes an index (map_cell), so no conversion of a NaN or of a value out of range is left to the compiler.
+static __device__ __forceinline__ int map_cell(double v, int n)      // v = floor(.): the cell index clamped to 0 .. n - 1; NaN -> 0
+{
+    return v >= 0 ? (v < (double)n ? (int)v : n - 1) : 0;
+}
+// the slab test of one axis on [t0, t1], in cell units: the grid's extent 0 .. n grown by P
+static __device__ __forceinline__ void map_clip(double u, double v, int n, double P, double& t0, double& t1, bool& ok)
+{
+    const double lo = -P, hi = (double)n + P;
+    if (v == 0) {
+        ok = ok && u >= lo && u <= hi;
+        return;
+    }
+    const double ta = (lo - u) / v, tb = (hi - u) / v;
+    ok = ok && ta == ta && tb == tb;
+    const double tmin = ta < tb ? ta : tb, tmax = ta < tb ? tb : ta;
+    t0 = tmin > t0 ? tmin : t0;
+    t1 = tmax < t1 ? tmax : t1;
+}
+// the cells of one axis that the points of [ts, te] come within P of
+static __device__ __forceinline__ void map_range(double u, double v, double ts, double te, double P, int n, int& lo, int& hi)
+{
+    const double p0 = u + v * ts, p1 = u + v * te;
+    const double pmin = p0 < p1 ? p0 : p1, pmax = p0 < p1 ? p1 : p0;
+    lo = map_cell(floor(pmin - P), n);
+    hi = map_cell(floor(pmax + P), n);
+}
+
+template <bool DIR>
+static __device__ __forceinline__ void map_receivers(const ReceiveMapArgs& a, int64_t i, const RayRec& r, double t_end, double L)
+{
+    const int B = a.bands;
+    const double h = a.map_h, P = a.map_pad;
+    const int n0 = a.map_n[0], n1 = a.map_n[1], n2 = a.map_n[2];
+    const double u0 = (r.x - a.map_org[0]) / h, u1 = (r.y - a.map_org[1]) / h, u2 = (r.z - a.map_org[2]) / h;
+    const double v0 = r.dx / h, v1 = r.dy / h, v2 = r.dz / h;
+    double t0 = 0, t1 = t_end;
+    bool ok = true;
+    map_clip(u0, v0, n0, P, t0, t1, ok);
+    map_clip(u1, v1, n1, P, t0, t1, ok);
+    map_clip(u2, v2, n2, P, t0, t1, ok);
+    if (!(ok && t0 <= t1 && t1 < __builtin_inf())) return;
+    int m = 0;                                                          // the major axis: a tie goes to the lowest
+    double vm = v0;
+    if (fabs(v1) > fabs(vm)) { m = 1; vm = v1; }
+    if (fabs(v2) > fabs(vm)) { m = 2; vm = v2; }
+    if (vm == 0) return;
+    const double um = m == 0 ? u0 : (m == 1 ? u1 : u2);
+    const int nm = m == 0 ? n0 : (m == 1 ? n1 : n2);
+    const double a0 = um + vm * t0, a1 = um + vm * t1;
+    const double amin = a0 < a1 ? a0 : a1, amax = a0 < a1 ? a1 : a0;
+    const int jlo = map_cell(floor(amin - P), nm), jhi = map_cell(floor(amax + P), nm);
+    const double nb = (double)a.n_bins;
+    for (int j = jlo; j <= jhi; ++j) {                                  // the slabs of cells along the major axis: distinct, so no cell twice
+        const double fj = (double)j;
+        const double tA = ((fj - P) - um) / vm, tB = (((fj + 1.0) + P) - um) / vm;
+        const double tlo = tA < tB ? tA : tB, thi = tA < tB ? tB : tA;
+        const double ts = tlo > t0 ? tlo : t0, te = thi < t1 ? thi : t1;
+        if (!(ts <= te)) continue;
+        int lo0, hi0, lo1, hi1, lo2, hi2;
+        map_range(u0, v0, ts, te, P, n0, lo0, hi0);
+        map_range(u1, v1, ts, te, P, n1, lo1, hi1);
+        map_range(u2, v2, ts, te, P, n2, lo2, hi2);
+        if (m == 0) lo0 = hi0 = j;
+        if (m == 1) lo1 = hi1 = j;
+        if (m == 2) lo2 = hi2 = j;
+        for (int iz = lo2; iz <= hi2; ++iz)
+            for (int iy = lo1; iy <= hi1; ++iy) {
+                // cells lo0 .. hi0 of a row are consecutive, and so are their items: one range of the CSR
+                const size_t row = ((size_t)iz * (size_t)n1 + (size_t)iy) * (size_t)n0;
+                unsigned q = a.map_start[row + (size_t)lo0];
+                const unsigned qe = a.map_start[row + (size_t)hi0 + 1];
+                for (; q < qe; ++q) {
+                    const int k = (int)a.map_items[q];
+                    const double cx = a.rcv[4 * (size_t)k + 0], cy = a.rcv[4 * (size_t)k + 1], cz = a.rcv[4 * (size_t)k + 2],
+                                 r2 = a.rcv[4 * (size_t)k + 3];
+                    const double wx = cx - r.x, wy = cy - r.y, wz = cz - r.z;
+                    const double s = ((wx * r.dx + wy * r.dy) + wz * r.dz) / ((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
+                    const double qx = (r.x + r.dx * s) - cx, qy = (r.y + r.dy * s) - cy, qz = (r.z + r.dz * s) - cz;
+                    if (!(s >= 0 && s < t_end && ((qx * qx + qy * qy) + qz * qz) < r2)) continue;
+                    const double x = (L + s) / a.bin_len;
+                    const bool binned = x >= 0 && x < nb;
+                    atomicAdd(&a.det[2 * (size_t)k + (binned ? 0 : 1)], 1ull);
+                    if (!binned) continue;
+                    const int bin = (int)floor(x);
+                    // a detection is rare beside the cells walked: the ray's energies are read here, not held through the walk, and the
+                    // arrival vector is formed per detection
+                    if constexpr (DIR) {
+                        const double len = sqrt((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
+                        const double ax = -(r.dx / len), ay = -(r.dy / len), az = -(r.dz / len);
+                        unsigned long long* const w = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B * 4;
+                        for (int b = 0; b < B; ++b) {
+                            const double Eb = a.init_state ? 1.0 : a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i];
+                            const double mb = quant_m(Eb * a.scale);
+                            atomicAdd(&w[4 * b + 0], (unsigned long long)rint(mb));
+                            atomicAdd(&w[4 * b + 1], dir_q(mb, ax));
+                            atomicAdd(&w[4 * b + 2], dir_q(mb, ay));
+                            atomicAdd(&w[4 * b + 3], dir_q(mb, az));
+                        }
+                    } else {
+                        unsigned long long* const w = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B;
+                        for (int b = 0; b < B; ++b) {
+                            const double Eb = a.init_state ? 1.0 : a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i];
+                            atomicAdd(&w[b], (unsigned long long)rint(quant_m(Eb * a.scale)));
+                        }
+                    }
+                }
+            }
+    }
+}
+
 // RAIN (hare_receive_scatter_rain, HARE_RECEIVE_DIFFUSE_RAIN): a ray whose reflection in the previous cast was diffuse (ReceiveArgs::rain_flag)
 // skips the receiver step -- hare_rain_step has deposited that segment -- and every reflected ray writes the flag after its choice.
 // DIR (the _dir kernels, HARE_RECEIVE_DIRECTIONAL): four channels per histogram word.  The arrival vector is one per ray and cast; it costs a
 // sqrt and three divisions, so it is formed behind the first ballot that found a binned detection, not for every ray of every cast.  The
 // quantised words are formed inside the band loop (4 x 8 of them held per lane would be 64 VGPRs).  Aggregated, lanes 16 ch + b add the
 // 4 B contiguous words of a bin (at most 256 B) in one atomic instruction.
-template <bool SCATTER, bool RAIN = false, bool DIR = false>
-static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
+// MAP (the _map kernels, a scene with a receiver map): no staging; the receiver step is map_receivers, above.  Everything below the
+// receiver step is the same code.
+template <bool SCATTER, bool RAIN = false, bool DIR = false, bool MAP = false, typename Args = ReceiveArgs>
+static __device__ __forceinline__ void receive_body(const Args& a)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const int B = a.bands;
     __shared__ double rcv[kMaxReceivers * 4];                        // the receivers: uniform LDS reads (broadcast) in the loop below
+                                                                     // (MAP: never referenced, so the _map kernels hold none of it)
     bool live = i < a.n;
     if (live && a.marks_valid && a.excl[i] == -2) live = false;
     // a workgroup whose 256 rays are all retired stages nothing: its rays cost their 4-byte mark and this one barrier (it still writes
@@ -139,8 +260,10 @@ static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
         }
         return;
     }
-    for (int k = threadIdx.x; k < a.n_rcv * 4; k += blockDim.x) rcv[k] = a.rcv[k];
-    __syncthreads();
+    if constexpr (!MAP) {
+        for (int k = threadIdx.x; k < a.n_rcv * 4; k += blockDim.x) rcv[k] = a.rcv[k];
+        __syncthreads();
+    }
     XEventRec e;
     RayRec r;
     double L = 0;
@@ -148,75 +271,118 @@ static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
 #pragma unroll
     for (int b = 0; b < kMaxBands; ++b) E[b] = 0;
     bool rained = false;
+    if constexpr (MAP) {
+        // the walk holds the ray, t_end and L only: the event and the energies are read behind it (nothing the walk adds to overlaps them)
+        if (live) {
+            r = a.rays[i];
+            if (!a.init_state) L = a.state[i];
+            const XEventRec& ei = a.ev[i];
+            map_receivers<DIR>(a, i, r, ei.hit ? ei.t : __builtin_inf(), L);
+        }
+    }
     if (live) {
         e = a.ev[i];
-        r = a.rays[i];
+        if constexpr (!MAP) r = a.rays[i];
         if constexpr (RAIN) rained = a.rain_flag[i] != 0;
         if (a.init_state) {
 #pragma unroll
             for (int b = 0; b < kMaxBands; ++b) E[b] = 1.0;
         } else {
-            L = a.state[i];
+            if constexpr (!MAP) L = a.state[i];
 #pragma unroll
             for (int b = 0; b < kMaxBands; ++b)
                 if (b < B) E[b] = a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i];
         }
     }
     // ---- receivers
-    const bool seen = live && !rained;
-    if (__ballot(seen) != 0ull) {
-        const double t_end = (live && e.hit) ? e.t : __builtin_inf();
-        const double nb = (double)a.n_bins;
-        [[maybe_unused]] double ax = 0, ay = 0, az = 0;
-        [[maybe_unused]] bool have_a = false;                               // wave-uniform
-        for (int k = 0; k < a.n_rcv; ++k) {
-            const double cx = rcv[4 * k + 0], cy = rcv[4 * k + 1], cz = rcv[4 * k + 2], r2 = rcv[4 * k + 3];
-            bool det = false, binned = false;
-            int bin = 0;
-            if (seen) {
-                const double wx = cx - r.x, wy = cy - r.y, wz = cz - r.z;
-                const double s = ((wx * r.dx + wy * r.dy) + wz * r.dz) / ((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
-                const double qx = (r.x + r.dx * s) - cx, qy = (r.y + r.dy * s) - cy, qz = (r.z + r.dz * s) - cz;
-                det = s >= 0 && s < t_end && ((qx * qx + qy * qy) + qz * qz) < r2;
-                if (det) {
-                    const double x = (L + s) / a.bin_len;
-                    binned = x >= 0 && x < nb;
-                    if (binned) bin = (int)floor(x);
-                }
-            }
-            const unsigned long long dm = __ballot(det);
-            if (dm == 0ull) continue;                                       // the common case: nobody passed receiver k
-            const unsigned long long bm = __ballot(binned);
-            if (lane == 0) {
-                if (bm) atomicAdd(&a.det[2 * k], (unsigned long long)__popcll(bm));
-                if (dm & ~bm) atomicAdd(&a.det[2 * k + 1], (unsigned long long)__popcll(dm & ~bm));
-            }
-            if (bm == 0ull) continue;
-            if constexpr (DIR) {
-                if (!have_a) {
-                    have_a = true;
-                    if (seen) {
-                        const double len = sqrt((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
-                        ax = -(r.dx / len);
-                        ay = -(r.dy / len);
-                        az = -(r.dz / len);
+    if constexpr (!MAP) {                                                // the linear step; a map has taken its own, above
+        const bool seen = live && !rained;
+        if (__ballot(seen) != 0ull) {
+            const double t_end = (live && e.hit) ? e.t : __builtin_inf();
+            const double nb = (double)a.n_bins;
+            [[maybe_unused]] double ax = 0, ay = 0, az = 0;
+            [[maybe_unused]] bool have_a = false;                               // wave-uniform
+            for (int k = 0; k < a.n_rcv; ++k) {
+                const double cx = rcv[4 * k + 0], cy = rcv[4 * k + 1], cz = rcv[4 * k + 2], r2 = rcv[4 * k + 3];
+                bool det = false, binned = false;
+                int bin = 0;
+                if (seen) {
+                    const double wx = cx - r.x, wy = cy - r.y, wz = cz - r.z;
+                    const double s = ((wx * r.dx + wy * r.dy) + wz * r.dz) / ((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
+                    const double qx = (r.x + r.dx * s) - cx, qy = (r.y + r.dy * s) - cy, qz = (r.z + r.dz * s) - cz;
+                    det = s >= 0 && s < t_end && ((qx * qx + qy * qy) + qz * qz) < r2;
+                    if (det) {
+                        const double x = (L + s) / a.bin_len;
+                        binned = x >= 0 && x < nb;
+                        if (binned) bin = (int)floor(x);
                     }
                 }
-                unsigned long long* const row = a.hist + (size_t)k * (size_t)a.n_bins * (size_t)B * 4;
-                if (!a.aggregate) {                                          // naive form (A/B): every detecting lane adds its own words
-                    if (binned)
-                        for (int b = 0; b < B; ++b) {
-                            const double m = quant_m(E[b] * a.scale);
-                            unsigned long long* const w = &row[((size_t)bin * B + b) * 4];
-                            atomicAdd(&w[0], (unsigned long long)rint(m));
-                            atomicAdd(&w[1], dir_q(m, ax));
-                            atomicAdd(&w[2], dir_q(m, ay));
-                            atomicAdd(&w[3], dir_q(m, az));
+                const unsigned long long dm = __ballot(det);
+                if (dm == 0ull) continue;                                       // the common case: nobody passed receiver k
+                const unsigned long long bm = __ballot(binned);
+                if (lane == 0) {
+                    if (bm) atomicAdd(&a.det[2 * k], (unsigned long long)__popcll(bm));
+                    if (dm & ~bm) atomicAdd(&a.det[2 * k + 1], (unsigned long long)__popcll(dm & ~bm));
+                }
+                if (bm == 0ull) continue;
+                if constexpr (DIR) {
+                    if (!have_a) {
+                        have_a = true;
+                        if (seen) {
+                            const double len = sqrt((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
+                            ax = -(r.dx / len);
+                            ay = -(r.dy / len);
+                            az = -(r.dz / len);
                         }
+                    }
+                    unsigned long long* const row = a.hist + (size_t)k * (size_t)a.n_bins * (size_t)B * 4;
+                    if (!a.aggregate) {                                          // naive form (A/B): every detecting lane adds its own words
+                        if (binned)
+                            for (int b = 0; b < B; ++b) {
+                                const double m = quant_m(E[b] * a.scale);
+                                unsigned long long* const w = &row[((size_t)bin * B + b) * 4];
+                                atomicAdd(&w[0], (unsigned long long)rint(m));
+                                atomicAdd(&w[1], dir_q(m, ax));
+                                atomicAdd(&w[2], dir_q(m, ay));
+                                atomicAdd(&w[3], dir_q(m, az));
+                            }
+                        continue;
+                    }
+                    unsigned long long todo = bm;
+                    while (todo) {                                               // one round per distinct bin among the wave's detections
+                        const int leader = __ffsll((long long)todo) - 1;
+                        const int lb = __shfl(bin, leader, 64);
+                        const bool mine = binned && bin == lb;
+                        todo &= ~__ballot(mine);
+                        unsigned long long mysum = 0;
+#pragma unroll
+                        for (int b = 0; b < kMaxBands; ++b) {
+                            if (b < B) {
+                                const double m = mine ? quant_m(E[b] * a.scale) : 0.0;     // m = 0 quantises to four zero words
+                                const unsigned long long sb =
+                                    wave_sum4_u64((unsigned long long)rint(m), dir_q(m, ax), dir_q(m, ay), dir_q(m, az), lane);
+                                if ((lane & 15) == b) mysum = sb;
+                            }
+                        }
+                        // lane 16 ch + b holds channel ch of band b: 4 B contiguous 8-byte adds, one instruction
+                        if ((lane & 15) < B) atomicAdd(&row[((size_t)lb * B + (lane & 15)) * 4 + (lane >> 4)], mysum);
+                    }
+                    continue;
+                }
+                unsigned long long q[kMaxBands];
+#pragma unroll
+                for (int b = 0; b < kMaxBands; ++b) {
+                    q[b] = 0;
+                    if (b < B && binned) q[b] = (unsigned long long)rint(quant_m(E[b] * a.scale));
+                }
+                unsigned long long* const row = a.hist + (size_t)k * (size_t)a.n_bins * (size_t)B;
+                if (!a.aggregate) {                                              // naive form (A/B): every detecting lane adds its own bands
+                    if (binned)
+                        for (int b = 0; b < B; ++b) atomicAdd(&row[(size_t)bin * B + b], q[b]);
                     continue;
                 }
                 unsigned long long todo = bm;
-                while (todo) {                                               // one round per distinct bin among the wave's detections
+                while (todo) {                                                   // one round per distinct bin among the wave's detections
                     const int leader = __ffsll((long long)todo) - 1;
                     const int lb = __shfl(bin, leader, 64);
                     const bool mine = binned && bin == lb;
@@ -225,44 +391,12 @@ static __device__ __forceinline__ void receive_body(const ReceiveArgs& a)
 #pragma unroll
                     for (int b = 0; b < kMaxBands; ++b) {
                         if (b < B) {
-                            const double m = mine ? quant_m(E[b] * a.scale) : 0.0;     // m = 0 quantises to four zero words
-                            const unsigned long long sb =
-                                wave_sum4_u64((unsigned long long)rint(m), dir_q(m, ax), dir_q(m, ay), dir_q(m, az), lane);
-                            if ((lane & 15) == b) mysum = sb;
+                            const unsigned long long sb = wave_allsum_u64(mine ? q[b] : 0ull);
+                            if (lane == b) mysum = sb;
                         }
                     }
-                    // lane 16 ch + b holds channel ch of band b: 4 B contiguous 8-byte adds, one instruction
-                    if ((lane & 15) < B) atomicAdd(&row[((size_t)lb * B + (lane & 15)) * 4 + (lane >> 4)], mysum);
+                    if (lane < B) atomicAdd(&row[(size_t)lb * B + lane], mysum);     // B contiguous 8-byte adds: one instruction
                 }
-                continue;
-            }
-            unsigned long long q[kMaxBands];
-#pragma unroll
-            for (int b = 0; b < kMaxBands; ++b) {
-                q[b] = 0;
-                if (b < B && binned) q[b] = (unsigned long long)rint(quant_m(E[b] * a.scale));
-            }
-            unsigned long long* const row = a.hist + (size_t)k * (size_t)a.n_bins * (size_t)B;
-            if (!a.aggregate) {                                              // naive form (A/B): every detecting lane adds its own bands
-                if (binned)
-                    for (int b = 0; b < B; ++b) atomicAdd(&row[(size_t)bin * B + b], q[b]);
-                continue;
-            }
-            unsigned long long todo = bm;
-            while (todo) {                                                   // one round per distinct bin among the wave's detections
-                const int leader = __ffsll((long long)todo) - 1;
-                const int lb = __shfl(bin, leader, 64);
-                const bool mine = binned && bin == lb;
-                todo &= ~__ballot(mine);
-                unsigned long long mysum = 0;
-#pragma unroll
-                for (int b = 0; b < kMaxBands; ++b) {
-                    if (b < B) {
-                        const unsigned long long sb = wave_allsum_u64(mine ? q[b] : 0ull);
-                        if (lane == b) mysum = sb;
-                    }
-                }
-                if (lane < B) atomicAdd(&row[(size_t)lb * B + lane], mysum);     // B contiguous 8-byte adds: one instruction
             }
         }
     }
@@ -393,6 +527,26 @@ extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_dir(Recei
 extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_rain_dir(ReceiveArgs a)
 {
     receive_body<true, true, true>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect_map(ReceiveMapArgs a)
+{
+    receive_body<false, false, false, true, ReceiveMapArgs>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_map(ReceiveMapArgs a)
+{
+    receive_body<true, false, false, true, ReceiveMapArgs>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect_map_dir(ReceiveMapArgs a)
+{
+    receive_body<false, false, true, true, ReceiveMapArgs>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_map_dir(ReceiveMapArgs a)
+{
+    receive_body<true, false, true, true, ReceiveMapArgs>(a);
 }
 
 // ---- diffuse rain (HARE_RECEIVE_DIFFUSE_RAIN; the header's "receivers", "Diffuse rain")

@@ -125,7 +125,8 @@ struct DeviceModule {
     hipFunction_t reflect = nullptr, occlusion = nullptr;
     // receive.hip, [directional]: hare_receive_reflect / _scatter / _scatter_rain (no table / a scattering table / with diffuse rain),
     // hare_rain_step, and HARE_RECEIVE_DIRECTIONAL's _dir forms
-    hipFunction_t receive[3][2] = {}, rain_step[2] = {};
+    // receive[3], receive[4]: hare_receive_reflect_map / hare_receive_scatter_map (a scene with a receiver map)
+    hipFunction_t receive[5][2] = {}, rain_step[2] = {};
     hipFunction_t emit_source = nullptr;                                   // source.hip
     hipFunction_t voxel_occl_tri = nullptr, voxel_occl_quad = nullptr, voxel_occl_tri_g = nullptr, voxel_occl_quad_g = nullptr, octree_occl = nullptr, octree_occl_any = nullptr;
     hipFunction_t events_pack_slim = nullptr;
@@ -295,6 +296,16 @@ struct Scene {
     std::vector<double> rcv;                     // K x 4: cx, cy, cz, r * r (hare_receive_reflect's layout)
     void* d_rcv = nullptr;
     bool rcv_on_device = false;
+    // hare_scene_set_receiver_map: rcv holds up to kMaxMapReceivers receivers and the uniform grid over their centers (each receiver in
+    // the cell of its center, CSR, x fastest).  The device block of a map is sized by its K (d_rcv: the fixed block of the linear loop)
+    struct ReceiverMap {
+        bool set = false;
+        double org[3] = {0, 0, 0}, h = 0, R = 0, pad = 0;      // lower corner, cell edge, R = r_max + h / 8, pad = R / h
+        int32_t n[3] = {0, 0, 0};
+        std::vector<uint32_t> start, items;                     // cells + 1, K
+        void *d_rcv = nullptr, *d_start = nullptr, *d_items = nullptr;
+    };
+    ReceiverMap rmap;
     struct BandTable {
         std::vector<double> host;                // P x bands coefficients, or empty (no table)
         void* dev = nullptr;                     // device copy, or null
@@ -349,12 +360,16 @@ struct RainWork {
 };
 // The receive loop of one call (receive.cpp: receive_plan), host side only
 struct ReceivePlan {
-    ReceiveArgs args;           // receivers, state, histogram and switches; the loop fills in rays, events and marks per cast
+    ReceiveMapArgs args;        // (the grid's fields: p.map only) receivers, state, histogram and switches; the loop fills in rays, events and marks per cast
     RainWork work;              // rain only
     bool rain = false;          // HARE_RECEIVE_DIFFUSE_RAIN on a topology with a scattering table (args.sigma, args.rain_flag set)
     bool directional = false;   // HARE_RECEIVE_DIRECTIONAL: args.hist has four channels per word and the _dir kernels run
+    bool map = false;           // the scene holds a receiver map: the _map kernels run (never with rain)
 };
-inline int receive_form(const ReceivePlan& p) { return !p.args.sigma ? 0 : (p.rain ? 2 : 1); }      // DeviceModule::receive's first index
+inline int receive_form(const ReceivePlan& p)      // DeviceModule::receive's first index
+{
+    return p.map ? (p.args.sigma ? 4 : 3) : (!p.args.sigma ? 0 : (p.rain ? 2 : 1));
+}
 // rcv non-null (hare_receive_*): always a launch per cast, hare_receive_reflect (hare_receive_scatter where rcv->args.sigma is set) behind
 // every cast (the last included) instead of hare_reflect.  rcv->rain: diffuse rain before the receive kernel of every cast but the last,
 // hare_receive_scatter_rain in hare_receive_scatter's place.

@@ -373,6 +373,41 @@ class Spatial_Partition:
         check(lib.hare_scene_set_receivers(self._h, c.shape[0], ptr(c), ptr(r)))
         return self
 
+    def set_receiver_map(self, centers, radii, cell: float = 0.0):
+        """hare_scene_set_receiver_map: up to 65 536 receivers, centers [K, 3], radii [K], found through a uniform grid over the centers
+        (include/hare_hip.h, "Receiver maps").  cell: the grid's cell edge; 0 for the default, twice the largest radius.  Replaces the
+        scene's receivers; set_receivers afterwards returns the scene to the linear loop."""
+        c = np.ascontiguousarray(centers, np.float64).reshape(-1, 3)
+        r = np.ascontiguousarray(radii, np.float64).reshape(-1)
+        if r.shape[0] != c.shape[0]:
+            raise ValueError("one radius per center")
+        check(lib.hare_scene_set_receiver_map(self._h, c.shape[0], ptr(c), ptr(r), float(cell)))
+        return self
+
+    def receiver_map_info(self):
+        """hare_scene_get_receiver_map: the grid of the scene's receiver map as a dict -- origin [3], cell (the edge h), pad (R), dims [3]
+        (cells per axis, x fastest), cell_start [cells + 1] and cell_items [K] (CSR: each receiver in the cell of its center)."""
+        geom, dims = np.zeros(5, np.float64), np.zeros(3, np.int32)
+        check(lib.hare_scene_get_receiver_map(self._h, ptr(geom), ptr(dims), None, None))
+        start = np.zeros(int(dims.prod(dtype=np.int64)) + 1, np.uint32)
+        items = np.zeros(self.get_option("receivers"), np.uint32)
+        check(lib.hare_scene_get_receiver_map(self._h, None, None, ptr(start), ptr(items)))
+        return dict(origin=geom[:3].copy(), cell=float(geom[3]), pad=float(geom[4]), dims=dims, cell_start=start, cell_items=items)
+
+    @staticmethod
+    def receiver_plane(lo, hi, height: float, spacing: float, radius: float):
+        """A map's layout: receivers on the plane z = height, `spacing` apart in x and y, centred in the rectangle lo .. hi (two points;
+        their x and y are read).  Returns (centers [K, 3], radii [K]) for set_receiver_map."""
+        lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+        axes = []
+        for a in range(2):
+            cnt = max(1, int(np.floor((hi[a] - lo[a]) / spacing)) + 1)
+            first = 0.5 * ((lo[a] + hi[a]) - (cnt - 1) * spacing)
+            axes.append(first + spacing * np.arange(cnt))
+        x, y = np.meshgrid(axes[0], axes[1], indexing="xy")
+        c = np.stack([x.ravel(), y.ravel(), np.full(x.size, float(height))], axis=1)
+        return np.ascontiguousarray(c), np.full(c.shape[0], float(radius))
+
     def set_absorption(self, alpha, top_index: int = 0):
         """hare_scene_set_absorption: alpha [P, B] in [0, 1] for Model[top_index] (B = 1 .. 8 bands)."""
         a = np.ascontiguousarray(alpha, np.float64)

@@ -445,7 +445,7 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
 
 /* ---- receivers: energy-time histograms from the bounce loop (harness-defined; the reference has no receivers -- Pachyderm, its
  * caller, intersects every reflected segment with its receivers on the host) ----
- * The scene holds receivers: K spheres (center c_k, radius r_k), with 1 <= K <= 256.  For each topology it may also hold an
+ * The scene holds receivers: K spheres (center c_k, radius r_k), with 1 <= K <= 256 (up to 65 536 as a map: "Receiver maps", below).  For each topology it may also hold an
  * absorption table: alpha[p][b], one value in [0, 1] per polygon p and band b, with 1 <= B <= 8 bands.  A topology with no table
  * acts as B = 1 with every alpha = 0.
  *
@@ -614,6 +614,54 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * run to run, between the one-device and the sharded call, and against a restatement on the host.  (r*r is formed once, when the
  * receivers are set: the same FP64 product.)
  *
+ * Receiver maps (hare_scene_set_receiver_map).  A map is a plane or cloud of up to 65 536 receivers, one histogram each.  The setter lays
+ * a uniform grid over the centers, on the host, FP64, no contraction:
+ *
+ *   r_max = the largest radius;  lo_a / hi_a = the smallest / largest center coordinate on axis a (a = 0, 1, 2)
+ *   h     = cell > 0 ? cell : 2.0 * r_max                       the cell edge; then, until n_0 * n_1 * n_2 <= 2^21:  h = h * 2.0
+ *   n_a   = q >= 0 && q < 2^21 ? floor(q) + 1 : (q is NaN ? 1 : too many)          with q = (hi_a - lo_a) / h
+ *   R     = r_max + h / 8.0;   P = R / h                          the pad, and the pad in cell edges
+ *   cell of receiver k on axis a:  u = (c_a - lo_a) / h;  i_a = u >= 0 ? (u < n_a ? floor(u) : n_a - 1) : 0      (NaN: 0)
+ *
+ * Every receiver is listed in exactly ONE cell, the cell of its center; cell (i_0, i_1, i_2) has the index (i_2 * n_1 + i_1) * n_0 + i_0
+ * and the lists are CSR: cell_start[cells + 1], cell_items[K], ascending k within a cell.  With a map set, the receiver step of a cast
+ * is the one above -- the same test, the same binning, the same adds -- run not for k = 0 .. K-1 but for the ray's CANDIDATES: the
+ * receivers listed in the cells the ray's segment VISITS.  The visit rule, in cell units, for the ray o, d and t_end of the receiver step
+ * (t_end = +inf for a miss).  Every comparison with a NaN is false, and x ? a : b is exactly that:
+ *
+ *   u_a = (o_a - lo_a) / h;  v_a = d_a / h                                                    a = 0, 1, 2
+ *   clip:   t0 = 0; t1 = t_end; ok = true; then for a = 0, 1, 2 with L = -P and H = (double)n_a + P:
+ *             v_a == 0:   ok = ok && u_a >= L && u_a <= H
+ *             otherwise:  ta = (L - u_a) / v_a;  tb = (H - u_a) / v_a;  ok = ok && ta == ta && tb == tb
+ *                         tmin = ta < tb ? ta : tb;  tmax = ta < tb ? tb : ta;  t0 = tmin > t0 ? tmin : t0;  t1 = tmax < t1 ? tmax : t1
+ *           no candidates unless  ok && t0 <= t1 && t1 < +inf
+ *   major:  m = 0; if |v_1| > |v_m| then m = 1; if |v_2| > |v_m| then m = 2          (a tie goes to the lowest axis)
+ *           no candidates if v_m == 0
+ *   slabs:  a0 = u_m + v_m * t0;  a1 = u_m + v_m * t1;  amin = a0 < a1 ? a0 : a1;  amax = a0 < a1 ? a1 : a0
+ *           jlo = idx(floor(amin - P), n_m);  jhi = idx(floor(amax + P), n_m)
+ *           idx(x, n) = x >= 0 ? (x < n ? (int)x : n - 1) : 0          the clamp is made on the double; a NaN gives 0
+ *   for every slab j = jlo .. jhi:
+ *           tA = (((double)j - P) - u_m) / v_m;  tB = ((((double)j + 1.0) + P) - u_m) / v_m
+ *           ts = max(t0, the smaller of tA, tB);  te = min(t1, the larger)      (selected as tmin / tmax above); skip j unless ts <= te
+ *           on the axis m the cell range is [j, j]; on each other axis a:
+ *             p0 = u_a + v_a * ts;  p1 = u_a + v_a * te;  pmin = p0 < p1 ? p0 : p1;  pmax = p0 < p1 ? p1 : p0
+ *             range [idx(floor(pmin - P), n_a), idx(floor(pmax + P), n_a)]
+ *           visit every cell of the three ranges
+ *
+ * The slabs are distinct, so no cell is visited twice and every receiver is tested at most once per ray and cast.  The histogram is a
+ * function of the inputs for every input, NaN, infinite, denormal and enormous rays included.
+ * The guarantee.  For a ray and a grid in this DOMAIN -- o, d, t_end (of a hit) and every center finite; |o_a - lo_a|, |c_a - lo_a| and, for
+ * a hit, |(o_a + d_a * t_end) - lo_a| at most 2^20 * h on every axis, and |o_a|, |c_a| at most 2^20 * h too (the grid is not placed far
+ * from the origin in units of its cell); h and the largest |d_a| between 2^-500 and 2^500 -- every receiver the linear definition above
+ * detects is a candidate.  Inside the domain a map of K <= 256 receivers therefore gives the histogram, detections, state, rays and events
+ * of hare_scene_set_receivers with the same receivers, byte for byte (integer sums do not depend on the order of the adds).  Outside the
+ * domain the map's own definition, above, holds: a receiver that the linear loop would detect may then not be a candidate.  (DESIGN.md
+ * 7b, "Receiver maps", argues the guarantee: the pad exceeds r_max by h / 8, a thousand times the rounding of every step above.)
+ * Diffuse rain does not combine with a map (it costs K occlusion launches per cast): a receive call with HARE_RECEIVE_DIFFUSE_RAIN on a
+ * scene that holds a map and, for that topology, a scattering table is HARE_E_INVALID, refused before anything runs.  Everything else --
+ * HARE_RECEIVE_DIRECTIONAL, HARE_RECEIVE_TIME_LIMIT, the floor and roulette, scattering, every receive call -- works as without a map;
+ * the histogram cap (K x n_bins x B, x 4 with channels, <= 2^27 words) stays.  The sharded calls refuse scenes whose maps differ.
+ *
  * Setters: single-caller, like the build calls.  They validate, keep a host copy, and upload it when a device is present (as a build
  * pushes its partition; on a GPU-less host the copy goes up with the first receive call).  No receive call allocates for them.
  *   hare_scene_set_receivers    replaces the receivers: centers K x 3, radii K.  HARE_E_INVALID for K outside 1..256, a non-finite
@@ -622,10 +670,23 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  *                               any alpha outside [0, 1] or NaN, or a B other than that of the topology's scattering table
  *   hare_scene_set_scattering   sigma: P x B of Model[top_index], checked as alpha is (and against the absorption table's B); B = 0 with
  *                               sigma NULL removes the table
+ *   hare_scene_set_receiver_map replaces the receivers by a map: 1 <= K <= 65 536, centers and radii as above; cell: the grid's cell edge,
+ *                               0 for the default 2 r_max (either is doubled until the grid has at most 2^21 cells).  HARE_E_INVALID for
+ *                               K outside the range, a non-finite center, a radius that is not finite and > 0, and a cell that is NaN,
+ *                               negative or infinite; a refused call changes nothing.  hare_scene_set_receivers afterwards replaces the
+ *                               map and returns the scene to the linear loop (its own limit stays K <= 256)
+ *   hare_scene_get_receiver_map reads a map back (HARE_E_STATE when none is set); every output is nullable.  geom: 5 doubles, lo_0, lo_1,
+ *                               lo_2, h and R; dims: n_0, n_1, n_2; cell_start: cells + 1 offsets; cell_items: K receiver indices
+ * hare_scene_get_option also reads "receiver_map" (1 while a map is set, else 0), "receiver_map_cells" (the grid's cell count; 0 without
+ * a map) and "receiver_map_cell" (the cell edge h as the 64 bits of the double, the getter's values being integers; 0 without a map).
  * hare_scene_get_option reads back "receivers" (K; 0 before the first set), "bands" (B of topology 0) and "bands:<top>" (B of topology
  * <top>): the sizes of a receive call's histogram (K x n_bins x B) and state ((1 + B) x n) for that topology.  The library cannot check the
  * size of a caller's host buffer: the bindings size theirs from these. */
 HARE_API int hare_scene_set_receivers(hare_scene *s, int32_t K, const double *centers, const double *radii);
+HARE_API int hare_scene_set_receiver_map(hare_scene *s, int32_t K, const double *centers /* K x 3 */, const double *radii /* K */,
+                                         double cell /* 0: default */);
+HARE_API int hare_scene_get_receiver_map(const hare_scene *s, double *geom /* 5 */, int32_t *dims /* 3 */, uint32_t *cell_start,
+                                         uint32_t *cell_items);
 HARE_API int hare_scene_set_absorption(hare_scene *s, int32_t top_index, int32_t B, const double *alpha);
 HARE_API int hare_scene_set_scattering(hare_scene *s, int32_t top_index, int32_t B, const double *sigma);
 HARE_API int hare_scene_set_source(hare_scene *s, const double pos[3], int32_t B, const double *power /* B, nullable */,

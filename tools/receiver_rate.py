@@ -20,9 +20,13 @@ With --source (K = 8, B = 8 only; nothing else of the above runs), the host wall
 given the same rays (the source's own, downloaded once), without and with state_in: the three calls interleaved, the median of --reps
 runs (default there: 9) after a warm-up, and the spread (min, max) of each; and hare_emit_source alone between HIP events, beside the
 120 B per ray it writes at B = 8.  Run it under rocprofv3 --kernel-trace --stats for the kernel's own time.
+With --map K[,K..] (B = 8, bins of 0.2 m: 1 000, or as many as the histogram cap leaves the largest K; nothing else of the above runs), the
+receive loop with a receiver map (hare_scene_set_receiver_map; the _map kernels): the plain bounce loop, the linear loop at K = 256, the
+map over the same 256 receivers, a plane of at most K receivers at 1.2 m for every K given, and a cloud of 4 096 in the room, interleaved,
+the median of --reps runs; `over` is the time over the plain loop.  Run it under rocprofv3 --kernel-trace --stats for the kernels' times.
 Prints ONE JSON line.  usage: python tools/receiver_rate.py [hall|cathedral] [--rays N] [--bounces B] [--reps R] [--host] [--quick]
                                                           [--scatter SIGMA] [--rain] [--directional] [--time-limit] [--floor-bits N [--roulette]]
-                                                          [--source]"""
+                                                          [--source] [--map K[,K..]]"""
 import argparse
 import json
 import os
@@ -50,6 +54,7 @@ ap.add_argument("--time-limit", action="store_true", help="the loop again with H
 ap.add_argument("--floor-bits", type=int, default=0, metavar="N", help="the loop again with the energy floor 2^-N (scene option receive_floor_bits)")
 ap.add_argument("--roulette", action="store_true", help="with --floor-bits: Russian roulette under the floor (scene option receive_roulette)")
 ap.add_argument("--source", action="store_true", help="K = 8, B = 8: hare_receive_source against hare_receive_batch from host rays, wall time")
+ap.add_argument("--map", default=None, metavar="K[,K..]", help="B = 8: receiver maps (planes of about K receivers, a cloud of 4096) against the linear loop at K = 256")
 a = ap.parse_args()
 if a.reps is None:
     a.reps = 9 if a.source else 10
@@ -123,6 +128,74 @@ if a.source:
     sys.exit(0)
 
 
+def bounce():
+    g.bounce_device(n, d_rays.data_ptr(), nb, d_work.data_ptr(), d_events_last=d_last.data_ptr(), stream=st)
+
+
+def map_run():
+    """The receive loop with a map against the plain bounce loop and the linear loop at K = 256, every loop on a scene of its own."""
+    B, bin_len = 8, 0.2
+    size = np.asarray(mesh.size)
+    alpha = np.random.default_rng(B).uniform(0.02, 0.3, (T.Polygon_Count, B))
+    c256, r256 = receivers(256)
+    r256 = np.minimum(r256, 0.3)                                          # map-sized spheres (the linear rows above use up to 1 m)
+    layouts = {"linear_256": (c256, r256, False), "map_256": (c256, r256, True)}
+    for K in [int(x) for x in a.map.split(",")]:
+        spacing = float(np.sqrt(size[0] * size[1] / K))
+        while (int(size[0] // spacing) + 1) * (int(size[1] // spacing) + 1) > K:      # the lattice's border rows: at most K receivers
+            spacing *= 1.002
+        c, r = H.Voxel_Grid.receiver_plane([0.0, 0.0], size[:2], 1.2, spacing, min(0.4 * spacing, 0.3))
+        assert c.shape[0] <= K
+        layouts["plane_%d" % K] = (c, r, True)
+    rng = np.random.default_rng(4096)
+    layouts["cloud_4096"] = (rng.uniform(0.05, 0.95, (4096, 3)) * size, np.full(4096, 0.3), True)
+    n_bins = min(1000, (1 << 27) // (max(v[0].shape[0] for v in layouts.values()) * B))      # the histogram cap, from the K laid out
+    init = torch.cat([torch.zeros((1, n), dtype=torch.float64, device="cuda"), torch.ones((B, n), dtype=torch.float64, device="cuda")])
+    d_state = torch.empty_like(init)
+    runs = {"bounce": bounce}
+    rows = {"bounce": {}}
+    keep = []
+    for name, (c, r, as_map) in layouts.items():
+        p = H.Voxel_Grid([T], D)
+        (p.set_receiver_map if as_map else p.set_receivers)(c, r)
+        p.set_absorption(alpha)
+        K = c.shape[0]
+        d_hist = torch.zeros(K * n_bins * B, dtype=torch.int64, device="cuda")
+        d_det = torch.zeros(2 * K, dtype=torch.int64, device="cuda")
+        keep.append((p, d_hist, d_det))
+        runs[name] = (lambda p=p, d_hist=d_hist, d_det=d_det: p.receive_device(n, d_rays.data_ptr(), nb, n_bins, bin_len, FRAC, d_state.data_ptr(),
+                                                                               d_work.data_ptr(), d_last.data_ptr(), d_hist.data_ptr(),
+                                                                               d_det.data_ptr(), stream=st))
+        rows[name] = {"K": K, "cells": p.get_option("receiver_map_cells")}
+    ms = {k: [] for k in runs}
+    for rep in range(a.reps + 1):                                         # interleaved; the first round warms up
+        for name, fn in runs.items():
+            d_rays.copy_(d_src); d_state.copy_(init)
+            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record(); torch.cuda.synchronize()
+            if rep:
+                ms[name].append(e0.elapsed_time(e1))
+    base = float(np.median(ms["bounce"]))
+    for (name, row), kept in zip(list(rows.items())[1:], keep):
+        det = kept[2].cpu().numpy().reshape(-1, 2)
+        row["detections_per_call"] = int(det.sum()) // (a.reps + 1)
+        row["receivers_hit"] = int((det.sum(axis=1) > 0).sum())
+    for name, row in rows.items():
+        row["ms"] = round(float(np.median(ms[name])), 3)
+        row["min_max_ms"] = [round(min(ms[name]), 3), round(max(ms[name]), 3)]
+        row["over"] = round(row["ms"] / base, 3)
+    same = keep[0][1].cpu().numpy().tobytes() == keep[1][1].cpu().numpy().tobytes()
+    print(json.dumps({"scene": a.scene, "domain": D, "rays": n, "bounces": nb, "B": B, "n_bins": n_bins, "bin_len": bin_len, "reps": a.reps,
+                      "map_256_same_bytes_as_linear_256": bool(same), "rows": rows}))
+
+
+if a.map:
+    map_run()
+    sys.exit(0)
+
+
 def timed(fn, reps):
     fn(); torch.cuda.synchronize()
     ms = []
@@ -134,10 +207,6 @@ def timed(fn, reps):
         e1.record(); torch.cuda.synchronize()
         ms.append(e0.elapsed_time(e1))
     return float(np.median(ms))
-
-
-def bounce():
-    g.bounce_device(n, d_rays.data_ptr(), nb, d_work.data_ptr(), d_events_last=d_last.data_ptr(), stream=st)
 
 
 ms_bounce = timed(bounce, a.reps)
