@@ -1,12 +1,18 @@
 """Inputs for the receive loop's device tests (include/hare_hip.h, "receivers"): case records built from numpy and the oracle alone, no
-GPU.  Two sets.  edge_cases(): fixed, hand-built states and parameters at the numeric edges of the definition -- "0 unless > 0",
+GPU.  Case is the one record of every set -- the two below, the termination rules' (tests/receive_cut_ref.py) and the receiver maps'
+(tests/receive_map_ref.py) -- and reference(case) the one way from a case to what the library must return.  Two sets here.  edge_cases(): fixed, hand-built states and parameters at the numeric edges of the definition -- "0 unless > 0",
 min(., 2^63), rint's ties, the NaN branch and the +-2^62 clamp of the directional words, sums that wrap, x exactly on a bin edge and
 exactly at n_bins, detections that are not binned -- at every band count, at K up to 256, at batch sizes around a wave, a workgroup and
 the live-block list's threshold, with poly_origin1 / poly_origin2 on the first cast.  sweep_case(seed): one case drawn from a seed over the
 whole parameter space (tools/fuzz_receive.py runs them by the thousand).  reference(case) runs tests.receive_ref.receive_loop on a case and
 returns what the library must return, byte for byte, with the tallies that say which edge classes the case went through
-(tests/test_receive_cases.py asserts that the sets hold what they claim to hold)."""
+(tests/test_receive_cases.py asserts that the sets hold what they claim to hold).  digest(result) is the SHA-256 that
+tests/golden/receive_reference_digests.json pins for every fixed case and sweep seed (tests/test_receive_reference_pinned.py)."""
 import dataclasses
+import functools
+import hashlib
+import json
+import os
 
 import numpy as np
 
@@ -49,6 +55,12 @@ class Case:
     excl2: np.ndarray = None
     shards: int = 1                      # 2: Receive_batch_sharded over two partitions
     device: bool = False                 # also through receive_device with caller-owned buffers
+    time_limit: bool = False             # HARE_RECEIVE_TIME_LIMIT
+    floor_bits: int = 0                  # scene option "receive_floor_bits"
+    roulette: bool = False               # scene option "receive_roulette"
+    map_cell: float = None               # None: the linear receiver loop; >= 0: a receiver map with this `cell` (0: the default)
+    map_shape: str = None                # tests.receive_map_ref.map_layout's shape (for describe() only)
+    two_scenes: bool = False             # also through Receive_batch_sharded over two scenes
 
     @property
     def n(self):
@@ -70,10 +82,17 @@ class Case:
         return self.K * self.n_bins * self.B * (4 if self.directional else 1)
 
     def describe(self):
+        rules = f" time_limit={int(self.time_limit)} floor_bits={self.floor_bits} roulette={int(self.roulette)}"
         return (f"{self.name}: {' '.join(str(x) for x in self.scene)} {' '.join(str(x) for x in self.partition)} n={self.n} bounces={self.bounces} "
                 f"K={self.K} B={self.B} {self.mode}{' directional' if self.directional else ''} aggregate={self.aggregate} pack={self.pack} "
                 f"frac_bits={self.frac_bits} n_bins={self.n_bins} bin_len={self.bin_len!r} state_in={self.state_in is not None} "
-                f"seed={self.seed} excl={self.excl1 is not None} shards={self.shards}")
+                f"seed={self.seed} excl={self.excl1 is not None} shards={self.shards}"
+                f"{rules if self.time_limit or self.floor_bits or self.roulette else ''}"
+                f"{'' if self.map_cell is None else f' map={self.map_shape} cell={self.map_cell!r}'}")
+
+    def without(self, **fields):
+        """The case with some fields replaced (the rules switched off, say); it keeps its name."""
+        return dataclasses.replace(self, **fields)
 
 
 def partition_room():
@@ -118,17 +137,68 @@ def oracle_of(case):
     return _ORACLES[key]
 
 
-def reference(case, counts=False, nthreads=16):
+_REFERENCES = {}
+REFERENCES_KEPT = 160                    # the fixed sets and their rules-off variants together are about a hundred
+
+
+def reference(case, counts=False, nthreads=16, keep=False):
     """tests.receive_ref.receive_loop on the case: dict with hist, det, state and rays as that function returns them, events (the last
-    cast's), stats (the rain's eligible / occluded queries), tallies (receive_ref.TALLIES) and, on request, counts [K, n_bins]."""
+    cast's), stats (the rain's eligible / occluded queries), tallies (receive_ref.TALLIES), counts [K, n_bins] (on request, else None),
+    per_cast (live rays, the rules' retirements and the roulette's survivors per cast) and share ((candidate pairs, pairs) per receiver
+    step of a map; empty without one).  keep: the result is kept, and served from then on, under the case's name and what separates
+    two cases of one name (`without` variants) -- for the fixed sets, whose tests share it and leave it unchanged; the oldest of more
+    than REFERENCES_KEPT goes."""
+    key = (case.name, case.time_limit, case.floor_bits, case.roulette, case.map_cell, counts)
+    if key in _REFERENCES:
+        return _REFERENCES[key]
     To, o = oracle_of(case)
-    stats, tallies, last = {}, {}, []
+    stats, tallies, last, per_cast, share = {}, {}, [], {}, []
     cnt = np.zeros((case.K, case.n_bins), np.int64) if counts else None
+    visit = None
+    if case.map_cell is not None:
+        from tests.receive_map_ref import build_grid, candidates          # that module builds its cases from this one's
+        visit = functools.partial(candidates, build_grid(case.centers, case.radii, case.map_cell))
     hist, det, state, rays = receive_loop(po, To, o, case.rays, case.bounces, case.centers, case.radii, case.n_bins, case.bin_len, case.frac_bits,
                                           alpha=case.alpha, sigma=case.sigma if case.mode != "specular" else None, seed=case.seed,
                                           state_in=case.state_in, rain=case.mode == "rain", directional=case.directional, stats=stats,
-                                          counts=cnt, nthreads=nthreads, tallies=tallies, excl1=case.excl1, excl2=case.excl2, last_events=last)
-    return dict(hist=hist, det=det, state=state, rays=rays, events=last[0], stats=stats, tallies=tallies, counts=cnt)
+                                          counts=cnt, nthreads=nthreads, tallies=tallies, excl1=case.excl1, excl2=case.excl2, last_events=last,
+                                          time_limit=case.time_limit, floor_bits=case.floor_bits, roulette=case.roulette, visit=visit,
+                                          per_cast=per_cast, share=share)
+    out = dict(hist=hist, det=det, state=state, rays=rays, events=last[0], stats=stats, tallies=tallies, counts=cnt, per_cast=per_cast,
+               share=share)
+    if keep:
+        if len(_REFERENCES) >= REFERENCES_KEPT:
+            del _REFERENCES[next(iter(_REFERENCES))]
+        _REFERENCES[key] = out
+    return out
+
+
+def digest(out, per_cast=False):
+    """SHA-256 (hex) over a reference result: hist, det, state, rays, every field of the last events and, on request, per_cast's four
+    arrays; of each its name, dtype, shape and bytes, every NaN first replaced by one bit pattern (its sign and payload are the FPU's,
+    DESIGN.md 1)."""
+    h = hashlib.sha256()
+    arrays = [(k, out[k]) for k in ("hist", "det", "state", "rays")] + [("events." + f, out["events"][f]) for f in out["events"].dtype.names]
+    if per_cast:
+        arrays += [("per_cast." + k, out["per_cast"][k]) for k in ("live", "time", "floor", "boosted")]
+    for name, a in arrays:
+        a = np.ascontiguousarray(a)
+        if a.dtype.kind == "f":
+            assert a.dtype == np.float64, (name, a.dtype)
+            a = a.copy()
+            a.view(np.uint64)[np.isnan(a)] = np.uint64(0x7FF8000000000000)
+        h.update(f"{name} {a.dtype.str} {a.shape}\n".encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+@functools.lru_cache(maxsize=None)
+def pinned_digests():
+    """tests/golden/receive_reference_digests.json: digest() of every fixed case ("edge/", "cut/", "map/", "identity/" + name), of the
+    sweeps' seeds ("sweep/" 0 .. 199, "sweep-cut/" 0 .. 39) and of four rules' cases with the rules off ("rules-off/"), as the three
+    loops that receive_loop replaced returned them; per_cast is in the digest of "cut/" and "sweep-cut/"."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "receive_reference_digests.json")) as f:
+        return json.load(f)
 
 
 def wave_counts(case, w):

@@ -1,20 +1,16 @@
 """numpy restatement of receiver maps (include/hare_hip.h, "receivers", "Receiver maps"), operation for operation in FP64: the grid the
-setter builds (build_grid: cells, CSR), the visit rule as a candidate mask per ray and cast (candidates), and the receive loop with the
-receiver step run for the candidates only (map_loop: tests.receive_cut_ref.cut_loop without the rain, which a map refuses).  The test,
-the binning and the adds are tests.receive_ref.receiver_step's, called per receiver on the rays that hold it as a candidate.
+setter builds (build_grid: cells, CSR) and the visit rule as a candidate mask per ray and cast (candidates).  The loop is
+tests.receive_ref.receive_loop with visit=functools.partial(candidates, grid): its receiver step then runs, per receiver, on the rays
+that hold the receiver as a candidate (a map refuses the rain).
 
 Below it: the cases that the CPU tests (tests/test_receive_map_api.py) and the device tests (tests/test_gpu_receive_map.py) share --
-MapCase, a tests.receive_cases.Case whose receivers are a map -- and reference(), which runs map_loop on one and keeps the result."""
+plain tests.receive_cases.Case records with map_cell set, run by tests.receive_cases.reference like every other case."""
 import dataclasses
 
 import numpy as np
 
 import hare_amd.scenes as scenes
-from oracle import pyoracle as po
-from tests.receive_cases import TINY, Case, edge_state, mesh_of, oracle_of
-from tests.receive_cut_ref import decide
-from tests.receive_ref import receiver_step
-from tests.scatter_ref import choose, normals_of, ray_base, scatter_rays, uniform, weights
+from tests.receive_cases import TINY, Case, edge_state, mesh_of
 
 MAX_CELLS = 1 << 21
 MAX_K = 65536
@@ -133,90 +129,6 @@ def candidates(g, o, d, t_end):
     return cand
 
 
-def map_receiver_step(g, o, d, t_end, L, E, centers, radii, n_bins, bin_len, frac_bits, hist, det, share=None):
-    """tests.receive_ref.receiver_step for the candidates only: per receiver, on the rays whose visited cells list it.
-    share (list, optional) receives (candidate pairs, rays x receivers) of the call."""
-    cand = candidates(g, o, d, t_end)
-    if share is not None:
-        share.append((int(cand.sum()), cand.size))
-    centers = np.asarray(centers, F).reshape(-1, 3)
-    radii = np.asarray(radii, F).reshape(-1)
-    for k in np.nonzero(cand.any(axis=0))[0]:
-        sel = cand[:, k]
-        receiver_step(o[sel], d[sel], t_end[sel], L[sel], E[:, sel], centers[k:k + 1], radii[k:k + 1], n_bins, bin_len, frac_bits,
-                      hist[k:k + 1], det[k:k + 1])
-    return cand
-
-
-def map_loop(po, topo, part, rays, bounces, centers, radii, cell, n_bins, bin_len, frac_bits, alpha=None, sigma=None, seed=0, state_in=None,
-             g0=0, directional=False, time_limit=False, floor_bits=0, roulette=False, nthreads=16, excl1=None, excl2=None, last_events=None,
-             share=None):
-    """The receive loop of a scene with a receiver map, cast by cast (tests.receive_cut_ref.cut_loop without the rain).
-    Returns (hist, det, state [1 + B, n], final rays [n, 6])."""
-    rays = np.ascontiguousarray(rays, F).reshape(-1, 6)
-    n = rays.shape[0]
-    B = 1
-    for t in (alpha, sigma):
-        if t is not None:
-            B = np.asarray(t).shape[1]
-    grid = build_grid(centers, radii, cell)
-    K = np.asarray(centers).reshape(-1, 3).shape[0]
-    hist = np.zeros((K, n_bins, B, 4) if directional else (K, n_bins, B), np.uint64)
-    det = np.zeros((K, 2), np.uint64)
-    if state_in is None:
-        L, E = np.zeros(n), np.ones((B, n))
-    else:
-        st = np.array(state_in, F).reshape(1 + B, n)
-        L, E = st[0].copy(), st[1:].copy()
-    normals = normals_of(topo)
-    base = ray_base(seed, np.arange(g0, g0 + n, dtype=np.uint64))
-    cur = rays.copy()
-    e1 = np.full(n, -1, np.int32) if excl1 is None else np.asarray(excl1, np.int32).copy()
-    e2 = None if excl2 is None else np.asarray(excl2, np.int32).copy()
-    live = np.ones(n, bool)
-    for c in range(bounces):
-        ev = np.zeros(n, po.XEVENT_DTYPE)
-        ev["poly_id"] = -1
-        if live.any():
-            ev[live] = part.shoot(cur[live], excl1=e1[live], excl2=None if e2 is None else e2[live], nthreads=nthreads)[0]
-        hit = ev["hit"] == 1
-        t_end = np.where(hit, ev["t"], np.inf)
-        if live.any():
-            map_receiver_step(grid, cur[live, :3], cur[live, 3:], t_end[live], L[live], E[:, live], centers, radii, n_bins, bin_len,
-                              frac_bits, hist, det, share)
-        upd = live & hit
-        if alpha is not None:
-            a = np.asarray(alpha, F)[ev["poly_id"][upd]].T
-            with np.errstate(invalid="ignore"):
-                E[:, upd] = E[:, upd] * (1.0 - a)
-        L[upd] = L[upd] + ev["t"][upd]
-        goes_on = upd
-        if c + 1 < bounces:
-            nxt = po.reflect_batch(topo, cur, ev)
-            idx = np.nonzero(upd)[0]
-            if sigma is not None and idx.size:
-                srow = np.asarray(sigma, F)[ev["poly_id"][idx]]
-                p, diff = choose(srow, uniform(base[idx], c, 0))
-                with np.errstate(invalid="ignore", over="ignore"):
-                    E[:, idx] = E[:, idx] * weights(srow, p, diff).T
-                di = idx[diff]
-                if di.size:
-                    nxt[di] = scatter_rays(cur[di], ev[di], normals, base[di], c)
-            if (time_limit or floor_bits) and idx.size:
-                ct, cf, _, E[:, idx] = decide(L[idx], E[:, idx], base[idx], c, n_bins, bin_len, time_limit, floor_bits, roulette)
-                gone = idx[ct | cf]
-                nxt[gone] = cur[gone]
-                goes_on = upd.copy()
-                goes_on[gone] = False
-            cur = nxt
-        e1 = np.where(goes_on, ev["poly_id"], -2).astype(np.int32)
-        e2 = None
-        live = goes_on
-        if last_events is not None and c + 1 == bounces:
-            last_events.append(ev)
-    return hist, det, np.concatenate([L[None], E], axis=0), cur
-
-
 # ---- map layouts
 def map_layout(shape, K, size, rng):
     """(centers [K, 3], radii [K], cell) of one of the map shapes.  plane: a square lattice at z = 1.2 that reaches past the model's
@@ -249,24 +161,6 @@ def map_layout(shape, K, size, rng):
 
 
 # ---- cases
-@dataclasses.dataclass
-class MapCase:
-    case: Case
-    shape: str
-    cell: float = 0.0
-    time_limit: bool = False
-    floor_bits: int = 0
-    roulette: bool = False
-    call: str = "batch"             # "batch" | "device" (also receive_device) | "sharded" (also two scenes) | "source" (hare_receive_source)
-
-    @property
-    def name(self):
-        return self.case.name
-
-    def describe(self):
-        return f"{self.case.describe()} map={self.shape} cell={self.cell!r} rules={int(self.time_limit)}/{self.floor_bits}/{int(self.roulette)}"
-
-
 PARTITIONS = {"voxel": ("voxel", 8), "octree": ("octree", 4, 8), "kdtree": ("kdtree", 8, 6)}
 SOUP = ("soup", 120, 40, 3)
 N_BINS, BIN_LEN = 48, 0.25          # 12 m: the second and third casts of a 10 m room run past the end (detections that are not binned)
@@ -274,6 +168,7 @@ N_BINS, BIN_LEN = 48, 0.25          # 12 m: the second and third casts of a 10 m
 
 def map_case(name, shape, K, n, B=1, bounces=3, mode="specular", directional=False, partition="voxel", scene=("shoebox",), special=False,
              tiny=False, call="batch", n_bins=N_BINS, rules=None, state=None):
+    """call: "batch" (Receive_batch alone), "device" (also receive_device) or "sharded" (also the sharded call over two scenes)."""
     rng = np.random.default_rng(90000 + 7 * K + n)
     verts, nverts, size = mesh_of(scene)
     P = verts.shape[0]
@@ -290,9 +185,9 @@ def map_case(name, shape, K, n, B=1, bounces=3, mode="specular", directional=Fal
         state_in = edge_state(n, B, n_bins, BIN_LEN, rng, spread=False)
     elif state or (state is None and bounces == 1):
         state_in = np.concatenate([rng.uniform(-0.5 * BIN_LEN, 1.3 * n_bins * BIN_LEN, (1, n)), rng.uniform(0.0, 2.0, (B, n))])
-    case = Case(name, scene, PARTITIONS[partition], np.ascontiguousarray(rays), bounces, centers, radii, n_bins, BIN_LEN, 30, mode, directional, 1, 1,
-                alpha, sigma, state_in, 1234 + K, None, None, 1, call == "device")
-    return MapCase(case, shape, cell, call=call, **(rules or {}))
+    return Case(name, scene, PARTITIONS[partition], np.ascontiguousarray(rays), bounces, centers, radii, n_bins, BIN_LEN, 30, mode, directional, 1, 1,
+                alpha, sigma, state_in, 1234 + K, None, None, 1, call == "device", map_cell=cell, map_shape=shape, two_scenes=call == "sharded",
+                **(rules or {}))
 
 
 def map_cases():
@@ -323,21 +218,9 @@ def map_cases():
     return c
 
 
-_REFERENCES = {}
-
-
-def reference(mc, nthreads=16):
-    """map_loop on the case: dict of hist, det, state, rays, events (the last cast's) and share (candidate pairs, pairs) per cast.  Kept
-    by the case's name (the tests share it and leave it unchanged)."""
-    if mc.name in _REFERENCES:
-        return _REFERENCES[mc.name]
-    case = mc.case
-    To, o = oracle_of(case)
-    last, share = [], []
-    hist, det, state, rays = map_loop(po, To, o, case.rays, case.bounces, case.centers, case.radii, mc.cell, case.n_bins, case.bin_len,
-                                      case.frac_bits, alpha=case.alpha, sigma=case.sigma, seed=case.seed, state_in=case.state_in,
-                                      directional=case.directional, time_limit=mc.time_limit, floor_bits=mc.floor_bits, roulette=mc.roulette,
-                                      nthreads=nthreads, last_events=last, share=share)
-    out = dict(hist=hist, det=det, state=state, rays=rays, events=last[0], share=share)
-    _REFERENCES[mc.name] = out
-    return out
+def identity_cases():
+    """K <= 256 receivers that both setters take: the map and the linear loop must give the same bytes."""
+    return [map_case("identity-omni", "plane", 256, 4097, B=3, bounces=4),
+            map_case("identity-dir", "cloud", 200, 4097, B=3, bounces=3, directional=True, partition="octree"),
+            map_case("identity-scatter", "coincident", 256, 4097, B=8, bounces=3, mode="scatter", scene=("room",)),
+            map_case("identity-scatter-dir", "cell", 255, 257, B=1, bounces=4, mode="scatter", directional=True, partition="kdtree")]

@@ -1,7 +1,10 @@
 """numpy restatement of the receive loop (include/hare_hip.h, "receivers"), operation for operation in FP64: the receiver step, the rain
-step ("Diffuse rain"), the deposit in its omni and its directional ("Directional") form, and the one cast-by-cast loop that serves every
-mode -- specular (no table), scattering (tests/scatter_ref.py's RNG, choice, weights and directions) and diffuse rain, each with one word
-or four channels per band.  numpy evaluates every product, quotient and sum on its own (no contraction), in the order written here, and
+step ("Diffuse rain"), the deposit in its omni and its directional ("Directional") form, the termination rules ("Termination"), and the
+ONE cast-by-cast loop that serves every mode -- specular (no table), scattering (tests/scatter_ref.py's RNG, choice, weights and
+directions) and diffuse rain, each with one word or four channels per band, with or without the rules, over the linear receiver loop or
+the candidates of a receiver map ("Receiver maps": the grid and the visit rule are tests/receive_map_ref.py's).  A feature of the loop
+is added here, once; tests/golden/receive_reference_digests.json pins what the loop returns (tests/test_receive_reference_pinned.py).
+numpy evaluates every product, quotient and sum on its own (no contraction), in the order written here, and
 its sqrt and division are correctly rounded, so the library's results must match it bit for bit."""
 import numpy as np
 
@@ -88,11 +91,13 @@ def deposit(hist, k, bins, v, frac_bits, arrival, counts=None, tallies=None):
                 np.add.at(hist[k, :, b, 1 + i], bins, signed_words(m[b], a[i]))
 
 
-def receiver_step(o, d, t_end, L, E, centers, radii, n_bins, bin_len, frac_bits, hist, det, counts=None, tallies=None):
+def receiver_step(o, d, t_end, L, E, centers, radii, n_bins, bin_len, frac_bits, hist, det, counts=None, tallies=None, cand=None):
     """One cast's receiver step for the live rays given: o, d [m, 3]; t_end [m] (+inf for a miss); L [m]; E [B, m].
     hist [K, n_bins, B] or [K, n_bins, B, 4] and det [K, 2] (uint64) are accumulated into (wrapping mod 2^64).  The arrival vector of
     the directional form is one per ray, the same for every receiver: len = sqrt((dx*dx + dy*dy) + dz*dz),
-    a = (-(dx / len), -(dy / len), -(dz / len))."""
+    a = (-(dx / len), -(dy / len), -(dz / len)).  cand (bool [m, K], optional): the candidate mask of a receiver map -- for receiver k
+    only the rays with cand[:, k] take part, the others are out before anything is counted (detection is per ray and receiver, and the
+    adds are integer sums mod 2^64: the result is that of the step run per receiver on its candidates alone)."""
     o = np.asarray(o, np.float64).reshape(-1, 3)
     d = np.asarray(d, np.float64).reshape(-1, 3)
     E = np.asarray(E, np.float64).reshape(hist.shape[2], -1)
@@ -102,7 +107,7 @@ def receiver_step(o, d, t_end, L, E, centers, radii, n_bins, bin_len, frac_bits,
     dx, dy, dz = d[:, 0], d[:, 1], d[:, 2]
     with np.errstate(all="ignore"):
         dd = (dx * dx + dy * dy) + dz * dz
-        for k in range(centers.shape[0]):
+        for k in range(centers.shape[0]) if cand is None else np.nonzero(cand.any(axis=0))[0]:
             cx, cy, cz = centers[k]
             wx = cx - ox
             wy = cy - oy
@@ -112,6 +117,8 @@ def receiver_step(o, d, t_end, L, E, centers, radii, n_bins, bin_len, frac_bits,
             qy = (oy + dy * s) - cy
             qz = (oz + dz * s) - cz
             detected = (s >= 0) & (s < t_end) & (((qx * qx + qy * qy) + qz * qz) < r2[k])
+            if cand is not None:
+                detected &= cand[:, k]
             x = (L + s) / np.float64(bin_len)
             binned = detected & (x >= 0) & (x < np.float64(n_bins))
             det[k, 0] += np.uint64(np.count_nonzero(binned))
@@ -179,19 +186,62 @@ def rain_step(part, x, nprime, pid, length, Lp, Ea, sg, centers, radii, n_bins, 
                         tallies)                                        # ((Ea * sg) * w) * 2^frac_bits
 
 
+ROULETTE_WORD = 65                       # u_65: scattering draws j = 0 .. 64
+
+
+def decide(L, E, base, c, n_bins, bin_len, time_limit, floor_bits, roulette):
+    """The termination rules ("Termination": the time limit HARE_RECEIVE_TIME_LIMIT, the energy floor "receive_floor_bits" and its Russian
+    roulette "receive_roulette") for m rays that hit in cast c and would be reflected: L [m] and E [B, m] AFTER the cast's state update,
+    base [m] the RNG's per-ray base.  Returns (cut_time [m] bool, cut_floor [m] bool, boosted [m] bool, E' [B, m]): E' is E but for the
+    roulette's survivors, whose bands are divided by ps."""
+    m_rays = L.shape[0]
+    cut_time = np.zeros(m_rays, bool)
+    cut_floor = np.zeros(m_rays, bool)
+    boosted = np.zeros(m_rays, bool)
+    E = E.copy()
+    with np.errstate(all="ignore"):
+        if time_limit:
+            cut_time = (L / np.float64(bin_len)) >= np.float64(n_bins)          # a NaN compares false
+        if floor_bits:
+            F = np.ldexp(np.float64(1.0), -int(floor_bits))
+            m = E[0].copy()
+            for b in range(1, E.shape[0]):
+                m = np.where(E[b] > m, E[b], m)                                  # a NaN E[b] never replaces m
+            below = (m < F) & ~cut_time                                          # m = NaN: not below
+            if roulette:
+                at = np.nonzero(below)[0]
+                ps = m[at] / F
+                u = uniform(base[at], c, ROULETTE_WORD)
+                win = u < ps
+                E[:, at[win]] = E[:, at[win]] / ps[win]
+                boosted[at[win]] = True
+                cut_floor[at[~win]] = True
+            else:
+                cut_floor = below
+    return cut_time, cut_floor, boosted, E
+
+
 def receive_loop(po, topo, part, rays, bounces, centers, radii, n_bins, bin_len, frac_bits, alpha=None, sigma=None, seed=0, state_in=None,
                  g0=0, rain=False, directional=False, keep_rays_after=None, stats=None, counts=None, nthreads=16, events=None,
-                 tallies=None, excl1=None, excl2=None, last_events=None):
+                 tallies=None, excl1=None, excl2=None, last_events=None, time_limit=False, floor_bits=0, roulette=False, visit=None,
+                 per_cast=None, share=None):
     """The receive loop, cast by cast: part.shoot (an oracle partition) on the live rays, the receiver step, the state update, then (but
-    behind the last cast) the choice, the rain, the weights and the reflection -- specular rays with the oracle's reflection, diffuse
-    ones with tests/scatter_ref.py's.  sigma: the scattering table (None: specular).  rain: diffuse rain, with the receiver step skipped
-    for the segment behind a diffuse reflection (as in the library, it changes nothing without a table).  directional: four channels
-    per band.  g0: the global index of ray 0.  counts: an int64 array [K, n_bins] that collects the adds per (receiver, bin), or None.
-    events [bounces, n] (e.g. tests.helpers.oracle_bounce_loop): replay these recorded events of every cast instead of shooting.
-    tallies: deposit's dict of edge-case classes, or None.  excl1, excl2 [n]: poly_origin1 / poly_origin2 of the first cast (default:
-    none).  last_events: a list that receives the last cast's events [n] (a miss record for a retired ray), or None.
+    behind the last cast) the choice, the rain, the weights, the reflection -- specular rays with the oracle's reflection, diffuse
+    ones with tests/scatter_ref.py's -- and the termination rules.  sigma: the scattering table (None: specular).  rain: diffuse rain,
+    with the receiver step skipped for the segment behind a diffuse reflection (as in the library, it changes nothing without a table).
+    directional: four channels per band.  g0: the global index of ray 0.  counts: an int64 array [K, n_bins] that collects the adds per
+    (receiver, bin), or None.  events [bounces, n] (e.g. tests.helpers.oracle_bounce_loop): replay these recorded events of every cast
+    instead of shooting.  tallies: deposit's dict of edge-case classes, or None.  excl1, excl2 [n]: poly_origin1 / poly_origin2 of the
+    first cast (default: none).  last_events: a list that receives the last cast's events [n] (a miss record for a retired ray), or None.
+    time_limit, floor_bits, roulette: the rules of decide(), above (default: none).  visit: a callable (o, d, t_end) -> bool [m, K], the
+    candidate mask of a receiver map (tests.receive_map_ref.candidates on a grid), or None for the linear loop; with rain and a table it
+    is refused, as by the library.  per_cast: a dict that receives four int64 arrays [bounces] -- "live" (rays that took part in the
+    cast), "time" and "floor" (rays the rule retired in it), "boosted" (roulette survivors) -- or None.  share: a list that receives
+    (candidate pairs, rays x receivers) of every receiver step under `visit`, or None.
     Returns (hist [K, n_bins, B] or [K, n_bins, B, 4] uint64, det [K, 2], state [1 + B, n], the rays [n, 6] behind cast
     `keep_rays_after`, or the final ones)."""
+    if visit is not None and rain and sigma is not None:
+        raise ValueError("diffuse rain with a receiver map and a scattering table")
     rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
     n = rays.shape[0]
     B = 1
@@ -214,7 +264,11 @@ def receive_loop(po, topo, part, rays, bounces, centers, radii, n_bins, bin_len,
     live = np.ones(n, bool)
     rained = np.zeros(n, bool)              # the segment behind a diffuse reflection: deposited by the rain, not detected
     kept = None
+    if per_cast is not None:
+        per_cast.update({k: np.zeros(bounces, np.int64) for k in ("live", "time", "floor", "boosted")})
     for c in range(bounces):
+        if per_cast is not None:
+            per_cast["live"][c] = int(live.sum())
         ev = np.zeros(n, po.XEVENT_DTYPE)
         ev["poly_id"] = -1
         if live.any():
@@ -224,8 +278,13 @@ def receive_loop(po, topo, part, rays, bounces, centers, radii, n_bins, bin_len,
         t_end = np.where(hit, ev["t"], np.inf)
         seen = live & ~rained
         if seen.any():
+            cand = None
+            if visit is not None:
+                cand = visit(cur[seen, :3], cur[seen, 3:], t_end[seen])
+                if share is not None:
+                    share.append((int(cand.sum()), cand.size))
             receiver_step(cur[seen, :3], cur[seen, 3:], t_end[seen], L[seen], E[:, seen], centers, radii, n_bins, bin_len, frac_bits,
-                          hist, det, counts, tallies)
+                          hist, det, counts, tallies, cand)
         upd = live & hit
         if alpha is not None:
             a = np.asarray(alpha, np.float64)[ev["poly_id"][upd]].T          # [B, m]
@@ -233,10 +292,11 @@ def receive_loop(po, topo, part, rays, bounces, centers, radii, n_bins, bin_len,
                 E[:, upd] = E[:, upd] * (1.0 - a)
         L[upd] = L[upd] + ev["t"][upd]
         rained = np.zeros(n, bool)
+        goes_on = upd
         if c + 1 < bounces:
             nxt = po.reflect_batch(topo, cur, ev)
-            if sigma is not None and upd.any():
-                idx = np.nonzero(upd)[0]
+            idx = np.nonzero(upd)[0]
+            if sigma is not None and idx.size:
                 pid = ev["poly_id"][idx]
                 srow = np.asarray(sigma, np.float64)[pid]
                 p, diff = choose(srow, uniform(base[idx], c, 0))
@@ -255,12 +315,23 @@ def receive_loop(po, topo, part, rays, bounces, centers, radii, n_bins, bin_len,
                 di = idx[diff]
                 if di.size:
                     nxt[di] = scatter_rays(cur[di], ev[di], normals, base[di], c)
+            # termination: behind the state update; a retired ray keeps the ray the cast received and is treated as a miss from here
+            if (time_limit or floor_bits) and idx.size:
+                ct, cf, boosted, E[:, idx] = decide(L[idx], E[:, idx], base[idx], c, n_bins, bin_len, time_limit, floor_bits, roulette)
+                gone = idx[ct | cf]
+                nxt[gone] = cur[gone]
+                goes_on = upd.copy()
+                goes_on[gone] = False
+                rained[gone] = False
+                if per_cast is not None:
+                    for name, v in (("time", ct), ("floor", cf), ("boosted", boosted)):
+                        per_cast[name][c] = int(v.sum())
             cur = nxt
             if keep_rays_after == c:
                 kept = cur.copy()
-        e1 = np.where(upd, ev["poly_id"], -2).astype(np.int32)
+        e1 = np.where(goes_on, ev["poly_id"], -2).astype(np.int32)
         e2 = None
-        live = upd
+        live = goes_on
         if last_events is not None and c + 1 == bounces:
             last_events.append(ev)
     return hist, det, np.concatenate([L[None], E], axis=0), cur if keep_rays_after is None else kept

@@ -6,11 +6,13 @@ of 1 mm .. 10 m, a starting state or none, scatter seeds over the whole int64 ra
 Compared with the numpy restatement as tests/test_gpu_receive_edges.py compares.  No seed is skipped or redrawn
 (tests/test_receive_cases.py: each detects something).  tools/fuzz_receive.py runs the same cases over any seed range.
 
-N = 200.  The reference side of these seeds takes about 150 s on a 16-thread CPU host.  The wall time on the device is not yet recorded."""
+N = 200.  The reference side of these seeds takes about 150 s on a 16-thread CPU host.  On an MI355X host the whole module, reference
+side included, takes 37 s of wall time (200 passed; 16 threads of a faster CPU; 38 s before tests/receive_harness.py took over the
+device side)."""
 import pytest
 
 from tests.receive_cases import reference, sweep_case
-from tests.test_gpu_receive_edges import check_case
+from tests.receive_harness import check_case
 
 pytestmark = pytest.mark.gpu
 

@@ -1,7 +1,8 @@
 """What tests/test_gpu_receive_edges.py and tests/test_gpu_receive_sweep.py feed the library, proved by the reference alone (no GPU): over
 the edge set every class of the definition's awkward cases occurs (tests.receive_ref.TALLIES) and so does every shape the kernels treat
-differently; every sweep seed detects something and stays within the histogram's size bound.  Without this a device test could pass
-on inputs that never reach the code it is there for.
+differently; every sweep seed detects something, stays within the histogram's size bound and gives the result whose digest
+tests/golden/receive_reference_digests.json pins (tests/test_receive_reference_pinned.py holds the other cases).  Without this a device
+test could pass on inputs that never reach the code it is there for.
 
 One class cannot occur in any deposit: a directional word zeroed for NaN.  m is never NaN (it is 0 unless > 0) and a deposit's arrival
 vector is finite: a = -(d / len) needs len = 0 or inf, i.e. dd = 0 or inf, and then s = (w.d) / dd is NaN, +-inf or 0 / inf with a
@@ -11,7 +12,7 @@ that deposits nothing with m = 0 and its own arrival vector, and 0 * NaN (or 0 *
 to stay 0 and the edge set is asserted to hold such lanes (a direction scaled by 2^-600: dd underflows to 0) beside depositing ones."""
 import numpy as np
 
-from tests.receive_cases import MODES, WORDS_MAX, edge_cases, reference, sweep_case, wave_counts
+from tests.receive_cases import MODES, WORDS_MAX, digest, edge_cases, pinned_digests, reference, sweep_case, wave_counts
 from tests.receive_ref import TALLIES, signed_words
 
 SWEEP_SEEDS = 200                        # tests/test_gpu_receive_sweep.py's N
@@ -23,7 +24,7 @@ def test_edge_set_holds_every_class_and_every_shape():
     binned = unbinned = 0
     forms, rain_seen, room_occlusion = set(), False, False
     for c in cases:
-        r = reference(c)
+        r = reference(c, keep=True)
         assert r["det"].sum() > 0, c.describe()
         for k, v in r["tallies"].items():
             total[k] += v
@@ -90,6 +91,7 @@ def test_sweep_seeds_detect_something_within_the_size_bound():
         c = sweep_case(seed)
         r = reference(c)
         assert r["det"].sum() > 0, c.describe()
+        assert digest(r) == pinned_digests()[f"sweep/{seed}"], c.describe()       # the one pass over the seeds serves the pin too
         assert c.words <= WORDS_MAX and 1 <= c.K <= 256 and 1 <= c.B <= 8 and 1 <= c.bounces <= 8 and 0 <= c.frac_bits <= 62
         kinds.add((c.scene[0], c.partition[0]))
         modes.add((c.mode, c.directional, c.aggregate))

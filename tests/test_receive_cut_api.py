@@ -1,7 +1,8 @@
 """The receive loop's termination rules (include/hare_hip.h, "receivers", "Termination") without a GPU: the flag's value, the two scene
 options' ranges and read-back, the sharded call's refusal of scenes that differ in them before any device work -- and, with the numpy
-restatement alone (tests/receive_cut_ref.py), what the device tests rest on: with both rules off it is tests.receive_ref.receive_loop;
-the time limit leaves the histogram and detections[:, 0] as they are; the cases of tests/test_gpu_receive_cut.py are not vacuous (every
+restatement alone (tests/receive_ref.py), what the device tests rest on: with both rules off it returns what the loop returned before
+it knew the rules (the pinned digests of tests/golden/receive_reference_digests.json); the time limit leaves the histogram and
+detections[:, 0] as they are; the cases of tests/test_gpu_receive_cut.py are not vacuous (every
 rule under test retires at least 10 % of the rays before the last cast, at least 10 % still run the last cast, a roulette has survivors
 and casualties); and the roulette keeps every band's expected histogram total."""
 import dataclasses
@@ -12,10 +13,16 @@ import pytest
 import hare_amd as H
 from hare_amd import capi
 from oracle import pyoracle as po
-from tests.receive_cases import oracle_of, reference as plain_reference
-from tests.receive_cut_ref import cut_case, cut_cases, cut_loop, reference, same_bits, sweep_cut_case
+from tests.receive_cases import digest, oracle_of, pinned_digests, reference as any_reference
+from tests.receive_cut_ref import cut_case, cut_cases, sweep_cut_case
+from tests.receive_harness import same_bits
+from tests.receive_ref import receive_loop
 
 CASES = cut_cases()
+
+
+def reference(cc):
+    return any_reference(cc, keep=True)          # the fixed cases and their variants: shared, unchanged
 
 
 def grid():
@@ -78,12 +85,9 @@ def test_the_sharded_call_refuses_scenes_that_differ_in_the_options_before_any_d
 
 @pytest.mark.parametrize("cc", [CASES[1], CASES[12], CASES[16], CASES[17]], ids=lambda cc: cc.name)
 def test_with_both_rules_off_the_restatement_is_the_receive_loop(cc):
+    """The digest was taken from the loop without the rules, before the one with them replaced it."""
     off = reference(cc.without(time_limit=False, floor_bits=0, roulette=False))
-    want = plain_reference(cc.case)
-    for what in ("hist", "det", "state", "rays"):
-        assert same_bits(off[what], want[what]) is None, (cc.name, what)
-    for f in want["events"].dtype.names:
-        assert same_bits(off["events"][f], want["events"][f]) is None, (cc.name, f)
+    assert digest(off) == pinned_digests()["rules-off/" + cc.name], cc.name
     assert off["per_cast"]["time"].sum() == 0 and off["per_cast"]["floor"].sum() == 0 and off["per_cast"]["boosted"].sum() == 0
 
 
@@ -98,7 +102,7 @@ def test_the_time_limit_leaves_the_histogram_and_the_binned_detections_alone(cc)
 
 @pytest.mark.parametrize("cc", CASES, ids=lambda cc: cc.name)
 def test_the_cases_are_not_vacuous(cc):
-    pc, n = reference(cc)["per_cast"], cc.case.n
+    pc, n = reference(cc)["per_cast"], cc.n
     print(cc.describe(), {k: v.tolist() for k, v in pc.items()})
     assert cc.time_limit or cc.floor_bits
     assert pc["time"][-1] == 0 and pc["floor"][-1] == 0 and pc["boosted"][-1] == 0           # the last cast decides nothing
@@ -115,30 +119,30 @@ def test_the_cases_are_not_vacuous(cc):
     elif cc.floor_bits:
         assert pc["boosted"].sum() == 0
     assert pc["live"][-1] >= 0.1 * n
-    if cc.case.scene[0] == "room-open":                                     # rays retire by missing too
+    if cc.scene[0] == "room-open":                                          # rays retire by missing too
         retired = n - pc["live"][-1]
         assert retired - pc["time"].sum() - pc["floor"].sum() >= 0.02 * n
 
 
 def test_the_cases_cover_what_they_claim():
     def has(**kw):
-        return any(all((getattr(c, k) if hasattr(c, k) else getattr(c.case, k)) == v for k, v in kw.items()) for c in CASES)
+        return any(all(getattr(c, k) == v for k, v in kw.items()) for c in CASES)
     for n in (63, 257, 4097, 4159):
-        assert any(c.case.n == n for c in CASES)
+        assert any(c.n == n for c in CASES)
     for kind in ("voxel", "octree", "kdtree"):
-        assert any(c.case.partition[0] == kind for c in CASES)
-    assert any(c.case.B == 1 for c in CASES) and any(c.case.B == 3 for c in CASES)
+        assert any(c.partition[0] == kind for c in CASES)
+    assert any(c.B == 1 for c in CASES) and any(c.B == 3 for c in CASES)
     for mode in ("specular", "scatter", "rain"):
         assert has(mode=mode)
     assert has(time_limit=True, floor_bits=0) and has(time_limit=False, roulette=False) and has(time_limit=False, roulette=True)
     assert has(time_limit=True, roulette=True)
     assert has(mode="specular", roulette=True)                              # the roulette without a scattering table
     assert has(directional=True) and has(pack=0) and has(pack=1) and has(aggregate=0) and has(aggregate=1) and has(device=True)
-    assert any(c.case.state_in is not None and np.isnan(c.case.state_in[0]).any() and np.isinf(c.case.state_in[0]).any() for c in CASES)
+    assert any(c.state_in is not None and np.isnan(c.state_in[0]).any() and np.isinf(c.state_in[0]).any() for c in CASES)
     # both sides of the live-block list's threshold, on the partition that has the list, with it and without
-    assert any(c.case.partition[0] == "voxel" and c.case.n >= 4096 and c.case.pack == 1 for c in CASES)
-    assert any(c.case.partition[0] == "voxel" and c.case.n >= 4096 and c.case.pack == 0 for c in CASES)
-    assert any(c.case.partition[0] == "voxel" and c.case.n < 4096 for c in CASES)
+    assert any(c.partition[0] == "voxel" and c.n >= 4096 and c.pack == 1 for c in CASES)
+    assert any(c.partition[0] == "voxel" and c.n >= 4096 and c.pack == 0 for c in CASES)
+    assert any(c.partition[0] == "voxel" and c.n < 4096 for c in CASES)
 
 
 def test_a_sweep_seed_draws_every_rule_somewhere():
@@ -153,15 +157,15 @@ def test_the_roulette_keeps_every_bands_expected_histogram_total():
     band agrees within three standard errors of the mean, the standard error being that of the 16 totals without a floor.  F = 2^-2 and
     alpha = 0.3: every ray passes under the floor at its fourth hit, so three quarters of the 24 casts are played by survivors.  (The
     plain floor at the same F loses a fifth of the total -- asserted too: the bound is not so wide that it would pass anything.)"""
-    base = cut_case("unbiased", "roulette", 4096, B=3, mode="scatter").case
+    base = cut_case("unbiased", "roulette", 4096, B=3, mode="scatter")
     P = base.alpha.shape[0]
     alpha = np.full((P, 3), 0.3) * np.array([1.0, 0.9, 1.1])
     case = dataclasses.replace(base, alpha=alpha, sigma=np.full((P, 3), 0.5), bounces=24, n_bins=400, bin_len=0.5, frac_bits=30)
     To, o = oracle_of(case)
 
     def totals(seed, **rules):
-        hist = cut_loop(po, To, o, case.rays, case.bounces, case.centers, case.radii, case.n_bins, case.bin_len, case.frac_bits, alpha=case.alpha,
-                        sigma=case.sigma, seed=seed, **rules)[0]
+        hist = receive_loop(po, To, o, case.rays, case.bounces, case.centers, case.radii, case.n_bins, case.bin_len, case.frac_bits, alpha=case.alpha,
+                            sigma=case.sigma, seed=seed, **rules)[0]
         return hist.astype(np.float64).sum(axis=(0, 1)) * 2.0 ** -case.frac_bits                # [B]
 
     none = np.array([totals(s) for s in range(16)])

@@ -11,7 +11,8 @@ import pytest
 
 import hare_amd as H
 from hare_amd import capi
-from tests.receive_map_ref import MAX_K, build_grid, candidates, map_cases, map_layout, reference
+from tests.receive_cases import reference
+from tests.receive_map_ref import MAX_K, build_grid, candidates, map_cases, map_layout
 from tests.receive_ref import receiver_step
 
 NEW = ("hare_scene_set_receiver_map", "hare_scene_get_receiver_map")
@@ -241,9 +242,9 @@ def test_the_visit_rule_is_a_function_of_any_input():
 # ---- the device cases are not vacuous (the restatement alone)
 @pytest.mark.parametrize("mc", CASES, ids=[c.name for c in CASES])
 def test_device_case_detects_binned_and_unbinned(mc):
-    want = reference(mc)
+    want = reference(mc, keep=True)
     assert want["det"][:, 0].sum() > 0 and want["det"][:, 1].sum() > 0, mc.describe()
     assert want["hist"].any()
-    if mc.shape in ("plane", "cell") and mc.case.K >= 256:
+    if mc.map_shape in ("plane", "cell") and mc.K >= 256:
         pairs = np.array(want["share"], np.float64)
         assert pairs[:, 0].sum() / pairs[:, 1].sum() < 0.25, mc.describe()
