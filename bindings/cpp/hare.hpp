@@ -236,11 +236,96 @@ public:
                                   state_out ? state_out->data() : nullptr, hist.data(), detections.data(), &c));
         return c.hits;
     }
+    // the reduction of a histogram on the device (include/hare_hip.h, "receivers", "Reduction"): per receiver and band, the sums S0 = sum g
+    // and S1 = sum i g over bin windows and the bins at which the backward-integrated decay crosses the levels.  What to compute:
+    struct Reduction {
+        std::vector<int32_t> windows;       // lo_0, hi_0, lo_1, hi_1, ...: up to 16 bin ranges [lo, hi)
+        std::vector<uint32_t> levels;       // up to 32 fractions in units of 2^-32 (DecayLevel)
+        std::vector<uint32_t> weight;       // n_bins x B in units of 2^-32 (AirWeights), or empty: none
+    };
+    static uint32_t DecayLevel(double dB)   // min(2^32 - 1, floor(10^(dB / 10) * 2^32)), dB <= 0
+    {
+        const double f = std::floor(std::pow(10.0, dB / 10.0) * 4294967296.0);
+        return f >= 4294967295.0 ? 4294967295u : (f > 0 ? (uint32_t)f : 0u);
+    }
+    // weights for air absorption: m holds the energy attenuation per unit of path length of each band;
+    // min(2^32 - 1, floor(exp(-m_b * (i + 0.5) * bin_len) * 2^32)), bin-major
+    static std::vector<uint32_t> AirWeights(const std::vector<double>& m, double bin_len, int n_bins)
+    {
+        std::vector<uint32_t> w((size_t)(n_bins > 0 ? n_bins : 0) * m.size());
+        for (int i = 0; i < n_bins; ++i)
+            for (size_t b = 0; b < m.size(); ++b) {
+                const double f = std::floor(std::exp(-m[b] * ((double)i + 0.5) * bin_len) * 4294967296.0);
+                w[(size_t)i * m.size() + b] = f >= 4294967295.0 ? 4294967295u : (f > 0 ? (uint32_t)f : 0u);
+            }
+        return w;
+    }
+    // hare_hist_reduce: hist is K x n_bins x B (x 4 with channels = 4; channel 0 is read) as Receive returns it.  sums: K x B x n_win x 4
+    // (S0 lo, S0 hi, S1 lo, S1 hi); cross: K x B x n_lev
+    void HistReduce(const std::vector<uint64_t>& hist, int K, int n_bins, int B, int channels, const Reduction& r, std::vector<uint64_t>& sums,
+                    std::vector<int32_t>& cross)
+    {
+        if (K < 0 || n_bins < 0 || B < 0 || channels < 0 || hist.size() != (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels)
+            throw std::invalid_argument("HistReduce: hist must hold K x n_bins x B x channels values");
+        const int n_win = check_reduction(r, n_bins, B, "HistReduce"), n_lev = (int)r.levels.size();
+        sums.assign((size_t)K * (size_t)B * (size_t)n_win * 4, 0);
+        cross.assign((size_t)K * (size_t)B * (size_t)n_lev, 0);
+        check(hare_hist_reduce(scene_, K, n_bins, B, channels, hist.data(), r.weight.empty() ? nullptr : r.weight.data(), n_win, r.windows.data(),
+                               n_lev, r.levels.data(), sums.data(), cross.data()));
+    }
+    // Receive / ReceiveSource with the histogram reduced on the device (hare_receive_batch_reduced / hare_receive_source_reduced): sums and
+    // cross as HistReduce gives them on the histogram Receive returns; the histogram itself never comes down
+    uint64_t ReceiveReduced(const std::vector<hare_ray>& rays, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
+                            const Reduction& r, std::vector<uint64_t>& sums, std::vector<int32_t>& cross, std::vector<uint64_t>& detections,
+                            const std::vector<double>* state_in = nullptr, std::vector<double>* state_out = nullptr, bool directional = false)
+    {
+        const int64_t K = GetOption("receivers"), B = Bands(top_index);
+        const size_t n_state = (size_t)(1 + B) * rays.size();
+        if (state_in && state_in->size() != n_state) throw std::invalid_argument("ReceiveReduced: state_in must hold (1 + B) x rays.size() values");
+        const int n_win = check_reduction(r, n_bins, (int)B, "ReceiveReduced"), n_lev = (int)r.levels.size();
+        sums.assign((size_t)(K * B) * (size_t)n_win * 4, 0);
+        cross.assign((size_t)(K * B) * (size_t)n_lev, 0);
+        detections.assign((size_t)(2 * K), 0);
+        if (state_out) state_out->assign(n_state, 0.0);
+        hare_counters c{};
+        check(hare_receive_batch_reduced(scene_, kind_, top_index, (int64_t)rays.size(), rays.data(), nullptr, nullptr, bounces,
+                                         directional ? HARE_RECEIVE_DIRECTIONAL : 0u, n_bins, bin_len, frac_bits,
+                                         state_in ? state_in->data() : nullptr, state_out ? state_out->data() : nullptr,
+                                         r.weight.empty() ? nullptr : r.weight.data(), n_win, r.windows.data(), n_lev, r.levels.data(), sums.data(),
+                                         cross.data(), detections.data(), &c));
+        return c.hits;
+    }
+    uint64_t ReceiveSourceReduced(int64_t n, int64_t first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
+                                  const Reduction& r, std::vector<uint64_t>& sums, std::vector<int32_t>& cross, std::vector<uint64_t>& detections,
+                                  std::vector<double>* state_out = nullptr, bool directional = false)
+    {
+        if (n < 0) throw std::invalid_argument("ReceiveSourceReduced: n must be >= 0");
+        const int64_t K = GetOption("receivers"), B = Bands(top_index);
+        const int n_win = check_reduction(r, n_bins, (int)B, "ReceiveSourceReduced"), n_lev = (int)r.levels.size();
+        sums.assign((size_t)(K * B) * (size_t)n_win * 4, 0);
+        cross.assign((size_t)(K * B) * (size_t)n_lev, 0);
+        detections.assign((size_t)(2 * K), 0);
+        if (state_out) state_out->assign((size_t)(1 + B) * (size_t)n, 0.0);
+        hare_counters c{};
+        check(hare_receive_source_reduced(scene_, kind_, top_index, n, first_ray, bounces, directional ? HARE_RECEIVE_DIRECTIONAL : 0u, n_bins,
+                                          bin_len, frac_bits, state_out ? state_out->data() : nullptr,
+                                          r.weight.empty() ? nullptr : r.weight.data(), n_win, r.windows.data(), n_lev, r.levels.data(), sums.data(),
+                                          cross.data(), detections.data(), &c));
+        return c.hits;
+    }
     void SetOption(const char* name, int64_t value) { check(hare_scene_set_option(scene_, name, value)); }
     int64_t GetOption(const char* name) const { int64_t v = 0; check(hare_scene_get_option(scene_, name, &v)); return v; }
     hare_scene* native() const { return scene_; }
 
 protected:
+    // what the library cannot check of a Reduction -- the sizes of its vectors; returns n_win
+    static int check_reduction(const Reduction& r, int n_bins, int B, const char* who)
+    {
+        if (r.windows.size() % 2 != 0) throw std::invalid_argument(std::string(who) + ": windows must hold lo, hi pairs");
+        if (!r.weight.empty() && (n_bins < 0 || B < 0 || r.weight.size() != (size_t)n_bins * (size_t)B))
+            throw std::invalid_argument(std::string(who) + ": weight must hold n_bins x B values (or none)");
+        return (int)(r.windows.size() / 2);
+    }
     Spatial_Partition(const std::vector<const Topology*>& Model_in, int kind, int device) : Model(Model_in), kind_(kind)
     {
         std::vector<hare_topology_desc> d;

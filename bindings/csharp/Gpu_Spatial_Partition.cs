@@ -363,6 +363,72 @@ namespace Hare
                 return (long)ctr.hits;
             }
 
+            /// <summary>Receive / ReceiveSource with the histogram reduced on the device (hare_receive_batch_reduced /
+            /// hare_receive_source_reduced; include/hare_hip.h, "Reduction"): the histogram never comes down.  win holds n_win pairs
+            /// lo, hi of bins; levels fractions in units of 2^-32 (DecayLevel); weight n_bins x B values in units of 2^-32 (AirWeights) or
+            /// null.  sums: receivers x B x n_win x 4 (S0 lo, S0 hi, S1 lo, S1 hi); cross: receivers x B x levels.Length.  rays null: the
+            /// scene's source emits n rays from first_ray.  One scene only: a crossing is not additive over shards.</summary>
+            public long ReceiveReduced(hare_ray[] rays, long n, long first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
+                                       uint[] weight, int[] win, uint[] levels, ulong[] sums, int[] cross, ulong[] detections, double[] state = null,
+                                       bool directional = false)
+            {
+                if (scenes.Length != 1) throw new NotSupportedException("ReceiveReduced runs on one scene: reduce the histogram of the sharded Receive with HistReduce");
+                if (bounces < 1) throw new ArgumentException("bounces must be at least 1");
+                if (rays != null) n = rays.LongLength;
+                if (n < 0) throw new ArgumentException("n must be at least 0");
+                long K = GetOption("receivers"), B = Bands(top_index);
+                int n_win = win == null ? 0 : win.Length / 2, n_lev = levels == null ? 0 : levels.Length;
+                if (win != null && win.Length % 2 != 0) throw new ArgumentException("win must hold lo, hi pairs");
+                if (weight != null && weight.LongLength != (long)n_bins * B) throw new ArgumentException("weight must hold n_bins x Bands(top_index) values (or be null)");
+                if (n_win > 0 && (sums == null || sums.LongLength < K * B * n_win * 4)) throw new ArgumentException("sums must hold receivers x Bands(top_index) x windows x 4 values");
+                if (n_lev > 0 && (cross == null || cross.LongLength < K * B * n_lev)) throw new ArgumentException("cross must hold receivers x Bands(top_index) x levels values");
+                if (detections == null || detections.LongLength < 2 * K) throw new ArgumentException("detections must hold 2 x receivers values");
+                if (state != null && state.LongLength < (1 + B) * n) throw new ArgumentException("state must hold (1 + Bands(top_index)) x n values");
+                hare_counters ctr;
+                uint flags = directional ? HareHip.HARE_RECEIVE_DIRECTIONAL : 0u;
+                if (rays != null)
+                    HareHip.Check(HareHip.hare_receive_batch_reduced(scenes[0], Kind, top_index, n, rays, null, null, bounces, flags, n_bins, bin_len, frac_bits,
+                                                                     null, state, weight, n_win, win, n_lev, levels, sums, cross, detections, out ctr));
+                else
+                    HareHip.Check(HareHip.hare_receive_source_reduced(scenes[0], Kind, top_index, n, first_ray, bounces, flags, n_bins, bin_len, frac_bits,
+                                                                      state, weight, n_win, win, n_lev, levels, sums, cross, detections, out ctr));
+                return (long)ctr.hits;
+            }
+
+            /// <summary>hare_hist_reduce on a histogram a Receive call returned (K x n_bins x B, x 4 when directional: channels = 4), on the
+            /// first scene's device.</summary>
+            public void HistReduce(ulong[] hist, int K, int n_bins, int B, int channels, uint[] weight, int[] win, uint[] levels, ulong[] sums, int[] cross)
+            {
+                if (hist == null || hist.LongLength < (long)K * n_bins * B * channels) throw new ArgumentException("hist must hold K x n_bins x B x channels values");
+                if (win != null && win.Length % 2 != 0) throw new ArgumentException("win must hold lo, hi pairs");
+                int n_win = win == null ? 0 : win.Length / 2, n_lev = levels == null ? 0 : levels.Length;
+                if (weight != null && weight.LongLength != (long)n_bins * B) throw new ArgumentException("weight must hold n_bins x B values (or be null)");
+                if (n_win > 0 && (sums == null || sums.LongLength < (long)K * B * n_win * 4)) throw new ArgumentException("sums must hold K x B x windows x 4 values");
+                if (n_lev > 0 && (cross == null || cross.LongLength < (long)K * B * n_lev)) throw new ArgumentException("cross must hold K x B x levels values");
+                HareHip.Check(HareHip.hare_hist_reduce(scenes[0], K, n_bins, B, channels, hist, weight, n_win, win, n_lev, levels, sums, cross));
+            }
+
+            /// <summary>min(2^32 - 1, floor(10^(dB / 10) * 2^32)): a level of the reduction from decibels (dB at most 0).</summary>
+            public static uint DecayLevel(double dB)
+            {
+                double f = Math.Floor(Math.Pow(10.0, dB / 10.0) * 4294967296.0);
+                return f >= 4294967295.0 ? 4294967295u : (f > 0 ? (uint)f : 0u);
+            }
+
+            /// <summary>Weights of the reduction for air absorption: m[b] is the energy attenuation per unit of path length in band b;
+            /// min(2^32 - 1, floor(exp(-m[b] (i + 0.5) bin_len) 2^32)), bin-major.</summary>
+            public static uint[] AirWeights(double[] m, double bin_len, int n_bins)
+            {
+                uint[] w = new uint[(long)n_bins * m.Length];
+                for (int i = 0; i < n_bins; ++i)
+                    for (int b = 0; b < m.Length; ++b)
+                    {
+                        double f = Math.Floor(Math.Exp(-m[b] * (i + 0.5) * bin_len) * 4294967296.0);
+                        w[(long)i * m.Length + b] = f >= 4294967295.0 ? 4294967295u : (f > 0 ? (uint)f : 0u);
+                    }
+                return w;
+            }
+
             /// <summary>The same on managed objects: result[b][i] is the X_Event of ray i in cast b (X_Event() once the ray has
             /// left the model).  rays[] is not modified.</summary>
             public X_Event[][] Bounce(Ray[] rays, int top_index, int bounces)

@@ -263,6 +263,25 @@ namespace Hare
                                                                  int bounces, uint flags, int n_bins, double bin_len, int frac_bits,
                                                                  [Out] double[] state_out, [Out] ulong[] hist, [Out] ulong[] detections,
                                                                  out hare_counters ctr);
+            // the reduction of a histogram on the device (include/hare_hip.h, "receivers", "Reduction")
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_hist_reduce_device(IntPtr scene, int K, int n_bins, int B, int channels, IntPtr d_hist, IntPtr d_weight,
+                                                             int n_win, [In] int[] win, int n_lev, [In] uint[] levels, IntPtr d_sums, IntPtr d_cross,
+                                                             IntPtr stream);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_hist_reduce(IntPtr scene, int K, int n_bins, int B, int channels, [In] ulong[] hist, [In] uint[] weight,
+                                                      int n_win, [In] int[] win, int n_lev, [In] uint[] levels, [Out] ulong[] sums, [Out] int[] cross);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_receive_batch_reduced(IntPtr scene, int kind, int top_index, long n, [In] hare_ray[] rays, int[] excl1,
+                                                                int[] excl2, int bounces, uint flags, int n_bins, double bin_len, int frac_bits,
+                                                                [In] double[] state_in, [Out] double[] state_out, [In] uint[] weight, int n_win,
+                                                                [In] int[] win, int n_lev, [In] uint[] levels, [Out] ulong[] sums, [Out] int[] cross,
+                                                                [Out] ulong[] detections, out hare_counters ctr);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_receive_source_reduced(IntPtr scene, int kind, int top_index, long n, long first_ray, int bounces, uint flags,
+                                                                 int n_bins, double bin_len, int frac_bits, [Out] double[] state_out, [In] uint[] weight,
+                                                                 int n_win, [In] int[] win, int n_lev, [In] uint[] levels, [Out] ulong[] sums,
+                                                                 [Out] int[] cross, [Out] ulong[] detections, out hare_counters ctr);
 
             public static void Check(int rc)
             {

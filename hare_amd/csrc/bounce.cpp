@@ -29,6 +29,8 @@
 
 namespace hare {
 
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb);     // launch.cpp
+
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
         hipError_t _e = (expr);                                                                \
@@ -41,13 +43,14 @@ void free_bounce_buffers(const HipApi* H, Scene& s)
         Scene::BounceBuf& b = c.bounce;
         if (b.copy_st) { (void)H->StreamSynchronize(b.copy_st); (void)H->StreamDestroy(b.copy_st); b.copy_st = nullptr; }
         for (void** p : {&b.rays[0], &b.rays[1], &b.excl[0], &b.excl[1], &b.excl2, &b.idx[0], &b.idx[1], &b.ev[0], &b.ev[1], &b.full,
-                         &b.tiles, &b.ctr, &b.state, &b.hist, &b.rain})
+                         &b.tiles, &b.ctr, &b.state, &b.hist, &b.rain, &b.red})
             dev_free(H, *p);
         b.cap = 0;
         b.ctr_cap = 0;
         b.state_cap = 0;
         b.hist_cap = 0;
         b.rain_cap = 0;
+        b.red_cap = 0;
     }
 }
 
@@ -231,6 +234,11 @@ struct ReceiveJob {
     uint32_t flags = 0;        // the call's HARE_RECEIVE_* bits
     bool from_source = false;  // hare_receive_source: rays and state come from hare_emit_source (rays from ray_base on), not from the caller
     const char* who = "hare_receive_batch";
+    // hare_receive_*_reduced: the histogram stays in BounceBuf::hist and hare_hist_reduce runs behind the last cast; sums and cross come
+    // down in its place (hist is null)
+    const ReduceSpec* reduce = nullptr;
+    uint64_t* sums = nullptr;
+    int32_t* cross = nullptr;
 };
 
 // The receive loop for one scene: rays, exclusions and state go up, the loop is enqueued ONCE (a launch per cast, hare_receive_reflect
@@ -265,6 +273,17 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
         HIP_TRY(H->Malloc(&b.rain, rain_bytes));
         b.rain_cap = rain_bytes;
     }
+    // the reduction's own block: sums, crossings, weights, each from a 16-byte boundary
+    const ReduceSpec* const red = job.reduce;
+    const size_t sums_bytes = red ? K * (size_t)B * (size_t)red->n_win * 4 * sizeof(uint64_t) : 0;
+    const size_t cross_words = red ? K * (size_t)B * (size_t)red->n_lev : 0, cross_bytes = (cross_words * sizeof(int32_t) + 15) & ~(size_t)15;
+    const size_t weight_bytes = red && red->weight ? (size_t)job.n_bins * (size_t)B * sizeof(uint32_t) : 0;
+    if (red && sums_bytes + cross_bytes + weight_bytes > b.red_cap) {
+        dev_free(H, b.red);
+        b.red_cap = 0;
+        HIP_TRY(H->Malloc(&b.red, sums_bytes + cross_bytes + weight_bytes));
+        b.red_cap = sums_bytes + cross_bytes + weight_bytes;
+    }
     if (!c.st[0]) HIP_TRY(H->StreamCreate(&c.st[0]));
     hipStream_t st = c.st[0];
     uint64_t* const d_hist = (uint64_t*)b.hist;
@@ -291,7 +310,19 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
     if (int rc = bounce_device_impl(s, H, kind, top, n, b.rays[0], excl1 ? b.excl[0] : nullptr, excl2 ? b.excl2 : nullptr, bounces, flags, work,
                                     nullptr, b.ev[0], nullptr, b.ctr, st, &plan))
         return rc;
-    HIP_TRY(H->MemcpyAsync(job.hist, d_hist, hist_words * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (red) {
+        char* const d_sums = (char*)b.red;
+        char* const d_cross = d_sums + sums_bytes;
+        char* const d_weight = d_cross + cross_bytes;
+        if (weight_bytes) HIP_TRY(H->MemcpyAsync(d_weight, red->weight, weight_bytes, hipMemcpyHostToDevice, st));
+        if (int rc = reduce_enqueue(s, H, (int32_t)K, job.n_bins, B, (job.flags & HARE_RECEIVE_DIRECTIONAL) ? 4 : 1, d_hist,
+                                    weight_bytes ? d_weight : nullptr, *red, d_sums, d_cross, st))
+            return rc;
+        if (sums_bytes) HIP_TRY(H->MemcpyAsync(job.sums, d_sums, sums_bytes, hipMemcpyDeviceToHost, st));
+        if (cross_words) HIP_TRY(H->MemcpyAsync(job.cross, d_cross, cross_words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    } else {
+        HIP_TRY(H->MemcpyAsync(job.hist, d_hist, hist_words * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(H->MemcpyAsync(job.det, d_det, 2 * K * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     if (job.state_out)
         for (int32_t p = 0; p <= B; ++p)
@@ -477,7 +508,8 @@ int hare_bounce_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int32
 static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n_scenes, int32_t kind, int32_t top_index, int64_t n,
                            const hare_ray* rays, const int32_t* excl1, const int32_t* excl2, int32_t bounces, uint32_t flags, int32_t n_bins,
                            double bin_len, int32_t frac_bits, const double* state_in, double* state_out, uint64_t* hist, uint64_t* detections,
-                           hare_counters* ctr, const int64_t* first_ray)
+                           hare_counters* ctr, const int64_t* first_ray, const ReduceSpec* red = nullptr, uint64_t* sums = nullptr,
+                           int32_t* cross = nullptr)
 {
     if (!scenes || n_scenes < 1 || n_scenes > 64) {
         set_error(std::string(who) + ": need 1..64 scenes");
@@ -490,9 +522,32 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
         }
     hare_scene* const s0 = scenes[0];
     if (int rc = receive_check_args(who, *s0, flags, kind, top_index, n, bounces, n_bins, bin_len, frac_bits)) return rc;
-    if ((n > 0 && !rays && !first_ray) || !hist || !detections) {
+    if ((n > 0 && !rays && !first_ray) || (!hist && !red) || !detections) {
         set_error(std::string(who) + ": null rays, histogram or detections");
         return HARE_E_INVALID;
+    }
+    if (red && n_scenes != 1) {      // a crossing is not additive over shards
+        set_error(std::string(who) + ": the reduction runs on one scene");
+        return HARE_E_INVALID;
+    }
+    if (red) {      // the _reduced calls: the reduction's own checks, at the histogram's shape
+        const size_t K1 = std::max<size_t>(1, s0->rcv.size() / 4), KB = K1 * (size_t)scene_bands(*s0, top_index);
+        if (int rc = reduce_check_spec(who, (int64_t)K1, n_bins, scene_bands(*s0, top_index), (flags & HARE_RECEIVE_DIRECTIONAL) ? 4 : 1, *red)) return rc;
+        if ((red->n_win > 0 && !sums) || (red->n_lev > 0 && !cross)) {
+            set_error(std::string(who) + ": null sums / crossings");
+            return HARE_E_INVALID;
+        }
+        const struct { const void* p; size_t bytes; } bufs[] = {{sums, KB * (size_t)red->n_win * 4 * sizeof(uint64_t)},
+                                                                {cross, KB * (size_t)red->n_lev * sizeof(int32_t)},
+                                                                {detections, K1 * 2 * sizeof(uint64_t)},
+                                                                {state_out, (size_t)n * (size_t)(1 + scene_bands(*s0, top_index)) * sizeof(double)},
+                                                                {red->weight, (size_t)n_bins * (size_t)scene_bands(*s0, top_index) * sizeof(uint32_t)}};
+        for (size_t x = 0; x < 2; ++x)      // the two new outputs against each other and the rest; the parent's buffers are checked as the parent checks them
+            for (size_t y = x + 1; y < 5; ++y)
+                if (ranges_overlap(bufs[x].p, bufs[x].bytes, bufs[y].p, bufs[y].bytes)) {
+                    set_error(std::string(who) + ": sums, crossings, detections, state and weights must not overlap");
+                    return HARE_E_INVALID;
+                }
     }
     if (first_ray) {
         if (int rc = source_check_range(who, n, *first_ray)) return rc;
@@ -534,7 +589,11 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
     GUARD_BEGIN
     const int G = n_scenes;
     const size_t K = s0->rcv.size() / 4, hist_words = receive_hist_words(*s0, top_index, n_bins, flags);
-    memset(hist, 0, hist_words * sizeof(uint64_t));
+    if (hist) memset(hist, 0, hist_words * sizeof(uint64_t));
+    if (red) {      // n == 0 runs nothing: the reduction of an empty histogram
+        if (red->n_win > 0) memset(sums, 0, K * (size_t)scene_bands(*s0, top_index) * (size_t)red->n_win * 4 * sizeof(uint64_t));
+        if (red->n_lev > 0) memset(cross, 0, K * (size_t)scene_bands(*s0, top_index) * (size_t)red->n_lev * sizeof(int32_t));
+    }
     memset(detections, 0, 2 * K * sizeof(uint64_t));
     if (ctr) memset(ctr, 0, sizeof *ctr);
     std::vector<int> rcs((size_t)G, HARE_OK);
@@ -561,6 +620,9 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
         job.flags = flags;
         job.from_source = first_ray != nullptr;
         job.who = who;
+        job.reduce = red;
+        job.sums = sums;
+        job.cross = cross;
         try {
             rcs[(size_t)k] = bounce_one(scenes[k], kind, top_index, hi - lo, rays ? rays + lo : nullptr, excl1 ? excl1 + lo : nullptr,
                                         excl2 ? excl2 + lo : nullptr, bounces, flags, nullptr, n, nullptr, pcs[(size_t)k].data(), &job);
@@ -632,6 +694,44 @@ int hare_receive_source_sharded(hare_scene* const* scenes, int32_t n_scenes, int
 {
     return receive_sharded(n_scenes == 1 ? "hare_receive_source" : "hare_receive_source_sharded", scenes, n_scenes, kind, top_index, n, nullptr,
                            nullptr, nullptr, bounces, flags, n_bins, bin_len, frac_bits, nullptr, state_out, hist, detections, ctr, &first_ray);
+}
+
+}  // extern "C"
+
+// hare_receive_batch / hare_receive_source with the histogram reduced on the device (include/hare_hip.h, "receivers", "Reduction")
+static ReduceSpec reduce_spec(const uint32_t* weight, int32_t n_win, const int32_t* win, int32_t n_lev, const uint32_t* levels)
+{
+    ReduceSpec r;
+    r.weight = weight;
+    r.n_win = n_win;
+    r.win = win;
+    r.n_lev = n_lev;
+    r.levels = levels;
+    return r;
+}
+
+extern "C" {
+
+int hare_receive_batch_reduced(hare_scene* s, int32_t kind, int32_t top_index, int64_t n, const hare_ray* rays, const int32_t* excl1,
+                               const int32_t* excl2, int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits,
+                               const double* state_in, double* state_out, const uint32_t* weight, int32_t n_win, const int32_t* win,
+                               int32_t n_lev, const uint32_t* levels, uint64_t* sums, int32_t* cross, uint64_t* detections, hare_counters* ctr)
+{
+    hare_scene* const one[1] = {s};
+    const ReduceSpec r = reduce_spec(weight, n_win, win, n_lev, levels);
+    return receive_sharded("hare_receive_batch_reduced", one, 1, kind, top_index, n, rays, excl1, excl2, bounces, flags, n_bins, bin_len, frac_bits,
+                           state_in, state_out, nullptr, detections, ctr, nullptr, &r, sums, cross);
+}
+
+int hare_receive_source_reduced(hare_scene* s, int32_t kind, int32_t top_index, int64_t n, int64_t first_ray, int32_t bounces, uint32_t flags,
+                                int32_t n_bins, double bin_len, int32_t frac_bits, double* state_out, const uint32_t* weight, int32_t n_win,
+                                const int32_t* win, int32_t n_lev, const uint32_t* levels, uint64_t* sums, int32_t* cross, uint64_t* detections,
+                                hare_counters* ctr)
+{
+    hare_scene* const one[1] = {s};
+    const ReduceSpec r = reduce_spec(weight, n_win, win, n_lev, levels);
+    return receive_sharded("hare_receive_source_reduced", one, 1, kind, top_index, n, nullptr, nullptr, nullptr, bounces, flags, n_bins, bin_len,
+                           frac_bits, nullptr, state_out, nullptr, detections, ctr, &first_ray, &r, sums, cross);
 }
 
 }  // extern "C"

@@ -130,6 +130,7 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_ob_count", &m->ob_count},
         {"hare_ob_fill", &m->ob_fill},
         {"hare_emit_source", &m->emit_source},
+        {"hare_hist_reduce", &m->hist_reduce},
     };
     for (auto& t : table) {
         hipError_t e = H->ModuleGetFunction(t.fn, m->mod, t.name);

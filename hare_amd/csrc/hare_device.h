@@ -571,6 +571,24 @@ struct SourceArgs {
     int32_t res;               // R: 0 (no table) .. kMaxSourceRes
 };
 
+// hare_hist_reduce (reduce.hip): a receive histogram reduced to window sums and decay-level crossings per receiver and band
+// (include/hare_hip.h, "receivers", "Reduction").  Windows, levels and counts by value (276 of the struct's 312 bytes): no upload
+constexpr int kMaxReduceWindows = 16;
+constexpr int kMaxReduceLevels = 32;
+struct ReduceArgs {
+    const unsigned long long* hist;   // K x n_bins x bands x channels words; channel 0 is read
+    const uint32_t* weight;           // n_bins x bands, units of 2^-32 (null: none)
+    unsigned long long* sums;         // K x bands x n_win x 4: S0 lo, S0 hi, S1 lo, S1 hi; each word written once
+    int32_t* cross;                   // K x bands x n_lev; each word written once
+    int32_t n_bins;
+    int32_t bands;                    // 1 .. kMaxBands
+    int32_t channels;                 // 1 or 4
+    int32_t n_win;                    // 0 .. kMaxReduceWindows
+    int32_t n_lev;                    // 0 .. kMaxReduceLevels
+    int32_t win[2 * kMaxReduceWindows];       // [lo, hi) bin pairs
+    uint32_t levels[kMaxReduceLevels];        // fractions in units of 2^-32
+};
+
 #if defined(__HIPCC__)
 // Every kernel argument as a scalar of its OWN (round 6).  The compiler fetches the 720-byte argument block in tuples of 8 and 16 SGPRs and,
 // short of SGPRs in these kernels, spills and reloads them AS tuples: a block that needs the rays' pointer reloaded sixteen registers to get

@@ -327,6 +327,74 @@ int emit_source(const Scene& s, const HipApi* H, int64_t n, int64_t first_ray, v
     return launch(H, s.module->emit_source, (unsigned)((n + 255) / 256), 256, 0, st, args);
 }
 
+// ---- the reduction of a histogram (include/hare_hip.h, "receivers", "Reduction"; the kernel: reduce.hip)
+int reduce_check_spec(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const ReduceSpec& r)
+{
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    if (K < 1 || K > kMaxMapReceivers) return bad("K out of range (1 .. 65 536)");
+    if (n_bins < 1) return bad("n_bins must be >= 1");
+    if (B < 1 || B > kMaxBands) return bad("bands out of range (1 .. 8)");
+    if (channels != 1 && channels != 4) return bad("channels must be 1 or 4");
+    if ((unsigned __int128)K * (unsigned)n_bins * (unsigned)B * (unsigned)channels > ((size_t)1 << 27)) return bad("K x n_bins x bands x channels exceeds 2^27");
+    if (r.n_win < 0 || r.n_win > kMaxReduceWindows) return bad("n_win out of range (0 .. 16)");
+    if (r.n_lev < 0 || r.n_lev > kMaxReduceLevels) return bad("n_lev out of range (0 .. 32)");
+    if (r.n_win + r.n_lev < 1) return bad("nothing to compute: n_win and n_lev are both 0");
+    if ((r.n_win > 0 && !r.win) || (r.n_lev > 0 && !r.levels)) return bad("null win / levels");
+    for (int32_t j = 0; j < r.n_win; ++j)
+        if (r.win[2 * j] < 0 || r.win[2 * j] > r.win[2 * j + 1] || r.win[2 * j + 1] > n_bins)
+            return bad("window " + std::to_string(j) + " is not 0 <= lo <= hi <= n_bins");
+    return HARE_OK;
+}
+
+int reduce_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist,
+                   const void* d_weight, const ReduceSpec& r, void* d_sums, void* d_cross, hipStream_t st)
+{
+    if (!s.module || !s.module->hist_reduce) {
+        set_error("hare_hist_reduce missing from code object");
+        return HARE_E_STATE;
+    }
+    ReduceArgs a;
+    memset(&a, 0, sizeof a);
+    a.hist = (const unsigned long long*)d_hist;
+    a.weight = (const uint32_t*)d_weight;
+    a.sums = (unsigned long long*)d_sums;
+    a.cross = (int32_t*)d_cross;
+    a.n_bins = n_bins;
+    a.bands = B;
+    a.channels = channels;
+    a.n_win = r.n_win;
+    a.n_lev = r.n_lev;
+    for (int32_t j = 0; j < 2 * r.n_win; ++j) a.win[j] = r.win[j];
+    for (int32_t l = 0; l < r.n_lev; ++l) a.levels[l] = r.levels[l];
+    void* args[] = {&a};
+    return launch(H, s.module->hist_reduce, (unsigned)K, 256, 0, st, args);          // a workgroup per receiver
+}
+
+// what hare_hist_reduce_device and hare_hist_reduce check of their buffers, device or host: none null that is used, no output on another buffer
+static int reduce_check_buffers(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const void* hist, const void* weight,
+                                const ReduceSpec& r, const void* sums, const void* cross)
+{
+    if (!hist || (r.n_win > 0 && !sums) || (r.n_lev > 0 && !cross)) {
+        set_error(std::string(who) + ": null histogram / sums / crossings");
+        return HARE_E_INVALID;
+    }
+    const size_t KB = (size_t)K * (size_t)B;
+    const struct { const void* p; size_t bytes; } bufs[] = {{sums, KB * (size_t)r.n_win * 4 * sizeof(uint64_t)},
+                                                            {cross, KB * (size_t)r.n_lev * sizeof(int32_t)},
+                                                            {hist, KB * (size_t)n_bins * (size_t)channels * sizeof(uint64_t)},
+                                                            {weight, (size_t)n_bins * (size_t)B * sizeof(uint32_t)}};
+    for (size_t x = 0; x < 2; ++x)
+        for (size_t y = x + 1; y < 4; ++y)
+            if (ranges_overlap(bufs[x].p, bufs[x].bytes, bufs[y].p, bufs[y].bytes)) {
+                set_error(std::string(who) + ": sums and crossings must not overlap each other, the histogram or the weights");
+                return HARE_E_INVALID;
+            }
+    return HARE_OK;
+}
+
 // hare_scene_set_absorption / _scattering behind their own checks of top_index and B: P x B coefficients in [0, 1] become Model[top]'s
 // table `mine` (`name` in the messages), with the B of the topology's other table where it has one
 static int set_band_table(Scene& s, const char* who, const char* name, std::vector<Scene::BandTable>& mine, const std::vector<Scene::BandTable>& other,
@@ -662,6 +730,81 @@ int hare_emit_device(hare_scene* s, int64_t n, int64_t first_ray, void* d_rays, 
     }
     if (int rc = source_ready(*s, H, "hare_emit_device")) return rc;
     return emit_source(*s, H, n, first_ray, d_rays, d_state, (hipStream_t)stream);
+    GUARD_END
+}
+
+int hare_hist_reduce_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
+                            int32_t n_win, const int32_t* win, int32_t n_lev, const uint32_t* levels, void* d_sums, void* d_cross, void* stream)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    ReduceSpec r;
+    r.n_win = n_win;
+    r.win = win;
+    r.n_lev = n_lev;
+    r.levels = levels;
+    if (int rc = reduce_check_spec("hare_hist_reduce_device", K, n_bins, B, channels, r)) return rc;
+    if (int rc = reduce_check_buffers("hare_hist_reduce_device", K, n_bins, B, channels, d_hist, d_weight, r, d_sums, d_cross)) return rc;
+    GUARD_BEGIN
+    const HipApi* H = api_or_err();
+    if (!H) return HARE_E_NODEVICE;
+    DeviceGuard dev_guard(H, s->device);
+    if (!s->module) {
+        int rc = ensure_device(*s, H);
+        if (rc) return rc;
+    }
+    return reduce_enqueue(*s, H, K, n_bins, B, channels, d_hist, d_weight, r, d_sums, d_cross, (hipStream_t)stream);
+    GUARD_END
+}
+
+int hare_hist_reduce(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t* hist, const uint32_t* weight,
+                     int32_t n_win, const int32_t* win, int32_t n_lev, const uint32_t* levels, uint64_t* sums, int32_t* cross)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    ReduceSpec r;
+    r.weight = weight;
+    r.n_win = n_win;
+    r.win = win;
+    r.n_lev = n_lev;
+    r.levels = levels;
+    if (int rc = reduce_check_spec("hare_hist_reduce", K, n_bins, B, channels, r)) return rc;
+    if (int rc = reduce_check_buffers("hare_hist_reduce", K, n_bins, B, channels, hist, weight, r, sums, cross)) return rc;
+    GUARD_BEGIN
+    const HipApi* H = api_or_err();
+    if (!H) return HARE_E_NODEVICE;
+    DeviceGuard dev_guard(H, s->device);
+    if (!s->module) {
+        int rc = ensure_device(*s, H);
+        if (rc) return rc;
+    }
+    // one device block: histogram, sums, crossings, weights (each from a 16-byte boundary); up, reduce, down, one synchronisation
+    const size_t KB = (size_t)K * (size_t)B;
+    const size_t hist_bytes = KB * (size_t)n_bins * (size_t)channels * sizeof(uint64_t), sums_bytes = KB * (size_t)n_win * 4 * sizeof(uint64_t);
+    const size_t cross_bytes = (KB * (size_t)n_lev * sizeof(int32_t) + 15) & ~(size_t)15, weight_bytes = (size_t)n_bins * (size_t)B * sizeof(uint32_t);
+    void* block = nullptr;
+    HIP_TRY(H->Malloc(&block, hist_bytes + sums_bytes + cross_bytes + weight_bytes + 16));
+    char* const d_hist = (char*)block;
+    char* const d_sums = d_hist + hist_bytes;
+    char* const d_cross = d_sums + sums_bytes;
+    char* const d_weight = d_cross + cross_bytes;
+    auto run = [&]() -> int {
+        HIP_TRY(H->MemcpyAsync(d_hist, hist, hist_bytes, hipMemcpyHostToDevice, nullptr));
+        if (weight) HIP_TRY(H->MemcpyAsync(d_weight, weight, weight_bytes, hipMemcpyHostToDevice, nullptr));
+        if (int rc = reduce_enqueue(*s, H, K, n_bins, B, channels, d_hist, weight ? d_weight : nullptr, r, d_sums, d_cross, nullptr)) return rc;
+        if (n_win > 0) HIP_TRY(H->MemcpyAsync(sums, d_sums, sums_bytes, hipMemcpyDeviceToHost, nullptr));
+        if (n_lev > 0) HIP_TRY(H->MemcpyAsync(cross, d_cross, KB * (size_t)n_lev * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(H->StreamSynchronize(nullptr));
+        return HARE_OK;
+    };
+    const int rc = run();
+    if (rc != HARE_OK) (void)H->StreamSynchronize(nullptr);      // copies may still be in flight
+    dev_free(H, block);
+    return rc;
     GUARD_END
 }
 

@@ -128,6 +128,7 @@ struct DeviceModule {
     // receive[3], receive[4]: hare_receive_reflect_map / hare_receive_scatter_map (a scene with a receiver map)
     hipFunction_t receive[5][2] = {}, rain_step[2] = {};
     hipFunction_t emit_source = nullptr;                                   // source.hip
+    hipFunction_t hist_reduce = nullptr;                                   // reduce.hip
     hipFunction_t voxel_occl_tri = nullptr, voxel_occl_quad = nullptr, voxel_occl_tri_g = nullptr, voxel_occl_quad_g = nullptr, octree_occl = nullptr, octree_occl_any = nullptr;
     hipFunction_t events_pack_slim = nullptr;
     hipFunction_t block_occ = nullptr;                                     // build_kernels.hip: hare_block_occ
@@ -251,7 +252,8 @@ struct Scene {
         void* state = nullptr;          // hare_receive_batch: (1 + B) x n doubles, the histogram and the detections
         void* hist = nullptr;
         void* rain = nullptr;           // hare_receive_batch with HARE_RECEIVE_DIFFUSE_RAIN: the loop's work array with the rain's scratch
-        size_t state_cap = 0, hist_cap = 0, rain_cap = 0;     // bytes
+        void* red = nullptr;            // hare_receive_*_reduced: the sums, the crossings and the weights of hare_hist_reduce
+        size_t state_cap = 0, hist_cap = 0, rain_cap = 0, red_cap = 0;     // bytes
         int64_t cap = 0;
         int32_t ctr_cap = 0;
         hipStream_t copy_st = nullptr;
@@ -403,6 +405,19 @@ int receive_ready(Scene& s, const HipApi* H, const char* who);
 int source_check_range(const char* who, int64_t n, int64_t first_ray);
 int source_ready(Scene& s, const HipApi* H, const char* who);
 int emit_source(const Scene& s, const HipApi* H, int64_t n, int64_t first_ray, void* d_rays, void* d_state, hipStream_t st);
+// The reduction of a receive histogram (receive.cpp; include/hare_hip.h, "receivers", "Reduction").  ReduceSpec: what the caller asks for,
+// host pointers (weight: n_bins x B, nullable).  reduce_check_spec: the checks that need no buffer (HARE_E_INVALID); reduce_enqueue:
+// hare_hist_reduce on the stream, device buffers, win and levels read here
+struct ReduceSpec {
+    const uint32_t* weight = nullptr;
+    int32_t n_win = 0;
+    const int32_t* win = nullptr;
+    int32_t n_lev = 0;
+    const uint32_t* levels = nullptr;
+};
+int reduce_check_spec(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const ReduceSpec& r);
+int reduce_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist,
+                   const void* d_weight, const ReduceSpec& r, void* d_sums, void* d_cross, hipStream_t st);
 
 // device plumbing (device_scene.cpp) shared with api.cpp, launch.cpp and build_gpu.cpp
 const HipApi* api_or_err();

@@ -162,6 +162,51 @@ def _result_array(out, shape, dtype):
     return out
 
 
+def decay_levels(dB_list):
+    """The levels of a reduction (include/hare_hip.h, "receivers", "Reduction") from decibels <= 0: uint32 fractions in units of 2^-32,
+    min(2^32 - 1, floor(10^(dB / 10) * 2^32)) -- -5 dB is floor(10^-0.5 * 2^32).  A host convenience that produces data: whatever uint32
+    values the caller passes are the definition's f_l."""
+    dB = np.asarray(dB_list, np.float64).reshape(-1)
+    if not (np.isfinite(dB).all() and (dB <= 0).all()):
+        raise ValueError("levels are finite decibels <= 0")
+    return np.minimum(np.floor(10.0 ** (dB / 10.0) * 4294967296.0), 4294967295.0).astype(np.uint32)
+
+
+def air_weights(m, bin_len: float, n_bins: int):
+    """The weights of a reduction for air absorption: m [B], the energy attenuation per unit of path length in each band; returns uint32
+    [n_bins, B] in units of 2^-32, min(2^32 - 1, floor(exp(-m_b * (i + 0.5) * bin_len) * 2^32)): the attenuation at the middle of bin i.  A
+    host convenience that produces data, like decay_levels."""
+    m = np.asarray(m, np.float64).reshape(-1)
+    if not (np.isfinite(m).all() and (m >= 0).all()):
+        raise ValueError("attenuation coefficients are finite and >= 0")
+    mid = (np.arange(int(n_bins), dtype=np.float64) + 0.5) * float(bin_len)
+    return np.minimum(np.floor(np.exp(-m[None, :] * mid[:, None]) * 4294967296.0), 4294967295.0).astype(np.uint32)
+
+
+def sums_to_float(sums):
+    """The sums of a reduction [..., 4] (S0 lo, S0 hi, S1 lo, S1 hi; uint64) as float64 (S0, S1): rounded, for the ratios a caller forms."""
+    s = np.asarray(sums).astype(np.float64)
+    return s[..., 0] + s[..., 1] * 2.0 ** 64, s[..., 2] + s[..., 3] * 2.0 ** 64
+
+
+def _reduce_spec(reduce, n_bins: int, B: int):
+    """reduce = dict(windows=[(lo, hi), ...] or None, levels=uint32 array or None, weight=uint32 [n_bins, B] or None), checked for shape
+    only (the library checks the values): (weight, n_win, win, n_lev, levels), arrays or None."""
+    unknown = set(reduce) - {"windows", "levels", "weight"}
+    if unknown:
+        raise ValueError("reduce: unknown keys %s" % sorted(unknown))
+    win = reduce.get("windows")
+    win = None if win is None else np.ascontiguousarray(win, np.int32).reshape(-1, 2)
+    lev = reduce.get("levels")
+    lev = None if lev is None else np.ascontiguousarray(lev, np.uint32).reshape(-1)
+    w = reduce.get("weight")
+    if w is not None:
+        w = np.ascontiguousarray(w, np.uint32)
+        if w.shape != (int(n_bins), int(B)):
+            raise ValueError("weight must be uint32 [n_bins, B] = [%d, %d]" % (n_bins, B))
+    return w, 0 if win is None else win.shape[0], win, 0 if lev is None else lev.shape[0], lev
+
+
 class Spatial_Partition:
     """Hare.Geometry.Spatial_Partition (Spatial_Partition.cs:27-35) over a native scene."""
 
@@ -461,6 +506,14 @@ class Spatial_Partition:
         return Spatial_Partition._receive_source([self], n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain, directional,
                                                  time_limit)
 
+    def Receive_source_reduced(self, n: int, bounces: int, n_bins: int, bin_len: float, windows=None, levels=None, weight=None,
+                               first_ray: int = 0, frac_bits: int = 40, top_index: int = 0, directional: bool = False,
+                               time_limit: bool = False):
+        """hare_receive_source_reduced: Receive_source with the histogram kept on the device and reduced there, as in
+        Receive_batch_reduced; returns what that returns."""
+        return Spatial_Partition._receive_source([self], n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, None, False, directional,
+                                                 time_limit, dict(windows=windows, levels=levels, weight=weight))
+
     @staticmethod
     def Receive_source_sharded(partitions, n: int, bounces: int, n_bins: int, bin_len: float, first_ray: int = 0, frac_bits: int = 40,
                                top_index: int = 0, out=None, rain: bool = False, directional: bool = False, time_limit: bool = False):
@@ -470,7 +523,7 @@ class Spatial_Partition:
                                                  directional, time_limit)
 
     @staticmethod
-    def _receive_source(parts, n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain, directional, time_limit):
+    def _receive_source(parts, n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain, directional, time_limit, reduce=None):
         if not parts or any(p._kind != parts[0]._kind for p in parts):
             raise ValueError("need one or more partitions of the same kind")
         n = int(n)
@@ -478,12 +531,19 @@ class Spatial_Partition:
             raise ValueError("n must be >= 0")
         shape = parts[0]._receive_shape(top_index, n_bins, bool(directional))
         K, nb, B = shape[:3]
-        hist = _result_array(out, (max(K, 0),) + shape[1:], np.uint64)
         det = np.zeros((max(K, 0), 2), np.uint64)
         state_out = np.empty((1 + B, n), np.float64)
         ctr = capi.Counters()
         flags = ((capi.RECEIVE_DIFFUSE_RAIN if rain else 0) | (capi.RECEIVE_DIRECTIONAL if directional else 0) |
                  (capi.RECEIVE_TIME_LIMIT if time_limit else 0))
+        if reduce is not None:
+            w, n_win, win, n_lev, lev = _reduce_spec(reduce, nb, B)
+            sums, cross = np.zeros((max(K, 0), B, n_win, 4), np.uint64), np.zeros((max(K, 0), B, n_lev), np.int32)
+            check(lib.hare_receive_source_reduced(parts[0]._h, parts[0]._kind, int(top_index), n, int(first_ray), int(bounces), flags, nb,
+                                                  float(bin_len), int(frac_bits), ptr(state_out), ptr(w), n_win, ptr(win), n_lev, ptr(lev),
+                                                  ptr(sums), ptr(cross), ptr(det), C.addressof(ctr)))
+            return sums, cross, det, state_out, ctr.as_dict()
+        hist = _result_array(out, (max(K, 0),) + shape[1:], np.uint64)
         if len(parts) == 1:
             rc = lib.hare_receive_source(parts[0]._h, parts[0]._kind, int(top_index), n, int(first_ray), int(bounces), flags, nb, float(bin_len),
                                          int(frac_bits), ptr(state_out), ptr(hist), ptr(det), C.addressof(ctr))
@@ -525,6 +585,16 @@ class Spatial_Partition:
         return Spatial_Partition._receive([self], rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1,
                                           poly_origin2, out, rain, directional, time_limit)
 
+    def Receive_batch_reduced(self, rays, bounces: int, n_bins: int, bin_len: float, windows=None, levels=None, weight=None, energy=None,
+                              frac_bits: int = 40, top_index: int = 0, poly_origin1=None, poly_origin2=None, directional: bool = False,
+                              time_limit: bool = False):
+        """hare_receive_batch_reduced (include/hare_hip.h, "receivers", "Reduction"): Receive_batch with the histogram kept on the device
+        and reduced there.  windows: [(lo, hi), ...] bin ranges; levels: uint32 fractions (decay_levels); weight: uint32 [n_bins, B]
+        (air_weights) or None.  Returns (sums [K, B, n_win, 4] uint64 -- S0 lo, S0 hi, S1 lo, S1 hi --, cross [K, B, n_lev] int32,
+        detections, final state, counters): sums and cross are hist_reduce of the histogram Receive_batch returns."""
+        return Spatial_Partition._receive([self], rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1, poly_origin2,
+                                          None, False, directional, time_limit, dict(windows=windows, levels=levels, weight=weight))
+
     @staticmethod
     def Receive_batch_sharded(partitions, rays, bounces: int, n_bins: int, bin_len: float, energy=None, frac_bits: int = 40,
                               top_index: int = 0, poly_origin1=None, poly_origin2=None, out=None, rain: bool = False,
@@ -536,7 +606,7 @@ class Spatial_Partition:
 
     @staticmethod
     def _receive(parts, rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1, poly_origin2, out, rain=False, directional=False,
-                 time_limit=False):
+                 time_limit=False, reduce=None):
         if not parts or any(p._kind != parts[0]._kind for p in parts):
             raise ValueError("need one or more partitions of the same kind")
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
@@ -553,12 +623,19 @@ class Spatial_Partition:
             state_in = np.ascontiguousarray(energy, np.float64)
             if state_in.shape != (1 + B, n):
                 raise ValueError("energy must be the state [1 + B, n] = [%d, %d]" % (1 + B, n))
-        hist = _result_array(out, (max(K, 0),) + shape[1:], np.uint64)
         det = np.zeros((max(K, 0), 2), np.uint64)
         state_out = np.empty((1 + B, n), np.float64)
         ctr = capi.Counters()
         flags = ((capi.RECEIVE_DIFFUSE_RAIN if rain else 0) | (capi.RECEIVE_DIRECTIONAL if directional else 0) |
                  (capi.RECEIVE_TIME_LIMIT if time_limit else 0))
+        if reduce is not None:
+            w, n_win, win, n_lev, lev = _reduce_spec(reduce, nb, B)
+            sums, cross = np.zeros((max(K, 0), B, n_win, 4), np.uint64), np.zeros((max(K, 0), B, n_lev), np.int32)
+            check(lib.hare_receive_batch_reduced(parts[0]._h, parts[0]._kind, int(top_index), n, ptr(rays), ptr(e1), ptr(e2), int(bounces), flags,
+                                                 nb, float(bin_len), int(frac_bits), ptr(state_in), ptr(state_out), ptr(w), n_win, ptr(win),
+                                                 n_lev, ptr(lev), ptr(sums), ptr(cross), ptr(det), C.addressof(ctr)))
+            return sums, cross, det, state_out, ctr.as_dict()
+        hist = _result_array(out, (max(K, 0),) + shape[1:], np.uint64)
         if len(parts) == 1:
             rc = lib.hare_receive_batch(parts[0]._h, parts[0]._kind, int(top_index), n, ptr(rays), ptr(e1), ptr(e2), int(bounces), flags, nb,
                                         float(bin_len), int(frac_bits), ptr(state_in), ptr(state_out), ptr(hist), ptr(det), C.addressof(ctr))
@@ -569,6 +646,30 @@ class Spatial_Partition:
                                                 ptr(hist), ptr(det), C.addressof(ctr))
         check(rc)
         return hist, hist.astype(np.float64) * 2.0 ** -int(frac_bits), det, state_out, ctr.as_dict()
+
+    def hist_reduce(self, hist, windows=None, levels=None, weight=None):
+        """hare_hist_reduce: a histogram [K, n_bins, B] (or [K, n_bins, B, 4], directional: channel 0 is read) of uint64, as the receive
+        calls return it, reduced on this partition's device (include/hare_hip.h, "receivers", "Reduction").  windows: [(lo, hi), ...] bin
+        ranges; levels: uint32 fractions (decay_levels); weight: uint32 [n_bins, B] (air_weights) or None.  Returns (sums [K, B, n_win, 4]
+        uint64 -- S0 lo, S0 hi, S1 lo, S1 hi --, cross [K, B, n_lev] int32)."""
+        hist = np.ascontiguousarray(hist, np.uint64)
+        if hist.ndim not in (3, 4) or (hist.ndim == 4 and hist.shape[3] != 4):
+            raise ValueError("hist must be uint64 [K, n_bins, B] or [K, n_bins, B, 4]")
+        K, nb, B = hist.shape[:3]
+        w, n_win, win, n_lev, lev = _reduce_spec(dict(windows=windows, levels=levels, weight=weight), nb, B)
+        sums, cross = np.zeros((K, B, n_win, 4), np.uint64), np.zeros((K, B, n_lev), np.int32)
+        check(lib.hare_hist_reduce(self._h, K, nb, B, 4 if hist.ndim == 4 else 1, ptr(hist), ptr(w), n_win, ptr(win), n_lev, ptr(lev),
+                                   ptr(sums), ptr(cross)))
+        return sums, cross
+
+    def hist_reduce_device(self, K: int, n_bins: int, B: int, channels: int, d_hist: int, d_sums: int, d_cross: int, windows=None,
+                           levels=None, d_weight: int = 0, stream: int = 0):
+        """hare_hist_reduce_device on raw device addresses + a hipStream_t: d_hist as receive_device accumulates it, d_sums (K x B x n_win
+        x 4 uint64) and d_cross (K x B x n_lev int32) written, d_weight (n_bins x B uint32) or 0.  windows and levels are host data, read
+        at the call.  Stream-ordered: no allocation, no free, no wait."""
+        _, n_win, win, n_lev, lev = _reduce_spec(dict(windows=windows, levels=levels), n_bins, B)
+        check(lib.hare_hist_reduce_device(self._h, int(K), int(n_bins), int(B), int(channels), d_hist or None, d_weight or None, n_win,
+                                          ptr(win), n_lev, ptr(lev), d_sums or None, d_cross or None, stream or None))
 
     @staticmethod
     def receive_work_bytes(n: int, rain: bool = False) -> int:

@@ -662,6 +662,36 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * HARE_RECEIVE_DIRECTIONAL, HARE_RECEIVE_TIME_LIMIT, the floor and roulette, scattering, every receive call -- works as without a map;
  * the histogram cap (K x n_bins x B, x 4 with channels, <= 2^27 words) stays.  The sharded calls refuse scenes whose maps differ.
  *
+ * Reduction (hare_hist_reduce_device, hare_hist_reduce, hare_receive_batch_reduced, hare_receive_source_reduced).  What a map's user reads
+ * from a histogram is a handful of numbers per receiver and band; the reduction forms them on the device, where the histogram lies, in
+ * integer arithmetic only -- a function of the inputs, bit for bit, like the histogram itself.  Inputs: a histogram laid out as the
+ * receive calls write it, K receivers x n_bins bins x B bands, with `channels` 1 or 4 words per entry (4: HARE_RECEIVE_DIRECTIONAL's; the
+ * word of channel 0, W, is the one read):
+ *
+ *   h(k, i, b) = hist[((k * n_bins + i) * B + b) * channels]                                             (uint64)
+ *   g(k, i, b) = weight ? floor(h * weight[i * B + b] / 2^32) : h        weight: n_bins x B uint32 in units of 2^-32, or NULL
+ *
+ * The product is 64 x 32 bits shifted right by 32 and fits uint64; with NULL g is h exactly (a weight cannot express 1.0).  The weights
+ * are where air absorption goes: it depends on the distance only, that is on the bin and the band.
+ * Windows: n_win (0 .. 16) bin ranges [lo_j, hi_j) = [win[2 j], win[2 j + 1]) with 0 <= lo_j <= hi_j <= n_bins; an empty window is legal.
+ * Levels: n_lev (0 .. 32) fractions f_l, uint32 in units of 2^-32 (-5 dB is floor(10^-0.5 * 2^32)).  n_win + n_lev >= 1.
+ * Outputs, for every receiver k and band b; every sum is an exact unsigned integer of 128 bits, returned as (lo, hi) uint64 pairs, and
+ * nothing wraps (2^27 words below 2^64 stay below 2^91; with the bin factor below 2^122):
+ *
+ *   sums[((k * B + b) * n_win + j) * 4 + 0 .. 3] = S0_lo, S0_hi, S1_lo, S1_hi
+ *       S0 = sum over i in [lo_j, hi_j) of g(k, i, b);   S1 = sum over the same i of i * g(k, i, b)
+ *   cross[(k * B + b) * n_lev + l]  (int32):  with T = sum over all i of g, P(i) = sum over i' < i of g and R(i) = T - P(i), the
+ *       smallest i in 0 .. n_bins with R(i) * 2^32 <= T * f_l, compared as 128-bit integers.  R(n_bins) = 0, so it always exists;
+ *       T = 0 gives 0; f_l = 0 gives the first bin from which the histogram is empty
+ *
+ * What the caller does with them.  Level (G, SPL) and the clarity ratios (C50, C80, D50) are quotients of S0 of two windows; the centre
+ * time is S1 / S0, a bin index, times bin_len; decay times (EDT, T20, T30) come from pairs of crossings of the backward-integrated decay
+ * R, or from a regression over up to 32 of them -- ISO 3382's least-squares fit is the caller's, on the crossings; the resolution of a
+ * crossing is one bin.  frac_bits cancels in every ratio.
+ * One workgroup reduces one receiver (K up to 65 536 of them); K = 1 with a huge n_bins therefore runs on one workgroup: a host-sized
+ * problem, and not what the call is for.  There are no sharded variants: a crossing is not additive over shards, and summing device
+ * histograms across GPUs is not part of this call -- reduce the histogram the sharded receive call returns with hare_hist_reduce.
+ *
  * Setters: single-caller, like the build calls.  They validate, keep a host copy, and upload it when a device is present (as a build
  * pushes its partition; on a GPU-less host the copy goes up with the first receive call).  No receive call allocates for them.
  *   hare_scene_set_receivers    replaces the receivers: centers K x 3, radii K.  HARE_E_INVALID for K outside 1..256, a non-finite
@@ -744,6 +774,34 @@ HARE_API int hare_receive_source(hare_scene *s, int32_t kind, int32_t top_index,
 HARE_API int hare_receive_source_sharded(hare_scene *const *scenes, int32_t n_scenes, int32_t kind, int32_t top_index, int64_t n,
                                          int64_t first_ray, int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len,
                                          int32_t frac_bits, double *state_out, uint64_t *hist, uint64_t *detections, hare_counters *ctr);
+
+/* The reduction of a histogram ("receivers", "Reduction" above) on DEVICE buffers: one launch, stream-ordered like hare_shoot_device -- no
+ * allocation, no free, no wait.  win (2 n_win) and levels (n_lev) are HOST arrays, read at the call (they travel as kernel arguments);
+ * d_weight nullable; d_sums (K x B x n_win x 4 uint64; unused when n_win = 0) and d_cross (K x B x n_lev int32; unused when n_lev = 0) are
+ * WRITTEN, every word once.  Checked before anything runs (HARE_E_INVALID): 1 <= K <= 65 536, n_bins >= 1, 1 <= B <= 8, channels 1 or 4,
+ * K x n_bins x B x channels <= 2^27, 0 <= n_win <= 16, 0 <= n_lev <= 32 and not both 0, every window 0 <= lo <= hi <= n_bins, null
+ * buffers, and sums or crossings overlapping each other, the histogram or the weights.  Then HARE_E_NODEVICE, then HARE_E_STATE.  The
+ * scene names the device; its geometry is not read. */
+HARE_API int hare_hist_reduce_device(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void *d_hist,
+                                     const void *d_weight /* nullable */, int32_t n_win, const int32_t *win /* host */, int32_t n_lev,
+                                     const uint32_t *levels /* host */, void *d_sums, void *d_cross, void *stream);
+/* The same from host buffers: upload, reduce, download, one synchronisation. */
+HARE_API int hare_hist_reduce(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t *hist,
+                              const uint32_t *weight /* nullable */, int32_t n_win, const int32_t *win, int32_t n_lev,
+                              const uint32_t *levels, uint64_t *sums, int32_t *cross);
+/* hare_receive_batch / hare_receive_source with `hist` replaced by the reduction's arguments: the loop runs as in the parent call, the
+ * histogram stays on the device, the reduction is enqueued behind the last cast on the same stream, and sums, crossings, detections,
+ * state and counters come down -- never the histogram.  K and B are the scene's; channels is 4 with HARE_RECEIVE_DIRECTIONAL, else 1.
+ * sums and cross are what hare_hist_reduce gives on the histogram the parent call returns.  Checks: the parent's, then the reduction's. */
+HARE_API int hare_receive_batch_reduced(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, const hare_ray *rays,
+                                        const int32_t *excl1, const int32_t *excl2, int32_t bounces, uint32_t flags, int32_t n_bins,
+                                        double bin_len, int32_t frac_bits, const double *state_in, double *state_out,
+                                        const uint32_t *weight /* nullable */, int32_t n_win, const int32_t *win, int32_t n_lev,
+                                        const uint32_t *levels, uint64_t *sums, int32_t *cross, uint64_t *detections, hare_counters *ctr);
+HARE_API int hare_receive_source_reduced(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, int64_t first_ray, int32_t bounces,
+                                         uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits, double *state_out,
+                                         const uint32_t *weight /* nullable */, int32_t n_win, const int32_t *win, int32_t n_lev,
+                                         const uint32_t *levels, uint64_t *sums, int32_t *cross, uint64_t *detections, hare_counters *ctr);
 
 #ifdef __cplusplus
 }
