@@ -221,9 +221,11 @@ public:
         check(hare_scene_set_source(scene_, pos.data(), (int32_t)power.size(), power.data(), frame.empty() ? nullptr : frame.data(), R,
                                     R > 0 ? gain.data() : nullptr));
     }
+    // direct (HARE_RECEIVE_DIRECT; the header's "Direct sound"): the direct sound is one visibility-tested deposit per receiver, standing
+    // for the call's n rays, and cast 0 detects nothing.
     uint64_t ReceiveSource(int64_t n, int64_t first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
                            std::vector<uint64_t>& hist, std::vector<uint64_t>& detections, std::vector<double>* state_out = nullptr,
-                           bool rain = false, bool directional = false)
+                           bool rain = false, bool directional = false, bool direct = false)
     {
         if (n < 0) throw std::invalid_argument("ReceiveSource: n must be >= 0");
         const int64_t K = GetOption("receivers"), B = Bands(top_index);
@@ -232,9 +234,20 @@ public:
         if (state_out) state_out->assign((size_t)(1 + B) * (size_t)n, 0.0);
         hare_counters c{};
         check(hare_receive_source(scene_, kind_, top_index, n, first_ray, bounces,
-                                  (rain ? HARE_RECEIVE_DIFFUSE_RAIN : 0u) | (directional ? HARE_RECEIVE_DIRECTIONAL : 0u), n_bins, bin_len, frac_bits,
-                                  state_out ? state_out->data() : nullptr, hist.data(), detections.data(), &c));
+                                  (rain ? HARE_RECEIVE_DIFFUSE_RAIN : 0u) | (directional ? HARE_RECEIVE_DIRECTIONAL : 0u) |
+                                      (direct ? HARE_RECEIVE_DIRECT : 0u),
+                                  n_bins, bin_len, frac_bits, state_out ? state_out->data() : nullptr, hist.data(), detections.data(), &c));
         return c.hits;
+    }
+    // hare_direct_device on device pointers and a hipStream_t: the direct sound's deposit alone, for n_weight source rays, ACCUMULATED into
+    // d_hist (K x n_bins x B, x 4 with directional) and d_detections (2 K); d_work holds DirectWorkBytes(K) bytes.  Stream-ordered.  For a
+    // caller who runs the burst in chunks through hare_receive_device (on native()) with HARE_RECEIVE_DIRECT: one deposit for the whole count.
+    static int64_t DirectWorkBytes(int64_t K) { return HARE_DIRECT_WORK_BYTES(K); }
+    void DirectDevice(int top_index, int64_t n_weight, int n_bins, double bin_len, int frac_bits, void* d_work, void* d_hist, void* d_detections,
+                      bool directional = false, void* stream = nullptr)
+    {
+        check(hare_direct_device(scene_, kind_, top_index, n_weight, directional ? HARE_RECEIVE_DIRECTIONAL : 0u, n_bins, bin_len, frac_bits,
+                                 d_work, d_hist, d_detections, stream));
     }
     // the reduction of a histogram on the device (include/hare_hip.h, "receivers", "Reduction"): per receiver and band, the sums S0 = sum g
     // and S1 = sum i g over bin windows and the bins at which the backward-integrated decay crosses the levels.  What to compute:
@@ -297,7 +310,7 @@ public:
     }
     uint64_t ReceiveSourceReduced(int64_t n, int64_t first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
                                   const Reduction& r, std::vector<uint64_t>& sums, std::vector<int32_t>& cross, std::vector<uint64_t>& detections,
-                                  std::vector<double>* state_out = nullptr, bool directional = false)
+                                  std::vector<double>* state_out = nullptr, bool directional = false, bool direct = false)
     {
         if (n < 0) throw std::invalid_argument("ReceiveSourceReduced: n must be >= 0");
         const int64_t K = GetOption("receivers"), B = Bands(top_index);
@@ -307,7 +320,8 @@ public:
         detections.assign((size_t)(2 * K), 0);
         if (state_out) state_out->assign((size_t)(1 + B) * (size_t)n, 0.0);
         hare_counters c{};
-        check(hare_receive_source_reduced(scene_, kind_, top_index, n, first_ray, bounces, directional ? HARE_RECEIVE_DIRECTIONAL : 0u, n_bins,
+        check(hare_receive_source_reduced(scene_, kind_, top_index, n, first_ray, bounces,
+                                          (directional ? HARE_RECEIVE_DIRECTIONAL : 0u) | (direct ? HARE_RECEIVE_DIRECT : 0u), n_bins,
                                           bin_len, frac_bits, state_out ? state_out->data() : nullptr,
                                           r.weight.empty() ? nullptr : r.weight.data(), n_win, r.windows.data(), n_lev, r.levels.data(), sums.data(),
                                           cross.data(), detections.data(), &c));

@@ -107,6 +107,9 @@ namespace Hare
             // F is retired -- biased by design) and "receive_roulette" 1 (such a ray survives with probability ps = m / F and is then
             // divided by ps: every band's expected energy is kept).  The same values on every scene of a sharded call.
             public const uint HARE_RECEIVE_TIME_LIMIT = 512;
+            // hare_receive_source / _sharded / _reduced and hare_receive_device: the direct sound is one visibility-tested deposit per receiver
+            // and cast 0 detects nothing (include/hare_hip.h, "Direct sound"); the hare_receive_batch calls refuse it
+            public const uint HARE_RECEIVE_DIRECT = 1024;
 
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr hare_last_error();
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int hare_device_count(out int count);
@@ -263,6 +266,10 @@ namespace Hare
                                                                  int bounces, uint flags, int n_bins, double bin_len, int frac_bits,
                                                                  [Out] double[] state_out, [Out] ulong[] hist, [Out] ulong[] detections,
                                                                  out hare_counters ctr);
+            // the direct sound's deposit on device buffers (include/hare_hip.h, "receivers", "Direct sound"); d_work: 64 K + 256 bytes
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_direct_device(IntPtr scene, int kind, int top_index, long n_weight, uint flags, int n_bins, double bin_len,
+                                                        int frac_bits, IntPtr d_work, IntPtr d_hist, IntPtr d_detections, IntPtr stream);
             // the reduction of a histogram on the device (include/hare_hip.h, "receivers", "Reduction")
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_hist_reduce_device(IntPtr scene, int K, int n_bins, int B, int channels, IntPtr d_hist, IntPtr d_weight,

@@ -43,7 +43,7 @@ void free_bounce_buffers(const HipApi* H, Scene& s)
         Scene::BounceBuf& b = c.bounce;
         if (b.copy_st) { (void)H->StreamSynchronize(b.copy_st); (void)H->StreamDestroy(b.copy_st); b.copy_st = nullptr; }
         for (void** p : {&b.rays[0], &b.rays[1], &b.excl[0], &b.excl[1], &b.excl2, &b.idx[0], &b.idx[1], &b.ev[0], &b.ev[1], &b.full,
-                         &b.tiles, &b.ctr, &b.state, &b.hist, &b.rain, &b.red})
+                         &b.tiles, &b.ctr, &b.state, &b.hist, &b.rain, &b.red, &b.direct})
             dev_free(H, *p);
         b.cap = 0;
         b.ctr_cap = 0;
@@ -51,6 +51,7 @@ void free_bounce_buffers(const HipApi* H, Scene& s)
         b.hist_cap = 0;
         b.rain_cap = 0;
         b.red_cap = 0;
+        b.direct_cap = 0;
     }
 }
 
@@ -233,6 +234,7 @@ struct ReceiveJob {
     int64_t ray_base = 0;      // this shard's first ray in the whole batch (the scattering RNG's global ray index)
     uint32_t flags = 0;        // the call's HARE_RECEIVE_* bits
     bool from_source = false;  // hare_receive_source: rays and state come from hare_emit_source (rays from ray_base on), not from the caller
+    int64_t direct_weight = 0; // HARE_RECEIVE_DIRECT: > 0 in the ONE scene that deposits the direct sound, for the call's whole n (else 0)
     const char* who = "hare_receive_batch";
     // hare_receive_*_reduced: the histogram stays in BounceBuf::hist and hare_hist_reduce runs behind the last cast; sums and cross come
     // down in its place (hist is null)
@@ -284,6 +286,13 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
         HIP_TRY(H->Malloc(&b.red, sums_bytes + cross_bytes + weight_bytes));
         b.red_cap = sums_bytes + cross_bytes + weight_bytes;
     }
+    const size_t direct_bytes = job.direct_weight > 0 ? (size_t)HARE_DIRECT_WORK_BYTES(K) : 0;
+    if (direct_bytes > b.direct_cap) {
+        dev_free(H, b.direct);
+        b.direct_cap = 0;
+        HIP_TRY(H->Malloc(&b.direct, direct_bytes));
+        b.direct_cap = direct_bytes;
+    }
     if (!c.st[0]) HIP_TRY(H->StreamCreate(&c.st[0]));
     hipStream_t st = c.st[0];
     uint64_t* const d_hist = (uint64_t*)b.hist;
@@ -303,6 +312,9 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
     HIP_TRY(H->MemsetAsync(b.hist, 0, hist_bytes, st));
     HIP_TRY(H->MemsetAsync(b.ctr, 0, (size_t)bounces * sizeof(hare_counters), st));
     void* const work = rain ? b.rain : b.ev[1];         // b.ev[1] holds the loop's 2 n int32; with rain, a buffer of its own holds them and the rain's scratch
+    if (job.direct_weight > 0)      // the direct sound, once per call, ahead of cast 0 (whose receiver step the flag switches off)
+        if (int rc = direct_enqueue(s, H, kind, top, job.direct_weight, job.flags, job.n_bins, job.bin_len, job.frac_bits, b.direct, d_hist, d_det, st))
+            return rc;
     ReceivePlan plan;
     if (int rc = receive_plan(s, top, job.flags, n, job.n_bins, job.bin_len, job.frac_bits, d_state, d_hist, d_det, work,
                               job.state_in == nullptr && !job.from_source, job.ray_base, plan))
@@ -522,6 +534,10 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
         }
     hare_scene* const s0 = scenes[0];
     if (int rc = receive_check_args(who, *s0, flags, kind, top_index, n, bounces, n_bins, bin_len, frac_bits)) return rc;
+    if ((flags & HARE_RECEIVE_DIRECT) && !first_ray) {      // the caller's rays: the library cannot know them to be the source's
+        set_error(std::string(who) + ": HARE_RECEIVE_DIRECT needs the scene's source (hare_receive_source, hare_receive_device + hare_direct_device)");
+        return HARE_E_INVALID;
+    }
     if ((n > 0 && !rays && !first_ray) || (!hist && !red) || !detections) {
         set_error(std::string(who) + ": null rays, histogram or detections");
         return HARE_E_INVALID;
@@ -619,6 +635,8 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
         job.ray_base = (first_ray ? *first_ray : 0) + lo;
         job.flags = flags;
         job.from_source = first_ray != nullptr;
+        // the direct sound is deposited once, for the whole n: by the first scene whose shard holds a ray (scenes[0] whenever n >= G)
+        job.direct_weight = ((flags & HARE_RECEIVE_DIRECT) && hi > lo && lo == 0) ? n : 0;
         job.who = who;
         job.reduce = red;
         job.sums = sums;

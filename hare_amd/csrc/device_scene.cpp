@@ -131,6 +131,9 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_ob_fill", &m->ob_fill},
         {"hare_emit_source", &m->emit_source},
         {"hare_hist_reduce", &m->hist_reduce},
+        {"hare_direct_emit", &m->direct_emit},
+        {"hare_direct_deposit", &m->direct_deposit[0]},
+        {"hare_direct_deposit_dir", &m->direct_deposit[1]},
     };
     for (auto& t : table) {
         hipError_t e = H->ModuleGetFunction(t.fn, m->mod, t.name);

@@ -523,6 +523,7 @@ constexpr int kMaxMapCells = 1 << 21;
 constexpr int32_t kCutTime = 1;      // HARE_RECEIVE_TIME_LIMIT
 constexpr int32_t kCutFloor = 2;     // "receive_floor_bits" > 0
 constexpr int32_t kCutRoulette = 4;  // ... with "receive_roulette" 1
+constexpr int32_t kCutSkipDetect = 8; // HARE_RECEIVE_DIRECT, cast 0 only: no receiver step in this cast (the direct sound is deposited by hare_direct_deposit)
 
 // hare_rain_step (receive.hip): diffuse rain between the shoot and the receive kernel of a cast -- the deposit of receiver k_dep's
 // visibility query (its flags in `socc`) and the emission of receiver k_emit's.  Reads what hare_receive_scatter_rain reads before it
@@ -569,6 +570,31 @@ struct SourceArgs {
     double frame[9];           // M, row-major: the lookup is in l = M d
     int32_t bands;             // 1 .. kMaxBands
     int32_t res;               // R: 0 (no table) .. kMaxSourceRes
+};
+
+// hare_direct_emit / hare_direct_deposit[_dir] (direct.hip): the direct sound (include/hare_hip.h, "receivers", "Direct sound") -- a lane per
+// receiver.  The emission writes receiver k's shadow ray (origin: the source, direction: to the center, t_max 1.0; exclusion word -1, or -2
+// for a receiver the source lies inside: no traversal, not occluded); the flags-only occlusion kernels answer; the deposit adds the
+// visible receivers' words.  Position, power and frame by value, as in SourceArgs
+struct DirectArgs {
+    const double* rcv;         // n_rcv x 4: cx, cy, cz, r * r
+    const double* gain;        // the source's table (null iff res == 0)
+    unsigned long long* hist;  // n_rcv x n_bins x bands (x 4: hare_direct_deposit_dir), accumulated
+    unsigned long long* det;   // 2 n_rcv, accumulated
+    RayRec* srays;             // n_rcv shadow rays
+    double* stmax;             // n_rcv t_max (1.0)
+    int32_t* sexcl;            // n_rcv: -1 for an eligible receiver, -2 for the others
+    const int32_t* socc;       // n_rcv occlusion flags (the deposit reads them)
+    double pos[3];
+    double power[kMaxBands];
+    double frame[9];
+    double bin_len;
+    double scale;              // 2^frac_bits
+    double weight;             // W = (double)n_weight
+    int32_t n_rcv;
+    int32_t bands;
+    int32_t res;
+    int32_t n_bins;
 };
 
 // hare_hist_reduce (reduce.hip): a receive histogram reduced to window sums and decay-level crossings per receiver and band

@@ -1,7 +1,7 @@
 // receive.cpp -- receivers, absorption and scattering of a scene (hare_scene_set_receivers / _absorption / _scattering), the receive loop's plan
 // and its per-cast step (receive_plan, receive_step: what bounce_device_impl, launch.cpp, runs between its casts) and hare_receive_device
 // (include/hare_hip.h, "receivers"; the kernels: receive.hip); the point source (hare_scene_set_source, hare_emit_device; the kernel:
-// source.hip).  The host-buffer calls hare_receive_batch / _sharded and hare_receive_source / _sharded are in bounce.cpp, beside the loop
+// source.hip); the direct sound (direct_enqueue, hare_direct_device; the kernels: direct.hip).  The host-buffer calls hare_receive_batch / _sharded and hare_receive_source / _sharded are in bounce.cpp, beside the loop
 // they share with hare_bounce_batch.
 //
 // Harness-defined: the reference has no receivers (Pachyderm, its caller, detects them on the host per ray).
@@ -184,6 +184,7 @@ int receive_plan(const Scene& s, int32_t top, uint32_t flags, int64_t n, int32_t
     p.rain = receive_rains(s, top, flags);
     p.work = p.rain ? rain_work(d_work, n) : RainWork();
     ra.rain_flag = p.work.flag;
+    p.skip_cast0 = (flags & HARE_RECEIVE_DIRECT) != 0;
     return HARE_OK;
 }
 
@@ -234,6 +235,7 @@ int receive_step(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n
     ra.last = last_cast ? 1 : 0;
     ra.init_state = cast == 0 ? p.args.init_state : 0;      // the starting state is the first cast's business only
     ra.cast = cast;
+    if (p.skip_cast0 && cast == 0) ra.cut |= kCutSkipDetect;      // the direct sound is hare_direct_deposit's: calls without the flag pass today's bytes
     if (p.rain && !last_cast) {
         // diffuse rain (receive.hip: hare_rain_step): receiver k's query is emitted, answered by the flags-only occlusion kernel of this
         // partition, and deposited by the launch that emits k + 1's
@@ -325,6 +327,61 @@ int emit_source(const Scene& s, const HipApi* H, int64_t n, int64_t first_ray, v
     }
     void* args[] = {&a};
     return launch(H, s.module->emit_source, (unsigned)((n + 255) / 256), 256, 0, st, args);
+}
+
+// ---- the direct sound (include/hare_hip.h, "receivers", "Direct sound"; the kernels: direct.hip)
+// What hare_direct_device and the flag on the source calls check of their numbers (HARE_E_INVALID)
+static int direct_check_weight(const char* who, int64_t n_weight)
+{
+    if (n_weight < 1 || n_weight > ((int64_t)1 << 53)) {
+        set_error(std::string(who) + ": n_weight out of range (1 .. 2^53)");
+        return HARE_E_INVALID;
+    }
+    return HARE_OK;
+}
+
+// The scratch of a deposit: K shadow rays (48 B) from a 16-byte boundary, K t_max, K exclusion words, K occlusion flags: 64 K bytes and at
+// most 15 of padding, within HARE_DIRECT_WORK_BYTES(K)
+int direct_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                   int32_t frac_bits, void* d_work, void* d_hist, void* d_det, hipStream_t st)
+{
+    const Scene::Source& src = s.src;
+    const bool dir = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
+    if (!s.module || !s.module->direct_emit || !s.module->direct_deposit[dir]) {
+        set_error("hare_direct_emit / hare_direct_deposit missing from code object");
+        return HARE_E_STATE;
+    }
+    const int64_t K = (int64_t)(s.rcv.size() / 4);
+    DirectArgs a;
+    memset(&a, 0, sizeof a);
+    a.rcv = (const double*)(s.rmap.set ? s.rmap.d_rcv : s.d_rcv);
+    a.gain = src.R > 0 ? (const double*)src.d_gain : nullptr;
+    a.hist = (unsigned long long*)d_hist;
+    a.det = (unsigned long long*)d_det;
+    a.srays = (RayRec*)(((uintptr_t)d_work + 15u) & ~(uintptr_t)15u);
+    a.stmax = (double*)(a.srays + K);
+    a.sexcl = (int32_t*)(a.stmax + K);
+    int32_t* const occ = a.sexcl + K;
+    a.socc = occ;
+    memcpy(a.pos, src.pos, sizeof a.pos);
+    memcpy(a.power, src.power, sizeof a.power);
+    memcpy(a.frame, src.frame, sizeof a.frame);
+    a.bin_len = bin_len;
+    a.scale = ldexp(1.0, frac_bits);
+    a.weight = (double)n_weight;
+    a.n_rcv = (int32_t)K;
+    a.bands = src.B;
+    a.res = src.R;
+    a.n_bins = n_bins;
+    if (!a.rcv || (src.R > 0 && !a.gain)) {
+        set_error("direct sound: receivers or directivity table not on the device");
+        return HARE_E_STATE;
+    }
+    const unsigned grid = (unsigned)((K + 255) / 256);
+    void* args[] = {&a};
+    if (int rc = launch(H, s.module->direct_emit, grid, 256, 0, st, args)) return rc;
+    if (int rc = shoot_device_impl(s, H, kind, top, K, a.srays, a.sexcl, nullptr, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st, a.stmax, occ)) return rc;
+    return launch(H, s.module->direct_deposit[dir], grid, 256, 0, st, args);
 }
 
 // ---- the reduction of a histogram (include/hare_hip.h, "receivers", "Reduction"; the kernel: reduce.hip)
@@ -733,6 +790,50 @@ int hare_emit_device(hare_scene* s, int64_t n, int64_t first_ray, void* d_rays, 
     GUARD_END
 }
 
+int hare_direct_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                       int32_t frac_bits, void* d_work, void* d_hist, void* d_detections, void* stream)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    const char* const who = "hare_direct_device";
+    if (int rc = direct_check_weight(who, n_weight)) return rc;
+    flags &= HARE_RECEIVE_DIRECTIONAL;
+    if (int rc = receive_check_args(who, *s, flags, kind, top_index, 0, 1, n_bins, bin_len, frac_bits)) return rc;
+    if (s->src.set && s->src.B != scene_bands(*s, top_index)) {
+        set_error(std::string(who) + ": the source has " + std::to_string(s->src.B) + " bands, the topology " + std::to_string(scene_bands(*s, top_index)));
+        return HARE_E_INVALID;
+    }
+    if (!d_work || !d_hist || !d_detections) {
+        set_error(std::string(who) + ": null work array / histogram / detections");
+        return HARE_E_INVALID;
+    }
+    const size_t K = std::max<size_t>(1, s->rcv.size() / 4);
+    const struct { const void* p; size_t bytes; } bufs[] = {{d_work, (size_t)HARE_DIRECT_WORK_BYTES(K)},
+                                                            {d_hist, receive_hist_words(*s, top_index, n_bins, flags, 1) * sizeof(uint64_t)},
+                                                            {d_detections, K * 2 * sizeof(uint64_t)}};
+    for (size_t x = 0; x < 3; ++x)
+        for (size_t y = x + 1; y < 3; ++y)
+            if (ranges_overlap(bufs[x].p, bufs[x].bytes, bufs[y].p, bufs[y].bytes)) {
+                set_error(std::string(who) + ": work array, histogram and detections must not overlap");
+                return HARE_E_INVALID;
+            }
+    GUARD_BEGIN
+    const HipApi* H = api_or_err();
+    if (!H) return HARE_E_NODEVICE;
+    DeviceGuard dev_guard(H, s->device);
+    if (!s->module) {
+        int rc = ensure_device(*s, H);
+        if (rc) return rc;
+    }
+    if (int rc = source_ready(*s, H, who)) return rc;
+    if (int rc = upload_polys(*s, H)) return rc;
+    if (int rc = receive_ready(*s, H, who)) return rc;
+    return direct_enqueue(*s, H, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, d_work, d_hist, d_detections, (hipStream_t)stream);
+    GUARD_END
+}
+
 int hare_hist_reduce_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
                             int32_t n_win, const int32_t* win, int32_t n_lev, const uint32_t* levels, void* d_sums, void* d_cross, void* stream)
 {
@@ -817,6 +918,10 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
         return HARE_E_INVALID;
     }
     if (int rc = receive_check_args("hare_receive_device", *s, flags, kind, top_index, n, bounces, n_bins, bin_len, frac_bits)) return rc;
+    if ((flags & HARE_RECEIVE_DIRECT) && s->src.set && s->src.B != scene_bands(*s, top_index)) {
+        set_error("hare_receive_device: the source has " + std::to_string(s->src.B) + " bands, the topology " + std::to_string(scene_bands(*s, top_index)));
+        return HARE_E_INVALID;
+    }
     const size_t K = std::max<size_t>(1, s->rcv.size() / 4);
     const int32_t B = scene_bands(*s, top_index);
     const bool rain = (flags & HARE_RECEIVE_DIFFUSE_RAIN) != 0;
@@ -853,6 +958,8 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
     }
     if (int rc = upload_polys(*s, H)) return rc;
     if (int rc = receive_ready(*s, H, "hare_receive_device")) return rc;
+    if (flags & HARE_RECEIVE_DIRECT)      // suppression only, but of the SOURCE's direct sound: hare_direct_device deposits it
+        if (int rc = source_ready(*s, H, "hare_receive_device")) return rc;
     if (n == 0) return HARE_OK;
     ReceivePlan plan;
     if (int rc = receive_plan(*s, top_index, flags, n, n_bins, bin_len, frac_bits, d_state, d_hist, d_detections, d_work, false, 0, plan)) return rc;

@@ -277,7 +277,7 @@ static __device__ __forceinline__ void receive_body(const Args& a)
             r = a.rays[i];
             if (!a.init_state) L = a.state[i];
             const XEventRec& ei = a.ev[i];
-            map_receivers<DIR>(a, i, r, ei.hit ? ei.t : __builtin_inf(), L);
+            if (!(a.cut & kCutSkipDetect)) map_receivers<DIR>(a, i, r, ei.hit ? ei.t : __builtin_inf(), L);
         }
     }
     if (live) {
@@ -297,7 +297,7 @@ static __device__ __forceinline__ void receive_body(const Args& a)
     // ---- receivers
     if constexpr (!MAP) {                                                // the linear step; a map has taken its own, above
         const bool seen = live && !rained;
-        if (__ballot(seen) != 0ull) {
+        if (!(a.cut & kCutSkipDetect) && __ballot(seen) != 0ull) {      // kCutSkipDetect: cast 0 of a call with HARE_RECEIVE_DIRECT (uniform)
             const double t_end = (live && e.hit) ? e.t : __builtin_inf();
             const double nb = (double)a.n_bins;
             [[maybe_unused]] double ax = 0, ay = 0, az = 0;
@@ -444,7 +444,7 @@ static __device__ __forceinline__ void receive_body(const Args& a)
                     if (b < B && al) E[b] = E[b] * (1.0 - al[b]);              // no table: alpha = 0
             }
             const double Lp = e.hit ? L + e.t : L;
-            if (a.cut != 0 && scat) {                          // a.cut is uniform: a call without a rule pays this one scalar test
+            if ((a.cut & (kCutTime | kCutFloor)) != 0 && scat) {      // a.cut is uniform: a call without a rule pays this one scalar test
                 if ((a.cut & kCutTime) && Lp / a.bin_len >= (double)a.n_bins) {
                     cut = true;
                 } else if (a.cut & kCutFloor) {

@@ -129,6 +129,7 @@ struct DeviceModule {
     hipFunction_t receive[5][2] = {}, rain_step[2] = {};
     hipFunction_t emit_source = nullptr;                                   // source.hip
     hipFunction_t hist_reduce = nullptr;                                   // reduce.hip
+    hipFunction_t direct_emit = nullptr, direct_deposit[2] = {};           // direct.hip ([1]: the _dir form)
     hipFunction_t voxel_occl_tri = nullptr, voxel_occl_quad = nullptr, voxel_occl_tri_g = nullptr, voxel_occl_quad_g = nullptr, octree_occl = nullptr, octree_occl_any = nullptr;
     hipFunction_t events_pack_slim = nullptr;
     hipFunction_t block_occ = nullptr;                                     // build_kernels.hip: hare_block_occ
@@ -253,7 +254,8 @@ struct Scene {
         void* hist = nullptr;
         void* rain = nullptr;           // hare_receive_batch with HARE_RECEIVE_DIFFUSE_RAIN: the loop's work array with the rain's scratch
         void* red = nullptr;            // hare_receive_*_reduced: the sums, the crossings and the weights of hare_hist_reduce
-        size_t state_cap = 0, hist_cap = 0, rain_cap = 0, red_cap = 0;     // bytes
+        void* direct = nullptr;         // hare_receive_source* with HARE_RECEIVE_DIRECT: hare_direct_device's scratch, HARE_DIRECT_WORK_BYTES(K)
+        size_t state_cap = 0, hist_cap = 0, rain_cap = 0, red_cap = 0, direct_cap = 0;     // bytes
         int64_t cap = 0;
         int32_t ctr_cap = 0;
         hipStream_t copy_st = nullptr;
@@ -367,6 +369,7 @@ struct ReceivePlan {
     bool rain = false;          // HARE_RECEIVE_DIFFUSE_RAIN on a topology with a scattering table (args.sigma, args.rain_flag set)
     bool directional = false;   // HARE_RECEIVE_DIRECTIONAL: args.hist has four channels per word and the _dir kernels run
     bool map = false;           // the scene holds a receiver map: the _map kernels run (never with rain)
+    bool skip_cast0 = false;    // HARE_RECEIVE_DIRECT: cast 0 runs no receiver step (kCutSkipDetect in that cast's args.cut only)
 };
 inline int receive_form(const ReceivePlan& p)      // DeviceModule::receive's first index
 {
@@ -405,6 +408,11 @@ int receive_ready(Scene& s, const HipApi* H, const char* who);
 int source_check_range(const char* who, int64_t n, int64_t first_ray);
 int source_ready(Scene& s, const HipApi* H, const char* who);
 int emit_source(const Scene& s, const HipApi* H, int64_t n, int64_t first_ray, void* d_rays, void* d_state, hipStream_t st);
+// the direct sound (receive.cpp; include/hare_hip.h, "receivers", "Direct sound").  direct_enqueue: hare_direct_emit, the flags-only
+// occlusion query of the partition and hare_direct_deposit[_dir] on the stream, K lanes each; d_work: HARE_DIRECT_WORK_BYTES(K) of scratch.
+// Source and receivers must be on the device (source_ready, receive_ready)
+int direct_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                   int32_t frac_bits, void* d_work, void* d_hist, void* d_det, hipStream_t st);
 // The reduction of a receive histogram (receive.cpp; include/hare_hip.h, "receivers", "Reduction").  ReduceSpec: what the caller asks for,
 // host pointers (weight: n_bins x B, nullable).  reduce_check_spec: the checks that need no buffer (HARE_E_INVALID); reduce_enqueue:
 // hare_hist_reduce on the stream, device buffers, win and levels read here

@@ -499,31 +499,35 @@ class Spatial_Partition:
         check(lib.hare_emit_device(self._h, int(n), int(first_ray), d_rays or None, d_state or None, stream or None))
 
     def Receive_source(self, n: int, bounces: int, n_bins: int, bin_len: float, first_ray: int = 0, frac_bits: int = 40, top_index: int = 0,
-                       out=None, rain: bool = False, directional: bool = False, time_limit: bool = False):
+                       out=None, rain: bool = False, directional: bool = False, time_limit: bool = False, direct: bool = False):
         """hare_receive_source: Receive_batch with the rays and their state emitted on the device by the scene's source (set_source) --
         the rays first_ray .. first_ray + n - 1; nothing but the count goes up.  Returns what Receive_batch returns.  Calls over
-        [0, k) and [k, n) sum to the histogram and detections of the one call."""
+        [0, k) and [k, n) sum to the histogram and detections of the one call.  direct (HARE_RECEIVE_DIRECT; include/hare_hip.h, "Direct
+        sound"): the direct sound is one visibility-tested deposit per receiver, standing for the call's n rays, and cast 0 detects
+        nothing -- chunks then sum to the one call up to a unit per chunk and word."""
         return Spatial_Partition._receive_source([self], n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain, directional,
-                                                 time_limit)
+                                                 time_limit, direct=direct)
 
     def Receive_source_reduced(self, n: int, bounces: int, n_bins: int, bin_len: float, windows=None, levels=None, weight=None,
                                first_ray: int = 0, frac_bits: int = 40, top_index: int = 0, directional: bool = False,
-                               time_limit: bool = False):
+                               time_limit: bool = False, direct: bool = False):
         """hare_receive_source_reduced: Receive_source with the histogram kept on the device and reduced there, as in
-        Receive_batch_reduced; returns what that returns."""
+        Receive_batch_reduced; returns what that returns.  direct: as in Receive_source."""
         return Spatial_Partition._receive_source([self], n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, None, False, directional,
-                                                 time_limit, dict(windows=windows, levels=levels, weight=weight))
+                                                 time_limit, dict(windows=windows, levels=levels, weight=weight), direct=direct)
 
     @staticmethod
     def Receive_source_sharded(partitions, n: int, bounces: int, n_bins: int, bin_len: float, first_ray: int = 0, frac_bits: int = 40,
-                               top_index: int = 0, out=None, rain: bool = False, directional: bool = False, time_limit: bool = False):
+                               top_index: int = 0, out=None, rain: bool = False, directional: bool = False, time_limit: bool = False,
+                               direct: bool = False):
         """hare_receive_source_sharded: Receive_source over several partitions (contiguous ray shards, histograms summed); byte-identical.
-        The partitions must hold the same source and "source_seed"."""
+        The partitions must hold the same source and "source_seed".  direct: as in Receive_source; one partition makes the deposit."""
         return Spatial_Partition._receive_source(list(partitions), n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain,
-                                                 directional, time_limit)
+                                                 directional, time_limit, direct=direct)
 
     @staticmethod
-    def _receive_source(parts, n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain, directional, time_limit, reduce=None):
+    def _receive_source(parts, n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain, directional, time_limit, reduce=None,
+                        direct=False):
         if not parts or any(p._kind != parts[0]._kind for p in parts):
             raise ValueError("need one or more partitions of the same kind")
         n = int(n)
@@ -535,7 +539,7 @@ class Spatial_Partition:
         state_out = np.empty((1 + B, n), np.float64)
         ctr = capi.Counters()
         flags = ((capi.RECEIVE_DIFFUSE_RAIN if rain else 0) | (capi.RECEIVE_DIRECTIONAL if directional else 0) |
-                 (capi.RECEIVE_TIME_LIMIT if time_limit else 0))
+                 (capi.RECEIVE_TIME_LIMIT if time_limit else 0) | (capi.RECEIVE_DIRECT if direct else 0))
         if reduce is not None:
             w, n_win, win, n_lev, lev = _reduce_spec(reduce, nb, B)
             sums, cross = np.zeros((max(K, 0), B, n_win, 4), np.uint64), np.zeros((max(K, 0), B, n_lev), np.int32)
@@ -672,6 +676,21 @@ class Spatial_Partition:
                                           ptr(win), n_lev, ptr(lev), d_sums or None, d_cross or None, stream or None))
 
     @staticmethod
+    def direct_work_bytes(K: int) -> int:
+        """Bytes of direct_device's d_work for K receivers: HARE_DIRECT_WORK_BYTES(K)."""
+        return 64 * int(K) + 256
+
+    def direct_device(self, n_weight: int, n_bins: int, bin_len: float, frac_bits: int, d_work: int, d_hist: int, d_detections: int,
+                      top_index: int = 0, directional: bool = False, stream: int = 0):
+        """hare_direct_device on raw device addresses + a hipStream_t: the direct sound of the scene's source (include/hare_hip.h, "Direct
+        sound") -- one visibility query and one deposit per receiver, standing for n_weight source rays -- accumulated into d_hist
+        (K x n_bins x B uint64, x 4 with directional) and d_detections (2 K uint64); d_work holds direct_work_bytes(K) bytes.
+        Stream-ordered: no allocation, no free, no wait."""
+        check(lib.hare_direct_device(self._h, self._kind, int(top_index), int(n_weight), capi.RECEIVE_DIRECTIONAL if directional else 0,
+                                     int(n_bins), float(bin_len), int(frac_bits), d_work or None, d_hist or None, d_detections or None,
+                                     stream or None))
+
+    @staticmethod
     def receive_work_bytes(n: int, rain: bool = False) -> int:
         """Bytes of receive_device's d_work for n rays: 2 n int32, or HARE_RECEIVE_RAIN_WORK_BYTES(n) with rain."""
         return 80 * int(n) + 256 if rain else 8 * int(n)
@@ -679,12 +698,15 @@ class Spatial_Partition:
     def receive_device(self, n: int, d_rays: int, bounces: int, n_bins: int, bin_len: float, frac_bits: int, d_state: int, d_work: int,
                        d_events_last: int, d_hist: int, d_detections: int, top_index: int = 0, d_excl1: int = 0, d_excl2: int = 0,
                        d_counters: int = 0, stream: int = 0, flags: int = 0, rain: bool = False, directional: bool = False,
-                       time_limit: bool = False):
+                       time_limit: bool = False, direct: bool = False):
         """hare_receive_device on raw device addresses (e.g. torch.Tensor.data_ptr()) + a hipStream_t: d_state (1 + B) x n doubles is read
         and overwritten, d_hist (K x n_bins x B uint64) and d_detections (2 K uint64) are accumulated into.  Stream-ordered.  rain: diffuse
         rain (HARE_RECEIVE_DIFFUSE_RAIN); d_work then holds receive_work_bytes(n, rain=True) bytes.  directional
         (HARE_RECEIVE_DIRECTIONAL): d_hist is K x n_bins x B x 4 uint64, channels W, X, Y, Z.  time_limit (HARE_RECEIVE_TIME_LIMIT): as
-        in Receive_batch; a retired ray keeps the ray and the state of the cast that retired it."""
+        in Receive_batch; a retired ray keeps the ray and the state of the cast that retired it.  direct (HARE_RECEIVE_DIRECT): cast 0
+        detects nothing -- the rays are the scene's source's, and direct_device deposits their direct sound."""
+        if direct:
+            flags |= capi.RECEIVE_DIRECT
         if time_limit:
             flags |= capi.RECEIVE_TIME_LIMIT
         if rain:

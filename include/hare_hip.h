@@ -83,6 +83,8 @@ extern "C" {
 #define HARE_RECEIVE_DIFFUSE_RAIN 128u /* hare_receive_device / _batch / _batch_sharded only: diffuse rain ("receivers", "Diffuse rain", below)    */
 #define HARE_RECEIVE_DIRECTIONAL 256u  /* the same three calls only: four channels per histogram word, W X Y Z ("receivers", "Directional", below) */
 #define HARE_RECEIVE_TIME_LIMIT 512u   /* the same three calls only: a ray whose path has passed the histogram's end is retired ("receivers", "Termination")  */
+#define HARE_RECEIVE_DIRECT 1024u      /* hare_receive_source / _sharded / _reduced and hare_receive_device only: the direct sound is deposited once per  */
+                                       /* receiver, visibility-tested, and cast 0's receiver step is skipped ("receivers", "Direct sound")               */
 
 /* Hare.Geometry.Ray (Hare_Geometry_Primitives.cs:393-429): origin + direction.  Ray_ID/ThreadID
  * only serve the reference's mailbox pool and are not needed here. 48 bytes. */
@@ -610,6 +612,48 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  *                           1..8, R outside 0..64, R and gain disagreeing, any power or gain that is not finite and >= 0.
  *                           hare_scene_get_option reads "source" (0 / 1), "source_bands" and "source_res"
  *
+ * Direct sound (flag HARE_RECEIVE_DIRECT; hare_direct_device).  The direct sound needs no sampling: the source, its power, its directivity
+ * and the receivers all lie in the scene, so it is ONE visibility query and one deposit per receiver instead of however many of the burst's
+ * rays happen to pass through the sphere in cast 0.  All arithmetic is FP64 with no contraction, in this order.  For each receiver k, in
+ * any order (integer sums are order-free); pos, power[b] and gain_b are the scene's source, c and rr = r*r are receiver k as stored, and
+ * W = (double)n_weight is the number of source rays that the deposit stands for:
+ *
+ *   vx = cx - pos.x; vy = cy - pos.y; vz = cz - pos.z
+ *   d2 = (vx*vx + vy*vy) + vz*vz
+ *   eligible  iff  d2 > rr                                  (a NaN is not eligible; a source inside the sphere gets no direct deposit)
+ *   occluded  = the hare_occluded predicate on the shadow ray (origin pos, direction v, no exclusion, t_max = 1.0)
+ *   if eligible && !occluded:
+ *     dist = sqrt(d2);  x = rr / d2
+ *     f    = (0.5 * x) / (1.0 + sqrt(1.0 - x))              the sphere's share of the directions, (1 - cos theta) / 2, without cancellation
+ *     g_b  = gain_b(v)                                      "Source"'s cube-map lookup with d := v, not normalised (the lookup divides by a_f);
+ *                                                           1.0 without a table
+ *     m_b  = ((power[b] * g_b) * (f * W)) * 2^frac_bits     then 0 unless > 0; min(., 2^63); q_b = rint -> uint64, as in the receiver step
+ *     xb   = dist / bin_len                                 binned as in the receiver step
+ *     hist[(k*n_bins + bin)*B + b] += q_b;   detections[2k] += 1 if binned, detections[2k+1] += 1 otherwise
+ *     directional: a = ( -(vx / dist), -(vy / dist), -(vz / dist) ), channels as in "Directional" with this m_b
+ *
+ * Visibility is tested to the center only, as the rain does: a sphere that a wall hides in part counts as wholly seen or wholly hidden.
+ * The sound arrives at dist, the distance to the center (|d| = 1 for a source ray, so this is the path to the center, where the sampled
+ * direct sound arrives at the closest-approach parameter s of each ray, up to r short of it).
+ * Suppression.  In a call with the flag the receiver step of cast 0 is skipped for every ray: no add, no detection.  State update,
+ * scattering, rain, termination, reflection, the final state, rays, events and counters are those of the call without the flag.  So, word
+ * for word in wrapping uint64, and for detections alike:
+ *
+ *   hist(flag, bounces) = hist(no flag, bounces) - hist(no flag, bounces = 1) + direct
+ *
+ * (a one-cast call deposits exactly cast 0's receiver step and nothing else: rain and the rules need c < bounces - 1).
+ * Where the flag is accepted.  hare_receive_source, hare_receive_source_sharded and hare_receive_source_reduced: suppression plus the
+ * deposit with n_weight = n, the call's whole n, enqueued on the loop's stream before cast 0 (a call with n = 0 runs nothing).  In the
+ * sharded call ONE scene makes the deposit, once: scenes[0] (the first scene whose shard holds a ray, which is scenes[0] whenever
+ * n >= n_scenes).  hare_receive_device: suppression only; the device caller makes the deposit with hare_direct_device.
+ * hare_receive_batch, hare_receive_batch_sharded and hare_receive_batch_reduced: HARE_E_INVALID, refused before anything runs (their
+ * rays are the caller's: the library cannot know that they are the source's).  With a receiver map the flag works as with the linear
+ * receivers; rain, channels and the termination rules combine freely with it.  No source set: HARE_E_STATE.  The source's B differing
+ * from the topology's: HARE_E_INVALID, as without the flag.
+ * Chunking.  A burst split into chunks, each with the flag, sums to the one call's histogram up to one unit per chunk, word and band:
+ * each chunk rounds f * n_chunk on its own.  A caller who wants the bits of the one call makes ONE hare_direct_device deposit with the
+ * whole count and runs the chunks through hare_receive_device with the flag.
+ *
  * The histogram is fixed point in uint64: integer sums do not depend on the order of the adds, so the result is bit-identical from
  * run to run, between the one-device and the sharded call, and against a restatement on the host.  (r*r is formed once, when the
  * receivers are set: the same FP64 product.)
@@ -734,8 +778,8 @@ HARE_API int hare_emit_device(hare_scene *s, int64_t n, int64_t first_ray, void 
  *   d_state        (1 + B) planes of n doubles: plane 0 is L, planes 1..B are E.  Read and overwritten
  *   d_hist         K x n_bins x B uint64 (x 4 with HARE_RECEIVE_DIRECTIONAL), ACCUMULATED;  d_detections: 2 K uint64, ACCUMULATED
  *   d_counters     nullable: totals, ACCUMULATED (as hare_bounce_device's; the rain's occlusion queries are not counted)
- *   flags          HARE_SHOOT_COUNT_WORK / HARE_SHOOT_SIMPLE_KERNEL (the casts), HARE_RECEIVE_DIFFUSE_RAIN, HARE_RECEIVE_DIRECTIONAL and
- *                  HARE_RECEIVE_TIME_LIMIT; other bits are ignored.  With
+ *   flags          HARE_SHOOT_COUNT_WORK / HARE_SHOOT_SIMPLE_KERNEL (the casts), HARE_RECEIVE_DIFFUSE_RAIN, HARE_RECEIVE_DIRECTIONAL,
+ *                  HARE_RECEIVE_TIME_LIMIT and HARE_RECEIVE_DIRECT (suppression only: "Direct sound"); other bits are ignored.  With
  *                  HARE_RECEIVE_DIFFUSE_RAIN d_work holds HARE_RECEIVE_RAIN_WORK_BYTES(n) bytes: the 2 n int32, then the rain's scratch
  * Arguments are checked before anything runs (HARE_E_INVALID): kind, top_index, 0 <= n <= 2^31 - 256, 1 <= bounces <= 4096,
  * n_bins >= 1, bin_len finite and > 0, 0 <= frac_bits <= 62, K x n_bins x B <= 2^27 (K x n_bins x B x 4 <= 2^27 with
@@ -746,6 +790,16 @@ HARE_API int hare_receive_device(hare_scene *s, int32_t kind, int32_t top_index,
                                  const void *d_excl2, int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len,
                                  int32_t frac_bits, void *d_state, void *d_work, void *d_events_last, void *d_hist,
                                  void *d_detections, void *d_counters, void *stream);
+/* The direct sound's deposit on DEVICE buffers ("receivers", "Direct sound"): one visibility query and one deposit per receiver of the
+ * scene, from the scene's source, standing for n_weight source rays.  Stream-ordered like hare_emit_device: no allocation, no free, no
+ * wait.  d_hist (K x n_bins x B uint64, x 4 with HARE_RECEIVE_DIRECTIONAL, the only flag read) and d_detections (2 K uint64) are
+ * ACCUMULATED; d_work is scratch of HARE_DIRECT_WORK_BYTES(K) bytes (K shadow rays, t_max, exclusion words and flags), B the source's.
+ * Checked in this order: HARE_E_INVALID unless 1 <= n_weight <= 2^53, kind, top_index, n_bins >= 1, bin_len finite and > 0,
+ * 0 <= frac_bits <= 62, the histogram within 2^27 words, no buffer null and none overlapping another, and a source whose B is not
+ * the topology's; then HARE_E_NODEVICE; then HARE_E_STATE: no source, no receivers, or the partition not built. */
+#define HARE_DIRECT_WORK_BYTES(K) (64 * (int64_t)(K) + 256)
+HARE_API int hare_direct_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL only */,
+                                int32_t n_bins, double bin_len, int32_t frac_bits, void *d_work, void *d_hist, void *d_detections, void *stream);
 /* The same from host buffers (threading and staging as hare_bounce_batch's last-cast-only path: one enqueue, one synchronisation; no
  * events are downloaded).  state_in nullable (every ray starts at L = 0, E = 1); state_out nullable ((1 + B) x n, as d_state).
  * hist (K x n_bins x B, x 4 with HARE_RECEIVE_DIRECTIONAL) and detections (2 K) are WRITTEN, not accumulated; ctr nullable: counters summed over the casts.  flags as
@@ -767,7 +821,8 @@ HARE_API int hare_receive_batch_sharded(hare_scene *const *scenes, int32_t n_sce
  * first_ray .. first_ray + n - 1 of the scene's source ("Source" above), no exclusions.  In the sharded call the shard that starts at ray lo
  * emits from first_ray + lo.  Flags, checks and outputs as hare_receive_batch's, and HARE_E_INVALID when first_ray < 0 or
  * first_ray + n > 2^62, or when the source's B is not the band count of Model[top_index]; HARE_E_STATE when no source is set.  The sharded
- * call also refuses scenes whose source or "source_seed" differ. */
+ * call also refuses scenes whose source or "source_seed" differ.  These calls (and hare_receive_source_reduced) take HARE_RECEIVE_DIRECT
+ * ("Direct sound"); the hare_receive_batch calls refuse it. */
 HARE_API int hare_receive_source(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, int64_t first_ray, int32_t bounces,
                                  uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits, double *state_out, uint64_t *hist,
                                  uint64_t *detections, hare_counters *ctr);

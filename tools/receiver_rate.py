@@ -24,9 +24,14 @@ With --map K[,K..] (B = 8, bins of 0.2 m: 1 000, or as many as the histogram cap
 receive loop with a receiver map (hare_scene_set_receiver_map; the _map kernels): the plain bounce loop, the linear loop at K = 256, the
 map over the same 256 receivers, a plane of at most K receivers at 1.2 m for every K given, and a cloud of 4 096 in the room, interleaved,
 the median of --reps runs; `over` is the time over the plain loop.  Run it under rocprofv3 --kernel-trace --stats for the kernels' times.
+With --source --direct (B = 8, bins of 0.2 m; nothing else runs), the direct sound ("Direct sound": HARE_RECEIVE_DIRECT): the host wall time
+of hare_receive_source with and without the flag, interleaved, the median of --reps runs and the spread of each, for K = 8 linear receivers
+and for a plane of at most 4 096 receivers as a map; and the gain in noise -- the relative spread over 8 values of "source_seed" of one
+mid-hall receiver's summed 0 - 50 ms window (band 0; 17.15 m of path), with and without the flag, beside the cast-0 rays that receiver got.
+Run it under rocprofv3 --kernel-trace --stats for the three kernels' own times.
 Prints ONE JSON line.  usage: python tools/receiver_rate.py [hall|cathedral] [--rays N] [--bounces B] [--reps R] [--host] [--quick]
                                                           [--scatter SIGMA] [--rain] [--directional] [--time-limit] [--floor-bits N [--roulette]]
-                                                          [--source] [--map K[,K..]]"""
+                                                          [--source [--direct]] [--map K[,K..]]"""
 import argparse
 import json
 import os
@@ -54,6 +59,7 @@ ap.add_argument("--time-limit", action="store_true", help="the loop again with H
 ap.add_argument("--floor-bits", type=int, default=0, metavar="N", help="the loop again with the energy floor 2^-N (scene option receive_floor_bits)")
 ap.add_argument("--roulette", action="store_true", help="with --floor-bits: Russian roulette under the floor (scene option receive_roulette)")
 ap.add_argument("--source", action="store_true", help="K = 8, B = 8: hare_receive_source against hare_receive_batch from host rays, wall time")
+ap.add_argument("--direct", action="store_true", help="with --source: hare_receive_source with and without HARE_RECEIVE_DIRECT, time and noise")
 ap.add_argument("--map", default=None, metavar="K[,K..]", help="B = 8: receiver maps (planes of about K receivers, a cloud of 4096) against the linear loop at K = 256")
 a = ap.parse_args()
 if a.reps is None:
@@ -123,8 +129,62 @@ def source_run():
     print(json.dumps(row))
 
 
+def direct_run():
+    """hare_receive_source with and without HARE_RECEIVE_DIRECT: host wall time, and the spread of a mid-hall receiver's early energy."""
+    B, bin_len, n_bins = 8, 0.2, 1000
+    size = np.asarray(mesh.size)
+    alpha = np.random.default_rng(B).uniform(0.02, 0.3, (T.Polygon_Count, B))
+    spacing = float(np.sqrt(size[0] * size[1] / 4096))
+    while (int(size[0] // spacing) + 1) * (int(size[1] // spacing) + 1) > 4096:
+        spacing *= 1.002
+    plane = H.Voxel_Grid.receiver_plane([0.0, 0.0], size[:2], 1.2, spacing, 0.25)
+    layouts = {"linear_8": receivers(8) + (False,), "plane_4096": plane + (True,)}
+    early = int(np.ceil(17.15 / bin_len))                                 # 50 ms of path at 343 m/s
+    rows = {}
+    for name, (c, r, as_map) in layouts.items():
+        p = H.Voxel_Grid([T], D)
+        (p.set_receiver_map if as_map else p.set_receivers)(c, r)
+        p.set_absorption(alpha)
+        p.set_source(S, power=np.ones(B)).set_option("source_seed", 1)
+        calls = {"plain": lambda p=p: p.Receive_source(n, nb, n_bins, bin_len, frac_bits=FRAC),
+                 "direct": lambda p=p: p.Receive_source(n, nb, n_bins, bin_len, frac_bits=FRAC, direct=True)}
+        for f in calls.values():
+            f()                                                           # the warm-up
+        wall = {k: [] for k in calls}
+        for _ in range(a.reps):                                           # interleaved
+            for k, f in calls.items():
+                t0 = time.perf_counter()
+                f()
+                wall[k].append((time.perf_counter() - t0) * 1e3)
+        row = {"K": int(c.shape[0]), "map": as_map}
+        for k, v in wall.items():
+            row[k + "_ms"] = round(float(np.median(v)), 3)
+            row[k + "_min_max_ms"] = [round(min(v), 3), round(max(v), 3)]
+        row["direct_over_plain"] = round(row["direct_ms"] / row["plain_ms"], 4)
+        # the noise: one receiver about the middle of the hall, seen from the source
+        mid = int(np.argmin(((c - size * np.array([0.6, 0.5, 0.0]) - np.array([0, 0, c[0, 2]])) ** 2).sum(axis=1))) if as_map else 0
+        e = {"plain": [], "direct": []}
+        cast0 = []
+        for seed in range(8):
+            p.set_option("source_seed", 100 + seed)
+            for k, f in calls.items():
+                e[k].append(float(f()[0][mid, :early, 0].astype(np.float64).sum()) * 2.0 ** -FRAC)
+            cast0.append(int(p.Receive_source(n, 1, n_bins, bin_len, frac_bits=FRAC)[2][mid].sum()))
+        row["receiver"] = mid
+        row["receiver_distance_m"] = round(float(np.linalg.norm(c[mid] - S)), 3)
+        row["receiver_radius_m"] = round(float(r[mid]), 3)
+        row["cast0_rays"] = cast0
+        for k in e:
+            row["early_spread_" + k] = round(float(np.std(e[k], ddof=1) / np.mean(e[k])), 6)
+            row["early_mean_" + k] = round(float(np.mean(e[k])), 4)
+        rows[name] = row
+        print(json.dumps({name: row}), file=sys.stderr, flush=True)
+    print(json.dumps({"scene": a.scene, "domain": D, "rays": n, "bounces": nb, "B": B, "n_bins": n_bins, "bin_len": bin_len, "reps": a.reps,
+                      "early_bins": early, "rows": rows}))
+
+
 if a.source:
-    source_run()
+    direct_run() if a.direct else source_run()
     sys.exit(0)
 
 
