@@ -222,10 +222,12 @@ public:
                                     R > 0 ? gain.data() : nullptr));
     }
     // direct (HARE_RECEIVE_DIRECT; the header's "Direct sound"): the direct sound is one visibility-tested deposit per receiver, standing
-    // for the call's n rays, and cast 0 detects nothing.
+    // for the call's n rays, and cast 0 detects nothing.  image (HARE_RECEIVE_IMAGE; "Image sources (first order)"): the first-order specular
+    // reflections are one visibility-tested deposit per (receiver, polygon) pair, and in cast 1 the rays that left cast 0 specularly detect
+    // nothing; the pair list holds GetOption("image_max_pairs") pairs (std::runtime_error, HARE_E_NOMEM with the needed count, when the scene yields more).
     uint64_t ReceiveSource(int64_t n, int64_t first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
                            std::vector<uint64_t>& hist, std::vector<uint64_t>& detections, std::vector<double>* state_out = nullptr,
-                           bool rain = false, bool directional = false, bool direct = false)
+                           bool rain = false, bool directional = false, bool direct = false, bool image = false)
     {
         if (n < 0) throw std::invalid_argument("ReceiveSource: n must be >= 0");
         const int64_t K = GetOption("receivers"), B = Bands(top_index);
@@ -235,7 +237,7 @@ public:
         hare_counters c{};
         check(hare_receive_source(scene_, kind_, top_index, n, first_ray, bounces,
                                   (rain ? HARE_RECEIVE_DIFFUSE_RAIN : 0u) | (directional ? HARE_RECEIVE_DIRECTIONAL : 0u) |
-                                      (direct ? HARE_RECEIVE_DIRECT : 0u),
+                                      (direct ? HARE_RECEIVE_DIRECT : 0u) | (image ? HARE_RECEIVE_IMAGE : 0u),
                                   n_bins, bin_len, frac_bits, state_out ? state_out->data() : nullptr, hist.data(), detections.data(), &c));
         return c.hits;
     }
@@ -248,6 +250,16 @@ public:
     {
         check(hare_direct_device(scene_, kind_, top_index, n_weight, directional ? HARE_RECEIVE_DIRECTIONAL : 0u, n_bins, bin_len, frac_bits,
                                  d_work, d_hist, d_detections, stream));
+    }
+    // hare_image_device on device pointers and a hipStream_t: the first-order image sources' deposit alone, for n_weight source rays,
+    // ACCUMULATED into d_hist and d_detections (shaped as DirectDevice's); d_work holds ImageWorkBytes(K, P, max_pairs) bytes on a 16-byte
+    // boundary, and its first uint64 receives the number of pairs found (more than max_pairs: nothing was deposited).  Stream-ordered.
+    static int64_t ImageWorkBytes(int64_t K, int64_t P, int64_t max_pairs) { return HARE_IMAGE_WORK_BYTES(K, P, max_pairs); }
+    void ImageDevice(int top_index, int64_t n_weight, int n_bins, double bin_len, int frac_bits, int64_t max_pairs, void* d_work, void* d_hist,
+                     void* d_detections, bool directional = false, void* stream = nullptr)
+    {
+        check(hare_image_device(scene_, kind_, top_index, n_weight, directional ? HARE_RECEIVE_DIRECTIONAL : 0u, n_bins, bin_len, frac_bits,
+                                max_pairs, d_work, d_hist, d_detections, stream));
     }
     // the reduction of a histogram on the device (include/hare_hip.h, "receivers", "Reduction"): per receiver and band, the sums S0 = sum g
     // and S1 = sum i g over bin windows and the bins at which the backward-integrated decay crosses the levels.  What to compute:
@@ -310,7 +322,7 @@ public:
     }
     uint64_t ReceiveSourceReduced(int64_t n, int64_t first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
                                   const Reduction& r, std::vector<uint64_t>& sums, std::vector<int32_t>& cross, std::vector<uint64_t>& detections,
-                                  std::vector<double>* state_out = nullptr, bool directional = false, bool direct = false)
+                                  std::vector<double>* state_out = nullptr, bool directional = false, bool direct = false, bool image = false)
     {
         if (n < 0) throw std::invalid_argument("ReceiveSourceReduced: n must be >= 0");
         const int64_t K = GetOption("receivers"), B = Bands(top_index);
@@ -321,7 +333,9 @@ public:
         if (state_out) state_out->assign((size_t)(1 + B) * (size_t)n, 0.0);
         hare_counters c{};
         check(hare_receive_source_reduced(scene_, kind_, top_index, n, first_ray, bounces,
-                                          (directional ? HARE_RECEIVE_DIRECTIONAL : 0u) | (direct ? HARE_RECEIVE_DIRECT : 0u), n_bins,
+                                          (directional ? HARE_RECEIVE_DIRECTIONAL : 0u) | (direct ? HARE_RECEIVE_DIRECT : 0u) |
+                                              (image ? HARE_RECEIVE_IMAGE : 0u),
+                                          n_bins,
                                           bin_len, frac_bits, state_out ? state_out->data() : nullptr,
                                           r.weight.empty() ? nullptr : r.weight.data(), n_win, r.windows.data(), n_lev, r.levels.data(), sums.data(),
                                           cross.data(), detections.data(), &c));

@@ -346,9 +346,14 @@ namespace Hare
 
             /// <summary>Receive with the rays first_ray .. first_ray + n - 1 and their state emitted on the device by the source
             /// (hare_receive_source_sharded): nothing but the count goes up.  Calls over [0, k) and [k, n) sum to the histogram and the
-            /// detections of the one call.  hist, detections and state (optional, (1 + B) x n: the final state) as in Receive.</summary>
+            /// detections of the one call.  hist, detections and state (optional, (1 + B) x n: the final state) as in Receive.
+            /// direct (HARE_RECEIVE_DIRECT; include/hare_hip.h, "Direct sound"): the direct sound is one visibility-tested deposit per receiver
+            /// and cast 0 detects nothing.  image (HARE_RECEIVE_IMAGE; "Image sources (first order)"): the first-order specular reflections are
+            /// one deposit per (receiver, polygon) pair and in cast 1 the rays that left cast 0 specularly detect nothing; the pair list holds
+            /// GetOption("image_max_pairs") pairs (HARE_E_NOMEM with the needed count when the scene yields more).</summary>
             public long ReceiveSource(long n, long first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits, ulong[] hist,
-                                      ulong[] detections, double[] state = null, bool rain = false, bool directional = false)
+                                      ulong[] detections, double[] state = null, bool rain = false, bool directional = false, bool direct = false,
+                                      bool image = false)
             {
                 if (n < 0) throw new ArgumentException("n must be at least 0");
                 if (bounces < 1) throw new ArgumentException("bounces must be at least 1");
@@ -357,7 +362,8 @@ namespace Hare
                 if (detections == null || detections.LongLength < 2 * K) throw new ArgumentException("detections must hold 2 x receivers values");
                 if (state != null && state.LongLength < (1 + B) * n) throw new ArgumentException("state must hold (1 + Bands(top_index)) x n values");
                 hare_counters ctr;
-                uint flags = (rain ? HareHip.HARE_RECEIVE_DIFFUSE_RAIN : 0u) | (directional ? HareHip.HARE_RECEIVE_DIRECTIONAL : 0u);
+                uint flags = (rain ? HareHip.HARE_RECEIVE_DIFFUSE_RAIN : 0u) | (directional ? HareHip.HARE_RECEIVE_DIRECTIONAL : 0u) |
+                             (direct ? HareHip.HARE_RECEIVE_DIRECT : 0u) | (image ? HareHip.HARE_RECEIVE_IMAGE : 0u);
                 HareHip.Check(HareHip.hare_receive_source_sharded(scenes, scenes.Length, Kind, top_index, n, first_ray, bounces, flags, n_bins, bin_len,
                                                                   frac_bits, state, hist, detections, out ctr));
                 return (long)ctr.hits;
@@ -367,10 +373,11 @@ namespace Hare
             /// hare_receive_source_reduced; include/hare_hip.h, "Reduction"): the histogram never comes down.  win holds n_win pairs
             /// lo, hi of bins; levels fractions in units of 2^-32 (DecayLevel); weight n_bins x B values in units of 2^-32 (AirWeights) or
             /// null.  sums: receivers x B x n_win x 4 (S0 lo, S0 hi, S1 lo, S1 hi); cross: receivers x B x levels.Length.  rays null: the
-            /// scene's source emits n rays from first_ray.  One scene only: a crossing is not additive over shards.</summary>
+            /// scene's source emits n rays from first_ray.  One scene only: a crossing is not additive over shards.  direct, image: as in
+            /// ReceiveSource (with rays of the caller's the library refuses them).</summary>
             public long ReceiveReduced(hare_ray[] rays, long n, long first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
                                        uint[] weight, int[] win, uint[] levels, ulong[] sums, int[] cross, ulong[] detections, double[] state = null,
-                                       bool directional = false)
+                                       bool directional = false, bool direct = false, bool image = false)
             {
                 if (scenes.Length != 1) throw new NotSupportedException("ReceiveReduced runs on one scene: reduce the histogram of the sharded Receive with HistReduce");
                 if (bounces < 1) throw new ArgumentException("bounces must be at least 1");
@@ -385,7 +392,8 @@ namespace Hare
                 if (detections == null || detections.LongLength < 2 * K) throw new ArgumentException("detections must hold 2 x receivers values");
                 if (state != null && state.LongLength < (1 + B) * n) throw new ArgumentException("state must hold (1 + Bands(top_index)) x n values");
                 hare_counters ctr;
-                uint flags = directional ? HareHip.HARE_RECEIVE_DIRECTIONAL : 0u;
+                uint flags = (directional ? HareHip.HARE_RECEIVE_DIRECTIONAL : 0u) | (direct ? HareHip.HARE_RECEIVE_DIRECT : 0u) |
+                             (image ? HareHip.HARE_RECEIVE_IMAGE : 0u);
                 if (rays != null)
                     HareHip.Check(HareHip.hare_receive_batch_reduced(scenes[0], Kind, top_index, n, rays, null, null, bounces, flags, n_bins, bin_len, frac_bits,
                                                                      null, state, weight, n_win, win, n_lev, levels, sums, cross, detections, out ctr));

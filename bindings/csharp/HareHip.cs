@@ -110,6 +110,9 @@ namespace Hare
             // hare_receive_source / _sharded / _reduced and hare_receive_device: the direct sound is one visibility-tested deposit per receiver
             // and cast 0 detects nothing (include/hare_hip.h, "Direct sound"); the hare_receive_batch calls refuse it
             public const uint HARE_RECEIVE_DIRECT = 1024;
+            // the same calls: the first-order specular reflections are one visibility-tested deposit per (receiver, polygon) pair and in cast 1
+            // the rays that left cast 0 specularly detect nothing (include/hare_hip.h, "Image sources (first order)")
+            public const uint HARE_RECEIVE_IMAGE = 2048;
 
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr hare_last_error();
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int hare_device_count(out int count);
@@ -270,6 +273,10 @@ namespace Hare
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_direct_device(IntPtr scene, int kind, int top_index, long n_weight, uint flags, int n_bins, double bin_len,
                                                         int frac_bits, IntPtr d_work, IntPtr d_hist, IntPtr d_detections, IntPtr stream);
+            // the first-order image sources' deposit on device buffers ("Image sources (first order)"); d_work: 256 + 32 P + 136 max_pairs bytes
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_image_device(IntPtr scene, int kind, int top_index, long n_weight, uint flags, int n_bins, double bin_len,
+                                                       int frac_bits, long max_pairs, IntPtr d_work, IntPtr d_hist, IntPtr d_detections, IntPtr stream);
             // the reduction of a histogram on the device (include/hare_hip.h, "receivers", "Reduction")
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_hist_reduce_device(IntPtr scene, int K, int n_bins, int B, int channels, IntPtr d_hist, IntPtr d_weight,

@@ -900,6 +900,8 @@ const OptionEntry kOptionTable[] = {
         {"receive_aggregate", &SceneOptions::receive_aggregate, 0, 1},
         {"receive_floor_bits", &SceneOptions::receive_floor_bits, 0, 1000},
         {"receive_roulette", &SceneOptions::receive_roulette, 0, 1},
+        {"image_max_pairs", &SceneOptions::image_max_pairs, 1, 1 << 26},
+        {"image_cull", &SceneOptions::image_cull, 0, 1},
 };
 }  // namespace
 

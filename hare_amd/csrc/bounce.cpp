@@ -43,7 +43,7 @@ void free_bounce_buffers(const HipApi* H, Scene& s)
         Scene::BounceBuf& b = c.bounce;
         if (b.copy_st) { (void)H->StreamSynchronize(b.copy_st); (void)H->StreamDestroy(b.copy_st); b.copy_st = nullptr; }
         for (void** p : {&b.rays[0], &b.rays[1], &b.excl[0], &b.excl[1], &b.excl2, &b.idx[0], &b.idx[1], &b.ev[0], &b.ev[1], &b.full,
-                         &b.tiles, &b.ctr, &b.state, &b.hist, &b.rain, &b.red, &b.direct})
+                         &b.tiles, &b.ctr, &b.state, &b.hist, &b.rain, &b.red, &b.direct, &b.image})
             dev_free(H, *p);
         b.cap = 0;
         b.ctr_cap = 0;
@@ -52,6 +52,7 @@ void free_bounce_buffers(const HipApi* H, Scene& s)
         b.rain_cap = 0;
         b.red_cap = 0;
         b.direct_cap = 0;
+        b.image_cap = 0;
     }
 }
 
@@ -235,6 +236,7 @@ struct ReceiveJob {
     uint32_t flags = 0;        // the call's HARE_RECEIVE_* bits
     bool from_source = false;  // hare_receive_source: rays and state come from hare_emit_source (rays from ray_base on), not from the caller
     int64_t direct_weight = 0; // HARE_RECEIVE_DIRECT: > 0 in the ONE scene that deposits the direct sound, for the call's whole n (else 0)
+    int64_t image_weight = 0;  // HARE_RECEIVE_IMAGE: the same for the first-order image sources
     const char* who = "hare_receive_batch";
     // hare_receive_*_reduced: the histogram stays in BounceBuf::hist and hare_hist_reduce runs behind the last cast; sums and cross come
     // down in its place (hist is null)
@@ -293,6 +295,14 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
         HIP_TRY(H->Malloc(&b.direct, direct_bytes));
         b.direct_cap = direct_bytes;
     }
+    const int64_t image_pairs = s.opt.image_max_pairs;
+    const size_t image_bytes = job.image_weight > 0 ? (size_t)HARE_IMAGE_WORK_BYTES(K, s.topos[(size_t)top].P, image_pairs) : 0;
+    if (image_bytes > b.image_cap) {
+        dev_free(H, b.image);
+        b.image_cap = 0;
+        HIP_TRY(H->Malloc(&b.image, image_bytes));
+        b.image_cap = image_bytes;
+    }
     if (!c.st[0]) HIP_TRY(H->StreamCreate(&c.st[0]));
     hipStream_t st = c.st[0];
     uint64_t* const d_hist = (uint64_t*)b.hist;
@@ -314,6 +324,10 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
     void* const work = rain ? b.rain : b.ev[1];         // b.ev[1] holds the loop's 2 n int32; with rain, a buffer of its own holds them and the rain's scratch
     if (job.direct_weight > 0)      // the direct sound, once per call, ahead of cast 0 (whose receiver step the flag switches off)
         if (int rc = direct_enqueue(s, H, kind, top, job.direct_weight, job.flags, job.n_bins, job.bin_len, job.frac_bits, b.direct, d_hist, d_det, st))
+            return rc;
+    if (job.image_weight > 0)       // the first-order image sources, once per call (cast 1's receiver step is switched off for the specular rays)
+        if (int rc = image_enqueue(s, H, kind, top, job.image_weight, job.flags, job.n_bins, job.bin_len, job.frac_bits, image_pairs, b.image, d_hist,
+                                   d_det, st))
             return rc;
     ReceivePlan plan;
     if (int rc = receive_plan(s, top, job.flags, n, job.n_bins, job.bin_len, job.frac_bits, d_state, d_hist, d_det, work,
@@ -341,7 +355,14 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
             HIP_TRY(H->MemcpyAsync(job.state_out + (size_t)p * (size_t)job.stride, d_state + (size_t)p * (size_t)n, (size_t)n * sizeof(double),
                                    hipMemcpyDeviceToHost, st));
     HIP_TRY(H->MemcpyAsync(per_cast, b.ctr, (size_t)bounces * sizeof(hare_counters), hipMemcpyDeviceToHost, st));
+    uint64_t image_found = 0;       // the pairs the search found: the last download, so that no return lies between it and the wait
+    if (job.image_weight > 0) HIP_TRY(H->MemcpyAsync(&image_found, b.image, sizeof image_found, hipMemcpyDeviceToHost, st));
     HIP_TRY(H->StreamSynchronize(st));
+    if (image_found > (uint64_t)image_pairs) {      // the deposit kernels added nothing: the caller's results hold no image sources
+        set_error(std::string(job.who) + ": the scene yields " + std::to_string(image_found) + " image-source pairs, \"image_max_pairs\" is " +
+                  std::to_string(image_pairs) + " (needed: " + std::to_string(image_found) + ")");
+        return HARE_E_NOMEM;
+    }
     return HARE_OK;
 }
 
@@ -538,6 +559,10 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
         set_error(std::string(who) + ": HARE_RECEIVE_DIRECT needs the scene's source (hare_receive_source, hare_receive_device + hare_direct_device)");
         return HARE_E_INVALID;
     }
+    if ((flags & HARE_RECEIVE_IMAGE) && !first_ray) {
+        set_error(std::string(who) + ": HARE_RECEIVE_IMAGE needs the scene's source (hare_receive_source, hare_receive_device + hare_image_device)");
+        return HARE_E_INVALID;
+    }
     if ((n > 0 && !rays && !first_ray) || (!hist && !red) || !detections) {
         set_error(std::string(who) + ": null rays, histogram or detections");
         return HARE_E_INVALID;
@@ -637,6 +662,7 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
         job.from_source = first_ray != nullptr;
         // the direct sound is deposited once, for the whole n: by the first scene whose shard holds a ray (scenes[0] whenever n >= G)
         job.direct_weight = ((flags & HARE_RECEIVE_DIRECT) && hi > lo && lo == 0) ? n : 0;
+        job.image_weight = ((flags & HARE_RECEIVE_IMAGE) && hi > lo && lo == 0) ? n : 0;
         job.who = who;
         job.reduce = red;
         job.sums = sums;

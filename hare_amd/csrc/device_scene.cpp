@@ -134,6 +134,10 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_direct_emit", &m->direct_emit},
         {"hare_direct_deposit", &m->direct_deposit[0]},
         {"hare_direct_deposit_dir", &m->direct_deposit[1]},
+        {"hare_image_mirror", &m->image_mirror},
+        {"hare_image_pairs", &m->image_pairs},
+        {"hare_image_deposit", &m->image_deposit[0]},
+        {"hare_image_deposit_dir", &m->image_deposit[1]},
     };
     for (auto& t : table) {
         hipError_t e = H->ModuleGetFunction(t.fn, m->mod, t.name);

@@ -523,7 +523,10 @@ constexpr int kMaxMapCells = 1 << 21;
 constexpr int32_t kCutTime = 1;      // HARE_RECEIVE_TIME_LIMIT
 constexpr int32_t kCutFloor = 2;     // "receive_floor_bits" > 0
 constexpr int32_t kCutRoulette = 4;  // ... with "receive_roulette" 1
-constexpr int32_t kCutSkipDetect = 8; // HARE_RECEIVE_DIRECT, cast 0 only: no receiver step in this cast (the direct sound is deposited by hare_direct_deposit)
+constexpr int32_t kCutSkipDetect = 8; // HARE_RECEIVE_DIRECT, cast 0 only: no receiver step in this cast (the direct sound is deposited by hare_direct_deposit);
+                                      // HARE_RECEIVE_IMAGE on a topology without a scattering table, cast 1 only (every reflection behind cast 0 was specular)
+constexpr int32_t kCutSkipSpecular = 16; // HARE_RECEIVE_IMAGE, the scatter kernels, cast 1 only: a ray whose reflection behind cast 0 was specular runs no
+                                      // receiver step -- the choice recomputed from g, "scatter_seed" and the polygon it is leaving (its mark)
 
 // hare_rain_step (receive.hip): diffuse rain between the shoot and the receive kernel of a cast -- the deposit of receiver k_dep's
 // visibility query (its flags in `socc`) and the emission of receiver k_emit's.  Reads what hare_receive_scatter_rain reads before it
@@ -595,6 +598,45 @@ struct DirectArgs {
     int32_t bands;
     int32_t res;
     int32_t n_bins;
+};
+
+// hare_image_mirror / hare_image_pairs / hare_image_deposit[_dir] (image.hip): first-order image sources (include/hare_hip.h, "receivers",
+// "Image sources (first order)").  The mirror writes img (a lane per polygon), zeroes *count and marks every shadow slot -2; the pair search
+// (a lane per polygon, the receivers streamed) appends the accepted pairs: slot j holds the pair's (k, p) in pair_kp[2 j], [2 j + 1] and its
+// two shadow rays in srays[2 j] (reflection point -> center) and srays[2 j + 1] (reflection point -> source), t_max 1.0, exclusion word p; the
+// flags-only occlusion kernels answer all 2 * max_pairs slots; the deposit (a lane per pair) adds the words of the pairs with both legs free.
+// cull and cf are named as in VoxelArgs: cull_load / cull_ray / cull_test read them.  Position, power and frame by value, as in SourceArgs
+struct ImageArgs {
+    const PolyRec* polys;      // Model[top]
+    const QuadRec* quads;      // null when the topology is all triangles
+    const unsigned char* cull; // the pre-cull's dense records of the topology
+    const double* rcv;         // n_rcv x 4: cx, cy, cz, r * r
+    const double* alpha;       // nullable: P x bands
+    const double* sigma;       // nullable: P x bands
+    const double* gain;        // the source's table (null iff res == 0)
+    unsigned long long* hist;  // n_rcv x n_bins x bands (x 4: hare_image_deposit_dir), accumulated
+    unsigned long long* det;   // 2 n_rcv, accumulated
+    unsigned long long* count; // the work block's first word: pairs found (may exceed max_pairs: then nothing is deposited)
+    double* img;               // n_poly x 4: S'.x, S'.y, S'.z, 1.0 when mirrored (else 0.0)
+    RayRec* srays;             // 2 max_pairs shadow rays
+    double* stmax;             // 2 max_pairs t_max (1.0)
+    int32_t* pair_kp;          // 2 max_pairs: k, p per pair
+    int32_t* sexcl;            // 2 max_pairs: p for a slot in use, -2 for the others
+    const int32_t* socc;       // 2 max_pairs occlusion flags (the deposit reads them)
+    CullFrame cf;
+    double pos[3];
+    double power[kMaxBands];
+    double frame[9];
+    double bin_len;
+    double scale;              // 2^frac_bits
+    double weight;             // W = (double)n_weight
+    long long max_pairs;
+    int32_t n_rcv;
+    int32_t n_poly;
+    int32_t bands;
+    int32_t res;
+    int32_t n_bins;
+    int32_t use_cull;          // scene option "image_cull"
 };
 
 // hare_hist_reduce (reduce.hip): a receive histogram reduced to window sums and decay-level crossings per receiver and band

@@ -1,7 +1,8 @@
 // receive.cpp -- receivers, absorption and scattering of a scene (hare_scene_set_receivers / _absorption / _scattering), the receive loop's plan
 // and its per-cast step (receive_plan, receive_step: what bounce_device_impl, launch.cpp, runs between its casts) and hare_receive_device
 // (include/hare_hip.h, "receivers"; the kernels: receive.hip); the point source (hare_scene_set_source, hare_emit_device; the kernel:
-// source.hip); the direct sound (direct_enqueue, hare_direct_device; the kernels: direct.hip).  The host-buffer calls hare_receive_batch / _sharded and hare_receive_source / _sharded are in bounce.cpp, beside the loop
+// source.hip); the direct sound (direct_enqueue, hare_direct_device; the kernels: direct.hip); first-order image sources (image_enqueue,
+// hare_image_device; the kernels: image.hip).  The host-buffer calls hare_receive_batch / _sharded and hare_receive_source / _sharded are in bounce.cpp, beside the loop
 // they share with hare_bounce_batch.
 //
 // Harness-defined: the reference has no receivers (Pachyderm, its caller, detects them on the host per ray).
@@ -185,6 +186,7 @@ int receive_plan(const Scene& s, int32_t top, uint32_t flags, int64_t n, int32_t
     p.work = p.rain ? rain_work(d_work, n) : RainWork();
     ra.rain_flag = p.work.flag;
     p.skip_cast0 = (flags & HARE_RECEIVE_DIRECT) != 0;
+    p.skip_cast1_specular = (flags & HARE_RECEIVE_IMAGE) != 0;
     return HARE_OK;
 }
 
@@ -236,6 +238,9 @@ int receive_step(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n
     ra.init_state = cast == 0 ? p.args.init_state : 0;      // the starting state is the first cast's business only
     ra.cast = cast;
     if (p.skip_cast0 && cast == 0) ra.cut |= kCutSkipDetect;      // the direct sound is hare_direct_deposit's: calls without the flag pass today's bytes
+    // the first-order specular paths are hare_image_deposit's: without a scattering table every ray of cast 1 has left cast 0 specularly; with
+    // one, the scatter kernels recompute each ray's choice
+    if (p.skip_cast1_specular && cast == 1) ra.cut |= ra.sigma ? kCutSkipSpecular : kCutSkipDetect;
     if (p.rain && !last_cast) {
         // diffuse rain (receive.hip: hare_rain_step): receiver k's query is emitted, answered by the flags-only occlusion kernel of this
         // partition, and deposited by the launch that emits k + 1's
@@ -382,6 +387,71 @@ int direct_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t
     if (int rc = launch(H, s.module->direct_emit, grid, 256, 0, st, args)) return rc;
     if (int rc = shoot_device_impl(s, H, kind, top, K, a.srays, a.sexcl, nullptr, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st, a.stmax, occ)) return rc;
     return launch(H, s.module->direct_deposit[dir], grid, 256, 0, st, args);
+}
+
+// ---- first-order image sources (include/hare_hip.h, "receivers", "Image sources (first order)"; the kernels: image.hip)
+// The scratch of a deposit, from d_work (a 16-byte boundary): 256 bytes whose first word is the pair count; P images (32 B); then per list
+// slot two shadow rays (96 B), two t_max (16 B), the pair's k and p (8 B), two exclusion words (8 B), two occlusion flags (8 B):
+// 256 + 32 P + 136 max_pairs = HARE_IMAGE_WORK_BYTES
+int image_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                  int32_t frac_bits, int64_t max_pairs, void* d_work, void* d_hist, void* d_det, hipStream_t st)
+{
+    const Scene::Source& src = s.src;
+    const bool dir = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
+    if (!s.module || !s.module->image_mirror || !s.module->image_pairs || !s.module->image_deposit[dir]) {
+        set_error("hare_image_mirror / hare_image_pairs / hare_image_deposit missing from code object");
+        return HARE_E_STATE;
+    }
+    const int64_t K = (int64_t)(s.rcv.size() / 4), P = s.topos[(size_t)top].P, M = max_pairs;
+    ImageArgs a;
+    memset((void*)&a, 0, sizeof a);
+    a.polys = (const PolyRec*)s.d_polys[(size_t)top];
+    a.quads = (const QuadRec*)s.d_quads[(size_t)top];
+    a.cull = (const unsigned char*)s.d_cull[(size_t)top];
+    a.cf = s.cull_frames[(size_t)top];
+    a.rcv = (const double*)(s.rmap.set ? s.rmap.d_rcv : s.d_rcv);
+    a.alpha = has_table(s.alpha, top) ? (const double*)s.alpha[(size_t)top].dev : nullptr;
+    a.sigma = has_table(s.sigma, top) ? (const double*)s.sigma[(size_t)top].dev : nullptr;
+    a.gain = src.R > 0 ? (const double*)src.d_gain : nullptr;
+    a.hist = (unsigned long long*)d_hist;
+    a.det = (unsigned long long*)d_det;
+    char* const w = (char*)d_work;
+    a.count = (unsigned long long*)w;
+    a.img = (double*)(w + 256);
+    a.srays = (RayRec*)(a.img + 4 * P);
+    a.stmax = (double*)(a.srays + 2 * M);
+    a.pair_kp = (int32_t*)(a.stmax + 2 * M);
+    a.sexcl = a.pair_kp + 2 * M;
+    int32_t* const occ = a.sexcl + 2 * M;
+    a.socc = occ;
+    memcpy(a.pos, src.pos, sizeof a.pos);
+    memcpy(a.power, src.power, sizeof a.power);
+    memcpy(a.frame, src.frame, sizeof a.frame);
+    a.bin_len = bin_len;
+    a.scale = ldexp(1.0, frac_bits);
+    a.weight = (double)n_weight;
+    a.max_pairs = M;
+    a.n_rcv = (int32_t)K;
+    a.n_poly = (int32_t)P;
+    a.bands = src.B;
+    a.res = src.R;
+    a.n_bins = n_bins;
+    a.use_cull = s.opt.image_cull;
+    if (!a.polys || !a.cull || !a.rcv || (src.R > 0 && !a.gain) || (has_table(s.alpha, top) && !a.alpha) || (has_table(s.sigma, top) && !a.sigma)) {
+        set_error("image sources: polygons, receivers or tables not on the device");
+        return HARE_E_STATE;
+    }
+    if (P == 0) return HARE_OK;     // no polygon, no image (a topology is never empty today: hare_scene_create refuses P < 1)
+    void* args[] = {&a};
+    const int64_t fill = std::max<int64_t>(P, 2 * M);
+    if (int rc = launch(H, s.module->image_mirror, (unsigned)std::min<int64_t>((fill + 255) / 256, 4096), 256, 0, st, args)) return rc;
+    {
+        // hare_image_pairs: (polygon blocks) x (receiver tiles of 256), through the module API like the rest
+        const unsigned gx = (unsigned)((P + 255) / 256), gy = (unsigned)((K + 255) / 256);
+        HIP_TRY(H->ModuleLaunchKernel(s.module->image_pairs, gx, gy, 1, 256, 1, 1, 0, st, args, nullptr));
+    }
+    if (int rc = shoot_device_impl(s, H, kind, top, 2 * M, a.srays, a.sexcl, nullptr, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st, a.stmax, occ)) return rc;
+    return launch(H, s.module->image_deposit[dir], (unsigned)((M + 255) / 256), 256, 0, st, args);
 }
 
 // ---- the reduction of a histogram (include/hare_hip.h, "receivers", "Reduction"; the kernel: reduce.hip)
@@ -834,6 +904,55 @@ int hare_direct_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n
     GUARD_END
 }
 
+int hare_image_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                      int32_t frac_bits, int64_t max_pairs, void* d_work, void* d_hist, void* d_detections, void* stream)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    const char* const who = "hare_image_device";
+    if (int rc = direct_check_weight(who, n_weight)) return rc;
+    flags &= HARE_RECEIVE_DIRECTIONAL;
+    if (int rc = receive_check_args(who, *s, flags, kind, top_index, 0, 1, n_bins, bin_len, frac_bits)) return rc;
+    if (s->src.set && s->src.B != scene_bands(*s, top_index)) {
+        set_error(std::string(who) + ": the source has " + std::to_string(s->src.B) + " bands, the topology " + std::to_string(scene_bands(*s, top_index)));
+        return HARE_E_INVALID;
+    }
+    if (max_pairs < 1 || max_pairs > ((int64_t)1 << 26)) {
+        set_error(std::string(who) + ": max_pairs out of range (1 .. 2^26)");
+        return HARE_E_INVALID;
+    }
+    if (!d_work || !d_hist || !d_detections || ((uintptr_t)d_work & 15u)) {
+        set_error(std::string(who) + ": null work array / histogram / detections, or a work array off a 16-byte boundary");
+        return HARE_E_INVALID;
+    }
+    const size_t K = std::max<size_t>(1, s->rcv.size() / 4);
+    const struct { const void* p; size_t bytes; } bufs[] = {{d_work, (size_t)HARE_IMAGE_WORK_BYTES(K, s->topos[(size_t)top_index].P, max_pairs)},
+                                                            {d_hist, receive_hist_words(*s, top_index, n_bins, flags, 1) * sizeof(uint64_t)},
+                                                            {d_detections, K * 2 * sizeof(uint64_t)}};
+    for (size_t x = 0; x < 3; ++x)
+        for (size_t y = x + 1; y < 3; ++y)
+            if (ranges_overlap(bufs[x].p, bufs[x].bytes, bufs[y].p, bufs[y].bytes)) {
+                set_error(std::string(who) + ": work array, histogram and detections must not overlap");
+                return HARE_E_INVALID;
+            }
+    GUARD_BEGIN
+    const HipApi* H = api_or_err();
+    if (!H) return HARE_E_NODEVICE;
+    DeviceGuard dev_guard(H, s->device);
+    if (!s->module) {
+        int rc = ensure_device(*s, H);
+        if (rc) return rc;
+    }
+    if (int rc = source_ready(*s, H, who)) return rc;
+    if (int rc = upload_polys(*s, H)) return rc;
+    if (int rc = receive_ready(*s, H, who)) return rc;
+    return image_enqueue(*s, H, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, max_pairs, d_work, d_hist, d_detections,
+                         (hipStream_t)stream);
+    GUARD_END
+}
+
 int hare_hist_reduce_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
                             int32_t n_win, const int32_t* win, int32_t n_lev, const uint32_t* levels, void* d_sums, void* d_cross, void* stream)
 {
@@ -918,7 +1037,7 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
         return HARE_E_INVALID;
     }
     if (int rc = receive_check_args("hare_receive_device", *s, flags, kind, top_index, n, bounces, n_bins, bin_len, frac_bits)) return rc;
-    if ((flags & HARE_RECEIVE_DIRECT) && s->src.set && s->src.B != scene_bands(*s, top_index)) {
+    if ((flags & (HARE_RECEIVE_DIRECT | HARE_RECEIVE_IMAGE)) && s->src.set && s->src.B != scene_bands(*s, top_index)) {
         set_error("hare_receive_device: the source has " + std::to_string(s->src.B) + " bands, the topology " + std::to_string(scene_bands(*s, top_index)));
         return HARE_E_INVALID;
     }
@@ -958,7 +1077,7 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
     }
     if (int rc = upload_polys(*s, H)) return rc;
     if (int rc = receive_ready(*s, H, "hare_receive_device")) return rc;
-    if (flags & HARE_RECEIVE_DIRECT)      // suppression only, but of the SOURCE's direct sound: hare_direct_device deposits it
+    if (flags & (HARE_RECEIVE_DIRECT | HARE_RECEIVE_IMAGE))      // suppression only, but of the SOURCE's paths: hare_direct_device / hare_image_device deposit them
         if (int rc = source_ready(*s, H, "hare_receive_device")) return rc;
     if (n == 0) return HARE_OK;
     ReceivePlan plan;

@@ -271,13 +271,25 @@ static __device__ __forceinline__ void receive_body(const Args& a)
 #pragma unroll
     for (int b = 0; b < kMaxBands; ++b) E[b] = 0;
     bool rained = false;
+    // HARE_RECEIVE_IMAGE, cast 1 of the scatter kernels (kCutSkipSpecular, uniform): the first-order specular paths are hare_image_deposit's, so
+    // a ray whose reflection behind cast 0 was specular -- !(u_0 < p) at c = 0 for the polygon it is leaving, its mark -- runs no receiver step
+    bool imaged = false;
+    if constexpr (SCATTER) {
+        if ((a.cut & kCutSkipSpecular) && live && a.excl[i] >= 0) {
+            const double* sg = a.sigma + (size_t)a.excl[i] * (size_t)B;
+            double p = sg[0];
+            for (int b = 1; b < B; ++b) p = p + sg[b];
+            p = p / (double)B;
+            imaged = !(scatter_u(scatter_mix(scatter_mix(a.seed + kScatterGamma) ^ (unsigned long long)(a.ray_base + i)), 0ull, 0) < p);
+        }
+    }
     if constexpr (MAP) {
         // the walk holds the ray, t_end and L only: the event and the energies are read behind it (nothing the walk adds to overlaps them)
         if (live) {
             r = a.rays[i];
             if (!a.init_state) L = a.state[i];
             const XEventRec& ei = a.ev[i];
-            if (!(a.cut & kCutSkipDetect)) map_receivers<DIR>(a, i, r, ei.hit ? ei.t : __builtin_inf(), L);
+            if (!(a.cut & kCutSkipDetect) && !imaged) map_receivers<DIR>(a, i, r, ei.hit ? ei.t : __builtin_inf(), L);
         }
     }
     if (live) {
@@ -296,7 +308,7 @@ static __device__ __forceinline__ void receive_body(const Args& a)
     }
     // ---- receivers
     if constexpr (!MAP) {                                                // the linear step; a map has taken its own, above
-        const bool seen = live && !rained;
+        const bool seen = live && !rained && !imaged;
         if (!(a.cut & kCutSkipDetect) && __ballot(seen) != 0ull) {      // kCutSkipDetect: cast 0 of a call with HARE_RECEIVE_DIRECT (uniform)
             const double t_end = (live && e.hit) ? e.t : __builtin_inf();
             const double nb = (double)a.n_bins;

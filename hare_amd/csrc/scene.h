@@ -64,6 +64,8 @@ struct SceneOptions {
     int receive_aggregate = 1; // 1: hare_receive_reflect sums a wave's histogram adds per distinct (receiver, bin) before one atomic; 0: an atomic per detecting lane (A/B).  Same results
     int receive_floor_bits = 0;    // f: the receive loop's energy floor F = 2^-f (0: off; include/hare_hip.h, "Termination")
     int receive_roulette = 0;      // 1: a ray under the floor plays Russian roulette (word 65 of the scattering RNG)
+    int image_max_pairs = 1 << 20; // HARE_RECEIVE_IMAGE on the host calls: the pair list's length (HARE_E_NOMEM when the scene yields more; include/hare_hip.h, "Image sources")
+    int image_cull = 1;            // 1: hare_image_pairs runs the conservative FP32 pre-cull ahead of the exact test; 0: the exact test on every pair (A/B).  Same results
     long long scatter_seed = 0;    // the scattering RNG's seed S (hare_receive_scatter; read as uint64 bits)
     long long source_seed = 0;     // the point source's seed S (hare_emit_source; read as uint64 bits)
     long long dev_order_ptr = 0;   // developer experiments (a `dev` scene only): a device array of n uint32, the order K1q takes the rays in (ShootIO::order)
@@ -130,6 +132,7 @@ struct DeviceModule {
     hipFunction_t emit_source = nullptr;                                   // source.hip
     hipFunction_t hist_reduce = nullptr;                                   // reduce.hip
     hipFunction_t direct_emit = nullptr, direct_deposit[2] = {};           // direct.hip ([1]: the _dir form)
+    hipFunction_t image_mirror = nullptr, image_pairs = nullptr, image_deposit[2] = {};   // image.hip ([1]: the _dir form)
     hipFunction_t voxel_occl_tri = nullptr, voxel_occl_quad = nullptr, voxel_occl_tri_g = nullptr, voxel_occl_quad_g = nullptr, octree_occl = nullptr, octree_occl_any = nullptr;
     hipFunction_t events_pack_slim = nullptr;
     hipFunction_t block_occ = nullptr;                                     // build_kernels.hip: hare_block_occ
@@ -255,7 +258,8 @@ struct Scene {
         void* rain = nullptr;           // hare_receive_batch with HARE_RECEIVE_DIFFUSE_RAIN: the loop's work array with the rain's scratch
         void* red = nullptr;            // hare_receive_*_reduced: the sums, the crossings and the weights of hare_hist_reduce
         void* direct = nullptr;         // hare_receive_source* with HARE_RECEIVE_DIRECT: hare_direct_device's scratch, HARE_DIRECT_WORK_BYTES(K)
-        size_t state_cap = 0, hist_cap = 0, rain_cap = 0, red_cap = 0, direct_cap = 0;     // bytes
+        void* image = nullptr;          // hare_receive_source* with HARE_RECEIVE_IMAGE: hare_image_device's scratch, HARE_IMAGE_WORK_BYTES(K, P, "image_max_pairs"), grown on demand
+        size_t state_cap = 0, hist_cap = 0, rain_cap = 0, red_cap = 0, direct_cap = 0, image_cap = 0;     // bytes
         int64_t cap = 0;
         int32_t ctr_cap = 0;
         hipStream_t copy_st = nullptr;
@@ -370,6 +374,8 @@ struct ReceivePlan {
     bool directional = false;   // HARE_RECEIVE_DIRECTIONAL: args.hist has four channels per word and the _dir kernels run
     bool map = false;           // the scene holds a receiver map: the _map kernels run (never with rain)
     bool skip_cast0 = false;    // HARE_RECEIVE_DIRECT: cast 0 runs no receiver step (kCutSkipDetect in that cast's args.cut only)
+    bool skip_cast1_specular = false;   // HARE_RECEIVE_IMAGE: in cast 1 the rays that left cast 0 specularly run no receiver step (kCutSkipDetect without a
+                                // scattering table, kCutSkipSpecular with one; in that cast's args.cut only)
 };
 inline int receive_form(const ReceivePlan& p)      // DeviceModule::receive's first index
 {
@@ -413,6 +419,12 @@ int emit_source(const Scene& s, const HipApi* H, int64_t n, int64_t first_ray, v
 // Source and receivers must be on the device (source_ready, receive_ready)
 int direct_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                    int32_t frac_bits, void* d_work, void* d_hist, void* d_det, hipStream_t st);
+// first-order image sources (receive.cpp; include/hare_hip.h, "receivers", "Image sources (first order)").  image_enqueue: hare_image_mirror,
+// hare_image_pairs, ONE flags-only occlusion query of 2 * max_pairs slots and hare_image_deposit[_dir] on the stream; d_work:
+// HARE_IMAGE_WORK_BYTES(K, P, max_pairs) of scratch from a 16-byte boundary, its first word the number of pairs found.  Source, receivers and
+// tables must be on the device
+int image_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                  int32_t frac_bits, int64_t max_pairs, void* d_work, void* d_hist, void* d_det, hipStream_t st);
 // The reduction of a receive histogram (receive.cpp; include/hare_hip.h, "receivers", "Reduction").  ReduceSpec: what the caller asks for,
 // host pointers (weight: n_bins x B, nullable).  reduce_check_spec: the checks that need no buffer (HARE_E_INVALID); reduce_enqueue:
 // hare_hist_reduce on the stream, device buffers, win and levels read here

@@ -85,6 +85,9 @@ extern "C" {
 #define HARE_RECEIVE_TIME_LIMIT 512u   /* the same three calls only: a ray whose path has passed the histogram's end is retired ("receivers", "Termination")  */
 #define HARE_RECEIVE_DIRECT 1024u      /* hare_receive_source / _sharded / _reduced and hare_receive_device only: the direct sound is deposited once per  */
                                        /* receiver, visibility-tested, and cast 0's receiver step is skipped ("receivers", "Direct sound")               */
+#define HARE_RECEIVE_IMAGE 2048u       /* the same calls only: the first-order specular reflections are deposited once per (receiver, polygon) pair,      */
+                                       /* visibility-tested, and cast 1's receiver step is skipped for the rays that left cast 0 specularly               */
+                                       /* ("receivers", "Image sources (first order)").  The next bit, 0x1000, is the first developer bit                 */
 
 /* Hare.Geometry.Ray (Hare_Geometry_Primitives.cs:393-429): origin + direction.  Ray_ID/ThreadID
  * only serve the reference's mailbox pool and are not needed here. 48 bytes. */
@@ -654,6 +657,67 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * each chunk rounds f * n_chunk on its own.  A caller who wants the bits of the one call makes ONE hare_direct_device deposit with the
  * whole count and runs the chunks through hare_receive_device with the flag.
  *
+ * Image sources (first order) (flag HARE_RECEIVE_IMAGE; hare_image_device).  First-order specular reflections need no sampling either:
+ * for each polygon the source is mirrored in its plane, and for each receiver the path exists if the segment from the image to the
+ * receiver's center passes through that polygon; it counts if both of its legs are unoccluded.  This is the image-source method at order 1:
+ * ONE deposit per (receiver, polygon) pair instead of the few rays per million that happen to take that path.  All arithmetic is FP64 with
+ * no contraction, in this order.  pos, power[b] and gain_b are the scene's source; polygon p of top_index has corners v0..v2 (v3 for a
+ * quadrilateral) and the stored n = Normal(p); alpha[p][b] and sigma[p][b] are the topology's rows (a missing table is all 0); c and rr are
+ * receiver k as stored; W = (double)n_weight.
+ * Per polygon p:
+ *
+ *   h  = dot3(pos.x - v0.x, pos.y - v0.y, pos.z - v0.z, n.x, n.y, n.z)
+ *   nn = dot3(n, n)
+ *   mirrored  iff  nn > 0 && (h > 0 || h < 0)              (a NaN, or a source on the polygon's plane, h == 0: no image)
+ *   k2 = (2.0 * h) / nn
+ *   S' = (pos.x - n.x * k2, pos.y - n.y * k2, pos.z - n.z * k2)
+ *
+ * Per pair (k, p) with p mirrored, in any order (integer sums are order-free):
+ *
+ *   v  = c - S';  d2 = (vx*vx + vy*vy) + vz*vz;  eligible iff d2 > rr
+ *   on_poly = poly_fast(p, v3, o = S', d = v, t)  &&  t > 0.0 && t < 1.0
+ *             (the reference's two-sided Triangle / Quadrilateral.Intersect, Ray_Side and the 1e-6 determinant threshold included)
+ *   x  = (S'.x + vx*t, S'.y + vy*t, S'.z + vz*t)            the reflection point
+ *   occluded = hare_occluded(origin x, direction c - x,   poly_origin1 = p, t_max = 1.0)
+ *           || hare_occluded(origin x, direction pos - x, poly_origin1 = p, t_max = 1.0)
+ *   if eligible && on_poly && !occluded:
+ *     dist = sqrt(d2);  y = rr / d2;  f = (0.5 * y) / (1.0 + sqrt(1.0 - y))          as in "Direct sound"
+ *     g_b  = gain_b(x - pos)                                 "Source"'s lookup, not normalised; 1.0 without a table
+ *     r_b  = (1.0 - alpha[p][b]) * (1.0 - sigma[p][b])
+ *     m_b  = (((power[b] * g_b) * r_b) * (f * W)) * 2^frac_bits      then quantised exactly as the direct deposit's m_b
+ *     xb   = dist / bin_len                                  binned as in the receiver step
+ *     hist[(k*n_bins + bin)*B + b] += q_b;   detections[2k] += 1 if binned, detections[2k+1] += 1 otherwise
+ *     directional: a = ( -(vx / dist), -(vy / dist), -(vz / dist) ), channels as in "Directional" with this m_b
+ *
+ * What the caller has to know.  Visibility and the on-polygon test go to the receiver's CENTER only: a sphere whose cone a polygon's edge
+ * clips counts wholly or not at all.  A center path through an edge shared by two coplanar polygons is accepted by both (the test is
+ * inclusive, as in the tracer): a set of measure zero.  Each facet of a tessellated curved surface is its own mirror.  The arrival is at
+ * dist, the path length to the center.  r_b is the expected specular share of the sampled loop: absorption, then probability 1 - p times
+ * the weight (1 - sigma_b) / (1 - p).  The pair search runs a conservative FP32 pre-cull ahead of the exact test (scene option
+ * "image_cull", default 1; 0: the exact test on every pair): it only rejects what the exact test rejects, the results are the same.
+ * Suppression.  In a call with the flag, a ray skips cast 1's receiver step iff its reflection behind cast 0 was specular: no add, no
+ * detection.  On a topology without a scattering table that is every ray; with one it is exactly the rays with !(u_0 < p) at c = 0 for
+ * the polygon they hit in cast 0 -- the draw is counter-based, so cast 1 recomputes it from g, "scatter_seed" and the polygon the ray is
+ * leaving.  Rays that went diffuse detect as before (with HARE_RECEIVE_DIFFUSE_RAIN they skip already).  State, draws, weights, rain,
+ * termination, reflection, events and counters are those of the call without the flag.  Hence, on a topology without a scattering table
+ * and for bounces >= 2, word for word in wrapping uint64 and for detections alike:
+ *
+ *   hist(flag, bounces) = hist(no flag, bounces) - hist(no flag, 2) + hist(no flag, 1) + image
+ *
+ * With bounces == 1 nothing is suppressed and the deposit is still made.
+ * Where the flag is accepted: exactly where HARE_RECEIVE_DIRECT is.  hare_receive_source, hare_receive_source_sharded and
+ * hare_receive_source_reduced: suppression plus the deposit with n_weight = n, before cast 0; in the sharded call ONE scene makes the
+ * deposit, once, chosen as for the direct sound.  hare_receive_device: suppression only.  hare_receive_batch, hare_receive_batch_sharded
+ * and hare_receive_batch_reduced: HARE_E_INVALID, refused before anything runs.  The flag combines freely with HARE_RECEIVE_DIRECT,
+ * directional channels, rain, the termination rules and receiver maps.  No source set: HARE_E_STATE.  The source's B differing from the
+ * topology's: HARE_E_INVALID.
+ * The pair list.  Accepted pairs go to a list of max_pairs records; the host calls size it from the scene option "image_max_pairs"
+ * (default 2^20, 1 .. 2^26).  If the scene yields more pairs, the deposit kernels add NOTHING at all (the count is order-free, so this
+ * outcome is deterministic) and the host calls return HARE_E_NOMEM with the needed count in hare_last_error(); their outputs then hold the
+ * sampled loop without the image sources.
+ * Chunking.  As for the direct sound: a caller who wants the bits of the one call makes ONE hare_image_device deposit with the whole count
+ * and runs the chunks through hare_receive_device with the flag.
+ *
  * The histogram is fixed point in uint64: integer sums do not depend on the order of the adds, so the result is bit-identical from
  * run to run, between the one-device and the sharded call, and against a restatement on the host.  (r*r is formed once, when the
  * receivers are set: the same FP64 product.)
@@ -779,7 +843,8 @@ HARE_API int hare_emit_device(hare_scene *s, int64_t n, int64_t first_ray, void 
  *   d_hist         K x n_bins x B uint64 (x 4 with HARE_RECEIVE_DIRECTIONAL), ACCUMULATED;  d_detections: 2 K uint64, ACCUMULATED
  *   d_counters     nullable: totals, ACCUMULATED (as hare_bounce_device's; the rain's occlusion queries are not counted)
  *   flags          HARE_SHOOT_COUNT_WORK / HARE_SHOOT_SIMPLE_KERNEL (the casts), HARE_RECEIVE_DIFFUSE_RAIN, HARE_RECEIVE_DIRECTIONAL,
- *                  HARE_RECEIVE_TIME_LIMIT and HARE_RECEIVE_DIRECT (suppression only: "Direct sound"); other bits are ignored.  With
+ *                  HARE_RECEIVE_TIME_LIMIT, HARE_RECEIVE_DIRECT and HARE_RECEIVE_IMAGE (suppression only: "Direct sound", "Image sources");
+ *                  other bits are ignored.  With
  *                  HARE_RECEIVE_DIFFUSE_RAIN d_work holds HARE_RECEIVE_RAIN_WORK_BYTES(n) bytes: the 2 n int32, then the rain's scratch
  * Arguments are checked before anything runs (HARE_E_INVALID): kind, top_index, 0 <= n <= 2^31 - 256, 1 <= bounces <= 4096,
  * n_bins >= 1, bin_len finite and > 0, 0 <= frac_bits <= 62, K x n_bins x B <= 2^27 (K x n_bins x B x 4 <= 2^27 with
@@ -800,6 +865,18 @@ HARE_API int hare_receive_device(hare_scene *s, int32_t kind, int32_t top_index,
 #define HARE_DIRECT_WORK_BYTES(K) (64 * (int64_t)(K) + 256)
 HARE_API int hare_direct_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL only */,
                                 int32_t n_bins, double bin_len, int32_t frac_bits, void *d_work, void *d_hist, void *d_detections, void *stream);
+/* The first-order image sources' deposit on DEVICE buffers ("receivers", "Image sources (first order)"): the pair search receivers x
+ * polygons, one occlusion query of two shadow rays per accepted pair and one deposit per pair with both legs free, from the scene's source,
+ * standing for n_weight source rays.  Stream-ordered like hare_direct_device: no allocation, no free, no wait.  d_hist and d_detections
+ * are ACCUMULATED, shaped as hare_direct_device's.  d_work is scratch of HARE_IMAGE_WORK_BYTES(K, P, max_pairs) bytes on a 16-byte
+ * boundary (P: the polygons of Model[top_index]): a 256-byte head whose first 8-byte word receives the number of pairs found, the P images,
+ * and the list of max_pairs records (two shadow rays, their t_max and exclusion words, k and p, two flags), in unspecified order.  If more
+ * than max_pairs pairs are found nothing is deposited; the caller reads the count from the first word behind the stream.
+ * Checked as hare_direct_device checks, in its order, plus 1 <= max_pairs <= 2^26 and the work array's boundary (HARE_E_INVALID). */
+#define HARE_IMAGE_WORK_BYTES(K, P, max_pairs) (256 + 32 * (int64_t)(P) + 136 * (int64_t)(max_pairs) + 0 * (int64_t)(K))
+HARE_API int hare_image_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL only */,
+                               int32_t n_bins, double bin_len, int32_t frac_bits, int64_t max_pairs, void *d_work, void *d_hist,
+                               void *d_detections, void *stream);
 /* The same from host buffers (threading and staging as hare_bounce_batch's last-cast-only path: one enqueue, one synchronisation; no
  * events are downloaded).  state_in nullable (every ray starts at L = 0, E = 1); state_out nullable ((1 + B) x n, as d_state).
  * hist (K x n_bins x B, x 4 with HARE_RECEIVE_DIRECTIONAL) and detections (2 K) are WRITTEN, not accumulated; ctr nullable: counters summed over the casts.  flags as
@@ -822,7 +899,7 @@ HARE_API int hare_receive_batch_sharded(hare_scene *const *scenes, int32_t n_sce
  * emits from first_ray + lo.  Flags, checks and outputs as hare_receive_batch's, and HARE_E_INVALID when first_ray < 0 or
  * first_ray + n > 2^62, or when the source's B is not the band count of Model[top_index]; HARE_E_STATE when no source is set.  The sharded
  * call also refuses scenes whose source or "source_seed" differ.  These calls (and hare_receive_source_reduced) take HARE_RECEIVE_DIRECT
- * ("Direct sound"); the hare_receive_batch calls refuse it. */
+ * ("Direct sound") and HARE_RECEIVE_IMAGE ("Image sources (first order)"); the hare_receive_batch calls refuse both. */
 HARE_API int hare_receive_source(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, int64_t first_ray, int32_t bounces,
                                  uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits, double *state_out, uint64_t *hist,
                                  uint64_t *detections, hare_counters *ctr);

@@ -29,9 +29,13 @@ of hare_receive_source with and without the flag, interleaved, the median of --r
 and for a plane of at most 4 096 receivers as a map; and the gain in noise -- the relative spread over 8 values of "source_seed" of one
 mid-hall receiver's summed 0 - 50 ms window (band 0; 17.15 m of path), with and without the flag, beside the cast-0 rays that receiver got.
 Run it under rocprofv3 --kernel-trace --stats for the three kernels' own times.
+With --source --direct --image, the first-order image sources too ("Image sources (first order)": HARE_RECEIVE_IMAGE): the same run with two
+more calls interleaved, `direct + image` with the pair search's pre-cull (scene option "image_cull" 1) and without it (0), their wall
+times and the same noise figure for `direct + image`.  With --image-cull N as well (a profiling run: rocprofv3 --kernel-trace --stats, one
+run per N, then tools/image_kernel_times.py on the two traces), only `direct` and `direct + image` with "image_cull" N run, and no noise.
 Prints ONE JSON line.  usage: python tools/receiver_rate.py [hall|cathedral] [--rays N] [--bounces B] [--reps R] [--host] [--quick]
                                                           [--scatter SIGMA] [--rain] [--directional] [--time-limit] [--floor-bits N [--roulette]]
-                                                          [--source [--direct]] [--map K[,K..]]"""
+                                                          [--source [--direct [--image [--image-cull N]]]] [--map K[,K..]]"""
 import argparse
 import json
 import os
@@ -60,6 +64,8 @@ ap.add_argument("--floor-bits", type=int, default=0, metavar="N", help="the loop
 ap.add_argument("--roulette", action="store_true", help="with --floor-bits: Russian roulette under the floor (scene option receive_roulette)")
 ap.add_argument("--source", action="store_true", help="K = 8, B = 8: hare_receive_source against hare_receive_batch from host rays, wall time")
 ap.add_argument("--direct", action="store_true", help="with --source: hare_receive_source with and without HARE_RECEIVE_DIRECT, time and noise")
+ap.add_argument("--image", action="store_true", help="with --source --direct: also direct + HARE_RECEIVE_IMAGE, with and without the pair search's pre-cull")
+ap.add_argument("--image-cull", type=int, default=None, choices=[0, 1], metavar="N", help="with --image: a profiling run with \"image_cull\" N only")
 ap.add_argument("--map", default=None, metavar="K[,K..]", help="B = 8: receiver maps (planes of about K receivers, a cloud of 4096) against the linear loop at K = 256")
 a = ap.parse_args()
 if a.reps is None:
@@ -148,6 +154,16 @@ def direct_run():
         p.set_source(S, power=np.ones(B)).set_option("source_seed", 1)
         calls = {"plain": lambda p=p: p.Receive_source(n, nb, n_bins, bin_len, frac_bits=FRAC),
                  "direct": lambda p=p: p.Receive_source(n, nb, n_bins, bin_len, frac_bits=FRAC, direct=True)}
+        if a.image:
+            def imaged(cull, p=p):
+                p.set_option("image_cull", cull)
+                return p.Receive_source(n, nb, n_bins, bin_len, frac_bits=FRAC, direct=True, image=True)
+            if a.image_cull is None:
+                calls["direct_image"] = lambda: imaged(1)
+                calls["direct_image_nocull"] = lambda: imaged(0)
+            else:
+                del calls["plain"]
+                calls["direct_image"] = lambda: imaged(a.image_cull)
         for f in calls.values():
             f()                                                           # the warm-up
         wall = {k: [] for k in calls}
@@ -160,14 +176,25 @@ def direct_run():
         for k, v in wall.items():
             row[k + "_ms"] = round(float(np.median(v)), 3)
             row[k + "_min_max_ms"] = [round(min(v), 3), round(max(v), 3)]
-        row["direct_over_plain"] = round(row["direct_ms"] / row["plain_ms"], 4)
+        if "plain" in calls:
+            row["direct_over_plain"] = round(row["direct_ms"] / row["plain_ms"], 4)
+        if a.image:
+            row["image_added_ms"] = round(row["direct_image_ms"] - row["direct_ms"], 3)
+        if "direct_image_nocull" in calls:
+            row["image_nocull_added_ms"] = round(row["direct_image_nocull_ms"] - row["direct_ms"], 3)
+        if a.image_cull is not None:                                      # a profiling run: the kernels' times are the profiler's business
+            row["image_cull"] = a.image_cull
+            rows[name] = row
+            continue
         # the noise: one receiver about the middle of the hall, seen from the source
         mid = int(np.argmin(((c - size * np.array([0.6, 0.5, 0.0]) - np.array([0, 0, c[0, 2]])) ** 2).sum(axis=1))) if as_map else 0
-        e = {"plain": [], "direct": []}
+        e = {k: [] for k in calls if k != "direct_image_nocull"}
         cast0 = []
         for seed in range(8):
             p.set_option("source_seed", 100 + seed)
             for k, f in calls.items():
+                if k not in e:
+                    continue
                 e[k].append(float(f()[0][mid, :early, 0].astype(np.float64).sum()) * 2.0 ** -FRAC)
             cast0.append(int(p.Receive_source(n, 1, n_bins, bin_len, frac_bits=FRAC)[2][mid].sum()))
         row["receiver"] = mid
