@@ -225,9 +225,12 @@ public:
     // for the call's n rays, and cast 0 detects nothing.  image (HARE_RECEIVE_IMAGE; "Image sources (first order)"): the first-order specular
     // reflections are one visibility-tested deposit per (receiver, polygon) pair, and in cast 1 the rays that left cast 0 specularly detect
     // nothing; the pair list holds GetOption("image_max_pairs") pairs (std::runtime_error, HARE_E_NOMEM with the needed count, when the scene yields more).
+    // image2 (HARE_RECEIVE_IMAGE2, only with image; "Image sources (second order)"): the specular paths off two polygons are one deposit each
+    // and in cast 2 the rays reflected specularly twice detect nothing; the lists hold GetOption("image2_max_cands") candidates and
+    // GetOption("image2_max_paths") paths (std::runtime_error, HARE_E_NOMEM with both counts, when the scene yields more).
     uint64_t ReceiveSource(int64_t n, int64_t first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
                            std::vector<uint64_t>& hist, std::vector<uint64_t>& detections, std::vector<double>* state_out = nullptr,
-                           bool rain = false, bool directional = false, bool direct = false, bool image = false)
+                           bool rain = false, bool directional = false, bool direct = false, bool image = false, bool image2 = false)
     {
         if (n < 0) throw std::invalid_argument("ReceiveSource: n must be >= 0");
         const int64_t K = GetOption("receivers"), B = Bands(top_index);
@@ -237,7 +240,7 @@ public:
         hare_counters c{};
         check(hare_receive_source(scene_, kind_, top_index, n, first_ray, bounces,
                                   (rain ? HARE_RECEIVE_DIFFUSE_RAIN : 0u) | (directional ? HARE_RECEIVE_DIRECTIONAL : 0u) |
-                                      (direct ? HARE_RECEIVE_DIRECT : 0u) | (image ? HARE_RECEIVE_IMAGE : 0u),
+                                      (direct ? HARE_RECEIVE_DIRECT : 0u) | (image ? HARE_RECEIVE_IMAGE : 0u) | (image2 ? HARE_RECEIVE_IMAGE2 : 0u),
                                   n_bins, bin_len, frac_bits, state_out ? state_out->data() : nullptr, hist.data(), detections.data(), &c));
         return c.hits;
     }
@@ -260,6 +263,16 @@ public:
     {
         check(hare_image_device(scene_, kind_, top_index, n_weight, directional ? HARE_RECEIVE_DIRECTIONAL : 0u, n_bins, bin_len, frac_bits,
                                 max_pairs, d_work, d_hist, d_detections, stream));
+    }
+    // hare_image2_device on device pointers and a hipStream_t: the second-order image sources' deposit alone, ACCUMULATED into d_hist and
+    // d_detections; d_work holds Image2WorkBytes(P, max_cands, max_paths) bytes on a 16-byte boundary, and its first two uint64 receive the
+    // candidates and the paths found (either beyond its list: nothing was deposited).  Stream-ordered.
+    static int64_t Image2WorkBytes(int64_t P, int64_t max_cands, int64_t max_paths) { return HARE_IMAGE2_WORK_BYTES(P, max_cands, max_paths); }
+    void Image2Device(int top_index, int64_t n_weight, int n_bins, double bin_len, int frac_bits, int64_t max_cands, int64_t max_paths, void* d_work,
+                      void* d_hist, void* d_detections, bool directional = false, void* stream = nullptr)
+    {
+        check(hare_image2_device(scene_, kind_, top_index, n_weight, directional ? HARE_RECEIVE_DIRECTIONAL : 0u, n_bins, bin_len, frac_bits,
+                                 max_cands, max_paths, d_work, d_hist, d_detections, stream));
     }
     // the reduction of a histogram on the device (include/hare_hip.h, "receivers", "Reduction"): per receiver and band, the sums S0 = sum g
     // and S1 = sum i g over bin windows and the bins at which the backward-integrated decay crosses the levels.  What to compute:
@@ -322,7 +335,8 @@ public:
     }
     uint64_t ReceiveSourceReduced(int64_t n, int64_t first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
                                   const Reduction& r, std::vector<uint64_t>& sums, std::vector<int32_t>& cross, std::vector<uint64_t>& detections,
-                                  std::vector<double>* state_out = nullptr, bool directional = false, bool direct = false, bool image = false)
+                                  std::vector<double>* state_out = nullptr, bool directional = false, bool direct = false, bool image = false,
+                                  bool image2 = false)
     {
         if (n < 0) throw std::invalid_argument("ReceiveSourceReduced: n must be >= 0");
         const int64_t K = GetOption("receivers"), B = Bands(top_index);
@@ -334,7 +348,7 @@ public:
         hare_counters c{};
         check(hare_receive_source_reduced(scene_, kind_, top_index, n, first_ray, bounces,
                                           (directional ? HARE_RECEIVE_DIRECTIONAL : 0u) | (direct ? HARE_RECEIVE_DIRECT : 0u) |
-                                              (image ? HARE_RECEIVE_IMAGE : 0u),
+                                              (image ? HARE_RECEIVE_IMAGE : 0u) | (image2 ? HARE_RECEIVE_IMAGE2 : 0u),
                                           n_bins,
                                           bin_len, frac_bits, state_out ? state_out->data() : nullptr,
                                           r.weight.empty() ? nullptr : r.weight.data(), n_win, r.windows.data(), n_lev, r.levels.data(), sums.data(),

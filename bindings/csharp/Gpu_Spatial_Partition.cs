@@ -350,10 +350,13 @@ namespace Hare
             /// direct (HARE_RECEIVE_DIRECT; include/hare_hip.h, "Direct sound"): the direct sound is one visibility-tested deposit per receiver
             /// and cast 0 detects nothing.  image (HARE_RECEIVE_IMAGE; "Image sources (first order)"): the first-order specular reflections are
             /// one deposit per (receiver, polygon) pair and in cast 1 the rays that left cast 0 specularly detect nothing; the pair list holds
-            /// GetOption("image_max_pairs") pairs (HARE_E_NOMEM with the needed count when the scene yields more).</summary>
+            /// GetOption("image_max_pairs") pairs (HARE_E_NOMEM with the needed count when the scene yields more).  image2
+            /// (HARE_RECEIVE_IMAGE2, only with image; "Image sources (second order)"): the specular paths off two polygons are one deposit
+            /// each and in cast 2 the rays reflected specularly twice detect nothing; the lists hold GetOption("image2_max_cands") and
+            /// GetOption("image2_max_paths") records (HARE_E_NOMEM with both counts).</summary>
             public long ReceiveSource(long n, long first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits, ulong[] hist,
                                       ulong[] detections, double[] state = null, bool rain = false, bool directional = false, bool direct = false,
-                                      bool image = false)
+                                      bool image = false, bool image2 = false)
             {
                 if (n < 0) throw new ArgumentException("n must be at least 0");
                 if (bounces < 1) throw new ArgumentException("bounces must be at least 1");
@@ -363,7 +366,8 @@ namespace Hare
                 if (state != null && state.LongLength < (1 + B) * n) throw new ArgumentException("state must hold (1 + Bands(top_index)) x n values");
                 hare_counters ctr;
                 uint flags = (rain ? HareHip.HARE_RECEIVE_DIFFUSE_RAIN : 0u) | (directional ? HareHip.HARE_RECEIVE_DIRECTIONAL : 0u) |
-                             (direct ? HareHip.HARE_RECEIVE_DIRECT : 0u) | (image ? HareHip.HARE_RECEIVE_IMAGE : 0u);
+                             (direct ? HareHip.HARE_RECEIVE_DIRECT : 0u) | (image ? HareHip.HARE_RECEIVE_IMAGE : 0u) |
+                             (image2 ? HareHip.HARE_RECEIVE_IMAGE2 : 0u);
                 HareHip.Check(HareHip.hare_receive_source_sharded(scenes, scenes.Length, Kind, top_index, n, first_ray, bounces, flags, n_bins, bin_len,
                                                                   frac_bits, state, hist, detections, out ctr));
                 return (long)ctr.hits;
@@ -373,11 +377,11 @@ namespace Hare
             /// hare_receive_source_reduced; include/hare_hip.h, "Reduction"): the histogram never comes down.  win holds n_win pairs
             /// lo, hi of bins; levels fractions in units of 2^-32 (DecayLevel); weight n_bins x B values in units of 2^-32 (AirWeights) or
             /// null.  sums: receivers x B x n_win x 4 (S0 lo, S0 hi, S1 lo, S1 hi); cross: receivers x B x levels.Length.  rays null: the
-            /// scene's source emits n rays from first_ray.  One scene only: a crossing is not additive over shards.  direct, image: as in
+            /// scene's source emits n rays from first_ray.  One scene only: a crossing is not additive over shards.  direct, image, image2: as in
             /// ReceiveSource (with rays of the caller's the library refuses them).</summary>
             public long ReceiveReduced(hare_ray[] rays, long n, long first_ray, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
                                        uint[] weight, int[] win, uint[] levels, ulong[] sums, int[] cross, ulong[] detections, double[] state = null,
-                                       bool directional = false, bool direct = false, bool image = false)
+                                       bool directional = false, bool direct = false, bool image = false, bool image2 = false)
             {
                 if (scenes.Length != 1) throw new NotSupportedException("ReceiveReduced runs on one scene: reduce the histogram of the sharded Receive with HistReduce");
                 if (bounces < 1) throw new ArgumentException("bounces must be at least 1");
@@ -393,7 +397,7 @@ namespace Hare
                 if (state != null && state.LongLength < (1 + B) * n) throw new ArgumentException("state must hold (1 + Bands(top_index)) x n values");
                 hare_counters ctr;
                 uint flags = (directional ? HareHip.HARE_RECEIVE_DIRECTIONAL : 0u) | (direct ? HareHip.HARE_RECEIVE_DIRECT : 0u) |
-                             (image ? HareHip.HARE_RECEIVE_IMAGE : 0u);
+                             (image ? HareHip.HARE_RECEIVE_IMAGE : 0u) | (image2 ? HareHip.HARE_RECEIVE_IMAGE2 : 0u);
                 if (rays != null)
                     HareHip.Check(HareHip.hare_receive_batch_reduced(scenes[0], Kind, top_index, n, rays, null, null, bounces, flags, n_bins, bin_len, frac_bits,
                                                                      null, state, weight, n_win, win, n_lev, levels, sums, cross, detections, out ctr));

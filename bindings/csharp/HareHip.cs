@@ -113,6 +113,9 @@ namespace Hare
             // the same calls: the first-order specular reflections are one visibility-tested deposit per (receiver, polygon) pair and in cast 1
             // the rays that left cast 0 specularly detect nothing (include/hare_hip.h, "Image sources (first order)")
             public const uint HARE_RECEIVE_IMAGE = 2048;
+            // the same calls, only together with HARE_RECEIVE_IMAGE: the second-order specular reflections are one deposit per (receiver, polygon,
+            // polygon) path and in cast 2 the rays reflected specularly twice detect nothing ("Image sources (second order)")
+            public const uint HARE_RECEIVE_IMAGE2 = 65536;
 
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr hare_last_error();
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int hare_device_count(out int count);
@@ -277,6 +280,11 @@ namespace Hare
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_image_device(IntPtr scene, int kind, int top_index, long n_weight, uint flags, int n_bins, double bin_len,
                                                        int frac_bits, long max_pairs, IntPtr d_work, IntPtr d_hist, IntPtr d_detections, IntPtr stream);
+            // the second-order image sources' deposit on device buffers ("Image sources (second order)"); d_work: 256 + 32 P + 32 max_cands + 212 max_paths bytes
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_image2_device(IntPtr scene, int kind, int top_index, long n_weight, uint flags, int n_bins, double bin_len,
+                                                        int frac_bits, long max_cands, long max_paths, IntPtr d_work, IntPtr d_hist, IntPtr d_detections,
+                                                        IntPtr stream);
             // the reduction of a histogram on the device (include/hare_hip.h, "receivers", "Reduction")
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_hist_reduce_device(IntPtr scene, int K, int n_bins, int B, int channels, IntPtr d_hist, IntPtr d_weight,

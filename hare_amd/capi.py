@@ -23,6 +23,7 @@ RECEIVE_DIRECTIONAL = 256           # hare_receive_*: four channels per histogra
 RECEIVE_TIME_LIMIT = 512            # hare_receive_*: retire a ray whose path has passed the histogram's end (include/hare_hip.h, "Termination")
 RECEIVE_DIRECT = 1024               # hare_receive_source* / hare_receive_device: the direct sound deposited per receiver, cast 0 not detected ("Direct sound")
 RECEIVE_IMAGE = 2048                # the same calls: first-order specular reflections deposited per (receiver, polygon) pair, cast 1 not detected for specular rays ("Image sources (first order)")
+RECEIVE_IMAGE2 = 65536              # the same calls, only with RECEIVE_IMAGE: second-order specular reflections deposited per (receiver, polygon, polygon) path ("Image sources (second order)")
 
 RAY_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("dx", "<f8"), ("dy", "<f8"), ("dz", "<f8")])
 XEVENT_DTYPE = np.dtype(
@@ -118,6 +119,7 @@ SYMBOLS = {
     "hare_emit_device": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "hare_direct_device": (C.c_int, [_vp, _i32, _i32, _i64, _u32, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "hare_image_device": (C.c_int, [_vp, _i32, _i32, _i64, _u32, _i32, C.c_double, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "hare_image2_device": (C.c_int, [_vp, _i32, _i32, _i64, _u32, _i32, C.c_double, _i32, _i64, _i64, _vp, _vp, _vp, _vp]),
     "hare_receive_source": (C.c_int, [_vp, _i32, _i32, _i64, _i64, _i32, _u32, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "hare_receive_source_sharded": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i64, _i32, _u32, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "hare_hist_reduce_device": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),

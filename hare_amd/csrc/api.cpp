@@ -902,6 +902,9 @@ const OptionEntry kOptionTable[] = {
         {"receive_roulette", &SceneOptions::receive_roulette, 0, 1},
         {"image_max_pairs", &SceneOptions::image_max_pairs, 1, 1 << 26},
         {"image_cull", &SceneOptions::image_cull, 0, 1},
+        {"image2_max_cands", &SceneOptions::image2_max_cands, 1, 1 << 26},
+        {"image2_max_paths", &SceneOptions::image2_max_paths, 1, 1 << 26},
+        {"image2_prune", &SceneOptions::image2_prune, 0, 1},
 };
 }  // namespace
 

@@ -43,7 +43,7 @@ void free_bounce_buffers(const HipApi* H, Scene& s)
         Scene::BounceBuf& b = c.bounce;
         if (b.copy_st) { (void)H->StreamSynchronize(b.copy_st); (void)H->StreamDestroy(b.copy_st); b.copy_st = nullptr; }
         for (void** p : {&b.rays[0], &b.rays[1], &b.excl[0], &b.excl[1], &b.excl2, &b.idx[0], &b.idx[1], &b.ev[0], &b.ev[1], &b.full,
-                         &b.tiles, &b.ctr, &b.state, &b.hist, &b.rain, &b.red, &b.direct, &b.image})
+                         &b.tiles, &b.ctr, &b.state, &b.hist, &b.rain, &b.red, &b.direct, &b.image, &b.image2, &b.spec2})
             dev_free(H, *p);
         b.cap = 0;
         b.ctr_cap = 0;
@@ -53,6 +53,8 @@ void free_bounce_buffers(const HipApi* H, Scene& s)
         b.red_cap = 0;
         b.direct_cap = 0;
         b.image_cap = 0;
+        b.image2_cap = 0;
+        b.spec2_cap = 0;
     }
 }
 
@@ -237,6 +239,7 @@ struct ReceiveJob {
     bool from_source = false;  // hare_receive_source: rays and state come from hare_emit_source (rays from ray_base on), not from the caller
     int64_t direct_weight = 0; // HARE_RECEIVE_DIRECT: > 0 in the ONE scene that deposits the direct sound, for the call's whole n (else 0)
     int64_t image_weight = 0;  // HARE_RECEIVE_IMAGE: the same for the first-order image sources
+    int64_t image2_weight = 0; // HARE_RECEIVE_IMAGE2: the same for the second-order image sources
     const char* who = "hare_receive_batch";
     // hare_receive_*_reduced: the histogram stays in BounceBuf::hist and hare_hist_reduce runs behind the last cast; sums and cross come
     // down in its place (hist is null)
@@ -303,6 +306,22 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
         HIP_TRY(H->Malloc(&b.image, image_bytes));
         b.image_cap = image_bytes;
     }
+    const int64_t image2_cands = s.opt.image2_max_cands, image2_paths = s.opt.image2_max_paths;
+    const size_t image2_bytes = job.image2_weight > 0 ? (size_t)HARE_IMAGE2_WORK_BYTES(s.topos[(size_t)top].P, image2_cands, image2_paths) : 0;
+    if (image2_bytes > b.image2_cap) {
+        dev_free(H, b.image2);
+        b.image2_cap = 0;
+        HIP_TRY(H->Malloc(&b.image2, image2_bytes));
+        b.image2_cap = image2_bytes;
+    }
+    // the loop's byte per ray (ReceiveArgs::spec2): only a topology with a scattering table reads or writes it
+    const size_t spec2_bytes = ((job.flags & HARE_RECEIVE_IMAGE2) && scene_has_scattering(s, top)) ? (size_t)HARE_RECEIVE_IMAGE2_WORK_BYTES(n) : 0;
+    if (spec2_bytes > b.spec2_cap) {
+        dev_free(H, b.spec2);
+        b.spec2_cap = 0;
+        HIP_TRY(H->Malloc(&b.spec2, spec2_bytes));
+        b.spec2_cap = spec2_bytes;
+    }
     if (!c.st[0]) HIP_TRY(H->StreamCreate(&c.st[0]));
     hipStream_t st = c.st[0];
     uint64_t* const d_hist = (uint64_t*)b.hist;
@@ -329,10 +348,15 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
         if (int rc = image_enqueue(s, H, kind, top, job.image_weight, job.flags, job.n_bins, job.bin_len, job.frac_bits, image_pairs, b.image, d_hist,
                                    d_det, st))
             return rc;
+    if (job.image2_weight > 0)      // the second-order image sources, once per call (cast 2's receiver step is switched off for the twice-specular rays)
+        if (int rc = image2_enqueue(s, H, kind, top, job.image2_weight, job.flags, job.n_bins, job.bin_len, job.frac_bits, image2_cands, image2_paths,
+                                    b.image2, d_hist, d_det, st))
+            return rc;
     ReceivePlan plan;
     if (int rc = receive_plan(s, top, job.flags, n, job.n_bins, job.bin_len, job.frac_bits, d_state, d_hist, d_det, work,
                               job.state_in == nullptr && !job.from_source, job.ray_base, plan))
         return rc;
+    if (plan.args.spec2) plan.args.spec2 = (unsigned char*)b.spec2;      // the host calls keep the byte per ray in a buffer of its own, not behind `work`
     if (int rc = bounce_device_impl(s, H, kind, top, n, b.rays[0], excl1 ? b.excl[0] : nullptr, excl2 ? b.excl2 : nullptr, bounces, flags, work,
                                     nullptr, b.ev[0], nullptr, b.ctr, st, &plan))
         return rc;
@@ -357,7 +381,16 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
     HIP_TRY(H->MemcpyAsync(per_cast, b.ctr, (size_t)bounces * sizeof(hare_counters), hipMemcpyDeviceToHost, st));
     uint64_t image_found = 0;       // the pairs the search found: the last download, so that no return lies between it and the wait
     if (job.image_weight > 0) HIP_TRY(H->MemcpyAsync(&image_found, b.image, sizeof image_found, hipMemcpyDeviceToHost, st));
+    uint64_t image2_found[2] = {0, 0};      // candidates and paths
+    if (job.image2_weight > 0) HIP_TRY(H->MemcpyAsync(image2_found, b.image2, sizeof image2_found, hipMemcpyDeviceToHost, st));
     HIP_TRY(H->StreamSynchronize(st));
+    if (image2_found[0] > (uint64_t)image2_cands || image2_found[1] > (uint64_t)image2_paths) {      // nothing of the second order was deposited
+        set_error(std::string(job.who) + ": the scene yields " + std::to_string(image2_found[0]) + " second-order candidates and " +
+                  (image2_found[0] > (uint64_t)image2_cands ? std::string("an unknown number of") : std::to_string(image2_found[1])) +
+                  " paths, \"image2_max_cands\" is " + std::to_string(image2_cands) + " and \"image2_max_paths\" " + std::to_string(image2_paths) +
+                  " (needed: " + std::to_string(image2_found[0]) + ", " + std::to_string(image2_found[1]) + ")");
+        return HARE_E_NOMEM;
+    }
     if (image_found > (uint64_t)image_pairs) {      // the deposit kernels added nothing: the caller's results hold no image sources
         set_error(std::string(job.who) + ": the scene yields " + std::to_string(image_found) + " image-source pairs, \"image_max_pairs\" is " +
                   std::to_string(image_pairs) + " (needed: " + std::to_string(image_found) + ")");
@@ -563,6 +596,10 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
         set_error(std::string(who) + ": HARE_RECEIVE_IMAGE needs the scene's source (hare_receive_source, hare_receive_device + hare_image_device)");
         return HARE_E_INVALID;
     }
+    if ((flags & HARE_RECEIVE_IMAGE2) && !first_ray) {
+        set_error(std::string(who) + ": HARE_RECEIVE_IMAGE2 needs the scene's source (hare_receive_source, hare_receive_device + hare_image2_device)");
+        return HARE_E_INVALID;
+    }
     if ((n > 0 && !rays && !first_ray) || (!hist && !red) || !detections) {
         set_error(std::string(who) + ": null rays, histogram or detections");
         return HARE_E_INVALID;
@@ -663,6 +700,7 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
         // the direct sound is deposited once, for the whole n: by the first scene whose shard holds a ray (scenes[0] whenever n >= G)
         job.direct_weight = ((flags & HARE_RECEIVE_DIRECT) && hi > lo && lo == 0) ? n : 0;
         job.image_weight = ((flags & HARE_RECEIVE_IMAGE) && hi > lo && lo == 0) ? n : 0;
+        job.image2_weight = ((flags & HARE_RECEIVE_IMAGE2) && hi > lo && lo == 0) ? n : 0;
         job.who = who;
         job.reduce = red;
         job.sums = sums;

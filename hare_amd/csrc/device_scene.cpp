@@ -138,6 +138,11 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_image_pairs", &m->image_pairs},
         {"hare_image_deposit", &m->image_deposit[0]},
         {"hare_image_deposit_dir", &m->image_deposit[1]},
+        {"hare_image2_mirror", &m->image2_mirror},
+        {"hare_image2_cands", &m->image2_cands},
+        {"hare_image2_paths", &m->image2_paths},
+        {"hare_image2_deposit", &m->image2_deposit[0]},
+        {"hare_image2_deposit_dir", &m->image2_deposit[1]},
     };
     for (auto& t : table) {
         hipError_t e = H->ModuleGetFunction(t.fn, m->mod, t.name);

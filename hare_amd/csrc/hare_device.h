@@ -507,6 +507,8 @@ struct ReceiveArgs {
     // termination (include/hare_hip.h, "Termination"; last again): read under one wave-uniform branch on `cut`
     double floor;              // F = 2^-"receive_floor_bits" (kCutFloor)
     int32_t cut;               // kCut* bits; 0: no rule, the kernels behave as they did without them
+    // HARE_RECEIVE_IMAGE2, the scatter kernels, casts 1 and 2 only (kCutStoreSpecular2 / kCutSkipSpecular2; last, so that the fields above keep their offsets):
+    unsigned char* spec2;      // n bytes: 1 when the ray's reflections behind cast 0 AND behind cast 1 were both specular (null without the flag)
 };
 // The _map kernels (hare_scene_set_receiver_map): ReceiveArgs with the grid behind it, so that the kernels above keep their arguments,
 // byte for byte.  n_rcv is up to kMaxMapReceivers and rcv is not staged in LDS
@@ -527,6 +529,10 @@ constexpr int32_t kCutSkipDetect = 8; // HARE_RECEIVE_DIRECT, cast 0 only: no re
                                       // HARE_RECEIVE_IMAGE on a topology without a scattering table, cast 1 only (every reflection behind cast 0 was specular)
 constexpr int32_t kCutSkipSpecular = 16; // HARE_RECEIVE_IMAGE, the scatter kernels, cast 1 only: a ray whose reflection behind cast 0 was specular runs no
                                       // receiver step -- the choice recomputed from g, "scatter_seed" and the polygon it is leaving (its mark)
+// HARE_RECEIVE_IMAGE2 (kCutSkipDetect in cast 2 on a topology without a scattering table: every ray of cast 2 has been reflected specularly twice)
+constexpr int32_t kCutStoreSpecular2 = 32; // the scatter kernels, cast 1 only (beside kCutSkipSpecular): a live ray writes ReceiveArgs::spec2 -- cast 0's
+                                      // recomputed outcome AND this cast's own draw (made at the top of the body as well), both specular
+constexpr int32_t kCutSkipSpecular2 = 64; // the scatter kernels, cast 2 only: a ray whose spec2 byte is set runs no receiver step
 
 // hare_rain_step (receive.hip): diffuse rain between the shoot and the receive kernel of a cast -- the deposit of receiver k_dep's
 // visibility query (its flags in `socc`) and the emission of receiver k_emit's.  Reads what hare_receive_scatter_rain reads before it
@@ -637,6 +643,49 @@ struct ImageArgs {
     int32_t res;
     int32_t n_bins;
     int32_t use_cull;          // scene option "image_cull"
+};
+
+// hare_image2_mirror / _cands / _paths / _deposit[_dir] (image2.hip): second-order image sources (include/hare_hip.h, "receivers", "Image sources
+// (second order)").  The mirror writes img as hare_image_mirror does, zeroes the two counts and marks every shadow slot -2; the candidate
+// stage (a lane per first polygon p, the second polygons q streamed) appends (p, q, S''); the path stage (a lane per candidate, the receivers
+// streamed) appends, per accepted (k, candidate), its three shadow rays in srays[3 j .. 3 j + 2]: x2 -> center (exclusion q), x1 -> x2
+// (exclusions p and q), x1 -> source (exclusion p), t_max 1.0; the flags-only occlusion kernels answer all 3 * max_paths slots; the deposit
+// (a lane per path) adds the words of the paths with all three legs free.  The first fields are ImageArgs's, in its order
+struct Image2Args {
+    const PolyRec* polys;      // Model[top]
+    const QuadRec* quads;      // null when the topology is all triangles
+    const unsigned char* cull; // the pre-cull's dense records of the topology
+    const double* rcv;         // n_rcv x 4: cx, cy, cz, r * r
+    const double* alpha;       // nullable: P x bands
+    const double* sigma;       // nullable: P x bands
+    const double* gain;        // the source's table (null iff res == 0)
+    unsigned long long* hist;  // n_rcv x n_bins x bands (x 4: hare_image2_deposit_dir), accumulated
+    unsigned long long* det;   // 2 n_rcv, accumulated
+    unsigned long long* count; // the work block's first two words: candidates found, paths found (either may exceed its list: then nothing is deposited)
+    double* img;               // n_poly x 4: S'.x, S'.y, S'.z, 1.0 when mirrored (else 0.0)
+    double* cand_s;            // max_cands x 3: S''
+    int32_t* cand_pq;          // max_cands x 2: p, q
+    RayRec* srays;             // 3 max_paths shadow rays
+    double* stmax;             // 3 max_paths t_max (1.0)
+    int32_t* path_kc;          // 2 max_paths: k and the candidate's index per path
+    int32_t* sexcl;            // 3 max_paths: poly_origin1 of a slot in use, -2 for the others
+    int32_t* sexcl2;           // 3 max_paths: poly_origin2 (q on the middle leg, else -1)
+    const int32_t* socc;       // 3 max_paths occlusion flags (the deposit reads them)
+    CullFrame cf;
+    double pos[3];
+    double power[kMaxBands];
+    double frame[9];
+    double bin_len;
+    double scale;              // 2^frac_bits
+    double weight;             // W = (double)n_weight
+    long long max_cands;
+    long long max_paths;
+    int32_t n_rcv;
+    int32_t n_poly;
+    int32_t bands;
+    int32_t res;
+    int32_t n_bins;
+    int32_t prune;             // scene option "image2_prune"
 };
 
 // hare_hist_reduce (reduce.hip): a receive histogram reduced to window sums and decay-level crossings per receiver and band

@@ -30,6 +30,22 @@ static __device__ __forceinline__ double image_vector(double cx, double cy, doub
     return (vx * vx + vy * vy) + vz * vz;
 }
 
+// The point (sx, sy, sz) mirrored in the plane of polygon pr: o[0 .. 2] = the image, o[3] = 1.0 when mirrored, else 0.0 (a NaN, a point on the
+// plane or a normal of length 0: no image).  hare_image_mirror's arithmetic, shared with image2.hip (which mirrors S' again)
+static __device__ __forceinline__ bool image_mirror_point(const PolyRec& pr, double sx, double sy, double sz, double* o)
+{
+    const double nx = pr.n[0], ny = pr.n[1], nz = pr.n[2];
+    const double h = dot3(sx - pr.v0[0], sy - pr.v0[1], sz - pr.v0[2], nx, ny, nz);
+    const double nn = dot3(nx, ny, nz, nx, ny, nz);
+    const bool mirrored = nn > 0 && (h > 0 || h < 0);
+    const double k2 = (2.0 * h) / nn;
+    o[0] = sx - nx * k2;
+    o[1] = sy - ny * k2;
+    o[2] = sz - nz * k2;
+    o[3] = mirrored ? 1.0 : 0.0;
+    return mirrored;
+}
+
 // A lane per polygon (grid-stride): S' and the mirrored mark, img[4 p .. 4 p + 3] = S'.x, S'.y, S'.z, 1.0 / 0.0.  The same launch zeroes the
 // pair count and marks all 2 * max_pairs shadow-ray slots -2 (no query: the occlusion kernels skip them under HARE_SHOOT_RETIRED_RAYS), so
 // the occlusion launch needs no count on the host.
@@ -39,17 +55,7 @@ extern "C" __global__ __launch_bounds__(256) void hare_image_mirror(ImageArgs a)
     if (tid == 0) *a.count = 0ull;
     for (long long i = tid; i < 2 * a.max_pairs; i += stride) a.sexcl[i] = -2;
     for (long long p = tid; p < (long long)a.n_poly; p += stride) {
-        const PolyRec& pr = a.polys[p];
-        const double nx = pr.n[0], ny = pr.n[1], nz = pr.n[2];
-        const double h = dot3(a.pos[0] - pr.v0[0], a.pos[1] - pr.v0[1], a.pos[2] - pr.v0[2], nx, ny, nz);
-        const double nn = dot3(nx, ny, nz, nx, ny, nz);
-        const bool mirrored = nn > 0 && (h > 0 || h < 0);
-        const double k2 = (2.0 * h) / nn;
-        double* const o = a.img + 4 * (size_t)p;
-        o[0] = a.pos[0] - nx * k2;
-        o[1] = a.pos[1] - ny * k2;
-        o[2] = a.pos[2] - nz * k2;
-        o[3] = mirrored ? 1.0 : 0.0;
+        image_mirror_point(a.polys[p], a.pos[0], a.pos[1], a.pos[2], a.img + 4 * (size_t)p);
     }
 }
 

@@ -162,6 +162,10 @@ static_assert((HARE_RECEIVE_IMAGE & (kPublicFlags | HARE_SHOOT_BOUNCE_LOOP | HAR
                                      HARE_RECEIVE_DIRECT | 0xF000u | kFlagAnyHit | SHOOT_RETIRED_SILENT)) == 0 &&
                   (HARE_RECEIVE_IMAGE & (HARE_RECEIVE_IMAGE - 1u)) == 0,
               "the receive calls' image-source bit is a bit of its own, below the developer bits");
+static_assert((HARE_RECEIVE_IMAGE2 & (kPublicFlags | HARE_SHOOT_BOUNCE_LOOP | HARE_RECEIVE_DIFFUSE_RAIN | HARE_RECEIVE_DIRECTIONAL | HARE_RECEIVE_TIME_LIMIT |
+                                      HARE_RECEIVE_DIRECT | HARE_RECEIVE_IMAGE | 0xF000u | kFlagAnyHit | SHOOT_RETIRED_SILENT)) == 0 &&
+                  (HARE_RECEIVE_IMAGE2 & (HARE_RECEIVE_IMAGE2 - 1u)) == 0,
+              "the receive calls' second-order bit is a bit of its own: the first above the developer bits, below the internal ones");
 uint32_t sanitize_flags(const Scene& s, uint32_t flags)
 {
     return flags & (kPublicFlags | (s.opt.dev ? 0xF000u : 0u));

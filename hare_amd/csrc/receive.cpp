@@ -2,7 +2,7 @@
 // and its per-cast step (receive_plan, receive_step: what bounce_device_impl, launch.cpp, runs between its casts) and hare_receive_device
 // (include/hare_hip.h, "receivers"; the kernels: receive.hip); the point source (hare_scene_set_source, hare_emit_device; the kernel:
 // source.hip); the direct sound (direct_enqueue, hare_direct_device; the kernels: direct.hip); first-order image sources (image_enqueue,
-// hare_image_device; the kernels: image.hip).  The host-buffer calls hare_receive_batch / _sharded and hare_receive_source / _sharded are in bounce.cpp, beside the loop
+// hare_image_device; the kernels: image.hip) and second-order ones (image2_enqueue, hare_image2_device; the kernels: image2.hip).  The host-buffer calls hare_receive_batch / _sharded and hare_receive_source / _sharded are in bounce.cpp, beside the loop
 // they share with hare_bounce_batch.
 //
 // Harness-defined: the reference has no receivers (Pachyderm, its caller, detects them on the host per ray).
@@ -105,6 +105,8 @@ int receive_check_args(const char* who, const Scene& s, uint32_t flags, int32_t 
         set_error(std::string(who) + ": " + what);
         return HARE_E_INVALID;
     };
+    if ((flags & HARE_RECEIVE_IMAGE2) && !(flags & HARE_RECEIVE_IMAGE))
+        return bad("HARE_RECEIVE_IMAGE2 is accepted only together with HARE_RECEIVE_IMAGE (the second order stands on the first)");
     if (kind < HARE_KIND_VOXEL || kind > HARE_KIND_KDTREE) return bad("bad kind");
     if (top < 0 || top >= (int32_t)s.topos.size()) return bad("bad top_index");
     if (n < 0 || n > 0x7FFFFF00ll) return bad("n out of range (0 .. 2^31 - 256)");
@@ -187,6 +189,11 @@ int receive_plan(const Scene& s, int32_t top, uint32_t flags, int64_t n, int32_t
     ra.rain_flag = p.work.flag;
     p.skip_cast0 = (flags & HARE_RECEIVE_DIRECT) != 0;
     p.skip_cast1_specular = (flags & HARE_RECEIVE_IMAGE) != 0;
+    p.skip_cast2_specular = (flags & HARE_RECEIVE_IMAGE2) != 0;
+    // the byte per ray of casts 1 and 2 (a scattering table only): behind everything else the work array holds -- the loop's 2 n int32, or
+    // HARE_RECEIVE_RAIN_WORK_BYTES(n) in a call with HARE_RECEIVE_DIFFUSE_RAIN.  Null in every call without the flag
+    if (p.skip_cast2_specular && ra.sigma)
+        ra.spec2 = (unsigned char*)d_work + ((flags & HARE_RECEIVE_DIFFUSE_RAIN) ? (size_t)HARE_RECEIVE_RAIN_WORK_BYTES(n) : (size_t)n * 2 * sizeof(int32_t));
     return HARE_OK;
 }
 
@@ -241,6 +248,10 @@ int receive_step(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n
     // the first-order specular paths are hare_image_deposit's: without a scattering table every ray of cast 1 has left cast 0 specularly; with
     // one, the scatter kernels recompute each ray's choice
     if (p.skip_cast1_specular && cast == 1) ra.cut |= ra.sigma ? kCutSkipSpecular : kCutSkipDetect;
+    // the second-order specular paths are hare_image2_deposit's: without a table every ray of cast 2 was reflected specularly twice; with one,
+    // cast 1 stores each reflected ray's conjunction (its recomputed outcome of cast 0 and its own draw) and cast 2 reads it
+    if (p.skip_cast2_specular && cast == 1 && ra.sigma && !last_cast) ra.cut |= kCutStoreSpecular2;
+    if (p.skip_cast2_specular && cast == 2) ra.cut |= ra.sigma ? kCutSkipSpecular2 : kCutSkipDetect;
     if (p.rain && !last_cast) {
         // diffuse rain (receive.hip: hare_rain_step): receiver k's query is emitted, answered by the flags-only occlusion kernel of this
         // partition, and deposited by the launch that emits k + 1's
@@ -452,6 +463,83 @@ int image_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t 
     }
     if (int rc = shoot_device_impl(s, H, kind, top, 2 * M, a.srays, a.sexcl, nullptr, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st, a.stmax, occ)) return rc;
     return launch(H, s.module->image_deposit[dir], (unsigned)((M + 255) / 256), 256, 0, st, args);
+}
+
+// ---- second-order image sources (include/hare_hip.h, "receivers", "Image sources (second order)"; the kernels: image2.hip)
+// The scratch of a deposit, from d_work (a 16-byte boundary): 256 bytes whose first two words are the candidate count and the path count;
+// P images (32 B); per candidate S'' (24 B) and p, q (8 B); per path three shadow rays (144 B), three t_max (24 B), k and the candidate's
+// index (8 B), three poly_origin1, three poly_origin2 and three occlusion flags (36 B):
+// 256 + 32 P + 32 max_cands + 212 max_paths = HARE_IMAGE2_WORK_BYTES
+int image2_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                   int32_t frac_bits, int64_t max_cands, int64_t max_paths, void* d_work, void* d_hist, void* d_det, hipStream_t st)
+{
+    const Scene::Source& src = s.src;
+    const bool dir = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
+    const DeviceModule* const m = s.module;
+    if (!m || !m->image2_mirror || !m->image2_cands || !m->image2_paths || !m->image2_deposit[dir]) {
+        set_error("hare_image2_mirror / hare_image2_cands / hare_image2_paths / hare_image2_deposit missing from code object");
+        return HARE_E_STATE;
+    }
+    const int64_t K = (int64_t)(s.rcv.size() / 4), P = s.topos[(size_t)top].P, C = max_cands, M = max_paths;
+    Image2Args a;
+    memset((void*)&a, 0, sizeof a);
+    a.polys = (const PolyRec*)s.d_polys[(size_t)top];
+    a.quads = (const QuadRec*)s.d_quads[(size_t)top];
+    a.cull = (const unsigned char*)s.d_cull[(size_t)top];
+    a.cf = s.cull_frames[(size_t)top];
+    a.rcv = (const double*)(s.rmap.set ? s.rmap.d_rcv : s.d_rcv);
+    a.alpha = has_table(s.alpha, top) ? (const double*)s.alpha[(size_t)top].dev : nullptr;
+    a.sigma = has_table(s.sigma, top) ? (const double*)s.sigma[(size_t)top].dev : nullptr;
+    a.gain = src.R > 0 ? (const double*)src.d_gain : nullptr;
+    a.hist = (unsigned long long*)d_hist;
+    a.det = (unsigned long long*)d_det;
+    char* const w = (char*)d_work;
+    a.count = (unsigned long long*)w;
+    a.img = (double*)(w + 256);
+    a.cand_s = a.img + 4 * P;
+    a.cand_pq = (int32_t*)(a.cand_s + 3 * C);
+    a.srays = (RayRec*)(a.cand_pq + 2 * C);
+    a.stmax = (double*)(a.srays + 3 * M);
+    a.path_kc = (int32_t*)(a.stmax + 3 * M);
+    a.sexcl = a.path_kc + 2 * M;
+    a.sexcl2 = a.sexcl + 3 * M;
+    int32_t* const occ = a.sexcl2 + 3 * M;
+    a.socc = occ;
+    memcpy(a.pos, src.pos, sizeof a.pos);
+    memcpy(a.power, src.power, sizeof a.power);
+    memcpy(a.frame, src.frame, sizeof a.frame);
+    a.bin_len = bin_len;
+    a.scale = ldexp(1.0, frac_bits);
+    a.weight = (double)n_weight;
+    a.max_cands = C;
+    a.max_paths = M;
+    a.n_rcv = (int32_t)K;
+    a.n_poly = (int32_t)P;
+    a.bands = src.B;
+    a.res = src.R;
+    a.n_bins = n_bins;
+    a.prune = s.opt.image2_prune;
+    if (!a.polys || !a.cull || !a.rcv || (src.R > 0 && !a.gain) || (has_table(s.alpha, top) && !a.alpha) || (has_table(s.sigma, top) && !a.sigma)) {
+        set_error("image sources: polygons, receivers or tables not on the device");
+        return HARE_E_STATE;
+    }
+    if (P == 0) return HARE_OK;
+    void* args[] = {&a};
+    const int64_t fill = std::max<int64_t>(P, 3 * M);
+    if (int rc = launch(H, m->image2_mirror, (unsigned)std::min<int64_t>((fill + 255) / 256, 4096), 256, 0, st, args)) return rc;
+    {
+        // hare_image2_cands: (p blocks) x (q tiles of 256); hare_image2_paths: (candidate blocks) x (receiver tiles of 256).  A grid's
+        // second dimension holds at most 65 535 blocks: K <= 65 536 receivers are 256 tiles; P is refused beyond 65 535 * 256 polygons
+        if (P > 65535ll * 256) {
+            set_error("image sources (second order): more than 16 776 960 polygons");
+            return HARE_E_INVALID;
+        }
+        const unsigned gp = (unsigned)((P + 255) / 256);
+        HIP_TRY(H->ModuleLaunchKernel(m->image2_cands, gp, gp, 1, 256, 1, 1, 0, st, args, nullptr));
+        HIP_TRY(H->ModuleLaunchKernel(m->image2_paths, (unsigned)((C + 255) / 256), (unsigned)((K + 255) / 256), 1, 256, 1, 1, 0, st, args, nullptr));
+    }
+    if (int rc = shoot_device_impl(s, H, kind, top, 3 * M, a.srays, a.sexcl, a.sexcl2, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st, a.stmax, occ)) return rc;
+    return launch(H, m->image2_deposit[dir], (unsigned)((M + 255) / 256), 256, 0, st, args);
 }
 
 // ---- the reduction of a histogram (include/hare_hip.h, "receivers", "Reduction"; the kernel: reduce.hip)
@@ -953,6 +1041,55 @@ int hare_image_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n_
     GUARD_END
 }
 
+int hare_image2_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                       int32_t frac_bits, int64_t max_cands, int64_t max_paths, void* d_work, void* d_hist, void* d_detections, void* stream)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    const char* const who = "hare_image2_device";
+    if (int rc = direct_check_weight(who, n_weight)) return rc;
+    flags &= HARE_RECEIVE_DIRECTIONAL;
+    if (int rc = receive_check_args(who, *s, flags, kind, top_index, 0, 1, n_bins, bin_len, frac_bits)) return rc;
+    if (s->src.set && s->src.B != scene_bands(*s, top_index)) {
+        set_error(std::string(who) + ": the source has " + std::to_string(s->src.B) + " bands, the topology " + std::to_string(scene_bands(*s, top_index)));
+        return HARE_E_INVALID;
+    }
+    if (max_cands < 1 || max_cands > ((int64_t)1 << 26) || max_paths < 1 || max_paths > ((int64_t)1 << 26)) {
+        set_error(std::string(who) + ": max_cands or max_paths out of range (1 .. 2^26)");
+        return HARE_E_INVALID;
+    }
+    if (!d_work || !d_hist || !d_detections || ((uintptr_t)d_work & 15u)) {
+        set_error(std::string(who) + ": null work array / histogram / detections, or a work array off a 16-byte boundary");
+        return HARE_E_INVALID;
+    }
+    const size_t K = std::max<size_t>(1, s->rcv.size() / 4);
+    const struct { const void* p; size_t bytes; } bufs[] = {{d_work, (size_t)HARE_IMAGE2_WORK_BYTES(s->topos[(size_t)top_index].P, max_cands, max_paths)},
+                                                            {d_hist, receive_hist_words(*s, top_index, n_bins, flags, 1) * sizeof(uint64_t)},
+                                                            {d_detections, K * 2 * sizeof(uint64_t)}};
+    for (size_t x = 0; x < 3; ++x)
+        for (size_t y = x + 1; y < 3; ++y)
+            if (ranges_overlap(bufs[x].p, bufs[x].bytes, bufs[y].p, bufs[y].bytes)) {
+                set_error(std::string(who) + ": work array, histogram and detections must not overlap");
+                return HARE_E_INVALID;
+            }
+    GUARD_BEGIN
+    const HipApi* H = api_or_err();
+    if (!H) return HARE_E_NODEVICE;
+    DeviceGuard dev_guard(H, s->device);
+    if (!s->module) {
+        int rc = ensure_device(*s, H);
+        if (rc) return rc;
+    }
+    if (int rc = source_ready(*s, H, who)) return rc;
+    if (int rc = upload_polys(*s, H)) return rc;
+    if (int rc = receive_ready(*s, H, who)) return rc;
+    return image2_enqueue(*s, H, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, max_cands, max_paths, d_work, d_hist, d_detections,
+                          (hipStream_t)stream);
+    GUARD_END
+}
+
 int hare_hist_reduce_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
                             int32_t n_win, const int32_t* win, int32_t n_lev, const uint32_t* levels, void* d_sums, void* d_cross, void* stream)
 {
@@ -1052,7 +1189,8 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
         struct Buf { const void* p; size_t bytes; bool written; };
         const Buf bufs[] = {{d_rays, (size_t)n * sizeof(hare_ray), true},
                             {d_state, (size_t)n * (size_t)(1 + B) * sizeof(double), true},
-                            {d_work, rain ? (size_t)HARE_RECEIVE_RAIN_WORK_BYTES(n) : (size_t)n * 2 * sizeof(int32_t), true},
+                            {d_work, (rain ? (size_t)HARE_RECEIVE_RAIN_WORK_BYTES(n) : (size_t)n * 2 * sizeof(int32_t)) +
+                                         ((flags & HARE_RECEIVE_IMAGE2) ? (size_t)HARE_RECEIVE_IMAGE2_WORK_BYTES(n) : 0), true},
                             {d_events_last, (size_t)n * sizeof(hare_xevent), true},
                             {d_hist, receive_hist_words(*s, top_index, n_bins, flags, 1) * sizeof(uint64_t), true},
                             {d_detections, K * 2 * sizeof(uint64_t), true},

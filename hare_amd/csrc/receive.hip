@@ -283,6 +283,25 @@ static __device__ __forceinline__ void receive_body(const Args& a)
             imaged = !(scatter_u(scatter_mix(scatter_mix(a.seed + kScatterGamma) ^ (unsigned long long)(a.ray_base + i)), 0ull, 0) < p);
         }
     }
+    // HARE_RECEIVE_IMAGE2 (uniform bits; the scatter kernels).  Cast 1 stores the byte HERE, from cast 0's outcome and this cast's own draw,
+    // which it makes a second time for the purpose -- the draw is counter-based, so these are the bits the reflection below draws (same p,
+    // same word 0 of counter c = 1).  Nothing is held across the body and nothing is stored behind the reflection: a store there cost
+    // hare_receive_scatter_map_dir four VGPRs, and the second draw runs in one cast of a flagged call only.  A ray that misses is retired and
+    // its byte never read.  In cast 2 the byte IS the skip -- both reflections were specular: hare_image2_deposit's paths
+    if constexpr (SCATTER) {
+        if ((a.cut & kCutStoreSpecular2) && live) {
+            bool spec = false;
+            if (imaged && a.ev[i].hit) {
+                const double* sg = a.sigma + (size_t)a.ev[i].poly_id * (size_t)B;
+                double p = sg[0];
+                for (int b = 1; b < B; ++b) p = p + sg[b];
+                p = p / (double)B;
+                spec = !(scatter_u(scatter_mix(scatter_mix(a.seed + kScatterGamma) ^ (unsigned long long)(a.ray_base + i)), (unsigned long long)a.cast << 8, 0) < p);
+            }
+            a.spec2[i] = spec ? 1 : 0;
+        }
+        if ((a.cut & kCutSkipSpecular2) && live) imaged = a.spec2[i] != 0;
+    }
     if constexpr (MAP) {
         // the walk holds the ray, t_end and L only: the event and the energies are read behind it (nothing the walk adds to overlaps them)
         if (live) {

@@ -66,6 +66,9 @@ struct SceneOptions {
     int receive_roulette = 0;      // 1: a ray under the floor plays Russian roulette (word 65 of the scattering RNG)
     int image_max_pairs = 1 << 20; // HARE_RECEIVE_IMAGE on the host calls: the pair list's length (HARE_E_NOMEM when the scene yields more; include/hare_hip.h, "Image sources")
     int image_cull = 1;            // 1: hare_image_pairs runs the conservative FP32 pre-cull ahead of the exact test; 0: the exact test on every pair (A/B).  Same results
+    int image2_max_cands = 1 << 22; // HARE_RECEIVE_IMAGE2 on the host calls: the candidate list's length, (p, q) pairs (HARE_E_NOMEM when the scene yields more; include/hare_hip.h, "Image sources (second order)")
+    int image2_max_paths = 1 << 20; // ... and the path list's, (receiver, p, q) triples
+    int image2_prune = 1;          // 1: hare_image2_cands drops the pairs (p, q) that no receiver anywhere can use (a conservative filter); 0: every ordered pair is a candidate (A/B).  Same results
     long long scatter_seed = 0;    // the scattering RNG's seed S (hare_receive_scatter; read as uint64 bits)
     long long source_seed = 0;     // the point source's seed S (hare_emit_source; read as uint64 bits)
     long long dev_order_ptr = 0;   // developer experiments (a `dev` scene only): a device array of n uint32, the order K1q takes the rays in (ShootIO::order)
@@ -133,6 +136,7 @@ struct DeviceModule {
     hipFunction_t hist_reduce = nullptr;                                   // reduce.hip
     hipFunction_t direct_emit = nullptr, direct_deposit[2] = {};           // direct.hip ([1]: the _dir form)
     hipFunction_t image_mirror = nullptr, image_pairs = nullptr, image_deposit[2] = {};   // image.hip ([1]: the _dir form)
+    hipFunction_t image2_mirror = nullptr, image2_cands = nullptr, image2_paths = nullptr, image2_deposit[2] = {};   // image2.hip ([1]: the _dir form)
     hipFunction_t voxel_occl_tri = nullptr, voxel_occl_quad = nullptr, voxel_occl_tri_g = nullptr, voxel_occl_quad_g = nullptr, octree_occl = nullptr, octree_occl_any = nullptr;
     hipFunction_t events_pack_slim = nullptr;
     hipFunction_t block_occ = nullptr;                                     // build_kernels.hip: hare_block_occ
@@ -259,7 +263,9 @@ struct Scene {
         void* red = nullptr;            // hare_receive_*_reduced: the sums, the crossings and the weights of hare_hist_reduce
         void* direct = nullptr;         // hare_receive_source* with HARE_RECEIVE_DIRECT: hare_direct_device's scratch, HARE_DIRECT_WORK_BYTES(K)
         void* image = nullptr;          // hare_receive_source* with HARE_RECEIVE_IMAGE: hare_image_device's scratch, HARE_IMAGE_WORK_BYTES(K, P, "image_max_pairs"), grown on demand
-        size_t state_cap = 0, hist_cap = 0, rain_cap = 0, red_cap = 0, direct_cap = 0, image_cap = 0;     // bytes
+        void* image2 = nullptr;         // ... with HARE_RECEIVE_IMAGE2: hare_image2_device's scratch, HARE_IMAGE2_WORK_BYTES(P, "image2_max_cands", "image2_max_paths"), grown on demand
+        void* spec2 = nullptr;          // ... on a topology with a scattering table: the loop's byte per ray (ReceiveArgs::spec2)
+        size_t state_cap = 0, hist_cap = 0, rain_cap = 0, red_cap = 0, direct_cap = 0, image_cap = 0, image2_cap = 0, spec2_cap = 0;     // bytes
         int64_t cap = 0;
         int32_t ctr_cap = 0;
         hipStream_t copy_st = nullptr;
@@ -376,6 +382,8 @@ struct ReceivePlan {
     bool skip_cast0 = false;    // HARE_RECEIVE_DIRECT: cast 0 runs no receiver step (kCutSkipDetect in that cast's args.cut only)
     bool skip_cast1_specular = false;   // HARE_RECEIVE_IMAGE: in cast 1 the rays that left cast 0 specularly run no receiver step (kCutSkipDetect without a
                                 // scattering table, kCutSkipSpecular with one; in that cast's args.cut only)
+    bool skip_cast2_specular = false;   // HARE_RECEIVE_IMAGE2: in cast 2 the rays that left casts 0 and 1 specularly run no receiver step (kCutSkipDetect without a
+                                // scattering table; with one, cast 1 stores args.spec2 under kCutStoreSpecular2 and cast 2 reads it under kCutSkipSpecular2)
 };
 inline int receive_form(const ReceivePlan& p)      // DeviceModule::receive's first index
 {
@@ -425,6 +433,12 @@ int direct_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t
 // tables must be on the device
 int image_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                   int32_t frac_bits, int64_t max_pairs, void* d_work, void* d_hist, void* d_det, hipStream_t st);
+// second-order image sources (receive.cpp; include/hare_hip.h, "receivers", "Image sources (second order)").  image2_enqueue: hare_image2_mirror,
+// hare_image2_cands, hare_image2_paths, ONE flags-only occlusion query of 3 * max_paths slots and hare_image2_deposit[_dir] on the stream;
+// d_work: HARE_IMAGE2_WORK_BYTES(P, max_cands, max_paths) of scratch from a 16-byte boundary, its first two words the candidates and the
+// paths found.  Source, receivers and tables must be on the device
+int image2_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                   int32_t frac_bits, int64_t max_cands, int64_t max_paths, void* d_work, void* d_hist, void* d_det, hipStream_t st);
 // The reduction of a receive histogram (receive.cpp; include/hare_hip.h, "receivers", "Reduction").  ReduceSpec: what the caller asks for,
 // host pointers (weight: n_bins x B, nullable).  reduce_check_spec: the checks that need no buffer (HARE_E_INVALID); reduce_enqueue:
 // hare_hist_reduce on the stream, device buffers, win and levels read here

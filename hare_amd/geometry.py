@@ -500,7 +500,7 @@ class Spatial_Partition:
 
     def Receive_source(self, n: int, bounces: int, n_bins: int, bin_len: float, first_ray: int = 0, frac_bits: int = 40, top_index: int = 0,
                        out=None, rain: bool = False, directional: bool = False, time_limit: bool = False, direct: bool = False,
-                       image: bool = False):
+                       image: bool = False, image2: bool = False):
         """hare_receive_source: Receive_batch with the rays and their state emitted on the device by the scene's source (set_source) --
         the rays first_ray .. first_ray + n - 1; nothing but the count goes up.  Returns what Receive_batch returns.  Calls over
         [0, k) and [k, n) sum to the histogram and detections of the one call.  direct (HARE_RECEIVE_DIRECT; include/hare_hip.h, "Direct
@@ -508,30 +508,32 @@ class Spatial_Partition:
         nothing -- chunks then sum to the one call up to a unit per chunk and word.  image (HARE_RECEIVE_IMAGE; "Image sources (first
         order)"): the first-order specular reflections are one visibility-tested deposit per (receiver, polygon) pair, and in cast 1 the
         rays that left cast 0 specularly detect nothing; the pair list holds get_option("image_max_pairs") pairs (HareError, HARE_E_NOMEM,
-        with the needed count when the scene yields more)."""
+        with the needed count when the scene yields more).  image2 (HARE_RECEIVE_IMAGE2, only with image; "Image sources (second
+        order)"): the specular paths off two polygons are one deposit each, and in cast 2 the rays reflected specularly twice detect nothing;
+        the lists hold get_option("image2_max_cands") candidates and get_option("image2_max_paths") paths (HARE_E_NOMEM with both counts)."""
         return Spatial_Partition._receive_source([self], n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain, directional,
-                                                 time_limit, direct=direct, image=image)
+                                                 time_limit, direct=direct, image=image, image2=image2)
 
     def Receive_source_reduced(self, n: int, bounces: int, n_bins: int, bin_len: float, windows=None, levels=None, weight=None,
                                first_ray: int = 0, frac_bits: int = 40, top_index: int = 0, directional: bool = False,
-                               time_limit: bool = False, direct: bool = False, image: bool = False):
+                               time_limit: bool = False, direct: bool = False, image: bool = False, image2: bool = False):
         """hare_receive_source_reduced: Receive_source with the histogram kept on the device and reduced there, as in
         Receive_batch_reduced; returns what that returns.  direct, image: as in Receive_source."""
         return Spatial_Partition._receive_source([self], n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, None, False, directional,
-                                                 time_limit, dict(windows=windows, levels=levels, weight=weight), direct=direct, image=image)
+                                                 time_limit, dict(windows=windows, levels=levels, weight=weight), direct=direct, image=image, image2=image2)
 
     @staticmethod
     def Receive_source_sharded(partitions, n: int, bounces: int, n_bins: int, bin_len: float, first_ray: int = 0, frac_bits: int = 40,
                                top_index: int = 0, out=None, rain: bool = False, directional: bool = False, time_limit: bool = False,
-                               direct: bool = False, image: bool = False):
+                               direct: bool = False, image: bool = False, image2: bool = False):
         """hare_receive_source_sharded: Receive_source over several partitions (contiguous ray shards, histograms summed); byte-identical.
         The partitions must hold the same source and "source_seed".  direct, image: as in Receive_source; one partition makes each deposit."""
         return Spatial_Partition._receive_source(list(partitions), n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain,
-                                                 directional, time_limit, direct=direct, image=image)
+                                                 directional, time_limit, direct=direct, image=image, image2=image2)
 
     @staticmethod
     def _receive_source(parts, n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain, directional, time_limit, reduce=None,
-                        direct=False, image=False):
+                        direct=False, image=False, image2=False):
         if not parts or any(p._kind != parts[0]._kind for p in parts):
             raise ValueError("need one or more partitions of the same kind")
         n = int(n)
@@ -544,7 +546,7 @@ class Spatial_Partition:
         ctr = capi.Counters()
         flags = ((capi.RECEIVE_DIFFUSE_RAIN if rain else 0) | (capi.RECEIVE_DIRECTIONAL if directional else 0) |
                  (capi.RECEIVE_TIME_LIMIT if time_limit else 0) | (capi.RECEIVE_DIRECT if direct else 0) |
-                 (capi.RECEIVE_IMAGE if image else 0))
+                 (capi.RECEIVE_IMAGE if image else 0) | (capi.RECEIVE_IMAGE2 if image2 else 0))
         if reduce is not None:
             w, n_win, win, n_lev, lev = _reduce_spec(reduce, nb, B)
             sums, cross = np.zeros((max(K, 0), B, n_win, 4), np.uint64), np.zeros((max(K, 0), B, n_lev), np.int32)
@@ -713,14 +715,33 @@ class Spatial_Partition:
                                     d_detections or None, stream or None))
 
     @staticmethod
-    def receive_work_bytes(n: int, rain: bool = False) -> int:
-        """Bytes of receive_device's d_work for n rays: 2 n int32, or HARE_RECEIVE_RAIN_WORK_BYTES(n) with rain."""
-        return 80 * int(n) + 256 if rain else 8 * int(n)
+    def image2_work_bytes(P: int, max_cands: int, max_paths: int) -> int:
+        """Bytes of Image2_device's d_work for P polygons and lists of max_cands candidates and max_paths paths:
+        HARE_IMAGE2_WORK_BYTES(P, max_cands, max_paths)."""
+        return 256 + 32 * int(P) + 32 * int(max_cands) + 212 * int(max_paths)
+
+    def Image2_device(self, n_weight: int, n_bins: int, bin_len: float, frac_bits: int, max_cands: int, max_paths: int, d_work: int, d_hist: int,
+                      d_detections: int, top_index: int = 0, directional: bool = False, stream: int = 0):
+        """hare_image2_device on raw device addresses + a hipStream_t: the second-order image sources of the scene's source
+        (include/hare_hip.h, "Image sources (second order)") -- the candidate stage polygons x polygons, the path stage receivers x
+        candidates, three shadow rays per path and one deposit per path with all legs free, standing for n_weight source rays --
+        accumulated into d_hist and d_detections (shaped as Image_device's); d_work holds image2_work_bytes(P, max_cands, max_paths) bytes on
+        a 16-byte boundary and its first two uint64 receive the candidates and the paths found (either beyond its list: nothing was
+        deposited).  Stream-ordered: no allocation, no free, no wait."""
+        check(lib.hare_image2_device(self._h, self._kind, int(top_index), int(n_weight), capi.RECEIVE_DIRECTIONAL if directional else 0,
+                                     int(n_bins), float(bin_len), int(frac_bits), int(max_cands), int(max_paths), d_work or None, d_hist or None,
+                                     d_detections or None, stream or None))
+
+    @staticmethod
+    def receive_work_bytes(n: int, rain: bool = False, image2: bool = False) -> int:
+        """Bytes of receive_device's d_work for n rays: 2 n int32, or HARE_RECEIVE_RAIN_WORK_BYTES(n) with rain; with image2,
+        HARE_RECEIVE_IMAGE2_WORK_BYTES(n) = n more behind either."""
+        return (80 * int(n) + 256 if rain else 8 * int(n)) + (int(n) if image2 else 0)
 
     def receive_device(self, n: int, d_rays: int, bounces: int, n_bins: int, bin_len: float, frac_bits: int, d_state: int, d_work: int,
                        d_events_last: int, d_hist: int, d_detections: int, top_index: int = 0, d_excl1: int = 0, d_excl2: int = 0,
                        d_counters: int = 0, stream: int = 0, flags: int = 0, rain: bool = False, directional: bool = False,
-                       time_limit: bool = False, direct: bool = False, image: bool = False):
+                       time_limit: bool = False, direct: bool = False, image: bool = False, image2: bool = False):
         """hare_receive_device on raw device addresses (e.g. torch.Tensor.data_ptr()) + a hipStream_t: d_state (1 + B) x n doubles is read
         and overwritten, d_hist (K x n_bins x B uint64) and d_detections (2 K uint64) are accumulated into.  Stream-ordered.  rain: diffuse
         rain (HARE_RECEIVE_DIFFUSE_RAIN); d_work then holds receive_work_bytes(n, rain=True) bytes.  directional
@@ -731,6 +752,8 @@ class Spatial_Partition:
             flags |= capi.RECEIVE_DIRECT
         if image:                                    # suppression only ("Image sources (first order)"): Image_device makes the deposit
             flags |= capi.RECEIVE_IMAGE
+        if image2:                                   # suppression only ("Image sources (second order)"): Image2_device makes the deposit;
+            flags |= capi.RECEIVE_IMAGE2             # d_work then holds receive_work_bytes(n, rain, image2=True) bytes
         if time_limit:
             flags |= capi.RECEIVE_TIME_LIMIT
         if rain:

@@ -88,6 +88,10 @@ extern "C" {
 #define HARE_RECEIVE_IMAGE 2048u       /* the same calls only: the first-order specular reflections are deposited once per (receiver, polygon) pair,      */
                                        /* visibility-tested, and cast 1's receiver step is skipped for the rays that left cast 0 specularly               */
                                        /* ("receivers", "Image sources (first order)").  The next bit, 0x1000, is the first developer bit                 */
+#define HARE_RECEIVE_IMAGE2 65536u     /* the same calls, and only together with HARE_RECEIVE_IMAGE: the second-order specular reflections are deposited   */
+                                       /* once per (receiver, polygon, polygon) path and cast 2's receiver step is skipped for the rays reflected          */
+                                       /* specularly twice ("receivers", "Image sources (second order)").  0x10000: the first bit above the developer      */
+                                       /* bits 0x1000 .. 0x8000 (0x8000 is the cull audit), below the internal bits 0x40000 and 0x80000                    */
 
 /* Hare.Geometry.Ray (Hare_Geometry_Primitives.cs:393-429): origin + direction.  Ray_ID/ThreadID
  * only serve the reference's mailbox pool and are not needed here. 48 bytes. */
@@ -718,6 +722,71 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * Chunking.  As for the direct sound: a caller who wants the bits of the one call makes ONE hare_image_device deposit with the whole count
  * and runs the chunks through hare_receive_device with the flag.
  *
+ * Image sources (second order) (flag HARE_RECEIVE_IMAGE2, with HARE_RECEIVE_IMAGE; hare_image2_device).  The specular paths off TWO polygons,
+ * source -> p -> q -> receiver, are computed the same way: the image S' of the source in p's plane is mirrored again in q's plane, the
+ * path exists if the segment from that second image S'' to the receiver's center passes through q at x2 and the segment from S' to x2
+ * passes through p at x1, and it counts if its three legs are unoccluded.  ONE deposit per (receiver, p, q) path.  FP64, no contraction,
+ * in this order; pos, power, gain_b, alpha, sigma, c, rr and W as in the first-order section; p is the polygon hit first, q the second.
+ * Per polygon p: S'_p and mirrored_p exactly as first order.  Per ordered pair (p, q) with p != q, mirrored_p, and nn_q = dot3(n_q, n_q) > 0:
+ *
+ *   h2 = dot3(S'_p.x - v0_q.x, S'_p.y - v0_q.y, S'_p.z - v0_q.z, n_q.x, n_q.y, n_q.z)
+ *   mirrored2  iff  h2 > 0 || h2 < 0
+ *   k2 = (2.0 * h2) / nn_q
+ *   S'' = (S'_p.x - n_q.x * k2, S'_p.y - n_q.y * k2, S'_p.z - n_q.z * k2)
+ *
+ * Per triple (k, p, q) with mirrored2, in any order:
+ *
+ *   v  = c - S'';  d2 = (vx*vx + vy*vy) + vz*vz;  eligible iff d2 > rr
+ *   on_q = poly_fast(q, v3_q, o = S'', d = v, t2)  &&  t2 > 0.0 && t2 < 1.0
+ *   x2 = (S''.x + vx*t2, S''.y + vy*t2, S''.z + vz*t2)
+ *   w  = x2 - S'_p
+ *   on_p = poly_fast(p, v3_p, o = S'_p, d = w, t1)  &&  t1 > 0.0 && t1 < 1.0
+ *   x1 = (S'_p.x + wx*t1, S'_p.y + wy*t1, S'_p.z + wz*t1)
+ *   occluded = hare_occluded(origin x2, direction c   - x2, poly_origin1 = q,                    t_max = 1.0)
+ *           || hare_occluded(origin x1, direction x2  - x1, poly_origin1 = p, poly_origin2 = q, t_max = 1.0)
+ *           || hare_occluded(origin x1, direction pos - x1, poly_origin1 = p,                    t_max = 1.0)
+ *   if eligible && on_q && on_p && !occluded:
+ *     dist = sqrt(d2);  y = rr / d2;  f = (0.5 * y) / (1.0 + sqrt(1.0 - y))
+ *     g_b  = gain_b(x1 - pos)
+ *     r_b  = ((1.0 - alpha[p][b]) * (1.0 - sigma[p][b])) * ((1.0 - alpha[q][b]) * (1.0 - sigma[q][b]))
+ *     m_b  = (((power[b] * g_b) * r_b) * (f * W)) * 2^frac_bits
+ *     directional: a = ( -(vx / dist), -(vy / dist), -(vz / dist) )
+ *
+ * m_b is quantised, binned at xb = dist / bin_len, deposited and counted in detections exactly as the first-order deposit's.
+ * What the caller has to know.  The tests go to the receiver's CENTER only: a sphere whose cone an edge of p or q clips counts wholly or
+ * not at all.  A center path through an edge that two polygons share is accepted by each of them, at p and at q alike (the tests are
+ * inclusive): a set of measure zero.  Every facet of a tessellated surface is its own mirror, so a curved wall gives as many second images
+ * as it has pairs of facets.
+ * Suppression.  In a call with the flag, a ray skips cast 2's receiver step iff its reflections behind cast 0 AND behind cast 1 were both
+ * specular.  On a topology without a scattering table that is every ray of cast 2.  With one, cast 2 cannot recompute cast 0's choice
+ * (that polygon is no longer known), so cast 1, which recomputes it for HARE_RECEIVE_IMAGE and makes its own draw, stores the conjunction
+ * as one byte per reflected ray and cast 2 reads it.  Everything else is the call's without the flag.  Hence, on a topology without a
+ * scattering table and for bounces >= 3, word for word in wrapping uint64 and for detections alike:
+ *
+ *   hist(IMAGE | IMAGE2, bounces) = hist(0, bounces) - hist(0, 3) + hist(0, 1) + image + image2
+ *
+ * With bounces <= 2 nothing more is suppressed than HARE_RECEIVE_IMAGE suppresses, and the deposit is still made.
+ * Where the flag is accepted: where HARE_RECEIVE_IMAGE is, and only together with it -- alone it is HARE_E_INVALID, the first check of the
+ * call, before anything runs.  hare_receive_source, hare_receive_source_sharded and hare_receive_source_reduced: suppression plus ONE deposit
+ * with n_weight = n, before cast 0; in the sharded call the scene that deposits the direct sound makes it.  hare_receive_device:
+ * suppression only.  The hare_receive_batch calls refuse it as they refuse HARE_RECEIVE_IMAGE.  Rain, channels, termination rules and
+ * receiver maps combine as at first order.
+ * The byte array.  The host calls keep it in a buffer of their own.  hare_receive_device with the flag takes it from d_work, which then
+ * holds HARE_RECEIVE_IMAGE2_WORK_BYTES(n) more bytes BEHIND what the other flags need: n bytes from offset 8 n, or from offset
+ * HARE_RECEIVE_RAIN_WORK_BYTES(n) in a call with HARE_RECEIVE_DIFFUSE_RAIN.  It is written in cast 1 and read in cast 2 of calls with the
+ * flag on a topology with a scattering table, and by nothing else; a call without the flag reads and writes the bytes it did before.
+ * The two lists.  The candidate stage appends the ordered pairs (p, q) with mirrored2 to a list of max_cands records; the path stage appends
+ * the triples with eligible && on_q && on_p to a list of max_paths records.  The host calls size them from the scene options
+ * "image2_max_cands" (default 2^22: every ordered pair of up to 2 048 polygons) and "image2_max_paths" (default 2^20), both 1 .. 2^26.
+ * A scene of 10^5 polygons yields 10^9 candidates even pruned: more than any list holds, so the call returns HARE_E_NOMEM there.  If EITHER list overflows, the second-order
+ * deposit adds NOTHING at all, and the host calls return HARE_E_NOMEM with both counts in hare_last_error() (the path count is not known when
+ * the candidates overflowed); their outputs then hold everything but the second order.
+ * The prune (scene option "image2_prune", default 1).  With 0 every ordered pair with mirrored2 is a candidate.  With 1 a pair is dropped
+ * when no receiver anywhere can pass both on_q and on_p: every x2 lies in the pyramid with apex S'_p over p, beyond p, so q is dropped if its
+ * bounding sphere misses the bounding cone of that pyramid, or lies wholly behind p's plane as seen from the source -- both with outward
+ * margins of 1e-9 of the coordinates' size.  Non-finite values, a pyramid wider than a right angle and coordinates whose squares overflow
+ * take every pair.  The filter never decides a result: histogram, detections and the path count are the same with 0 and 1.
+ *
  * The histogram is fixed point in uint64: integer sums do not depend on the order of the adds, so the result is bit-identical from
  * run to run, between the one-device and the sharded call, and against a restatement on the host.  (r*r is formed once, when the
  * receivers are set: the same FP64 product.)
@@ -843,7 +912,8 @@ HARE_API int hare_emit_device(hare_scene *s, int64_t n, int64_t first_ray, void 
  *   d_hist         K x n_bins x B uint64 (x 4 with HARE_RECEIVE_DIRECTIONAL), ACCUMULATED;  d_detections: 2 K uint64, ACCUMULATED
  *   d_counters     nullable: totals, ACCUMULATED (as hare_bounce_device's; the rain's occlusion queries are not counted)
  *   flags          HARE_SHOOT_COUNT_WORK / HARE_SHOOT_SIMPLE_KERNEL (the casts), HARE_RECEIVE_DIFFUSE_RAIN, HARE_RECEIVE_DIRECTIONAL,
- *                  HARE_RECEIVE_TIME_LIMIT, HARE_RECEIVE_DIRECT and HARE_RECEIVE_IMAGE (suppression only: "Direct sound", "Image sources");
+ *                  HARE_RECEIVE_TIME_LIMIT, HARE_RECEIVE_DIRECT, HARE_RECEIVE_IMAGE and HARE_RECEIVE_IMAGE2 (suppression only: "Direct sound",
+ *                  "Image sources"; HARE_RECEIVE_IMAGE2 adds HARE_RECEIVE_IMAGE2_WORK_BYTES(n) bytes behind d_work's other contents);
  *                  other bits are ignored.  With
  *                  HARE_RECEIVE_DIFFUSE_RAIN d_work holds HARE_RECEIVE_RAIN_WORK_BYTES(n) bytes: the 2 n int32, then the rain's scratch
  * Arguments are checked before anything runs (HARE_E_INVALID): kind, top_index, 0 <= n <= 2^31 - 256, 1 <= bounces <= 4096,
@@ -877,6 +947,21 @@ HARE_API int hare_direct_device(hare_scene *s, int32_t kind, int32_t top_index, 
 HARE_API int hare_image_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL only */,
                                int32_t n_bins, double bin_len, int32_t frac_bits, int64_t max_pairs, void *d_work, void *d_hist,
                                void *d_detections, void *stream);
+/* The second-order image sources' deposit on DEVICE buffers ("receivers", "Image sources (second order)"): the candidate stage polygons x
+ * polygons, the path stage receivers x candidates, one occlusion query of three shadow rays per path and one deposit per path with all
+ * legs free, from the scene's source, standing for n_weight source rays.  Stream-ordered: no allocation, no free, no wait.  d_hist and
+ * d_detections are ACCUMULATED, shaped as hare_direct_device's.  d_work is scratch of HARE_IMAGE2_WORK_BYTES(P, max_cands, max_paths) bytes
+ * on a 16-byte boundary (P: the polygons of Model[top_index]): a 256-byte head whose first 8-byte word receives the number of candidates
+ * found and whose second the number of paths found; the P images (32 bytes each); the candidates (32 bytes: S'', p, q); the paths (212
+ * bytes: three shadow rays, their t_max, two exclusion words and a flag each, k and the candidate's index), in unspecified order.  If
+ * either count exceeds its list nothing is deposited (a candidate overflow leaves the path count 0); the caller reads both words behind
+ * the stream.  Checked as hare_image_device checks, in its order, with 1 <= max_cands, max_paths <= 2^26 (HARE_E_INVALID). */
+#define HARE_IMAGE2_WORK_BYTES(P, max_cands, max_paths) (256 + 32 * (int64_t)(P) + 32 * (int64_t)(max_cands) + 212 * (int64_t)(max_paths))
+/* hare_receive_device with HARE_RECEIVE_IMAGE2: the bytes d_work holds behind its other contents ("Image sources (second order)", "The byte array") */
+#define HARE_RECEIVE_IMAGE2_WORK_BYTES(n) ((int64_t)(n))
+HARE_API int hare_image2_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL only */,
+                                int32_t n_bins, double bin_len, int32_t frac_bits, int64_t max_cands, int64_t max_paths, void *d_work,
+                                void *d_hist, void *d_detections, void *stream);
 /* The same from host buffers (threading and staging as hare_bounce_batch's last-cast-only path: one enqueue, one synchronisation; no
  * events are downloaded).  state_in nullable (every ray starts at L = 0, E = 1); state_out nullable ((1 + B) x n, as d_state).
  * hist (K x n_bins x B, x 4 with HARE_RECEIVE_DIRECTIONAL) and detections (2 K) are WRITTEN, not accumulated; ctr nullable: counters summed over the casts.  flags as
@@ -899,7 +984,8 @@ HARE_API int hare_receive_batch_sharded(hare_scene *const *scenes, int32_t n_sce
  * emits from first_ray + lo.  Flags, checks and outputs as hare_receive_batch's, and HARE_E_INVALID when first_ray < 0 or
  * first_ray + n > 2^62, or when the source's B is not the band count of Model[top_index]; HARE_E_STATE when no source is set.  The sharded
  * call also refuses scenes whose source or "source_seed" differ.  These calls (and hare_receive_source_reduced) take HARE_RECEIVE_DIRECT
- * ("Direct sound") and HARE_RECEIVE_IMAGE ("Image sources (first order)"); the hare_receive_batch calls refuse both. */
+ * ("Direct sound"), HARE_RECEIVE_IMAGE ("Image sources (first order)") and, with it, HARE_RECEIVE_IMAGE2 ("Image sources (second order)");
+ * the hare_receive_batch calls refuse all three. */
 HARE_API int hare_receive_source(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, int64_t first_ray, int32_t bounces,
                                  uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits, double *state_out, uint64_t *hist,
                                  uint64_t *detections, hare_counters *ctr);

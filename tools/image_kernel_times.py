@@ -9,7 +9,7 @@ import json
 import statistics
 import sys
 
-WANTED = ("hare_image_", "hare_direct_", "_occl")
+WANTED = ("hare_image", "hare_direct_", "_occl")
 
 
 def summarise(path):

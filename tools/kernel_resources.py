@@ -1,20 +1,30 @@
-"""Register / spill / scratch / LDS figures of every kernel in the built code object, from the metadata the compiler
-writes into hare_amd/csrc/build/hare_kernels.s (made next to the code object by the Makefile)."""
+"""Register and scratch figures of kernels from the metadata the compiler writes next to the code object (hare_amd/csrc/build/hare_kernels.s,
+made by the library's Makefile): for every kernel whose name starts with one of the prefixes, vgpr_count, sgpr_count,
+private_segment_fixed_size (scratch), vgpr_spill_count and group_segment_fixed_size (LDS).  Prints ONE JSON object, keys sorted.
+tests/golden/image2/parent_receive_resources.json is this tool's output on a build of the parent commit of the second-order image sources:
+  git worktree add /tmp/parent <parent commit> && make -C /tmp/parent/hare_amd/csrc all
+  python tools/kernel_resources.py /tmp/parent/hare_amd/csrc/build/hare_kernels.s hare_receive hare_rain > tests/golden/image2/parent_receive_resources.json
+profiles/image2/kernel_resources.json is its output for `hare_image2` on this tree's build.
+usage: python tools/kernel_resources.py hare_kernels.s PREFIX [PREFIX ..]"""
+import json
 import re
 import sys
 
-path = sys.argv[1] if len(sys.argv) > 1 else "hare_amd/csrc/build/hare_kernels.s"
-txt = open(path).read()
-meta = txt[txt.index("amdhsa.kernels:"):]
-rows = []
-for blk in re.split(r"\n  - \.agpr_count:", meta)[1:]:
-    def g(key):
-        m = re.search(r"\." + key + r":\s+(\S+)", blk)
-        return m.group(1) if m else "?"
-    rows.append((g("name"), g("vgpr_count"), g("vgpr_spill_count"), g("sgpr_count"), g("sgpr_spill_count"),
-                 g("private_segment_fixed_size"), g("group_segment_fixed_size")))
-print(f"{'kernel':34s} {'vgpr':>5s} {'vspill':>6s} {'sgpr':>5s} {'sspill':>6s} {'scratch':>7s} {'lds':>6s}")
-for r in sorted(rows):
-    if len(sys.argv) > 2 and sys.argv[2] not in r[0]:
-        continue
-    print(f"{r[0]:34s} {r[1]:>5s} {r[2]:>6s} {r[3]:>5s} {r[4]:>6s} {r[5]:>7s} {r[6]:>6s}")
+
+def resources(path, prefixes):
+    txt = open(path).read()
+    meta = txt[txt.index("amdhsa.kernels:"):]
+    out = {}
+    for blk in re.split(r"\n  - \.agpr_count:", meta)[1:]:
+        def g(key):
+            return re.search(r"\." + key + r":\s+(\S+)", blk).group(1)
+        name = g("name")
+        if any(name.startswith(p) for p in prefixes):
+            out[name] = {k: int(g(k)) for k in ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size")}
+    return out
+
+
+if __name__ == "__main__":
+    if len(sys.argv) < 3:
+        sys.exit(__doc__)
+    print(json.dumps(resources(sys.argv[1], sys.argv[2:]), indent=1, sort_keys=True))

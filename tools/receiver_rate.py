@@ -33,9 +33,15 @@ With --source --direct --image, the first-order image sources too ("Image source
 more calls interleaved, `direct + image` with the pair search's pre-cull (scene option "image_cull" 1) and without it (0), their wall
 times and the same noise figure for `direct + image`.  With --image-cull N as well (a profiling run: rocprofv3 --kernel-trace --stats, one
 run per N, then tools/image_kernel_times.py on the two traces), only `direct` and `direct + image` with "image_cull" N run, and no noise.
+With --source --direct --image --image2, the second-order image sources ("Image sources (second order)": HARE_RECEIVE_IMAGE2): per layout,
+first a probe -- hare_image2_device alone on lists of 2^26 candidates and 2^24 paths, with "image2_prune" 1 and 0 (or only N with
+--image2-prune N: a profiling run under rocprofv3 --kernel-trace --stats, condensed by tools/image_kernel_times.py), its candidate and path
+counts and its device time (events around the call; median, min .. max) -- then, if the counts fit lists of 2^26, the options
+"image2_max_cands" / "image2_max_paths" set to the next powers of two and `direct + image` against `direct + image + image2`, interleaved,
+wall time and the same noise figure.
 Prints ONE JSON line.  usage: python tools/receiver_rate.py [hall|cathedral] [--rays N] [--bounces B] [--reps R] [--host] [--quick]
                                                           [--scatter SIGMA] [--rain] [--directional] [--time-limit] [--floor-bits N [--roulette]]
-                                                          [--source [--direct [--image [--image-cull N]]]] [--map K[,K..]]"""
+                                                          [--source [--direct [--image [--image-cull N] [--image2 [--image2-prune N]]]]] [--map K[,K..]]"""
 import argparse
 import json
 import os
@@ -66,6 +72,8 @@ ap.add_argument("--source", action="store_true", help="K = 8, B = 8: hare_receiv
 ap.add_argument("--direct", action="store_true", help="with --source: hare_receive_source with and without HARE_RECEIVE_DIRECT, time and noise")
 ap.add_argument("--image", action="store_true", help="with --source --direct: also direct + HARE_RECEIVE_IMAGE, with and without the pair search's pre-cull")
 ap.add_argument("--image-cull", type=int, default=None, choices=[0, 1], metavar="N", help="with --image: a profiling run with \"image_cull\" N only")
+ap.add_argument("--image2", action="store_true", help="with --source --direct --image: also direct + image + HARE_RECEIVE_IMAGE2, its counts, times and noise")
+ap.add_argument("--image2-prune", type=int, default=None, choices=[0, 1], metavar="N", help="with --image2: a profiling run, the probe with \"image2_prune\" N only")
 ap.add_argument("--map", default=None, metavar="K[,K..]", help="B = 8: receiver maps (planes of about K receivers, a cloud of 4096) against the linear loop at K = 256")
 a = ap.parse_args()
 if a.reps is None:
@@ -135,6 +143,30 @@ def source_run():
     print(json.dumps(row))
 
 
+def image2_probe(p, K, B, n_bins, bin_len, prunes):
+    """hare_image2_device alone on lists nothing overflows but the unpruned hall: counts and device time per "image2_prune"."""
+    C, M = 1 << 26, 1 << 24
+    d_w = torch.empty(H.Voxel_Grid.image2_work_bytes(T.Polygon_Count, C, M), dtype=torch.uint8, device="cuda")
+    d_h = torch.zeros(K * n_bins * B, dtype=torch.int64, device="cuda")
+    d_d = torch.zeros(2 * K, dtype=torch.int64, device="cuda")
+    out = {"max_cands": C, "max_paths": M}
+    for prune in prunes:
+        p.set_option("image2_prune", prune)
+        ms = []
+        for rep in range(4 if prune == 0 else a.reps + 1):              # the first is the warm-up
+            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            p.Image2_device(n, n_bins, bin_len, FRAC, C, M, d_w.data_ptr(), d_h.data_ptr(), d_d.data_ptr(), stream=st)
+            e1.record(); torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+            print("image2 probe", K, "prune", prune, "rep", rep, round(ms[-1], 3), "ms", file=sys.stderr, flush=True)
+        cnt = d_w[:16].cpu().numpy().view(np.uint64)
+        out["prune%d" % prune] = {"cands": int(cnt[0]), "paths": int(cnt[1]) if int(cnt[0]) <= C else None, "fits": bool(cnt[0] <= C and cnt[1] <= M),
+                                  "device_ms": round(float(np.median(ms[1:])), 3), "device_min_max_ms": [round(min(ms[1:]), 3), round(max(ms[1:]), 3)]}
+    p.set_option("image2_prune", 1)
+    return out
+
+
 def direct_run():
     """hare_receive_source with and without HARE_RECEIVE_DIRECT: host wall time, and the spread of a mid-hall receiver's early energy."""
     B, bin_len, n_bins = 8, 0.2, 1000
@@ -164,6 +196,18 @@ def direct_run():
             else:
                 del calls["plain"]
                 calls["direct_image"] = lambda: imaged(a.image_cull)
+        probe = None
+        if a.image2:
+            probe = image2_probe(p, int(c.shape[0]), B, n_bins, bin_len, (1, 0) if a.image2_prune is None else (a.image2_prune,))
+            if a.image2_prune is not None:                                # a profiling run: counts and the profiler's kernel times
+                rows[name] = {"K": int(c.shape[0]), "map": as_map, "image2_probe": probe}
+                continue
+            calls = {"direct_image": lambda: imaged(1)}
+            best = probe["prune1"]
+            if best["fits"]:
+                p.set_option("image2_max_cands", max(1024, 1 << int(best["cands"] - 1).bit_length()))
+                p.set_option("image2_max_paths", max(1024, 1 << int(best["paths"] - 1).bit_length()))
+                calls["direct_image2"] = lambda p=p: p.Receive_source(n, nb, n_bins, bin_len, frac_bits=FRAC, direct=True, image=True, image2=True)
         for f in calls.values():
             f()                                                           # the warm-up
         wall = {k: [] for k in calls}
@@ -173,12 +217,17 @@ def direct_run():
                 f()
                 wall[k].append((time.perf_counter() - t0) * 1e3)
         row = {"K": int(c.shape[0]), "map": as_map}
+        if probe is not None:
+            row["image2_probe"] = probe
+            row["image2_lists"] = [p.get_option("image2_max_cands"), p.get_option("image2_max_paths")]
         for k, v in wall.items():
             row[k + "_ms"] = round(float(np.median(v)), 3)
             row[k + "_min_max_ms"] = [round(min(v), 3), round(max(v), 3)]
         if "plain" in calls:
             row["direct_over_plain"] = round(row["direct_ms"] / row["plain_ms"], 4)
-        if a.image:
+        if "direct_image2" in calls:
+            row["image2_added_ms"] = round(row["direct_image2_ms"] - row["direct_image_ms"], 3)
+        if a.image and "direct" in calls:
             row["image_added_ms"] = round(row["direct_image_ms"] - row["direct_ms"], 3)
         if "direct_image_nocull" in calls:
             row["image_nocull_added_ms"] = round(row["direct_image_nocull_ms"] - row["direct_ms"], 3)
