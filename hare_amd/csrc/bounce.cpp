@@ -90,6 +90,17 @@ int ensure_bounce_buffers(const HipApi* H, Scene::BounceBuf& b, int64_t n, int32
     return HARE_OK;
 }
 
+// A device buffer of at least `bytes`: kept when it is large enough (0 bytes: always), else freed and allocated again
+int grow(const HipApi* H, void*& p, size_t& cap, size_t bytes)
+{
+    if (bytes <= cap) return HARE_OK;
+    dev_free(H, p);
+    cap = 0;
+    HIP_TRY(H->Malloc(&p, bytes));
+    cap = bytes;
+    return HARE_OK;
+}
+
 void fill_miss_host(hare_xevent* e, int64_t n)
 {
     memset(e, 0, (size_t)n * sizeof(hare_xevent));          // X_Event(): Hare_Geometry_Primitives.cs:454-462
@@ -260,68 +271,25 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
     const size_t K = s.rcv.size() / 4;
     const size_t state_bytes = (size_t)n * (size_t)(1 + B) * sizeof(double);
     const size_t hist_words = receive_hist_words(s, top, job.n_bins, job.flags), hist_bytes = (hist_words + 2 * K) * sizeof(uint64_t);
-    if (state_bytes > b.state_cap) {
-        dev_free(H, b.state);
-        b.state_cap = 0;
-        HIP_TRY(H->Malloc(&b.state, state_bytes));
-        b.state_cap = state_bytes;
-    }
-    if (hist_bytes > b.hist_cap) {
-        dev_free(H, b.hist);
-        b.hist_cap = 0;
-        HIP_TRY(H->Malloc(&b.hist, hist_bytes));
-        b.hist_cap = hist_bytes;
-    }
+    if (int rc = grow(H, b.state, b.state_cap, state_bytes)) return rc;
+    if (int rc = grow(H, b.hist, b.hist_cap, hist_bytes)) return rc;
     const bool rain = receive_rains(s, top, job.flags);
-    const size_t rain_bytes = (size_t)HARE_RECEIVE_RAIN_WORK_BYTES(n);
-    if (rain && rain_bytes > b.rain_cap) {
-        dev_free(H, b.rain);
-        b.rain_cap = 0;
-        HIP_TRY(H->Malloc(&b.rain, rain_bytes));
-        b.rain_cap = rain_bytes;
-    }
+    if (int rc = grow(H, b.rain, b.rain_cap, rain ? (size_t)HARE_RECEIVE_RAIN_WORK_BYTES(n) : 0)) return rc;
     // the reduction's own block: sums, crossings, weights, each from a 16-byte boundary
     const ReduceSpec* const red = job.reduce;
     const size_t sums_bytes = red ? K * (size_t)B * (size_t)red->n_win * 4 * sizeof(uint64_t) : 0;
     const size_t cross_words = red ? K * (size_t)B * (size_t)red->n_lev : 0, cross_bytes = (cross_words * sizeof(int32_t) + 15) & ~(size_t)15;
     const size_t weight_bytes = red && red->weight ? (size_t)job.n_bins * (size_t)B * sizeof(uint32_t) : 0;
-    if (red && sums_bytes + cross_bytes + weight_bytes > b.red_cap) {
-        dev_free(H, b.red);
-        b.red_cap = 0;
-        HIP_TRY(H->Malloc(&b.red, sums_bytes + cross_bytes + weight_bytes));
-        b.red_cap = sums_bytes + cross_bytes + weight_bytes;
-    }
-    const size_t direct_bytes = job.direct_weight > 0 ? (size_t)HARE_DIRECT_WORK_BYTES(K) : 0;
-    if (direct_bytes > b.direct_cap) {
-        dev_free(H, b.direct);
-        b.direct_cap = 0;
-        HIP_TRY(H->Malloc(&b.direct, direct_bytes));
-        b.direct_cap = direct_bytes;
-    }
+    if (int rc = grow(H, b.red, b.red_cap, red ? sums_bytes + cross_bytes + weight_bytes : 0)) return rc;
+    if (int rc = grow(H, b.direct, b.direct_cap, job.direct_weight > 0 ? (size_t)HARE_DIRECT_WORK_BYTES(K) : 0)) return rc;
     const int64_t image_pairs = s.opt.image_max_pairs;
-    const size_t image_bytes = job.image_weight > 0 ? (size_t)HARE_IMAGE_WORK_BYTES(K, s.topos[(size_t)top].P, image_pairs) : 0;
-    if (image_bytes > b.image_cap) {
-        dev_free(H, b.image);
-        b.image_cap = 0;
-        HIP_TRY(H->Malloc(&b.image, image_bytes));
-        b.image_cap = image_bytes;
-    }
+    if (int rc = grow(H, b.image, b.image_cap, job.image_weight > 0 ? (size_t)HARE_IMAGE_WORK_BYTES(K, s.topos[(size_t)top].P, image_pairs) : 0)) return rc;
     const int64_t image2_cands = s.opt.image2_max_cands, image2_paths = s.opt.image2_max_paths;
-    const size_t image2_bytes = job.image2_weight > 0 ? (size_t)HARE_IMAGE2_WORK_BYTES(s.topos[(size_t)top].P, image2_cands, image2_paths) : 0;
-    if (image2_bytes > b.image2_cap) {
-        dev_free(H, b.image2);
-        b.image2_cap = 0;
-        HIP_TRY(H->Malloc(&b.image2, image2_bytes));
-        b.image2_cap = image2_bytes;
-    }
+    if (int rc = grow(H, b.image2, b.image2_cap, job.image2_weight > 0 ? (size_t)HARE_IMAGE2_WORK_BYTES(s.topos[(size_t)top].P, image2_cands, image2_paths) : 0))
+        return rc;
     // the loop's byte per ray (ReceiveArgs::spec2): only a topology with a scattering table reads or writes it
-    const size_t spec2_bytes = ((job.flags & HARE_RECEIVE_IMAGE2) && scene_has_scattering(s, top)) ? (size_t)HARE_RECEIVE_IMAGE2_WORK_BYTES(n) : 0;
-    if (spec2_bytes > b.spec2_cap) {
-        dev_free(H, b.spec2);
-        b.spec2_cap = 0;
-        HIP_TRY(H->Malloc(&b.spec2, spec2_bytes));
-        b.spec2_cap = spec2_bytes;
-    }
+    const bool spec2 = (job.flags & HARE_RECEIVE_IMAGE2) && scene_has_scattering(s, top);
+    if (int rc = grow(H, b.spec2, b.spec2_cap, spec2 ? (size_t)HARE_RECEIVE_IMAGE2_WORK_BYTES(n) : 0)) return rc;
     if (!c.st[0]) HIP_TRY(H->StreamCreate(&c.st[0]));
     hipStream_t st = c.st[0];
     uint64_t* const d_hist = (uint64_t*)b.hist;

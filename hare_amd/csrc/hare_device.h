@@ -581,19 +581,18 @@ struct SourceArgs {
     int32_t res;               // R: 0 (no table) .. kMaxSourceRes
 };
 
-// hare_direct_emit / hare_direct_deposit[_dir] (direct.hip): the direct sound (include/hare_hip.h, "receivers", "Direct sound") -- a lane per
-// receiver.  The emission writes receiver k's shadow ray (origin: the source, direction: to the center, t_max 1.0; exclusion word -1, or -2
-// for a receiver the source lies inside: no traversal, not occluded); the flags-only occlusion kernels answer; the deposit adds the
-// visible receivers' words.  Position, power and frame by value, as in SourceArgs
-struct DirectArgs {
+// What every deposit of the deterministic source paths reads (deposit.hip: deposit_tail; receive.cpp: deposit_fill) -- the first member of
+// DirectArgs, ImageArgs and Image2Args.  S slots of shadow rays: K (direct), 2 max_pairs (first order), 3 max_paths (second order).
+// Position, power and frame by value, as in SourceArgs
+struct DepositArgs {
     const double* rcv;         // n_rcv x 4: cx, cy, cz, r * r
     const double* gain;        // the source's table (null iff res == 0)
-    unsigned long long* hist;  // n_rcv x n_bins x bands (x 4: hare_direct_deposit_dir), accumulated
+    unsigned long long* hist;  // n_rcv x n_bins x bands (x 4: the _dir deposits), accumulated
     unsigned long long* det;   // 2 n_rcv, accumulated
-    RayRec* srays;             // n_rcv shadow rays
-    double* stmax;             // n_rcv t_max (1.0)
-    int32_t* sexcl;            // n_rcv: -1 for an eligible receiver, -2 for the others
-    const int32_t* socc;       // n_rcv occlusion flags (the deposit reads them)
+    RayRec* srays;             // S shadow rays
+    double* stmax;             // S t_max (1.0)
+    int32_t* sexcl;            // S exclusion words (poly_origin1): -2 for a slot without a query
+    const int32_t* socc;       // S occlusion flags (the deposit reads them)
     double pos[3];
     double power[kMaxBands];
     double frame[9];
@@ -606,42 +605,38 @@ struct DirectArgs {
     int32_t n_bins;
 };
 
+// The topology as the image-source kernels read it (receive.cpp: image_scene_fill), a member of ImageArgs and Image2Args.  cull and cf are
+// named as in VoxelArgs: cull_load / cull_ray / cull_test are handed this struct
+struct ImageScene {
+    const PolyRec* polys;      // Model[top]
+    const QuadRec* quads;      // null when the topology is all triangles
+    const unsigned char* cull; // the pre-cull's dense records of the topology
+    const double* alpha;       // nullable: P x bands
+    const double* sigma;       // nullable: P x bands
+    CullFrame cf;
+    int32_t n_poly;
+};
+
+// hare_direct_emit / hare_direct_deposit[_dir] (direct.hip): the direct sound (include/hare_hip.h, "receivers", "Direct sound") -- a lane per
+// receiver.  The emission writes receiver k's shadow ray (origin: the source, direction: to the center, t_max 1.0; exclusion word -1, or -2
+// for a receiver the source lies inside: no traversal, not occluded); the flags-only occlusion kernels answer; the deposit adds the
+// visible receivers' words
+struct DirectArgs {
+    DepositArgs d;             // S = n_rcv
+};
+
 // hare_image_mirror / hare_image_pairs / hare_image_deposit[_dir] (image.hip): first-order image sources (include/hare_hip.h, "receivers",
 // "Image sources (first order)").  The mirror writes img (a lane per polygon), zeroes *count and marks every shadow slot -2; the pair search
 // (a lane per polygon, the receivers streamed) appends the accepted pairs: slot j holds the pair's (k, p) in pair_kp[2 j], [2 j + 1] and its
 // two shadow rays in srays[2 j] (reflection point -> center) and srays[2 j + 1] (reflection point -> source), t_max 1.0, exclusion word p; the
-// flags-only occlusion kernels answer all 2 * max_pairs slots; the deposit (a lane per pair) adds the words of the pairs with both legs free.
-// cull and cf are named as in VoxelArgs: cull_load / cull_ray / cull_test read them.  Position, power and frame by value, as in SourceArgs
+// flags-only occlusion kernels answer all 2 * max_pairs slots; the deposit (a lane per pair) adds the words of the pairs with both legs free
 struct ImageArgs {
-    const PolyRec* polys;      // Model[top]
-    const QuadRec* quads;      // null when the topology is all triangles
-    const unsigned char* cull; // the pre-cull's dense records of the topology
-    const double* rcv;         // n_rcv x 4: cx, cy, cz, r * r
-    const double* alpha;       // nullable: P x bands
-    const double* sigma;       // nullable: P x bands
-    const double* gain;        // the source's table (null iff res == 0)
-    unsigned long long* hist;  // n_rcv x n_bins x bands (x 4: hare_image_deposit_dir), accumulated
-    unsigned long long* det;   // 2 n_rcv, accumulated
+    DepositArgs d;             // S = 2 max_pairs; sexcl: p for a slot in use
+    ImageScene sc;
     unsigned long long* count; // the work block's first word: pairs found (may exceed max_pairs: then nothing is deposited)
     double* img;               // n_poly x 4: S'.x, S'.y, S'.z, 1.0 when mirrored (else 0.0)
-    RayRec* srays;             // 2 max_pairs shadow rays
-    double* stmax;             // 2 max_pairs t_max (1.0)
     int32_t* pair_kp;          // 2 max_pairs: k, p per pair
-    int32_t* sexcl;            // 2 max_pairs: p for a slot in use, -2 for the others
-    const int32_t* socc;       // 2 max_pairs occlusion flags (the deposit reads them)
-    CullFrame cf;
-    double pos[3];
-    double power[kMaxBands];
-    double frame[9];
-    double bin_len;
-    double scale;              // 2^frac_bits
-    double weight;             // W = (double)n_weight
     long long max_pairs;
-    int32_t n_rcv;
-    int32_t n_poly;
-    int32_t bands;
-    int32_t res;
-    int32_t n_bins;
     int32_t use_cull;          // scene option "image_cull"
 };
 
@@ -650,41 +645,18 @@ struct ImageArgs {
 // stage (a lane per first polygon p, the second polygons q streamed) appends (p, q, S''); the path stage (a lane per candidate, the receivers
 // streamed) appends, per accepted (k, candidate), its three shadow rays in srays[3 j .. 3 j + 2]: x2 -> center (exclusion q), x1 -> x2
 // (exclusions p and q), x1 -> source (exclusion p), t_max 1.0; the flags-only occlusion kernels answer all 3 * max_paths slots; the deposit
-// (a lane per path) adds the words of the paths with all three legs free.  The first fields are ImageArgs's, in its order
+// (a lane per path) adds the words of the paths with all three legs free
 struct Image2Args {
-    const PolyRec* polys;      // Model[top]
-    const QuadRec* quads;      // null when the topology is all triangles
-    const unsigned char* cull; // the pre-cull's dense records of the topology
-    const double* rcv;         // n_rcv x 4: cx, cy, cz, r * r
-    const double* alpha;       // nullable: P x bands
-    const double* sigma;       // nullable: P x bands
-    const double* gain;        // the source's table (null iff res == 0)
-    unsigned long long* hist;  // n_rcv x n_bins x bands (x 4: hare_image2_deposit_dir), accumulated
-    unsigned long long* det;   // 2 n_rcv, accumulated
+    DepositArgs d;             // S = 3 max_paths; sexcl: poly_origin1 of a slot in use
+    ImageScene sc;
     unsigned long long* count; // the work block's first two words: candidates found, paths found (either may exceed its list: then nothing is deposited)
     double* img;               // n_poly x 4: S'.x, S'.y, S'.z, 1.0 when mirrored (else 0.0)
     double* cand_s;            // max_cands x 3: S''
     int32_t* cand_pq;          // max_cands x 2: p, q
-    RayRec* srays;             // 3 max_paths shadow rays
-    double* stmax;             // 3 max_paths t_max (1.0)
     int32_t* path_kc;          // 2 max_paths: k and the candidate's index per path
-    int32_t* sexcl;            // 3 max_paths: poly_origin1 of a slot in use, -2 for the others
     int32_t* sexcl2;           // 3 max_paths: poly_origin2 (q on the middle leg, else -1)
-    const int32_t* socc;       // 3 max_paths occlusion flags (the deposit reads them)
-    CullFrame cf;
-    double pos[3];
-    double power[kMaxBands];
-    double frame[9];
-    double bin_len;
-    double scale;              // 2^frac_bits
-    double weight;             // W = (double)n_weight
     long long max_cands;
     long long max_paths;
-    int32_t n_rcv;
-    int32_t n_poly;
-    int32_t bands;
-    int32_t res;
-    int32_t n_bins;
     int32_t prune;             // scene option "image2_prune"
 };
 

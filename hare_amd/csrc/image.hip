@@ -1,6 +1,7 @@
 // image.hip -- hare_image_mirror, hare_image_pairs, hare_image_deposit, hare_image_deposit_dir: first-order image sources (include/hare_hip.h,
-// "receivers", "Image sources (first order)"), #included from kernels.hip behind direct.hip, whose helpers (source_gains, quant_m, dir_q) it
-// shares.  Four launches per call (receive.cpp: image_enqueue): the mirror writes each polygon's image S' of the source; the pair search
+// "receivers", "Image sources (first order)"), #included from kernels.hip behind deposit.hip, whose vector (path_vector) and deposit
+// (deposit_tail) it shares.  What it shares with image2.hip is here: the mirror's arithmetic and fill, the receiver tile, the image load, the
+// append of the searches (wave_append) and a polygon's reflectance.  Four launches per call (receive.cpp: image_enqueue): the mirror writes each polygon's image S' of the source; the pair search
 // finds the (receiver, polygon) pairs whose segment S' -> center passes through the polygon and appends, per pair, the reflection point's
 // two shadow rays; the flags-only occlusion kernels of the call's partition answer them -- no traversal code here; the deposit adds the
 // words of the pairs both of whose legs are free.  FP64, no contraction; sqrt and / are the correctly rounded ones: bit-exact with
@@ -20,16 +21,6 @@
 // exact test rejects); the exact two-sided FP64 test (poly_fast, hare_math.h) runs on the survivors, which are about as many as the pairs
 // found.  Accepted pairs are appended with ONE atomic per wave (ballot, popcount, the leader adds, the lanes take their ranks).
 
-// v = c_k - S' and d2 = |v|^2, the same operations in the pair search and in the deposit (so the deposit sees the search's bits)
-static __device__ __forceinline__ double image_vector(double cx, double cy, double cz, double sx, double sy, double sz, double& vx, double& vy,
-                                                      double& vz)
-{
-    vx = cx - sx;
-    vy = cy - sy;
-    vz = cz - sz;
-    return (vx * vx + vy * vy) + vz * vz;
-}
-
 // The point (sx, sy, sz) mirrored in the plane of polygon pr: o[0 .. 2] = the image, o[3] = 1.0 when mirrored, else 0.0 (a NaN, a point on the
 // plane or a normal of length 0: no image).  hare_image_mirror's arithmetic, shared with image2.hip (which mirrors S' again)
 static __device__ __forceinline__ bool image_mirror_point(const PolyRec& pr, double sx, double sy, double sz, double* o)
@@ -46,20 +37,79 @@ static __device__ __forceinline__ bool image_mirror_point(const PolyRec& pr, dou
     return mirrored;
 }
 
-// A lane per polygon (grid-stride): S' and the mirrored mark, img[4 p .. 4 p + 3] = S'.x, S'.y, S'.z, 1.0 / 0.0.  The same launch zeroes the
-// pair count and marks all 2 * max_pairs shadow-ray slots -2 (no query: the occlusion kernels skip them under HARE_SHOOT_RETIRED_RAYS), so
-// the occlusion launch needs no count on the host.
+// The mirror kernels' body, a lane per polygon (grid-stride: lane tid of stride, which the kernel forms): S' and the mirrored mark, img[4 p .. 4 p + 3] = S'.x, S'.y, S'.z, 1.0 / 0.0.  The
+// same launch marks all `slots` shadow-ray slots -2 (no query: the occlusion kernels skip them under HARE_SHOOT_RETIRED_RAYS), with
+// poly_origin2 -1 where the call has a second exclusion array, so the occlusion launch needs no count on the host
+static __device__ __forceinline__ void image_mirror_fill(const DepositArgs& d, const ImageScene& sc, double* img, long long slots, int32_t* sexcl2,
+                                                         long long tid, long long stride)
+{
+    for (long long i = tid; i < slots; i += stride) {
+        d.sexcl[i] = -2;
+        if (sexcl2) sexcl2[i] = -1;
+    }
+    for (long long p = tid; p < (long long)sc.n_poly; p += stride) image_mirror_point(sc.polys[p], d.pos[0], d.pos[1], d.pos[2], img + 4 * (size_t)p);
+}
+
+// The same launch also zeroes the pair count
 extern "C" __global__ __launch_bounds__(256) void hare_image_mirror(ImageArgs a)
 {
     const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
     if (tid == 0) *a.count = 0ull;
-    for (long long i = tid; i < 2 * a.max_pairs; i += stride) a.sexcl[i] = -2;
-    for (long long p = tid; p < (long long)a.n_poly; p += stride) {
-        image_mirror_point(a.polys[p], a.pos[0], a.pos[1], a.pos[2], a.img + 4 * (size_t)p);
-    }
+    image_mirror_fill(a.d, a.sc, a.img, 2 * a.max_pairs, nullptr, tid, stride);
 }
 
 constexpr int kImageTile = 256;          // receivers a workgroup stages in LDS (32 B each)
+
+// Receivers k0 .. k0 + nk - 1 (center, r * r) into the workgroup's tile, and the barrier behind it
+static __device__ __forceinline__ void stage_receivers(double* lds, const double* rcv, int k0, int nk)
+{
+    for (int j = threadIdx.x; j < nk * 4; j += blockDim.x) lds[j] = rcv[4 * (size_t)k0 + (size_t)j];
+    __syncthreads();
+}
+
+// S' of polygon p for a lane that is on; `on` goes off where p has no image
+static __device__ __forceinline__ void load_image(const double* img, int p, bool& on, double& sx, double& sy, double& sz)
+{
+    sx = sy = sz = 0;
+    if (on) {
+        const double* const im = img + 4 * (size_t)p;
+        sx = im[0];
+        sy = im[1];
+        sz = im[2];
+        on = im[3] != 0.0;
+    }
+}
+
+// The fourth corner of polygon p, null for a triangle
+static __device__ __forceinline__ const double* quad_v3(const QuadRec* quads, int p)
+{
+    return (quads && quads[p].nverts == 4) ? quads[p].v3 : nullptr;
+}
+
+// The reflectance of polygon p in band b: (1 - alpha) (1 - sigma), a missing table counting as zeros.  The deposits ask per band, behind the
+// bin test: row pointers formed ahead of deposit_tail would stay live across it (six more VGPRs in the second-order deposit)
+static __device__ __forceinline__ double poly_reflectance(const ImageScene& sc, int B, int p, int b)
+{
+    const size_t j = (size_t)p * (size_t)B + (size_t)b;
+    return (1.0 - (sc.alpha ? sc.alpha[j] : 0.0)) * (1.0 - (sc.sigma ? sc.sigma[j] : 0.0));
+}
+
+// The append of the three searches, ONE atomic per wave: the lanes that accepted are counted (ballot, popcount), the first of them adds the
+// count to *counter, and each takes its rank behind the old value and hands its slot to write(slot).  The slot may lie beyond the caller's
+// list (counted, not written): write tests slot < its limit.  A wave in which no lane accepted -- the common case -- leaves behind the
+// ballot.  (A form that returns the slot to the caller costs the empty wave four more instructions and pairs / cands two VGPRs: the
+// compiler keeps the merged "no slot" value alive instead of branching on.)
+template <class Write>
+static __device__ __forceinline__ void wave_append(bool acc, unsigned long long* counter, int lane, Write write)
+{
+    const unsigned long long m = __ballot(acc);
+    if (m == 0ull) return;
+    const int leader = __ffsll((long long)m) - 1;
+    unsigned long long base = 0;
+    if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(m));
+    base = __shfl(base, leader, 64);
+    if (acc) write(base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull)));
+}
 
 extern "C" __global__ __launch_bounds__(256) void hare_image_pairs(ImageArgs a)
 {
@@ -67,31 +117,24 @@ extern "C" __global__ __launch_bounds__(256) void hare_image_pairs(ImageArgs a)
     const int lane = threadIdx.x & 63;
     const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     const int k0 = (int)blockIdx.y * kImageTile;
-    const int nk = a.n_rcv - k0 < kImageTile ? a.n_rcv - k0 : kImageTile;
-    for (int j = threadIdx.x; j < nk * 4; j += blockDim.x) rcv[j] = a.rcv[4 * (size_t)k0 + (size_t)j];
-    __syncthreads();
-    bool on = p < a.n_poly;
-    double sx = 0, sy = 0, sz = 0;
-    if (on) {
-        const double* const im = a.img + 4 * (size_t)p;
-        sx = im[0];
-        sy = im[1];
-        sz = im[2];
-        on = im[3] != 0.0;
-    }
+    const int nk = a.d.n_rcv - k0 < kImageTile ? a.d.n_rcv - k0 : kImageTile;
+    stage_receivers(rcv, a.d.rcv, k0, nk);
+    bool on = p < a.sc.n_poly;
+    double sx, sy, sz;
+    load_image(a.img, p, on, sx, sy, sz);
     if (__ballot(on) == 0ull) return;                                  // a wave without a mirrored polygon
     const int pi = on ? p : 0;
     const bool cull = a.use_cull != 0;                                  // scene option "image_cull" (uniform)
-    CullRaw cr = cull_load(a, pi);
-    CullRay ray = cull_ray(a, sx, sy, sz, 0.0, 0.0, 0.0);               // the origin part: S' for every receiver
-    const double* const v3 = (a.quads && a.quads[pi].nverts == 4) ? a.quads[pi].v3 : nullptr;
+    CullRaw cr = cull_load(a.sc, pi);
+    CullRay ray = cull_ray(a.sc, sx, sy, sz, 0.0, 0.0, 0.0);            // the origin part: S' for every receiver
+    const double* const v3 = quad_v3(a.sc.quads, pi);
     const V3 o = {sx, sy, sz};
     for (int j = 0; j < nk; ++j) {
         const double cx = rcv[4 * j + 0], cy = rcv[4 * j + 1], cz = rcv[4 * j + 2], rr = rcv[4 * j + 3];
         bool acc = false;
         double t = 0, vx = 0, vy = 0, vz = 0;
         if (on) {
-            const double d2 = image_vector(cx, cy, cz, sx, sy, sz, vx, vy, vz);
+            const double d2 = path_vector(cx, cy, cz, sx, sy, sz, vx, vy, vz);
             if (d2 > rr) {
                 bool test = true;
                 if (cull) {
@@ -99,43 +142,35 @@ extern "C" __global__ __launch_bounds__(256) void hare_image_pairs(ImageArgs a)
                     ray.dfy = (float)vy;
                     ray.dfz = (float)vz;
                     ray.dm = fabsf(ray.dfx) + fabsf(ray.dfy) + fabsf(ray.dfz);
-                    test = !cull_test(a, ray, cr);
+                    test = !cull_test(a.sc, ray, cr);
                 }
                 if (test) {
                     const V3 d = {vx, vy, vz};
-                    acc = poly_fast(a.polys[pi], v3, o, d, t) && t > 0.0 && t < 1.0;
+                    acc = poly_fast(a.sc.polys[pi], v3, o, d, t) && t > 0.0 && t < 1.0;
                 }
             }
         }
-        const unsigned long long m = __ballot(acc);
-        if (m == 0ull) continue;                                        // the common case: no lane's polygon reflects to receiver j
-        const int leader = __ffsll((long long)m) - 1;
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(a.count, (unsigned long long)__popcll(m));
-        base = __shfl(base, leader, 64);
-        if (acc) {
-            const unsigned long long slot = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-            if (slot < (unsigned long long)a.max_pairs) {              // beyond the list: counted, not written (the deposit then adds nothing)
-                RayRec s;
-                s.x = sx + vx * t;
-                s.y = sy + vy * t;
-                s.z = sz + vz * t;
-                s.dx = cx - s.x;
-                s.dy = cy - s.y;
-                s.dz = cz - s.z;
-                a.srays[2 * slot] = s;
-                s.dx = a.pos[0] - s.x;
-                s.dy = a.pos[1] - s.y;
-                s.dz = a.pos[2] - s.z;
-                a.srays[2 * slot + 1] = s;
-                a.stmax[2 * slot] = 1.0;
-                a.stmax[2 * slot + 1] = 1.0;
-                a.sexcl[2 * slot] = p;
-                a.sexcl[2 * slot + 1] = p;
-                a.pair_kp[2 * slot] = k0 + j;
-                a.pair_kp[2 * slot + 1] = p;
-            }
-        }
+        wave_append(acc, a.count, lane, [&](unsigned long long slot) {
+            if (slot >= (unsigned long long)a.max_pairs) return;        // beyond the list: counted, not written (the deposit then adds nothing)
+            RayRec s;
+            s.x = sx + vx * t;
+            s.y = sy + vy * t;
+            s.z = sz + vz * t;
+            s.dx = cx - s.x;
+            s.dy = cy - s.y;
+            s.dz = cz - s.z;
+            a.d.srays[2 * slot] = s;
+            s.dx = a.d.pos[0] - s.x;
+            s.dy = a.d.pos[1] - s.y;
+            s.dz = a.d.pos[2] - s.z;
+            a.d.srays[2 * slot + 1] = s;
+            a.d.stmax[2 * slot] = 1.0;
+            a.d.stmax[2 * slot + 1] = 1.0;
+            a.d.sexcl[2 * slot] = p;
+            a.d.sexcl[2 * slot + 1] = p;
+            a.pair_kp[2 * slot] = k0 + j;
+            a.pair_kp[2 * slot + 1] = p;
+        });
     }
 }
 
@@ -148,49 +183,18 @@ static __device__ __forceinline__ void image_deposit_body(const ImageArgs& a)
     if (found > (unsigned long long)a.max_pairs) return;               // the list overflowed: nothing at all is added
     const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= found) return;
-    if (a.socc[2 * i] != 0 || a.socc[2 * i + 1] != 0) return;           // a leg is occluded
+    if (a.d.socc[2 * i] != 0 || a.d.socc[2 * i + 1] != 0) return;       // a leg is occluded
     const int k = a.pair_kp[2 * i], p = a.pair_kp[2 * i + 1];
-    const int B = a.bands;
     const double* const im = a.img + 4 * (size_t)p;
-    const double* const rc = a.rcv + 4 * (size_t)k;
-    const double rr = rc[3];
-    double vx, vy, vz;
-    const double d2 = image_vector(rc[0], rc[1], rc[2], im[0], im[1], im[2], vx, vy, vz);
-    const double dist = sqrt(d2);
-    const double y = rr / d2;
-    const double f = (0.5 * y) / (1.0 + sqrt(1.0 - y));
-    const double fw = f * a.weight;
-    const double xb = dist / a.bin_len;
-    const bool binned = xb >= 0 && xb < (double)a.n_bins;
-    atomicAdd(&a.det[2 * (size_t)k + (binned ? 0 : 1)], 1ull);
-    if (!binned) return;
-    const int bin = (int)floor(xb);
-    const RayRec& s = a.srays[2 * i];                                   // its origin: the reflection point x
-    const double* const g = a.res > 0 ? source_gains(a.gain, a.frame, a.res, B, s.x - a.pos[0], s.y - a.pos[1], s.z - a.pos[2]) : nullptr;
-    const double* const al = a.alpha ? a.alpha + (size_t)p * (size_t)B : nullptr;
-    const double* const sg = a.sigma ? a.sigma + (size_t)p * (size_t)B : nullptr;
-    unsigned long long* const w = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B * (DIR ? 4 : 1);
-    [[maybe_unused]] double ax = 0, ay = 0, az = 0;
-    if constexpr (DIR) {
-        ax = -(vx / dist);
-        ay = -(vy / dist);
-        az = -(vz / dist);
-    }
-#pragma unroll
-    for (int b = 0; b < kMaxBands; ++b) {
-        if (b < B) {
-            const double r = (1.0 - (al ? al[b] : 0.0)) * (1.0 - (sg ? sg[b] : 0.0));
-            const double m = quant_m((((a.power[b] * (g ? g[b] : 1.0)) * r) * fw) * a.scale);
-            if constexpr (DIR) {
-                atomicAdd(&w[4 * b + 0], (unsigned long long)rint(m));
-                atomicAdd(&w[4 * b + 1], dir_q(m, ax));
-                atomicAdd(&w[4 * b + 2], dir_q(m, ay));
-                atomicAdd(&w[4 * b + 3], dir_q(m, az));
-            } else {
-                atomicAdd(&w[b], (unsigned long long)rint(m));
-            }
-        }
-    }
+    deposit_tail<DIR>(
+        a.d, k, im[0], im[1], im[2],
+        [&](double& gx, double& gy, double& gz) {                       // source -> x, the reflection point: the origin of the pair's shadow rays
+            const RayRec& s = a.d.srays[2 * i];
+            gx = s.x - a.d.pos[0];
+            gy = s.y - a.d.pos[1];
+            gz = s.z - a.d.pos[2];
+        },
+        [&](int b) { return poly_reflectance(a.sc, a.d.bands, p, b); });
 }
 
 extern "C" __global__ __launch_bounds__(256) void hare_image_deposit(ImageArgs a)

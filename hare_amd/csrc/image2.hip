@@ -1,6 +1,7 @@
 // image2.hip -- hare_image2_mirror, hare_image2_cands, hare_image2_paths, hare_image2_deposit, hare_image2_deposit_dir: second-order image
 // sources (include/hare_hip.h, "receivers", "Image sources (second order)"), #included from kernels.hip behind image.hip, whose helpers
-// (image_mirror_point, image_vector) and direct.hip's (source_gains, quant_m, dir_q) it shares.  Five launches per call (receive.cpp:
+// (image_mirror_point, image_mirror_fill, stage_receivers, load_image, quad_v3, wave_append, poly_reflectance) and deposit.hip's
+// (path_vector, deposit_tail) it shares.  Five launches per call (receive.cpp:
 // image2_enqueue): the mirror writes each polygon's image S' of the source; the candidate stage finds the ordered pairs (p, q) whose second
 // image S'' exists and that the prune cannot rule out, and appends (p, q, S''); the path stage finds the (receiver, candidate) triples whose
 // segment S'' -> center passes through q and whose segment S' -> x2 passes through p, and appends, per triple, three shadow rays; the
@@ -25,8 +26,7 @@
 // lane per receiver would leave most of the machine idle.  The grid is (max_cands / 256) x (receiver tiles); blocks beyond the count leave
 // at once.  The FP32 pre-cull on q (tv = S'' - v0_q) runs first, the two exact tests on its survivors.
 
-// A lane per polygon (grid-stride): S' and the mirrored mark, as hare_image_mirror.  The same launch zeroes both counts and marks all
-// 3 * max_paths shadow-ray slots -2 (no query), with poly_origin2 -1
+// image_mirror_fill with all 3 * max_paths shadow-ray slots and their poly_origin2; the same launch zeroes both counts
 extern "C" __global__ __launch_bounds__(256) void hare_image2_mirror(Image2Args a)
 {
     const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
@@ -34,12 +34,7 @@ extern "C" __global__ __launch_bounds__(256) void hare_image2_mirror(Image2Args 
         a.count[0] = 0ull;
         a.count[1] = 0ull;
     }
-    for (long long i = tid; i < 3 * a.max_paths; i += stride) {
-        a.sexcl[i] = -2;
-        a.sexcl2[i] = -1;
-    }
-    for (long long p = tid; p < (long long)a.n_poly; p += stride)
-        image_mirror_point(a.polys[p], a.pos[0], a.pos[1], a.pos[2], a.img + 4 * (size_t)p);
+    image_mirror_fill(a.d, a.sc, a.img, 3 * a.max_paths, a.sexcl2, tid, stride);
 }
 
 constexpr int kImage2Tile = 256;         // second polygons (80 B each) / receivers (32 B each) a workgroup stages in LDS
@@ -57,11 +52,11 @@ extern "C" __global__ __launch_bounds__(256) void hare_image2_cands(Image2Args a
     const int lane = threadIdx.x & 63;
     const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     const int q0 = (int)blockIdx.y * kImage2Tile;
-    const int nq = a.n_poly - q0 < kImage2Tile ? a.n_poly - q0 : kImage2Tile;
+    const int nq = a.sc.n_poly - q0 < kImage2Tile ? a.sc.n_poly - q0 : kImage2Tile;
     if ((int)threadIdx.x < nq) {         // stage q = q0 + threadIdx.x: the mirror's operands and the bounding sphere (centroid, farthest corner)
         const int q = q0 + (int)threadIdx.x;
-        const PolyRec& pr = a.polys[q];
-        const double* const v3 = (a.quads && a.quads[q].nverts == 4) ? a.quads[q].v3 : nullptr;
+        const PolyRec& pr = a.sc.polys[q];
+        const double* const v3 = quad_v3(a.sc.quads, q);
         double mx = (pr.v0[0] + pr.v1[0]) + pr.v2[0], my = (pr.v0[1] + pr.v1[1]) + pr.v2[1], mz = (pr.v0[2] + pr.v1[2]) + pr.v2[2];
         if (v3) {
             mx = (mx + v3[0]) / 4.0;
@@ -88,22 +83,16 @@ extern "C" __global__ __launch_bounds__(256) void hare_image2_cands(Image2Args a
         o[9] = rho;
     }
     __syncthreads();
-    bool on = p < a.n_poly;
-    double sx = 0, sy = 0, sz = 0;
-    if (on) {
-        const double* const im = a.img + 4 * (size_t)p;
-        sx = im[0];
-        sy = im[1];
-        sz = im[2];
-        on = im[3] != 0.0;
-    }
+    bool on = p < a.sc.n_poly;
+    double sx, sy, sz;
+    load_image(a.img, p, on, sx, sy, sz);
     if (__ballot(on) == 0ull) return;                                  // a wave without a mirrored polygon
     // ---- what the prune holds of p: the bounding cone of the pyramid (apex S', base p) and p's plane with the source's side
     bool prune = a.prune != 0 && on;
     double ax = 0, ay = 0, az = 0, cosm = 1.0, sinm = 0.0, pnx = 0, pny = 0, pnz = 0, pvx = 0, pvy = 0, pvz = 0, sgn = 0, nlen = 0, s1 = 0;
     if (prune) {
-        const PolyRec& pr = a.polys[p];
-        const double* const v3 = (a.quads && a.quads[p].nverts == 4) ? a.quads[p].v3 : nullptr;
+        const PolyRec& pr = a.sc.polys[p];
+        const double* const v3 = quad_v3(a.sc.quads, p);
         const double nv = v3 ? 4.0 : 3.0;
         const double gx = ((pr.v0[0] + pr.v1[0]) + pr.v2[0]) + (v3 ? v3[0] : 0.0), gy = ((pr.v0[1] + pr.v1[1]) + pr.v2[1]) + (v3 ? v3[1] : 0.0),
                      gz = ((pr.v0[2] + pr.v1[2]) + pr.v2[2]) + (v3 ? v3[2] : 0.0);
@@ -131,7 +120,7 @@ extern "C" __global__ __launch_bounds__(256) void hare_image2_cands(Image2Args a
         prune = prune && cosm > 1e-6;                                  // a cone of less than a right angle, or no prune for this p
         pnx = pr.n[0]; pny = pr.n[1]; pnz = pr.n[2];
         pvx = pr.v0[0]; pvy = pr.v0[1]; pvz = pr.v0[2];
-        sgn = dot3(a.pos[0] - pvx, a.pos[1] - pvy, a.pos[2] - pvz, pnx, pny, pnz) > 0 ? 1.0 : -1.0;
+        sgn = dot3(a.d.pos[0] - pvx, a.d.pos[1] - pvy, a.d.pos[2] - pvz, pnx, pny, pnz) > 0 ? 1.0 : -1.0;
         nlen = norm3(pnx, pny, pnz);
         s1 = (fabs(sx) + fabs(sy)) + fabs(sz);
     }
@@ -159,24 +148,16 @@ extern "C" __global__ __launch_bounds__(256) void hare_image2_cands(Image2Args a
                 acc = !(out_cone || out_side);
             }
         }
-        const unsigned long long m = __ballot(acc);
-        if (m == 0ull) continue;
-        const int leader = __ffsll((long long)m) - 1;
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(&a.count[0], (unsigned long long)__popcll(m));
-        base = __shfl(base, leader, 64);
-        if (acc) {
-            const unsigned long long slot = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-            if (slot < (unsigned long long)a.max_cands) {              // beyond the list: counted, not written (then nothing is deposited)
-                const double k2 = (2.0 * h2) / nn;
-                double* const o = a.cand_s + 3 * slot;
-                o[0] = sx - nx * k2;
-                o[1] = sy - ny * k2;
-                o[2] = sz - nz * k2;
-                a.cand_pq[2 * slot] = p;
-                a.cand_pq[2 * slot + 1] = q;
-            }
-        }
+        wave_append(acc, &a.count[0], lane, [&](unsigned long long slot) {
+            if (slot >= (unsigned long long)a.max_cands) return;        // beyond the list: counted, not written (then nothing is deposited)
+            const double k2 = (2.0 * h2) / nn;
+            double* const o = a.cand_s + 3 * slot;
+            o[0] = sx - nx * k2;
+            o[1] = sy - ny * k2;
+            o[2] = sz - nz * k2;
+            a.cand_pq[2 * slot] = p;
+            a.cand_pq[2 * slot + 1] = q;
+        });
     }
 }
 
@@ -189,9 +170,8 @@ extern "C" __global__ __launch_bounds__(256) void hare_image2_paths(Image2Args a
     const int lane = threadIdx.x & 63;
     const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int k0 = (int)blockIdx.y * kImage2Tile;
-    const int nk = a.n_rcv - k0 < kImage2Tile ? a.n_rcv - k0 : kImage2Tile;
-    for (int j = threadIdx.x; j < nk * 4; j += blockDim.x) rcv[j] = a.rcv[4 * (size_t)k0 + (size_t)j];
-    __syncthreads();
+    const int nk = a.d.n_rcv - k0 < kImage2Tile ? a.d.n_rcv - k0 : kImage2Tile;
+    stage_receivers(rcv, a.d.rcv, k0, nk);
     const bool on = i < found;
     if (__ballot(on) == 0ull) return;
     const unsigned long long ci = on ? i : 0ull;
@@ -199,10 +179,10 @@ extern "C" __global__ __launch_bounds__(256) void hare_image2_paths(Image2Args a
     const double sx = a.cand_s[3 * ci], sy = a.cand_s[3 * ci + 1], sz = a.cand_s[3 * ci + 2];     // S''
     const double* const im = a.img + 4 * (size_t)p;
     const V3 o1 = {im[0], im[1], im[2]};                                                            // S' of p
-    CullRaw cr = cull_load(a, q);
-    CullRay ray = cull_ray(a, sx, sy, sz, 0.0, 0.0, 0.0);               // the origin part: S'' for every receiver
-    const double* const v3q = (a.quads && a.quads[q].nverts == 4) ? a.quads[q].v3 : nullptr;
-    const double* const v3p = (a.quads && a.quads[p].nverts == 4) ? a.quads[p].v3 : nullptr;
+    CullRaw cr = cull_load(a.sc, q);
+    CullRay ray = cull_ray(a.sc, sx, sy, sz, 0.0, 0.0, 0.0);            // the origin part: S'' for every receiver
+    const double* const v3q = quad_v3(a.sc.quads, q);
+    const double* const v3p = quad_v3(a.sc.quads, p);
     const V3 o2 = {sx, sy, sz};
     for (int j = 0; j < nk; ++j) {
         const double cx = rcv[4 * j + 0], cy = rcv[4 * j + 1], cz = rcv[4 * j + 2], rr = rcv[4 * j + 3];
@@ -210,65 +190,57 @@ extern "C" __global__ __launch_bounds__(256) void hare_image2_paths(Image2Args a
         double t1 = 0, t2 = 0, vx = 0, vy = 0, vz = 0;
         V3 x2 = {0, 0, 0}, w = {0, 0, 0};
         if (on) {
-            const double d2 = image_vector(cx, cy, cz, sx, sy, sz, vx, vy, vz);
+            const double d2 = path_vector(cx, cy, cz, sx, sy, sz, vx, vy, vz);
             if (d2 > rr) {
                 ray.dfx = (float)vx;
                 ray.dfy = (float)vy;
                 ray.dfz = (float)vz;
                 ray.dm = fabsf(ray.dfx) + fabsf(ray.dfy) + fabsf(ray.dfz);
-                if (!cull_test(a, ray, cr)) {
+                if (!cull_test(a.sc, ray, cr)) {
                     const V3 d = {vx, vy, vz};
-                    if (poly_fast(a.polys[q], v3q, o2, d, t2) && t2 > 0.0 && t2 < 1.0) {
+                    if (poly_fast(a.sc.polys[q], v3q, o2, d, t2) && t2 > 0.0 && t2 < 1.0) {
                         x2.x = sx + vx * t2;
                         x2.y = sy + vy * t2;
                         x2.z = sz + vz * t2;
                         w.x = x2.x - o1.x;
                         w.y = x2.y - o1.y;
                         w.z = x2.z - o1.z;
-                        acc = poly_fast(a.polys[p], v3p, o1, w, t1) && t1 > 0.0 && t1 < 1.0;
+                        acc = poly_fast(a.sc.polys[p], v3p, o1, w, t1) && t1 > 0.0 && t1 < 1.0;
                     }
                 }
             }
         }
-        const unsigned long long m = __ballot(acc);
-        if (m == 0ull) continue;                                        // the common case: no lane's candidate reflects to receiver j
-        const int leader = __ffsll((long long)m) - 1;
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(&a.count[1], (unsigned long long)__popcll(m));
-        base = __shfl(base, leader, 64);
-        if (acc) {
-            const unsigned long long slot = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-            if (slot < (unsigned long long)a.max_paths) {              // beyond the list: counted, not written
-                RayRec s;
-                s.x = x2.x;                                             // x2 -> center, leaving q
-                s.y = x2.y;
-                s.z = x2.z;
-                s.dx = cx - x2.x;
-                s.dy = cy - x2.y;
-                s.dz = cz - x2.z;
-                a.srays[3 * slot] = s;
-                s.x = o1.x + w.x * t1;                                  // x1 -> x2, leaving p, arriving on q
-                s.y = o1.y + w.y * t1;
-                s.z = o1.z + w.z * t1;
-                s.dx = x2.x - s.x;
-                s.dy = x2.y - s.y;
-                s.dz = x2.z - s.z;
-                a.srays[3 * slot + 1] = s;
-                s.dx = a.pos[0] - s.x;                                  // x1 -> source, leaving p
-                s.dy = a.pos[1] - s.y;
-                s.dz = a.pos[2] - s.z;
-                a.srays[3 * slot + 2] = s;
-                a.stmax[3 * slot] = 1.0;
-                a.stmax[3 * slot + 1] = 1.0;
-                a.stmax[3 * slot + 2] = 1.0;
-                a.sexcl[3 * slot] = q;
-                a.sexcl[3 * slot + 1] = p;
-                a.sexcl[3 * slot + 2] = p;
-                a.sexcl2[3 * slot + 1] = q;
-                a.path_kc[2 * slot] = k0 + j;
-                a.path_kc[2 * slot + 1] = (int)i;
-            }
-        }
+        wave_append(acc, &a.count[1], lane, [&](unsigned long long slot) {
+            if (slot >= (unsigned long long)a.max_paths) return;        // beyond the list: counted, not written
+            RayRec s;
+            s.x = x2.x;                                             // x2 -> center, leaving q
+            s.y = x2.y;
+            s.z = x2.z;
+            s.dx = cx - x2.x;
+            s.dy = cy - x2.y;
+            s.dz = cz - x2.z;
+            a.d.srays[3 * slot] = s;
+            s.x = o1.x + w.x * t1;                                  // x1 -> x2, leaving p, arriving on q
+            s.y = o1.y + w.y * t1;
+            s.z = o1.z + w.z * t1;
+            s.dx = x2.x - s.x;
+            s.dy = x2.y - s.y;
+            s.dz = x2.z - s.z;
+            a.d.srays[3 * slot + 1] = s;
+            s.dx = a.d.pos[0] - s.x;                                  // x1 -> source, leaving p
+            s.dy = a.d.pos[1] - s.y;
+            s.dz = a.d.pos[2] - s.z;
+            a.d.srays[3 * slot + 2] = s;
+            a.d.stmax[3 * slot] = 1.0;
+            a.d.stmax[3 * slot + 1] = 1.0;
+            a.d.stmax[3 * slot + 2] = 1.0;
+            a.d.sexcl[3 * slot] = q;
+            a.d.sexcl[3 * slot + 1] = p;
+            a.d.sexcl[3 * slot + 2] = p;
+            a.sexcl2[3 * slot + 1] = q;
+            a.path_kc[2 * slot] = k0 + j;
+            a.path_kc[2 * slot + 1] = (int)i;
+        });
     }
 }
 
@@ -280,53 +252,19 @@ static __device__ __forceinline__ void image2_deposit_body(const Image2Args& a)
     if (a.count[0] > (unsigned long long)a.max_cands || found > (unsigned long long)a.max_paths) return;      // a list overflowed: nothing at all is added
     const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= found) return;
-    if (a.socc[3 * i] != 0 || a.socc[3 * i + 1] != 0 || a.socc[3 * i + 2] != 0) return;      // a leg is occluded
+    if (a.d.socc[3 * i] != 0 || a.d.socc[3 * i + 1] != 0 || a.d.socc[3 * i + 2] != 0) return;      // a leg is occluded
     const int k = a.path_kc[2 * i];
     const size_t ci = (size_t)a.path_kc[2 * i + 1];
     const int p = a.cand_pq[2 * ci], q = a.cand_pq[2 * ci + 1];
-    const int B = a.bands;
-    const double* const rc = a.rcv + 4 * (size_t)k;
-    const double rr = rc[3];
-    double vx, vy, vz;
-    const double d2 = image_vector(rc[0], rc[1], rc[2], a.cand_s[3 * ci], a.cand_s[3 * ci + 1], a.cand_s[3 * ci + 2], vx, vy, vz);
-    const double dist = sqrt(d2);
-    const double y = rr / d2;
-    const double f = (0.5 * y) / (1.0 + sqrt(1.0 - y));
-    const double fw = f * a.weight;
-    const double xb = dist / a.bin_len;
-    const bool binned = xb >= 0 && xb < (double)a.n_bins;
-    atomicAdd(&a.det[2 * (size_t)k + (binned ? 0 : 1)], 1ull);
-    if (!binned) return;
-    const int bin = (int)floor(xb);
-    const RayRec& s = a.srays[3 * i + 1];                               // its origin: the first reflection point x1
-    const double* const g = a.res > 0 ? source_gains(a.gain, a.frame, a.res, B, s.x - a.pos[0], s.y - a.pos[1], s.z - a.pos[2]) : nullptr;
-    const double* const alp = a.alpha ? a.alpha + (size_t)p * (size_t)B : nullptr;
-    const double* const sgp = a.sigma ? a.sigma + (size_t)p * (size_t)B : nullptr;
-    const double* const alq = a.alpha ? a.alpha + (size_t)q * (size_t)B : nullptr;
-    const double* const sgq = a.sigma ? a.sigma + (size_t)q * (size_t)B : nullptr;
-    unsigned long long* const w = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B * (DIR ? 4 : 1);
-    [[maybe_unused]] double ax = 0, ay = 0, az = 0;
-    if constexpr (DIR) {
-        ax = -(vx / dist);
-        ay = -(vy / dist);
-        az = -(vz / dist);
-    }
-#pragma unroll
-    for (int b = 0; b < kMaxBands; ++b) {
-        if (b < B) {
-            const double rp = (1.0 - (alp ? alp[b] : 0.0)) * (1.0 - (sgp ? sgp[b] : 0.0));
-            const double rq = (1.0 - (alq ? alq[b] : 0.0)) * (1.0 - (sgq ? sgq[b] : 0.0));
-            const double m = quant_m((((a.power[b] * (g ? g[b] : 1.0)) * (rp * rq)) * fw) * a.scale);
-            if constexpr (DIR) {
-                atomicAdd(&w[4 * b + 0], (unsigned long long)rint(m));
-                atomicAdd(&w[4 * b + 1], dir_q(m, ax));
-                atomicAdd(&w[4 * b + 2], dir_q(m, ay));
-                atomicAdd(&w[4 * b + 3], dir_q(m, az));
-            } else {
-                atomicAdd(&w[b], (unsigned long long)rint(m));
-            }
-        }
-    }
+    deposit_tail<DIR>(
+        a.d, k, a.cand_s[3 * ci], a.cand_s[3 * ci + 1], a.cand_s[3 * ci + 2],
+        [&](double& gx, double& gy, double& gz) {                       // source -> x1, the first reflection point: the origin of the middle leg
+            const RayRec& s = a.d.srays[3 * i + 1];
+            gx = s.x - a.d.pos[0];
+            gy = s.y - a.d.pos[1];
+            gz = s.z - a.d.pos[2];
+        },
+        [&](int b) { return poly_reflectance(a.sc, a.d.bands, p, b) * poly_reflectance(a.sc, a.d.bands, q, b); });
 }
 
 extern "C" __global__ __launch_bounds__(256) void hare_image2_deposit(Image2Args a)

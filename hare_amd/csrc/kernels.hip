@@ -1957,6 +1957,7 @@ __global__ __launch_bounds__(256) void hare_occlusion(const XEventRec* ev, const
 
 #include "receive.hip"         // hare_receive_reflect / _scatter: the receiver step of hare_receive_device's loop
 #include "source.hip"          // hare_emit_source: the point source's rays and starting state (hare_emit_device, hare_receive_source)
+#include "deposit.hip"         // path_vector, deposit_tail: what the three deterministic source paths below share; no kernel
 #include "direct.hip"          // hare_direct_emit / hare_direct_deposit[_dir]: the direct sound, a lane per receiver (hare_direct_device, HARE_RECEIVE_DIRECT)
 #include "image.hip"           // hare_image_mirror / _pairs / _deposit[_dir]: first-order image sources (hare_image_device, HARE_RECEIVE_IMAGE)
 #include "image2.hip"          // hare_image2_mirror / _cands / _paths / _deposit[_dir]: second-order image sources (hare_image2_device, HARE_RECEIVE_IMAGE2)

@@ -2,8 +2,10 @@
 // and its per-cast step (receive_plan, receive_step: what bounce_device_impl, launch.cpp, runs between its casts) and hare_receive_device
 // (include/hare_hip.h, "receivers"; the kernels: receive.hip); the point source (hare_scene_set_source, hare_emit_device; the kernel:
 // source.hip); the direct sound (direct_enqueue, hare_direct_device; the kernels: direct.hip); first-order image sources (image_enqueue,
-// hare_image_device; the kernels: image.hip) and second-order ones (image2_enqueue, hare_image2_device; the kernels: image2.hip).  The host-buffer calls hare_receive_batch / _sharded and hare_receive_source / _sharded are in bounce.cpp, beside the loop
-// they share with hare_bounce_batch.
+// hare_image_device; the kernels: image.hip) and second-order ones (image2_enqueue, hare_image2_device; the kernels: image2.hip).  The three
+// plans fill what their kernels share through deposit_fill and image_scene_fill, and the three calls check and prepare through
+// deposit_call_check, deposit_buffers_check and deposit_call_run.  The host-buffer calls hare_receive_batch / _sharded and
+// hare_receive_source / _sharded are in bounce.cpp, beside the loop they share with hare_bounce_batch.
 //
 // Harness-defined: the reference has no receivers (Pachyderm, its caller, detects them on the host per ray).
 // Product code; nothing from oracle/.
@@ -345,23 +347,53 @@ int emit_source(const Scene& s, const HipApi* H, int64_t n, int64_t first_ray, v
     return launch(H, s.module->emit_source, (unsigned)((n + 255) / 256), 256, 0, st, args);
 }
 
-// ---- the direct sound (include/hare_hip.h, "receivers", "Direct sound"; the kernels: direct.hip)
-// What hare_direct_device and the flag on the source calls check of their numbers (HARE_E_INVALID)
-static int direct_check_weight(const char* who, int64_t n_weight)
+// ---- the deterministic source paths: what their three plans share
+// The fields every deposit reads (DepositArgs), but for the four shadow-ray arrays, which each plan carves from its own scratch.  False:
+// receivers or directivity table not on the device
+static bool deposit_fill(DepositArgs& d, const Scene& s, int64_t n_weight, int32_t n_bins, double bin_len, int32_t frac_bits, void* d_hist, void* d_det)
 {
-    if (n_weight < 1 || n_weight > ((int64_t)1 << 53)) {
-        set_error(std::string(who) + ": n_weight out of range (1 .. 2^53)");
-        return HARE_E_INVALID;
+    const Scene::Source& src = s.src;
+    d.rcv = (const double*)(s.rmap.set ? s.rmap.d_rcv : s.d_rcv);
+    d.gain = src.R > 0 ? (const double*)src.d_gain : nullptr;
+    d.hist = (unsigned long long*)d_hist;
+    d.det = (unsigned long long*)d_det;
+    memcpy(d.pos, src.pos, sizeof d.pos);
+    memcpy(d.power, src.power, sizeof d.power);
+    memcpy(d.frame, src.frame, sizeof d.frame);
+    d.bin_len = bin_len;
+    d.scale = ldexp(1.0, frac_bits);
+    d.weight = (double)n_weight;
+    d.n_rcv = (int32_t)(s.rcv.size() / 4);
+    d.bands = src.B;
+    d.res = src.R;
+    d.n_bins = n_bins;
+    return d.rcv && (src.R == 0 || d.gain);
+}
+
+// The topology as the image-source kernels read it (ImageScene), and the image sources' one "not on the device" for it and for what
+// deposit_fill found
+static int image_scene_fill(ImageScene& sc, const Scene& s, int32_t top, bool deposit_on_device)
+{
+    sc.polys = (const PolyRec*)s.d_polys[(size_t)top];
+    sc.quads = (const QuadRec*)s.d_quads[(size_t)top];
+    sc.cull = (const unsigned char*)s.d_cull[(size_t)top];
+    sc.alpha = has_table(s.alpha, top) ? (const double*)s.alpha[(size_t)top].dev : nullptr;
+    sc.sigma = has_table(s.sigma, top) ? (const double*)s.sigma[(size_t)top].dev : nullptr;
+    sc.cf = s.cull_frames[(size_t)top];
+    sc.n_poly = (int32_t)s.topos[(size_t)top].P;
+    if (!deposit_on_device || !sc.polys || !sc.cull || (has_table(s.alpha, top) && !sc.alpha) || (has_table(s.sigma, top) && !sc.sigma)) {
+        set_error("image sources: polygons, receivers or tables not on the device");
+        return HARE_E_STATE;
     }
     return HARE_OK;
 }
 
+// ---- the direct sound (include/hare_hip.h, "receivers", "Direct sound"; the kernels: direct.hip)
 // The scratch of a deposit: K shadow rays (48 B) from a 16-byte boundary, K t_max, K exclusion words, K occlusion flags: 64 K bytes and at
 // most 15 of padding, within HARE_DIRECT_WORK_BYTES(K)
 int direct_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                    int32_t frac_bits, void* d_work, void* d_hist, void* d_det, hipStream_t st)
 {
-    const Scene::Source& src = s.src;
     const bool dir = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
     if (!s.module || !s.module->direct_emit || !s.module->direct_deposit[dir]) {
         set_error("hare_direct_emit / hare_direct_deposit missing from code object");
@@ -370,33 +402,20 @@ int direct_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t
     const int64_t K = (int64_t)(s.rcv.size() / 4);
     DirectArgs a;
     memset(&a, 0, sizeof a);
-    a.rcv = (const double*)(s.rmap.set ? s.rmap.d_rcv : s.d_rcv);
-    a.gain = src.R > 0 ? (const double*)src.d_gain : nullptr;
-    a.hist = (unsigned long long*)d_hist;
-    a.det = (unsigned long long*)d_det;
-    a.srays = (RayRec*)(((uintptr_t)d_work + 15u) & ~(uintptr_t)15u);
-    a.stmax = (double*)(a.srays + K);
-    a.sexcl = (int32_t*)(a.stmax + K);
-    int32_t* const occ = a.sexcl + K;
-    a.socc = occ;
-    memcpy(a.pos, src.pos, sizeof a.pos);
-    memcpy(a.power, src.power, sizeof a.power);
-    memcpy(a.frame, src.frame, sizeof a.frame);
-    a.bin_len = bin_len;
-    a.scale = ldexp(1.0, frac_bits);
-    a.weight = (double)n_weight;
-    a.n_rcv = (int32_t)K;
-    a.bands = src.B;
-    a.res = src.R;
-    a.n_bins = n_bins;
-    if (!a.rcv || (src.R > 0 && !a.gain)) {
+    DepositArgs& d = a.d;
+    d.srays = (RayRec*)(((uintptr_t)d_work + 15u) & ~(uintptr_t)15u);
+    d.stmax = (double*)(d.srays + K);
+    d.sexcl = (int32_t*)(d.stmax + K);
+    int32_t* const occ = d.sexcl + K;
+    d.socc = occ;
+    if (!deposit_fill(d, s, n_weight, n_bins, bin_len, frac_bits, d_hist, d_det)) {
         set_error("direct sound: receivers or directivity table not on the device");
         return HARE_E_STATE;
     }
     const unsigned grid = (unsigned)((K + 255) / 256);
     void* args[] = {&a};
     if (int rc = launch(H, s.module->direct_emit, grid, 256, 0, st, args)) return rc;
-    if (int rc = shoot_device_impl(s, H, kind, top, K, a.srays, a.sexcl, nullptr, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st, a.stmax, occ)) return rc;
+    if (int rc = shoot_device_impl(s, H, kind, top, K, d.srays, d.sexcl, nullptr, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st, d.stmax, occ)) return rc;
     return launch(H, s.module->direct_deposit[dir], grid, 256, 0, st, args);
 }
 
@@ -407,7 +426,6 @@ int direct_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t
 int image_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                   int32_t frac_bits, int64_t max_pairs, void* d_work, void* d_hist, void* d_det, hipStream_t st)
 {
-    const Scene::Source& src = s.src;
     const bool dir = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
     if (!s.module || !s.module->image_mirror || !s.module->image_pairs || !s.module->image_deposit[dir]) {
         set_error("hare_image_mirror / hare_image_pairs / hare_image_deposit missing from code object");
@@ -416,42 +434,19 @@ int image_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t 
     const int64_t K = (int64_t)(s.rcv.size() / 4), P = s.topos[(size_t)top].P, M = max_pairs;
     ImageArgs a;
     memset((void*)&a, 0, sizeof a);
-    a.polys = (const PolyRec*)s.d_polys[(size_t)top];
-    a.quads = (const QuadRec*)s.d_quads[(size_t)top];
-    a.cull = (const unsigned char*)s.d_cull[(size_t)top];
-    a.cf = s.cull_frames[(size_t)top];
-    a.rcv = (const double*)(s.rmap.set ? s.rmap.d_rcv : s.d_rcv);
-    a.alpha = has_table(s.alpha, top) ? (const double*)s.alpha[(size_t)top].dev : nullptr;
-    a.sigma = has_table(s.sigma, top) ? (const double*)s.sigma[(size_t)top].dev : nullptr;
-    a.gain = src.R > 0 ? (const double*)src.d_gain : nullptr;
-    a.hist = (unsigned long long*)d_hist;
-    a.det = (unsigned long long*)d_det;
+    DepositArgs& d = a.d;
     char* const w = (char*)d_work;
     a.count = (unsigned long long*)w;
     a.img = (double*)(w + 256);
-    a.srays = (RayRec*)(a.img + 4 * P);
-    a.stmax = (double*)(a.srays + 2 * M);
-    a.pair_kp = (int32_t*)(a.stmax + 2 * M);
-    a.sexcl = a.pair_kp + 2 * M;
-    int32_t* const occ = a.sexcl + 2 * M;
-    a.socc = occ;
-    memcpy(a.pos, src.pos, sizeof a.pos);
-    memcpy(a.power, src.power, sizeof a.power);
-    memcpy(a.frame, src.frame, sizeof a.frame);
-    a.bin_len = bin_len;
-    a.scale = ldexp(1.0, frac_bits);
-    a.weight = (double)n_weight;
+    d.srays = (RayRec*)(a.img + 4 * P);
+    d.stmax = (double*)(d.srays + 2 * M);
+    a.pair_kp = (int32_t*)(d.stmax + 2 * M);
+    d.sexcl = a.pair_kp + 2 * M;
+    int32_t* const occ = d.sexcl + 2 * M;
+    d.socc = occ;
     a.max_pairs = M;
-    a.n_rcv = (int32_t)K;
-    a.n_poly = (int32_t)P;
-    a.bands = src.B;
-    a.res = src.R;
-    a.n_bins = n_bins;
     a.use_cull = s.opt.image_cull;
-    if (!a.polys || !a.cull || !a.rcv || (src.R > 0 && !a.gain) || (has_table(s.alpha, top) && !a.alpha) || (has_table(s.sigma, top) && !a.sigma)) {
-        set_error("image sources: polygons, receivers or tables not on the device");
-        return HARE_E_STATE;
-    }
+    if (int rc = image_scene_fill(a.sc, s, top, deposit_fill(d, s, n_weight, n_bins, bin_len, frac_bits, d_hist, d_det))) return rc;
     if (P == 0) return HARE_OK;     // no polygon, no image (a topology is never empty today: hare_scene_create refuses P < 1)
     void* args[] = {&a};
     const int64_t fill = std::max<int64_t>(P, 2 * M);
@@ -461,7 +456,7 @@ int image_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t 
         const unsigned gx = (unsigned)((P + 255) / 256), gy = (unsigned)((K + 255) / 256);
         HIP_TRY(H->ModuleLaunchKernel(s.module->image_pairs, gx, gy, 1, 256, 1, 1, 0, st, args, nullptr));
     }
-    if (int rc = shoot_device_impl(s, H, kind, top, 2 * M, a.srays, a.sexcl, nullptr, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st, a.stmax, occ)) return rc;
+    if (int rc = shoot_device_impl(s, H, kind, top, 2 * M, d.srays, d.sexcl, nullptr, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st, d.stmax, occ)) return rc;
     return launch(H, s.module->image_deposit[dir], (unsigned)((M + 255) / 256), 256, 0, st, args);
 }
 
@@ -473,7 +468,6 @@ int image_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t 
 int image2_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                    int32_t frac_bits, int64_t max_cands, int64_t max_paths, void* d_work, void* d_hist, void* d_det, hipStream_t st)
 {
-    const Scene::Source& src = s.src;
     const bool dir = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
     const DeviceModule* const m = s.module;
     if (!m || !m->image2_mirror || !m->image2_cands || !m->image2_paths || !m->image2_deposit[dir]) {
@@ -483,46 +477,23 @@ int image2_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t
     const int64_t K = (int64_t)(s.rcv.size() / 4), P = s.topos[(size_t)top].P, C = max_cands, M = max_paths;
     Image2Args a;
     memset((void*)&a, 0, sizeof a);
-    a.polys = (const PolyRec*)s.d_polys[(size_t)top];
-    a.quads = (const QuadRec*)s.d_quads[(size_t)top];
-    a.cull = (const unsigned char*)s.d_cull[(size_t)top];
-    a.cf = s.cull_frames[(size_t)top];
-    a.rcv = (const double*)(s.rmap.set ? s.rmap.d_rcv : s.d_rcv);
-    a.alpha = has_table(s.alpha, top) ? (const double*)s.alpha[(size_t)top].dev : nullptr;
-    a.sigma = has_table(s.sigma, top) ? (const double*)s.sigma[(size_t)top].dev : nullptr;
-    a.gain = src.R > 0 ? (const double*)src.d_gain : nullptr;
-    a.hist = (unsigned long long*)d_hist;
-    a.det = (unsigned long long*)d_det;
+    DepositArgs& d = a.d;
     char* const w = (char*)d_work;
     a.count = (unsigned long long*)w;
     a.img = (double*)(w + 256);
     a.cand_s = a.img + 4 * P;
     a.cand_pq = (int32_t*)(a.cand_s + 3 * C);
-    a.srays = (RayRec*)(a.cand_pq + 2 * C);
-    a.stmax = (double*)(a.srays + 3 * M);
-    a.path_kc = (int32_t*)(a.stmax + 3 * M);
-    a.sexcl = a.path_kc + 2 * M;
-    a.sexcl2 = a.sexcl + 3 * M;
+    d.srays = (RayRec*)(a.cand_pq + 2 * C);
+    d.stmax = (double*)(d.srays + 3 * M);
+    a.path_kc = (int32_t*)(d.stmax + 3 * M);
+    d.sexcl = a.path_kc + 2 * M;
+    a.sexcl2 = d.sexcl + 3 * M;
     int32_t* const occ = a.sexcl2 + 3 * M;
-    a.socc = occ;
-    memcpy(a.pos, src.pos, sizeof a.pos);
-    memcpy(a.power, src.power, sizeof a.power);
-    memcpy(a.frame, src.frame, sizeof a.frame);
-    a.bin_len = bin_len;
-    a.scale = ldexp(1.0, frac_bits);
-    a.weight = (double)n_weight;
+    d.socc = occ;
     a.max_cands = C;
     a.max_paths = M;
-    a.n_rcv = (int32_t)K;
-    a.n_poly = (int32_t)P;
-    a.bands = src.B;
-    a.res = src.R;
-    a.n_bins = n_bins;
     a.prune = s.opt.image2_prune;
-    if (!a.polys || !a.cull || !a.rcv || (src.R > 0 && !a.gain) || (has_table(s.alpha, top) && !a.alpha) || (has_table(s.sigma, top) && !a.sigma)) {
-        set_error("image sources: polygons, receivers or tables not on the device");
-        return HARE_E_STATE;
-    }
+    if (int rc = image_scene_fill(a.sc, s, top, deposit_fill(d, s, n_weight, n_bins, bin_len, frac_bits, d_hist, d_det))) return rc;
     if (P == 0) return HARE_OK;
     void* args[] = {&a};
     const int64_t fill = std::max<int64_t>(P, 3 * M);
@@ -538,7 +509,7 @@ int image2_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t
         HIP_TRY(H->ModuleLaunchKernel(m->image2_cands, gp, gp, 1, 256, 1, 1, 0, st, args, nullptr));
         HIP_TRY(H->ModuleLaunchKernel(m->image2_paths, (unsigned)((C + 255) / 256), (unsigned)((K + 255) / 256), 1, 256, 1, 1, 0, st, args, nullptr));
     }
-    if (int rc = shoot_device_impl(s, H, kind, top, 3 * M, a.srays, a.sexcl, a.sexcl2, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st, a.stmax, occ)) return rc;
+    if (int rc = shoot_device_impl(s, H, kind, top, 3 * M, d.srays, d.sexcl, a.sexcl2, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st, d.stmax, occ)) return rc;
     return launch(H, m->image2_deposit[dir], (unsigned)((M + 255) / 256), 256, 0, st, args);
 }
 
@@ -754,6 +725,69 @@ using namespace hare;
         return HARE_E_INVALID;                                  \
     }
 
+// ---- what hare_direct_device, hare_image_device and hare_image2_device share (the calls themselves are below).  Their checks fire in
+// this order: deposit_call_check, the call's own list lengths, deposit_buffers_check -- all HARE_E_INVALID, ahead of the device.
+// The scene, the weight and the numbers; flags comes back masked to what these calls read
+static int deposit_call_check(const char* who, const hare_scene* s, int32_t kind, int32_t top, int64_t n_weight, uint32_t& flags, int32_t n_bins,
+                              double bin_len, int32_t frac_bits)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    if (n_weight < 1 || n_weight > ((int64_t)1 << 53)) {
+        set_error(std::string(who) + ": n_weight out of range (1 .. 2^53)");
+        return HARE_E_INVALID;
+    }
+    flags &= HARE_RECEIVE_DIRECTIONAL;
+    if (int rc = receive_check_args(who, *s, flags, kind, top, 0, 1, n_bins, bin_len, frac_bits)) return rc;
+    if (s->src.set && s->src.B != scene_bands(*s, top)) {
+        set_error(std::string(who) + ": the source has " + std::to_string(s->src.B) + " bands, the topology " + std::to_string(scene_bands(*s, top)));
+        return HARE_E_INVALID;
+    }
+    return HARE_OK;
+}
+
+// The three buffers: none null, the work array on a 16-byte boundary where the call does not align it itself, no two overlapping
+static int deposit_buffers_check(const char* who, const Scene& s, int32_t top, uint32_t flags, int32_t n_bins, const void* d_work, size_t work_bytes,
+                                 bool need_aligned, const void* d_hist, const void* d_det)
+{
+    if (!d_work || !d_hist || !d_det || (need_aligned && ((uintptr_t)d_work & 15u))) {
+        set_error(std::string(who) + ": null work array / histogram / detections" + (need_aligned ? ", or a work array off a 16-byte boundary" : ""));
+        return HARE_E_INVALID;
+    }
+    const size_t K = std::max<size_t>(1, s.rcv.size() / 4);
+    const struct { const void* p; size_t bytes; } bufs[] = {{d_work, work_bytes},
+                                                            {d_hist, receive_hist_words(s, top, n_bins, flags, 1) * sizeof(uint64_t)},
+                                                            {d_det, K * 2 * sizeof(uint64_t)}};
+    for (size_t x = 0; x < 3; ++x)
+        for (size_t y = x + 1; y < 3; ++y)
+            if (ranges_overlap(bufs[x].p, bufs[x].bytes, bufs[y].p, bufs[y].bytes)) {
+                set_error(std::string(who) + ": work array, histogram and detections must not overlap");
+                return HARE_E_INVALID;
+            }
+    return HARE_OK;
+}
+
+// The device, the module, the source, the polygons and the receivers, then the call's own enqueue under the scene's device
+template <class Enqueue>
+static int deposit_call_run(Scene& s, const char* who, Enqueue enqueue)
+{
+    GUARD_BEGIN
+    const HipApi* H = api_or_err();
+    if (!H) return HARE_E_NODEVICE;
+    DeviceGuard dev_guard(H, s.device);
+    if (!s.module) {
+        int rc = ensure_device(s, H);
+        if (rc) return rc;
+    }
+    if (int rc = source_ready(s, H, who)) return rc;
+    if (int rc = upload_polys(s, H)) return rc;
+    if (int rc = receive_ready(s, H, who)) return rc;
+    return enqueue(H);
+    GUARD_END
+}
+
 extern "C" {
 
 int hare_scene_set_receivers(hare_scene* s, int32_t K, const double* centers, const double* radii)
@@ -951,143 +985,48 @@ int hare_emit_device(hare_scene* s, int64_t n, int64_t first_ray, void* d_rays, 
 int hare_direct_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                        int32_t frac_bits, void* d_work, void* d_hist, void* d_detections, void* stream)
 {
-    if (!s) {
-        set_error("null scene");
-        return HARE_E_INVALID;
-    }
     const char* const who = "hare_direct_device";
-    if (int rc = direct_check_weight(who, n_weight)) return rc;
-    flags &= HARE_RECEIVE_DIRECTIONAL;
-    if (int rc = receive_check_args(who, *s, flags, kind, top_index, 0, 1, n_bins, bin_len, frac_bits)) return rc;
-    if (s->src.set && s->src.B != scene_bands(*s, top_index)) {
-        set_error(std::string(who) + ": the source has " + std::to_string(s->src.B) + " bands, the topology " + std::to_string(scene_bands(*s, top_index)));
-        return HARE_E_INVALID;
-    }
-    if (!d_work || !d_hist || !d_detections) {
-        set_error(std::string(who) + ": null work array / histogram / detections");
-        return HARE_E_INVALID;
-    }
+    if (int rc = deposit_call_check(who, s, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits)) return rc;
     const size_t K = std::max<size_t>(1, s->rcv.size() / 4);
-    const struct { const void* p; size_t bytes; } bufs[] = {{d_work, (size_t)HARE_DIRECT_WORK_BYTES(K)},
-                                                            {d_hist, receive_hist_words(*s, top_index, n_bins, flags, 1) * sizeof(uint64_t)},
-                                                            {d_detections, K * 2 * sizeof(uint64_t)}};
-    for (size_t x = 0; x < 3; ++x)
-        for (size_t y = x + 1; y < 3; ++y)
-            if (ranges_overlap(bufs[x].p, bufs[x].bytes, bufs[y].p, bufs[y].bytes)) {
-                set_error(std::string(who) + ": work array, histogram and detections must not overlap");
-                return HARE_E_INVALID;
-            }
-    GUARD_BEGIN
-    const HipApi* H = api_or_err();
-    if (!H) return HARE_E_NODEVICE;
-    DeviceGuard dev_guard(H, s->device);
-    if (!s->module) {
-        int rc = ensure_device(*s, H);
-        if (rc) return rc;
-    }
-    if (int rc = source_ready(*s, H, who)) return rc;
-    if (int rc = upload_polys(*s, H)) return rc;
-    if (int rc = receive_ready(*s, H, who)) return rc;
-    return direct_enqueue(*s, H, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, d_work, d_hist, d_detections, (hipStream_t)stream);
-    GUARD_END
+    if (int rc = deposit_buffers_check(who, *s, top_index, flags, n_bins, d_work, (size_t)HARE_DIRECT_WORK_BYTES(K), false, d_hist, d_detections)) return rc;
+    return deposit_call_run(*s, who, [&](const HipApi* H) {
+        return direct_enqueue(*s, H, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, d_work, d_hist, d_detections, (hipStream_t)stream);
+    });
 }
 
 int hare_image_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                       int32_t frac_bits, int64_t max_pairs, void* d_work, void* d_hist, void* d_detections, void* stream)
 {
-    if (!s) {
-        set_error("null scene");
-        return HARE_E_INVALID;
-    }
     const char* const who = "hare_image_device";
-    if (int rc = direct_check_weight(who, n_weight)) return rc;
-    flags &= HARE_RECEIVE_DIRECTIONAL;
-    if (int rc = receive_check_args(who, *s, flags, kind, top_index, 0, 1, n_bins, bin_len, frac_bits)) return rc;
-    if (s->src.set && s->src.B != scene_bands(*s, top_index)) {
-        set_error(std::string(who) + ": the source has " + std::to_string(s->src.B) + " bands, the topology " + std::to_string(scene_bands(*s, top_index)));
-        return HARE_E_INVALID;
-    }
+    if (int rc = deposit_call_check(who, s, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits)) return rc;
     if (max_pairs < 1 || max_pairs > ((int64_t)1 << 26)) {
         set_error(std::string(who) + ": max_pairs out of range (1 .. 2^26)");
         return HARE_E_INVALID;
     }
-    if (!d_work || !d_hist || !d_detections || ((uintptr_t)d_work & 15u)) {
-        set_error(std::string(who) + ": null work array / histogram / detections, or a work array off a 16-byte boundary");
-        return HARE_E_INVALID;
-    }
     const size_t K = std::max<size_t>(1, s->rcv.size() / 4);
-    const struct { const void* p; size_t bytes; } bufs[] = {{d_work, (size_t)HARE_IMAGE_WORK_BYTES(K, s->topos[(size_t)top_index].P, max_pairs)},
-                                                            {d_hist, receive_hist_words(*s, top_index, n_bins, flags, 1) * sizeof(uint64_t)},
-                                                            {d_detections, K * 2 * sizeof(uint64_t)}};
-    for (size_t x = 0; x < 3; ++x)
-        for (size_t y = x + 1; y < 3; ++y)
-            if (ranges_overlap(bufs[x].p, bufs[x].bytes, bufs[y].p, bufs[y].bytes)) {
-                set_error(std::string(who) + ": work array, histogram and detections must not overlap");
-                return HARE_E_INVALID;
-            }
-    GUARD_BEGIN
-    const HipApi* H = api_or_err();
-    if (!H) return HARE_E_NODEVICE;
-    DeviceGuard dev_guard(H, s->device);
-    if (!s->module) {
-        int rc = ensure_device(*s, H);
-        if (rc) return rc;
-    }
-    if (int rc = source_ready(*s, H, who)) return rc;
-    if (int rc = upload_polys(*s, H)) return rc;
-    if (int rc = receive_ready(*s, H, who)) return rc;
-    return image_enqueue(*s, H, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, max_pairs, d_work, d_hist, d_detections,
-                         (hipStream_t)stream);
-    GUARD_END
+    const size_t work_bytes = (size_t)HARE_IMAGE_WORK_BYTES(K, s->topos[(size_t)top_index].P, max_pairs);
+    if (int rc = deposit_buffers_check(who, *s, top_index, flags, n_bins, d_work, work_bytes, true, d_hist, d_detections)) return rc;
+    return deposit_call_run(*s, who, [&](const HipApi* H) {
+        return image_enqueue(*s, H, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, max_pairs, d_work, d_hist, d_detections,
+                             (hipStream_t)stream);
+    });
 }
 
 int hare_image2_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                        int32_t frac_bits, int64_t max_cands, int64_t max_paths, void* d_work, void* d_hist, void* d_detections, void* stream)
 {
-    if (!s) {
-        set_error("null scene");
-        return HARE_E_INVALID;
-    }
     const char* const who = "hare_image2_device";
-    if (int rc = direct_check_weight(who, n_weight)) return rc;
-    flags &= HARE_RECEIVE_DIRECTIONAL;
-    if (int rc = receive_check_args(who, *s, flags, kind, top_index, 0, 1, n_bins, bin_len, frac_bits)) return rc;
-    if (s->src.set && s->src.B != scene_bands(*s, top_index)) {
-        set_error(std::string(who) + ": the source has " + std::to_string(s->src.B) + " bands, the topology " + std::to_string(scene_bands(*s, top_index)));
-        return HARE_E_INVALID;
-    }
+    if (int rc = deposit_call_check(who, s, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits)) return rc;
     if (max_cands < 1 || max_cands > ((int64_t)1 << 26) || max_paths < 1 || max_paths > ((int64_t)1 << 26)) {
         set_error(std::string(who) + ": max_cands or max_paths out of range (1 .. 2^26)");
         return HARE_E_INVALID;
     }
-    if (!d_work || !d_hist || !d_detections || ((uintptr_t)d_work & 15u)) {
-        set_error(std::string(who) + ": null work array / histogram / detections, or a work array off a 16-byte boundary");
-        return HARE_E_INVALID;
-    }
-    const size_t K = std::max<size_t>(1, s->rcv.size() / 4);
-    const struct { const void* p; size_t bytes; } bufs[] = {{d_work, (size_t)HARE_IMAGE2_WORK_BYTES(s->topos[(size_t)top_index].P, max_cands, max_paths)},
-                                                            {d_hist, receive_hist_words(*s, top_index, n_bins, flags, 1) * sizeof(uint64_t)},
-                                                            {d_detections, K * 2 * sizeof(uint64_t)}};
-    for (size_t x = 0; x < 3; ++x)
-        for (size_t y = x + 1; y < 3; ++y)
-            if (ranges_overlap(bufs[x].p, bufs[x].bytes, bufs[y].p, bufs[y].bytes)) {
-                set_error(std::string(who) + ": work array, histogram and detections must not overlap");
-                return HARE_E_INVALID;
-            }
-    GUARD_BEGIN
-    const HipApi* H = api_or_err();
-    if (!H) return HARE_E_NODEVICE;
-    DeviceGuard dev_guard(H, s->device);
-    if (!s->module) {
-        int rc = ensure_device(*s, H);
-        if (rc) return rc;
-    }
-    if (int rc = source_ready(*s, H, who)) return rc;
-    if (int rc = upload_polys(*s, H)) return rc;
-    if (int rc = receive_ready(*s, H, who)) return rc;
-    return image2_enqueue(*s, H, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, max_cands, max_paths, d_work, d_hist, d_detections,
-                          (hipStream_t)stream);
-    GUARD_END
+    const size_t work_bytes = (size_t)HARE_IMAGE2_WORK_BYTES(s->topos[(size_t)top_index].P, max_cands, max_paths);
+    if (int rc = deposit_buffers_check(who, *s, top_index, flags, n_bins, d_work, work_bytes, true, d_hist, d_detections)) return rc;
+    return deposit_call_run(*s, who, [&](const HipApi* H) {
+        return image2_enqueue(*s, H, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, max_cands, max_paths, d_work, d_hist, d_detections,
+                              (hipStream_t)stream);
+    });
 }
 
 int hare_hist_reduce_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,

@@ -424,7 +424,8 @@ int source_ready(Scene& s, const HipApi* H, const char* who);
 int emit_source(const Scene& s, const HipApi* H, int64_t n, int64_t first_ray, void* d_rays, void* d_state, hipStream_t st);
 // the direct sound (receive.cpp; include/hare_hip.h, "receivers", "Direct sound").  direct_enqueue: hare_direct_emit, the flags-only
 // occlusion query of the partition and hare_direct_deposit[_dir] on the stream, K lanes each; d_work: HARE_DIRECT_WORK_BYTES(K) of scratch.
-// Source and receivers must be on the device (source_ready, receive_ready)
+// Source and receivers must be on the device (source_ready, receive_ready).  The three *_enqueue plans below fill what their kernels share
+// (DepositArgs, ImageScene: hare_device.h) through receive.cpp's deposit_fill and image_scene_fill
 int direct_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                    int32_t frac_bits, void* d_work, void* d_hist, void* d_det, hipStream_t st);
 // first-order image sources (receive.cpp; include/hare_hip.h, "receivers", "Image sources (first order)").  image_enqueue: hare_image_mirror,

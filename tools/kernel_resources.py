@@ -4,6 +4,8 @@ private_segment_fixed_size (scratch), vgpr_spill_count and group_segment_fixed_s
 tests/golden/image2/parent_receive_resources.json is this tool's output on a build of the parent commit of the second-order image sources:
   git worktree add /tmp/parent <parent commit> && make -C /tmp/parent/hare_amd/csrc all
   python tools/kernel_resources.py /tmp/parent/hare_amd/csrc/build/hare_kernels.s hare_receive hare_rain > tests/golden/image2/parent_receive_resources.json
+tests/golden/deposits/parent_resources.json is its output on a build of the parent commit of the shared deposit (deposit.hip), twelve kernels:
+  python tools/kernel_resources.py /tmp/parent/hare_amd/csrc/build/hare_kernels.s hare_direct hare_image > tests/golden/deposits/parent_resources.json
 profiles/image2/kernel_resources.json is its output for `hare_image2` on this tree's build.
 usage: python tools/kernel_resources.py hare_kernels.s PREFIX [PREFIX ..]"""
 import json
