@@ -791,18 +791,8 @@ int hare_bounce_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n
 const char* hare_shoot_kernel_name(const hare_scene* s, int32_t kind, int32_t top_index, int64_t n, uint32_t flags)
 {
     if (!s || top_index < 0 || top_index >= (int32_t)s->topos.size() || kind < HARE_KIND_VOXEL || kind > HARE_KIND_KDTREE) return "";
-    // the launcher's own selection (choose_kernel), fall-backs included
-    const KernChoice kc = choose_kernel(*s, s->module, kind, (size_t)top_index, n, sanitize_flags(*s, flags));
-    if ((flags & HARE_SHOOT_BOUNCE_LOOP) && kc.k == Kern::VoxelPool && s->opt.bounce_fused && (flags & (HARE_SHOOT_COUNT_WORK | HARE_SHOOT_SIMPLE_KERNEL)) == 0) {
-        // hare_bounce_device (<= 16 casts): the fused build of the pool kernel, where it exists and fits (bounce_device_impl's rule)
-        const bool quads = s->topos[(size_t)top_index].has_quads, coarse = s->occ_shift > 0;
-        const unsigned plds = (unsigned)((s->occ_words + 3) / 4) * 16u + (unsigned)kPoolWaves * (unsigned)(kPoolWaveBytes + kPoolBounceExtra);
-        const DeviceModule* M = s->module;
-        const bool have = !M || (!coarse ? (quads ? M->voxel_bounce_quad : M->voxel_bounce_tri) : (quads ? M->voxel_bounce_quad_g : M->voxel_bounce_tri_g)) != nullptr;
-        if (have && plds <= kLdsMax)
-            return !coarse ? (quads ? "hare_voxel_bounce_quad" : "hare_voxel_bounce_tri") : (quads ? "hare_voxel_bounce_quad_g" : "hare_voxel_bounce_tri_g");
-    }
-    return kc.name;
+    // the launcher's own plan (plan_shoot), fall-backs included; HARE_SHOOT_BOUNCE_LOOP: the plan of hare_bounce_device's one launch
+    return plan_shoot(*s, s->module, kind, (size_t)top_index, n, sanitize_flags(*s, flags), false, (flags & HARE_SHOOT_BOUNCE_LOOP) ? 1 : 0).name;
 }
 
 // Slim records back to X_Events (include/hare_hip.h).  Same arithmetic as the kernels: hare_math.h is compiled for the host with

@@ -1,7 +1,6 @@
 // device_scene.cpp -- what a scene keeps on its device: the code object, the polygon / grid / tree records and their uploads, the tight
 // boxes of voxels and subtrees, the kd-tree's one-line node records, the scratch rings sized at build time.  (Split from api.cpp in round 5.)
 #include <math.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -10,9 +9,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/hare_hip.h"
@@ -43,6 +40,15 @@ int hip_fail(const HipApi* H, hipError_t e, const char* what)
     return (e == hipErrorOutOfMemory) ? HARE_E_NOMEM : HARE_E_HIP;
 }
 
+const char* const kVoxelKernelNames[DeviceModule::kFamilies][2][2] = {
+    {{"hare_voxel_pool_tri", "hare_voxel_pool_quad"}, {"hare_voxel_pool_tri_g", "hare_voxel_pool_quad_g"}},
+    {{"hare_voxel_pool_tri_ov", "hare_voxel_pool_quad_ov"}, {"hare_voxel_pool_tri_g_ov", "hare_voxel_pool_quad_g_ov"}},
+    {{"hare_voxel_pool_tri_own", "hare_voxel_pool_quad_own"}, {"hare_voxel_pool_tri_g_own", "hare_voxel_pool_quad_g_own"}},
+    {{"hare_voxel_persist_tri", "hare_voxel_persist_quad"}, {"hare_voxel_persist_tri_g", "hare_voxel_persist_quad_g"}},
+    {{"hare_voxel_occl_tri", "hare_voxel_occl_quad"}, {"hare_voxel_occl_tri_g", "hare_voxel_occl_quad_g"}},
+    {{"hare_voxel_bounce_tri", "hare_voxel_bounce_quad"}, {"hare_voxel_bounce_tri_g", "hare_voxel_bounce_quad_g"}},
+};
+
 std::mutex g_mod_mu;
 std::map<int, std::unique_ptr<DeviceModule>> g_modules;
 
@@ -61,27 +67,7 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_voxel_shoot_tri", &m->voxel_tri},
         {"hare_voxel_shoot_quad", &m->voxel_quad},
         {"hare_voxel_shoot_count", &m->voxel_count},
-        {"hare_voxel_persist_tri", &m->voxel_persist_tri},
-        {"hare_voxel_persist_quad", &m->voxel_persist_quad},
-        {"hare_voxel_persist_tri_g", &m->voxel_persist_tri_g},
-        {"hare_voxel_persist_quad_g", &m->voxel_persist_quad_g},
-        {"hare_voxel_pool_tri", &m->voxel_pool_tri},
-        {"hare_voxel_pool_quad", &m->voxel_pool_quad},
-        {"hare_voxel_pool_tri_g", &m->voxel_pool_tri_g},
-        {"hare_voxel_pool_quad_g", &m->voxel_pool_quad_g},
-        {"hare_voxel_pool_tri_ov", &m->voxel_pool_tri_ov},
-        {"hare_voxel_pool_quad_ov", &m->voxel_pool_quad_ov},
-        {"hare_voxel_pool_tri_g_ov", &m->voxel_pool_tri_g_ov},
-        {"hare_voxel_pool_quad_g_ov", &m->voxel_pool_quad_g_ov},
-        {"hare_voxel_pool_tri_own", &m->voxel_pool_tri_own},
-        {"hare_voxel_pool_quad_own", &m->voxel_pool_quad_own},
-        {"hare_voxel_pool_tri_g_own", &m->voxel_pool_tri_g_own},
-        {"hare_voxel_pool_quad_g_own", &m->voxel_pool_quad_g_own},
         {"hare_octree_dense_own", &m->octree_dense_own},
-        {"hare_voxel_bounce_tri", &m->voxel_bounce_tri},
-        {"hare_voxel_bounce_quad", &m->voxel_bounce_quad},
-        {"hare_voxel_bounce_tri_g", &m->voxel_bounce_tri_g},
-        {"hare_voxel_bounce_quad_g", &m->voxel_bounce_quad_g},
         {"hare_counters_sum", &m->counters_sum},
         {"hare_octree_shoot", &m->octree},
         {"hare_octree_shoot_count", &m->octree_count},
@@ -99,10 +85,6 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_kdtree_shoot_count", &m->kdtree_count},
         {"hare_reflect", &m->reflect},
         {"hare_occlusion", &m->occlusion},
-        {"hare_voxel_occl_tri", &m->voxel_occl_tri},
-        {"hare_voxel_occl_quad", &m->voxel_occl_quad},
-        {"hare_voxel_occl_tri_g", &m->voxel_occl_tri_g},
-        {"hare_voxel_occl_quad_g", &m->voxel_occl_quad_g},
         {"hare_octree_occl", &m->octree_occl},
         {"hare_octree_occl_any", &m->octree_occl_any},
         {"hare_events_pack_slim", &m->events_pack_slim},
@@ -148,6 +130,8 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         hipError_t e = H->ModuleGetFunction(t.fn, m->mod, t.name);
         if (e != hipSuccess) *t.fn = nullptr;   // optional kernels may be absent in a given build
     }
+    for (int i = 0; i < DeviceModule::kFamilies * 4; ++i)          // the voxel families, member by member
+        if (H->ModuleGetFunction(&m->voxel[0][0][0] + i, m->mod, (&kVoxelKernelNames[0][0][0])[i]) != hipSuccess) (&m->voxel[0][0][0])[i] = nullptr;
     const char* const receive_names[6] = {"hare_receive_reflect", "hare_receive_scatter", "hare_receive_scatter_rain", "hare_receive_reflect_map",
                                           "hare_receive_scatter_map", "hare_rain_step"};
     for (int f = 0; f < 6; ++f)
@@ -372,7 +356,7 @@ int upload_voxel(Scene& s, const HipApi* H)
     occ_layout(g.ct, s.occ_shift, s.occ_cd, s.occ_words);
     for (size_t m = 0; m < M; ++m) {
         std::vector<CellRec> cells(ncell);
-        std::vector<uint32_t> occ((size_t)((s.occ_words + 3) / 4) * 4, 0u);   // padded to 16 bytes for uint4 staging
+        std::vector<uint32_t> occ(bitmap_lds(s.occ_words) / 4u, 0u);   // padded to 16 bytes for uint4 staging
         for (size_t c = 0; c < ncell; ++c) {
             cells[c].start = g.start[m][c];
             cells[c].count = g.start[m][c + 1] - g.start[m][c];
@@ -405,15 +389,10 @@ int launch(const HipApi* H, hipFunction_t f, unsigned grid, unsigned block, unsi
 // They are an ACCELERATION, never a precondition, and cost 32 B per voxel and topology (twice the CellRec array: 4.3 GB at D = 512),
 // so they exist only where they are used:
 //   * the option voxel_tight is on (hare_scene_set_option("voxel_tight", 1) on a grid built without them builds them then);
-//   * the pool kernel K1q, the only kernel that reads them, can serve the grid (pool_can_serve: ct <= 512, bitmap + pools fit LDS);
+//   * the pool kernel K1q, the only kernel that reads them, can serve the grid (launch.h: pool_can_serve);
 //   * they fit the budget `voxel_tight_max_mb` (0 = no budget) -- and an allocation that fails is "no boxes", not a failed build:
 //     what was allocated is freed, cellbox_rad stays -1, the grid is traced exactly as before (every list scanned).
 // Returns an error only for a kernel launch / synchronisation failure (the device is then in trouble whatever we do).
-bool pool_can_serve(const Scene& s)
-{
-    const unsigned lds = (unsigned)((s.occ_words + 3) / 4) * 16u;
-    return lds + (unsigned)kPoolWaves * (unsigned)kPoolWaveBytes <= 160u * 1024u && s.vox.ct <= 512;
-}
 // The order ring of the pool kernel (scene.h; launch.cpp: the order pass of hare_cost_order): reserved HERE, when the grid goes to the device
 // (every builder ends in upload_cell_boxes) and when the options that size it change -- single-caller moments by contract, nothing of the
 // scene in flight -- so that a shoot never allocates.  kOrderRing blocks of `voxel_order_max_rays` entries, one allocation; the ring
@@ -454,12 +433,11 @@ void upload_block_occ(Scene& s, const HipApi* H)
     if (!s.opt.voxel_skip || !pool_can_serve(s) || !s.module || !s.module->block_occ || !s.vox.built || s.d_cells.size() != s.topos.size()) return;
     const int nb = (s.vox.ct + 3) / 4;
     const long long words = ((long long)nb * nb * nb + 31) / 32;
-    const unsigned lds = (unsigned)((s.occ_words + 3) / 4) * 16u + (unsigned)kPoolWaves * (unsigned)kPoolWaveBytes;
-    if (lds + (unsigned long long)((words + 3) / 4) * 16ull + 256ull > 160ull * 1024ull) return;       // (256: the kernel's static LDS)
+    if ((unsigned long long)pool_lds(s) + bitmap_lds(words) + 256ull > kLdsMax) return;       // (256: the kernel's static LDS)
     const long long ncell = (long long)s.vox.ct * s.vox.ct * s.vox.ct;
     for (size_t m = 0; m < s.topos.size(); ++m) {
         if (!s.d_cells[m]) continue;
-        const size_t bytes = (size_t)((words + 3) / 4) * 16u;
+        const size_t bytes = bitmap_lds(words);
         if (H->Malloc(&s.d_bocc[m], bytes) != hipSuccess) { (void)H->GetLastError(); s.d_bocc[m] = nullptr; continue; }
         if (H->Memset(s.d_bocc[m], 0, bytes) != hipSuccess) { (void)H->GetLastError(); dev_free(H, s.d_bocc[m]); continue; }
         const void* cells = s.d_cells[m];
@@ -560,25 +538,26 @@ int32_t octree_levels(const OctreeHost& o)
 void reserve_oct_scratch(Scene& s, const HipApi* H)
 {
     if (!s.module || !H) return;
-    const size_t cus = (size_t)std::max(1, s.module->cu_count);
-    const size_t levels = (size_t)std::max(1, s.oct_levels);
-    const size_t spill_entries = (size_t)std::max(0, 7 * (int)levels + 8 - kGroupStack);
-    const size_t glds = 4u * (size_t)kGroupWaveBytes;
-    const size_t g_per_cu = std::min<size_t>((size_t)HARE_K2G_WAVES_PER_EU, std::max<size_t>(1, kLdsMax / glds));
-    const size_t need_group = cus * g_per_cu * 4u * 8u * spill_entries * 24u;
-    const size_t plds = levels * 256u * 20u;
-    const size_t p_per_cu = std::min<size_t>((size_t)HARE_K2P_WAVES_PER_EU, std::max<size_t>(1, kLdsMax / plds));
-    const size_t stride = ((size_t)kOctTailHead + 20u * levels + 15u) & ~(size_t)15u;
-    const size_t rec_bytes = (cus * p_per_cu * 4u * 64u * stride + 255u) & ~(size_t)255u;
-    const size_t tail_spill = cus * (size_t)HARE_K2G_WAVES_PER_EU * 4u * 8u * spill_entries * 24u;
+    // the launch plans (plan_shoot) of the two largest launches, whatever the scene's own rule picks and the code object holds: the options forced to K2g, and to
+    // K2p with the K2g-tail behind it, every octree kernel taken as present, at the largest batch the persistent kernels take (a build call: nothing reads the options meanwhile)
+    const SceneOptions own = s.opt;
+    DeviceModule full = *s.module;
+    full.octree_group = full.octree_persist = full.octree_group_tail = full.voxel_tri;
+    const auto block_of = [&](int kernel) {
+        s.opt.octree_kernel = kernel; s.opt.octree_tail = 2; s.opt.k2p_tail_max = 0;
+        const ShootPlan p = plan_shoot(s, &full, HARE_KIND_OCTREE, 0, 0x7FFFFF00ll - 1, 0u);
+        s.opt = own;
+        return oct_scratch_block(p.grid, p.block, p.oc, p.oc.tail_levels > 0, (unsigned)std::max(1, full.cu_count)).bytes();
+    };
+    const size_t need_group = block_of(3), need_handed = block_of(1);
     // ... but only what the scene's OPTIONS can launch (ADVICE, round 5): by the library's rule -- K2g below 320 rays per CU, K2d above, K2d handing
     // nothing over -- no launch ever writes a hand-over record, and the blocks hold K2g's stack spill alone (nothing for trees up to
     // (kGroupStack - 8) / 7 levels: the 8-level bench tree reserves 0 bytes where round 5 held 0.7 GB per scene).  Records are reserved when
     // K2p is forced ("octree_kernel" 1), a developer hand-over rule is set, or the tree is too deep for K2d's LDS -- hare_scene_set_option
     // calls this again when one of those changes.
-    const bool dense_fits = (unsigned)levels * 256u * 20u + kOctDenseExtra <= kLdsMax;
+    const bool dense_fits = oct_persist_lds(std::max(1, s.oct_levels), true) <= kLdsMax;
     const bool handover = s.opt.octree_tail != 0 && (s.opt.octree_kernel == 1 || s.opt.k2p_tail_max > 0 || s.opt.k2p_tail_patience >= 0 || !dense_fits);
-    const size_t need = std::max(need_group, handover ? rec_bytes + tail_spill : (size_t)0);
+    const size_t need = std::max(need_group, handover ? need_handed : (size_t)0);
     std::lock_guard<std::mutex> lk(s.oct_tail_mu);
     if (need <= s.oct_tail_block_bytes) return;
     if (s.d_oct_tail) {

@@ -1,19 +1,13 @@
-// launch.cpp -- which kernel serves a batch and how it is launched: the launch-slot ring, the scene options, the kernel choice
-// (ONE function for the launcher and for hare_shoot_kernel_name), hare_shoot_device / hare_bounce_device behind the C-ABI.  (Split from api.cpp in round 5.)
-#include <math.h>
+// launch.cpp -- which kernel serves a batch and how it is launched.  plan_shoot fills the launch plan (launch.h: ShootPlan) from the scene, its
+// options, the module and the batch size alone: ONE function for the launchers, hare_shoot_kernel_name and reserve_oct_scratch; the sizes it works
+// with have one definition each in launch.h.  What depends on a call's buffers (aliasing checks, ShootIO's pointers, the order pass, K2q's scratch
+// ring) is in launch_voxel / launch_octree / launch_kdtree behind shoot_device_impl.  Also: the launch-slot ring, the scene options, the bounce loop.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
-#include <cmath>
-#include <limits>
-#include <map>
-#include <memory>
 #include <mutex>
-#include <new>
 #include <string>
-#include <thread>
-#include <vector>
 
 #include "../../include/hare_hip.h"
 #include "scene.h"
@@ -28,19 +22,7 @@ namespace hare {
 // finished, which is the rule), so a 65th launch in flight waits for the first instead of sharing its ticket word.  The
 // slot's mutex keeps wait + launch + record together when several host threads launch on one scene.
 // args[1] must point to `io`.
-// Octree launches get a block of the scene's octree scratch ring (one block per launch in flight, event-ordered):
-//   tail_levels > 0     a K2p launch: hand-over records for the rays its waves give up (tail_max per wave), followed on the same
-//                       stream, inside the slot's lock, by the tail kernel -- K2t (octree_coop.hip: a wave per ray, the last few
-//                       rays of a wave) or K2g-tail (octree_group.hip: eight lanes per ray, ALL the rays a wave still holds when
-//                       the tickets run dry)
-//   spill_entries > 0   K2g's stack entries beyond what LDS holds (24 bytes x entries per group of eight lanes), for the K2g
-//                       launch itself or for the K2g-tail behind K2p
-struct OctScratch {
-    int tail_levels = 0;
-    int tail_max = 0, tail_patience = 0;
-    bool group_tail = false;
-    int spill_entries = 0;
-};
+// Octree launches get a block of the scene's octree scratch ring (launch.h: OctScratch, oct_scratch_block).
 // A stream under capture (hipStreamBeginCapture) takes kernel launches but not this library's cross-launch event protocol in a form a
 // graph replay could honour twice: the order pass is skipped there (the cast runs in the caller's order: same events).
 static bool stream_is_capturing(const HipApi* H, hipStream_t st)
@@ -66,17 +48,12 @@ int launch_on_slot(Scene& s, const HipApi* H, hipFunction_t f, unsigned grid, un
     const hipFunction_t tail_fn = oc.group_tail ? s.module->octree_group_tail : s.module->octree_tail;
     const bool with_tail = oc.tail_levels > 0 && s.opt.coop_tail && tail_fn != nullptr;
     const unsigned cus = (unsigned)std::max(1, s.module->cu_count);
-    // the tail kernel's grid: K2t a wave per ray of a typical hand-over; K2g-tail a chip full of groups (waves without a record end at once)
-    const unsigned tgrid = !with_tail ? 0u : (oc.group_tail ? cus * (unsigned)HARE_K2G_WAVES_PER_EU : std::max(1u, std::min(grid, 4u * cus)));
-    const unsigned spill_groups = oc.spill_entries <= 0 ? 0u : (with_tail && oc.group_tail ? tgrid * 4u * 8u : grid * (block / 64u) * 8u);
-    const bool with_spill = spill_groups > 0 && (!oc.tail_levels || (with_tail && oc.group_tail));
+    const OctBlock blk = oct_scratch_block(grid, block, oc, with_tail, cus);
+    const bool with_spill = blk.spill_bytes > 0;
     std::unique_lock<std::mutex> tail_lk(s.oct_tail_mu, std::defer_lock);
     int tail_ring = -1;
     if (with_tail || with_spill) {
-        const size_t stride = !with_tail ? 0 : (((size_t)kOctTailHead + 20u * (size_t)oc.tail_levels + 15u) & ~(size_t)15u);
-        const size_t rec_bytes = !with_tail ? 0 : (((size_t)grid * (block / 64u) * (size_t)oc.tail_max * stride + 255u) & ~(size_t)255u);
-        const size_t spill_bytes = with_spill ? (size_t)spill_groups * (size_t)oc.spill_entries * 24u : 0;
-        const size_t need = rec_bytes + spill_bytes;
+        const size_t need = blk.bytes();
         tail_lk.lock();                      // held until the launch (and the tail behind it) is enqueued and the block's event recorded
         if (need > s.oct_tail_block_bytes) {
             // larger blocks: only when reserve_oct_scratch could not allocate at build time (it sizes the ring for the largest launch
@@ -96,13 +73,13 @@ int launch_on_slot(Scene& s, const HipApi* H, hipFunction_t f, unsigned grid, un
         unsigned char* blockp = static_cast<unsigned char*>(s.d_oct_tail) + (size_t)tail_ring * s.oct_tail_block_bytes;
         if (with_tail) {
             io.oct_tail = blockp;
-            io.oct_tail_stride = (int32_t)stride;
+            io.oct_tail_stride = (int32_t)blk.stride;
             io.oct_tail_levels = oc.tail_levels;
             io.oct_tail_max = oc.tail_max;
             io.oct_tail_patience = oc.tail_patience;
         }
         if (with_spill) {
-            io.oct_spill = blockp + rec_bytes;
+            io.oct_spill = blockp + blk.rec_bytes;
             io.oct_spill_cap = oc.spill_entries;
         }
     }
@@ -126,8 +103,8 @@ int launch_on_slot(Scene& s, const HipApi* H, hipFunction_t f, unsigned grid, un
     if (with_tail) {
         // the tail reads the count K2p left behind.  K2t (HARE_K2T_GROUP = 64): a whole wave per handed-over ray, four rays per workgroup,
         // LDS one 20-byte frame per level for each; K2g-tail: the groups' stacks and pending lists, as K2g
-        const unsigned tlds = oc.group_tail ? 4u * (unsigned)kGroupWaveBytes : kOctTailGroupsPerBlock * 20u * (unsigned)oc.tail_levels;
-        rc = launch(H, tail_fn, tgrid, 256, tlds, st, args);
+        const unsigned tlds = oc.group_tail ? kGroupLds : kOctTailGroupsPerBlock * 20u * (unsigned)oc.tail_levels;
+        rc = launch(H, tail_fn, blk.tail_grid, 256, tlds, st, args);
         if (rc) return fail_after_launch(rc);
     }
     if (tail_ring >= 0) {
@@ -207,6 +184,13 @@ void read_env_options(SceneOptions& o)
     }
 }
 
+// developer sweeps (tools/sweep.py, tools/phase_prof.py), HARE_TUNE = steps,refill,chunk,blocks_per_cu,exact: only blocks_per_cu reaches the production kernels, the rest the profiling build
+static bool tune_given(const SceneOptions& o) { return o.tune[0] > 0 && o.tune[1] > 0 && o.tune[1] <= 64 && o.tune[2] > 0; }
+// rays per ticket: the kernel's own default unless the developer option "ticket_rays" sets it
+static int clamp_ticket(const SceneOptions& o, int by_rule) { return o.ticket_rays > 0 ? std::max(8, std::min(4096, o.ticket_rays)) : by_rule; }
+// the developer options "k1p_static_rays" / "k2p_static_rays": the static first chunk in the kernel's own steps
+static int32_t static_override(int option, int32_t by_rule, int step, int lo, int hi) { return option > 0 ? std::max(lo, std::min(hi, option / step * step)) : by_rule; }
+
 // The persistent kernels (K1p, K2p) give every wave of the grid a static first chunk of rays and hand out the rest by tickets:
 // 128 rays per wave when the batch has plenty, less for a batch that does not (a fixed 128 left half of the grid's waves
 // without any work at 262k rays), in steps of 32 and at least 64.  How much less differs (measured): a voxel ray
@@ -237,7 +221,7 @@ size_t voxel_scene_bytes(const Scene& s, size_t top)
 }
 int ticket_rays_for(const Scene& s, int64_t n, bool pool)
 {
-    if (s.opt.ticket_rays > 0) return std::max(8, std::min(4096, s.opt.ticket_rays));            // developer sweeps
+    if (s.opt.ticket_rays > 0) return clamp_ticket(s.opt, 0);            // developer sweeps
     // measured optimum on MI355X (tools/sweep_ticket.py): 32 rays up to ~1.5M rays, where the end of the batch dominates,
     // growing to 128 where the ~11 ns/ticket same-address atomic rate would start to bind
     // K1q: 64 rays -- one full round of set-ups -- at every size (re-swept on the final round-3 kernel, hall and cathedral, 524k ... 8M
@@ -248,9 +232,9 @@ int ticket_rays_for(const Scene& s, int64_t n, bool pool)
     return n < 1572864 ? 32 : (n < 6291456 ? 64 : (n < 12582912 ? 96 : 128));
 }
 
-// Which kernel serves a shoot: ONE function, used by the launcher and by hare_shoot_kernel_name, so that the name a profile
-// is read by is the kernel that ran -- including the fall-backs (kernel missing from the code object, LDS that does not fit).
-// `M` may be null (no device yet): the rule alone, for a 256-CU part.
+// The launch plan: which kernel serves a shoot and what its launch is made of.  ONE function, used by the launchers, by hare_shoot_kernel_name
+// and by the reservations, so that the name a profile is read by is the kernel that ran -- including the fall-backs (kernel missing from the
+// code object, LDS that does not fit).  `M` may be null (no device yet): the rule alone, for a 256-CU part.
 //
 // The voxel path has two production kernels (measured on MI355X over 9 scene / grid combinations): K1q
 // (hare_voxel_pool_*) once a launch is long enough for its steady state to outweigh its longer ramp and drain, K1p
@@ -264,16 +248,17 @@ int ticket_rays_for(const Scene& s, int64_t n, bool pool)
 constexpr bool kOctreePoolDefault = false;
 constexpr int64_t kK2dShortBatchPerCu = 1280;      // K2d: below this many rays per CU (327 680 on 256 CUs) a wave is refilled at 32 idle lanes instead of 16
 
+// The first half of the plan: kernel id, name and function.
 // flags_only: an occlusion query without events (hare_occluded_* with events == NULL): the hare_*_occl kernels, which write the
 // flag and cut the traversal short; the simple kernels (counting, forced, kd-tree) write the flag after the full trace.
-KernChoice choose_kernel(const Scene& s, const DeviceModule* M, int32_t kind, size_t top, int64_t n, uint32_t flags, bool flags_only)
+static ShootPlan choose_kernel(const Scene& s, const DeviceModule* M, int32_t kind, size_t top, int64_t n, uint32_t flags, bool flags_only)
 {
-    KernChoice c;
+    ShootPlan c;
     const bool count = (flags & HARE_SHOOT_COUNT_WORK) != 0, simple = (flags & HARE_SHOOT_SIMPLE_KERNEL) != 0;
     // HARE_SHOOT_COUNT_OWN: the production kernel's counting build (K1q, K2d, the kd-tree kernel); a batch another kernel would serve
     // has none -> no kernel (the caller reports HARE_E_UNSUPPORTED)
     const bool own = (flags & HARE_SHOOT_COUNT_OWN) != 0 && !count && !simple && !flags_only;
-    const bool quads = s.topos[top].has_quads;
+    const int quads = s.topos[top].has_quads ? 1 : 0;
     const bool huge = n >= 0x7FFFFF00ll;                  // the persistent kernels index rays with 32 bits
     const int cus = (M && M->cu_count > 0) ? M->cu_count : 256;
     auto pick = [&](Kern k, const char* name, hipFunction_t DeviceModule::*f) {
@@ -283,31 +268,22 @@ KernChoice choose_kernel(const Scene& s, const DeviceModule* M, int32_t kind, si
     };
     auto have = [&](hipFunction_t DeviceModule::*f) { return !M || (M->*f) != nullptr; };
     if (kind == HARE_KIND_VOXEL) {
+        // a member of a voxel family (scene.h: DeviceModule::voxel), by the bitmap's resolution and the topology's polygons
+        const int coarse = s.occ_shift > 0 ? 1 : 0;
+        auto pick_voxel = [&](Kern k, DeviceModule::VoxelFamily fam) { c.k = k; c.name = kVoxelKernelNames[fam][coarse][quads]; c.f = M ? M->voxel[fam][coarse][quads] : nullptr; };
+        auto have_voxel = [&](DeviceModule::VoxelFamily fam, int co, int qu) { return !M || M->voxel[fam][co][qu] != nullptr; };
+        auto pick_simple = [&]() { pick(Kern::VoxelSimple, quads ? "hare_voxel_shoot_quad" : "hare_voxel_shoot_tri", quads ? &DeviceModule::voxel_quad : &DeviceModule::voxel_tri); };
         if (flags & 0x8000u) { pick(Kern::VoxelAudit, "hare_cull_audit", &DeviceModule::cull_audit); return c; }
-        const bool persist_ok = have(&DeviceModule::voxel_persist_tri) && have(&DeviceModule::voxel_persist_quad) &&
-                                have(&DeviceModule::voxel_persist_tri_g) && have(&DeviceModule::voxel_persist_quad_g);
+        const bool persist_ok = have_voxel(DeviceModule::Persist, 0, 0) && have_voxel(DeviceModule::Persist, 0, 1) &&
+                                have_voxel(DeviceModule::Persist, 1, 0) && have_voxel(DeviceModule::Persist, 1, 1);
         if (count) { pick(Kern::VoxelCount, "hare_voxel_shoot_count", &DeviceModule::voxel_count); return c; }
-        if (simple || huge || !persist_ok) {
-            if (quads) pick(Kern::VoxelSimple, "hare_voxel_shoot_quad", &DeviceModule::voxel_quad);
-            else pick(Kern::VoxelSimple, "hare_voxel_shoot_tri", &DeviceModule::voxel_tri);
-            return c;
-        }
-        const bool coarse = s.occ_shift > 0;
+        if (simple || huge || !persist_ok) { pick_simple(); return c; }
         if (flags_only) {
-            hipFunction_t DeviceModule::*of = !coarse ? (quads ? &DeviceModule::voxel_occl_quad : &DeviceModule::voxel_occl_tri)
-                                                       : (quads ? &DeviceModule::voxel_occl_quad_g : &DeviceModule::voxel_occl_tri_g);
-            if (have(of)) {
-                pick(Kern::VoxelOccl, !coarse ? (quads ? "hare_voxel_occl_quad" : "hare_voxel_occl_tri")
-                                              : (quads ? "hare_voxel_occl_quad_g" : "hare_voxel_occl_tri_g"), of);
-                return c;
-            }
-            if (quads) pick(Kern::VoxelSimple, "hare_voxel_shoot_quad", &DeviceModule::voxel_quad);
-            else pick(Kern::VoxelSimple, "hare_voxel_shoot_tri", &DeviceModule::voxel_tri);
+            if (have_voxel(DeviceModule::Occl, coarse, quads)) pick_voxel(Kern::VoxelOccl, DeviceModule::Occl);
+            else pick_simple();
             return c;
         }
-        const unsigned lds = (unsigned)((s.occ_words + 3) / 4) * 16u;
-        const bool pool_fits = lds + (unsigned)kPoolWaves * (unsigned)kPoolWaveBytes <= kLdsMax && s.vox.ct <= 512 && !(flags & 0x4000u);
-        const int64_t fill = (int64_t)cus * kPoolWaves * kPoolSlots;          // rays in flight when every pool of the chip is full
+        const bool pool_fits = pool_can_serve(s) && !(flags & 0x4000u);
         // K1q for every batch size.  Round 2 needed three pool fills of the chip on a resident scene before K1q won, the cooperative
         // tails brought that to two, the wide drain modes (voxel_pool.hip) to one -- and a batch BELOW one fill is spread over all waves
         // of the chip (ShootIO::static_rays), whose few rays each get several lanes from their second round on: K1p / K1q, ms, hall
@@ -316,49 +292,34 @@ KernChoice choose_kernel(const Scene& s, const DeviceModule* M, int32_t kind, si
         // 0.302 / 0.322, 262k 0.354 / 0.337, 524k 0.609 / 0.439 (profiles/r03_experiments/k1p_k1q_small_batches.log,
         // k1p_k1q_crossover_with_wide_drain.log).  K1p serves what the pool kernel cannot: grids beyond 512 voxels a side or a bitmap
         // that leaves no room for the pools, and the developer builds.
-        (void)fill;
         const bool pool_wanted = s.opt.voxel_kernel == 2 || s.opt.voxel_kernel == 0;
-        hipFunction_t DeviceModule::*pf = !coarse ? (quads ? &DeviceModule::voxel_pool_quad : &DeviceModule::voxel_pool_tri)
-                                                   : (quads ? &DeviceModule::voxel_pool_quad_g : &DeviceModule::voxel_pool_tri_g);
-        if (pool_wanted && pool_fits && have(pf)) {
-            pick(Kern::VoxelPool, !coarse ? (quads ? "hare_voxel_pool_quad" : "hare_voxel_pool_tri")
-                                          : (quads ? "hare_voxel_pool_quad_g" : "hare_voxel_pool_tri_g"), pf);
-            if (s.opt.voxel_overlap && !own) {      // scene option "voxel_overlap": the build with the fused round, same launch geometry
-                hipFunction_t DeviceModule::*vf = !coarse ? (quads ? &DeviceModule::voxel_pool_quad_ov : &DeviceModule::voxel_pool_tri_ov)
-                                                           : (quads ? &DeviceModule::voxel_pool_quad_g_ov : &DeviceModule::voxel_pool_tri_g_ov);
-                pick(Kern::VoxelPool, !coarse ? (quads ? "hare_voxel_pool_quad_ov" : "hare_voxel_pool_tri_ov")
-                                              : (quads ? "hare_voxel_pool_quad_g_ov" : "hare_voxel_pool_tri_g_ov"), vf);
-            }
-            if (own) {         // HARE_SHOOT_COUNT_OWN: the counting build of the SAME kernel, same launch geometry
-                hipFunction_t DeviceModule::*of = !coarse ? (quads ? &DeviceModule::voxel_pool_quad_own : &DeviceModule::voxel_pool_tri_own)
-                                                           : (quads ? &DeviceModule::voxel_pool_quad_g_own : &DeviceModule::voxel_pool_tri_g_own);
-                pick(Kern::VoxelPool, !coarse ? (quads ? "hare_voxel_pool_quad_own" : "hare_voxel_pool_tri_own")
-                                              : (quads ? "hare_voxel_pool_quad_g_own" : "hare_voxel_pool_tri_g_own"), of);
-            }
+        if (pool_wanted && pool_fits && have_voxel(DeviceModule::Pool, coarse, quads)) {
+            pick_voxel(Kern::VoxelPool, DeviceModule::Pool);
+            if (s.opt.voxel_overlap && !own) pick_voxel(Kern::VoxelPool, DeviceModule::PoolOv);      // scene option "voxel_overlap": the build with the fused round, same launch geometry
+            if (own) pick_voxel(Kern::VoxelPool, DeviceModule::PoolOwn);         // HARE_SHOOT_COUNT_OWN: the counting build of the SAME kernel, same launch geometry
             return c;
         }
-        if (own) { c = KernChoice(); return c; }          // no counting build of K1p
-        if ((flags & 0x4000u) && have(&DeviceModule::voxel_persist_prof) && (!M || M->voxel_persist_prof) && !coarse && !quads) {
+        if (own) { c = ShootPlan(); return c; }          // no counting build of K1p
+        if ((flags & 0x4000u) && have(&DeviceModule::voxel_persist_prof) && !coarse && !quads) {
             pick(Kern::VoxelProf, "hare_voxel_persist_prof", &DeviceModule::voxel_persist_prof);
             return c;
         }
-        pick(Kern::VoxelPersist, !coarse ? (quads ? "hare_voxel_persist_quad" : "hare_voxel_persist_tri")
-                                         : (quads ? "hare_voxel_persist_quad_g" : "hare_voxel_persist_tri_g"),
-             !coarse ? (quads ? &DeviceModule::voxel_persist_quad : &DeviceModule::voxel_persist_tri)
-                     : (quads ? &DeviceModule::voxel_persist_quad_g : &DeviceModule::voxel_persist_tri_g));
+        pick_voxel(Kern::VoxelPersist, DeviceModule::Persist);
         return c;
     }
     if (kind == HARE_KIND_OCTREE) {
         if (count) { pick(Kern::OctCount, "hare_octree_shoot_count", &DeviceModule::octree_count); return c; }
         const int levels = std::max(1, s.oct_levels);
         const bool small_tree = (int64_t)s.oct.nodes.size() < (1 << 23);
+        const bool fits_p = oct_persist_lds(levels, false) <= kLdsMax, fits_d = oct_persist_lds(levels, true) <= kLdsMax;
         if (!simple && !huge && small_tree && flags_only) {
-            if ((flags & kFlagAnyHit) && (unsigned)levels * 256u * 20u <= kLdsMax && have(&DeviceModule::octree_occl_any)) {
+            if ((flags & kFlagAnyHit) && fits_p && have(&DeviceModule::octree_occl_any)) {
                 pick(Kern::OctOccl, "hare_octree_occl_any", &DeviceModule::octree_occl_any);      // no t_max: K2p's OCC build (tests a leaf at once)
                 return c;
             }
-            if ((unsigned)levels * 256u * 20u + kOctDenseExtra <= kLdsMax && have(&DeviceModule::octree_occl)) {
+            if (fits_d && have(&DeviceModule::octree_occl)) {
                 pick(Kern::OctOccl, "hare_octree_occl", &DeviceModule::octree_occl);
+                c.oct_dense = true;
                 return c;
             }
         } else if (!simple && !huge && small_tree) {
@@ -372,7 +333,7 @@ KernChoice choose_kernel(const Scene& s, const DeviceModule* M, int32_t kind, si
             //       K2d / K2g Mrays/s at 262k 235 / 256, 393k 271 / 281, 524k 350 / 301, 786k 441 / 312, 1M 493 / 319, 4M 656 / 337.
             //   K2p (hare_octree_persist) is K2d's predecessor: the A/B baseline (octree_kernel = 1) and the fall-back where K2d's LDS does not fit.
             // The threshold scales with the CU count.
-            const bool fits_p = (unsigned)levels * 256u * 20u <= kLdsMax && have(&DeviceModule::octree_persist);
+            const bool persist_ok = fits_p && have(&DeviceModule::octree_persist);
             const bool group_ok = have(&DeviceModule::octree_group);
             // (second half of round 4: K2d no longer spends a pop step on an exhausted frame, forms its slabs in cursor order and keeps HALF
             //  of a wave's share for tickets -- K2d / K2g at 131k 159 / 180, 196k 235 / 225, 262k 293 / 255, 393k 418 / 283, 524k 474 / 304:
@@ -380,21 +341,21 @@ KernChoice choose_kernel(const Scene& s, const DeviceModule* M, int32_t kind, si
             // (round 6: K2d's static first chunk is half a wave's share at EVERY size -- a floor of 64 rays used to make a small batch all static --
             //  and the crossover fell: K2d / K2g at 65 536 rays 123 / 135, 81 920 169 / 152, 98 304 188 / 168, 131 072 263 / 217 Mrays/s)
             const int64_t group_below = (int64_t)cus * 320;           // 81 920 rays on the 256-CU part
-            const bool group_wanted = s.opt.octree_kernel == 3 || (s.opt.octree_kernel == 0 && (n < group_below || !fits_p));
+            const bool group_wanted = s.opt.octree_kernel == 3 || (s.opt.octree_kernel == 0 && (n < group_below || !persist_ok));
             if (group_wanted && group_ok) {
-                if (own) { c = KernChoice(); return c; }          // no counting build of K2g: the caller is told so
+                if (own) { c = ShootPlan(); return c; }          // no counting build of K2g: the caller is told so
                 pick(Kern::OctGroup, "hare_octree_group", &DeviceModule::octree_group);
                 return c;
             }
             // K2d (K2p's DENSE build) wherever it exists and its LDS fits; K2p (octree_kernel = 1) is the A/B baseline and the fall-back
-            if ((s.opt.octree_kernel == 4 || s.opt.octree_kernel == 0) && (unsigned)levels * 256u * 20u + kOctDenseExtra <= kLdsMax &&
-                have(&DeviceModule::octree_dense)) {
+            if ((s.opt.octree_kernel == 4 || s.opt.octree_kernel == 0) && fits_d && have(&DeviceModule::octree_dense)) {
                 pick(Kern::OctDense, "hare_octree_dense", &DeviceModule::octree_dense);
                 if (own) pick(Kern::OctDense, "hare_octree_dense_own", &DeviceModule::octree_dense_own);
+                c.oct_dense = true;
                 return c;
             }
-            if (own) { c = KernChoice(); return c; }
-            if ((unsigned)levels * 256u * 20u <= kLdsMax && have(&DeviceModule::octree_persist)) {
+            if (own) { c = ShootPlan(); return c; }
+            if (persist_ok) {
                 pick(Kern::OctPersist, "hare_octree_persist", &DeviceModule::octree_persist);
                 return c;
             }
@@ -426,6 +387,142 @@ KernChoice choose_kernel(const Scene& s, const DeviceModule* M, int32_t kind, si
     return c;
 }
 
+int32_t voxel_block_bits_words(const Scene& s, size_t top) { return s.opt.voxel_skip && top < s.d_bocc.size() && s.d_bocc[top] && s.bocc_nb > 0 ? s.bocc_words : 0; }
+
+// The second half: grid, block, dynamic LDS, tickets, static chunk and the scratch request of the kernel chosen.
+ShootPlan plan_shoot(const Scene& s, const DeviceModule* M, int32_t kind, size_t top, int64_t n, uint32_t flags, bool flags_only, int32_t bounce_casts)
+{
+    ShootPlan p = choose_kernel(s, M, kind, top, n, flags, flags_only);
+    const unsigned cus = M ? (unsigned)std::max(1, M->cu_count) : 256u;
+    const bool tuned = tune_given(s.opt);
+    if (tuned) p.refill_min_idle = s.opt.tune[1];
+    p.block = 256;
+    p.grid = (unsigned)((n + 255) / 256);               // the one-ray-per-lane kernels; the persistent ones below
+    switch (p.k) {
+    case Kern::VoxelPool: {
+        // K1q (voxel_pool.hip): more rays than lanes, ray state in LDS, one workgroup per CU
+        // a workgroup per CU whenever the batch has a ray for every wave; the static first chunk is what the batch has for each wave,
+        // in steps of 8, at most 128 (a small batch: few rays per wave, each with several lanes from its second round on)
+        p.block = 64u * (unsigned)kPoolWaves;
+        p.grid = std::max(1u, std::min<unsigned>(cus, (unsigned)((n + kPoolWaves - 1) / kPoolWaves)));
+        const int64_t per_wave = (n + (int64_t)p.grid * kPoolWaves - 1) / ((int64_t)p.grid * kPoolWaves);
+        p.static_rays = (int32_t)std::max<int64_t>(8, std::min<int64_t>(128, (per_wave + 7) / 8 * 8));
+        p.ticket_rays = ticket_rays_for(s, n, true);
+        // hare_bounce_device (<= 16 casts): ONE launch of the fused build of the pool kernel, where the option asks for it, it exists and fits
+        const int coarse = s.occ_shift > 0 ? 1 : 0, quads = s.topos[top].has_quads ? 1 : 0;
+        if (bounce_casts > 0 && bounce_casts <= kBounceMaxCasts && s.opt.bounce_fused && (!M || M->voxel[DeviceModule::Bounce][coarse][quads]) &&
+            pool_lds(s, true) <= kLdsMax) {
+            p.k = Kern::VoxelBounce; p.name = kVoxelKernelNames[DeviceModule::Bounce][coarse][quads]; p.f = M ? M->voxel[DeviceModule::Bounce][coarse][quads] : nullptr;
+            p.lds = pool_lds(s, true);
+            break;
+        }
+        p.lds = pool_lds(s, false, voxel_block_bits_words(s, top));
+        p.static_rays = static_override(s.opt.k1p_static_rays, p.static_rays, 8, 8, 1024);      // developer sweeps (tools/k1q_ticket_sweep.py)
+        p.walk_steps = n >= 2 * (int64_t)cus * kPoolWaves * kPoolSlots ? 32 : 16;      // long walk tasks once the batch is two pool fills of the chip (786 432 rays on 256 CUs)
+        break;
+    }
+    case Kern::VoxelPersist:
+    case Kern::VoxelOccl:
+    case Kern::VoxelProf: {
+        // persistent kernel K1p: a grid that just fills the chip; waves draw ray chunks from a ticket
+        const unsigned lds = bitmap_lds(s.occ_words);     // the occupancy bitmap, <= 64 KB (occ_layout)
+        unsigned per_cu = p.k == Kern::VoxelOccl ? HARE_OCCL_WAVES_PER_EU : 4;       // what the occlusion build is compiled for (kernels.hip)
+        if (tuned && s.opt.tune[3] > 0) per_cu = (unsigned)s.opt.tune[3];
+        if (lds) per_cu = std::min<unsigned>(per_cu, (unsigned)(kLdsMax / lds));
+        p.grid = std::max(1u, std::min<unsigned>(cus * std::max(1u, per_cu), (unsigned)((n + 63) / 64 + 3) / 4));
+        p.ticket_rays = ticket_rays_for(s, n, false);
+        // static first chunk per wave (static_chunk_rays): at 262k rays, where 128 left half the grid's waves without work, 0.348 -> 0.239 ms
+        p.static_rays = static_override(s.opt.k1p_static_rays, static_chunk_rays(n, p.grid, false), 32, 32, 256);   // developer sweeps
+        p.lds = lds + (p.k == Kern::VoxelProf ? 4u * 18u * 8u : 0u);                  // + the profiling build's per-wave statistics
+        break;
+    }
+    case Kern::OctPool:
+        // K2q (octree_pool.hip): more rays than lanes; frames below the top one in a device scratch block per launch in flight
+        p.block = 64u * (unsigned)kOctPoolWaves;
+        p.grid = std::max(1u, std::min<unsigned>(cus, (unsigned)((n + 64 * kOctPoolWaves - 1) / (64 * kOctPoolWaves))));
+        p.lds = (unsigned)kOctPoolWaves * (unsigned)kOctPoolWaveBytes;
+        p.ticket_rays = clamp_ticket(s.opt, 32);
+        break;
+    case Kern::OctGroup: {
+        // K2g (octree_group.hip): workgroups of four waves, eight rays per wave
+        p.grid = std::max(1u, std::min<unsigned>(cus * std::min((unsigned)HARE_K2G_WAVES_PER_EU, std::max(1u, kLdsMax / kGroupLds)), (unsigned)((n + 7) / 8 + 3) / 4));   // a wave per eight rays at least
+        p.lds = kGroupLds;
+        p.ticket_rays = clamp_ticket(s.opt, 8);    // swept 8 / 16 / 32 / 64: 8 (1M rays), flat at 4M
+        // static first chunk per wave: what the batch has for every wave, at most 32 rays (four rounds of eight), at least 8
+        const int64_t per_wave = n / ((int64_t)p.grid * 4);
+        p.static_rays = static_override(s.opt.k2p_static_rays, (int32_t)std::max<int64_t>(8, std::min<int64_t>(32, per_wave / 2 / 8 * 8)), 8, 8, 256);   // developer sweeps
+        p.oc.spill_entries = group_spill_entries(std::max(1, s.oct_levels));
+        break;
+    }
+    case Kern::OctPersist:
+    case Kern::OctDense:
+    case Kern::OctOccl: {
+        // K2p (+ a tail kernel behind it), K2d, or an occlusion build (hare_octree_occl is K2d's OCC build, hare_octree_occl_any K2p's)
+        const int levels = std::max(1, s.oct_levels);
+        const bool dense = p.oct_dense;
+        p.lds = oct_persist_lds(levels, dense);
+        // the kernel is compiled for HARE_K2P_WAVES_PER_EU (K2d: HARE_K2D_WAVES_PER_EU) waves per SIMD (= workgroups of 4 waves per CU); a
+        // persistent grid must not exceed what is resident, or the extra workgroups start when the others have finished
+        const unsigned per_cu = std::min((unsigned)(dense ? HARE_K2D_WAVES_PER_EU : HARE_K2P_WAVES_PER_EU), std::max(1u, kLdsMax / p.lds));
+        p.grid = std::max(1u, std::min<unsigned>(cus * per_cu, (unsigned)((n + 63) / 64 + 3) / 4));      // (a wave for every 32 rays of a small batch was measured: no better)
+        // an octree ray costs ~10x a voxel ray: ticket atomics never bind.  K2p: 32 rays; K2d finishes rays sooner and likes 16
+        // (8 / 16 / 24 / 32 rays per ticket: 1M rays 478 / 502 / 466 / 489 Mrays/s, 1.5M 553 / 570 / 569 / 563, 524k 353 / 354 / 348 / 346)
+        p.ticket_rays = clamp_ticket(s.opt, dense ? 16 : 32);
+        // K2d refills a wave when this many of its lanes are idle: 16 on long batches; on short ones (a wave draws only a few tickets) 32 --
+        // swept (k2d_refill_by_size.log), 16 / 24 / 32 / 48 idle lanes: 196 608 rays 247 / 249 / 251 / 251 Mrays/s, 262 144 317 / 336 / 341 / 340,
+        // 393 216 489 / 495 / 471 / 395, 524 288 559 / 556 / 558 / 530, 655 360 662 / 649 / 624 / 587, 1M 775 / 775 / 757 / 676
+        if (dense && !(s.opt.tune[0] > 0 && s.opt.tune[1] > 0)) p.refill_min_idle = n < (int64_t)cus * kK2dShortBatchPerCu ? 32 : 16;
+        // K2p: 262k rays 2.607 -> 1.861 ms, 524k 2.569 -> 2.336; K2d: half the share (393k rays 338 -> 418 Mrays/s, 524k 421 -> 474, 655k 393 -> 515)
+        p.static_rays = static_override(s.opt.k2p_static_rays, static_chunk_rays(n, p.grid, true, dense, dense), 8, 8, 256);   // developer sweeps
+        // The closest-hit kernel hands rays to a tail kernel (the occlusion build keeps them).  Rule: K2g-tail takes EVERY ray a wave
+        // still walks when the tickets run dry (option "octree_tail" 2, the default); K2t takes a wave's last sixteen after 64 rounds (1)
+        // K2d hands nothing over by the rule: its dense passes put the whole wave on whatever entries its last rays hold, which is what
+        // a tail kernel was for (1M rays: no tail 485 Mrays/s, K2g-tail after 8 / 16 / 32 / 64 / 96 rounds 428 / 451 / 465 / 454 / 463, K2t 464)
+        if (p.k != Kern::OctOccl && s.opt.octree_tail != 0 && !(dense && s.opt.k2p_tail_max == 0 && s.opt.k2p_tail_patience < 0)) {
+            OctScratch& oc = p.oc;
+            oc.tail_levels = levels;
+            oc.group_tail = s.opt.octree_tail == 2 && (!M || M->octree_group_tail != nullptr);
+            oc.tail_max = oc.group_tail ? 64 : kOctTailMax;
+            // K2g-tail: every ray the wave still holds 32 rounds after its tickets ran dry (swept: (64, 0) 345 Mrays/s, (64, 8) 367,
+            // (64, 24..48) 391-396, (64, 64) 377, (64, 128) 347; (24..40, x) the same within 1 %; K2t (16, 64) 384)
+            oc.tail_patience = oc.group_tail ? 32 : HARE_K2P_TAIL_PATIENCE;
+            if (s.opt.k2p_tail_max > 0) oc.tail_max = std::min(64, s.opt.k2p_tail_max);          // developer sweeps
+            if (s.opt.k2p_tail_patience >= 0) oc.tail_patience = s.opt.k2p_tail_patience;
+            if (oc.group_tail) oc.spill_entries = group_spill_entries(levels);
+        }
+        break;
+    }
+    case Kern::OctSimple:
+    case Kern::OctCount: {
+        // one frame per interior level and lane in LDS: 24 bytes x levels x block
+        const unsigned levels = (unsigned)std::max(1, s.oct_levels);
+        unsigned ob = 256;
+        while (ob > 64 && (size_t)levels * ob * 24 > 64 * 1024) ob >>= 1;   // ob = 64: up to 106 levels fit 160 KB
+        p.block = ob;
+        p.grid = (unsigned)((n + ob - 1) / ob);
+        p.lds = levels * ob * 24;
+        break;
+    }
+    case Kern::KdDense: {
+        // K3d: a grid that just fills the chip (what its LDS -- (depth + 2) stack entries of 8 bytes per lane -- allows per CU, at most
+        // HARE_K3D_WAVES_PER_EU workgroups); static first chunk and tickets as K2d
+        p.lds = kd_dense_lds(s.kd.depth_reached);
+        const unsigned per_cu = std::min((unsigned)HARE_K3D_WAVES_PER_EU, std::max(1u, (unsigned)(kLdsMax / p.lds)));
+        p.grid = std::max(1u, std::min<unsigned>(cus * per_cu, (unsigned)((n + 63) / 64 + 3) / 4));
+        p.ticket_rays = clamp_ticket(s.opt, 16);
+        p.static_rays = static_override(s.opt.k2p_static_rays, static_chunk_rays(n, p.grid, true, true), 32, 32, 256);   // developer sweeps
+        break;
+    }
+    case Kern::KdSimple:
+    case Kern::KdCount:
+        p.lds = ((unsigned)s.kd.depth_reached + 2) * 256u * 4u;      // node stack in LDS: at most depth + 2 entries per lane
+        break;
+    default:          // the one-ray-per-lane voxel kernels and the audit: no LDS
+        break;
+    }
+    return p;
+}
+
 // [a, a + na) and [b, b + nb) share a byte
 bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
 {
@@ -451,7 +548,7 @@ static void fill_voxel_args(const Scene& s, int32_t top, VoxelArgs& g)
     g.bocc = nullptr;
     g.bocc_nb = 0;
     g.bocc_words = 0;
-    if (s.opt.voxel_skip && (size_t)top < s.d_bocc.size() && s.d_bocc[(size_t)top] && s.bocc_nb > 0) {
+    if (voxel_block_bits_words(s, (size_t)top) > 0) {
         g.bocc = (const uint32_t*)s.d_bocc[(size_t)top];
         g.bocc_nb = s.bocc_nb;
         g.bocc_words = s.bocc_words;
@@ -506,13 +603,9 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
     }
     if (rcv && rcv->rain) HIP_TRY(H->MemsetAsync(rcv->work.flag, 0, (size_t)n * sizeof(int32_t), st));      // no segment of this call has been rained yet
     // ---- one launch?  (never for the receive loop: its receiver step runs between the casts)
-    if (!rcv && kind == HARE_KIND_VOXEL && casts <= kBounceMaxCasts && flags == 0 && s.vox.built && !s.d_cells.empty()) {
-        const KernChoice kc = choose_kernel(s, &M, kind, (size_t)top, n, 0u);
-        const bool quads = s.topos[top].has_quads, coarse = s.occ_shift > 0;
-        hipFunction_t f = !coarse ? (quads ? M.voxel_bounce_quad : M.voxel_bounce_tri) : (quads ? M.voxel_bounce_quad_g : M.voxel_bounce_tri_g);
-        const unsigned lds = (unsigned)((s.occ_words + 3) / 4) * 16u;
-        const unsigned plds = lds + (unsigned)kPoolWaves * (unsigned)(kPoolWaveBytes + kPoolBounceExtra);
-        if (kc.k == Kern::VoxelPool && f != nullptr && plds <= kLdsMax && s.opt.bounce_fused) {
+    if (!rcv && kind == HARE_KIND_VOXEL && flags == 0 && s.vox.built && !s.d_cells.empty()) {
+        const ShootPlan kc = plan_shoot(s, &M, kind, (size_t)top, n, 0u, false, casts);
+        if (kc.k == Kern::VoxelBounce && kc.f != nullptr) {
             // the work arrays: exclusions of cast 0 (none: -1), rewritten per ray as it goes from cast to cast
             if (d_e1) HIP_TRY(H->MemcpyAsync(work, d_e1, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
             else HIP_TRY(H->MemsetAsync(work, 0xFF, (size_t)n * sizeof(int32_t), st));
@@ -537,14 +630,10 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
             io.out_all = (XEventRec*)all;
             io.out_stride = n;
             io.ctr_casts = (unsigned long long*)d_ctr_casts;
-            const unsigned cus = (unsigned)std::max(1, M.cu_count);
-            unsigned pgrid = std::min<unsigned>(cus, (unsigned)((n + kPoolWaves - 1) / kPoolWaves));
-            if (pgrid == 0) pgrid = 1;
-            const int64_t per_wave = (n + (int64_t)pgrid * kPoolWaves - 1) / ((int64_t)pgrid * kPoolWaves);
-            io.static_rays = (int32_t)std::max<int64_t>(8, std::min<int64_t>(128, (per_wave + 7) / 8 * 8));
-            io.ticket_rays = ticket_rays_for(s, n, true);
+            io.static_rays = kc.static_rays;
+            io.ticket_rays = kc.ticket_rays;
             void* args[] = {&g, &io};
-            return launch_on_slot(s, H, f, pgrid, 64u * (unsigned)kPoolWaves, plds, st, io, args, true);
+            return launch_on_slot(s, H, kc.f, kc.grid, kc.block, kc.lds, st, io, args, true);
         }
     }
     // ---- a launch per cast
@@ -576,7 +665,7 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
     // (Not with a buffer per cast, `all`: there every slot of every cast is written, a retired ray's with its miss record.)
     const bool use_blocks = !all && kind == HARE_KIND_VOXEL && M.live_blocks != nullptr && s.opt.bounce_pack != 0 && n >= 4096 && nblk <= 0x7FFFFFF0ll &&
                             blk_pad + (size_t)((nblk + 15) & ~(int64_t)15) + (size_t)(nblk + 4) * 4u <= (size_t)n * 4u &&
-                            choose_kernel(s, &M, kind, (size_t)top, n, flags | HARE_SHOOT_RETIRED_RAYS).k == Kern::VoxelPool;
+                            plan_shoot(s, &M, kind, (size_t)top, n, flags | HARE_SHOOT_RETIRED_RAYS).k == Kern::VoxelPool;
     if (int rc = sum_counters(-1)) return rc;            // the per-cast blocks are accumulated into: the totals get what THIS loop adds
     // From here on the caller's totals have the per-cast blocks SUBTRACTED: whatever ends the loop early (a cast whose kernel has no counting
     // build under HARE_SHOOT_COUNT_OWN, a failed launch) must put them back, or the totals stay short by what earlier loops counted (ADVICE)
@@ -622,6 +711,192 @@ int bounce_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int
     if (all && d_last) HIP_TRY(H->MemcpyAsync(d_last, all + (size_t)(casts - 1) * (size_t)n, (size_t)n * sizeof(hare_xevent), hipMemcpyDeviceToDevice, st));
     if (int rc = sum_counters(+1)) return rc;
     return HARE_OK;
+}
+
+// The plan as a launcher takes it: refused when the kernel is missing, else applied to the kernel's ShootIO.  flags: the call's public flags
+static int take_plan(const ShootPlan& p, uint32_t flags, const char* missing, ShootIO& io)
+{
+    if (!p.f && (flags & HARE_SHOOT_COUNT_OWN)) {
+        set_error("hare_shoot: HARE_SHOOT_COUNT_OWN -- the kernel this batch gets has no counting build (the pool kernel of Voxel_Grid, "
+                  "hare_octree_dense from 768 rays per CU, the kd-tree kernel have one)");
+        return HARE_E_UNSUPPORTED;
+    }
+    if (!p.f) { set_error(missing); return HARE_E_STATE; }
+    io.ticket_rays = p.ticket_rays; io.static_rays = p.static_rays;
+    io.walk_steps = p.walk_steps; io.refill_min_idle = p.refill_min_idle;
+    return HARE_OK;
+}
+
+// ---- the per-kind launchers: what depends on the call's buffers.  `io` holds the call's pointers and n; `flags` are its public flags.
+static int launch_voxel(Scene& s, const HipApi* H, int32_t top, ShootIO& io, uint32_t flags, bool flags_only, hipStream_t st, const ShootExtra* extra)
+{
+    if (!s.vox.built || s.d_cells.empty()) {
+        set_error("hare_shoot: voxel grid not built");
+        return HARE_E_STATE;
+    }
+    const DeviceModule& M = *s.module;
+    const int64_t n = io.n;
+    VoxelArgs g;
+    fill_voxel_args(s, top, g);
+    const ShootPlan kc = plan_shoot(s, &M, HARE_KIND_VOXEL, (size_t)top, n, flags, flags_only);
+    if (int rc = take_plan(kc, flags, kc.k == Kern::VoxelAudit ? "hare_shoot: the cull audit kernel is missing from the code object" : "hare_shoot: kernel missing from code object", io)) return rc;
+    void* args[] = {&g, &io};
+    if (kc.k == Kern::VoxelAudit || kc.k == Kern::VoxelCount || kc.k == Kern::VoxelSimple)
+        return launch(H, kc.f, kc.grid, kc.block, 0, st, args);
+    if ((flags & 0x3000u) && io.ctr) io.prof = io.ctr + CTR_WORDS;   // developer timeline (0x2000) / round trace (0x1000)
+    if (kc.k == Kern::VoxelPool) {
+        if (extra && extra->blocks) { io.blocks = extra->blocks; io.blk_words = extra->blk_words; }      // a cast of the bounce loop: live blocks only
+        if (s.opt.dev && s.opt.dev_order_ptr && !io.blocks) io.order = (const uint32_t*)(uintptr_t)s.opt.dev_order_ptr;
+        // The order in which K1q takes the rays (order_kernels.hip): inside every window of 4 096 consecutive rays, by an estimate of
+        // the walk length -- a pool of rays of similar cost wastes fewer lane-steps (C4 shard -6.8 %, C2 -5.3 % of the kernel's time with
+        // the order given; window_sort_*.log), the batch's own locality stays.  Rule ("voxel_order" 1, the default): batches of PRIMARY
+        // rays -- no exclusion arrays, not a cast of the bounce loop: reflected rays gain nothing and pay for the indirection
+        // (+5 ... +8 %, window_sort_cathedral_bounce5.log) -- from kOrderMinRays: the pass reads every ray once more (12 us per million
+        // rays: half of HBM's rate), which at 1M rays is what the order gains.  The scratch is a block of the scene's order ring
+        // (stream-ordered allocation was tried first: hipMallocAsync / hipFreeAsync cost the stream more than the pass itself).
+        const bool order_rule = io.blocks ? false : s.opt.voxel_order == 2 || (s.opt.voxel_order == 1 && !io.excl1 && !io.excl2 && !(flags & SHOOT_RETIRED_RAYS) && n >= kOrderMinRays);
+        if (!io.order && order_rule && M.cost_order && (size_t)n <= s.order_cap && (flags & 0xF000u) == 0 && !stream_is_capturing(H, st)) {
+            // a block of the scene's order ring (scene.h), reserved when the grid went to the device: nothing is allocated, freed or
+            // synchronised here.  The block's mutex is held across wait + launches + record (four enqueues)
+            const int ob = (int)(s.order_seq.fetch_add(1) % (unsigned)Scene::kOrderRing);
+            std::lock_guard<std::mutex> olk(s.order_blk_mu[ob]);
+            if (s.order_used[ob]) HIP_TRY(H->StreamWaitEvent(st, s.order_ev[ob], 0));
+            const void* rp = io.rays;
+            void* d_order = static_cast<uint32_t*>(s.d_order) + (size_t)ob * s.order_cap;
+            long long nn = n;
+            float o0[3], o1[3], iv[3];
+            for (int a = 0; a < 3; ++a) { o0[a] = (float)s.vox.omin[a]; o1[a] = (float)s.vox.omax[a]; iv[a] = (float)(1.0 / s.vox.vd[a]); }
+            float bpv = (float)kOrderBins / (3.0f * (float)std::max(1, s.vox.ct));
+            void* oargs[] = {&rp, &nn, &o0[0], &o0[1], &o0[2], &o1[0], &o1[1], &o1[2], &iv[0], &iv[1], &iv[2], &bpv, &d_order};
+            int rc = launch(H, M.cost_order, (unsigned)((n + kOrderWindow - 1) / kOrderWindow), (unsigned)kOrderThreads, 0, st, oargs);
+            if (rc == HARE_OK) {
+                io.order = (const uint32_t*)d_order;
+                rc = launch_on_slot(s, H, kc.f, kc.grid, kc.block, kc.lds, st, io, args, true);
+            }
+            if (H->EventRecord(s.order_ev[ob], st) == hipSuccess) s.order_used[ob] = true;
+            else (void)H->GetLastError();
+            return rc;
+        }
+        return launch_on_slot(s, H, kc.f, kc.grid, kc.block, kc.lds, st, io, args, true);
+    }
+    // persistent kernel K1p
+    if (kc.k == Kern::VoxelProf) {
+        if (!io.ctr) {
+            set_error("hare_shoot: the phase profile needs a counters block");
+            return HARE_E_INVALID;
+        }
+        io.prof = io.ctr + CTR_WORDS;      // phase statistics land in the 17 u64 words FOLLOWING the counters block
+    }
+    return launch_on_slot(s, H, kc.f, kc.grid, kc.block, kc.lds, st, io, args, true);
+}
+
+static int launch_octree(Scene& s, const HipApi* H, int32_t top, ShootIO& io, uint32_t flags, bool flags_only, hipStream_t st)
+{
+    if (!s.oct.built || !s.d_oct_nodes) {
+        set_error("hare_shoot: octree not built");
+        return HARE_E_STATE;
+    }
+    if (s.oct.id_count > s.topos[(size_t)top].P) {   // the reference would index Model[top_index] out of range ("Octree - alt.cs":216)
+        set_error("hare_shoot: the octree holds polygon ids of the last topology that topology " + std::to_string(top) + " does not have");
+        return HARE_E_INVALID;
+    }
+    const DeviceModule& M = *s.module;
+    OctreeArgs g;
+    memset(&g, 0, sizeof g);
+    g.polys = (const PolyRec*)s.d_polys[top];
+    g.cull = (const unsigned char*)s.d_cull[top];
+    g.cf = s.cull_frames[(size_t)top];
+    g.quads = (const QuadRec*)s.d_quads[top];
+    g.nodes = (const OctNode*)s.d_oct_nodes;
+    g.items = (const int32_t*)s.d_oct_items;
+    if (s.opt.octree_tight && (size_t)top < s.d_oct_tight.size() && s.oct_tight_rad > 0) {
+        g.tight = (const float*)s.d_oct_tight[(size_t)top];
+        for (int a = 0; a < 3; ++a) g.tight_mid[a] = s.oct_tight_mid[a];
+        g.tight_rad = s.oct_tight_rad;
+    }
+    g.n_nodes = (int32_t)s.oct.nodes.size();
+    g.max_depth = std::max(1, s.oct_levels);   // frames per lane = interior levels the tree really has (<= maxDepth)
+    if ((size_t)g.max_depth * 64u * 24u > kLdsMax) {   // (24 bytes per level and lane: the simple kernel's frames)   // cannot happen while hare_octree_build caps maxDepth at 24
+        set_error("hare_shoot: octree is deeper than the per-lane frames the kernels keep in LDS (" +
+                  std::to_string(g.max_depth) + " levels)");
+        return HARE_E_UNSUPPORTED;
+    }
+    const ShootPlan kc = plan_shoot(s, &M, HARE_KIND_OCTREE, (size_t)top, io.n, flags, flags_only);
+    if (int rc = take_plan(kc, flags, "hare_shoot: octree kernel missing from code object", io)) return rc;
+    if ((flags & 0x3000u) && io.ctr) io.prof = io.ctr + CTR_WORDS;   // developer timeline (0x2000) / round trace (0x1000)
+    void* args[] = {&g, &io};
+    if (kc.k == Kern::OctPool) {
+        // K2q (octree_pool.hip): frames below the top one in a device scratch block per launch in flight
+        const unsigned cus = (unsigned)std::max(1, M.cu_count);
+        const unsigned stride = 24u + 24u * (unsigned)g.max_depth;
+        const size_t need = (size_t)cus * kOctPoolWaves * kOctPoolSlots * stride;
+        // The scratch ring: the block's previous user must have finished before this launch starts, and the event that says
+        // so must have been RECORDED before a later launch waits on it -- so the lock is held across wait + launch + record
+        // (several host threads may launch on one scene: hare_shoot_batch runs up to 12 chunk streams).
+        std::lock_guard<std::mutex> lk(s.oct_scratch_mu);
+        if (s.oct_scratch_bytes < need) {          // first use, or a deeper tree since: (re)allocate the ring
+            for (int k = 0; k < kOctScratchRing; ++k) {
+                if (s.oct_scratch_ev[k]) (void)H->EventSynchronize(s.oct_scratch_ev[k]);
+                dev_free(H, s.d_oct_scratch[k]);
+            }
+            s.oct_scratch_bytes = 0;
+            for (int k = 0; k < kOctScratchRing; ++k) {
+                HIP_TRY(H->Malloc(&s.d_oct_scratch[k], need));
+                if (!s.oct_scratch_ev[k]) HIP_TRY(H->EventCreateWithFlags(&s.oct_scratch_ev[k], hipEventDisableTiming));
+            }
+            s.oct_scratch_bytes = need;
+            s.oct_scratch_next = 0;
+        }
+        const unsigned seq = s.oct_scratch_next.fetch_add(1);
+        const unsigned ring = seq % (unsigned)kOctScratchRing;
+        unsigned char* scratch = (unsigned char*)s.d_oct_scratch[ring];
+        if (seq >= (unsigned)kOctScratchRing) HIP_TRY(H->StreamWaitEvent(st, s.oct_scratch_ev[ring], 0));
+        unsigned stride_arg = stride;
+        void* qargs[] = {&g, &io, &scratch, &stride_arg};
+        const int rc = launch_on_slot(s, H, kc.f, kc.grid, kc.block, kc.lds, st, io, qargs);
+        if (rc == HARE_OK) HIP_TRY(H->EventRecord(s.oct_scratch_ev[ring], st));
+        return rc;
+    }
+    // K2g, K2p (+ its tail kernel), K2d and the occlusion builds: a block of the scene's octree scratch ring as the plan asks
+    if (kc.k == Kern::OctGroup || kc.k == Kern::OctPersist || kc.k == Kern::OctDense || kc.k == Kern::OctOccl)
+        return launch_on_slot(s, H, kc.f, kc.grid, kc.block, kc.lds, st, io, args, false, kc.oc);
+    return launch(H, kc.f, kc.grid, kc.block, kc.lds, st, args);
+}
+
+static int launch_kdtree(Scene& s, const HipApi* H, int32_t top, ShootIO& io, uint32_t flags, bool flags_only, hipStream_t st)
+{
+    if (!s.kd.built || !s.d_kd_nodes) {
+        set_error("hare_shoot: kd-tree not built");
+        return HARE_E_STATE;
+    }
+    if (s.kd.id_count > s.topos[(size_t)top].P) {
+        set_error("hare_shoot: the kd-tree holds polygon ids of the last topology that topology " + std::to_string(top) + " does not have");
+        return HARE_E_INVALID;
+    }
+    KdArgs g;
+    memset(&g, 0, sizeof g);
+    g.polys = (const PolyRec*)s.d_polys[top];
+    g.quads = (const QuadRec*)s.d_quads[top];
+    g.nodes = (const KdNodeRec*)s.d_kd_nodes;
+    g.items = (const int32_t*)s.d_kd_items;
+    g.n_nodes = (int32_t)s.kd.nodes.size();
+    g.max_depth = s.kd.depth_reached;
+    g.cull = (const unsigned char*)s.d_cull[top];
+    g.cf = s.cull_frames[(size_t)top];
+    if (s.opt.octree_tight && (size_t)top < s.d_kd_tight.size() && s.kd_tight_rad > 0) {     // the option name is the octree's: one switch for both trees
+        g.tight = (const float*)s.d_kd_tight[(size_t)top];
+        for (int a = 0; a < 3; ++a) g.tight_mid[a] = s.kd_tight_mid[a];
+        g.tight_rad = s.kd_tight_rad;
+    }
+    const ShootPlan kc = plan_shoot(s, s.module, HARE_KIND_KDTREE, (size_t)top, io.n, flags, flags_only);
+    if (int rc = take_plan(kc, flags, "hare_shoot: kd-tree kernel missing from code object", io)) return rc;
+    void* args[] = {&g, &io};
+    if (kc.k == Kern::KdDense) {
+        g.dnodes = (const KdDevNode*)s.d_kd_dev[(size_t)top];
+        if ((flags & 0x2000u) && io.ctr) io.prof = io.ctr + CTR_WORDS;   // developer timeline
+        return launch_on_slot(s, H, kc.f, kc.grid, kc.block, kc.lds, st, io, args);
+    }
+    return launch(H, kc.f, kc.grid, kc.block, kc.lds, st, args);
 }
 
 int shoot_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n, void* d_rays,
@@ -685,328 +960,17 @@ int shoot_device_impl(Scene& s, const HipApi* H, int32_t kind, int32_t top, int6
     io.n = n;
     io.flags = flags | (extra ? extra->internal_flags : 0u);        // (internal bits -- SHOOT_RETIRED_SILENT -- come from this library's own loops, never through sanitize_flags)
     io.steps_per_round = 10;
-    io.refill_min_idle = 16;
     io.ray_chunk = 128;
     io.exact_min_parked = 8;
     io.audit_polys = s.topos[top].P;
-    unsigned tune_blocks_per_cu = 0;
-    if (s.opt.tune[0] > 0 && s.opt.tune[1] > 0 && s.opt.tune[1] <= 64 && s.opt.tune[2] > 0) {
-        // developer sweeps (tools/sweep.py, tools/phase_prof.py): steps,refill,chunk,blocks_per_cu,exact;
-        // only blocks_per_cu reaches the production kernels, the rest the profiling build
+    if (tune_given(s.opt)) {       // developer sweeps (refill and blocks_per_cu: plan_shoot)
         io.steps_per_round = s.opt.tune[0];
-        io.refill_min_idle = s.opt.tune[1];
         io.ray_chunk = s.opt.tune[2];
-        tune_blocks_per_cu = s.opt.tune[3] > 0 ? (unsigned)s.opt.tune[3] : 0u;
         if (s.opt.tune[4] > 0 && s.opt.tune[4] <= 64) io.exact_min_parked = s.opt.tune[4];
     }
-    const DeviceModule& M = *s.module;
-    auto no_own_build = [&]() {
-        set_error("hare_shoot: HARE_SHOOT_COUNT_OWN -- the kernel this batch gets has no counting build (the pool kernel of Voxel_Grid, "
-                  "hare_octree_dense from 768 rays per CU, the kd-tree kernel have one)");
-        return HARE_E_UNSUPPORTED;
-    };
-    const unsigned block = 256;
-    const unsigned grid = (unsigned)((n + block - 1) / block);
-    const unsigned cus = (unsigned)std::max(1, M.cu_count);
-
-    if (kind == HARE_KIND_VOXEL) {
-        if (!s.vox.built || s.d_cells.empty()) {
-            set_error("hare_shoot: voxel grid not built");
-            return HARE_E_STATE;
-        }
-        VoxelArgs g;
-        fill_voxel_args(s, top, g);
-        const KernChoice kc = choose_kernel(s, &M, kind, (size_t)top, n, flags, flags_only);
-        if (!kc.f && (flags & HARE_SHOOT_COUNT_OWN)) return no_own_build();
-        if (!kc.f) {
-            set_error(kc.k == Kern::VoxelAudit ? "hare_shoot: the cull audit kernel is missing from the code object"
-                                               : "hare_shoot: kernel missing from code object");
-            return HARE_E_STATE;
-        }
-        void* args[] = {&g, &io};
-        if (kc.k == Kern::VoxelAudit || kc.k == Kern::VoxelCount || kc.k == Kern::VoxelSimple)
-            return launch(H, kc.f, grid, block, 0, st, args);
-        const unsigned lds = (unsigned)((s.occ_words + 3) / 4) * 16u;     // the occupancy bitmap, <= 64 KB (occ_layout)
-        if ((flags & 0x3000u) && d_ctr) io.prof = (unsigned long long*)d_ctr + CTR_WORDS;   // developer timeline (0x2000) / round trace (0x1000)
-        if (kc.k == Kern::VoxelPool) {
-            // K1q (voxel_pool.hip): more rays than lanes, ray state in LDS, one workgroup per CU
-            const unsigned plds = lds + (unsigned)kPoolWaves * (unsigned)kPoolWaveBytes + (g.bocc ? (unsigned)((g.bocc_words + 3) / 4) * 16u : 0u);     // + the block bits of "voxel_skip"
-            // a workgroup per CU whenever the batch has a ray for every wave; the static first chunk is what the batch has for each wave,
-            // in steps of 8, at most 128 (a small batch: few rays per wave, each with several lanes from its second round on)
-            unsigned pgrid = std::min<unsigned>(cus, (unsigned)((n + kPoolWaves - 1) / kPoolWaves));
-            if (pgrid == 0) pgrid = 1;
-            const int64_t per_wave = (n + (int64_t)pgrid * kPoolWaves - 1) / ((int64_t)pgrid * kPoolWaves);
-            io.static_rays = (int32_t)std::max<int64_t>(8, std::min<int64_t>(128, (per_wave + 7) / 8 * 8));
-            if (s.opt.k1p_static_rays > 0) io.static_rays = std::max(8, std::min(1024, s.opt.k1p_static_rays / 8 * 8));   // developer sweeps (tools/k1q_ticket_sweep.py)
-            io.ticket_rays = ticket_rays_for(s, n, true);
-            io.walk_steps = n >= 2 * (int64_t)cus * kPoolWaves * kPoolSlots ? 32 : 16;      // long walk tasks once the batch is two pool fills of the chip (786 432 rays on 256 CUs)
-            if (extra && extra->blocks) { io.blocks = extra->blocks; io.blk_words = extra->blk_words; }      // a cast of the bounce loop: live blocks only
-            if (s.opt.dev && s.opt.dev_order_ptr && !io.blocks) io.order = (const uint32_t*)(uintptr_t)s.opt.dev_order_ptr;
-            // The order in which K1q takes the rays (order_kernels.hip): inside every window of 4 096 consecutive rays, by an estimate of
-            // the walk length -- a pool of rays of similar cost wastes fewer lane-steps (C4 shard -6.8 %, C2 -5.3 % of the kernel's time with
-            // the order given; window_sort_*.log), the batch's own locality stays.  Rule ("voxel_order" 1, the default): batches of PRIMARY
-            // rays -- no exclusion arrays, not a cast of the bounce loop: reflected rays gain nothing and pay for the indirection
-            // (+5 ... +8 %, window_sort_cathedral_bounce5.log) -- from kOrderMinRays: the pass reads every ray once more (12 us per million
-            // rays: half of HBM's rate), which at 1M rays is what the order gains.  The scratch is a block of the scene's order ring
-            // (stream-ordered allocation was tried first: hipMallocAsync / hipFreeAsync cost the stream more than the pass itself).
-            const bool order_rule = io.blocks ? false : s.opt.voxel_order == 2 || (s.opt.voxel_order == 1 && !d_e1 && !d_e2 && !(flags & SHOOT_RETIRED_RAYS) && n >= kOrderMinRays);
-            if (!io.order && order_rule && M.cost_order && (size_t)n <= s.order_cap && (flags & 0xF000u) == 0 && !stream_is_capturing(H, st)) {
-                // a block of the scene's order ring (scene.h), reserved when the grid went to the device: nothing is allocated, freed or
-                // synchronised here.  The block's mutex is held across wait + launches + record (four enqueues)
-                const int ob = (int)(s.order_seq.fetch_add(1) % (unsigned)Scene::kOrderRing);
-                std::lock_guard<std::mutex> olk(s.order_blk_mu[ob]);
-                if (s.order_used[ob]) HIP_TRY(H->StreamWaitEvent(st, s.order_ev[ob], 0));
-                const void* rp = d_rays;
-                void* d_order = static_cast<uint32_t*>(s.d_order) + (size_t)ob * s.order_cap;
-                long long nn = n;
-                float o0[3], o1[3], iv[3];
-                for (int a = 0; a < 3; ++a) { o0[a] = (float)s.vox.omin[a]; o1[a] = (float)s.vox.omax[a]; iv[a] = (float)(1.0 / s.vox.vd[a]); }
-                float bpv = (float)kOrderBins / (3.0f * (float)std::max(1, s.vox.ct));
-                void* oargs[] = {&rp, &nn, &o0[0], &o0[1], &o0[2], &o1[0], &o1[1], &o1[2], &iv[0], &iv[1], &iv[2], &bpv, &d_order};
-                int rc = launch(H, M.cost_order, (unsigned)((n + kOrderWindow - 1) / kOrderWindow), (unsigned)kOrderThreads, 0, st, oargs);
-                if (rc == HARE_OK) {
-                    io.order = (const uint32_t*)d_order;
-                    rc = launch_on_slot(s, H, kc.f, pgrid, 64u * (unsigned)kPoolWaves, plds, st, io, args, true);
-                }
-                if (H->EventRecord(s.order_ev[ob], st) == hipSuccess) s.order_used[ob] = true;
-                else (void)H->GetLastError();
-                return rc;
-            }
-            return launch_on_slot(s, H, kc.f, pgrid, 64u * (unsigned)kPoolWaves, plds, st, io, args, true);
-        }
-        // persistent kernel K1p: a grid that just fills the chip; waves draw ray chunks from a ticket
-#ifndef HARE_OCCL_WAVES_PER_EU
-#define HARE_OCCL_WAVES_PER_EU 4
-#endif
-        unsigned per_cu = kc.k == Kern::VoxelOccl ? HARE_OCCL_WAVES_PER_EU : 4;       // what the occlusion build is compiled for (kernels.hip)
-        if (tune_blocks_per_cu) per_cu = tune_blocks_per_cu;
-        if (lds) per_cu = std::min<unsigned>(per_cu, (unsigned)(kLdsMax / lds));
-        unsigned pgrid = cus * std::max(1u, per_cu);
-        pgrid = std::min<unsigned>(pgrid, (unsigned)((n + 63) / 64 + 3) / 4);
-        if (pgrid == 0) pgrid = 1;
-        io.ticket_rays = ticket_rays_for(s, n, false);
-        // static first chunk per wave (static_chunk_rays): at 262k rays, where 128 left half the grid's waves without work, 0.348 -> 0.239 ms
-        io.static_rays = static_chunk_rays(n, pgrid, false);
-        if (s.opt.k1p_static_rays > 0) io.static_rays = std::max(32, std::min(256, s.opt.k1p_static_rays / 32 * 32));   // developer sweeps
-        unsigned lds_total = lds;
-        if (kc.k == Kern::VoxelProf) {
-            if (!d_ctr) {
-                set_error("hare_shoot: the phase profile needs a counters block");
-                return HARE_E_INVALID;
-            }
-            io.prof = (unsigned long long*)d_ctr + CTR_WORDS;      // phase statistics land in the 17 u64 words FOLLOWING the counters block
-            lds_total += 4u * 18u * 8u;                            // + the profiling build's per-wave statistics
-        }
-        return launch_on_slot(s, H, kc.f, pgrid, block, lds_total, st, io, args, true);
-    }
-    if (kind == HARE_KIND_OCTREE) {
-        if (!s.oct.built || !s.d_oct_nodes) {
-            set_error("hare_shoot: octree not built");
-            return HARE_E_STATE;
-        }
-        if (s.oct.id_count > s.topos[(size_t)top].P) {   // the reference would index Model[top_index] out of range ("Octree - alt.cs":216)
-            set_error("hare_shoot: the octree holds polygon ids of the last topology that topology " + std::to_string(top) + " does not have");
-            return HARE_E_INVALID;
-        }
-        OctreeArgs g;
-        memset(&g, 0, sizeof g);
-        g.polys = (const PolyRec*)s.d_polys[top];
-        g.cull = (const unsigned char*)s.d_cull[top];
-        g.cf = s.cull_frames[(size_t)top];
-        g.quads = (const QuadRec*)s.d_quads[top];
-        g.nodes = (const OctNode*)s.d_oct_nodes;
-        g.items = (const int32_t*)s.d_oct_items;
-        if (s.opt.octree_tight && (size_t)top < s.d_oct_tight.size() && s.oct_tight_rad > 0) {
-            g.tight = (const float*)s.d_oct_tight[(size_t)top];
-            for (int a = 0; a < 3; ++a) g.tight_mid[a] = s.oct_tight_mid[a];
-            g.tight_rad = s.oct_tight_rad;
-        }
-        g.n_nodes = (int32_t)s.oct.nodes.size();
-        g.max_depth = std::max(1, s.oct_levels);   // frames per lane = interior levels the tree really has (<= maxDepth)
-        if ((size_t)g.max_depth * 64u * 24u > kLdsMax) {   // (24 bytes per level and lane: the simple kernel's frames)   // cannot happen while hare_octree_build caps maxDepth at 24
-            set_error("hare_shoot: octree is deeper than the per-lane frames the kernels keep in LDS (" +
-                      std::to_string(g.max_depth) + " levels)");
-            return HARE_E_UNSUPPORTED;
-        }
-        const KernChoice kc = choose_kernel(s, &M, kind, (size_t)top, n, flags, flags_only);
-        if (!kc.f && (flags & HARE_SHOOT_COUNT_OWN)) return no_own_build();
-        if (!kc.f) {
-            set_error("hare_shoot: octree kernel missing from code object");
-            return HARE_E_STATE;
-        }
-        if ((flags & 0x3000u) && d_ctr) io.prof = (unsigned long long*)d_ctr + CTR_WORDS;   // developer timeline (0x2000) / round trace (0x1000)
-        if (kc.k == Kern::OctPool) {
-            // K2q (octree_pool.hip): more rays than lanes; frames below the top one in a device scratch block per launch in flight
-            const unsigned stride = 24u + 24u * (unsigned)g.max_depth;
-            unsigned pgrid = std::min<unsigned>(cus, (unsigned)((n + 64 * kOctPoolWaves - 1) / (64 * kOctPoolWaves)));
-            if (pgrid == 0) pgrid = 1;
-            const size_t need = (size_t)cus * kOctPoolWaves * kOctPoolSlots * stride;
-            // The scratch ring: the block's previous user must have finished before this launch starts, and the event that says
-            // so must have been RECORDED before a later launch waits on it -- so the lock is held across wait + launch + record
-            // (several host threads may launch on one scene: hare_shoot_batch runs up to 12 chunk streams).
-            std::lock_guard<std::mutex> lk(s.oct_scratch_mu);
-            if (s.oct_scratch_bytes < need) {          // first use, or a deeper tree since: (re)allocate the ring
-                for (int k = 0; k < kOctScratchRing; ++k) {
-                    if (s.oct_scratch_ev[k]) (void)H->EventSynchronize(s.oct_scratch_ev[k]);
-                    dev_free(H, s.d_oct_scratch[k]);
-                }
-                s.oct_scratch_bytes = 0;
-                for (int k = 0; k < kOctScratchRing; ++k) {
-                    HIP_TRY(H->Malloc(&s.d_oct_scratch[k], need));
-                    if (!s.oct_scratch_ev[k]) HIP_TRY(H->EventCreateWithFlags(&s.oct_scratch_ev[k], hipEventDisableTiming));
-                }
-                s.oct_scratch_bytes = need;
-                s.oct_scratch_next = 0;
-            }
-            const unsigned seq = s.oct_scratch_next.fetch_add(1);
-            const unsigned ring = seq % (unsigned)kOctScratchRing;
-            unsigned char* scratch = (unsigned char*)s.d_oct_scratch[ring];
-            if (seq >= (unsigned)kOctScratchRing) HIP_TRY(H->StreamWaitEvent(st, s.oct_scratch_ev[ring], 0));
-            io.ticket_rays = s.opt.ticket_rays > 0 ? std::max(8, std::min(4096, s.opt.ticket_rays)) : 32;
-            unsigned stride_arg = stride;
-            void* qargs[] = {&g, &io, &scratch, &stride_arg};
-            const int rc = launch_on_slot(s, H, kc.f, pgrid, 64u * (unsigned)kOctPoolWaves, (unsigned)kOctPoolWaves * (unsigned)kOctPoolWaveBytes, st, io, qargs);
-            if (rc == HARE_OK) HIP_TRY(H->EventRecord(s.oct_scratch_ev[ring], st));
-            return rc;
-        }
-        // K2g (octree_group.hip) on rays [off, off + m): workgroups of four waves, eight rays per wave; LDS = the groups' stacks and
-        // pending lists (hare_device.h).  A ray's stack can hold 7 x levels + 8 entries (the reference's LIFO, "Octree - alt.cs":268-272);
-        // what LDS does not hold spills to a block of the scene's octree scratch ring
-        auto launch_group = [&](int64_t off, int64_t m, hipStream_t stream) -> int {
-            ShootIO sub = io;
-            sub.rays = io.rays + off;
-            sub.out = io.out + off;
-            if (io.excl1) sub.excl1 = io.excl1 + off;
-            if (io.excl2) sub.excl2 = io.excl2 + off;
-            sub.n = m;
-            const unsigned glds = 4u * (unsigned)kGroupWaveBytes;
-            unsigned per_cu = std::min((unsigned)HARE_K2G_WAVES_PER_EU, std::max(1u, (unsigned)(kLdsMax / glds)));
-            unsigned pgrid = cus * per_cu;
-            pgrid = std::min<unsigned>(pgrid, (unsigned)((m + 7) / 8 + 3) / 4);            // a wave per eight rays at least
-            if (pgrid == 0) pgrid = 1;
-            sub.ticket_rays = s.opt.ticket_rays > 0 ? std::max(8, std::min(4096, s.opt.ticket_rays)) : 8;    // swept 8 / 16 / 32 / 64: 8 (1M rays), flat at 4M
-            // static first chunk per wave: what the batch has for every wave, at most 32 rays (four rounds of eight), at least 8
-            const int64_t per_wave = m / ((int64_t)pgrid * 4);
-            sub.static_rays = (int32_t)std::max<int64_t>(8, std::min<int64_t>(32, per_wave / 2 / 8 * 8));
-            if (s.opt.k2p_static_rays > 0) sub.static_rays = std::max(8, std::min(256, s.opt.k2p_static_rays / 8 * 8));   // developer sweeps
-            OctScratch oc;
-            oc.spill_entries = std::max(0, 7 * g.max_depth + 8 - kGroupStack);
-            void* a[] = {&g, &sub};
-            return launch_on_slot(s, H, M.octree_group, pgrid, 256, glds, stream, sub, a, false, oc);
-        };
-        // K2p (+ K2t behind it) or the occlusion build on rays [off, off + m)
-        auto launch_persist = [&](hipFunction_t f, bool closest_hit, int64_t off, int64_t m, hipStream_t stream) -> int {
-            ShootIO sub = io;
-            sub.rays = io.rays + off;
-            if (io.out) sub.out = io.out + off;
-            if (io.excl1) sub.excl1 = io.excl1 + off;
-            if (io.excl2) sub.excl2 = io.excl2 + off;
-            if (io.tmax) sub.tmax = io.tmax + off;
-            if (io.occluded) sub.occluded = io.occluded + off;
-            sub.n = m;
-            // the kernel is compiled for HARE_K2P_WAVES_PER_EU waves per SIMD (= workgroups of 4 waves per CU); a persistent
-            // grid must not exceed what is resident, or the extra workgroups start when the others have finished
-            // 20 bytes x levels x 256 lanes per workgroup (interval + child word); the dense build: + its pending survivors and tables
-            const bool dense_k = f != nullptr && (f == M.octree_dense || f == M.octree_dense_own || f == M.octree_occl);   // (the flags-only kernel is K2d's OCC build)
-            const unsigned plds = (unsigned)g.max_depth * 256u * 20u + (dense_k ? kOctDenseExtra : 0u);
-            unsigned per_cu = std::min((unsigned)(dense_k ? HARE_K2D_WAVES_PER_EU : HARE_K2P_WAVES_PER_EU), std::max(1u, (unsigned)(kLdsMax / plds)));
-            unsigned pgrid = cus * per_cu;
-            pgrid = std::min<unsigned>(pgrid, (unsigned)((m + 63) / 64 + 3) / 4);      // (a wave for every 32 rays of a small batch was measured: no better)
-            if (pgrid == 0) pgrid = 1;
-            // an octree ray costs ~10x a voxel ray: ticket atomics never bind.  K2p: 32 rays; K2d finishes rays sooner and likes 16
-            // (8 / 16 / 24 / 32 rays per ticket: 1M rays 478 / 502 / 466 / 489 Mrays/s, 1.5M 553 / 570 / 569 / 563, 524k 353 / 354 / 348 / 346)
-            sub.ticket_rays = s.opt.ticket_rays > 0 ? std::max(8, std::min(4096, s.opt.ticket_rays)) : (dense_k ? 16 : 32);
-            // K2d refills a wave when this many of its lanes are idle: 16 on long batches; on short ones (a wave draws only a few tickets) 32 --
-            // swept (k2d_refill_by_size.log), 16 / 24 / 32 / 48 idle lanes: 196 608 rays 247 / 249 / 251 / 251 Mrays/s, 262 144 317 / 336 / 341 / 340,
-            // 393 216 489 / 495 / 471 / 395, 524 288 559 / 556 / 558 / 530, 655 360 662 / 649 / 624 / 587, 1M 775 / 775 / 757 / 676
-            if (dense_k && !(s.opt.tune[0] > 0 && s.opt.tune[1] > 0)) sub.refill_min_idle = m < (int64_t)cus * kK2dShortBatchPerCu ? 32 : 16;
-            sub.static_rays = static_chunk_rays(m, pgrid, true, dense_k, dense_k);    // K2p: 262k rays 2.607 -> 1.861 ms, 524k 2.569 -> 2.336; K2d: half
-                                                                             // the share (393k rays 338 -> 418 Mrays/s, 524k 421 -> 474, 655k 393 -> 515)
-            if (s.opt.k2p_static_rays > 0) sub.static_rays = std::max(8, std::min(256, s.opt.k2p_static_rays / 8 * 8));   // developer sweeps
-            void* a[] = {&g, &sub};
-            // The closest-hit kernel hands rays to a tail kernel (the occlusion build keeps them).  Rule: K2g-tail takes EVERY ray a wave
-            // still walks when the tickets run dry (option "octree_tail" 2, the default); K2t takes a wave's last sixteen after 64 rounds (1)
-            OctScratch oc;
-            // K2d hands nothing over by the rule: its dense passes put the whole wave on whatever entries its last rays hold, which is what
-            // a tail kernel was for (1M rays: no tail 485 Mrays/s, K2g-tail after 8 / 16 / 32 / 64 / 96 rounds 428 / 451 / 465 / 454 / 463, K2t 464)
-            const bool dense = dense_k;
-            if (closest_hit && s.opt.octree_tail != 0 && !(dense && s.opt.k2p_tail_max == 0 && s.opt.k2p_tail_patience < 0)) {
-                oc.tail_levels = g.max_depth;
-                oc.group_tail = s.opt.octree_tail == 2 && M.octree_group_tail != nullptr;
-                oc.tail_max = oc.group_tail ? 64 : kOctTailMax;
-                // K2g-tail: every ray the wave still holds 32 rounds after its tickets ran dry (swept: (64, 0) 345 Mrays/s, (64, 8) 367,
-                // (64, 24..48) 391-396, (64, 64) 377, (64, 128) 347; (24..40, x) the same within 1 %; K2t (16, 64) 384)
-                oc.tail_patience = oc.group_tail ? 32 : HARE_K2P_TAIL_PATIENCE;
-                if (s.opt.k2p_tail_max > 0) oc.tail_max = std::min(64, s.opt.k2p_tail_max);          // developer sweeps
-                if (s.opt.k2p_tail_patience >= 0) oc.tail_patience = s.opt.k2p_tail_patience;
-                if (oc.group_tail) oc.spill_entries = std::max(0, 7 * g.max_depth + 8 - kGroupStack);
-            }
-            return launch_on_slot(s, H, f, pgrid, 256, plds, stream, sub, a, false, oc);
-        };
-        if (kc.k == Kern::OctGroup) return launch_group(0, n, st);
-        if (kc.k == Kern::OctPersist || kc.k == Kern::OctDense || kc.k == Kern::OctOccl) return launch_persist(kc.f, kc.k != Kern::OctOccl, 0, n, st);
-        void* args[] = {&g, &io};
-        // one frame per interior level and lane in LDS: 24 bytes x levels x block
-        const unsigned levels = (unsigned)g.max_depth;
-        unsigned ob = 256;
-        while (ob > 64 && (size_t)levels * ob * 24 > 64 * 1024) ob >>= 1;   // ob = 64: up to 106 levels fit 160 KB
-        const unsigned lds = levels * ob * 24;
-        return launch(H, kc.f, (unsigned)((n + ob - 1) / ob), ob, lds, st, args);
-    }
-    if (kind == HARE_KIND_KDTREE) {
-        if (!s.kd.built || !s.d_kd_nodes) {
-            set_error("hare_shoot: kd-tree not built");
-            return HARE_E_STATE;
-        }
-        if (s.kd.id_count > s.topos[(size_t)top].P) {
-            set_error("hare_shoot: the kd-tree holds polygon ids of the last topology that topology " + std::to_string(top) + " does not have");
-            return HARE_E_INVALID;
-        }
-        KdArgs g;
-        memset(&g, 0, sizeof g);
-        g.polys = (const PolyRec*)s.d_polys[top];
-        g.quads = (const QuadRec*)s.d_quads[top];
-        g.nodes = (const KdNodeRec*)s.d_kd_nodes;
-        g.items = (const int32_t*)s.d_kd_items;
-        g.n_nodes = (int32_t)s.kd.nodes.size();
-        g.max_depth = s.kd.depth_reached;
-        g.cull = (const unsigned char*)s.d_cull[top];
-        g.cf = s.cull_frames[(size_t)top];
-        if (s.opt.octree_tight && (size_t)top < s.d_kd_tight.size() && s.kd_tight_rad > 0) {     // the option name is the octree's: one switch for both trees
-            g.tight = (const float*)s.d_kd_tight[(size_t)top];
-            for (int a = 0; a < 3; ++a) g.tight_mid[a] = s.kd_tight_mid[a];
-            g.tight_rad = s.kd_tight_rad;
-        }
-        const KernChoice kkc = choose_kernel(s, &M, kind, (size_t)top, n, flags, flags_only);
-        hipFunction_t f = kkc.f;
-        if (!f && (flags & HARE_SHOOT_COUNT_OWN)) return no_own_build();
-        if (!f) {
-            set_error("hare_shoot: kd-tree kernel missing from code object");
-            return HARE_E_STATE;
-        }
-        if (kkc.k == Kern::KdDense) {
-            // K3d: a grid that just fills the chip (what its LDS -- (depth + 2) stack entries of 8 bytes per lane -- allows per CU, at most
-            // HARE_K3D_WAVES_PER_EU workgroups); static first chunk and tickets as K2d
-            g.dnodes = (const KdDevNode*)s.d_kd_dev[(size_t)top];
-            const unsigned klds = kd_dense_lds(g.max_depth);
-            unsigned per_cu = std::min((unsigned)HARE_K3D_WAVES_PER_EU, std::max(1u, (unsigned)(kLdsMax / klds)));
-            unsigned pgrid = cus * per_cu;
-            pgrid = std::min<unsigned>(pgrid, (unsigned)((n + 63) / 64 + 3) / 4);
-            if (pgrid == 0) pgrid = 1;
-            io.ticket_rays = s.opt.ticket_rays > 0 ? std::max(8, std::min(4096, s.opt.ticket_rays)) : 16;
-            io.static_rays = static_chunk_rays(n, pgrid, true, true);
-            if (s.opt.k2p_static_rays > 0) io.static_rays = std::max(32, std::min(256, s.opt.k2p_static_rays / 32 * 32));   // developer sweeps
-            if ((flags & 0x2000u) && d_ctr) io.prof = (unsigned long long*)d_ctr + CTR_WORDS;   // developer timeline
-            void* kargs[] = {&g, &io};
-            return launch_on_slot(s, H, f, pgrid, 256, klds, st, io, kargs);
-        }
-        // node stack in LDS: at most depth + 2 entries per lane
-        const unsigned slots = (unsigned)g.max_depth + 2;
-        const unsigned kb = 256;
-        const unsigned lds = slots * kb * 4;
-        void* args[] = {&g, &io};
-        return launch(H, f, (unsigned)((n + kb - 1) / kb), kb, lds, st, args);
-    }
+    if (kind == HARE_KIND_VOXEL) return launch_voxel(s, H, top, io, flags, flags_only, st, extra);
+    if (kind == HARE_KIND_OCTREE) return launch_octree(s, H, top, io, flags, flags_only, st);
+    if (kind == HARE_KIND_KDTREE) return launch_kdtree(s, H, top, io, flags, flags_only, st);
     set_error("hare_shoot: unknown partition kind");
     return HARE_E_INVALID;
 }

@@ -115,16 +115,14 @@ struct KdHost {
 struct DeviceModule {
     hipModule_t mod = nullptr;
     hipFunction_t voxel_tri = nullptr, voxel_quad = nullptr, voxel_count = nullptr;
-    hipFunction_t voxel_persist_tri = nullptr, voxel_persist_quad = nullptr;
-    hipFunction_t voxel_persist_tri_g = nullptr, voxel_persist_quad_g = nullptr;
-    hipFunction_t voxel_pool_tri = nullptr, voxel_pool_quad = nullptr, voxel_pool_tri_g = nullptr, voxel_pool_quad_g = nullptr;
-    // counting builds of the production kernels (HARE_SHOOT_COUNT_OWN)
-    hipFunction_t voxel_pool_tri_ov = nullptr, voxel_pool_quad_ov = nullptr, voxel_pool_tri_g_ov = nullptr, voxel_pool_quad_g_ov = nullptr;   // scene option "voxel_overlap"
-    hipFunction_t voxel_pool_tri_own = nullptr, voxel_pool_quad_own = nullptr, voxel_pool_tri_g_own = nullptr, voxel_pool_quad_g_own = nullptr;
+    // the voxel kernel families, [family][coarse bitmap (the _g builds)][quadrilaterals]; kVoxelKernelNames (device_scene.cpp) names them
+    // in the same order and get_module loads them from it
+    enum VoxelFamily { Pool, PoolOv /* scene option "voxel_overlap" */, PoolOwn /* the counting build, HARE_SHOOT_COUNT_OWN */, Persist, Occl, Bounce, kFamilies };
+    hipFunction_t voxel[kFamilies][2][2] = {};
     hipFunction_t octree_dense_own = nullptr;
     hipFunction_t cost_order = nullptr;                                    // order_kernels.hip
     hipFunction_t kdtree_dense = nullptr, kdtree_dense_own = nullptr, kdtree_occl = nullptr;      // K3d (kdtree_dense.hip) and its counting build
-    hipFunction_t voxel_bounce_tri = nullptr, voxel_bounce_quad = nullptr, voxel_bounce_tri_g = nullptr, voxel_bounce_quad_g = nullptr, counters_sum = nullptr;
+    hipFunction_t counters_sum = nullptr;
     hipFunction_t octree = nullptr, octree_count = nullptr, octree_persist = nullptr, octree_pool = nullptr, octree_tail = nullptr, octree_group = nullptr, octree_group_tail = nullptr, octree_dense = nullptr;
     hipFunction_t kdtree = nullptr, kdtree_count = nullptr;
     hipFunction_t reflect = nullptr, occlusion = nullptr;
@@ -137,7 +135,7 @@ struct DeviceModule {
     hipFunction_t direct_emit = nullptr, direct_deposit[2] = {};           // direct.hip ([1]: the _dir form)
     hipFunction_t image_mirror = nullptr, image_pairs = nullptr, image_deposit[2] = {};   // image.hip ([1]: the _dir form)
     hipFunction_t image2_mirror = nullptr, image2_cands = nullptr, image2_paths = nullptr, image2_deposit[2] = {};   // image2.hip ([1]: the _dir form)
-    hipFunction_t voxel_occl_tri = nullptr, voxel_occl_quad = nullptr, voxel_occl_tri_g = nullptr, voxel_occl_quad_g = nullptr, octree_occl = nullptr, octree_occl_any = nullptr;
+    hipFunction_t octree_occl = nullptr, octree_occl_any = nullptr;
     hipFunction_t events_pack_slim = nullptr;
     hipFunction_t block_occ = nullptr;                                     // build_kernels.hip: hare_block_occ
     hipFunction_t live_blocks = nullptr;                                   // kernels.hip: hare_live_blocks (the bounce loop's block list)
@@ -150,6 +148,7 @@ struct DeviceModule {
     hipFunction_t ob_count = nullptr, ob_fill = nullptr;
     int cu_count = 0;
 };
+extern const char* const kVoxelKernelNames[DeviceModule::kFamilies][2][2];
 
 // Makes `device` the calling thread's current HIP device for the guard's lifetime and restores the previous one
 // afterwards: a host that juggles several devices (torch device guards, one scene per GPU) must find its current
