@@ -34,7 +34,7 @@ L_SPECIAL = (0.0, -0.0, -1.0, -0.5, np.nan, np.inf, -np.inf, 1e300)
 @dataclasses.dataclass
 class Case:
     name: str
-    scene: tuple                         # ("shoebox",) | ("room",) | ("soup", n_tri, n_quad, seed)
+    scene: tuple                         # ("shoebox",) | ("room",) | ("soup", n_tri, n_quad, seed) | ("box", sx, sy, sz, tx, ty, tz)
     partition: tuple                     # ("voxel", domain) | ("octree", depth, max_polys) | ("kdtree", depth, max_polys)
     rays: np.ndarray                     # [n, 6]
     bounces: int
@@ -115,6 +115,11 @@ def mesh_of(scene):
             _MESHES[scene] = (m.verts, m.nverts, m.size)
         elif scene[0] == "room":
             _MESHES[scene] = partition_room()
+        elif scene[0] == "box":          # the shoebox mapped by a per-axis scale and a shift: x' = x * s + t; size is the scaled one
+            m = scenes.shoebox()
+            s, t = np.array(scene[1:4], np.float64), np.array(scene[4:7], np.float64)
+            used = np.arange(4)[None, :, None] < m.nverts[:, None, None]
+            _MESHES[scene] = (np.ascontiguousarray(np.where(used, m.verts * s + t, 0.0)), m.nverts, tuple(np.asarray(m.size) * s))
         else:
             _MESHES[scene] = soup(n_tri=scene[1], n_quad=scene[2], seed=scene[3])
     return _MESHES[scene]
@@ -141,23 +146,27 @@ _REFERENCES = {}
 REFERENCES_KEPT = 160                    # the fixed sets and their rules-off variants together are about a hundred
 
 
-def reference(case, counts=False, nthreads=16, keep=False):
+def reference(case, counts=False, nthreads=16, keep=False, candidates_fn=None):
     """tests.receive_ref.receive_loop on the case: dict with hist, det, state and rays as that function returns them, events (the last
     cast's), stats (the rain's eligible / occluded queries), tallies (receive_ref.TALLIES), counts [K, n_bins] (on request, else None),
     per_cast (live rays, the rules' retirements and the roulette's survivors per cast) and share ((candidate pairs, pairs) per receiver
-    step of a map; empty without one).  keep: the result is kept, and served from then on, under the case's name and what separates
+    step of a map; empty without one) and map_tallies (tests.receive_map_ref.MAP_TALLIES, the classes of the visit rule the casts went
+    through, summed over the casts; empty without a map).  candidates_fn: a visit rule to run in place of
+    tests.receive_map_ref.candidates (a test's variant of the rule; never kept).  keep: the result is kept, and served from then on, under the case's name and what separates
     two cases of one name (`without` variants) -- for the fixed sets, whose tests share it and leave it unchanged; the oldest of more
     than REFERENCES_KEPT goes."""
     key = (case.name, case.time_limit, case.floor_bits, case.roulette, case.map_cell, counts)
-    if key in _REFERENCES:
+    assert candidates_fn is None or not keep
+    if key in _REFERENCES and candidates_fn is None:
         return _REFERENCES[key]
     To, o = oracle_of(case)
-    stats, tallies, last, per_cast, share = {}, {}, [], {}, []
+    stats, tallies, last, per_cast, share, map_tallies = {}, {}, [], {}, [], {}
     cnt = np.zeros((case.K, case.n_bins), np.int64) if counts else None
     visit = None
     if case.map_cell is not None:
         from tests.receive_map_ref import build_grid, candidates          # that module builds its cases from this one's
-        visit = functools.partial(candidates, build_grid(case.centers, case.radii, case.map_cell))
+        visit = functools.partial(candidates_fn or candidates, build_grid(case.centers, case.radii, case.map_cell), tallies=map_tallies, centers=case.centers,
+                                  radii=case.radii)
     hist, det, state, rays = receive_loop(po, To, o, case.rays, case.bounces, case.centers, case.radii, case.n_bins, case.bin_len, case.frac_bits,
                                           alpha=case.alpha, sigma=case.sigma if case.mode != "specular" else None, seed=case.seed,
                                           state_in=case.state_in, rain=case.mode == "rain", directional=case.directional, stats=stats,
@@ -165,7 +174,7 @@ def reference(case, counts=False, nthreads=16, keep=False):
                                           time_limit=case.time_limit, floor_bits=case.floor_bits, roulette=case.roulette, visit=visit,
                                           per_cast=per_cast, share=share)
     out = dict(hist=hist, det=det, state=state, rays=rays, events=last[0], stats=stats, tallies=tallies, counts=cnt, per_cast=per_cast,
-               share=share)
+               share=share, map_tallies=map_tallies)
     if keep:
         if len(_REFERENCES) >= REFERENCES_KEPT:
             del _REFERENCES[next(iter(_REFERENCES))]

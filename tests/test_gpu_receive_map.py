@@ -1,7 +1,8 @@
 """Receiver maps on the MI355X (include/hare_hip.h, "receivers", "Receiver maps"): every case of tests.receive_map_ref.map_cases() --
 K = 1 .. 65 536, batch sizes about a wave, a workgroup and 4096, B = 1, 3, 8, one to four casts, the four _map kernels, the three
 partitions, shoebox, partition room and an open soup, the six map shapes, states with NaN and infinities beside directions scaled by
-2^-600 (NaN and infinite RAYS meet the visit rule in tests/test_receive_map_api.py, on the restatement: no cast is shot with them here), the time limit and the floor with roulette -- through Receive_batch and, for a subset, receive_device on the caller's buffers
+2^-600 (NaN and infinite RAYS reach the device in tests/test_gpu_receive_map_edges.py and tests/test_gpu_receive_map_sweep.py, with the
+visit rule's other edges; no cast is shot with them here), the time limit and the floor with roulette -- through Receive_batch and, for a subset, receive_device on the caller's buffers
 and the sharded call over two scenes.  Histogram, detections and final state (for the device call also the rays and the last events)
 equal the numpy restatement (tests/receive_ref.py with tests/receive_map_ref.py's visit rule) byte for byte; of a NaN only that it is
 one is compared.  Nothing is skipped or redrawn.  tests/test_receive_map_api.py proves with the restatement alone that the cases are not vacuous.  Further: the identity (the
