@@ -48,6 +48,18 @@ inline void check(int rc)
     throw std::runtime_error(msg);
 }
 
+// ambisonic order of a directional histogram (include/hare_hip.h, "Higher orders"): the channels per word and the calls' flag bits
+inline int Channels(int order)
+{
+    if (order < 1 || order > 3) throw std::invalid_argument("order must be 1, 2 or 3");
+    return order == 1 ? 4 : (order == 2 ? 9 : 16);
+}
+inline uint32_t ChannelFlags(bool directional, int order = 1)
+{
+    (void)Channels(order);
+    return (directional ? HARE_RECEIVE_DIRECTIONAL : 0u) | (order == 2 ? HARE_RECEIVE_ORDER2 : (order == 3 ? HARE_RECEIVE_ORDER3 : 0u));
+}
+
 class Topology {
 public:
     std::vector<double> verts;     // P x 4 x 3
@@ -156,6 +168,12 @@ public:
     // state: (1 + B) x rays.size() (L, then E per band); rain: diffuse rain (HARE_RECEIVE_DIFFUSE_RAIN).  Returns the hits over all casts.  Sizes are checked here: the library reads and
     // writes as many values as the scene says, whatever the vectors hold.  directional (HARE_RECEIVE_DIRECTIONAL): hist is K x n_bins x B x 4,
     // channel innermost: W (the omni word), then X, Y, Z as int64 in two's complement (positive for sound arriving from +x, +y, +z).
+    // order 2 or 3 beside it (HARE_RECEIVE_ORDER2 / HARE_RECEIVE_ORDER3; the header's "Higher orders"): hist is K x n_bins x B x 9 or x 16,
+    // the four channels first, then ACN 4 .. 8 or 4 .. 15 in SN3D, int64 like X, Y, Z.  A third-order room response of a burst:
+    //     std::vector<uint64_t> hist, det;
+    //     grid.ReceiveOrder(rays, 0, 8, 512, 0.25, 40, hist, det, nullptr, nullptr, false, /*directional=*/true, /*order=*/3);
+    //     int64_t y6 = (int64_t)hist[((k * 512 + bin) * B + b) * Hare::Geometry::Channels(3) + 6];      // ACN 6 of receiver k, bin, band b
+    // ChannelFlags(directional, order) gives the bits for the calls on native() that take `flags` (hare_receive_source, hare_direct_device ...).
     // Termination (the header's section of that name).  HARE_RECEIVE_TIME_LIMIT (512u, a flag of hare_receive_batch on native(); Receive
     // below does not set it): a ray whose path L has reached n_bins * bin_len after a hit is retired; hist and detections[2k] are
     // those of the call without it, detections[2k + 1] and the final state differ.  The energy
@@ -195,15 +213,22 @@ public:
                      std::vector<uint64_t>& hist, std::vector<uint64_t>& detections, const std::vector<double>* state_in = nullptr,
                      std::vector<double>* state_out = nullptr, bool rain = false, bool directional = false)
     {
+        return ReceiveOrder(rays, top_index, bounces, n_bins, bin_len, frac_bits, hist, detections, state_in, state_out, rain, directional, 1);
+    }
+    // Receive at ambisonic order 1, 2 or 3 (2, 3: only with directional)
+    uint64_t ReceiveOrder(const std::vector<hare_ray>& rays, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,
+                          std::vector<uint64_t>& hist, std::vector<uint64_t>& detections, const std::vector<double>* state_in,
+                          std::vector<double>* state_out, bool rain, bool directional, int order)
+    {
         const int64_t K = GetOption("receivers"), B = Bands(top_index);
         const size_t n_state = (size_t)(1 + B) * rays.size();
         if (state_in && state_in->size() != n_state) throw std::invalid_argument("Receive: state_in must hold (1 + B) x rays.size() values");
-        hist.assign((size_t)(K * (n_bins > 0 ? n_bins : 0) * B * (directional ? 4 : 1)), 0);
+        hist.assign((size_t)(K * (n_bins > 0 ? n_bins : 0) * B * (directional ? Channels(order) : 1)), 0);
         detections.assign((size_t)(2 * K), 0);
         if (state_out) state_out->assign(n_state, 0.0);
         hare_counters c{};
         check(hare_receive_batch(scene_, kind_, top_index, (int64_t)rays.size(), rays.data(), nullptr, nullptr, bounces,
-                                 (rain ? HARE_RECEIVE_DIFFUSE_RAIN : 0u) | (directional ? HARE_RECEIVE_DIRECTIONAL : 0u), n_bins, bin_len,
+                                 (rain ? HARE_RECEIVE_DIFFUSE_RAIN : 0u) | ChannelFlags(directional, order), n_bins, bin_len,
                                  frac_bits, state_in ? state_in->data() : nullptr, state_out ? state_out->data() : nullptr, hist.data(),
                                  detections.data(), &c));
         return c.hits;

@@ -116,6 +116,11 @@ namespace Hare
             // the same calls, only together with HARE_RECEIVE_IMAGE: the second-order specular reflections are one deposit per (receiver, polygon,
             // polygon) path and in cast 2 the rays reflected specularly twice detect nothing ("Image sources (second order)")
             public const uint HARE_RECEIVE_IMAGE2 = 65536;
+            // wherever HARE_RECEIVE_DIRECTIONAL is accepted, only together with it and one of the two at most: nine (ambisonic orders 0..2) or
+            // sixteen (orders 0..3) channels per histogram word -- W, X, Y, Z, then ACN 4 .. 8 or 4 .. 15 in SN3D as int64, evaluated on the
+            // same arrival vector (include/hare_hip.h, "Higher orders").  0x20000 and 0x100000
+            public const uint HARE_RECEIVE_ORDER2 = 131072;
+            public const uint HARE_RECEIVE_ORDER3 = 1048576;
 
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr hare_last_error();
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int hare_device_count(out int count);

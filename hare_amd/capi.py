@@ -24,6 +24,18 @@ RECEIVE_TIME_LIMIT = 512            # hare_receive_*: retire a ray whose path ha
 RECEIVE_DIRECT = 1024               # hare_receive_source* / hare_receive_device: the direct sound deposited per receiver, cast 0 not detected ("Direct sound")
 RECEIVE_IMAGE = 2048                # the same calls: first-order specular reflections deposited per (receiver, polygon) pair, cast 1 not detected for specular rays ("Image sources (first order)")
 RECEIVE_IMAGE2 = 65536              # the same calls, only with RECEIVE_IMAGE: second-order specular reflections deposited per (receiver, polygon, polygon) path ("Image sources (second order)")
+RECEIVE_ORDER2 = 131072             # wherever RECEIVE_DIRECTIONAL is accepted, only with it: nine channels per histogram word ("Higher orders")
+RECEIVE_ORDER3 = 1048576            # the same, sixteen channels; not together with RECEIVE_ORDER2
+ORDER_CHANNELS = {1: 4, 2: 9, 3: 16}        # channels of a directional histogram by ambisonic order
+
+
+def channel_flags(directional, order: int = 1) -> int:
+    """The flags of `directional=` and `order=` (1, 2 or 3): an order above 1 sets its bit whether or not directional is set -- the
+    library refuses it without (HARE_E_INVALID)."""
+    if order not in ORDER_CHANNELS:
+        raise ValueError("order must be 1, 2 or 3")
+    return (RECEIVE_DIRECTIONAL if directional else 0) | {1: 0, 2: RECEIVE_ORDER2, 3: RECEIVE_ORDER3}[order]
+
 
 RAY_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("dx", "<f8"), ("dy", "<f8"), ("dz", "<f8")])
 XEVENT_DTYPE = np.dtype(

@@ -333,7 +333,7 @@ int receive_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind
         char* const d_cross = d_sums + sums_bytes;
         char* const d_weight = d_cross + cross_bytes;
         if (weight_bytes) HIP_TRY(H->MemcpyAsync(d_weight, red->weight, weight_bytes, hipMemcpyHostToDevice, st));
-        if (int rc = reduce_enqueue(s, H, (int32_t)K, job.n_bins, B, (job.flags & HARE_RECEIVE_DIRECTIONAL) ? 4 : 1, d_hist,
+        if (int rc = reduce_enqueue(s, H, (int32_t)K, job.n_bins, B, receive_channels(job.flags), d_hist,
                                     weight_bytes ? d_weight : nullptr, *red, d_sums, d_cross, st))
             return rc;
         if (sums_bytes) HIP_TRY(H->MemcpyAsync(job.sums, d_sums, sums_bytes, hipMemcpyDeviceToHost, st));
@@ -578,7 +578,7 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
     }
     if (red) {      // the _reduced calls: the reduction's own checks, at the histogram's shape
         const size_t K1 = std::max<size_t>(1, s0->rcv.size() / 4), KB = K1 * (size_t)scene_bands(*s0, top_index);
-        if (int rc = reduce_check_spec(who, (int64_t)K1, n_bins, scene_bands(*s0, top_index), (flags & HARE_RECEIVE_DIRECTIONAL) ? 4 : 1, *red)) return rc;
+        if (int rc = reduce_check_spec(who, (int64_t)K1, n_bins, scene_bands(*s0, top_index), receive_channels(flags), *red)) return rc;
         if ((red->n_win > 0 && !sums) || (red->n_lev > 0 && !cross)) {
             set_error(std::string(who) + ": null sums / crossings");
             return HARE_E_INVALID;

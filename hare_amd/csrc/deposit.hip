@@ -15,13 +15,14 @@ static __device__ __forceinline__ double path_vector(double cx, double cy, doubl
 }
 
 // One visible path from S = (sx, sy, sz) to receiver k: the detection counter and, when the arrival falls in a bin, B histogram words (4 B in
-// the _dir form: the energy and its three arrival-axis moments).  Every add is an atomic: several paths of a call can land in one word.
+// the _dir form: the energy and its three arrival-axis moments; 9 B and 16 B in the _dir2 and _dir3 forms, the higher orders' channels of the
+// same arrival vector behind them: C is the channel count).  Every add is an atomic: several paths of a call can land in one word.
 //   gain_vec(gx, gy, gz): the direction in which the path leaves the source, for the directivity lookup.  It is handed v = c_k - S, which
 //     the direct sound leaves as it is, and is asked only when the path is binned and the source has a table (the image deposits read a
 //     shadow ray for it);
 //   refl(b): the path's reflectance in band b.  The band's energy is (((power * g) * refl(b)) * fw) * scale in this association; the direct
 //     sound passes the literal 1.0, a multiplication that is exact for every operand (no fast-math here) and that the compiler drops.
-template <bool DIR, class GainVec, class Refl>
+template <int C, class GainVec, class Refl>
 static __device__ __forceinline__ void deposit_tail(const DepositArgs& a, int k, double sx, double sy, double sz, GainVec gain_vec, Refl refl)
 {
     const int B = a.bands;
@@ -44,22 +45,25 @@ static __device__ __forceinline__ void deposit_tail(const DepositArgs& a, int k,
         gain_vec(gx, gy, gz);
         g = source_gains(a.gain, a.frame, a.res, B, gx, gy, gz);
     }
-    unsigned long long* const w = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B * (DIR ? 4 : 1);
+    unsigned long long* const w = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B * C;
     [[maybe_unused]] double ax = 0, ay = 0, az = 0;
-    if constexpr (DIR) {
+    [[maybe_unused]] double Y[kAmbiMax];
+    if constexpr (C >= 4) {
         ax = -(vx / dist);
         ay = -(vy / dist);
         az = -(vz / dist);
+        if constexpr (C > 4) ambi_harmonics<C>(ax, ay, az, Y);
     }
 #pragma unroll
     for (int b = 0; b < kMaxBands; ++b) {
         if (b < B) {
             const double m = quant_m((((a.power[b] * (g ? g[b] : 1.0)) * refl(b)) * fw) * a.scale);
-            if constexpr (DIR) {
-                atomicAdd(&w[4 * b + 0], (unsigned long long)rint(m));
-                atomicAdd(&w[4 * b + 1], dir_q(m, ax));
-                atomicAdd(&w[4 * b + 2], dir_q(m, ay));
-                atomicAdd(&w[4 * b + 3], dir_q(m, az));
+            if constexpr (C >= 4) {
+                atomicAdd(&w[C * b + 0], (unsigned long long)rint(m));
+                atomicAdd(&w[C * b + 1], dir_q(m, ax));
+                atomicAdd(&w[C * b + 2], dir_q(m, ay));
+                atomicAdd(&w[C * b + 3], dir_q(m, az));
+                if constexpr (C > 4) ambi_add<C>(&w[C * b], m, Y);
             } else {
                 atomicAdd(&w[b], (unsigned long long)rint(m));
             }

@@ -114,17 +114,11 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_emit_source", &m->emit_source},
         {"hare_hist_reduce", &m->hist_reduce},
         {"hare_direct_emit", &m->direct_emit},
-        {"hare_direct_deposit", &m->direct_deposit[0]},
-        {"hare_direct_deposit_dir", &m->direct_deposit[1]},
         {"hare_image_mirror", &m->image_mirror},
         {"hare_image_pairs", &m->image_pairs},
-        {"hare_image_deposit", &m->image_deposit[0]},
-        {"hare_image_deposit_dir", &m->image_deposit[1]},
         {"hare_image2_mirror", &m->image2_mirror},
         {"hare_image2_cands", &m->image2_cands},
         {"hare_image2_paths", &m->image2_paths},
-        {"hare_image2_deposit", &m->image2_deposit[0]},
-        {"hare_image2_deposit_dir", &m->image2_deposit[1]},
     };
     for (auto& t : table) {
         hipError_t e = H->ModuleGetFunction(t.fn, m->mod, t.name);
@@ -132,12 +126,15 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
     }
     for (int i = 0; i < DeviceModule::kFamilies * 4; ++i)          // the voxel families, member by member
         if (H->ModuleGetFunction(&m->voxel[0][0][0] + i, m->mod, (&kVoxelKernelNames[0][0][0])[i]) != hipSuccess) (&m->voxel[0][0][0])[i] = nullptr;
-    const char* const receive_names[6] = {"hare_receive_reflect", "hare_receive_scatter", "hare_receive_scatter_rain", "hare_receive_reflect_map",
-                                          "hare_receive_scatter_map", "hare_rain_step"};
-    for (int f = 0; f < 6; ++f)
-        for (int dir = 0; dir < 2; ++dir) {
-            hipFunction_t* fn = f < 5 ? &m->receive[f][dir] : &m->rain_step[dir];
-            if (H->ModuleGetFunction(fn, m->mod, (std::string(receive_names[f]) + (dir ? "_dir" : "")).c_str()) != hipSuccess) *fn = nullptr;
+    // the kernels with a form per channel count (scene.h: kChannelSuffix): the receive step's five, the rain and the three deposits
+    const char* const channel_names[9] = {"hare_receive_reflect", "hare_receive_scatter", "hare_receive_scatter_rain", "hare_receive_reflect_map",
+                                          "hare_receive_scatter_map", "hare_rain_step", "hare_direct_deposit", "hare_image_deposit",
+                                          "hare_image2_deposit"};
+    hipFunction_t* const channel_fns[4] = {m->rain_step, m->direct_deposit, m->image_deposit, m->image2_deposit};
+    for (int f = 0; f < 9; ++f)
+        for (int dir = 0; dir < 4; ++dir) {
+            hipFunction_t* fn = f < 5 ? &m->receive[f][dir] : &channel_fns[f - 5][dir];
+            if (H->ModuleGetFunction(fn, m->mod, (std::string(channel_names[f]) + kChannelSuffix[dir]).c_str()) != hipSuccess) *fn = nullptr;
         }
     (void)H->GetLastError();   // a failed lookup must not stay behind as the host's "last error"
     if (!m->voxel_tri || !m->voxel_quad) {

@@ -25,22 +25,32 @@ extern "C" __global__ __launch_bounds__(256) void hare_direct_emit(DirectArgs da
     a.sexcl[k] = d2 > rc[3] ? -1 : -2;
 }
 
-template <bool DIR>
+template <int C>
 static __device__ __forceinline__ void direct_deposit_body(const DepositArgs& a)
 {
     const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (k >= a.n_rcv) return;
     if (a.sexcl[k] == -2 || a.socc[k] != 0) return;             // not eligible, or the source does not see the center
     // the source's ray to the center is the path's own vector (the emission's: the same operations); no wall, reflectance 1.0
-    deposit_tail<DIR>(a, k, a.pos[0], a.pos[1], a.pos[2], [](double&, double&, double&) {}, [](int) { return 1.0; });
+    deposit_tail<C>(a, k, a.pos[0], a.pos[1], a.pos[2], [](double&, double&, double&) {}, [](int) { return 1.0; });
 }
 
 extern "C" __global__ __launch_bounds__(256) void hare_direct_deposit(DirectArgs a)
 {
-    direct_deposit_body<false>(a.d);
+    direct_deposit_body<1>(a.d);
 }
 
 extern "C" __global__ __launch_bounds__(256) void hare_direct_deposit_dir(DirectArgs a)
 {
-    direct_deposit_body<true>(a.d);
+    direct_deposit_body<4>(a.d);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_direct_deposit_dir2(DirectArgs a)
+{
+    direct_deposit_body<9>(a.d);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_direct_deposit_dir3(DirectArgs a)
+{
+    direct_deposit_body<16>(a.d);
 }

@@ -587,7 +587,7 @@ struct SourceArgs {
 struct DepositArgs {
     const double* rcv;         // n_rcv x 4: cx, cy, cz, r * r
     const double* gain;        // the source's table (null iff res == 0)
-    unsigned long long* hist;  // n_rcv x n_bins x bands (x 4: the _dir deposits), accumulated
+    unsigned long long* hist;  // n_rcv x n_bins x bands (x 4, 9, 16: the _dir, _dir2, _dir3 deposits), accumulated
     unsigned long long* det;   // 2 n_rcv, accumulated
     RayRec* srays;             // S shadow rays
     double* stmax;             // S t_max (1.0)

@@ -176,7 +176,7 @@ extern "C" __global__ __launch_bounds__(256) void hare_image_pairs(ImageArgs a)
 
 // A lane per pair of the list.  Several pairs can land in one histogram word (a receiver's reflections off two walls at the same
 // distance; a path through an edge that two coplanar polygons share): every add is an atomic.
-template <bool DIR>
+template <int C>
 static __device__ __forceinline__ void image_deposit_body(const ImageArgs& a)
 {
     const unsigned long long found = *a.count;
@@ -186,7 +186,7 @@ static __device__ __forceinline__ void image_deposit_body(const ImageArgs& a)
     if (a.d.socc[2 * i] != 0 || a.d.socc[2 * i + 1] != 0) return;       // a leg is occluded
     const int k = a.pair_kp[2 * i], p = a.pair_kp[2 * i + 1];
     const double* const im = a.img + 4 * (size_t)p;
-    deposit_tail<DIR>(
+    deposit_tail<C>(
         a.d, k, im[0], im[1], im[2],
         [&](double& gx, double& gy, double& gz) {                       // source -> x, the reflection point: the origin of the pair's shadow rays
             const RayRec& s = a.d.srays[2 * i];
@@ -199,10 +199,20 @@ static __device__ __forceinline__ void image_deposit_body(const ImageArgs& a)
 
 extern "C" __global__ __launch_bounds__(256) void hare_image_deposit(ImageArgs a)
 {
-    image_deposit_body<false>(a);
+    image_deposit_body<1>(a);
 }
 
 extern "C" __global__ __launch_bounds__(256) void hare_image_deposit_dir(ImageArgs a)
 {
-    image_deposit_body<true>(a);
+    image_deposit_body<4>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_image_deposit_dir2(ImageArgs a)
+{
+    image_deposit_body<9>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_image_deposit_dir3(ImageArgs a)
+{
+    image_deposit_body<16>(a);
 }

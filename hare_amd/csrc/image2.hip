@@ -245,7 +245,7 @@ extern "C" __global__ __launch_bounds__(256) void hare_image2_paths(Image2Args a
 }
 
 // A lane per path of the list; several paths can land in one histogram word: every add is an atomic.
-template <bool DIR>
+template <int C>
 static __device__ __forceinline__ void image2_deposit_body(const Image2Args& a)
 {
     const unsigned long long found = a.count[1];
@@ -256,7 +256,7 @@ static __device__ __forceinline__ void image2_deposit_body(const Image2Args& a)
     const int k = a.path_kc[2 * i];
     const size_t ci = (size_t)a.path_kc[2 * i + 1];
     const int p = a.cand_pq[2 * ci], q = a.cand_pq[2 * ci + 1];
-    deposit_tail<DIR>(
+    deposit_tail<C>(
         a.d, k, a.cand_s[3 * ci], a.cand_s[3 * ci + 1], a.cand_s[3 * ci + 2],
         [&](double& gx, double& gy, double& gz) {                       // source -> x1, the first reflection point: the origin of the middle leg
             const RayRec& s = a.d.srays[3 * i + 1];
@@ -269,10 +269,20 @@ static __device__ __forceinline__ void image2_deposit_body(const Image2Args& a)
 
 extern "C" __global__ __launch_bounds__(256) void hare_image2_deposit(Image2Args a)
 {
-    image2_deposit_body<false>(a);
+    image2_deposit_body<1>(a);
 }
 
 extern "C" __global__ __launch_bounds__(256) void hare_image2_deposit_dir(Image2Args a)
 {
-    image2_deposit_body<true>(a);
+    image2_deposit_body<4>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_image2_deposit_dir2(Image2Args a)
+{
+    image2_deposit_body<9>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_image2_deposit_dir3(Image2Args a)
+{
+    image2_deposit_body<16>(a);
 }

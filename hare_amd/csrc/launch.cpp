@@ -143,6 +143,17 @@ static_assert((HARE_RECEIVE_IMAGE2 & (kPublicFlags | HARE_SHOOT_BOUNCE_LOOP | HA
                                       HARE_RECEIVE_DIRECT | HARE_RECEIVE_IMAGE | 0xF000u | kFlagAnyHit | SHOOT_RETIRED_SILENT)) == 0 &&
                   (HARE_RECEIVE_IMAGE2 & (HARE_RECEIVE_IMAGE2 - 1u)) == 0,
               "the receive calls' second-order bit is a bit of its own: the first above the developer bits, below the internal ones");
+// HARE_RECEIVE_ORDER2 is 0x20000, between HARE_RECEIVE_IMAGE2 and the any-hit bit; HARE_RECEIVE_ORDER3 is 0x100000, the first bit above
+// SHOOT_RETIRED_SILENT (0x80000, which the value first proposed for it would have been)
+static_assert((HARE_RECEIVE_ORDER2 & (kPublicFlags | HARE_SHOOT_BOUNCE_LOOP | HARE_RECEIVE_DIFFUSE_RAIN | HARE_RECEIVE_DIRECTIONAL | HARE_RECEIVE_TIME_LIMIT |
+                                      HARE_RECEIVE_DIRECT | HARE_RECEIVE_IMAGE | HARE_RECEIVE_IMAGE2 | 0xF000u | kFlagAnyHit | SHOOT_RETIRED_SILENT)) == 0 &&
+                  (HARE_RECEIVE_ORDER2 & (HARE_RECEIVE_ORDER2 - 1u)) == 0,
+              "the receive calls' order-2 bit is a bit of its own, apart from the developer and the internal bits");
+static_assert((HARE_RECEIVE_ORDER3 & (kPublicFlags | HARE_SHOOT_BOUNCE_LOOP | HARE_RECEIVE_DIFFUSE_RAIN | HARE_RECEIVE_DIRECTIONAL | HARE_RECEIVE_TIME_LIMIT |
+                                      HARE_RECEIVE_DIRECT | HARE_RECEIVE_IMAGE | HARE_RECEIVE_IMAGE2 | HARE_RECEIVE_ORDER2 | 0xF000u | kFlagAnyHit |
+                                      SHOOT_RETIRED_SILENT)) == 0 &&
+                  (HARE_RECEIVE_ORDER3 & (HARE_RECEIVE_ORDER3 - 1u)) == 0,
+              "the receive calls' order-3 bit is a bit of its own, above the internal bits");
 uint32_t sanitize_flags(const Scene& s, uint32_t flags)
 {
     return flags & (kPublicFlags | (s.opt.dev ? 0xF000u : 0u));

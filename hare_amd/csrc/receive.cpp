@@ -96,7 +96,17 @@ int32_t scene_bands(const Scene& s, int32_t top)
 size_t receive_hist_words(const Scene& s, int32_t top, int32_t n_bins, uint32_t flags, size_t min_K)
 {
     const size_t K = std::max<size_t>(min_K, s.rcv.size() / 4);
-    return K * (size_t)n_bins * (size_t)scene_bands(s, top) * ((flags & HARE_RECEIVE_DIRECTIONAL) ? 4u : 1u);
+    return K * (size_t)n_bins * (size_t)scene_bands(s, top) * (size_t)receive_channels(flags);
+}
+
+int receive_check_order(const char* who, uint32_t flags)
+{
+    const uint32_t order = flags & (HARE_RECEIVE_ORDER2 | HARE_RECEIVE_ORDER3);
+    if (order && (!(flags & HARE_RECEIVE_DIRECTIONAL) || order == (HARE_RECEIVE_ORDER2 | HARE_RECEIVE_ORDER3))) {
+        set_error(std::string(who) + ": HARE_RECEIVE_ORDER2 / HARE_RECEIVE_ORDER3 are accepted only together with HARE_RECEIVE_DIRECTIONAL, and one of them at most");
+        return HARE_E_INVALID;
+    }
+    return HARE_OK;
 }
 
 // Everything a receive call checks before anything runs (HARE_E_INVALID); "no receivers" is HARE_E_STATE, after the device checks
@@ -107,6 +117,7 @@ int receive_check_args(const char* who, const Scene& s, uint32_t flags, int32_t 
         set_error(std::string(who) + ": " + what);
         return HARE_E_INVALID;
     };
+    if (int rc = receive_check_order(who, flags)) return rc;
     if ((flags & HARE_RECEIVE_IMAGE2) && !(flags & HARE_RECEIVE_IMAGE))
         return bad("HARE_RECEIVE_IMAGE2 is accepted only together with HARE_RECEIVE_IMAGE (the second order stands on the first)");
     if (kind < HARE_KIND_VOXEL || kind > HARE_KIND_KDTREE) return bad("bad kind");
@@ -118,7 +129,9 @@ int receive_check_args(const char* who, const Scene& s, uint32_t flags, int32_t 
     if (frac_bits < 0 || frac_bits > 62) return bad("frac_bits out of range (0 .. 62)");
     if (receive_hist_words(s, top, n_bins, 0, 1) > ((size_t)1 << 27)) return bad("receivers x n_bins x bands exceeds 2^27");
     if (receive_hist_words(s, top, n_bins, flags, 1) > ((size_t)1 << 27))
-        return bad("receivers x n_bins x bands x 4 channels (HARE_RECEIVE_DIRECTIONAL) exceeds 2^27");
+        return bad(flags & HARE_RECEIVE_ORDER3   ? "receivers x n_bins x bands x 16 channels (HARE_RECEIVE_ORDER3) exceeds 2^27"
+                   : flags & HARE_RECEIVE_ORDER2 ? "receivers x n_bins x bands x 9 channels (HARE_RECEIVE_ORDER2) exceeds 2^27"
+                                                 : "receivers x n_bins x bands x 4 channels (HARE_RECEIVE_DIRECTIONAL) exceeds 2^27");
     if (s.rmap.set && receive_rains(s, top, flags))
         return bad("HARE_RECEIVE_DIFFUSE_RAIN does not combine with a receiver map (hare_scene_set_receiver_map)");
     return HARE_OK;
@@ -185,7 +198,7 @@ int receive_plan(const Scene& s, int32_t top, uint32_t flags, int64_t n, int32_t
         ra.map_h = m.h;
         ra.map_pad = m.pad;
     }
-    p.directional = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
+    p.directional = receive_channel_form(flags);
     p.rain = receive_rains(s, top, flags);
     p.work = p.rain ? rain_work(d_work, n) : RainWork();
     ra.rain_flag = p.work.flag;
@@ -394,7 +407,7 @@ static int image_scene_fill(ImageScene& sc, const Scene& s, int32_t top, bool de
 int direct_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                    int32_t frac_bits, void* d_work, void* d_hist, void* d_det, hipStream_t st)
 {
-    const bool dir = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
+    const int dir = receive_channel_form(flags);
     if (!s.module || !s.module->direct_emit || !s.module->direct_deposit[dir]) {
         set_error("hare_direct_emit / hare_direct_deposit missing from code object");
         return HARE_E_STATE;
@@ -426,7 +439,7 @@ int direct_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t
 int image_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                   int32_t frac_bits, int64_t max_pairs, void* d_work, void* d_hist, void* d_det, hipStream_t st)
 {
-    const bool dir = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
+    const int dir = receive_channel_form(flags);
     if (!s.module || !s.module->image_mirror || !s.module->image_pairs || !s.module->image_deposit[dir]) {
         set_error("hare_image_mirror / hare_image_pairs / hare_image_deposit missing from code object");
         return HARE_E_STATE;
@@ -468,7 +481,7 @@ int image_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t 
 int image2_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                    int32_t frac_bits, int64_t max_cands, int64_t max_paths, void* d_work, void* d_hist, void* d_det, hipStream_t st)
 {
-    const bool dir = (flags & HARE_RECEIVE_DIRECTIONAL) != 0;
+    const int dir = receive_channel_form(flags);
     const DeviceModule* const m = s.module;
     if (!m || !m->image2_mirror || !m->image2_cands || !m->image2_paths || !m->image2_deposit[dir]) {
         set_error("hare_image2_mirror / hare_image2_cands / hare_image2_paths / hare_image2_deposit missing from code object");
@@ -523,7 +536,7 @@ int reduce_check_spec(const char* who, int64_t K, int32_t n_bins, int32_t B, int
     if (K < 1 || K > kMaxMapReceivers) return bad("K out of range (1 .. 65 536)");
     if (n_bins < 1) return bad("n_bins must be >= 1");
     if (B < 1 || B > kMaxBands) return bad("bands out of range (1 .. 8)");
-    if (channels != 1 && channels != 4) return bad("channels must be 1 or 4");
+    if (channels != 1 && channels != 4 && channels != 9 && channels != 16) return bad("channels must be 1, 4, 9 or 16");
     if ((unsigned __int128)K * (unsigned)n_bins * (unsigned)B * (unsigned)channels > ((size_t)1 << 27)) return bad("K x n_bins x bands x channels exceeds 2^27");
     if (r.n_win < 0 || r.n_win > kMaxReduceWindows) return bad("n_win out of range (0 .. 16)");
     if (r.n_lev < 0 || r.n_lev > kMaxReduceLevels) return bad("n_lev out of range (0 .. 32)");
@@ -735,11 +748,12 @@ static int deposit_call_check(const char* who, const hare_scene* s, int32_t kind
         set_error("null scene");
         return HARE_E_INVALID;
     }
+    if (int rc = receive_check_order(who, flags)) return rc;
     if (n_weight < 1 || n_weight > ((int64_t)1 << 53)) {
         set_error(std::string(who) + ": n_weight out of range (1 .. 2^53)");
         return HARE_E_INVALID;
     }
-    flags &= HARE_RECEIVE_DIRECTIONAL;
+    flags &= kReceiveChannelFlags;
     if (int rc = receive_check_args(who, *s, flags, kind, top, 0, 1, n_bins, bin_len, frac_bits)) return rc;
     if (s->src.set && s->src.B != scene_bands(*s, top)) {
         set_error(std::string(who) + ": the source has " + std::to_string(s->src.B) + " bands, the topology " + std::to_string(scene_bands(*s, top)));

@@ -115,6 +115,73 @@ static __device__ __forceinline__ unsigned long long wave_sum4_u64(unsigned long
     return v;
 }
 
+// ---- higher orders (HARE_RECEIVE_ORDER2 / _ORDER3; the header's "receivers", "Higher orders"): C = 9 or 16 channels per (receiver, bin,
+// band).  Channels 0..3 are the four above; channels 4 .. C - 1 are ACN 4 .. C - 1 in SN3D, polynomials of the arrival vector, quantised
+// with dir_q like X, Y, Z.  The kernels' DIR switch is the channel count C: 1 and 4 are the kernels above, unchanged; 9 and 16 are the
+// _dir2 and _dir3 forms.  The six constants are the correctly rounded doubles, written as their bits (tests/test_ambi_reference.py
+// compares them with numpy.sqrt).
+constexpr double kAmbiC3 = 0x1.bb67ae8584caap+0;        // sqrt(3)
+constexpr double kAmbiC3h = 0x1.bb67ae8584caap-1;       // 0.5 * sqrt(3)
+constexpr double kAmbiC15 = 0x1.efbdeb14f4edap+1;       // sqrt(15)
+constexpr double kAmbiC15h = 0x1.efbdeb14f4edap+0;      // 0.5 * sqrt(15)
+constexpr double kAmbiC58 = 0x1.94c583ada5b53p-1;       // sqrt(0.625)
+constexpr double kAmbiC38 = 0x1.3988e1409212ep-1;       // sqrt(0.375)
+constexpr int kAmbiMax = 12;                            // channels 4 .. 15
+// Y[j] = Y_{4 + j}(x, y, z), j < C - 4: the header's operations in the header's order
+template <int C>
+static __device__ __forceinline__ void ambi_harmonics(double x, double y, double z, double (&Y)[kAmbiMax])
+{
+    const double xx = x * x, yy = y * y, zz = z * z;
+    const double d = xx - yy;
+    Y[0] = kAmbiC3 * (x * y);
+    Y[1] = kAmbiC3 * (y * z);
+    Y[2] = 1.5 * zz - 0.5;
+    Y[3] = kAmbiC3 * (x * z);
+    Y[4] = kAmbiC3h * d;
+    if constexpr (C > 9) {
+        const double f = 5.0 * zz - 1.0;
+        Y[5] = kAmbiC58 * (y * (3.0 * xx - yy));
+        Y[6] = kAmbiC15 * ((x * y) * z);
+        Y[7] = kAmbiC38 * (y * f);
+        Y[8] = z * (2.5 * zz - 1.5);
+        Y[9] = kAmbiC38 * (x * f);
+        Y[10] = kAmbiC15h * (z * d);
+        Y[11] = kAmbiC58 * (x * (xx - 3.0 * yy));
+    }
+}
+// a lane's own adds of one band's channels 4 .. C - 1 at w = &hist[... + 0] (the map kernels, the rain and the source paths add per lane)
+template <int C>
+static __device__ __forceinline__ void ambi_add(unsigned long long* w, double m, const double (&Y)[kAmbiMax])
+{
+#pragma unroll
+    for (int j = 0; j < C - 4; ++j) atomicAdd(&w[4 + j], dir_q(m, Y[j]));
+}
+// The wave's sums of sixteen words per lane in 17 exchanges instead of 16 x 6: four steps halve what a lane holds (bit 5, 4, 3, 2 of the
+// lane picks the half it keeps and passes the other on), the last two are the plain butterfly.  Returns, in every lane, the wave's sum of
+// word (lane >> 2).  Wrapping uint64 adds only: exact whatever the order.  Nine channels run padded with zero words.  word(j) forms
+// the lane's word j; the first step takes the words in pairs (j, 8 + j) and the scheduler is held to that order, so that eight sums
+// and one pair are live, not sixteen words and what forming them takes.
+template <class Word>
+static __device__ __forceinline__ unsigned long long wave_sum16_u64(Word word, int lane)
+{
+    const bool h5 = (lane & 32) != 0, h4 = (lane & 16) != 0, h3 = (lane & 8) != 0, h2 = (lane & 4) != 0;
+    unsigned long long a[8], b[4], c[2];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const unsigned long long v0 = word(j), v1 = word(8 + j);
+        a[j] = (h5 ? v1 : v0) + __shfl_xor(h5 ? v0 : v1, 32, 64);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b[j] = (h4 ? a[4 + j] : a[j]) + __shfl_xor(h4 ? a[j] : a[4 + j], 16, 64);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) c[j] = (h3 ? b[2 + j] : b[j]) + __shfl_xor(h3 ? b[j] : b[2 + j], 8, 64);
+    unsigned long long s = (h2 ? c[1] : c[0]) + __shfl_xor(h2 ? c[0] : c[1], 4, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 1, 64);
+    return s;
+}
+
 // ---- receiver maps (hare_scene_set_receiver_map; the header's "receivers", "Receiver maps"): the _map kernels run a ray through its
 // CANDIDATES only, the receivers listed in the grid cells its segment visits, with the test, the binning and the adds of the loop above.
 // The receivers (up to 65 536 x 32 B) are not staged: every lane walks its own cells and reads its own candidates with vector loads;
@@ -150,7 +217,7 @@ static __device__ __forceinline__ void map_range(double u, double v, double ts, 
     hi = map_cell(floor(pmax + P), n);
 }
 
-template <bool DIR>
+template <int C>
 static __device__ __forceinline__ void map_receivers(const ReceiveMapArgs& a, int64_t i, const RayRec& r, double t_end, double L)
 {
     const int B = a.bands;
@@ -209,17 +276,20 @@ static __device__ __forceinline__ void map_receivers(const ReceiveMapArgs& a, in
                     const int bin = (int)floor(x);
                     // a detection is rare beside the cells walked: the ray's energies are read here, not held through the walk, and the
                     // arrival vector is formed per detection
-                    if constexpr (DIR) {
+                    if constexpr (C >= 4) {
                         const double len = sqrt((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
                         const double ax = -(r.dx / len), ay = -(r.dy / len), az = -(r.dz / len);
-                        unsigned long long* const w = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B * 4;
+                        [[maybe_unused]] double Y[kAmbiMax];                    // C > 4: per detection too, like a (nothing held through the walk)
+                        if constexpr (C > 4) ambi_harmonics<C>(ax, ay, az, Y);
+                        unsigned long long* const w = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B * C;
                         for (int b = 0; b < B; ++b) {
                             const double Eb = a.init_state ? 1.0 : a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i];
                             const double mb = quant_m(Eb * a.scale);
-                            atomicAdd(&w[4 * b + 0], (unsigned long long)rint(mb));
-                            atomicAdd(&w[4 * b + 1], dir_q(mb, ax));
-                            atomicAdd(&w[4 * b + 2], dir_q(mb, ay));
-                            atomicAdd(&w[4 * b + 3], dir_q(mb, az));
+                            atomicAdd(&w[C * b + 0], (unsigned long long)rint(mb));
+                            atomicAdd(&w[C * b + 1], dir_q(mb, ax));
+                            atomicAdd(&w[C * b + 2], dir_q(mb, ay));
+                            atomicAdd(&w[C * b + 3], dir_q(mb, az));
+                            if constexpr (C > 4) ambi_add<C>(&w[C * b], mb, Y);
                         }
                     } else {
                         unsigned long long* const w = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B;
@@ -241,7 +311,11 @@ static __device__ __forceinline__ void map_receivers(const ReceiveMapArgs& a, in
 // 4 B contiguous words of a bin (at most 256 B) in one atomic instruction.
 // MAP (the _map kernels, a scene with a receiver map): no staging; the receiver step is map_receivers, above.  Everything below the
 // receiver step is the same code.
-template <bool SCATTER, bool RAIN = false, bool DIR = false, bool MAP = false, typename Args = ReceiveArgs>
+// C (the channel count): 1, and 4 for DIR; 9 and 16 (the _dir2 / _dir3 kernels, HARE_RECEIVE_ORDER2 / _ORDER3) evaluate the polynomials of the
+// arrival vector with it, once per ray and cast, and hold them (10 or 24 VGPRs) through the receiver loop.  Aggregated, the wave sums a
+// band's words with wave_sum16_u64 -- lane 4 ch + s then holds channel ch -- and the sub-lane s keeps bands s and s + 4: the B C contiguous
+// words of a bin go out in one pass of 64 lanes over bands 0..3 and, for B > 4, a second over bands 4..7, one atomic per word per wave.
+template <bool SCATTER, bool RAIN = false, int C = 1, bool MAP = false, typename Args = ReceiveArgs>
 static __device__ __forceinline__ void receive_body(const Args& a)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -308,7 +382,7 @@ static __device__ __forceinline__ void receive_body(const Args& a)
             r = a.rays[i];
             if (!a.init_state) L = a.state[i];
             const XEventRec& ei = a.ev[i];
-            if (!(a.cut & kCutSkipDetect) && !imaged) map_receivers<DIR>(a, i, r, ei.hit ? ei.t : __builtin_inf(), L);
+            if (!(a.cut & kCutSkipDetect) && !imaged) map_receivers<C>(a, i, r, ei.hit ? ei.t : __builtin_inf(), L);
         }
     }
     if (live) {
@@ -332,6 +406,11 @@ static __device__ __forceinline__ void receive_body(const Args& a)
             const double t_end = (live && e.hit) ? e.t : __builtin_inf();
             const double nb = (double)a.n_bins;
             [[maybe_unused]] double ax = 0, ay = 0, az = 0;
+            [[maybe_unused]] double Y[kAmbiMax];                                // C > 4: channels 4 .. C - 1 of a
+            if constexpr (C > 4) {
+#pragma unroll
+                for (int j = 0; j < kAmbiMax; ++j) Y[j] = 0;
+            }
             [[maybe_unused]] bool have_a = false;                               // wave-uniform
             for (int k = 0; k < a.n_rcv; ++k) {
                 const double cx = rcv[4 * k + 0], cy = rcv[4 * k + 1], cz = rcv[4 * k + 2], r2 = rcv[4 * k + 3];
@@ -356,7 +435,7 @@ static __device__ __forceinline__ void receive_body(const Args& a)
                     if (dm & ~bm) atomicAdd(&a.det[2 * k + 1], (unsigned long long)__popcll(dm & ~bm));
                 }
                 if (bm == 0ull) continue;
-                if constexpr (DIR) {
+                if constexpr (C >= 4) {
                     if (!have_a) {
                         have_a = true;
                         if (seen) {
@@ -364,22 +443,52 @@ static __device__ __forceinline__ void receive_body(const Args& a)
                             ax = -(r.dx / len);
                             ay = -(r.dy / len);
                             az = -(r.dz / len);
+                            if constexpr (C > 4) ambi_harmonics<C>(ax, ay, az, Y);
                         }
                     }
-                    unsigned long long* const row = a.hist + (size_t)k * (size_t)a.n_bins * (size_t)B * 4;
+                    unsigned long long* const row = a.hist + (size_t)k * (size_t)a.n_bins * (size_t)B * C;
                     if (!a.aggregate) {                                          // naive form (A/B): every detecting lane adds its own words
                         if (binned)
                             for (int b = 0; b < B; ++b) {
                                 const double m = quant_m(E[b] * a.scale);
-                                unsigned long long* const w = &row[((size_t)bin * B + b) * 4];
+                                unsigned long long* const w = &row[((size_t)bin * B + b) * C];
                                 atomicAdd(&w[0], (unsigned long long)rint(m));
                                 atomicAdd(&w[1], dir_q(m, ax));
                                 atomicAdd(&w[2], dir_q(m, ay));
                                 atomicAdd(&w[3], dir_q(m, az));
+                                if constexpr (C > 4) ambi_add<C>(w, m, Y);
                             }
                         continue;
                     }
                     unsigned long long todo = bm;
+                    if constexpr (C > 4) {
+                        while (todo) {                                           // one round per distinct bin among the wave's detections
+                            const int leader = __ffsll((long long)todo) - 1;
+                            const int lb = __shfl(bin, leader, 64);
+                            const bool mine = binned && bin == lb;
+                            todo &= ~__ballot(mine);
+                            unsigned long long lo = 0, hi = 0;                   // channel lane >> 2 of bands (lane & 3) and (lane & 3) + 4
+#pragma unroll
+                            for (int b = 0; b < kMaxBands; ++b) {
+                                if (b < B) {
+                                    const double m = mine ? quant_m(E[b] * a.scale) : 0.0;     // m = 0 quantises to C zero words
+                                    const unsigned long long sb = wave_sum16_u64(
+                                        [&](int j) -> unsigned long long {
+                                            if (j == 0) return (unsigned long long)rint(m);
+                                            if (j >= C) return 0ull;
+                                            return dir_q(m, j == 1 ? ax : (j == 2 ? ay : (j == 3 ? az : Y[j < 4 ? 0 : j - 4])));
+                                        },
+                                        lane);
+                                    if ((lane & 3) == (b & 3)) (b < 4 ? lo : hi) = sb;
+                                }
+                            }
+                            const int ch = lane >> 2, s = lane & 3;
+                            unsigned long long* const w = &row[(size_t)lb * B * C];
+                            if (ch < C && s < B) atomicAdd(&w[s * C + ch], lo);
+                            if (ch < C && s + 4 < B) atomicAdd(&w[(s + 4) * C + ch], hi);
+                        }
+                        continue;
+                    }
                     while (todo) {                                               // one round per distinct bin among the wave's detections
                         const int leader = __ffsll((long long)todo) - 1;
                         const int lb = __shfl(bin, leader, 64);
@@ -547,38 +656,64 @@ extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_rain(Rece
 
 extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect_dir(ReceiveArgs a)
 {
-    receive_body<false, false, true>(a);
+    receive_body<false, false, 4>(a);
 }
 
 extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_dir(ReceiveArgs a)
 {
-    receive_body<true, false, true>(a);
+    receive_body<true, false, 4>(a);
 }
 
 extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_rain_dir(ReceiveArgs a)
 {
-    receive_body<true, true, true>(a);
+    receive_body<true, true, 4>(a);
 }
 
 extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect_map(ReceiveMapArgs a)
 {
-    receive_body<false, false, false, true, ReceiveMapArgs>(a);
+    receive_body<false, false, 1, true, ReceiveMapArgs>(a);
 }
 
 extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_map(ReceiveMapArgs a)
 {
-    receive_body<true, false, false, true, ReceiveMapArgs>(a);
+    receive_body<true, false, 1, true, ReceiveMapArgs>(a);
 }
 
 extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect_map_dir(ReceiveMapArgs a)
 {
-    receive_body<false, false, true, true, ReceiveMapArgs>(a);
+    receive_body<false, false, 4, true, ReceiveMapArgs>(a);
 }
 
 extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_map_dir(ReceiveMapArgs a)
 {
-    receive_body<true, false, true, true, ReceiveMapArgs>(a);
+    receive_body<true, false, 4, true, ReceiveMapArgs>(a);
 }
+
+// the higher orders' forms of the five kernels above (HARE_RECEIVE_ORDER2: _dir2, nine channels; HARE_RECEIVE_ORDER3: _dir3, sixteen)
+#define HARE_RECEIVE_ORDER_KERNELS(SUFFIX, C)                                                                      \
+    extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect##SUFFIX(ReceiveArgs a)                  \
+    {                                                                                                              \
+        receive_body<false, false, C>(a);                                                                          \
+    }                                                                                                              \
+    extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter##SUFFIX(ReceiveArgs a)                  \
+    {                                                                                                              \
+        receive_body<true, false, C>(a);                                                                           \
+    }                                                                                                              \
+    extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_rain##SUFFIX(ReceiveArgs a)             \
+    {                                                                                                              \
+        receive_body<true, true, C>(a);                                                                            \
+    }                                                                                                              \
+    extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect_map##SUFFIX(ReceiveMapArgs a)           \
+    {                                                                                                              \
+        receive_body<false, false, C, true, ReceiveMapArgs>(a);                                                    \
+    }                                                                                                              \
+    extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_map##SUFFIX(ReceiveMapArgs a)           \
+    {                                                                                                              \
+        receive_body<true, false, C, true, ReceiveMapArgs>(a);                                                     \
+    }
+HARE_RECEIVE_ORDER_KERNELS(_dir2, 9)
+HARE_RECEIVE_ORDER_KERNELS(_dir3, 16)
+#undef HARE_RECEIVE_ORDER_KERNELS
 
 // ---- diffuse rain (HARE_RECEIVE_DIFFUSE_RAIN; the header's "receivers", "Diffuse rain")
 // hare_rain_step runs between a cast's shoot and hare_receive_scatter_rain, which overwrites the rays and the state: a lane per ray reads what
@@ -589,7 +724,7 @@ extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_map_dir(R
 // receiver step does: nearly every visible ray deposits and their bins are spread, so the wave's rounds over distinct bins cost more than
 // they save (hall, 1M rays, K = 8, B = 8: the rain loop 94.5 ms aggregated, 79.5 ms per lane; the same histogram).
 // DIR (hare_rain_step_dir, HARE_RECEIVE_DIRECTIONAL): the deposit adds four words per band, weighted by -(v / dist).
-template <bool DIR>
+template <int C>
 static __device__ __forceinline__ void rain_body(const RainArgs& a)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -640,7 +775,8 @@ static __device__ __forceinline__ void rain_body(const RainArgs& a)
         for (int b = 0; b < kMaxBands; ++b) q[b] = 0;
         [[maybe_unused]] double mq[kMaxBands];                          // DIR: m_b, quantised where it is added
         [[maybe_unused]] double ax = 0, ay = 0, az = 0;
-        if constexpr (DIR) {
+        [[maybe_unused]] double Y[kAmbiMax];                            // C > 4: channels 4 .. C - 1 of a
+        if constexpr (C >= 4) {
 #pragma unroll
             for (int b = 0; b < kMaxBands; ++b) mq[b] = 0;
         }
@@ -657,10 +793,11 @@ static __device__ __forceinline__ void rain_body(const RainArgs& a)
             if (binned) {
                 bin = (int)floor(x);
                 const double* al = a.alpha ? a.alpha + (size_t)e.poly_id * (size_t)B : nullptr;
-                if constexpr (DIR) {
+                if constexpr (C >= 4) {
                     ax = -(vx / dist);
                     ay = -(vy / dist);
                     az = -(vz / dist);
+                    if constexpr (C > 4) ambi_harmonics<C>(ax, ay, az, Y);
                 }
 #pragma unroll
                 for (int b = 0; b < kMaxBands; ++b) {
@@ -668,7 +805,7 @@ static __device__ __forceinline__ void rain_body(const RainArgs& a)
                         const double E = a.init_state ? 1.0 : a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i];
                         const double Ea = al ? E * (1.0 - al[b]) : E;
                         const double v = quant_m(((Ea * sig[b]) * w) * a.scale);
-                        if constexpr (DIR) mq[b] = v;
+                        if constexpr (C >= 4) mq[b] = v;
                         else q[b] = (unsigned long long)rint(v);
                     }
                 }
@@ -679,16 +816,17 @@ static __device__ __forceinline__ void rain_body(const RainArgs& a)
             if (bm) atomicAdd(&a.det[2 * k], (unsigned long long)__popcll(bm));
             if (dm & ~bm) atomicAdd(&a.det[2 * k + 1], (unsigned long long)__popcll(dm & ~bm));
         }
-        if constexpr (DIR) {
-            if (binned) {                                               // per lane, the four words of a band one by one
-                unsigned long long* const row = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B * 4;
+        if constexpr (C >= 4) {
+            if (binned) {                                               // per lane, the C words of a band one by one
+                unsigned long long* const row = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B * C;
 #pragma unroll
                 for (int b = 0; b < kMaxBands; ++b) {
                     if (b < B) {
-                        atomicAdd(&row[4 * b + 0], (unsigned long long)rint(mq[b]));
-                        atomicAdd(&row[4 * b + 1], dir_q(mq[b], ax));
-                        atomicAdd(&row[4 * b + 2], dir_q(mq[b], ay));
-                        atomicAdd(&row[4 * b + 3], dir_q(mq[b], az));
+                        atomicAdd(&row[C * b + 0], (unsigned long long)rint(mq[b]));
+                        atomicAdd(&row[C * b + 1], dir_q(mq[b], ax));
+                        atomicAdd(&row[C * b + 2], dir_q(mq[b], ay));
+                        atomicAdd(&row[C * b + 3], dir_q(mq[b], az));
+                        if constexpr (C > 4) ambi_add<C>(&row[C * b], mq[b], Y);
                     }
                 }
             }
@@ -721,10 +859,20 @@ static __device__ __forceinline__ void rain_body(const RainArgs& a)
 
 extern "C" __global__ __launch_bounds__(256) void hare_rain_step(RainArgs a)
 {
-    rain_body<false>(a);
+    rain_body<1>(a);
 }
 
 extern "C" __global__ __launch_bounds__(256) void hare_rain_step_dir(RainArgs a)
 {
-    rain_body<true>(a);
+    rain_body<4>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_rain_step_dir2(RainArgs a)
+{
+    rain_body<9>(a);
+}
+
+extern "C" __global__ __launch_bounds__(256) void hare_rain_step_dir3(RainArgs a)
+{
+    rain_body<16>(a);
 }

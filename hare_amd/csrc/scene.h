@@ -126,15 +126,16 @@ struct DeviceModule {
     hipFunction_t octree = nullptr, octree_count = nullptr, octree_persist = nullptr, octree_pool = nullptr, octree_tail = nullptr, octree_group = nullptr, octree_group_tail = nullptr, octree_dense = nullptr;
     hipFunction_t kdtree = nullptr, kdtree_count = nullptr;
     hipFunction_t reflect = nullptr, occlusion = nullptr;
-    // receive.hip, [directional]: hare_receive_reflect / _scatter / _scatter_rain (no table / a scattering table / with diffuse rain),
-    // hare_rain_step, and HARE_RECEIVE_DIRECTIONAL's _dir forms
+    // receive.hip, [channel form]: hare_receive_reflect / _scatter / _scatter_rain (no table / a scattering table / with diffuse rain),
+    // hare_rain_step, and HARE_RECEIVE_DIRECTIONAL's _dir forms ([1]); [2], [3]: the _dir2 and _dir3 forms of HARE_RECEIVE_ORDER2 / _ORDER3
+    // (receive_channel_form, below; kChannelSuffix names them, here and in the three deposits)
     // receive[3], receive[4]: hare_receive_reflect_map / hare_receive_scatter_map (a scene with a receiver map)
-    hipFunction_t receive[5][2] = {}, rain_step[2] = {};
+    hipFunction_t receive[5][4] = {}, rain_step[4] = {};
     hipFunction_t emit_source = nullptr;                                   // source.hip
     hipFunction_t hist_reduce = nullptr;                                   // reduce.hip
-    hipFunction_t direct_emit = nullptr, direct_deposit[2] = {};           // direct.hip ([1]: the _dir form)
-    hipFunction_t image_mirror = nullptr, image_pairs = nullptr, image_deposit[2] = {};   // image.hip ([1]: the _dir form)
-    hipFunction_t image2_mirror = nullptr, image2_cands = nullptr, image2_paths = nullptr, image2_deposit[2] = {};   // image2.hip ([1]: the _dir form)
+    hipFunction_t direct_emit = nullptr, direct_deposit[4] = {};           // direct.hip ([channel form])
+    hipFunction_t image_mirror = nullptr, image_pairs = nullptr, image_deposit[4] = {};   // image.hip ([channel form])
+    hipFunction_t image2_mirror = nullptr, image2_cands = nullptr, image2_paths = nullptr, image2_deposit[4] = {};   // image2.hip ([channel form])
     hipFunction_t octree_occl = nullptr, octree_occl_any = nullptr;
     hipFunction_t events_pack_slim = nullptr;
     hipFunction_t block_occ = nullptr;                                     // build_kernels.hip: hare_block_occ
@@ -376,7 +377,8 @@ struct ReceivePlan {
     ReceiveMapArgs args;        // (the grid's fields: p.map only) receivers, state, histogram and switches; the loop fills in rays, events and marks per cast
     RainWork work;              // rain only
     bool rain = false;          // HARE_RECEIVE_DIFFUSE_RAIN on a topology with a scattering table (args.sigma, args.rain_flag set)
-    bool directional = false;   // HARE_RECEIVE_DIRECTIONAL: args.hist has four channels per word and the _dir kernels run
+    int directional = 0;        // receive_channel_form(flags): 1 (HARE_RECEIVE_DIRECTIONAL) args.hist has four channels per word and the _dir kernels
+                                // run; 2, 3 (with HARE_RECEIVE_ORDER2 / _ORDER3) nine and sixteen, the _dir2 / _dir3 kernels
     bool map = false;           // the scene holds a receiver map: the _map kernels run (never with rain)
     bool skip_cast0 = false;    // HARE_RECEIVE_DIRECT: cast 0 runs no receiver step (kCutSkipDetect in that cast's args.cut only)
     bool skip_cast1_specular = false;   // HARE_RECEIVE_IMAGE: in cast 1 the rays that left cast 0 specularly run no receiver step (kCutSkipDetect without a
@@ -384,6 +386,20 @@ struct ReceivePlan {
     bool skip_cast2_specular = false;   // HARE_RECEIVE_IMAGE2: in cast 2 the rays that left casts 0 and 1 specularly run no receiver step (kCutSkipDetect without a
                                 // scattering table; with one, cast 1 stores args.spec2 under kCutStoreSpecular2 and cast 2 reads it under kCutSkipSpecular2)
 };
+// The channel form of a call's flags: DeviceModule::receive's second index and the deposits' only one.  0: one word per band; 1: four
+// (HARE_RECEIVE_DIRECTIONAL); 2: nine (with HARE_RECEIVE_ORDER2); 3: sixteen (with HARE_RECEIVE_ORDER3).  receive_check_order has refused
+// an order flag without the directional one, and both together
+inline int receive_channel_form(uint32_t flags)
+{
+    return !(flags & HARE_RECEIVE_DIRECTIONAL) ? 0 : ((flags & HARE_RECEIVE_ORDER3) ? 3 : ((flags & HARE_RECEIVE_ORDER2) ? 2 : 1));
+}
+constexpr int kFormChannels[4] = {1, 4, 9, 16};
+constexpr const char* kChannelSuffix[4] = {"", "_dir", "_dir2", "_dir3"};
+inline int receive_channels(uint32_t flags)        // words per (receiver, bin, band)
+{
+    return kFormChannels[receive_channel_form(flags)];
+}
+constexpr uint32_t kReceiveChannelFlags = HARE_RECEIVE_DIRECTIONAL | HARE_RECEIVE_ORDER2 | HARE_RECEIVE_ORDER3;
 inline int receive_form(const ReceivePlan& p)      // DeviceModule::receive's first index
 {
     return p.map ? (p.args.sigma ? 4 : 3) : (!p.args.sigma ? 0 : (p.rain ? 2 : 1));
@@ -403,9 +419,11 @@ void free_receivers(const HipApi* H, Scene& s);
 int32_t scene_bands(const Scene& s, int32_t top);             // B of Model[top]'s absorption / scattering tables (1 without one)
 int receive_check_args(const char* who, const Scene& s, uint32_t flags, int32_t kind, int32_t top, int64_t n, int32_t bounces, int32_t n_bins, double bin_len,
                        int32_t frac_bits);
+// HARE_RECEIVE_ORDER2 / _ORDER3 without HARE_RECEIVE_DIRECTIONAL, or both: HARE_E_INVALID (receive_check_args' first check, and the source paths')
+int receive_check_order(const char* who, uint32_t flags);
 bool scene_has_scattering(const Scene& s, int32_t top);       // Model[top] has a scattering table (hare_receive_scatter)
 bool receive_rains(const Scene& s, int32_t top, uint32_t flags);      // rain needs a scattering table: without one the flag changes nothing
-// K x n_bins x B (x 4: HARE_RECEIVE_DIRECTIONAL) with K the scene's receiver count, or min_K where fewer are set (the checks that run before
+// K x n_bins x B (x 4: HARE_RECEIVE_DIRECTIONAL; x 9, x 16: with the order flags) with K the scene's receiver count, or min_K where fewer are set (the checks that run before
 // "no receivers" is found count one)
 size_t receive_hist_words(const Scene& s, int32_t top, int32_t n_bins, uint32_t flags, size_t min_K = 0);
 // flags: the call's HARE_RECEIVE_* bits; d_work: the loop's work array (with rain: HARE_RECEIVE_RAIN_WORK_BYTES(n));

@@ -500,7 +500,7 @@ class Spatial_Partition:
 
     def Receive_source(self, n: int, bounces: int, n_bins: int, bin_len: float, first_ray: int = 0, frac_bits: int = 40, top_index: int = 0,
                        out=None, rain: bool = False, directional: bool = False, time_limit: bool = False, direct: bool = False,
-                       image: bool = False, image2: bool = False):
+                       image: bool = False, image2: bool = False, *, order: int = 1):
         """hare_receive_source: Receive_batch with the rays and their state emitted on the device by the scene's source (set_source) --
         the rays first_ray .. first_ray + n - 1; nothing but the count goes up.  Returns what Receive_batch returns.  Calls over
         [0, k) and [k, n) sum to the histogram and detections of the one call.  direct (HARE_RECEIVE_DIRECT; include/hare_hip.h, "Direct
@@ -510,41 +510,43 @@ class Spatial_Partition:
         rays that left cast 0 specularly detect nothing; the pair list holds get_option("image_max_pairs") pairs (HareError, HARE_E_NOMEM,
         with the needed count when the scene yields more).  image2 (HARE_RECEIVE_IMAGE2, only with image; "Image sources (second
         order)"): the specular paths off two polygons are one deposit each, and in cast 2 the rays reflected specularly twice detect nothing;
-        the lists hold get_option("image2_max_cands") candidates and get_option("image2_max_paths") paths (HARE_E_NOMEM with both counts)."""
+        the lists hold get_option("image2_max_cands") candidates and get_option("image2_max_paths") paths (HARE_E_NOMEM with both counts).
+        order (with directional; HARE_RECEIVE_ORDER2 / _ORDER3, "Higher orders"): 2 or 3 widens the histogram to 9 or 16 channels."""
         return Spatial_Partition._receive_source([self], n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain, directional,
-                                                 time_limit, direct=direct, image=image, image2=image2)
+                                                 time_limit, direct=direct, image=image, image2=image2, order=order)
 
     def Receive_source_reduced(self, n: int, bounces: int, n_bins: int, bin_len: float, windows=None, levels=None, weight=None,
                                first_ray: int = 0, frac_bits: int = 40, top_index: int = 0, directional: bool = False,
-                               time_limit: bool = False, direct: bool = False, image: bool = False, image2: bool = False):
+                               time_limit: bool = False, direct: bool = False, image: bool = False, image2: bool = False, *, order: int = 1):
         """hare_receive_source_reduced: Receive_source with the histogram kept on the device and reduced there, as in
         Receive_batch_reduced; returns what that returns.  direct, image: as in Receive_source."""
         return Spatial_Partition._receive_source([self], n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, None, False, directional,
-                                                 time_limit, dict(windows=windows, levels=levels, weight=weight), direct=direct, image=image, image2=image2)
+                                                 time_limit, dict(windows=windows, levels=levels, weight=weight), direct=direct, image=image, image2=image2,
+                                                 order=order)
 
     @staticmethod
     def Receive_source_sharded(partitions, n: int, bounces: int, n_bins: int, bin_len: float, first_ray: int = 0, frac_bits: int = 40,
                                top_index: int = 0, out=None, rain: bool = False, directional: bool = False, time_limit: bool = False,
-                               direct: bool = False, image: bool = False, image2: bool = False):
+                               direct: bool = False, image: bool = False, image2: bool = False, *, order: int = 1):
         """hare_receive_source_sharded: Receive_source over several partitions (contiguous ray shards, histograms summed); byte-identical.
         The partitions must hold the same source and "source_seed".  direct, image: as in Receive_source; one partition makes each deposit."""
         return Spatial_Partition._receive_source(list(partitions), n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain,
-                                                 directional, time_limit, direct=direct, image=image, image2=image2)
+                                                 directional, time_limit, direct=direct, image=image, image2=image2, order=order)
 
     @staticmethod
     def _receive_source(parts, n, bounces, n_bins, bin_len, first_ray, frac_bits, top_index, out, rain, directional, time_limit, reduce=None,
-                        direct=False, image=False, image2=False):
+                        direct=False, image=False, image2=False, order=1):
         if not parts or any(p._kind != parts[0]._kind for p in parts):
             raise ValueError("need one or more partitions of the same kind")
         n = int(n)
         if n < 0:
             raise ValueError("n must be >= 0")
-        shape = parts[0]._receive_shape(top_index, n_bins, bool(directional))
+        shape = parts[0]._receive_shape(top_index, n_bins, bool(directional), order=order)
         K, nb, B = shape[:3]
         det = np.zeros((max(K, 0), 2), np.uint64)
         state_out = np.empty((1 + B, n), np.float64)
         ctr = capi.Counters()
-        flags = ((capi.RECEIVE_DIFFUSE_RAIN if rain else 0) | (capi.RECEIVE_DIRECTIONAL if directional else 0) |
+        flags = ((capi.RECEIVE_DIFFUSE_RAIN if rain else 0) | capi.channel_flags(directional, order) |
                  (capi.RECEIVE_TIME_LIMIT if time_limit else 0) | (capi.RECEIVE_DIRECT if direct else 0) |
                  (capi.RECEIVE_IMAGE if image else 0) | (capi.RECEIVE_IMAGE2 if image2 else 0))
         if reduce is not None:
@@ -565,64 +567,68 @@ class Spatial_Partition:
         check(rc)
         return hist, hist.astype(np.float64) * 2.0 ** -int(frac_bits), det, state_out, ctr.as_dict()
 
-    def _receive_shape(self, top_index: int, n_bins: int, directional: bool = False):
+    def _receive_shape(self, top_index: int, n_bins: int, directional: bool = False, *, order: int = 1):
         shape = (self.get_option("receivers"), int(n_bins), self._bands(top_index))
-        return shape + (4,) if directional else shape
+        capi.channel_flags(directional, order)                      # ValueError for an order that is none
+        return shape + (capi.ORDER_CHANNELS[int(order)],) if directional else shape
 
     @staticmethod
     def directional_signed(hist):
-        """The signed channels of a directional histogram [K, n_bins, B, 4]: X, Y, Z as int64 [K, n_bins, B, 3] (a view, no copy).
-        Channel 0 is W, the omni word a call without `directional` returns; channels 1, 2, 3 are X, Y, Z in world axes, positive for
-        sound ARRIVING FROM +x, +y, +z (the ambisonic sign convention), in two's complement at the same scale 2^-frac_bits."""
+        """The signed channels of a directional histogram [K, n_bins, B, C], C = 4, 9 or 16 (order 1, 2, 3): channels 1 .. C - 1 as int64
+        [K, n_bins, B, C - 1] (a view, no copy).  Channel 0 is W, the omni word a call without `directional` returns; channels 1, 2, 3
+        are X, Y, Z in world axes, positive for sound ARRIVING FROM +x, +y, +z (the ambisonic sign convention), in two's complement at
+        the same scale 2^-frac_bits; channels 4 .. C - 1 are ACN 4 .. C - 1 in SN3D ("Higher orders")."""
         hist = np.asarray(hist)
-        if hist.dtype != np.uint64 or hist.ndim < 1 or hist.shape[-1] != 4:
-            raise ValueError("need a directional histogram: uint64 [..., 4]")
+        if hist.dtype != np.uint64 or hist.ndim < 1 or hist.shape[-1] not in (4, 9, 16):
+            raise ValueError("need a directional histogram: uint64 [..., 4], [..., 9] or [..., 16]")
         return hist[..., 1:].view(np.int64)
 
     def _bands(self, top_index: int) -> int:
         return self.get_option("bands:%d" % int(top_index))          # the scene's own record, whoever set the table
 
     def Receive_batch(self, rays, bounces: int, n_bins: int, bin_len: float, energy=None, frac_bits: int = 40, top_index: int = 0,
-                      poly_origin1=None, poly_origin2=None, out=None, rain: bool = False, directional: bool = False, time_limit: bool = False):
+                      poly_origin1=None, poly_origin2=None, out=None, rain: bool = False, directional: bool = False, time_limit: bool = False,
+                      *, order: int = 1):
         """The bounce loop with the receiver step between its casts, from host buffers (hare_receive_batch).
         energy: None (every ray starts at L = 0, E = 1) or the state [1 + B, n] (row 0: L, rows 1..B: E).
         Returns (hist [K, n_bins, B] uint64, hist * 2^-frac_bits as float64, detections [K, 2] uint64, final state [1 + B, n],
         counters).  out (optional): the caller's uint64 histogram array [K, n_bins, B], as in Shoot_batch.  rain: diffuse rain
         (HARE_RECEIVE_DIFFUSE_RAIN) where the topology has a scattering table.  directional (HARE_RECEIVE_DIRECTIONAL): the histogram
         (and `out`) is [K, n_bins, B, 4], channels W, X, Y, Z (directional_signed gives X, Y, Z as int64); frac_bits must leave a sign
-        bit of headroom.  time_limit (HARE_RECEIVE_TIME_LIMIT): a ray whose path L has reached n_bins * bin_len after a hit is retired;
+        bit of headroom; order 2 or 3 with it (HARE_RECEIVE_ORDER2 / _ORDER3): [K, n_bins, B, 9] or [K, n_bins, B, 16], the channels
+        of "Higher orders" behind the four.  time_limit (HARE_RECEIVE_TIME_LIMIT): a ray whose path L has reached n_bins * bin_len after a hit is retired;
         histogram and detections[:, 0] stay as they are without it.  The energy floor is the scene's: options "receive_floor_bits"
         (F = 2^-f) and "receive_roulette" (include/hare_hip.h, "Termination")."""
         return Spatial_Partition._receive([self], rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1,
-                                          poly_origin2, out, rain, directional, time_limit)
+                                          poly_origin2, out, rain, directional, time_limit, order=order)
 
     def Receive_batch_reduced(self, rays, bounces: int, n_bins: int, bin_len: float, windows=None, levels=None, weight=None, energy=None,
                               frac_bits: int = 40, top_index: int = 0, poly_origin1=None, poly_origin2=None, directional: bool = False,
-                              time_limit: bool = False):
+                              time_limit: bool = False, *, order: int = 1):
         """hare_receive_batch_reduced (include/hare_hip.h, "receivers", "Reduction"): Receive_batch with the histogram kept on the device
         and reduced there.  windows: [(lo, hi), ...] bin ranges; levels: uint32 fractions (decay_levels); weight: uint32 [n_bins, B]
         (air_weights) or None.  Returns (sums [K, B, n_win, 4] uint64 -- S0 lo, S0 hi, S1 lo, S1 hi --, cross [K, B, n_lev] int32,
         detections, final state, counters): sums and cross are hist_reduce of the histogram Receive_batch returns."""
         return Spatial_Partition._receive([self], rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1, poly_origin2,
-                                          None, False, directional, time_limit, dict(windows=windows, levels=levels, weight=weight))
+                                          None, False, directional, time_limit, dict(windows=windows, levels=levels, weight=weight), order=order)
 
     @staticmethod
     def Receive_batch_sharded(partitions, rays, bounces: int, n_bins: int, bin_len: float, energy=None, frac_bits: int = 40,
                               top_index: int = 0, poly_origin1=None, poly_origin2=None, out=None, rain: bool = False,
-                              directional: bool = False, time_limit: bool = False):
+                              directional: bool = False, time_limit: bool = False, *, order: int = 1):
         """hare_receive_batch_sharded: Receive_batch over several partitions (contiguous ray shards, histograms summed); byte-identical.
         The partitions must agree in "receive_floor_bits" and "receive_roulette" (and, with roulette, in "scatter_seed")."""
         return Spatial_Partition._receive(list(partitions), rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1,
-                                          poly_origin2, out, rain, directional, time_limit)
+                                          poly_origin2, out, rain, directional, time_limit, order=order)
 
     @staticmethod
     def _receive(parts, rays, bounces, n_bins, bin_len, energy, frac_bits, top_index, poly_origin1, poly_origin2, out, rain=False, directional=False,
-                 time_limit=False, reduce=None):
+                 time_limit=False, reduce=None, order=1):
         if not parts or any(p._kind != parts[0]._kind for p in parts):
             raise ValueError("need one or more partitions of the same kind")
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
         n = rays.shape[0]
-        shape = parts[0]._receive_shape(top_index, n_bins, bool(directional))      # [K, n_bins, B], and the four channels with the flag
+        shape = parts[0]._receive_shape(top_index, n_bins, bool(directional), order=order)      # [K, n_bins, B], and the channels with the flag
         K, nb, B = shape[:3]
         e1 = None if poly_origin1 is None else np.ascontiguousarray(poly_origin1, np.int32)
         e2 = None if poly_origin2 is None else np.ascontiguousarray(poly_origin2, np.int32)
@@ -637,7 +643,7 @@ class Spatial_Partition:
         det = np.zeros((max(K, 0), 2), np.uint64)
         state_out = np.empty((1 + B, n), np.float64)
         ctr = capi.Counters()
-        flags = ((capi.RECEIVE_DIFFUSE_RAIN if rain else 0) | (capi.RECEIVE_DIRECTIONAL if directional else 0) |
+        flags = ((capi.RECEIVE_DIFFUSE_RAIN if rain else 0) | capi.channel_flags(directional, order) |
                  (capi.RECEIVE_TIME_LIMIT if time_limit else 0))
         if reduce is not None:
             w, n_win, win, n_lev, lev = _reduce_spec(reduce, nb, B)
@@ -659,17 +665,17 @@ class Spatial_Partition:
         return hist, hist.astype(np.float64) * 2.0 ** -int(frac_bits), det, state_out, ctr.as_dict()
 
     def hist_reduce(self, hist, windows=None, levels=None, weight=None):
-        """hare_hist_reduce: a histogram [K, n_bins, B] (or [K, n_bins, B, 4], directional: channel 0 is read) of uint64, as the receive
+        """hare_hist_reduce: a histogram [K, n_bins, B] (or [K, n_bins, B, C], directional with C = 4, 9 or 16: channel 0 is read) of uint64, as the receive
         calls return it, reduced on this partition's device (include/hare_hip.h, "receivers", "Reduction").  windows: [(lo, hi), ...] bin
         ranges; levels: uint32 fractions (decay_levels); weight: uint32 [n_bins, B] (air_weights) or None.  Returns (sums [K, B, n_win, 4]
         uint64 -- S0 lo, S0 hi, S1 lo, S1 hi --, cross [K, B, n_lev] int32)."""
         hist = np.ascontiguousarray(hist, np.uint64)
-        if hist.ndim not in (3, 4) or (hist.ndim == 4 and hist.shape[3] != 4):
-            raise ValueError("hist must be uint64 [K, n_bins, B] or [K, n_bins, B, 4]")
+        if hist.ndim not in (3, 4) or (hist.ndim == 4 and hist.shape[3] not in (4, 9, 16)):
+            raise ValueError("hist must be uint64 [K, n_bins, B] or [K, n_bins, B, C], C = 4, 9 or 16")
         K, nb, B = hist.shape[:3]
         w, n_win, win, n_lev, lev = _reduce_spec(dict(windows=windows, levels=levels, weight=weight), nb, B)
         sums, cross = np.zeros((K, B, n_win, 4), np.uint64), np.zeros((K, B, n_lev), np.int32)
-        check(lib.hare_hist_reduce(self._h, K, nb, B, 4 if hist.ndim == 4 else 1, ptr(hist), ptr(w), n_win, ptr(win), n_lev, ptr(lev),
+        check(lib.hare_hist_reduce(self._h, K, nb, B, hist.shape[3] if hist.ndim == 4 else 1, ptr(hist), ptr(w), n_win, ptr(win), n_lev, ptr(lev),
                                    ptr(sums), ptr(cross)))
         return sums, cross
 
@@ -688,12 +694,13 @@ class Spatial_Partition:
         return 64 * int(K) + 256
 
     def direct_device(self, n_weight: int, n_bins: int, bin_len: float, frac_bits: int, d_work: int, d_hist: int, d_detections: int,
-                      top_index: int = 0, directional: bool = False, stream: int = 0):
+                      top_index: int = 0, directional: bool = False, stream: int = 0, *, order: int = 1):
         """hare_direct_device on raw device addresses + a hipStream_t: the direct sound of the scene's source (include/hare_hip.h, "Direct
         sound") -- one visibility query and one deposit per receiver, standing for n_weight source rays -- accumulated into d_hist
-        (K x n_bins x B uint64, x 4 with directional) and d_detections (2 K uint64); d_work holds direct_work_bytes(K) bytes.
+        (K x n_bins x B uint64, x 4 with directional, x 9 or x 16 with order 2 or 3 beside it) and d_detections (2 K uint64); d_work holds
+        direct_work_bytes(K) bytes.
         Stream-ordered: no allocation, no free, no wait."""
-        check(lib.hare_direct_device(self._h, self._kind, int(top_index), int(n_weight), capi.RECEIVE_DIRECTIONAL if directional else 0,
+        check(lib.hare_direct_device(self._h, self._kind, int(top_index), int(n_weight), capi.channel_flags(directional, order),
                                      int(n_bins), float(bin_len), int(frac_bits), d_work or None, d_hist or None, d_detections or None,
                                      stream or None))
 
@@ -703,14 +710,14 @@ class Spatial_Partition:
         return 256 + 32 * int(P) + 136 * int(max_pairs)
 
     def Image_device(self, n_weight: int, n_bins: int, bin_len: float, frac_bits: int, max_pairs: int, d_work: int, d_hist: int,
-                     d_detections: int, top_index: int = 0, directional: bool = False, stream: int = 0):
+                     d_detections: int, top_index: int = 0, directional: bool = False, stream: int = 0, *, order: int = 1):
         """hare_image_device on raw device addresses + a hipStream_t: the first-order image sources of the scene's source
         (include/hare_hip.h, "Image sources (first order)") -- the pair search receivers x polygons, two shadow rays per accepted pair and
         one deposit per pair with both legs free, standing for n_weight source rays -- accumulated into d_hist (K x n_bins x B uint64,
-        x 4 with directional) and d_detections (2 K uint64); d_work holds image_work_bytes(K, P, max_pairs) bytes on a 16-byte boundary
+        x 4 with directional, x 9 or x 16 with order 2 or 3) and d_detections (2 K uint64); d_work holds image_work_bytes(K, P, max_pairs) bytes on a 16-byte boundary
         and its first uint64 receives the number of pairs found (more than max_pairs: nothing was deposited).  Stream-ordered: no
         allocation, no free, no wait."""
-        check(lib.hare_image_device(self._h, self._kind, int(top_index), int(n_weight), capi.RECEIVE_DIRECTIONAL if directional else 0,
+        check(lib.hare_image_device(self._h, self._kind, int(top_index), int(n_weight), capi.channel_flags(directional, order),
                                     int(n_bins), float(bin_len), int(frac_bits), int(max_pairs), d_work or None, d_hist or None,
                                     d_detections or None, stream or None))
 
@@ -721,14 +728,14 @@ class Spatial_Partition:
         return 256 + 32 * int(P) + 32 * int(max_cands) + 212 * int(max_paths)
 
     def Image2_device(self, n_weight: int, n_bins: int, bin_len: float, frac_bits: int, max_cands: int, max_paths: int, d_work: int, d_hist: int,
-                      d_detections: int, top_index: int = 0, directional: bool = False, stream: int = 0):
+                      d_detections: int, top_index: int = 0, directional: bool = False, stream: int = 0, *, order: int = 1):
         """hare_image2_device on raw device addresses + a hipStream_t: the second-order image sources of the scene's source
         (include/hare_hip.h, "Image sources (second order)") -- the candidate stage polygons x polygons, the path stage receivers x
         candidates, three shadow rays per path and one deposit per path with all legs free, standing for n_weight source rays --
         accumulated into d_hist and d_detections (shaped as Image_device's); d_work holds image2_work_bytes(P, max_cands, max_paths) bytes on
         a 16-byte boundary and its first two uint64 receive the candidates and the paths found (either beyond its list: nothing was
         deposited).  Stream-ordered: no allocation, no free, no wait."""
-        check(lib.hare_image2_device(self._h, self._kind, int(top_index), int(n_weight), capi.RECEIVE_DIRECTIONAL if directional else 0,
+        check(lib.hare_image2_device(self._h, self._kind, int(top_index), int(n_weight), capi.channel_flags(directional, order),
                                      int(n_bins), float(bin_len), int(frac_bits), int(max_cands), int(max_paths), d_work or None, d_hist or None,
                                      d_detections or None, stream or None))
 
@@ -741,11 +748,11 @@ class Spatial_Partition:
     def receive_device(self, n: int, d_rays: int, bounces: int, n_bins: int, bin_len: float, frac_bits: int, d_state: int, d_work: int,
                        d_events_last: int, d_hist: int, d_detections: int, top_index: int = 0, d_excl1: int = 0, d_excl2: int = 0,
                        d_counters: int = 0, stream: int = 0, flags: int = 0, rain: bool = False, directional: bool = False,
-                       time_limit: bool = False, direct: bool = False, image: bool = False, image2: bool = False):
+                       time_limit: bool = False, direct: bool = False, image: bool = False, image2: bool = False, *, order: int = 1):
         """hare_receive_device on raw device addresses (e.g. torch.Tensor.data_ptr()) + a hipStream_t: d_state (1 + B) x n doubles is read
         and overwritten, d_hist (K x n_bins x B uint64) and d_detections (2 K uint64) are accumulated into.  Stream-ordered.  rain: diffuse
         rain (HARE_RECEIVE_DIFFUSE_RAIN); d_work then holds receive_work_bytes(n, rain=True) bytes.  directional
-        (HARE_RECEIVE_DIRECTIONAL): d_hist is K x n_bins x B x 4 uint64, channels W, X, Y, Z.  time_limit (HARE_RECEIVE_TIME_LIMIT): as
+        (HARE_RECEIVE_DIRECTIONAL): d_hist is K x n_bins x B x 4 uint64, channels W, X, Y, Z (order 2, 3: x 9, x 16).  time_limit (HARE_RECEIVE_TIME_LIMIT): as
         in Receive_batch; a retired ray keeps the ray and the state of the cast that retired it.  direct (HARE_RECEIVE_DIRECT): cast 0
         detects nothing -- the rays are the scene's source's, and direct_device deposits their direct sound."""
         if direct:
@@ -758,8 +765,7 @@ class Spatial_Partition:
             flags |= capi.RECEIVE_TIME_LIMIT
         if rain:
             flags |= capi.RECEIVE_DIFFUSE_RAIN
-        if directional:
-            flags |= capi.RECEIVE_DIRECTIONAL
+        flags |= capi.channel_flags(directional, order)
         check(lib.hare_receive_device(self._h, self._kind, int(top_index), int(n), d_rays or None, d_excl1 or None, d_excl2 or None,
                                       int(bounces), int(flags), int(n_bins), float(bin_len), int(frac_bits), d_state or None, d_work or None,
                                       d_events_last or None, d_hist or None, d_detections or None, d_counters or None, stream or None))

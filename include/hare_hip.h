@@ -92,6 +92,10 @@ extern "C" {
                                        /* once per (receiver, polygon, polygon) path and cast 2's receiver step is skipped for the rays reflected          */
                                        /* specularly twice ("receivers", "Image sources (second order)").  0x10000: the first bit above the developer      */
                                        /* bits 0x1000 .. 0x8000 (0x8000 is the cull audit), below the internal bits 0x40000 and 0x80000                    */
+#define HARE_RECEIVE_ORDER2 131072u    /* wherever HARE_RECEIVE_DIRECTIONAL is accepted, and only together with it: nine channels per histogram word,      */
+                                       /* ambisonic orders 0..2 ("receivers", "Higher orders").  0x20000                                                   */
+#define HARE_RECEIVE_ORDER3 1048576u   /* the same, sixteen channels, orders 0..3; not together with HARE_RECEIVE_ORDER2.  0x100000: the first bit above   */
+                                       /* the internal bits 0x40000 and 0x80000                                                                            */
 
 /* Hare.Geometry.Ray (Hare_Geometry_Primitives.cs:393-429): origin + direction.  Ray_ID/ThreadID
  * only serve the reference's mailbox pool and are not needed here. 48 bytes. */
@@ -560,6 +564,32 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * 1/2); detections keep their shape and values; nothing about draws, choices, rays, state, suppression or detections changes.  d_hist of
  * the device call and hist of the host calls are four times as large, and the bound on the histogram becomes K x n_bins x B x 4 <= 2^27.
  *
+ * Higher orders (flags HARE_RECEIVE_ORDER2 and HARE_RECEIVE_ORDER3; ambisonic orders 2 and 3).  Each is valid only together with
+ * HARE_RECEIVE_DIRECTIONAL; either one without it, or both together, is HARE_E_INVALID, the first check of the call.  Each is accepted
+ * wherever HARE_RECEIVE_DIRECTIONAL is -- hare_receive_device / _batch / _batch_sharded, hare_receive_source / _sharded, the two _reduced
+ * calls, and the `flags` of hare_direct_device, hare_image_device and hare_image2_device -- and combines with diffuse rain, the
+ * termination rules, receiver maps, HARE_RECEIVE_DIRECT, HARE_RECEIVE_IMAGE and HARE_RECEIVE_IMAGE2 as the first-order flag does.  The
+ * histogram has C = 9 (order 2) or C = 16 (order 3) channels, channel innermost:
+ *
+ *   hist[((k*n_bins + bin)*B + b)*C + ch]        ch 0..3 = W, X, Y, Z;  ch 4..C-1 = ACN 4..C-1, SN3D        (K x n_bins x B x C uint64 words)
+ *
+ * Channels 0..3 are exactly those of "Directional": the same values as the call with HARE_RECEIVE_DIRECTIONAL alone.  Channels 4..15 are
+ * the real spherical harmonics of orders 2 and 3 in ACN order and SN3D normalisation, evaluated on the same arrival vector
+ * a = (x, y, z) -- the receiver step's, the rain deposit's, the direct deposit's or the image paths' last leg, each as it is defined in
+ * its section.  They are polynomials of a: FP64, no contraction, in exactly this order, the six constants the correctly rounded doubles:
+ *
+ *   c3 = sqrt(3.0);  c3h = 0.5*c3;  c15 = sqrt(15.0);  c15h = 0.5*c15;  c58 = sqrt(0.625);  c38 = sqrt(0.375)
+ *   xx = x*x;  yy = y*y;  zz = z*z;  d = xx - yy;  f = 5.0*zz - 1.0
+ *   Y4  = c3*(x*y)      Y5  = c3*(y*z)     Y6  = 1.5*zz - 0.5     Y7 = c3*(x*z)     Y8 = c3h*d
+ *   Y9  = c58*(y*(3.0*xx - yy))            Y10 = c15*((x*y)*z)    Y11 = c38*(y*f)   Y12 = z*(2.5*zz - 1.5)
+ *   Y13 = c38*(x*f)     Y14 = c15h*(z*d)   Y15 = c58*(x*(xx - 3.0*yy))
+ *   v = m_b * Y_ch;   v = 0 unless v == v (NaN);   v = min(max(v, -2^62), 2^62);   s_ch = (int64) rint(v);   hist[... + ch] += (uint64) s_ch
+ *
+ * with m_b as in "Directional".  What the caller has to know: |Y_ch| <= 1 up to rounding for a unit a, so the headroom rule of
+ * "Directional" holds unchanged; order 2 of a call equals the first nine channels of order 3 of the same call; nothing about draws,
+ * choices, rays, state, suppression or detections changes.  The bound on the histogram becomes K x n_bins x B x C <= 2^27.
+ * hare_hist_reduce_device / hare_hist_reduce and the _reduced receive calls accept `channels` 9 and 16 and read word 0, as they do for 4.
+ *
  * Termination (flag HARE_RECEIVE_TIME_LIMIT; scene options "receive_floor_bits" and "receive_roulette").  Two opt-in rules that retire a
  * ray before the call's `bounces` are spent.  Without the flag and with "receive_floor_bits" 0 nothing in this section applies.  Both are
  * decided in cast c for a ray that hit in cast c and would be reflected (c < bounces - 1), AFTER that cast's state update: after the
@@ -842,7 +872,7 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * Reduction (hare_hist_reduce_device, hare_hist_reduce, hare_receive_batch_reduced, hare_receive_source_reduced).  What a map's user reads
  * from a histogram is a handful of numbers per receiver and band; the reduction forms them on the device, where the histogram lies, in
  * integer arithmetic only -- a function of the inputs, bit for bit, like the histogram itself.  Inputs: a histogram laid out as the
- * receive calls write it, K receivers x n_bins bins x B bands, with `channels` 1 or 4 words per entry (4: HARE_RECEIVE_DIRECTIONAL's; the
+ * receive calls write it, K receivers x n_bins bins x B bands, with `channels` 1, 4, 9 or 16 words per entry (4: HARE_RECEIVE_DIRECTIONAL's, 9 and 16: the higher orders'; the
  * word of channel 0, W, is the one read):
  *
  *   h(k, i, b) = hist[((k * n_bins + i) * B + b) * channels]                                             (uint64)
@@ -909,7 +939,7 @@ HARE_API int hare_emit_device(hare_scene *s, int64_t n, int64_t first_ray, void 
  * Always a launch per cast (the scene option "bounce_fused" does not apply; results are the same either way).
  *   d_rays, d_excl1, d_excl2, d_work (2 n int32), d_events_last   as in hare_bounce_device
  *   d_state        (1 + B) planes of n doubles: plane 0 is L, planes 1..B are E.  Read and overwritten
- *   d_hist         K x n_bins x B uint64 (x 4 with HARE_RECEIVE_DIRECTIONAL), ACCUMULATED;  d_detections: 2 K uint64, ACCUMULATED
+ *   d_hist         K x n_bins x B uint64 (x 4 with HARE_RECEIVE_DIRECTIONAL; x 9, x 16 with the order flags), ACCUMULATED;  d_detections: 2 K uint64, ACCUMULATED
  *   d_counters     nullable: totals, ACCUMULATED (as hare_bounce_device's; the rain's occlusion queries are not counted)
  *   flags          HARE_SHOOT_COUNT_WORK / HARE_SHOOT_SIMPLE_KERNEL (the casts), HARE_RECEIVE_DIFFUSE_RAIN, HARE_RECEIVE_DIRECTIONAL,
  *                  HARE_RECEIVE_TIME_LIMIT, HARE_RECEIVE_DIRECT, HARE_RECEIVE_IMAGE and HARE_RECEIVE_IMAGE2 (suppression only: "Direct sound",
@@ -927,13 +957,13 @@ HARE_API int hare_receive_device(hare_scene *s, int32_t kind, int32_t top_index,
                                  void *d_detections, void *d_counters, void *stream);
 /* The direct sound's deposit on DEVICE buffers ("receivers", "Direct sound"): one visibility query and one deposit per receiver of the
  * scene, from the scene's source, standing for n_weight source rays.  Stream-ordered like hare_emit_device: no allocation, no free, no
- * wait.  d_hist (K x n_bins x B uint64, x 4 with HARE_RECEIVE_DIRECTIONAL, the only flag read) and d_detections (2 K uint64) are
+ * wait.  d_hist (K x n_bins x B uint64, x 4 with HARE_RECEIVE_DIRECTIONAL, x 9 or x 16 with HARE_RECEIVE_ORDER2 / _ORDER3 beside it: the only flags read) and d_detections (2 K uint64) are
  * ACCUMULATED; d_work is scratch of HARE_DIRECT_WORK_BYTES(K) bytes (K shadow rays, t_max, exclusion words and flags), B the source's.
  * Checked in this order: HARE_E_INVALID unless 1 <= n_weight <= 2^53, kind, top_index, n_bins >= 1, bin_len finite and > 0,
  * 0 <= frac_bits <= 62, the histogram within 2^27 words, no buffer null and none overlapping another, and a source whose B is not
  * the topology's; then HARE_E_NODEVICE; then HARE_E_STATE: no source, no receivers, or the partition not built. */
 #define HARE_DIRECT_WORK_BYTES(K) (64 * (int64_t)(K) + 256)
-HARE_API int hare_direct_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL only */,
+HARE_API int hare_direct_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL, _ORDER2, _ORDER3 only */,
                                 int32_t n_bins, double bin_len, int32_t frac_bits, void *d_work, void *d_hist, void *d_detections, void *stream);
 /* The first-order image sources' deposit on DEVICE buffers ("receivers", "Image sources (first order)"): the pair search receivers x
  * polygons, one occlusion query of two shadow rays per accepted pair and one deposit per pair with both legs free, from the scene's source,
@@ -944,7 +974,7 @@ HARE_API int hare_direct_device(hare_scene *s, int32_t kind, int32_t top_index, 
  * than max_pairs pairs are found nothing is deposited; the caller reads the count from the first word behind the stream.
  * Checked as hare_direct_device checks, in its order, plus 1 <= max_pairs <= 2^26 and the work array's boundary (HARE_E_INVALID). */
 #define HARE_IMAGE_WORK_BYTES(K, P, max_pairs) (256 + 32 * (int64_t)(P) + 136 * (int64_t)(max_pairs) + 0 * (int64_t)(K))
-HARE_API int hare_image_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL only */,
+HARE_API int hare_image_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL, _ORDER2, _ORDER3 only */,
                                int32_t n_bins, double bin_len, int32_t frac_bits, int64_t max_pairs, void *d_work, void *d_hist,
                                void *d_detections, void *stream);
 /* The second-order image sources' deposit on DEVICE buffers ("receivers", "Image sources (second order)"): the candidate stage polygons x
@@ -959,12 +989,12 @@ HARE_API int hare_image_device(hare_scene *s, int32_t kind, int32_t top_index, i
 #define HARE_IMAGE2_WORK_BYTES(P, max_cands, max_paths) (256 + 32 * (int64_t)(P) + 32 * (int64_t)(max_cands) + 212 * (int64_t)(max_paths))
 /* hare_receive_device with HARE_RECEIVE_IMAGE2: the bytes d_work holds behind its other contents ("Image sources (second order)", "The byte array") */
 #define HARE_RECEIVE_IMAGE2_WORK_BYTES(n) ((int64_t)(n))
-HARE_API int hare_image2_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL only */,
+HARE_API int hare_image2_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL, _ORDER2, _ORDER3 only */,
                                 int32_t n_bins, double bin_len, int32_t frac_bits, int64_t max_cands, int64_t max_paths, void *d_work,
                                 void *d_hist, void *d_detections, void *stream);
 /* The same from host buffers (threading and staging as hare_bounce_batch's last-cast-only path: one enqueue, one synchronisation; no
  * events are downloaded).  state_in nullable (every ray starts at L = 0, E = 1); state_out nullable ((1 + B) x n, as d_state).
- * hist (K x n_bins x B, x 4 with HARE_RECEIVE_DIRECTIONAL) and detections (2 K) are WRITTEN, not accumulated; ctr nullable: counters summed over the casts.  flags as
+ * hist (K x n_bins x B, x 4 with HARE_RECEIVE_DIRECTIONAL, x 9 / x 16 with the order flags) and detections (2 K) are WRITTEN, not accumulated; ctr nullable: counters summed over the casts.  flags as
  * hare_receive_device's (the call sizes the rain's scratch itself). */
 HARE_API int hare_receive_batch(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, const hare_ray *rays,
                                 const int32_t *excl1, const int32_t *excl2, int32_t bounces, uint32_t flags, int32_t n_bins,
@@ -996,7 +1026,7 @@ HARE_API int hare_receive_source_sharded(hare_scene *const *scenes, int32_t n_sc
 /* The reduction of a histogram ("receivers", "Reduction" above) on DEVICE buffers: one launch, stream-ordered like hare_shoot_device -- no
  * allocation, no free, no wait.  win (2 n_win) and levels (n_lev) are HOST arrays, read at the call (they travel as kernel arguments);
  * d_weight nullable; d_sums (K x B x n_win x 4 uint64; unused when n_win = 0) and d_cross (K x B x n_lev int32; unused when n_lev = 0) are
- * WRITTEN, every word once.  Checked before anything runs (HARE_E_INVALID): 1 <= K <= 65 536, n_bins >= 1, 1 <= B <= 8, channels 1 or 4,
+ * WRITTEN, every word once.  Checked before anything runs (HARE_E_INVALID): 1 <= K <= 65 536, n_bins >= 1, 1 <= B <= 8, channels 1, 4, 9 or 16,
  * K x n_bins x B x channels <= 2^27, 0 <= n_win <= 16, 0 <= n_lev <= 32 and not both 0, every window 0 <= lo <= hi <= n_bins, null
  * buffers, and sums or crossings overlapping each other, the histogram or the weights.  Then HARE_E_NODEVICE, then HARE_E_STATE.  The
  * scene names the device; its geometry is not read. */
@@ -1009,7 +1039,7 @@ HARE_API int hare_hist_reduce(hare_scene *s, int32_t K, int32_t n_bins, int32_t 
                               const uint32_t *levels, uint64_t *sums, int32_t *cross);
 /* hare_receive_batch / hare_receive_source with `hist` replaced by the reduction's arguments: the loop runs as in the parent call, the
  * histogram stays on the device, the reduction is enqueued behind the last cast on the same stream, and sums, crossings, detections,
- * state and counters come down -- never the histogram.  K and B are the scene's; channels is 4 with HARE_RECEIVE_DIRECTIONAL, else 1.
+ * state and counters come down -- never the histogram.  K and B are the scene's; channels is 4 with HARE_RECEIVE_DIRECTIONAL (9, 16 with the order flags), else 1.
  * sums and cross are what hare_hist_reduce gives on the histogram the parent call returns.  Checks: the parent's, then the reduction's. */
 HARE_API int hare_receive_batch_reduced(hare_scene *s, int32_t kind, int32_t top_index, int64_t n, const hare_ray *rays,
                                         const int32_t *excl1, const int32_t *excl2, int32_t bounces, uint32_t flags, int32_t n_bins,

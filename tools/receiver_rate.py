@@ -11,7 +11,9 @@ With --rain (B = 8, K = 1 and 8; SIGMA from --scatter, default 0.3), the scatter
 path on (summed over receivers and bands), with rain and without.
 With --directional (B = 8; K = 8 and 64, or K = 1 and 8 with --rain; combinable with --scatter and --rain), every loop of the run is timed
 again with HARE_RECEIVE_DIRECTIONAL in the same run (the _dir kernels, a four-fold histogram): dir_ms, scatter_dir_ms, rain_dir_ms and
-their cost over the same loop without the flag.
+their cost over the same loop without the flag.  With --order 2,3 beside it, the specular loop again at those ambisonic orders
+(HARE_RECEIVE_ORDER2 / _ORDER3: the _dir2 / _dir3 kernels, nine and sixteen channels): dir2_ms, dir3_ms, the highest order with
+"receive_aggregate" 0 too, and next to every dir row the spread of its timed runs, (max - min) / median in percent.
 With --time-limit and / or --floor-bits N [--roulette] (the header's "Termination"), the specular loop of every (K, B) again with the time
 limit, with the energy floor 2^-N, and with both where both are given: cut_*_ms against ms of the same row, and the share of the rays
 still live -- over all casts (the loop's ray counter over n x bounces) and in the casts 1, 2, 4, 8, ... (the counter's difference between
@@ -40,7 +42,7 @@ counts and its device time (events around the call; median, min .. max) -- then,
 "image2_max_cands" / "image2_max_paths" set to the next powers of two and `direct + image` against `direct + image + image2`, interleaved,
 wall time and the same noise figure.
 Prints ONE JSON line.  usage: python tools/receiver_rate.py [hall|cathedral] [--rays N] [--bounces B] [--reps R] [--host] [--quick]
-                                                          [--scatter SIGMA] [--rain] [--directional] [--time-limit] [--floor-bits N [--roulette]]
+                                                          [--scatter SIGMA] [--rain] [--directional [--order N[,N]]] [--time-limit] [--floor-bits N [--roulette]]
                                                           [--source [--direct [--image [--image-cull N] [--image2 [--image2-prune N]]]]] [--map K[,K..]]"""
 import argparse
 import json
@@ -65,6 +67,8 @@ ap.add_argument("--scatter", type=float, default=None, metavar="SIGMA",
                 help="K = 8, B = 8 only, and the loop again with a scattering table of SIGMA everywhere (scene option scatter_seed 1)")
 ap.add_argument("--rain", action="store_true", help="K = 1 and 8, B = 8: the scattering loop with and without diffuse rain, and its noise")
 ap.add_argument("--directional", action="store_true", help="B = 8: every loop again with HARE_RECEIVE_DIRECTIONAL, in the same run")
+ap.add_argument("--order", default="", metavar="N[,N]", help="with --directional: the loop again at ambisonic order 2 and / or 3 (HARE_RECEIVE_ORDER2 / _ORDER3), "
+                "each row with the spread of its timed runs; the highest order also with \"receive_aggregate\" 0")
 ap.add_argument("--time-limit", action="store_true", help="the loop again with HARE_RECEIVE_TIME_LIMIT")
 ap.add_argument("--floor-bits", type=int, default=0, metavar="N", help="the loop again with the energy floor 2^-N (scene option receive_floor_bits)")
 ap.add_argument("--roulette", action="store_true", help="with --floor-bits: Russian roulette under the floor (scene option receive_roulette)")
@@ -342,13 +346,15 @@ def timed(fn, reps):
         fn()
         e1.record(); torch.cuda.synchronize()
         ms.append(e0.elapsed_time(e1))
+    global last_spread_pct
+    last_spread_pct = round(100.0 * (max(ms) - min(ms)) / float(np.median(ms)), 2)      # of the call just timed: (max - min) / median
     return float(np.median(ms))
 
 
 ms_bounce = timed(bounce, a.reps)
 out = {"scene": a.scene, "domain": D, "rays": n, "bounces": nb, "n_bins": N_BINS, "bounce_ms": round(ms_bounce, 3),
        "bounce_Mcasts_s": round(n * nb / ms_bounce / 1e3, 1), "receive": []}
-cases = [(1, 8), (8, 8)] if a.rain else [(8, 8), (64, 8)] if a.directional else ([(8, 8)] if (a.quick or a.scatter is not None) else [(K, B) for K in (1, 8, 64) for B in (1, 8)])
+cases = [(1, 8), (8, 8)] if a.rain else ([(8, 8)] if a.quick else [(8, 8), (64, 8)]) if a.directional else ([(8, 8)] if (a.quick or a.scatter is not None) else [(K, B) for K in (1, 8, 64) for B in (1, 8)])
 d_work_rain = torch.zeros(H.Voxel_Grid.receive_work_bytes(n, rain=True), dtype=torch.uint8, device="cuda") if a.rain else None
 for K, B in cases:
     c, r = receivers(K)
@@ -358,12 +364,13 @@ for K, B in cases:
     init = torch.cat([torch.zeros((1, n), dtype=torch.float64, device="cuda"), torch.ones((B, n), dtype=torch.float64, device="cuda")])
     d_hist = torch.zeros(K * N_BINS * B, dtype=torch.int64, device="cuda")
     d_det = torch.zeros(2 * K, dtype=torch.int64, device="cuda")
-    d_hist4 = torch.zeros(K * N_BINS * B * 4, dtype=torch.int64, device="cuda") if a.directional else None
+    orders = [int(x) for x in a.order.split(",") if x] if a.directional else []
+    d_hist4 = torch.zeros(K * N_BINS * B * H.capi.ORDER_CHANNELS[max(orders + [1])], dtype=torch.int64, device="cuda") if a.directional else None
 
-    def receive(rain=False, directional=False, time_limit=False, casts=nb, d_counters=0):
+    def receive(rain=False, directional=False, time_limit=False, casts=nb, d_counters=0, order=1):
         g.receive_device(n, d_rays.data_ptr(), casts, N_BINS, BIN_LEN, FRAC, d_state.data_ptr(), (d_work_rain if rain else d_work).data_ptr(),
                          d_last.data_ptr(), (d_hist4 if directional else d_hist).data_ptr(), d_det.data_ptr(), stream=st, rain=rain,
-                         directional=directional, time_limit=time_limit, d_counters=d_counters)
+                         directional=directional, time_limit=time_limit, d_counters=d_counters, **({"order": order} if order > 1 else {}))
 
     def timed_cut(row, key, time_limit, floor_bits):                     # the specular loop under a rule, against row["ms"]
         g.set_option("receive_floor_bits", floor_bits).set_option("receive_roulette", int(a.roulette and floor_bits > 0))
@@ -381,9 +388,10 @@ for K, B in cases:
         row[key + "_live_in_cast"] = {c: round((cast_rays(c + 1) - cast_rays(c)) / n, 4) for c in at}
         g.set_option("receive_floor_bits", 0).set_option("receive_roulette", 0)
 
-    def timed_dir(row, key, base_key, rain=False):                       # the same loop with the flag, against row[base_key]
-        ms = timed(lambda: (d_state.copy_(init), receive(rain, True)), a.reps)
+    def timed_dir(row, key, base_key, rain=False, order=1):              # the same loop with the flag, against row[base_key]
+        ms = timed(lambda: (d_state.copy_(init), receive(rain, True, order=order)), a.reps)
         row[key] = round(ms - ms_copy, 3)
+        row[key.replace("ms", "spread_pct")] = last_spread_pct
         row[key.replace("ms", "over_pct")] = round(100.0 * (ms - ms_copy - row[base_key]) / row[base_key], 1)
         row[key.replace("ms", "over_bounce_pct")] = round(100.0 * (ms - ms_copy - ms_bounce) / ms_bounce, 1)
     row = {"K": K, "B": B}
@@ -402,6 +410,12 @@ for K, B in cases:
         g.set_option("receive_aggregate", 0)
         timed_dir(row, "dir_naive_ms", "ms")
         g.set_option("receive_aggregate", 1)
+        for order in orders:
+            timed_dir(row, "dir%d_ms" % order, "ms", order=order)
+        if orders:
+            g.set_option("receive_aggregate", 0)
+            timed_dir(row, "dir%d_naive_ms" % max(orders), "ms", order=max(orders))
+            g.set_option("receive_aggregate", 1)
     if a.time_limit:
         timed_cut(row, "cut_time", True, 0)
     if a.floor_bits:
