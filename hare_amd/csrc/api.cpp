@@ -13,12 +13,13 @@
 #include <mutex>
 #include <new>
 #include <string>
-#include <thread>
+#include <thread>      // hardware_concurrency
 #include <vector>
 
 #include "../../include/hare_hip.h"
 #include "scene.h"
 #include "launch.h"
+#include "fan_out.h"
 
 // the embedded gfx950 code object (embed.S)
 extern "C" const unsigned char hare_kernels_co[];
@@ -195,21 +196,6 @@ void hare_scene_destroy(hare_scene* s)
     }
     delete s;
 }
-
-#define GUARD_BEGIN try {
-#define GUARD_END                                               \
-    }                                                           \
-    catch (const std::bad_alloc&)                               \
-    {                                                           \
-        set_error("out of host memory");                        \
-        return HARE_E_NOMEM;                                    \
-    }                                                           \
-    catch (...)                                                 \
-    {                                                           \
-        set_error("unexpected C++ exception");                  \
-        return HARE_E_INVALID;                                  \
-    }
-
 
 // Build the grid on the GPU when a device is present (HARE_BUILD=host forces the host builder; both
 // produce identical lists).  *on_gpu = false: the caller runs the host builder.
@@ -503,26 +489,13 @@ static int batch_impl(hare_scene* s, int32_t kind, int32_t top_index, int64_t n,
     }
     DeviceGuard dev_guard(hip_api(nullptr), s->device);
     const HipApi* H = nullptr;
-    Scene::BatchCtx* c = nullptr;
-    {
-        std::unique_lock<std::mutex> lk(s->mu);
-        int rc = ensure_device(*s, H);
-        if (rc) return rc;
-        if (ctr) memset(ctr, 0, sizeof *ctr);
-        if (n == 0) return HARE_OK;
-        // a free staging context, or wait for one: concurrent callers (Pachyderm's worker threads) run side by side
-        s->cv.wait(lk, [&] { for (Scene::BatchCtx& x : s->ctx) if (!x.busy) return true; return false; });
-        for (Scene::BatchCtx& x : s->ctx)
-            if (!x.busy && x.cap >= n) { c = &x; break; }          // prefer one that is already large enough
-        if (!c)
-            for (Scene::BatchCtx& x : s->ctx)
-                if (!x.busy) { c = &x; break; }
-        c->busy = true;
-    }
-    struct Release {
-        hare_scene* s; Scene::BatchCtx* c;
-        ~Release() { { std::lock_guard<std::mutex> lk(s->mu); c->busy = false; } s->cv.notify_one(); }
-    } release{s, c};
+    std::unique_lock<std::mutex> lk(s->mu);
+    int rc = ensure_device(*s, H);
+    if (rc) return rc;
+    if (ctr) memset(ctr, 0, sizeof *ctr);
+    if (n == 0) return HARE_OK;
+    const CtxLease lease(*s, lk, [n](const Scene::BatchCtx& x) { return x.cap >= n; });       // (releases lk)
+    Scene::BatchCtx* const c = lease.get();
     constexpr int kMaxChunks = 16;
     if (n > c->cap) {
         for (void** p : {&c->d_rays, &c->d_e1, &c->d_e2, &c->d_out, &c->d_tmax, &c->d_occ, &c->d_slim}) dev_free(H, *p);
@@ -563,11 +536,8 @@ static int batch_impl(hare_scene* s, int32_t kind, int32_t top_index, int64_t n,
         if (!c->st[k]) HIP_TRY(H->StreamCreate(&c->st[k]));
     hare_counters parts[kMaxChunks];
     memset(parts, 0, sizeof parts);
-    int rcs[kMaxChunks];
-    for (int& r : rcs) r = HARE_OK;
-    std::string errs[kMaxChunks];
     auto chunk_body = [&](int k, hipStream_t st) -> int {
-        const int64_t lo = (int64_t)((__int128)n * k / K), m = (int64_t)((__int128)n * (k + 1) / K) - lo;
+        const int64_t lo = part_range(n, k, K).lo, m = part_range(n, k, K).size();
         if (m == 0) return HARE_OK;
         hare_ray* dr = (hare_ray*)c->d_rays + lo;
         int32_t* de1 = (int32_t*)c->d_e1 + lo;
@@ -608,40 +578,13 @@ static int batch_impl(hare_scene* s, int32_t kind, int32_t top_index, int64_t n,
         if (r != HARE_OK) (void)H->StreamSynchronize(st);
         return r;
     };
-    auto guarded = [&](int k) {
-        try {
-            rcs[k] = chunk(k);
-        } catch (...) {
-            rcs[k] = HARE_E_NOMEM;
-            set_error("hare_shoot_batch: exception in a chunk");
-        }
-        if (rcs[k] != HARE_OK) errs[k] = hare_last_error();     // thread-local: carry it to the caller's thread
-    };
-    {
-        std::vector<std::thread> workers;
-        workers.reserve((size_t)K);
-        for (int k = 1; k < K; ++k) {
-            try {
-                workers.emplace_back(guarded, k);
-            } catch (...) {
-                guarded(k);          // no thread to be had: run the chunk here (a started thread must never be left unjoined)
-            }
-        }
-        guarded(0);
-        for (auto& w : workers) w.join();
+    const FanResult f = fan_out(K, "hare_shoot_batch: exception in a chunk", chunk);
+    if (f.rc != HARE_OK) {
+        set_error(f.text);
+        return f.rc;
     }
-    for (int k = 0; k < K; ++k)
-        if (rcs[k] != HARE_OK) {
-            set_error(errs[k]);
-            return rcs[k];
-        }
-    if (ctr) {
-        uint64_t* dst = reinterpret_cast<uint64_t*>(ctr);
-        for (int k = 0; k < K; ++k) {
-            const uint64_t* src = reinterpret_cast<const uint64_t*>(&parts[k]);
-            for (size_t w = 0; w < sizeof(hare_counters) / 8; ++w) dst[w] += src[w];
-        }
-    }
+    if (ctr)
+        for (int k = 0; k < K; ++k) add_counters(*ctr, parts[k]);
     return HARE_OK;
     GUARD_END
 }
@@ -660,67 +603,52 @@ int hare_shoot_batch(hare_scene* s, int32_t kind, int32_t top_index, int64_t n, 
     return batch_impl(s, kind, top_index, n, rays, excl1, excl2, flags, out, ctr, nullptr, nullptr);
 }
 
+// hare_shoot_batch_sharded and (occl) hare_occluded_batch_sharded: shard k of the rays on scenes[k] through the single-scene call, the
+// shards side by side.  `must` is the output a call with n > 0 cannot do without: the events, or the occlusion flags
+static int batch_sharded(const char* who, bool occl, hare_scene* const* scenes, int32_t n_scenes, int32_t kind, int32_t top_index, int64_t n,
+                         hare_ray* rays, const int32_t* excl1, const int32_t* excl2, uint32_t flags, hare_xevent* out, hare_counters* ctr,
+                         const double* tmax, int32_t* occluded)
+{
+    if (int rc = check_scenes(who, scenes, n_scenes)) return rc;
+    const void* must = occl ? (const void*)occluded : (const void*)out;
+    if (n < 0 || (n > 0 && (!rays || !must))) {
+        set_error(std::string(who) + ": bad arguments");
+        return HARE_E_INVALID;
+    }
+    GUARD_BEGIN
+    flags &= ~HARE_SHOOT_RETIRED_RAYS;      // each shard's single-scene call masks the rest by its own scene's options
+    if (ctr) memset(ctr, 0, sizeof *ctr);
+    const int G = n_scenes;
+    std::vector<hare_counters> parts((size_t)G);      // (zeroed)
+    // with HARE_SHOOT_SLIM_EVENTS hare_shoot_batch's `out` is an array of 16- or 32-byte records, not of X_Events
+    const size_t rec = (occl || !(flags & HARE_SHOOT_SLIM_EVENTS)) ? sizeof(hare_xevent)
+                                                                   : (kind == HARE_KIND_VOXEL ? sizeof(hare_slim_event) : sizeof(hare_slim_event_uv));
+    auto shard = [&](int k) -> int {
+        const PartRange r = part_range(n, k, G);
+        hare_ray* r_k = rays ? rays + r.lo : nullptr;
+        const int32_t *e1_k = excl1 ? excl1 + r.lo : nullptr, *e2_k = excl2 ? excl2 + r.lo : nullptr;
+        hare_xevent* o_k = out ? reinterpret_cast<hare_xevent*>(reinterpret_cast<unsigned char*>(out) + (size_t)r.lo * rec) : nullptr;
+        if (!occl) return hare_shoot_batch(scenes[k], kind, top_index, r.size(), r_k, e1_k, e2_k, flags, o_k, &parts[(size_t)k]);
+        return hare_occluded_batch(scenes[k], kind, top_index, r.size(), r_k, e1_k, e2_k, tmax ? tmax + r.lo : nullptr, flags,
+                                   occluded ? occluded + r.lo : nullptr, o_k, &parts[(size_t)k]);
+    };
+    const std::string thrown = std::string(who) + ": exception in a shard";
+    const FanResult f = fan_out(G, thrown.c_str(), shard);
+    if (f.rc != HARE_OK) {
+        set_error(f.shard_text());
+        return f.rc;
+    }
+    if (ctr)
+        for (const hare_counters& p : parts) add_counters(*ctr, p);
+    return HARE_OK;
+    GUARD_END
+}
+
 int hare_shoot_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int32_t kind, int32_t top_index, int64_t n,
                              hare_ray* rays, const int32_t* excl1, const int32_t* excl2, uint32_t flags, hare_xevent* out,
                              hare_counters* ctr)
 {
-    if (!scenes || n_scenes < 1 || n_scenes > 64) {
-        set_error("hare_shoot_batch_sharded: need 1..64 scenes");
-        return HARE_E_INVALID;
-    }
-    for (int32_t k = 0; k < n_scenes; ++k)
-        if (!scenes[k]) {
-            set_error("hare_shoot_batch_sharded: null scene");
-            return HARE_E_INVALID;
-        }
-    if (n < 0 || (n > 0 && (!rays || !out))) {
-        set_error("hare_shoot_batch_sharded: bad arguments");
-        return HARE_E_INVALID;
-    }
-    GUARD_BEGIN
-    flags &= ~HARE_SHOOT_RETIRED_RAYS;      // each shard's hare_shoot_batch masks the rest by its own scene's options
-    if (ctr) memset(ctr, 0, sizeof *ctr);
-    const int G = n_scenes;
-    std::vector<int> rcs((size_t)G, HARE_OK);
-    std::vector<std::string> errs((size_t)G);
-    std::vector<hare_counters> parts((size_t)G);
-    auto shard = [&](int k) {
-        const int64_t lo = (int64_t)((__int128)n * k / G), hi = (int64_t)((__int128)n * (k + 1) / G);
-        memset(&parts[k], 0, sizeof parts[k]);
-        // with HARE_SHOOT_SLIM_EVENTS `out` is an array of 16- or 32-byte records, not of X_Events
-        const size_t rec = !(flags & HARE_SHOOT_SLIM_EVENTS) ? sizeof(hare_xevent)
-                                                              : (kind == HARE_KIND_VOXEL ? sizeof(hare_slim_event) : sizeof(hare_slim_event_uv));
-        hare_xevent* o_k = out ? reinterpret_cast<hare_xevent*>(reinterpret_cast<unsigned char*>(out) + (size_t)lo * rec) : nullptr;
-        rcs[k] = hare_shoot_batch(scenes[k], kind, top_index, hi - lo, rays ? rays + lo : nullptr, excl1 ? excl1 + lo : nullptr,
-                                  excl2 ? excl2 + lo : nullptr, flags, o_k, &parts[k]);
-        if (rcs[k] != HARE_OK) errs[k] = hare_last_error();     // thread-local: carry it to the caller's thread
-    };
-    std::vector<std::thread> workers;
-    workers.reserve((size_t)G);
-    for (int k = 1; k < G; ++k) {
-        try {
-            workers.emplace_back(shard, k);
-        } catch (...) {
-            shard(k);                // no thread to be had: run the shard here
-        }
-    }
-    shard(0);
-    for (auto& w : workers) w.join();
-    for (int k = 0; k < G; ++k)
-        if (rcs[k] != HARE_OK) {
-            set_error("shard " + std::to_string(k) + ": " + errs[k]);
-            return rcs[k];
-        }
-    if (ctr)
-        for (int k = 0; k < G; ++k) {
-            ctr->rays += parts[k].rays;
-            ctr->hits += parts[k].hits;
-            ctr->cells += parts[k].cells;
-            ctr->entries += parts[k].entries;
-            ctr->tests += parts[k].tests;
-        }
-    return HARE_OK;
-    GUARD_END
+    return batch_sharded("hare_shoot_batch_sharded", false, scenes, n_scenes, kind, top_index, n, rays, excl1, excl2, flags, out, ctr, nullptr, nullptr);
 }
 
 int hare_reflect_device(hare_scene* s, int32_t top_index, int64_t n, void* d_rays, const void* d_events,
@@ -843,18 +771,13 @@ int hare_expand_events(const hare_scene* s, int32_t kind, int64_t n, const hare_
             out[i] = e;
         }
     };
-    const int64_t nt = std::max<int64_t>(1, std::min<int64_t>({(int64_t)std::thread::hardware_concurrency(), 16, n / 65536}));
-    std::vector<std::thread> th;
-    for (int64_t k = 1; k < nt; ++k) {
-        try {
-            th.emplace_back(body, n * k / nt, n * (k + 1) / nt);
-        } catch (...) {
-            body(n * k / nt, n * (k + 1) / nt);
-        }
-    }
-    body(0, n / nt);
-    for (auto& t : th) t.join();
-    return HARE_OK;
+    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)std::thread::hardware_concurrency(), 16, n / 65536}));
+    const FanResult f = fan_out(nt, "hare_expand_events: exception in a part", [&](int k) {
+        body(part_range(n, k, nt).lo, part_range(n, k, nt).hi);
+        return (int)HARE_OK;
+    });
+    if (f.rc != HARE_OK) set_error(f.text);
+    return f.rc;
     GUARD_END
 }
 
@@ -1094,59 +1017,7 @@ int hare_occluded_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int
                                 const int32_t* excl1, const int32_t* excl2, const double* tmax, uint32_t flags, int32_t* occluded,
                                 hare_xevent* events, hare_counters* ctr)
 {
-    if (!scenes || n_scenes < 1 || n_scenes > 64) {
-        set_error("hare_occluded_batch_sharded: need 1..64 scenes");
-        return HARE_E_INVALID;
-    }
-    for (int32_t k = 0; k < n_scenes; ++k)
-        if (!scenes[k]) {
-            set_error("hare_occluded_batch_sharded: null scene");
-            return HARE_E_INVALID;
-        }
-    if (n < 0 || (n > 0 && (!rays || !occluded))) {
-        set_error("hare_occluded_batch_sharded: bad arguments");
-        return HARE_E_INVALID;
-    }
-    GUARD_BEGIN
-    if (ctr) memset(ctr, 0, sizeof *ctr);
-    const int G = n_scenes;
-    std::vector<int> rcs((size_t)G, HARE_OK);
-    std::vector<std::string> errs((size_t)G);
-    std::vector<hare_counters> parts((size_t)G);
-    auto shard = [&](int k) {
-        const int64_t lo = (int64_t)((__int128)n * k / G), hi = (int64_t)((__int128)n * (k + 1) / G);
-        memset(&parts[(size_t)k], 0, sizeof(hare_counters));
-        rcs[(size_t)k] = hare_occluded_batch(scenes[k], kind, top_index, hi - lo, rays + lo, excl1 ? excl1 + lo : nullptr,
-                                             excl2 ? excl2 + lo : nullptr, tmax ? tmax + lo : nullptr, flags, occluded + lo,
-                                             events ? events + lo : nullptr, &parts[(size_t)k]);
-        if (rcs[(size_t)k] != HARE_OK) errs[(size_t)k] = hare_last_error();     // thread-local: carry it to the caller's thread
-    };
-    std::vector<std::thread> workers;
-    workers.reserve((size_t)G);
-    for (int k = 1; k < G; ++k) {
-        try {
-            workers.emplace_back(shard, k);
-        } catch (...) {
-            shard(k);                // no thread to be had: run the shard here
-        }
-    }
-    shard(0);
-    for (auto& w : workers) w.join();
-    for (int k = 0; k < G; ++k)
-        if (rcs[(size_t)k] != HARE_OK) {
-            set_error("shard " + std::to_string(k) + ": " + errs[(size_t)k]);
-            return rcs[(size_t)k];
-        }
-    if (ctr)
-        for (int k = 0; k < G; ++k) {
-            ctr->rays += parts[(size_t)k].rays;
-            ctr->hits += parts[(size_t)k].hits;
-            ctr->cells += parts[(size_t)k].cells;
-            ctr->entries += parts[(size_t)k].entries;
-            ctr->tests += parts[(size_t)k].tests;
-        }
-    return HARE_OK;
-    GUARD_END
+    return batch_sharded("hare_occluded_batch_sharded", true, scenes, n_scenes, kind, top_index, n, rays, excl1, excl2, flags, events, ctr, tmax, occluded);
 }
 
 }  // extern "C"

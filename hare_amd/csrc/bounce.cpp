@@ -21,11 +21,11 @@
 #include <mutex>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/hare_hip.h"
 #include "scene.h"
+#include "fan_out.h"
 
 namespace hare {
 
@@ -391,29 +391,17 @@ int bounce_one(hare_scene* s, int32_t kind, int32_t top, int64_t n, const hare_r
     flags = sanitize_flags(*s, flags) & (HARE_SHOOT_COUNT_WORK | HARE_SHOOT_SIMPLE_KERNEL);
     DeviceGuard dev_guard(hip_api(nullptr), s->device);
     const HipApi* H = nullptr;
-    Scene::BatchCtx* c = nullptr;
-    {
-        std::unique_lock<std::mutex> lk(s->mu);
-        int rc = ensure_device(*s, H);
-        if (rc) return rc;
-        rc = upload_polys(*s, H);
-        if (rc) return rc;
-        if (job && (rc = receive_ready(*s, H, job->who))) return rc;
-        if (job && job->from_source && (rc = source_ready(*s, H, job->who))) return rc;
-        if (n == 0) return HARE_OK;
-        s->cv.wait(lk, [&] { for (Scene::BatchCtx& x : s->ctx) if (!x.busy) return true; return false; });
-        for (Scene::BatchCtx& x : s->ctx)
-            if (!x.busy && x.bounce.cap >= n) { c = &x; break; }
-        if (!c)
-            for (Scene::BatchCtx& x : s->ctx)
-                if (!x.busy) { c = &x; break; }
-        c->busy = true;
-    }
-    struct Release {
-        hare_scene* s; Scene::BatchCtx* c;
-        ~Release() { { std::lock_guard<std::mutex> lk(s->mu); c->busy = false; } s->cv.notify_one(); }
-    } release{s, c};
-    const int rc = job ? receive_on_scene(*s, H, *c, kind, top, n, rays, excl1, excl2, bounces, flags, *job, per_cast)
+    std::unique_lock<std::mutex> lk(s->mu);
+    int rc = ensure_device(*s, H);
+    if (rc) return rc;
+    rc = upload_polys(*s, H);
+    if (rc) return rc;
+    if (job && (rc = receive_ready(*s, H, job->who))) return rc;
+    if (job && job->from_source && (rc = source_ready(*s, H, job->who))) return rc;
+    if (n == 0) return HARE_OK;
+    const CtxLease lease(*s, lk, [n](const Scene::BatchCtx& x) { return x.bounce.cap >= n; });       // (releases lk)
+    Scene::BatchCtx* const c = lease.get();
+    rc = job ? receive_on_scene(*s, H, *c, kind, top, n, rays, excl1, excl2, bounces, flags, *job, per_cast)
                        : bounce_on_scene(*s, H, *c, kind, top, n, rays, excl1, excl2, bounces, flags, events_all, stride, events_last, per_cast);
     if (rc != HARE_OK) {          // copies into the caller's buffers may still be in flight: drain before the error returns
         if (c->st[0]) (void)H->StreamSynchronize(c->st[0]);
@@ -422,33 +410,19 @@ int bounce_one(hare_scene* s, int32_t kind, int32_t top, int64_t n, const hare_r
     return rc;
 }
 
-void add_counters(hare_counters& dst, const hare_counters& src)
+// one shard's counters per cast into the call's total and (nullable both) its per-cast array
+void add_cast_counters(hare_counters* ctr, hare_counters* ctr_per_cast, const std::vector<hare_counters>& pc)
 {
-    dst.rays += src.rays;
-    dst.hits += src.hits;
-    dst.cells += src.cells;
-    dst.entries += src.entries;
-    dst.tests += src.tests;
+    for (size_t b = 0; b < pc.size(); ++b) {
+        if (ctr) add_counters(*ctr, pc[b]);
+        if (ctr_per_cast) add_counters(ctr_per_cast[b], pc[b]);
+    }
 }
 
 }  // namespace
 }  // namespace hare
 
 using namespace hare;
-
-#define GUARD_BEGIN try {
-#define GUARD_END                                               \
-    }                                                           \
-    catch (const std::bad_alloc&)                               \
-    {                                                           \
-        set_error("out of host memory");                        \
-        return HARE_E_NOMEM;                                    \
-    }                                                           \
-    catch (...)                                                 \
-    {                                                           \
-        set_error("unexpected C++ exception");                  \
-        return HARE_E_INVALID;                                  \
-    }
 
 extern "C" {
 
@@ -468,10 +442,7 @@ int hare_bounce_batch(hare_scene* s, int32_t kind, int32_t top_index, int64_t n,
     if (ctr_per_cast) memset(ctr_per_cast, 0, (size_t)bounces * sizeof(hare_counters));
     const int rc = bounce_one(s, kind, top_index, n, rays, excl1, excl2, bounces, flags, events_all, n, events_last, pc.data());
     if (rc) return rc;
-    for (int32_t b = 0; b < bounces; ++b) {
-        if (ctr) add_counters(*ctr, pc[(size_t)b]);
-        if (ctr_per_cast) ctr_per_cast[b] = pc[(size_t)b];
-    }
+    add_cast_counters(ctr, ctr_per_cast, pc);
     return HARE_OK;
     GUARD_END
 }
@@ -480,57 +451,24 @@ int hare_bounce_batch_sharded(hare_scene* const* scenes, int32_t n_scenes, int32
                               const hare_ray* rays, const int32_t* excl1, const int32_t* excl2, int32_t bounces, uint32_t flags,
                               hare_xevent* events_all, hare_xevent* events_last, hare_counters* ctr, hare_counters* ctr_per_cast)
 {
-    if (!scenes || n_scenes < 1 || n_scenes > 64) {
-        set_error("hare_bounce_batch_sharded: need 1..64 scenes");
-        return HARE_E_INVALID;
-    }
-    for (int32_t k = 0; k < n_scenes; ++k)
-        if (!scenes[k]) {
-            set_error("hare_bounce_batch_sharded: null scene");
-            return HARE_E_INVALID;
-        }
+    if (int rc = check_scenes("hare_bounce_batch_sharded", scenes, n_scenes)) return rc;
     if (int rc = check_args("hare_bounce_batch_sharded", n, rays, bounces, events_all, events_last)) return rc;
     GUARD_BEGIN
     const int G = n_scenes;
-    std::vector<int> rcs((size_t)G, HARE_OK);
-    std::vector<std::string> errs((size_t)G);
-    std::vector<std::vector<hare_counters>> pcs((size_t)G, std::vector<hare_counters>((size_t)bounces));
-    auto shard = [&](int k) {
-        const int64_t lo = (int64_t)((__int128)n * k / G), hi = (int64_t)((__int128)n * (k + 1) / G);
-        memset(pcs[(size_t)k].data(), 0, (size_t)bounces * sizeof(hare_counters));
-        try {
-            rcs[(size_t)k] = bounce_one(scenes[k], kind, top_index, hi - lo, rays ? rays + lo : nullptr, excl1 ? excl1 + lo : nullptr,
-                                        excl2 ? excl2 + lo : nullptr, bounces, flags, events_all ? events_all + lo : nullptr, n,
-                                        events_last ? events_last + lo : nullptr, pcs[(size_t)k].data());
-        } catch (...) {
-            rcs[(size_t)k] = HARE_E_NOMEM;
-            set_error("hare_bounce_batch_sharded: exception in a shard");
-        }
-        if (rcs[(size_t)k] != HARE_OK) errs[(size_t)k] = hare_last_error();     // thread-local: carry it to the caller's thread
-    };
-    std::vector<std::thread> workers;
-    workers.reserve((size_t)G);
-    for (int k = 1; k < G; ++k) {
-        try {
-            workers.emplace_back(shard, k);
-        } catch (...) {
-            shard(k);                // no thread to be had: run the shard here
-        }
+    std::vector<std::vector<hare_counters>> pcs((size_t)G, std::vector<hare_counters>((size_t)bounces));      // (zeroed)
+    const FanResult f = fan_out(G, "hare_bounce_batch_sharded: exception in a shard", [&](int k) {
+        const PartRange r = part_range(n, k, G);
+        return bounce_one(scenes[k], kind, top_index, r.size(), rays ? rays + r.lo : nullptr, excl1 ? excl1 + r.lo : nullptr,
+                          excl2 ? excl2 + r.lo : nullptr, bounces, flags, events_all ? events_all + r.lo : nullptr, n,
+                          events_last ? events_last + r.lo : nullptr, pcs[(size_t)k].data());
+    });
+    if (f.rc != HARE_OK) {
+        set_error(f.shard_text());
+        return f.rc;
     }
-    shard(0);
-    for (auto& w : workers) w.join();
-    for (int k = 0; k < G; ++k)
-        if (rcs[(size_t)k] != HARE_OK) {
-            set_error("shard " + std::to_string(k) + ": " + errs[(size_t)k]);
-            return rcs[(size_t)k];
-        }
     if (ctr) memset(ctr, 0, sizeof *ctr);
     if (ctr_per_cast) memset(ctr_per_cast, 0, (size_t)bounces * sizeof(hare_counters));
-    for (int k = 0; k < G; ++k)
-        for (int32_t b = 0; b < bounces; ++b) {
-            if (ctr) add_counters(*ctr, pcs[(size_t)k][(size_t)b]);
-            if (ctr_per_cast) add_counters(ctr_per_cast[b], pcs[(size_t)k][(size_t)b]);
-        }
+    for (const std::vector<hare_counters>& pc : pcs) add_cast_counters(ctr, ctr_per_cast, pc);
     return HARE_OK;
     GUARD_END
 }
@@ -545,15 +483,7 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
                            hare_counters* ctr, const int64_t* first_ray, const ReduceSpec* red = nullptr, uint64_t* sums = nullptr,
                            int32_t* cross = nullptr)
 {
-    if (!scenes || n_scenes < 1 || n_scenes > 64) {
-        set_error(std::string(who) + ": need 1..64 scenes");
-        return HARE_E_INVALID;
-    }
-    for (int32_t k = 0; k < n_scenes; ++k)
-        if (!scenes[k]) {
-            set_error("null scene");
-            return HARE_E_INVALID;
-        }
+    if (int rc = check_scenes(who, scenes, n_scenes, true)) return rc;
     hare_scene* const s0 = scenes[0];
     if (int rc = receive_check_args(who, *s0, flags, kind, top_index, n, bounces, n_bins, bin_len, frac_bits)) return rc;
     if ((flags & HARE_RECEIVE_DIRECT) && !first_ray) {      // the caller's rays: the library cannot know them to be the source's
@@ -642,17 +572,14 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
     }
     memset(detections, 0, 2 * K * sizeof(uint64_t));
     if (ctr) memset(ctr, 0, sizeof *ctr);
-    std::vector<int> rcs((size_t)G, HARE_OK);
-    std::vector<std::string> errs((size_t)G);
-    std::vector<std::vector<hare_counters>> pcs((size_t)G, std::vector<hare_counters>((size_t)bounces));
+    std::vector<std::vector<hare_counters>> pcs((size_t)G, std::vector<hare_counters>((size_t)bounces));      // (zeroed)
     std::vector<std::vector<uint64_t>> hists((size_t)G), dets((size_t)G);    // shard 0 writes the caller's arrays
     for (int k = 1; k < G; ++k) {
         hists[(size_t)k].assign(hist_words, 0);
         dets[(size_t)k].assign(2 * K, 0);
     }
-    auto shard = [&](int k) {
-        const int64_t lo = (int64_t)((__int128)n * k / G), hi = (int64_t)((__int128)n * (k + 1) / G);
-        memset(pcs[(size_t)k].data(), 0, (size_t)bounces * sizeof(hare_counters));
+    auto shard = [&](int k) -> int {
+        const int64_t lo = part_range(n, k, G).lo, hi = part_range(n, k, G).hi;
         ReceiveJob job;
         job.n_bins = n_bins;
         job.bin_len = bin_len;
@@ -673,38 +600,20 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
         job.reduce = red;
         job.sums = sums;
         job.cross = cross;
-        try {
-            rcs[(size_t)k] = bounce_one(scenes[k], kind, top_index, hi - lo, rays ? rays + lo : nullptr, excl1 ? excl1 + lo : nullptr,
-                                        excl2 ? excl2 + lo : nullptr, bounces, flags, nullptr, n, nullptr, pcs[(size_t)k].data(), &job);
-        } catch (...) {
-            rcs[(size_t)k] = HARE_E_NOMEM;
-            set_error(std::string(who) + ": exception in a shard");
-        }
-        if (rcs[(size_t)k] != HARE_OK) errs[(size_t)k] = hare_last_error();
+        return bounce_one(scenes[k], kind, top_index, hi - lo, rays ? rays + lo : nullptr, excl1 ? excl1 + lo : nullptr,
+                          excl2 ? excl2 + lo : nullptr, bounces, flags, nullptr, n, nullptr, pcs[(size_t)k].data(), &job);
     };
-    std::vector<std::thread> workers;
-    workers.reserve((size_t)G);
-    for (int k = 1; k < G; ++k) {
-        try {
-            workers.emplace_back(shard, k);
-        } catch (...) {
-            shard(k);
-        }
+    const std::string thrown = std::string(who) + ": exception in a shard";
+    const FanResult f = fan_out(G, thrown.c_str(), shard);
+    if (f.rc != HARE_OK) {
+        set_error(G == 1 ? f.text : f.shard_text());
+        return f.rc;
     }
-    shard(0);
-    for (auto& w : workers) w.join();
-    for (int k = 0; k < G; ++k)
-        if (rcs[(size_t)k] != HARE_OK) {
-            set_error(G == 1 ? errs[0] : "shard " + std::to_string(k) + ": " + errs[(size_t)k]);
-            return rcs[(size_t)k];
-        }
     for (int k = 1; k < G; ++k) {                 // integer sums (mod 2^64, so right for the signed channels too): the order of the shards does not matter
         for (size_t w = 0; w < hist_words; ++w) hist[w] += hists[(size_t)k][w];
         for (size_t w = 0; w < 2 * K; ++w) detections[w] += dets[(size_t)k][w];
     }
-    if (ctr)
-        for (int k = 0; k < G; ++k)
-            for (int32_t b = 0; b < bounces; ++b) add_counters(*ctr, pcs[(size_t)k][(size_t)b]);
+    for (const std::vector<hare_counters>& pc : pcs) add_cast_counters(ctr, nullptr, pc);
     return HARE_OK;
     GUARD_END
 }

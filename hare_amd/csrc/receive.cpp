@@ -18,6 +18,7 @@
 #include "../../include/hare_hip.h"
 #include "launch.h"
 #include "scene.h"
+#include "fan_out.h"
 
 namespace hare {
 
@@ -723,20 +724,6 @@ static void build_receiver_map(Scene::ReceiverMap& m, int32_t K, const double* c
 }  // namespace hare
 
 using namespace hare;
-
-#define GUARD_BEGIN try {
-#define GUARD_END                                               \
-    }                                                           \
-    catch (const std::bad_alloc&)                               \
-    {                                                           \
-        set_error("out of host memory");                        \
-        return HARE_E_NOMEM;                                    \
-    }                                                           \
-    catch (...)                                                 \
-    {                                                           \
-        set_error("unexpected C++ exception");                  \
-        return HARE_E_INVALID;                                  \
-    }
 
 // ---- what hare_direct_device, hare_image_device and hare_image2_device share (the calls themselves are below).  Their checks fire in
 // this order: deposit_call_check, the call's own list lengths, deposit_buffers_check -- all HARE_E_INVALID, ahead of the device.

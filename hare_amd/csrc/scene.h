@@ -343,6 +343,36 @@ struct Scene {
     };
     Source src;
 };
+// One of the scene's staging contexts, held for a host-buffer call: concurrent callers (Pachyderm's worker threads) run side by side, each
+// on a context of its own.  Constructed with s.mu held through `lk`: waits for a free context, prefers a free one that `fits` (already
+// large enough for the call), else takes the first free one, marks it busy and RELEASES lk.  The destructor gives the context back and
+// wakes one waiter.  A per-scene worker would own its context in place of this lease.
+class CtxLease {
+public:
+    template <class Fits>
+    CtxLease(Scene& s, std::unique_lock<std::mutex>& lk, Fits fits) : s_(s)
+    {
+        s.cv.wait(lk, [&] { for (Scene::BatchCtx& x : s.ctx) if (!x.busy) return true; return false; });
+        for (Scene::BatchCtx& x : s.ctx)
+            if (!x.busy && fits(x)) { c_ = &x; break; }
+        if (!c_)
+            for (Scene::BatchCtx& x : s.ctx)
+                if (!x.busy) { c_ = &x; break; }
+        c_->busy = true;
+        lk.unlock();
+    }
+    ~CtxLease()
+    {
+        { std::lock_guard<std::mutex> lk(s_.mu); c_->busy = false; }
+        s_.cv.notify_one();
+    }
+    CtxLease(const CtxLease&) = delete;
+    CtxLease& operator=(const CtxLease&) = delete;
+    Scene::BatchCtx* get() const { return c_; }
+private:
+    Scene& s_;
+    Scene::BatchCtx* c_ = nullptr;
+};
 void free_host_mirror(Scene& s);             // host_trace.cpp
 void make_poly_records(const Topo& T, std::vector<PolyRec>& rec, std::vector<QuadRec>& quads);   // device_scene.cpp
 void make_cull_records(const Topo& T, const std::vector<PolyRec>& rec, std::vector<unsigned char>& dense, CullFrame& cf);   // device_scene.cpp

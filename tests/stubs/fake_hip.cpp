@@ -4,7 +4,7 @@
 // hipModuleLaunchKernel runs nothing: it appends one line to a log -- kernel, grid, block, dynamic LDS, and for the hare_voxel_* /
 // hare_octree_* / hare_kdtree_* kernels the two argument structs decoded with the tree's own hare_device.h.  A scalar field that is zero and a
 // pointer that is null are left out of the line (absent = 0 / null); every other pointer is written `name+offset`: relative to the caller's
-// buffers (FAKE_HIP_BUFFERS: name=hex address, ... ; each 2^40 bytes) or to the live allocations, numbered in the order they were made (a0,
+// buffers (real ones named through fake_hip_name_host_range; FAKE_HIP_BUFFERS: name=hex address, ... ; each 2^40 bytes) or to the live allocations, numbered in the order they were made (a0,
 // a1, ...).  Events and streams are numbered the same way (e0 ...; s0 is the null stream).  hipMemsetAsync, hipMemcpyAsync, hipStreamWaitEvent
 // and hipEventRecord are logged in order.  The stub never dereferences a pointer it did not allocate (host sources of uploads apart).
 // Built with g++ alone: no HIP header, the runtime's enums are ints at the ABI.
@@ -31,6 +31,8 @@ std::mutex g_mu;
 std::vector<Alloc> g_allocs;              // live, in the order they were made
 std::vector<void*> g_events, g_streams;   // live handles, in the order they were made
 std::vector<Region> g_regions;
+struct HostRange { std::string name; uintptr_t base; size_t bytes; };
+std::vector<HostRange> g_host;            // the caller's real buffers (fake_hip_name_host_range)
 std::set<std::string> g_names;            // interned kernel names: a hipFunction_t is the address of one
 std::string g_log;
 bool g_log_on = true;
@@ -70,6 +72,11 @@ std::string ptr_name(const void* p)
     read_regions();
     char buf[96];
     const uintptr_t x = (uintptr_t)p;
+    for (const HostRange& r : g_host)
+        if (x >= r.base && x < r.base + std::max<size_t>(r.bytes, 1)) {
+            snprintf(buf, sizeof buf, "%s+%llu", r.name.c_str(), (unsigned long long)(x - r.base));
+            return buf;
+        }
     for (const Region& r : g_regions)
         if (x >= r.base && x < r.base + kRegionBytes) {
             snprintf(buf, sizeof buf, "%s+%llu", r.name.c_str(), (unsigned long long)(x - r.base));
@@ -164,6 +171,13 @@ const char* fake_hip_log(void) { std::lock_guard<std::mutex> lk(g_mu); static st
 void fake_hip_log_clear(void) { std::lock_guard<std::mutex> lk(g_mu); g_log.clear(); }
 void fake_hip_log_enable(int on) { std::lock_guard<std::mutex> lk(g_mu); g_log_on = on != 0; }
 long long fake_hip_live_allocations(void) { std::lock_guard<std::mutex> lk(g_mu); return (long long)g_allocs.size(); }
+// a real host buffer of the caller's: pointers into [base, base + bytes) print as name+offset (a null name forgets every range)
+void fake_hip_name_host_range(const char* name, const void* base, size_t bytes)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!name) g_host.clear();
+    else g_host.push_back({name, (uintptr_t)base, bytes});
+}
 
 // ---- the entry points hiprt.cpp binds
 int hipGetDeviceCount(int* n) { *n = 1; return 0; }

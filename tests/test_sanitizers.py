@@ -21,3 +21,11 @@ def test_host_library_under_asan_ubsan():
     out = subprocess.run(["make", "-C", os.path.join(ROOT, "hare_amd", "csrc"), "-s", "asan-test"], capture_output=True, text=True, env=env)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "0 failures" in out.stdout and "ERROR" not in out.stderr
+
+
+def test_host_threading_under_tsan():
+    # the fan-out, the ray split and the context lease of the host-buffer calls (tests/stubs/fan_out_tsan.cpp), against the recording HIP
+    # stand-in: a program of its own, no GPU
+    out = subprocess.run(["make", "-C", os.path.join(ROOT, "hare_amd", "csrc"), "-s", "tsan-test"], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "fan_out_tsan: 0 failures" in out.stdout and "ThreadSanitizer" not in out.stderr
