@@ -336,6 +336,26 @@ public:
         check(hare_hist_reduce(scene_, K, n_bins, B, channels, hist.data(), r.weight.empty() ? nullptr : r.weight.data(), n_win, r.windows.data(),
                                n_lev, r.levels.data(), sums.data(), cross.data()));
     }
+    // hare_hist_render (include/hare_hip.h, "receivers", "Rendering"): hist as Receive returns it (K x n_bins x B x channels), rendered to
+    // impulse responses of M samples per bin -- noise from `seed`, filtered per band by taps (B x T), shaped by the histogram.  out:
+    // K x channels x (n_bins * M).  weight: n_bins x B in units of 2^-32 (AirWeights), or empty: none
+    void HistRender(const std::vector<uint64_t>& hist, int K, int n_bins, int B, int channels, int frac_bits, int M, const std::vector<double>& taps,
+                    uint64_t seed, std::vector<double>& out, const std::vector<uint32_t>& weight = {})
+    {
+        if (K < 0 || n_bins < 0 || B < 1 || channels < 0 || M < 0 || hist.size() != (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels)
+            throw std::invalid_argument("HistRender: hist must hold K x n_bins x B x channels values");
+        if (taps.empty() || taps.size() % (size_t)B != 0) throw std::invalid_argument("HistRender: taps must hold B x T values");
+        if (!weight.empty() && weight.size() != (size_t)n_bins * (size_t)B) throw std::invalid_argument("HistRender: weight must hold n_bins x B values (or none)");
+        out.assign((size_t)K * (size_t)channels * (size_t)n_bins * (size_t)M, 0.0);
+        check(hare_hist_render(scene_, K, n_bins, B, channels, hist.data(), weight.empty() ? nullptr : weight.data(), frac_bits, M,
+                               (int32_t)(taps.size() / (size_t)B), taps.data(), seed, out.data()));
+    }
+    // hare_hist_render_device on device pointers and a hipStream_t: d_out (K x channels x n_bins x M doubles) written.  Stream-ordered.
+    void HistRenderDevice(int K, int n_bins, int B, int channels, const void* d_hist, int frac_bits, int M, int T, const void* d_taps, uint64_t seed,
+                          void* d_out, const void* d_weight = nullptr, void* stream = nullptr)
+    {
+        check(hare_hist_render_device(scene_, K, n_bins, B, channels, d_hist, d_weight, frac_bits, M, T, d_taps, seed, d_out, stream));
+    }
     // Receive / ReceiveSource with the histogram reduced on the device (hare_receive_batch_reduced / hare_receive_source_reduced): sums and
     // cross as HistReduce gives them on the histogram Receive returns; the histogram itself never comes down
     uint64_t ReceiveReduced(const std::vector<hare_ray>& rays, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,

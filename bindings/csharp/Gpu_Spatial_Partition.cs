@@ -420,6 +420,18 @@ namespace Hare
                 HareHip.Check(HareHip.hare_hist_reduce(scenes[0], K, n_bins, B, channels, hist, weight, n_win, win, n_lev, levels, sums, cross));
             }
 
+            /// <summary>hare_hist_render on a histogram a Receive call returned: impulse responses of M samples per bin, K x channels x
+            /// (n_bins * M) doubles into result, on the first scene's device (include/hare_hip.h, "Rendering").  taps: B x T.</summary>
+            public void HistRender(ulong[] hist, int K, int n_bins, int B, int channels, uint[] weight, int frac_bits, int M, double[] taps, ulong seed,
+                                   double[] result)
+            {
+                if (hist == null || hist.LongLength < (long)K * n_bins * B * channels) throw new ArgumentException("hist must hold K x n_bins x B x channels values");
+                if (B < 1 || taps == null || taps.Length == 0 || taps.Length % B != 0) throw new ArgumentException("taps must hold B x T values");
+                if (weight != null && weight.LongLength != (long)n_bins * B) throw new ArgumentException("weight must hold n_bins x B values (or be null)");
+                if (result == null || result.LongLength < (long)K * channels * n_bins * M) throw new ArgumentException("result must hold K x channels x n_bins x M values");
+                HareHip.Check(HareHip.hare_hist_render(scenes[0], K, n_bins, B, channels, hist, weight, frac_bits, M, taps.Length / B, taps, seed, result));
+            }
+
             /// <summary>min(2^32 - 1, floor(10^(dB / 10) * 2^32)): a level of the reduction from decibels (dB at most 0).</summary>
             public static uint DecayLevel(double dB)
             {

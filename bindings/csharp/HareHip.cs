@@ -298,6 +298,13 @@ namespace Hare
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_hist_reduce(IntPtr scene, int K, int n_bins, int B, int channels, [In] ulong[] hist, [In] uint[] weight,
                                                       int n_win, [In] int[] win, int n_lev, [In] uint[] levels, [Out] ulong[] sums, [Out] int[] cross);
+            // the rendering of a histogram to impulse responses on the device (include/hare_hip.h, "receivers", "Rendering")
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_hist_render_device(IntPtr scene, int K, int n_bins, int B, int channels, IntPtr d_hist, IntPtr d_weight,
+                                                             int frac_bits, int M, int T, IntPtr d_taps, ulong seed, IntPtr d_out, IntPtr stream);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_hist_render(IntPtr scene, int K, int n_bins, int B, int channels, [In] ulong[] hist, [In] uint[] weight,
+                                                      int frac_bits, int M, int T, [In] double[] taps, ulong seed, [Out] double[] result);
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_receive_batch_reduced(IntPtr scene, int kind, int top_index, long n, [In] hare_ray[] rays, int[] excl1,
                                                                 int[] excl2, int bounces, uint flags, int n_bins, double bin_len, int frac_bits,

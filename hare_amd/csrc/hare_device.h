@@ -678,6 +678,30 @@ struct ReduceArgs {
     uint32_t levels[kMaxReduceLevels];        // fractions in units of 2^-32
 };
 
+// hare_hist_render (render.hip): a receive histogram rendered to pressure impulse responses, band noise shaped by the energy envelope
+// (include/hare_hip.h, "receivers", "Rendering").  A workgroup renders `tile_bins` whole bins of one receiver; the host sizes the tile and
+// the dynamic LDS (render_plan, receive.cpp)
+constexpr int kMaxRenderBin = 1024;        // M: samples per bin
+constexpr int kMaxRenderTaps = 1024;       // T: taps per band filter
+constexpr int kRenderThreads = 512;
+constexpr int kRenderRun = 8;              // consecutive samples a lane filters at once (render.hip)
+struct RenderArgs {
+    const unsigned long long* hist;   // K x n_bins x bands x channels words
+    const uint32_t* weight;           // n_bins x bands, units of 2^-32 (null: none)
+    const double* taps;               // bands x T
+    double* out;                      // K x channels x (n_bins * M); each word written once
+    unsigned long long seed;
+    int32_t n_bins;
+    int32_t bands;                    // 1 .. kMaxBands
+    int32_t channels;                 // 1, 4, 9 or 16
+    int32_t frac_bits;
+    int32_t M;                        // 1 .. kMaxRenderBin
+    int32_t T;                        // 1 .. kMaxRenderTaps
+    int32_t tile_bins;                // bins per workgroup
+    int32_t tiles;                    // workgroups per receiver: ceil(n_bins / tile_bins)
+    int32_t sign_words;               // 64-bit words of the tile's sign mask, pad included
+};
+
 #if defined(__HIPCC__)
 // Every kernel argument as a scalar of its OWN (round 6).  The compiler fetches the 720-byte argument block in tuples of 8 and 16 SGPRs and,
 // short of SGPRs in these kernels, spills and reloads them AS tuples: a block that needs the rays' pointer reloaded sixteen registers to get

@@ -528,7 +528,8 @@ int image2_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t
 }
 
 // ---- the reduction of a histogram (include/hare_hip.h, "receivers", "Reduction"; the kernel: reduce.hip)
-int reduce_check_spec(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const ReduceSpec& r)
+// what the reduction and the rendering check of a histogram's shape
+static int hist_check_shape(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels)
 {
     auto bad = [&](const std::string& what) {
         set_error(std::string(who) + ": " + what);
@@ -539,6 +540,16 @@ int reduce_check_spec(const char* who, int64_t K, int32_t n_bins, int32_t B, int
     if (B < 1 || B > kMaxBands) return bad("bands out of range (1 .. 8)");
     if (channels != 1 && channels != 4 && channels != 9 && channels != 16) return bad("channels must be 1, 4, 9 or 16");
     if ((unsigned __int128)K * (unsigned)n_bins * (unsigned)B * (unsigned)channels > ((size_t)1 << 27)) return bad("K x n_bins x bands x channels exceeds 2^27");
+    return HARE_OK;
+}
+
+int reduce_check_spec(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const ReduceSpec& r)
+{
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    if (int rc = hist_check_shape(who, K, n_bins, B, channels)) return rc;
     if (r.n_win < 0 || r.n_win > kMaxReduceWindows) return bad("n_win out of range (0 .. 16)");
     if (r.n_lev < 0 || r.n_lev > kMaxReduceLevels) return bad("n_lev out of range (0 .. 32)");
     if (r.n_win + r.n_lev < 1) return bad("nothing to compute: n_win and n_lev are both 0");
@@ -593,6 +604,67 @@ static int reduce_check_buffers(const char* who, int64_t K, int32_t n_bins, int3
                 return HARE_E_INVALID;
             }
     return HARE_OK;
+}
+
+// ---- the rendering of a histogram (include/hare_hip.h, "receivers", "Rendering"; the kernel: render.hip)
+// everything hare_hist_render_device and hare_hist_render check before anything runs, in the header's order; buffers device or host
+static int render_check(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const void* hist, const void* weight,
+                        int32_t frac_bits, int32_t M, int32_t T, const void* taps, const void* out)
+{
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    if (int rc = hist_check_shape(who, K, n_bins, B, channels)) return rc;
+    if (M < 1 || M > kMaxRenderBin) return bad("M out of range (1 .. 1024)");
+    if (T < 1 || T > kMaxRenderTaps) return bad("T out of range (1 .. 1024)");
+    if (frac_bits < 0 || frac_bits > 62) return bad("frac_bits out of range (0 .. 62)");
+    if ((unsigned __int128)K * (unsigned)channels * (unsigned)n_bins * (unsigned)M > ((size_t)1 << 28)) return bad("K x channels x n_bins x M exceeds 2^28");
+    if (!hist || !taps || !out) return bad("null histogram / taps / output");
+    const size_t out_bytes = (size_t)K * (size_t)channels * (size_t)n_bins * (size_t)M * sizeof(double);
+    const struct { const void* p; size_t bytes; } in[] = {{hist, (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels * sizeof(uint64_t)},
+                                                          {weight, (size_t)n_bins * (size_t)B * sizeof(uint32_t)},
+                                                          {taps, (size_t)B * (size_t)T * sizeof(double)}};
+    for (const auto& b : in)
+        if (ranges_overlap(out, out_bytes, b.p, b.bytes)) return bad("the output must not overlap the histogram, the weights or the taps");
+    return HARE_OK;
+}
+
+// The tile of hare_hist_render (render.hip): whole bins, as many as keep the B x S filtered samples near 32 KiB and the gains within
+// 16 KiB -- one bin where a bin alone is more.  LDS: taps, samples, gains, a, sign mask: at most 8 * (8192 + 8192 + 2048 + 256 + 35) bytes
+static unsigned render_plan(RenderArgs& a)
+{
+    const int32_t B = a.bands, C = a.channels;
+    a.tile_bins = std::max<int32_t>(1, std::min<int32_t>({(4096 / B) / a.M, 2048 / (B * C), a.n_bins}));
+    a.tiles = (a.n_bins + a.tile_bins - 1) / a.tile_bins;
+    const int32_t S = a.tile_bins * a.M;
+    a.sign_words = ((S + a.T + kRenderRun + 62) >> 6) + 2;
+    return (unsigned)(sizeof(double) * (size_t)(B * a.T + B * S + a.tile_bins * B * C + a.tile_bins * B + a.sign_words));
+}
+
+static int render_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist,
+                          const void* d_weight, int32_t frac_bits, int32_t M, int32_t T, const void* d_taps, uint64_t seed, void* d_out, hipStream_t st)
+{
+    if (!s.module || !s.module->hist_render) {
+        set_error("hare_hist_render missing from code object");
+        return HARE_E_STATE;
+    }
+    RenderArgs a;
+    memset(&a, 0, sizeof a);
+    a.hist = (const unsigned long long*)d_hist;
+    a.weight = (const uint32_t*)d_weight;
+    a.taps = (const double*)d_taps;
+    a.out = (double*)d_out;
+    a.seed = seed;
+    a.n_bins = n_bins;
+    a.bands = B;
+    a.channels = channels;
+    a.frac_bits = frac_bits;
+    a.M = M;
+    a.T = T;
+    const unsigned lds = render_plan(a);
+    void* args[] = {&a};
+    return launch(H, s.module->hist_render, (unsigned)K * (unsigned)a.tiles, kRenderThreads, lds, st, args);      // K x n_bins <= 2^27 workgroups
 }
 
 // hare_scene_set_absorption / _scattering behind their own checks of top_index and B: P x B coefficients in [0, 1] become Model[top]'s
@@ -1095,6 +1167,74 @@ int hare_hist_reduce(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_
         if (int rc = reduce_enqueue(*s, H, K, n_bins, B, channels, d_hist, weight ? d_weight : nullptr, r, d_sums, d_cross, nullptr)) return rc;
         if (n_win > 0) HIP_TRY(H->MemcpyAsync(sums, d_sums, sums_bytes, hipMemcpyDeviceToHost, nullptr));
         if (n_lev > 0) HIP_TRY(H->MemcpyAsync(cross, d_cross, KB * (size_t)n_lev * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(H->StreamSynchronize(nullptr));
+        return HARE_OK;
+    };
+    const int rc = run();
+    if (rc != HARE_OK) (void)H->StreamSynchronize(nullptr);      // copies may still be in flight
+    dev_free(H, block);
+    return rc;
+    GUARD_END
+}
+
+int hare_hist_render_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
+                            int32_t frac_bits, int32_t M, int32_t T, const void* d_taps, uint64_t seed, void* d_out, void* stream)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    if (int rc = render_check("hare_hist_render_device", K, n_bins, B, channels, d_hist, d_weight, frac_bits, M, T, d_taps, d_out)) return rc;
+    GUARD_BEGIN
+    const HipApi* H = api_or_err();
+    if (!H) return HARE_E_NODEVICE;
+    DeviceGuard dev_guard(H, s->device);
+    if (!s->module) {
+        int rc = ensure_device(*s, H);
+        if (rc) return rc;
+    }
+    return render_enqueue(*s, H, K, n_bins, B, channels, d_hist, d_weight, frac_bits, M, T, d_taps, seed, d_out, (hipStream_t)stream);
+    GUARD_END
+}
+
+int hare_hist_render(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t* hist, const uint32_t* weight,
+                     int32_t frac_bits, int32_t M, int32_t T, const double* taps, uint64_t seed, double* out)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    if (int rc = render_check("hare_hist_render", K, n_bins, B, channels, hist, weight, frac_bits, M, T, taps, out)) return rc;
+    for (size_t x = 0; x < (size_t)B * (size_t)T; ++x)
+        if (!std::isfinite(taps[x])) {
+            set_error("hare_hist_render: taps[" + std::to_string(x) + "] is not finite");
+            return HARE_E_INVALID;
+        }
+    GUARD_BEGIN
+    const HipApi* H = api_or_err();
+    if (!H) return HARE_E_NODEVICE;
+    DeviceGuard dev_guard(H, s->device);
+    if (!s->module) {
+        int rc = ensure_device(*s, H);
+        if (rc) return rc;
+    }
+    // one device block: output, histogram, taps, weights (sizes of whole 8-byte words: each stays aligned); up, render, down, one synchronisation
+    const size_t hist_bytes = (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels * sizeof(uint64_t);
+    const size_t out_bytes = (size_t)K * (size_t)channels * (size_t)n_bins * (size_t)M * sizeof(double);
+    const size_t taps_bytes = (size_t)B * (size_t)T * sizeof(double), weight_bytes = (size_t)n_bins * (size_t)B * sizeof(uint32_t);
+    void* block = nullptr;
+    HIP_TRY(H->Malloc(&block, out_bytes + hist_bytes + taps_bytes + weight_bytes + 16));
+    char* const d_out = (char*)block;
+    char* const d_hist = d_out + out_bytes;
+    char* const d_taps = d_hist + hist_bytes;
+    char* const d_weight = d_taps + taps_bytes;
+    auto run = [&]() -> int {
+        HIP_TRY(H->MemcpyAsync(d_hist, hist, hist_bytes, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(H->MemcpyAsync(d_taps, taps, taps_bytes, hipMemcpyHostToDevice, nullptr));
+        if (weight) HIP_TRY(H->MemcpyAsync(d_weight, weight, weight_bytes, hipMemcpyHostToDevice, nullptr));
+        if (int rc = render_enqueue(*s, H, K, n_bins, B, channels, d_hist, weight ? d_weight : nullptr, frac_bits, M, T, d_taps, seed, d_out, nullptr))
+            return rc;
+        HIP_TRY(H->MemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, nullptr));
         HIP_TRY(H->StreamSynchronize(nullptr));
         return HARE_OK;
     };

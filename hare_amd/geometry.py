@@ -183,6 +183,27 @@ def air_weights(m, bin_len: float, n_bins: int):
     return np.minimum(np.floor(np.exp(-m[None, :] * mid[:, None]) * 4294967296.0), 4294967295.0).astype(np.uint32)
 
 
+def band_taps(fs: float, edges, T: int):
+    """Band filters for hist_render: float64 [B, T] with B = len(edges) + 1, T odd.  Lowpass l is the Hamming-windowed sinc of cut-off
+    edges[l] (Hz, ascending, below fs / 2), scaled to unit gain at 0 Hz; band 0 is lowpass 0, band b is lowpass b minus lowpass b - 1, and
+    the top band is the unit impulse at (T - 1) / 2 minus the last lowpass: the bands telescope to a pure delay of (T - 1) / 2 samples.  A
+    host convenience that produces data: whatever taps the caller passes are the definition's."""
+    T = int(T)
+    edges = np.asarray(edges, np.float64).reshape(-1)
+    if T < 1 or T % 2 == 0:
+        raise ValueError("T must be odd and >= 1")
+    if not (np.isfinite(fs) and fs > 0 and np.isfinite(edges).all() and (edges > 0).all() and (edges < fs / 2).all() and (np.diff(edges) > 0).all()):
+        raise ValueError("edges are ascending frequencies in (0, fs / 2)")
+    n = np.arange(T, dtype=np.float64) - (T - 1) / 2
+    window = np.hamming(T) if T > 1 else np.ones(1)
+    low = [np.sinc(2.0 * f / fs * n) * window for f in edges]
+    low = [h / h.sum() for h in low]
+    delta = np.zeros(T)
+    delta[(T - 1) // 2] = 1.0
+    steps = [np.zeros(T)] + low + [delta]
+    return np.ascontiguousarray([steps[b + 1] - steps[b] for b in range(len(edges) + 1)])
+
+
 def sums_to_float(sums):
     """The sums of a reduction [..., 4] (S0 lo, S0 hi, S1 lo, S1 hi; uint64) as float64 (S0, S1): rounded, for the ratios a caller forms."""
     s = np.asarray(sums).astype(np.float64)
@@ -687,6 +708,32 @@ class Spatial_Partition:
         _, n_win, win, n_lev, lev = _reduce_spec(dict(windows=windows, levels=levels), n_bins, B)
         check(lib.hare_hist_reduce_device(self._h, int(K), int(n_bins), int(B), int(channels), d_hist or None, d_weight or None, n_win,
                                           ptr(win), n_lev, ptr(lev), d_sums or None, d_cross or None, stream or None))
+
+    def hist_render(self, hist, taps, M: int, frac_bits: int, seed: int = 0, weight=None):
+        """hare_hist_render: a histogram [K, n_bins, B] or [K, n_bins, B, C] (C = 4, 9 or 16) of uint64, as the receive calls return it,
+        rendered on this partition's device to impulse responses (include/hare_hip.h, "receivers", "Rendering"): M samples per bin, taps
+        [B, T] float64 (band_taps), seed uint64, weight uint32 [n_bins, B] (air_weights) or None.  Returns float64 [K, channels, n_bins * M]."""
+        hist = np.ascontiguousarray(hist, np.uint64)
+        if hist.ndim not in (3, 4) or (hist.ndim == 4 and hist.shape[3] not in (4, 9, 16)):
+            raise ValueError("hist must be uint64 [K, n_bins, B] or [K, n_bins, B, C], C = 4, 9 or 16")
+        K, nb, B = hist.shape[:3]
+        channels = hist.shape[3] if hist.ndim == 4 else 1
+        taps = np.ascontiguousarray(taps, np.float64)
+        if taps.ndim != 2 or taps.shape[0] != B:
+            raise ValueError("taps must be float64 [B, T] = [%d, T]" % B)
+        w, *_ = _reduce_spec(dict(weight=weight), nb, B)
+        out = np.zeros((K, channels, nb * max(0, int(M))), np.float64)
+        check(lib.hare_hist_render(self._h, K, nb, B, channels, ptr(hist), ptr(w), int(frac_bits), int(M), taps.shape[1], ptr(taps),
+                                   int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out)))
+        return out
+
+    def hist_render_device(self, K: int, n_bins: int, B: int, channels: int, d_hist: int, frac_bits: int, M: int, T: int, d_taps: int,
+                           seed: int, d_out: int, d_weight: int = 0, stream: int = 0):
+        """hare_hist_render_device on raw device addresses + a hipStream_t: d_hist as receive_device accumulates it, d_taps (B x T float64),
+        d_out (K x channels x n_bins x M float64) written, d_weight (n_bins x B uint32) or 0.  Stream-ordered: no allocation, no free, no
+        wait."""
+        check(lib.hare_hist_render_device(self._h, int(K), int(n_bins), int(B), int(channels), d_hist or None, d_weight or None, int(frac_bits),
+                                          int(M), int(T), d_taps or None, int(seed) & 0xFFFFFFFFFFFFFFFF, d_out or None, stream or None))
 
     @staticmethod
     def direct_work_bytes(K: int) -> int:

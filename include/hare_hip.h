@@ -899,6 +899,33 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * problem, and not what the call is for.  There are no sharded variants: a crossing is not additive over shards, and summing device
  * histograms across GPUs is not part of this call -- reduce the histogram the sharded receive call returns with hare_hist_reduce.
  *
+ * Rendering (hare_hist_render_device, hare_hist_render).  The other thing wanted from a histogram is a pressure impulse response to listen
+ * to: band-filtered noise shaped by the energy envelope, weighted per channel by the direction the histogram recorded -- the usual
+ * rendering of the late part of a ray-traced response.  A pure function of the histogram, a seed and a filter table, formed on the device.
+ * Inputs: a histogram as in "Reduction" (K x n_bins x B entries of `channels` 1, 4, 9 or 16 words, frac_bits as given to the receive
+ * call); the optional weight of "Reduction" (n_bins x B uint32); M, the samples per bin (1 .. 1024); T, the taps per band filter
+ * (1 .. 1024); taps, B x T doubles, one FIR filter per band; seed, a uint64.  Output: out[(k * channels + ch) * N + n], doubles, with
+ * N = n_bins * M; every word is written once.  All floating-point work is FP64 without contraction, integers are uint64 and wrap, mix and
+ * G are those of "Scattering", and the steps run in exactly this order:
+ *
+ *   base_k   = mix(mix(seed + G) ^ (uint64)k)
+ *   s(k,i)   = (mix(base_k + (uint64)i * G) >> 63) ? -1.0 : 1.0            i = 0 .. N+T-2
+ *   y(k,b,n) : y = taps[b*T+0] * s(k, n+T-1);  for t = 1 .. T-1:  y = y + taps[b*T+t] * s(k, n+T-1-t)
+ *   p(k,b,i) : p = y0*y0;  for j = 1 .. M-1:  p = p + y_j*y_j           y_j = y(k,b,i*M+j); product rounded, then the add
+ *   g(k,i,b)   as in "Reduction" (h, or floor(h*weight/2^32)); W word only
+ *   e        = ldexp((double)g, -frac_bits)                               uint64 -> double, round to nearest even
+ *   a        = (p > 0.0 && e > 0.0) ? sqrt(e / p) : 0.0                   NaN p gives 0; infinite p gives 0
+ *   r_0 = 1.0;  for ch >= 1:  hW = hist[..+0] (unweighted), hc = (int64)hist[..+ch];  r_ch = hW != 0 ? (double)hc / (double)hW : 0.0
+ *   out(k,ch,n): i = n / M;  z = (a(k,i,0)*r_ch(k,i,0)) * y(k,0,n);  for b = 1 .. B-1:  z = z + (a(k,i,b)*r_ch(k,i,b)) * y(k,b,n)
+ *
+ * What the caller has to know.  The product by +-1 is exact, so each y is a sequential sum of signed taps.  For one band alone the sum
+ * of out^2 over a bin's samples equals e up to rounding; band cross terms vanish only as far as the caller's filters are orthogonal.  All
+ * channels of a receiver share one noise sequence, so direction is carried by the gains; receivers are decorrelated through k.  r_ch is
+ * the energy-weighted mean of the SN3D harmonic in that bin.  The gain is constant across a bin (no interpolation).  Deterministic early
+ * paths are better rendered as impulses than as noise: a caller who wants that deposits the direct sound and the image sources into a
+ * histogram of their own with the _device calls and renders only the rest here; rendering impulses is not part of this call.  The
+ * sequential order of y, p and z is part of the definition: parallelism is over (k, b, n) and (k, b, i), never inside a sum.
+ *
  * Setters: single-caller, like the build calls.  They validate, keep a host copy, and upload it when a device is present (as a build
  * pushes its partition; on a GPU-less host the copy goes up with the first receive call).  No receive call allocates for them.
  *   hare_scene_set_receivers    replaces the receivers: centers K x 3, radii K.  HARE_E_INVALID for K outside 1..256, a non-finite
@@ -1037,6 +1064,19 @@ HARE_API int hare_hist_reduce_device(hare_scene *s, int32_t K, int32_t n_bins, i
 HARE_API int hare_hist_reduce(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t *hist,
                               const uint32_t *weight /* nullable */, int32_t n_win, const int32_t *win, int32_t n_lev,
                               const uint32_t *levels, uint64_t *sums, int32_t *cross);
+/* The rendering of a histogram ("receivers", "Rendering" above) on DEVICE buffers: one launch, stream-ordered like hare_shoot_device -- no
+ * allocation, no free, no wait.  d_taps (B x T doubles) is a device buffer of the caller's: the call has nothing to upload.  d_weight
+ * nullable; d_out (K x channels x n_bins x M doubles) is WRITTEN, every word once.  Checked before anything runs (HARE_E_INVALID), in this
+ * order: 1 <= K <= 65 536, n_bins >= 1, 1 <= B <= 8, channels 1, 4, 9 or 16, K x n_bins x B x channels <= 2^27; 1 <= M <= 1024 and
+ * 1 <= T <= 1024; 0 <= frac_bits <= 62; K x channels x n_bins x M <= 2^28; null buffers; out overlapping the histogram, the weights or
+ * the taps.  Then HARE_E_NODEVICE, then HARE_E_STATE.  The scene names the device; its geometry is not read. */
+HARE_API int hare_hist_render_device(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void *d_hist,
+                                     const void *d_weight /* nullable */, int32_t frac_bits, int32_t M, int32_t T, const void *d_taps,
+                                     uint64_t seed, void *d_out, void *stream);
+/* The same from host buffers: upload, render, download, one synchronisation.  Also HARE_E_INVALID: a tap that is not finite. */
+HARE_API int hare_hist_render(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t *hist,
+                              const uint32_t *weight /* nullable */, int32_t frac_bits, int32_t M, int32_t T, const double *taps,
+                              uint64_t seed, double *out);
 /* hare_receive_batch / hare_receive_source with `hist` replaced by the reduction's arguments: the loop runs as in the parent call, the
  * histogram stays on the device, the reduction is enqueued behind the last cast on the same stream, and sums, crossings, detections,
  * state and counters come down -- never the histogram.  K and B are the scene's; channels is 4 with HARE_RECEIVE_DIRECTIONAL (9, 16 with the order flags), else 1.
