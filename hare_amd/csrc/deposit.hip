@@ -55,18 +55,6 @@ static __device__ __forceinline__ void deposit_tail(const DepositArgs& a, int k,
         if constexpr (C > 4) ambi_harmonics<C>(ax, ay, az, Y);
     }
 #pragma unroll
-    for (int b = 0; b < kMaxBands; ++b) {
-        if (b < B) {
-            const double m = quant_m((((a.power[b] * (g ? g[b] : 1.0)) * refl(b)) * fw) * a.scale);
-            if constexpr (C >= 4) {
-                atomicAdd(&w[C * b + 0], (unsigned long long)rint(m));
-                atomicAdd(&w[C * b + 1], dir_q(m, ax));
-                atomicAdd(&w[C * b + 2], dir_q(m, ay));
-                atomicAdd(&w[C * b + 3], dir_q(m, az));
-                if constexpr (C > 4) ambi_add<C>(&w[C * b], m, Y);
-            } else {
-                atomicAdd(&w[b], (unsigned long long)rint(m));
-            }
-        }
-    }
+    for (int b = 0; b < kMaxBands; ++b)
+        if (b < B) hist_add<C>(&w[C * b], quant_m((((a.power[b] * (g ? g[b] : 1.0)) * refl(b)) * fw) * a.scale), ax, ay, az, Y);
 }

@@ -35,22 +35,10 @@ static __device__ __forceinline__ void direct_deposit_body(const DepositArgs& a)
     deposit_tail<C>(a, k, a.pos[0], a.pos[1], a.pos[2], [](double&, double&, double&) {}, [](int) { return 1.0; });
 }
 
-extern "C" __global__ __launch_bounds__(256) void hare_direct_deposit(DirectArgs a)
-{
-    direct_deposit_body<1>(a.d);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_direct_deposit_dir(DirectArgs a)
-{
-    direct_deposit_body<4>(a.d);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_direct_deposit_dir2(DirectArgs a)
-{
-    direct_deposit_body<9>(a.d);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_direct_deposit_dir3(DirectArgs a)
-{
-    direct_deposit_body<16>(a.d);
-}
+#define HARE_DIRECT_DEPOSIT_KERNEL(SUFFIX, C)                                                   \
+    extern "C" __global__ __launch_bounds__(256) void hare_direct_deposit##SUFFIX(DirectArgs a) \
+    {                                                                                           \
+        direct_deposit_body<C>(a.d);                                                            \
+    }
+HARE_CHANNEL_FORMS(HARE_DIRECT_DEPOSIT_KERNEL)
+#undef HARE_DIRECT_DEPOSIT_KERNEL

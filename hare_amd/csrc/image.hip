@@ -197,22 +197,10 @@ static __device__ __forceinline__ void image_deposit_body(const ImageArgs& a)
         [&](int b) { return poly_reflectance(a.sc, a.d.bands, p, b); });
 }
 
-extern "C" __global__ __launch_bounds__(256) void hare_image_deposit(ImageArgs a)
-{
-    image_deposit_body<1>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_image_deposit_dir(ImageArgs a)
-{
-    image_deposit_body<4>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_image_deposit_dir2(ImageArgs a)
-{
-    image_deposit_body<9>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_image_deposit_dir3(ImageArgs a)
-{
-    image_deposit_body<16>(a);
-}
+#define HARE_IMAGE_DEPOSIT_KERNEL(SUFFIX, C)                                                  \
+    extern "C" __global__ __launch_bounds__(256) void hare_image_deposit##SUFFIX(ImageArgs a) \
+    {                                                                                         \
+        image_deposit_body<C>(a);                                                             \
+    }
+HARE_CHANNEL_FORMS(HARE_IMAGE_DEPOSIT_KERNEL)
+#undef HARE_IMAGE_DEPOSIT_KERNEL

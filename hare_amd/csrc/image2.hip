@@ -267,22 +267,10 @@ static __device__ __forceinline__ void image2_deposit_body(const Image2Args& a)
         [&](int b) { return poly_reflectance(a.sc, a.d.bands, p, b) * poly_reflectance(a.sc, a.d.bands, q, b); });
 }
 
-extern "C" __global__ __launch_bounds__(256) void hare_image2_deposit(Image2Args a)
-{
-    image2_deposit_body<1>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_image2_deposit_dir(Image2Args a)
-{
-    image2_deposit_body<4>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_image2_deposit_dir2(Image2Args a)
-{
-    image2_deposit_body<9>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_image2_deposit_dir3(Image2Args a)
-{
-    image2_deposit_body<16>(a);
-}
+#define HARE_IMAGE2_DEPOSIT_KERNEL(SUFFIX, C)                                                   \
+    extern "C" __global__ __launch_bounds__(256) void hare_image2_deposit##SUFFIX(Image2Args a) \
+    {                                                                                           \
+        image2_deposit_body<C>(a);                                                              \
+    }
+HARE_CHANNEL_FORMS(HARE_IMAGE2_DEPOSIT_KERNEL)
+#undef HARE_IMAGE2_DEPOSIT_KERNEL

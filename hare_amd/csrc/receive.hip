@@ -1,6 +1,8 @@
-// receive.hip -- hare_receive_reflect / hare_receive_scatter / hare_receive_scatter_rain (and their _dir forms): the receiver step of the receive loop (include/hare_hip.h,
-// "receivers"), #included from kernels.hip.  One body (receive_body), three kernels: scattering and rain are compile-time switches.  And
-// hare_rain_step, diffuse rain's emit and deposit (below).
+// receive.hip -- the receiver step of the receive loop (include/hare_hip.h, "receivers"), #included from kernels.hip.  One body
+// (receive_body) makes hare_receive_reflect, hare_receive_scatter, hare_receive_scatter_rain and the two _map kernels, each in the four
+// channel forms of HARE_CHANNEL_FORMS (20 entry points): scattering, rain, the channel count and the receiver map are compile-time
+// switches.  And hare_rain_step, diffuse rain's emit and deposit (rain_body, four forms).  The pieces every kernel that adds histogram
+// words shares are here too: quant_m, dir_q, ambi_harmonics, hist_add, scatter_base and the form list.
 //
 // One lane per ray, in place of hare_reflect behind every cast of hare_receive_device's loop (receive.cpp: receive_step, which
 // bounce_device_impl runs behind every cast).  A live ray reads its ray, its event and its state once; runs through every receiver sphere in ascending order with the
@@ -50,6 +52,13 @@ constexpr unsigned long long kScatterGamma = 0x9E3779B97F4A7C15ull;
 static __device__ __forceinline__ double scatter_u(unsigned long long base, unsigned long long c8, unsigned j)
 {
     return (double)(scatter_mix(base + (c8 | (unsigned long long)j) * kScatterGamma) >> 11) * 0x1p-53;
+}
+// the stream of ray i of a call, the `base` of its draws: mix(mix(seed + G) ^ global ray index).  Counter-based: whoever asks for word j
+// of cast c of this ray draws the same bits
+template <class Args>
+static __device__ __forceinline__ unsigned long long scatter_base(const Args& a, int64_t i)
+{
+    return scatter_mix(scatter_mix(a.seed + kScatterGamma) ^ (unsigned long long)(a.ray_base + i));
 }
 // the diffuse direction of a ray r that hit a polygon of normal n at e (|d_out| = |d|): the header's operations in the header's order
 static __device__ __forceinline__ RayRec scatter_hit(double nx, double ny, double nz, const RayRec& r, const XEventRec& e,
@@ -149,12 +158,24 @@ static __device__ __forceinline__ void ambi_harmonics(double x, double y, double
         Y[11] = kAmbiC58 * (x * (xx - 3.0 * yy));
     }
 }
-// a lane's own adds of one band's channels 4 .. C - 1 at w = &hist[... + 0] (the map kernels, the rain and the source paths add per lane)
+// The channel forms of a kernel, (name suffix, channel count C): the host names them through the same list (scene.h: kChannelSuffix).
+// Every kernel that adds histogram words -- the five receive kernels, hare_rain_step and the three deposits of the source paths
+// (direct.hip, image.hip, image2.hip) -- is instantiated from it
+#define HARE_CHANNEL_FORMS(X) X(, 1) X(_dir, 4) X(_dir2, 9) X(_dir3, 16)
+// THE band writer: a lane's own adds of the C words of one band at w (the map kernels, the naive form, the rain and the source paths add
+// per lane).  Word 0 is rint(m); words 1 .. 3 are m times the arrival vector a and words 4 .. C - 1 m times its polynomials Y, through
+// dir_q.  C = 1 reads neither a nor Y
 template <int C>
-static __device__ __forceinline__ void ambi_add(unsigned long long* w, double m, const double (&Y)[kAmbiMax])
+static __device__ __forceinline__ void hist_add(unsigned long long* w, double m, double ax, double ay, double az, const double (&Y)[kAmbiMax])
 {
+    atomicAdd(&w[0], (unsigned long long)rint(m));
+    if constexpr (C >= 4) {
+        atomicAdd(&w[1], dir_q(m, ax));
+        atomicAdd(&w[2], dir_q(m, ay));
+        atomicAdd(&w[3], dir_q(m, az));
 #pragma unroll
-    for (int j = 0; j < C - 4; ++j) atomicAdd(&w[4 + j], dir_q(m, Y[j]));
+        for (int j = 0; j < C - 4; ++j) atomicAdd(&w[4 + j], dir_q(m, Y[j]));
+    }
 }
 // The wave's sums of sixteen words per lane in 17 exchanges instead of 16 x 6: four steps halve what a lane holds (bit 5, 4, 3, 2 of the
 // lane picks the half it keeps and passes the other on), the last two are the plain butterfly.  Returns, in every lane, the wave's sum of
@@ -285,11 +306,7 @@ static __device__ __forceinline__ void map_receivers(const ReceiveMapArgs& a, in
                         for (int b = 0; b < B; ++b) {
                             const double Eb = a.init_state ? 1.0 : a.state[(size_t)(b + 1) * (size_t)a.n + (size_t)i];
                             const double mb = quant_m(Eb * a.scale);
-                            atomicAdd(&w[C * b + 0], (unsigned long long)rint(mb));
-                            atomicAdd(&w[C * b + 1], dir_q(mb, ax));
-                            atomicAdd(&w[C * b + 2], dir_q(mb, ay));
-                            atomicAdd(&w[C * b + 3], dir_q(mb, az));
-                            if constexpr (C > 4) ambi_add<C>(&w[C * b], mb, Y);
+                            hist_add<C>(&w[C * b], mb, ax, ay, az, Y);
                         }
                     } else {
                         unsigned long long* const w = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B;
@@ -303,18 +320,24 @@ static __device__ __forceinline__ void map_receivers(const ReceiveMapArgs& a, in
     }
 }
 
-// RAIN (hare_receive_scatter_rain, HARE_RECEIVE_DIFFUSE_RAIN): a ray whose reflection in the previous cast was diffuse (ReceiveArgs::rain_flag)
-// skips the receiver step -- hare_rain_step has deposited that segment -- and every reflected ray writes the flag after its choice.
-// DIR (the _dir kernels, HARE_RECEIVE_DIRECTIONAL): four channels per histogram word.  The arrival vector is one per ray and cast; it costs a
-// sqrt and three divisions, so it is formed behind the first ballot that found a binned detection, not for every ray of every cast.  The
-// quantised words are formed inside the band loop (4 x 8 of them held per lane would be 64 VGPRs).  Aggregated, lanes 16 ch + b add the
-// 4 B contiguous words of a bin (at most 256 B) in one atomic instruction.
-// MAP (the _map kernels, a scene with a receiver map): no staging; the receiver step is map_receivers, above.  Everything below the
-// receiver step is the same code.
-// C (the channel count): 1, and 4 for DIR; 9 and 16 (the _dir2 / _dir3 kernels, HARE_RECEIVE_ORDER2 / _ORDER3) evaluate the polynomials of the
-// arrival vector with it, once per ray and cast, and hold them (10 or 24 VGPRs) through the receiver loop.  Aggregated, the wave sums a
-// band's words with wave_sum16_u64 -- lane 4 ch + s then holds channel ch -- and the sub-lane s keeps bands s and s + 4: the B C contiguous
-// words of a bin go out in one pass of 64 lanes over bands 0..3 and, for B > 4, a second over bands 4..7, one atomic per word per wave.
+// The body of one cast, a lane per ray, in four parts.
+//   1. Who takes the receiver step.  A retired ray takes none of the body.  With RAIN a ray whose last reflection was diffuse
+//      (ReceiveArgs::rain_flag) skips the step: hare_rain_step has deposited that segment.  In a call with the image flags a ray whose
+//      reflections so far were specular skips it too (`imaged`): those paths are the image deposits'.
+//   2. The receiver step.  MAP: map_receivers, above, per lane and before the event and the energies are read.  Otherwise the linear
+//      loop over the staged receivers: the header's test, a ballot, the detection counters from lane 0, and the adds of the lanes that
+//      are binned.  The arrival vector (C >= 4) costs a sqrt and three divisions and, for C > 4, its polynomials, held through the loop
+//      (10 or 24 VGPRs): it is formed once per ray and cast, behind the first ballot that found a binned detection.  Naive
+//      (`aggregate` 0), a lane adds its own words with hist_add (C = 1: its B quantised words).  Aggregated, the wave runs one round per
+//      distinct bin and sums its lanes' words first; the quantised words are formed inside the band loop, never held.  Which lane ends
+//      up with which word is what differs between the channel counts:
+//        C = 1   wave_allsum_u64 per band; lane b adds band b: B contiguous words, one atomic instruction;
+//        C = 4   wave_sum4_u64 per band; lane 16 ch + b adds channel ch of band b: 4 B contiguous words, one instruction;
+//        C > 4   wave_sum16_u64 per band; lane 4 ch + s holds channel ch and keeps bands s and s + 4: the B C contiguous words go out
+//                in one pass over bands 0 .. 3 and, for B > 4, a second over bands 4 .. 7, one atomic per word per wave.
+//   3. State update and termination: absorption, with SCATTER the choice (scatter_base, word 0 of this cast's counter against the row
+//      mean p) and its weights, the rules of ReceiveArgs::cut, then the stores.
+//   4. Reflection, marks and the live-block byte, as hare_reflect; with RAIN every reflected ray writes its flag after its choice.
 template <bool SCATTER, bool RAIN = false, int C = 1, bool MAP = false, typename Args = ReceiveArgs>
 static __device__ __forceinline__ void receive_body(const Args& a)
 {
@@ -354,7 +377,7 @@ static __device__ __forceinline__ void receive_body(const Args& a)
             double p = sg[0];
             for (int b = 1; b < B; ++b) p = p + sg[b];
             p = p / (double)B;
-            imaged = !(scatter_u(scatter_mix(scatter_mix(a.seed + kScatterGamma) ^ (unsigned long long)(a.ray_base + i)), 0ull, 0) < p);
+            imaged = !(scatter_u(scatter_base(a, i), 0ull, 0) < p);
         }
     }
     // HARE_RECEIVE_IMAGE2 (uniform bits; the scatter kernels).  Cast 1 stores the byte HERE, from cast 0's outcome and this cast's own draw,
@@ -370,7 +393,7 @@ static __device__ __forceinline__ void receive_body(const Args& a)
                 double p = sg[0];
                 for (int b = 1; b < B; ++b) p = p + sg[b];
                 p = p / (double)B;
-                spec = !(scatter_u(scatter_mix(scatter_mix(a.seed + kScatterGamma) ^ (unsigned long long)(a.ray_base + i)), (unsigned long long)a.cast << 8, 0) < p);
+                spec = !(scatter_u(scatter_base(a, i), (unsigned long long)a.cast << 8, 0) < p);
             }
             a.spec2[i] = spec ? 1 : 0;
         }
@@ -449,15 +472,7 @@ static __device__ __forceinline__ void receive_body(const Args& a)
                     unsigned long long* const row = a.hist + (size_t)k * (size_t)a.n_bins * (size_t)B * C;
                     if (!a.aggregate) {                                          // naive form (A/B): every detecting lane adds its own words
                         if (binned)
-                            for (int b = 0; b < B; ++b) {
-                                const double m = quant_m(E[b] * a.scale);
-                                unsigned long long* const w = &row[((size_t)bin * B + b) * C];
-                                atomicAdd(&w[0], (unsigned long long)rint(m));
-                                atomicAdd(&w[1], dir_q(m, ax));
-                                atomicAdd(&w[2], dir_q(m, ay));
-                                atomicAdd(&w[3], dir_q(m, az));
-                                if constexpr (C > 4) ambi_add<C>(w, m, Y);
-                            }
+                            for (int b = 0; b < B; ++b) hist_add<C>(&row[((size_t)bin * B + b) * C], quant_m(E[b] * a.scale), ax, ay, az, Y);
                         continue;
                     }
                     unsigned long long todo = bm;
@@ -570,7 +585,7 @@ static __device__ __forceinline__ void receive_body(const Args& a)
                     for (int b = 1; b < kMaxBands; ++b)
                         if (b < B) p = p + sig[b];
                     p = p / (double)B;
-                    base = scatter_mix(scatter_mix(a.seed + kScatterGamma) ^ (unsigned long long)(a.ray_base + i));
+                    base = scatter_base(a, i);
                     c8 = (unsigned long long)a.cast << 8;
                     diffuse = scatter_u(base, c8, 0) < p;
                     const double den = diffuse ? p : 1.0 - p;                  // one division per band: sigma / p or (1 - sigma) / (1 - p)
@@ -596,7 +611,7 @@ static __device__ __forceinline__ void receive_body(const Args& a)
                         cut = true;
                         if (a.cut & kCutRoulette) {
                             if constexpr (!SCATTER) {
-                                base = scatter_mix(scatter_mix(a.seed + kScatterGamma) ^ (unsigned long long)(a.ray_base + i));
+                                base = scatter_base(a, i);
                                 c8 = (unsigned long long)a.cast << 8;
                             }
                             const double ps = m / a.floor;
@@ -639,58 +654,7 @@ static __device__ __forceinline__ void receive_body(const Args& a)
     }
 }
 
-extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect(ReceiveArgs a)
-{
-    receive_body<false>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter(ReceiveArgs a)
-{
-    receive_body<true>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_rain(ReceiveArgs a)
-{
-    receive_body<true, true>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect_dir(ReceiveArgs a)
-{
-    receive_body<false, false, 4>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_dir(ReceiveArgs a)
-{
-    receive_body<true, false, 4>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_rain_dir(ReceiveArgs a)
-{
-    receive_body<true, true, 4>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect_map(ReceiveMapArgs a)
-{
-    receive_body<false, false, 1, true, ReceiveMapArgs>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_map(ReceiveMapArgs a)
-{
-    receive_body<true, false, 1, true, ReceiveMapArgs>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect_map_dir(ReceiveMapArgs a)
-{
-    receive_body<false, false, 4, true, ReceiveMapArgs>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_map_dir(ReceiveMapArgs a)
-{
-    receive_body<true, false, 4, true, ReceiveMapArgs>(a);
-}
-
-// the higher orders' forms of the five kernels above (HARE_RECEIVE_ORDER2: _dir2, nine channels; HARE_RECEIVE_ORDER3: _dir3, sixteen)
-#define HARE_RECEIVE_ORDER_KERNELS(SUFFIX, C)                                                                      \
+#define HARE_RECEIVE_KERNELS(SUFFIX, C)                                                                            \
     extern "C" __global__ __launch_bounds__(256) void hare_receive_reflect##SUFFIX(ReceiveArgs a)                  \
     {                                                                                                              \
         receive_body<false, false, C>(a);                                                                          \
@@ -711,9 +675,8 @@ extern "C" __global__ __launch_bounds__(256) void hare_receive_scatter_map_dir(R
     {                                                                                                              \
         receive_body<true, false, C, true, ReceiveMapArgs>(a);                                                     \
     }
-HARE_RECEIVE_ORDER_KERNELS(_dir2, 9)
-HARE_RECEIVE_ORDER_KERNELS(_dir3, 16)
-#undef HARE_RECEIVE_ORDER_KERNELS
+HARE_CHANNEL_FORMS(HARE_RECEIVE_KERNELS)
+#undef HARE_RECEIVE_KERNELS
 
 // ---- diffuse rain (HARE_RECEIVE_DIFFUSE_RAIN; the header's "receivers", "Diffuse rain")
 // hare_rain_step runs between a cast's shoot and hare_receive_scatter_rain, which overwrites the rays and the state: a lane per ray reads what
@@ -723,7 +686,8 @@ HARE_RECEIVE_ORDER_KERNELS(_dir3, 16)
 // kernels skip under HARE_SHOOT_RETIRED_RAYS (no traversal, flag 0).  The deposit adds per lane, not per distinct bin of a wave as the
 // receiver step does: nearly every visible ray deposits and their bins are spread, so the wave's rounds over distinct bins cost more than
 // they save (hall, 1M rays, K = 8, B = 8: the rain loop 94.5 ms aggregated, 79.5 ms per lane; the same histogram).
-// DIR (hare_rain_step_dir, HARE_RECEIVE_DIRECTIONAL): the deposit adds four words per band, weighted by -(v / dist).
+// C is the channel count: for C >= 4 the deposit adds a band's C words with hist_add, weighted by the arrival vector -(v / dist) and its
+// polynomials, quantised where they are added; C = 1 adds the B words it quantised in the band loop.
 template <int C>
 static __device__ __forceinline__ void rain_body(const RainArgs& a)
 {
@@ -821,13 +785,7 @@ static __device__ __forceinline__ void rain_body(const RainArgs& a)
                 unsigned long long* const row = a.hist + ((size_t)k * (size_t)a.n_bins + (size_t)bin) * (size_t)B * C;
 #pragma unroll
                 for (int b = 0; b < kMaxBands; ++b) {
-                    if (b < B) {
-                        atomicAdd(&row[C * b + 0], (unsigned long long)rint(mq[b]));
-                        atomicAdd(&row[C * b + 1], dir_q(mq[b], ax));
-                        atomicAdd(&row[C * b + 2], dir_q(mq[b], ay));
-                        atomicAdd(&row[C * b + 3], dir_q(mq[b], az));
-                        if constexpr (C > 4) ambi_add<C>(&row[C * b], mq[b], Y);
-                    }
+                    if (b < B) hist_add<C>(&row[C * b], mq[b], ax, ay, az, Y);
                 }
             }
         } else if (binned) {                                            // per lane: rain's bins are spread, see above
@@ -857,22 +815,10 @@ static __device__ __forceinline__ void rain_body(const RainArgs& a)
     }
 }
 
-extern "C" __global__ __launch_bounds__(256) void hare_rain_step(RainArgs a)
-{
-    rain_body<1>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_rain_step_dir(RainArgs a)
-{
-    rain_body<4>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_rain_step_dir2(RainArgs a)
-{
-    rain_body<9>(a);
-}
-
-extern "C" __global__ __launch_bounds__(256) void hare_rain_step_dir3(RainArgs a)
-{
-    rain_body<16>(a);
-}
+#define HARE_RAIN_KERNEL(SUFFIX, C)                                                                \
+    extern "C" __global__ __launch_bounds__(256) void hare_rain_step##SUFFIX(RainArgs a)           \
+    {                                                                                              \
+        rain_body<C>(a);                                                                           \
+    }
+HARE_CHANNEL_FORMS(HARE_RAIN_KERNEL)
+#undef HARE_RAIN_KERNEL

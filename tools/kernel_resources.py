@@ -6,6 +6,9 @@ tests/golden/image2/parent_receive_resources.json is this tool's output on a bui
   python tools/kernel_resources.py /tmp/parent/hare_amd/csrc/build/hare_kernels.s hare_receive hare_rain > tests/golden/image2/parent_receive_resources.json
 tests/golden/deposits/parent_resources.json is its output on a build of the parent commit of the shared deposit (deposit.hip), twelve kernels:
   python tools/kernel_resources.py /tmp/parent/hare_amd/csrc/build/hare_kernels.s hare_direct hare_image > tests/golden/deposits/parent_resources.json
+tests/golden/receive_pieces/parent_resources.json is its output on a build of the parent commit of the shared band writer (hist_add), the 36
+kernels that add histogram words:
+  python tools/kernel_resources.py /tmp/parent/hare_amd/csrc/build/hare_kernels.s hare_receive hare_rain hare_direct_deposit hare_image_deposit hare_image2_deposit > tests/golden/receive_pieces/parent_resources.json
 profiles/image2/kernel_resources.json is its output for `hare_image2` on this tree's build.
 usage: python tools/kernel_resources.py hare_kernels.s PREFIX [PREFIX ..]"""
 import json
