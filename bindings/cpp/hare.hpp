@@ -336,6 +336,27 @@ public:
         check(hare_hist_reduce(scene_, K, n_bins, B, channels, hist.data(), r.weight.empty() ? nullptr : r.weight.data(), n_win, r.windows.data(),
                                n_lev, r.levels.data(), sums.data(), cross.data()));
     }
+    // hare_hist_project (include/hare_hip.h, "receivers", "Projection"): hist as Receive returns it (K x n_bins x B x channels; channel 0 is
+    // read) projected onto the vectors coef (J x n_bins, vector-major, 1 <= J <= 32).  proj: K x B x J x 2, the lo and hi words of the exact
+    // 128-bit two's-complement sums over the bins of coef[j][i] * g(k, i, b).  weight: n_bins x B in units of 2^-32 (AirWeights), or empty: none
+    void HistProject(const std::vector<uint64_t>& hist, int K, int n_bins, int B, int channels, const std::vector<int32_t>& coef,
+                     std::vector<uint64_t>& proj, const std::vector<uint32_t>& weight = {})
+    {
+        if (K < 0 || n_bins < 1 || B < 0 || channels < 0 || hist.size() != (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels)
+            throw std::invalid_argument("HistProject: hist must hold K x n_bins x B x channels values");
+        if (coef.empty() || coef.size() % (size_t)n_bins != 0) throw std::invalid_argument("HistProject: coef must hold J x n_bins values");
+        if (!weight.empty() && weight.size() != (size_t)n_bins * (size_t)B) throw std::invalid_argument("HistProject: weight must hold n_bins x B values (or none)");
+        const size_t J = coef.size() / (size_t)n_bins;
+        proj.assign((size_t)K * (size_t)B * J * 2, 0);
+        check(hare_hist_project(scene_, K, n_bins, B, channels, hist.data(), weight.empty() ? nullptr : weight.data(), (int32_t)J, coef.data(),
+                                proj.data()));
+    }
+    // hare_hist_project_device on device pointers and a hipStream_t: d_proj (K x B x J x 2 uint64) written.  Stream-ordered.
+    void HistProjectDevice(int K, int n_bins, int B, int channels, const void* d_hist, int J, const void* d_coef, void* d_proj,
+                           const void* d_weight = nullptr, void* stream = nullptr)
+    {
+        check(hare_hist_project_device(scene_, K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj, stream));
+    }
     // hare_hist_render (include/hare_hip.h, "receivers", "Rendering"): hist as Receive returns it (K x n_bins x B x channels), rendered to
     // impulse responses of M samples per bin -- noise from `seed`, filtered per band by taps (B x T), shaped by the histogram.  out:
     // K x channels x (n_bins * M).  weight: n_bins x B in units of 2^-32 (AirWeights), or empty: none

@@ -298,6 +298,13 @@ namespace Hare
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_hist_reduce(IntPtr scene, int K, int n_bins, int B, int channels, [In] ulong[] hist, [In] uint[] weight,
                                                       int n_win, [In] int[] win, int n_lev, [In] uint[] levels, [Out] ulong[] sums, [Out] int[] cross);
+            // the projection of a histogram onto integer vectors over the bins on the device (include/hare_hip.h, "receivers", "Projection")
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_hist_project_device(IntPtr scene, int K, int n_bins, int B, int channels, IntPtr d_hist, IntPtr d_weight,
+                                                              int J, IntPtr d_coef, IntPtr d_proj, IntPtr stream);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_hist_project(IntPtr scene, int K, int n_bins, int B, int channels, [In] ulong[] hist, [In] uint[] weight,
+                                                       int J, [In] int[] coef, [Out] ulong[] proj);
             // the rendering of a histogram to impulse responses on the device (include/hare_hip.h, "receivers", "Rendering")
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_hist_render_device(IntPtr scene, int K, int n_bins, int B, int channels, IntPtr d_hist, IntPtr d_weight,

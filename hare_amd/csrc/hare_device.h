@@ -678,6 +678,21 @@ struct ReduceArgs {
     uint32_t levels[kMaxReduceLevels];        // fractions in units of 2^-32
 };
 
+// hare_hist_project (project.hip): a receive histogram projected onto caller-supplied integer vectors over the bins, per receiver and band
+// (include/hare_hip.h, "receivers", "Projection").  Everything but the four buffers by value
+constexpr int kMaxProjectVectors = 32;
+constexpr int kProjectGroup = 8;           // vectors a sweep over the receiver's block carries (project.hip)
+struct ProjectArgs {
+    const unsigned long long* hist;   // K x n_bins x bands x channels words; channel 0 is read
+    const uint32_t* weight;           // n_bins x bands, units of 2^-32 (null: none)
+    const int32_t* coef;              // n_vec x n_bins, vector-major
+    unsigned long long* proj;         // K x bands x n_vec x 2: lo, hi; each word written once
+    int32_t n_bins;
+    int32_t bands;                    // 1 .. kMaxBands
+    int32_t channels;                 // 1, 4, 9 or 16
+    int32_t n_vec;                    // J: 1 .. kMaxProjectVectors
+};
+
 // hare_hist_render (render.hip): a receive histogram rendered to pressure impulse responses, band noise shaped by the energy envelope
 // (include/hare_hip.h, "receivers", "Rendering").  A workgroup renders `tile_bins` whole bins of one receiver; the host sizes the tile and
 // the dynamic LDS (render_plan, receive.cpp)

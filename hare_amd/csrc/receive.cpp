@@ -606,6 +606,48 @@ static int reduce_check_buffers(const char* who, int64_t K, int32_t n_bins, int3
     return HARE_OK;
 }
 
+// ---- the projection of a histogram (include/hare_hip.h, "receivers", "Projection"; the kernel: project.hip)
+// everything hare_hist_project_device and hare_hist_project check before anything runs, in the header's order; buffers device or host
+static int project_check(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const void* hist, const void* weight, int32_t J,
+                         const void* coef, const void* proj)
+{
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    if (int rc = hist_check_shape(who, K, n_bins, B, channels)) return rc;
+    if (J < 1 || J > kMaxProjectVectors) return bad("J out of range (1 .. 32)");
+    if (!hist || !coef || !proj) return bad("null histogram / coefficients / output");
+    const size_t proj_bytes = (size_t)K * (size_t)B * (size_t)J * 2 * sizeof(uint64_t);
+    const struct { const void* p; size_t bytes; } in[] = {{hist, (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels * sizeof(uint64_t)},
+                                                          {weight, (size_t)n_bins * (size_t)B * sizeof(uint32_t)},
+                                                          {coef, (size_t)J * (size_t)n_bins * sizeof(int32_t)}};
+    for (const auto& b : in)
+        if (ranges_overlap(proj, proj_bytes, b.p, b.bytes)) return bad("the output must not overlap the histogram, the weights or the coefficients");
+    return HARE_OK;
+}
+
+static int project_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist,
+                           const void* d_weight, int32_t J, const void* d_coef, void* d_proj, hipStream_t st)
+{
+    if (!s.module || !s.module->hist_project) {
+        set_error("hare_hist_project missing from code object");
+        return HARE_E_STATE;
+    }
+    ProjectArgs a;
+    memset(&a, 0, sizeof a);
+    a.hist = (const unsigned long long*)d_hist;
+    a.weight = (const uint32_t*)d_weight;
+    a.coef = (const int32_t*)d_coef;
+    a.proj = (unsigned long long*)d_proj;
+    a.n_bins = n_bins;
+    a.bands = B;
+    a.channels = channels;
+    a.n_vec = J;
+    void* args[] = {&a};
+    return launch(H, s.module->hist_project, (unsigned)K, 256, 0, st, args);         // a workgroup per receiver
+}
+
 // ---- the rendering of a histogram (include/hare_hip.h, "receivers", "Rendering"; the kernel: render.hip)
 // everything hare_hist_render_device and hare_hist_render check before anything runs, in the header's order; buffers device or host
 static int render_check(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const void* hist, const void* weight,
@@ -1167,6 +1209,68 @@ int hare_hist_reduce(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_
         if (int rc = reduce_enqueue(*s, H, K, n_bins, B, channels, d_hist, weight ? d_weight : nullptr, r, d_sums, d_cross, nullptr)) return rc;
         if (n_win > 0) HIP_TRY(H->MemcpyAsync(sums, d_sums, sums_bytes, hipMemcpyDeviceToHost, nullptr));
         if (n_lev > 0) HIP_TRY(H->MemcpyAsync(cross, d_cross, KB * (size_t)n_lev * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(H->StreamSynchronize(nullptr));
+        return HARE_OK;
+    };
+    const int rc = run();
+    if (rc != HARE_OK) (void)H->StreamSynchronize(nullptr);      // copies may still be in flight
+    dev_free(H, block);
+    return rc;
+    GUARD_END
+}
+
+int hare_hist_project_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
+                             int32_t J, const void* d_coef, void* d_proj, void* stream)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    if (int rc = project_check("hare_hist_project_device", K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj)) return rc;
+    GUARD_BEGIN
+    const HipApi* H = api_or_err();
+    if (!H) return HARE_E_NODEVICE;
+    DeviceGuard dev_guard(H, s->device);
+    if (!s->module) {
+        int rc = ensure_device(*s, H);
+        if (rc) return rc;
+    }
+    return project_enqueue(*s, H, K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj, (hipStream_t)stream);
+    GUARD_END
+}
+
+int hare_hist_project(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t* hist, const uint32_t* weight,
+                      int32_t J, const int32_t* coef, uint64_t* proj)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    if (int rc = project_check("hare_hist_project", K, n_bins, B, channels, hist, weight, J, coef, proj)) return rc;
+    GUARD_BEGIN
+    const HipApi* H = api_or_err();
+    if (!H) return HARE_E_NODEVICE;
+    DeviceGuard dev_guard(H, s->device);
+    if (!s->module) {
+        int rc = ensure_device(*s, H);
+        if (rc) return rc;
+    }
+    // one device block: histogram, output, coefficients, weights (the first two whole 8-byte words, then 4-byte words); up, project, down, one synchronisation
+    const size_t hist_bytes = (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels * sizeof(uint64_t);
+    const size_t proj_bytes = (size_t)K * (size_t)B * (size_t)J * 2 * sizeof(uint64_t);
+    const size_t coef_bytes = (size_t)J * (size_t)n_bins * sizeof(int32_t), weight_bytes = (size_t)n_bins * (size_t)B * sizeof(uint32_t);
+    void* block = nullptr;
+    HIP_TRY(H->Malloc(&block, hist_bytes + proj_bytes + coef_bytes + weight_bytes));
+    char* const d_hist = (char*)block;
+    char* const d_proj = d_hist + hist_bytes;
+    char* const d_coef = d_proj + proj_bytes;
+    char* const d_weight = d_coef + coef_bytes;
+    auto run = [&]() -> int {
+        HIP_TRY(H->MemcpyAsync(d_hist, hist, hist_bytes, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(H->MemcpyAsync(d_coef, coef, coef_bytes, hipMemcpyHostToDevice, nullptr));
+        if (weight) HIP_TRY(H->MemcpyAsync(d_weight, weight, weight_bytes, hipMemcpyHostToDevice, nullptr));
+        if (int rc = project_enqueue(*s, H, K, n_bins, B, channels, d_hist, weight ? d_weight : nullptr, J, d_coef, d_proj, nullptr)) return rc;
+        HIP_TRY(H->MemcpyAsync(proj, d_proj, proj_bytes, hipMemcpyDeviceToHost, nullptr));
         HIP_TRY(H->StreamSynchronize(nullptr));
         return HARE_OK;
     };

@@ -210,6 +210,26 @@ def sums_to_float(sums):
     return s[..., 0] + s[..., 1] * 2.0 ** 64, s[..., 2] + s[..., 3] * 2.0 ** 64
 
 
+def proj_to_int(proj):
+    """The sums of a projection [..., 2] (lo, hi; uint64) as an object array [...] of Python integers: the 128-bit two's complement read
+    exactly."""
+    p = np.asarray(proj, np.uint64)
+    lo, hi = p[..., 0].astype(object), p[..., 1].astype(object)
+    v = lo + hi * (1 << 64)
+    return v - (hi >> 63) * (1 << 128)
+
+
+def _project_coef(coef, n_bins: int):
+    """coef of a projection as a C-contiguous int32 [J, n_bins]; values outside int32 are an error, never wrapped."""
+    c = np.asarray(coef)
+    if c.ndim != 2 or c.shape[1] != n_bins or c.shape[0] < 1:
+        raise ValueError("coef must be int32 [J, n_bins] = [J, %d], J >= 1" % n_bins)
+    if c.dtype != np.int32:
+        if c.dtype.kind not in "iu" or (c.size and (int(c.max()) > 2 ** 31 - 1 or int(c.min()) < -2 ** 31)):
+            raise ValueError("coef must hold integers within int32")
+    return np.ascontiguousarray(c, np.int32)
+
+
 def _reduce_spec(reduce, n_bins: int, B: int):
     """reduce = dict(windows=[(lo, hi), ...] or None, levels=uint32 array or None, weight=uint32 [n_bins, B] or None), checked for shape
     only (the library checks the values): (weight, n_win, win, n_lev, levels), arrays or None."""
@@ -708,6 +728,31 @@ class Spatial_Partition:
         _, n_win, win, n_lev, lev = _reduce_spec(dict(windows=windows, levels=levels), n_bins, B)
         check(lib.hare_hist_reduce_device(self._h, int(K), int(n_bins), int(B), int(channels), d_hist or None, d_weight or None, n_win,
                                           ptr(win), n_lev, ptr(lev), d_sums or None, d_cross or None, stream or None))
+
+    def hist_project(self, hist, coef, weight=None, as_int: bool = False):
+        """hare_hist_project: a histogram [K, n_bins, B] or [K, n_bins, B, C] (C = 4, 9 or 16: channel 0 is read) of uint64, as the receive
+        calls return it, projected on this partition's device onto the vectors coef, int32 [J, n_bins] with 1 <= J <= 32 (include/hare_hip.h,
+        "receivers", "Projection"): the exact signed sums over the bins of coef[j, i] * g[k, i, b].  weight: uint32 [n_bins, B] (air_weights)
+        or None.  Returns uint64 [K, B, J, 2], the (lo, hi) words of the 128-bit two's-complement sums, or with as_int an object array
+        [K, B, J] of Python integers (proj_to_int)."""
+        hist = np.ascontiguousarray(hist, np.uint64)
+        if hist.ndim not in (3, 4) or (hist.ndim == 4 and hist.shape[3] not in (4, 9, 16)):
+            raise ValueError("hist must be uint64 [K, n_bins, B] or [K, n_bins, B, C], C = 4, 9 or 16")
+        K, nb, B = hist.shape[:3]
+        coef = _project_coef(coef, nb)
+        w, *_ = _reduce_spec(dict(weight=weight), nb, B)
+        proj = np.zeros((K, B, coef.shape[0], 2), np.uint64)
+        check(lib.hare_hist_project(self._h, K, nb, B, hist.shape[3] if hist.ndim == 4 else 1, ptr(hist), ptr(w), coef.shape[0], ptr(coef),
+                                    ptr(proj)))
+        return proj_to_int(proj) if as_int else proj
+
+    def hist_project_device(self, K: int, n_bins: int, B: int, channels: int, d_hist: int, J: int, d_coef: int, d_proj: int, d_weight: int = 0,
+                            stream: int = 0):
+        """hare_hist_project_device on raw device addresses + a hipStream_t: d_hist as receive_device accumulates it, d_coef (J x n_bins
+        int32), d_proj (K x B x J x 2 uint64) written, d_weight (n_bins x B uint32) or 0.  Stream-ordered: no allocation, no free, no wait,
+        no upload."""
+        check(lib.hare_hist_project_device(self._h, int(K), int(n_bins), int(B), int(channels), d_hist or None, d_weight or None, int(J),
+                                           d_coef or None, d_proj or None, stream or None))
 
     def hist_render(self, hist, taps, M: int, frac_bits: int, seed: int = 0, weight=None):
         """hare_hist_render: a histogram [K, n_bins, B] or [K, n_bins, B, C] (C = 4, 9 or 16) of uint64, as the receive calls return it,

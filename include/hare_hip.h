@@ -899,6 +899,30 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * problem, and not what the call is for.  There are no sharded variants: a crossing is not additive over shards, and summing device
  * histograms across GPUs is not part of this call -- reduce the histogram the sharded receive call returns with hare_hist_reduce.
  *
+ * Projection (hare_hist_project_device, hare_hist_project).  The reduction's sums are unsigned with a fixed weight (1 and i).  The general
+ * operation is the projection of each receiver's band histogram onto a few vectors of the caller's over the bins -- cosine and sine tables
+ * for the modulation transfer function behind the speech transmission index (IEC 60268-16), arbitrary time weightings, windows with soft
+ * edges, regressions over the decay -- formed on the device in integer arithmetic only, exact like everything else read from a histogram.
+ * Inputs: the histogram exactly as in "Reduction" (K x n_bins x B entries of `channels` 1, 4, 9 or 16 words; only the W word is read); the
+ * optional weight of "Reduction" (n_bins x B uint32, g = floor(h * w / 2^32); NULL: g = h); and
+ *
+ *   coef: J x n_bins int32, vector-major: c_j[i] = coef[j * n_bins + i]; every int32 value is legal, INT32_MIN included.  1 <= J <= 32.
+ *
+ * Output, for every receiver k, band b and vector j: the exact signed sum as a 128-bit two's-complement integer in two uint64 words, lo
+ * then hi:
+ *
+ *   proj[((k * B + b) * J + j) * 2 + 0 .. 1] = lo, hi of   sum over i in 0 .. n_bins-1 of  (int128) c_j[i] * g(k, i, b)
+ *
+ * Nothing wraps: |c| <= 2^31, g < 2^64 and at most 2^27 bins give |P| < 2^122.  What the caller does with it.  The units of c are the
+ * caller's -- round(cos(.) * 2^30), say -- and are divided out by the caller; frac_bits cancels in every ratio of two projections.  A
+ * vector of ones gives the total T = sum g, and c = i the reduction's S1 over the full window.  The modulation transfer function at the
+ * frequency F is sqrt(C^2 + S^2) / (T * 2^30) with C and S the projections onto round(2^30 cos(2 pi F t_i)) and round(2^30 sin(2 pi F t_i)),
+ * t_i the time of bin i's centre.  One workgroup projects one receiver, as in "Reduction".  There is no sharded variant and no _projected
+ * receive call; unlike a crossing a projection IS additive over shards, so a caller may add, as 128-bit integers, the results of
+ * hare_hist_project_device on each shard's device histogram (or project the histogram a sharded receive call returns).  With weight NULL
+ * the sum of the shards' projections is exactly the projection of the summed histogram; with weights each shard's floor() is taken on its
+ * own words, so g of the shards sums to at most one unit per bin, band and shard less than g of the summed histogram.
+ *
  * Rendering (hare_hist_render_device, hare_hist_render).  The other thing wanted from a histogram is a pressure impulse response to listen
  * to: band-filtered noise shaped by the energy envelope, weighted per channel by the direction the histogram recorded -- the usual
  * rendering of the late part of a ray-traced response.  A pure function of the histogram, a seed and a filter table, formed on the device.
@@ -1064,6 +1088,17 @@ HARE_API int hare_hist_reduce_device(hare_scene *s, int32_t K, int32_t n_bins, i
 HARE_API int hare_hist_reduce(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t *hist,
                               const uint32_t *weight /* nullable */, int32_t n_win, const int32_t *win, int32_t n_lev,
                               const uint32_t *levels, uint64_t *sums, int32_t *cross);
+/* The projection of a histogram ("receivers", "Projection" above) on DEVICE buffers: one launch, stream-ordered like hare_shoot_device --
+ * no allocation, no free, no wait, no upload.  d_coef (J x n_bins int32) is a device buffer of the caller's; d_weight nullable; d_proj
+ * (K x B x J x 2 uint64) is WRITTEN, every word once.  Checked before anything runs (HARE_E_INVALID), in this order: 1 <= K <= 65 536,
+ * n_bins >= 1, 1 <= B <= 8, channels 1, 4, 9 or 16, K x n_bins x B x channels <= 2^27; 1 <= J <= 32; null buffers; proj overlapping the
+ * histogram, the weights or the coefficients.  Then HARE_E_NODEVICE, then HARE_E_STATE.  The scene names the device; its geometry is not
+ * read.  Behind hare_receive_device on the same stream it projects the histogram that call accumulated. */
+HARE_API int hare_hist_project_device(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void *d_hist,
+                                      const void *d_weight /* nullable */, int32_t J, const void *d_coef, void *d_proj, void *stream);
+/* The same from host buffers: one allocation, upload, project, download, one synchronisation. */
+HARE_API int hare_hist_project(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t *hist,
+                               const uint32_t *weight /* nullable */, int32_t J, const int32_t *coef, uint64_t *proj);
 /* The rendering of a histogram ("receivers", "Rendering" above) on DEVICE buffers: one launch, stream-ordered like hare_shoot_device -- no
  * allocation, no free, no wait.  d_taps (B x T doubles) is a device buffer of the caller's: the call has nothing to upload.  d_weight
  * nullable; d_out (K x channels x n_bins x M doubles) is WRITTEN, every word once.  Checked before anything runs (HARE_E_INVALID), in this
