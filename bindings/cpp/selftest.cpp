@@ -104,6 +104,23 @@ int main()
         if (hare_scene_create(nullptr, 1, 0, &bad) != HARE_E_INVALID) ++failures;
         if (hare_voxel_build(fixed.native(), 0) != HARE_E_INVALID) ++failures;
         if (hare_shoot_batch(fixed.native(), 7, 0, 1, rays.data(), nullptr, nullptr, 0, ev.data(), nullptr) == HARE_OK) ++failures;
+        {   // the histogram calls (hist.cpp): refusals of the shape, of a null buffer and of an output on an input; all ahead of the device
+            std::vector<uint64_t> h(2 * 8 * 2, 1), o(2 * 2 * 3 * 4);
+            std::vector<int32_t> c(3 * 8, 1), win = {0, 8};
+            std::vector<uint32_t> w(8 * 2, 1u << 31);
+            std::vector<double> taps(2 * 3, 0.5);
+            hare_scene* const s = fixed.native();
+            if (hare_hist_reduce(s, 0, 8, 2, 1, h.data(), w.data(), 1, win.data(), 0, nullptr, o.data(), nullptr) != HARE_E_INVALID) ++failures;
+            if (hare_hist_reduce(s, 2, 8, 2, 1, h.data(), w.data(), 1, win.data(), 0, nullptr, nullptr, nullptr) != HARE_E_INVALID) ++failures;
+            if (hare_hist_reduce(s, 2, 8, 2, 1, h.data(), w.data(), 1, win.data(), 0, nullptr, h.data() + 4, nullptr) != HARE_E_INVALID) ++failures;
+            if (hare_hist_project(s, 2, 8, 2, 1, h.data(), w.data(), 33, c.data(), o.data()) != HARE_E_INVALID) ++failures;
+            if (hare_hist_project(s, 2, 8, 2, 1, h.data(), w.data(), 3, nullptr, o.data()) != HARE_E_INVALID) ++failures;
+            if (hare_hist_project(s, 2, 8, 2, 1, h.data(), w.data(), 3, c.data(), (uint64_t*)c.data()) != HARE_E_INVALID) ++failures;
+            if (hare_hist_render(s, 2, 8, 2, 1, h.data(), w.data(), 40, 0, 3, taps.data(), 7, (double*)o.data()) != HARE_E_INVALID) ++failures;
+            if (hare_hist_render(s, 2, 8, 2, 1, h.data(), w.data(), 40, 4, 3, nullptr, 7, (double*)o.data()) != HARE_E_INVALID) ++failures;
+            if (hare_hist_render(s, 2, 8, 2, 1, h.data(), w.data(), 40, 4, 3, taps.data(), 7, taps.data()) != HARE_E_INVALID) ++failures;
+            if (hare_hist_reduce_device(nullptr, 2, 8, 2, 1, h.data(), nullptr, 1, win.data(), 0, nullptr, o.data(), nullptr, nullptr) != HARE_E_INVALID) ++failures;
+        }
     } catch (const std::exception& e) {
         std::printf("exception: %s\n", e.what());
         return 2;

@@ -29,8 +29,6 @@
 
 namespace hare {
 
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb);     // launch.cpp
-
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
         hipError_t _e = (expr);                                                                \
@@ -513,17 +511,15 @@ static int receive_sharded(const char* who, hare_scene* const* scenes, int32_t n
             set_error(std::string(who) + ": null sums / crossings");
             return HARE_E_INVALID;
         }
-        const struct { const void* p; size_t bytes; } bufs[] = {{sums, KB * (size_t)red->n_win * 4 * sizeof(uint64_t)},
-                                                                {cross, KB * (size_t)red->n_lev * sizeof(int32_t)},
-                                                                {detections, K1 * 2 * sizeof(uint64_t)},
-                                                                {state_out, (size_t)n * (size_t)(1 + scene_bands(*s0, top_index)) * sizeof(double)},
-                                                                {red->weight, (size_t)n_bins * (size_t)scene_bands(*s0, top_index) * sizeof(uint32_t)}};
-        for (size_t x = 0; x < 2; ++x)      // the two new outputs against each other and the rest; the parent's buffers are checked as the parent checks them
-            for (size_t y = x + 1; y < 5; ++y)
-                if (ranges_overlap(bufs[x].p, bufs[x].bytes, bufs[y].p, bufs[y].bytes)) {
-                    set_error(std::string(who) + ": sums, crossings, detections, state and weights must not overlap");
-                    return HARE_E_INVALID;
-                }
+        // the two new outputs against each other and the rest; the parent's buffers are checked as the parent checks them
+        if (spans_overlap({{sums, KB * (size_t)red->n_win * 4 * sizeof(uint64_t)},
+                           {cross, KB * (size_t)red->n_lev * sizeof(int32_t)},
+                           {detections, K1 * 2 * sizeof(uint64_t)},
+                           {state_out, (size_t)n * (size_t)(1 + scene_bands(*s0, top_index)) * sizeof(double)},
+                           {red->weight, (size_t)n_bins * (size_t)scene_bands(*s0, top_index) * sizeof(uint32_t)}}, 2)) {
+            set_error(std::string(who) + ": sums, crossings, detections, state and weights must not overlap");
+            return HARE_E_INVALID;
+        }
     }
     if (first_ray) {
         if (int rc = source_check_range(who, n, *first_ray)) return rc;

@@ -695,7 +695,7 @@ struct ProjectArgs {
 
 // hare_hist_render (render.hip): a receive histogram rendered to pressure impulse responses, band noise shaped by the energy envelope
 // (include/hare_hip.h, "receivers", "Rendering").  A workgroup renders `tile_bins` whole bins of one receiver; the host sizes the tile and
-// the dynamic LDS (render_plan, receive.cpp)
+// the dynamic LDS (render_plan, hist.cpp)
 constexpr int kMaxRenderBin = 1024;        // M: samples per bin
 constexpr int kMaxRenderTaps = 1024;       // T: taps per band filter
 constexpr int kRenderThreads = 512;

@@ -1,0 +1,350 @@
+// hist.cpp -- what runs on a receive histogram once it is on the device (include/hare_hip.h, "receivers"): the reduction (hare_hist_reduce
+// / _device; the kernel: reduce.hip), the projection (hare_hist_project / _device; project.hip) and the rendering (hare_hist_render /
+// _device; render.hip).  A call is its own check and its own enqueue; what the calls share is the device prelude (device_call, launch.h),
+// the overlap test (spans_overlap, scene.h), one byte count per buffer, used by the check and by the staging, and the staging of the
+// host-buffer calls (staged_run).  reduce_check_spec and reduce_enqueue also serve hare_receive_*_reduced (bounce.cpp).
+// Product code; nothing from oracle/.
+#include <math.h>
+#include <string.h>
+#include <algorithm>
+#include <string>
+
+#include "../../include/hare_hip.h"
+#include "launch.h"
+#include "scene.h"
+
+namespace hare {
+
+namespace {
+
+int null_scene()
+{
+    set_error("null scene");
+    return HARE_E_INVALID;
+}
+
+// the two buffers every call reads
+size_t hist_bytes(int64_t K, int32_t n_bins, int32_t B, int32_t channels)
+{
+    return (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels * sizeof(uint64_t);
+}
+size_t weight_bytes(int32_t n_bins, int32_t B)
+{
+    return (size_t)n_bins * (size_t)B * sizeof(uint32_t);
+}
+
+// One buffer of a host-buffer call: copied up from src, down to dst, or neither
+struct StagePart {
+    size_t bytes;
+    const void* src;
+    void* dst;
+};
+
+// The host-buffer calls: ONE device block carved into the parts, each from a 16-byte boundary; the up-copies in list order, the call's
+// enqueue on the device addresses (null for a part of no bytes: an optional input left out, an output not asked for), the down-copies, one
+// synchronisation.  Everything on the null stream
+template <size_t N, class Enqueue>
+int staged_run(const HipApi* H, const StagePart (&parts)[N], Enqueue enqueue)
+{
+    size_t at[N], total = 0;
+    for (size_t x = 0; x < N; ++x) {
+        at[x] = total;
+        total += (parts[x].bytes + 15) & ~(size_t)15;
+    }
+    void* block = nullptr;
+    HIP_TRY(H->Malloc(&block, total));
+    void* d[N];
+    for (size_t x = 0; x < N; ++x) d[x] = parts[x].bytes ? (char*)block + at[x] : nullptr;
+    auto run = [&]() -> int {
+        for (size_t x = 0; x < N; ++x)
+            if (d[x] && parts[x].src) HIP_TRY(H->MemcpyAsync(d[x], parts[x].src, parts[x].bytes, hipMemcpyHostToDevice, nullptr));
+        if (int rc = enqueue(d)) return rc;
+        for (size_t x = 0; x < N; ++x)
+            if (d[x] && parts[x].dst) HIP_TRY(H->MemcpyAsync(parts[x].dst, d[x], parts[x].bytes, hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(H->StreamSynchronize(nullptr));
+        return HARE_OK;
+    };
+    const int rc = run();
+    if (rc != HARE_OK) (void)H->StreamSynchronize(nullptr);      // copies may still be in flight
+    dev_free(H, block);
+    return rc;
+}
+
+// what the three calls check of a histogram's shape
+int hist_check_shape(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels)
+{
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    if (K < 1 || K > kMaxMapReceivers) return bad("K out of range (1 .. 65 536)");
+    if (n_bins < 1) return bad("n_bins must be >= 1");
+    if (B < 1 || B > kMaxBands) return bad("bands out of range (1 .. 8)");
+    if (channels != 1 && channels != 4 && channels != 9 && channels != 16) return bad("channels must be 1, 4, 9 or 16");
+    if ((unsigned __int128)K * (unsigned)n_bins * (unsigned)B * (unsigned)channels > ((size_t)1 << 27)) return bad("K x n_bins x bands x channels exceeds 2^27");
+    return HARE_OK;
+}
+
+}  // namespace
+
+// ---- the reduction (include/hare_hip.h, "receivers", "Reduction"; the kernel: reduce.hip)
+int reduce_check_spec(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const ReduceSpec& r)
+{
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    if (int rc = hist_check_shape(who, K, n_bins, B, channels)) return rc;
+    if (r.n_win < 0 || r.n_win > kMaxReduceWindows) return bad("n_win out of range (0 .. 16)");
+    if (r.n_lev < 0 || r.n_lev > kMaxReduceLevels) return bad("n_lev out of range (0 .. 32)");
+    if (r.n_win + r.n_lev < 1) return bad("nothing to compute: n_win and n_lev are both 0");
+    if ((r.n_win > 0 && !r.win) || (r.n_lev > 0 && !r.levels)) return bad("null win / levels");
+    for (int32_t j = 0; j < r.n_win; ++j)
+        if (r.win[2 * j] < 0 || r.win[2 * j] > r.win[2 * j + 1] || r.win[2 * j + 1] > n_bins)
+            return bad("window " + std::to_string(j) + " is not 0 <= lo <= hi <= n_bins");
+    return HARE_OK;
+}
+
+int reduce_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist,
+                   const void* d_weight, const ReduceSpec& r, void* d_sums, void* d_cross, hipStream_t st)
+{
+    if (!s.module || !s.module->hist_reduce) {
+        set_error("hare_hist_reduce missing from code object");
+        return HARE_E_STATE;
+    }
+    ReduceArgs a;
+    memset(&a, 0, sizeof a);
+    a.hist = (const unsigned long long*)d_hist;
+    a.weight = (const uint32_t*)d_weight;
+    a.sums = (unsigned long long*)d_sums;
+    a.cross = (int32_t*)d_cross;
+    a.n_bins = n_bins;
+    a.bands = B;
+    a.channels = channels;
+    a.n_win = r.n_win;
+    a.n_lev = r.n_lev;
+    for (int32_t j = 0; j < 2 * r.n_win; ++j) a.win[j] = r.win[j];
+    for (int32_t l = 0; l < r.n_lev; ++l) a.levels[l] = r.levels[l];
+    void* args[] = {&a};
+    return launch(H, s.module->hist_reduce, (unsigned)K, 256, 0, st, args);          // a workgroup per receiver
+}
+
+namespace {
+
+struct ReduceBytes {
+    size_t hist, weight, sums, cross;
+};
+
+// what both reduce calls check of their buffers, device or host, behind reduce_check_spec: none null that is used, no output on another buffer
+int reduce_check_buffers(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const void* hist, const void* weight,
+                         const ReduceSpec& r, const void* sums, const void* cross, ReduceBytes& z)
+{
+    if (!hist || (r.n_win > 0 && !sums) || (r.n_lev > 0 && !cross)) {
+        set_error(std::string(who) + ": null histogram / sums / crossings");
+        return HARE_E_INVALID;
+    }
+    const size_t KB = (size_t)K * (size_t)B;
+    z = {hist_bytes(K, n_bins, B, channels), weight_bytes(n_bins, B), KB * (size_t)r.n_win * 4 * sizeof(uint64_t), KB * (size_t)r.n_lev * sizeof(int32_t)};
+    if (spans_overlap({{sums, z.sums}, {cross, z.cross}, {hist, z.hist}, {weight, z.weight}}, 2)) {
+        set_error(std::string(who) + ": sums and crossings must not overlap each other, the histogram or the weights");
+        return HARE_E_INVALID;
+    }
+    return HARE_OK;
+}
+
+// ---- the projection (include/hare_hip.h, "receivers", "Projection"; the kernel: project.hip)
+struct ProjectBytes {
+    size_t hist, weight, coef, proj;
+};
+
+// everything both project calls check before anything runs, in the header's order; buffers device or host
+int project_check(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const void* hist, const void* weight, int32_t J,
+                  const void* coef, const void* proj, ProjectBytes& z)
+{
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    if (int rc = hist_check_shape(who, K, n_bins, B, channels)) return rc;
+    if (J < 1 || J > kMaxProjectVectors) return bad("J out of range (1 .. 32)");
+    if (!hist || !coef || !proj) return bad("null histogram / coefficients / output");
+    z = {hist_bytes(K, n_bins, B, channels), weight_bytes(n_bins, B), (size_t)J * (size_t)n_bins * sizeof(int32_t),
+         (size_t)K * (size_t)B * (size_t)J * 2 * sizeof(uint64_t)};
+    if (spans_overlap({{proj, z.proj}, {hist, z.hist}, {weight, z.weight}, {coef, z.coef}}, 1))
+        return bad("the output must not overlap the histogram, the weights or the coefficients");
+    return HARE_OK;
+}
+
+int project_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
+                    int32_t J, const void* d_coef, void* d_proj, hipStream_t st)
+{
+    if (!s.module || !s.module->hist_project) {
+        set_error("hare_hist_project missing from code object");
+        return HARE_E_STATE;
+    }
+    ProjectArgs a;
+    memset(&a, 0, sizeof a);
+    a.hist = (const unsigned long long*)d_hist;
+    a.weight = (const uint32_t*)d_weight;
+    a.coef = (const int32_t*)d_coef;
+    a.proj = (unsigned long long*)d_proj;
+    a.n_bins = n_bins;
+    a.bands = B;
+    a.channels = channels;
+    a.n_vec = J;
+    void* args[] = {&a};
+    return launch(H, s.module->hist_project, (unsigned)K, 256, 0, st, args);         // a workgroup per receiver
+}
+
+// ---- the rendering (include/hare_hip.h, "receivers", "Rendering"; the kernel: render.hip)
+struct RenderBytes {
+    size_t hist, weight, taps, out;
+};
+
+// everything both render calls check before anything runs, in the header's order; buffers device or host
+int render_check(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const void* hist, const void* weight, int32_t frac_bits,
+                 int32_t M, int32_t T, const void* taps, const void* out, RenderBytes& z)
+{
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    if (int rc = hist_check_shape(who, K, n_bins, B, channels)) return rc;
+    if (M < 1 || M > kMaxRenderBin) return bad("M out of range (1 .. 1024)");
+    if (T < 1 || T > kMaxRenderTaps) return bad("T out of range (1 .. 1024)");
+    if (frac_bits < 0 || frac_bits > 62) return bad("frac_bits out of range (0 .. 62)");
+    if ((unsigned __int128)K * (unsigned)channels * (unsigned)n_bins * (unsigned)M > ((size_t)1 << 28)) return bad("K x channels x n_bins x M exceeds 2^28");
+    if (!hist || !taps || !out) return bad("null histogram / taps / output");
+    z = {hist_bytes(K, n_bins, B, channels), weight_bytes(n_bins, B), (size_t)B * (size_t)T * sizeof(double),
+         (size_t)K * (size_t)channels * (size_t)n_bins * (size_t)M * sizeof(double)};
+    if (spans_overlap({{out, z.out}, {hist, z.hist}, {weight, z.weight}, {taps, z.taps}}, 1))
+        return bad("the output must not overlap the histogram, the weights or the taps");
+    return HARE_OK;
+}
+
+// The tile of hare_hist_render (render.hip): whole bins, as many as keep the B x S filtered samples near 32 KiB and the gains within
+// 16 KiB -- one bin where a bin alone is more.  LDS: taps, samples, gains, a, sign mask: at most 8 * (8192 + 8192 + 2048 + 256 + 35) bytes
+unsigned render_plan(RenderArgs& a)
+{
+    const int32_t B = a.bands, C = a.channels;
+    a.tile_bins = std::max<int32_t>(1, std::min<int32_t>({(4096 / B) / a.M, 2048 / (B * C), a.n_bins}));
+    a.tiles = (a.n_bins + a.tile_bins - 1) / a.tile_bins;
+    const int32_t S = a.tile_bins * a.M;
+    a.sign_words = ((S + a.T + kRenderRun + 62) >> 6) + 2;
+    return (unsigned)(sizeof(double) * (size_t)(B * a.T + B * S + a.tile_bins * B * C + a.tile_bins * B + a.sign_words));
+}
+
+int render_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
+                   int32_t frac_bits, int32_t M, int32_t T, const void* d_taps, uint64_t seed, void* d_out, hipStream_t st)
+{
+    if (!s.module || !s.module->hist_render) {
+        set_error("hare_hist_render missing from code object");
+        return HARE_E_STATE;
+    }
+    RenderArgs a;
+    memset(&a, 0, sizeof a);
+    a.hist = (const unsigned long long*)d_hist;
+    a.weight = (const uint32_t*)d_weight;
+    a.taps = (const double*)d_taps;
+    a.out = (double*)d_out;
+    a.seed = seed;
+    a.n_bins = n_bins;
+    a.bands = B;
+    a.channels = channels;
+    a.frac_bits = frac_bits;
+    a.M = M;
+    a.T = T;
+    const unsigned lds = render_plan(a);
+    void* args[] = {&a};
+    return launch(H, s.module->hist_render, (unsigned)K * (unsigned)a.tiles, kRenderThreads, lds, st, args);      // K x n_bins <= 2^27 workgroups
+}
+
+}  // namespace
+
+}  // namespace hare
+
+using namespace hare;
+
+extern "C" {
+
+int hare_hist_reduce_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
+                            int32_t n_win, const int32_t* win, int32_t n_lev, const uint32_t* levels, void* d_sums, void* d_cross, void* stream)
+{
+    if (!s) return null_scene();
+    const ReduceSpec r = {nullptr, n_win, win, n_lev, levels};
+    ReduceBytes z;
+    if (int rc = reduce_check_spec("hare_hist_reduce_device", K, n_bins, B, channels, r)) return rc;
+    if (int rc = reduce_check_buffers("hare_hist_reduce_device", K, n_bins, B, channels, d_hist, d_weight, r, d_sums, d_cross, z)) return rc;
+    return device_call(*s, [&](const HipApi* H) {
+        return reduce_enqueue(*s, H, K, n_bins, B, channels, d_hist, d_weight, r, d_sums, d_cross, (hipStream_t)stream);
+    });
+}
+
+int hare_hist_reduce(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t* hist, const uint32_t* weight,
+                     int32_t n_win, const int32_t* win, int32_t n_lev, const uint32_t* levels, uint64_t* sums, int32_t* cross)
+{
+    if (!s) return null_scene();
+    const ReduceSpec r = {weight, n_win, win, n_lev, levels};
+    ReduceBytes z;
+    if (int rc = reduce_check_spec("hare_hist_reduce", K, n_bins, B, channels, r)) return rc;
+    if (int rc = reduce_check_buffers("hare_hist_reduce", K, n_bins, B, channels, hist, weight, r, sums, cross, z)) return rc;
+    return device_call(*s, [&](const HipApi* H) {
+        const StagePart parts[] = {{z.hist, hist, nullptr}, {z.sums, nullptr, sums}, {z.cross, nullptr, cross}, {weight ? z.weight : 0, weight, nullptr}};
+        return staged_run(H, parts, [&](void* const* d) { return reduce_enqueue(*s, H, K, n_bins, B, channels, d[0], d[3], r, d[1], d[2], nullptr); });
+    });
+}
+
+int hare_hist_project_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
+                             int32_t J, const void* d_coef, void* d_proj, void* stream)
+{
+    if (!s) return null_scene();
+    ProjectBytes z;
+    if (int rc = project_check("hare_hist_project_device", K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj, z)) return rc;
+    return device_call(*s, [&](const HipApi* H) {
+        return project_enqueue(*s, H, K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj, (hipStream_t)stream);
+    });
+}
+
+int hare_hist_project(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t* hist, const uint32_t* weight,
+                      int32_t J, const int32_t* coef, uint64_t* proj)
+{
+    if (!s) return null_scene();
+    ProjectBytes z;
+    if (int rc = project_check("hare_hist_project", K, n_bins, B, channels, hist, weight, J, coef, proj, z)) return rc;
+    return device_call(*s, [&](const HipApi* H) {
+        const StagePart parts[] = {{z.hist, hist, nullptr}, {z.proj, nullptr, proj}, {z.coef, coef, nullptr}, {weight ? z.weight : 0, weight, nullptr}};
+        return staged_run(H, parts, [&](void* const* d) { return project_enqueue(*s, H, K, n_bins, B, channels, d[0], d[3], J, d[2], d[1], nullptr); });
+    });
+}
+
+int hare_hist_render_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
+                            int32_t frac_bits, int32_t M, int32_t T, const void* d_taps, uint64_t seed, void* d_out, void* stream)
+{
+    if (!s) return null_scene();
+    RenderBytes z;
+    if (int rc = render_check("hare_hist_render_device", K, n_bins, B, channels, d_hist, d_weight, frac_bits, M, T, d_taps, d_out, z)) return rc;
+    return device_call(*s, [&](const HipApi* H) {
+        return render_enqueue(*s, H, K, n_bins, B, channels, d_hist, d_weight, frac_bits, M, T, d_taps, seed, d_out, (hipStream_t)stream);
+    });
+}
+
+int hare_hist_render(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t* hist, const uint32_t* weight,
+                     int32_t frac_bits, int32_t M, int32_t T, const double* taps, uint64_t seed, double* out)
+{
+    if (!s) return null_scene();
+    RenderBytes z;
+    if (int rc = render_check("hare_hist_render", K, n_bins, B, channels, hist, weight, frac_bits, M, T, taps, out, z)) return rc;
+    for (size_t x = 0; x < (size_t)B * (size_t)T; ++x)
+        if (!std::isfinite(taps[x])) {
+            set_error("hare_hist_render: taps[" + std::to_string(x) + "] is not finite");
+            return HARE_E_INVALID;
+        }
+    return device_call(*s, [&](const HipApi* H) {
+        const StagePart parts[] = {{z.out, nullptr, out}, {z.hist, hist, nullptr}, {z.taps, taps, nullptr}, {weight ? z.weight : 0, weight, nullptr}};
+        return staged_run(H, parts, [&](void* const* d) {
+            return render_enqueue(*s, H, K, n_bins, B, channels, d[1], d[3], frac_bits, M, T, d[2], seed, d[0], nullptr);
+        });
+    });
+}
+
+}  // extern "C"

@@ -1963,6 +1963,7 @@ __global__ __launch_bounds__(256) void hare_occlusion(const XEventRec* ev, const
 #include "direct.hip"          // hare_direct_emit / hare_direct_deposit[_dir]: the direct sound, a lane per receiver (hare_direct_device, HARE_RECEIVE_DIRECT)
 #include "image.hip"           // hare_image_mirror / _pairs / _deposit[_dir]: first-order image sources (hare_image_device, HARE_RECEIVE_IMAGE)
 #include "image2.hip"          // hare_image2_mirror / _cands / _paths / _deposit[_dir]: second-order image sources (hare_image2_device, HARE_RECEIVE_IMAGE2)
+#include "hist_block.h"        // U128, weighted, band_total, Block: what the three kernels on a histogram share; no kernel
 #include "reduce.hip"          // hare_hist_reduce: window sums and decay crossings of a receive histogram (hare_hist_reduce_device)
 #include "render.hip"          // hare_hist_render: a receive histogram rendered to impulse responses, shaped band noise (hare_hist_render_device)
 #include "project.hip"         // hare_hist_project: a receive histogram projected onto integer vectors over the bins (hare_hist_project_device)

@@ -541,6 +541,14 @@ bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
     return a && b && x < y + nb && y < x + na;
 }
 
+bool spans_overlap(std::initializer_list<Span> v, size_t n_out)
+{
+    for (const Span* x = v.begin(); x < v.begin() + n_out; ++x)
+        for (const Span* y = x + 1; y < v.end(); ++y)
+            if (ranges_overlap(x->p, x->bytes, y->p, y->bytes)) return true;
+    return false;
+}
+
 // The grid as the voxel kernels take it
 static void fill_voxel_args(const Scene& s, int32_t top, VoxelArgs& g)
 {

@@ -6,6 +6,7 @@
 
 #include "../../include/hare_hip.h"
 #include "scene.h"
+#include "fan_out.h"
 
 namespace hare {
 
@@ -114,5 +115,22 @@ struct ShootPlan {
 // `bounce_casts` casts (Kern::VoxelBounce) where the fused loop serves, else the plan of one cast.  Pure: no allocation, no lock, no device
 ShootPlan plan_shoot(const Scene& s, const DeviceModule* M, int32_t kind, size_t top, int64_t n, uint32_t flags, bool flags_only = false, int32_t bounce_casts = 0);
 int32_t voxel_block_bits_words(const Scene& s, size_t top);      // words of the "voxel_skip" block bits the pool kernel stages for this topology (0: none)
+
+// The device prelude of a C-ABI call behind its checks (receive.cpp, hist.cpp): no exception out, the HIP runtime bound (HARE_E_NODEVICE),
+// the scene's device current for the call and its module loaded; then body(H), whose code is the call's
+template <class Body>
+int device_call(Scene& s, Body body)
+{
+    GUARD_BEGIN
+    const HipApi* H = api_or_err();
+    if (!H) return HARE_E_NODEVICE;
+    DeviceGuard dev_guard(H, s.device);
+    if (!s.module) {
+        int rc = ensure_device(s, H);
+        if (rc) return rc;
+    }
+    return body(H);
+    GUARD_END
+}
 
 }  // namespace hare

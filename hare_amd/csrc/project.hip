@@ -1,12 +1,9 @@
 // project.hip -- hare_hist_project: a receive histogram projected, on the device, onto up to 32 caller-supplied integer vectors over the
 // bins (include/hare_hip.h, "receivers", "Projection"): per receiver k, band b and vector j the exact signed sum
-// P(k, b, j) = sum over i of c_j[i] * g(k, i, b) as a 128-bit two's-complement integer.  #included from kernels.hip behind reduce.hip, whose
-// 128-bit pieces (U128, add128, sub128, wave_scan) it uses.  Integer arithmetic only: the result is a function of the inputs, bit for bit
-// (tests/project_ref.py restates it in Python integers).
-//
-// The layout is pass 1 of hare_hist_reduce (reduce.hip): a workgroup of 256 threads owns a receiver, reads its block in tiles of
-// step = 256 / B bins, thread t < A = step * B taking word t of each tile -- consecutive lanes on consecutive 8-byte words, four loads in
-// flight -- and keeps ONE band, b = t % B, and the bin t / B of every tile.
+// P(k, b, j) = sum over i of c_j[i] * g(k, i, b) as a 128-bit two's-complement integer.  #included from kernels.hip behind hist_block.h,
+// whose 128-bit pieces, band totals and layout it shares with hare_hist_reduce: Block, a workgroup of 256 threads per receiver, a thread on
+// ONE band and one bin of every tile, and Block::g4, this kernel's loader: four tiles' words in flight, no branch.  Integer arithmetic
+// only: the result is a function of the inputs, bit for bit (tests/project_ref.py restates it in Python integers).
 //
 //   signs    c * g is signed 32 x unsigned 64.  The kernel multiplies by the OFFSET coefficient c' = c + 2^31 (one xor of the top bit), which
 //            is an unsigned 32-bit number: U_j = sum c'_j[i] * g is a sum of unsigned 96-bit products (U_j < 2^32 * 2^91), and with
@@ -29,7 +26,7 @@
 // blockIdx.x = k.  K = 1 with a huge n_bins runs on this one workgroup: a host-sized problem, and not what the kernel is for.
 namespace hare_project {
 
-using hare_reduce::U128;
+using namespace hare_hist;
 constexpr int kGroup = kProjectGroup;           // vectors per sweep, at most
 
 struct Acc {                                    // a 128-bit unsigned sum: bits 0 .. 31, 32 .. 63, 64 .. 127
@@ -46,40 +43,10 @@ __device__ __forceinline__ void mul_add(Acc& acc, unsigned long long x, uint32_t
     acc.a23 += p1 >> 32;
 }
 
-struct Block {                                  // what a thread knows of its receiver's block
-    const unsigned long long* h;
-    const uint32_t* weight;
-    size_t ch;
-    int nb, B, b, li, step, tiles;
-    bool on;
-    // g(k, i, b) of this thread's band for the bins i0 + q * step, q = 0 .. 3; 0 past the end and for an idle thread.  Without a branch per
-    // word: such a thread reads word 0 of the block, which exists, and drops it; the loads go out together, then the weights' products
-    __device__ __forceinline__ void g4(int i0, unsigned long long (&g)[4]) const
-    {
-        int e[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = i0 + q * step;
-            e[q] = on && i < nb ? i * B + b : -1;
-            g[q] = h[(size_t)max(e[q], 0) * ch];
-        }
-        if (weight) {
-            unsigned long long w[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) w[q] = weight[max(e[q], 0)];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) g[q] = (g[q] >> 32) * w[q] + (((g[q] & 0xFFFFFFFFull) * w[q]) >> 32);      // floor(h * w / 2^32)
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g[q] = e[q] >= 0 ? g[q] : 0ull;
-    }
-};
-
 // One sweep over the block for the N vectors at c0 (vector-major, n_bins apart): the thread's sums U_u of c'_u[i] * g into s_tot[1 + u],
 // and with WANT_T its sum of g into s_tot[0]; per wave and band
 template <int N> __device__ __forceinline__ void sweep(const Block& k, const int32_t* c0, bool want_T, U128 (*s_tot)[4][kMaxBands], int lane, int wv)
 {
-    using namespace hare_reduce;
     Acc U[N];
 #pragma unroll
     for (int u = 0; u < N; ++u) U[u].a0 = U[u].a1 = 0, U[u].a23 = 0;
@@ -119,24 +86,13 @@ template <int N> __device__ __forceinline__ void sweep(const Block& k, const int
 
 extern "C" __global__ __launch_bounds__(256) void hare_hist_project(ProjectArgs a)
 {
-    using namespace hare_reduce;
     using namespace hare_project;
     __shared__ U128 s_tot[1 + kGroup][4][kMaxBands];   // T, then U per vector of the sweep; per wave and band: the wave's total
     __shared__ U128 s_T[kMaxBands];                     // 2^31 * T per band, from the first sweep on
 
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const int J = a.n_vec;
-    Block k;
-    k.nb = a.n_bins;
-    k.B = a.bands;
-    k.step = 256 / k.B;
-    k.b = t % k.B;
-    k.li = t / k.B;
-    k.on = t < k.step * k.B;
-    k.tiles = (k.nb + k.step - 1) / k.step;
-    k.ch = (size_t)a.channels;
-    k.h = a.hist + (size_t)blockIdx.x * (size_t)k.nb * (size_t)k.B * k.ch;
-    k.weight = a.weight;
+    const Block k = block_of(a.hist, a.weight, a.n_bins, a.bands, a.channels);
     const int b = k.b, li = k.li;
 
     for (int j0 = 0; j0 < J; j0 += kGroup) {
@@ -155,11 +111,13 @@ extern "C" __global__ __launch_bounds__(256) void hare_hist_project(ProjectArgs 
         }
         __syncthreads();
         if (want_T && t < k.B) {
-            const U128 s = add128(add128(s_tot[0][0][t], s_tot[0][1][t]), add128(s_tot[0][2][t], s_tot[0][3][t]));
+            const U128 s = band_total(s_tot[0], t);
             s_T[t] = make128(s.lo << 31, (s.hi << 31) | (s.lo >> 33));        // T < 2^91: nothing is shifted out
         }
         __syncthreads();
         if (t < kGroup * k.B && li < n_act) {                                  // thread (u, b) = (li, b): vector j0 + u of band b
+            // band_total, written out: through the helper the compiler orders this tail's LDS reads and adds differently, and the
+            // kernel's instruction stream is kept as it was measured
             const U128 s = add128(add128(s_tot[1 + li][0][b], s_tot[1 + li][1][b]), add128(s_tot[1 + li][2][b], s_tot[1 + li][3][b]));
             const U128 p = sub128(s, s_T[b]);                                  // mod 2^128: the two's complement of a negative sum
             unsigned long long* out = a.proj + (((size_t)blockIdx.x * (size_t)k.B + (size_t)b) * (size_t)J + (size_t)(j0 + li)) * 2;

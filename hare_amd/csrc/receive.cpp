@@ -5,7 +5,8 @@
 // hare_image_device; the kernels: image.hip) and second-order ones (image2_enqueue, hare_image2_device; the kernels: image2.hip).  The three
 // plans fill what their kernels share through deposit_fill and image_scene_fill, and the three calls check and prepare through
 // deposit_call_check, deposit_buffers_check and deposit_call_run.  The host-buffer calls hare_receive_batch / _sharded and
-// hare_receive_source / _sharded are in bounce.cpp, beside the loop they share with hare_bounce_batch.
+// hare_receive_source / _sharded are in bounce.cpp, beside the loop they share with hare_bounce_batch; what post-processes a histogram
+// (hare_hist_reduce, _project, _render) is in hist.cpp.
 //
 // Harness-defined: the reference has no receivers (Pachyderm, its caller, detects them on the host per ray).
 // Product code; nothing from oracle/.
@@ -527,188 +528,6 @@ int image2_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t
     return launch(H, m->image2_deposit[dir], (unsigned)((M + 255) / 256), 256, 0, st, args);
 }
 
-// ---- the reduction of a histogram (include/hare_hip.h, "receivers", "Reduction"; the kernel: reduce.hip)
-// what the reduction and the rendering check of a histogram's shape
-static int hist_check_shape(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels)
-{
-    auto bad = [&](const std::string& what) {
-        set_error(std::string(who) + ": " + what);
-        return HARE_E_INVALID;
-    };
-    if (K < 1 || K > kMaxMapReceivers) return bad("K out of range (1 .. 65 536)");
-    if (n_bins < 1) return bad("n_bins must be >= 1");
-    if (B < 1 || B > kMaxBands) return bad("bands out of range (1 .. 8)");
-    if (channels != 1 && channels != 4 && channels != 9 && channels != 16) return bad("channels must be 1, 4, 9 or 16");
-    if ((unsigned __int128)K * (unsigned)n_bins * (unsigned)B * (unsigned)channels > ((size_t)1 << 27)) return bad("K x n_bins x bands x channels exceeds 2^27");
-    return HARE_OK;
-}
-
-int reduce_check_spec(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const ReduceSpec& r)
-{
-    auto bad = [&](const std::string& what) {
-        set_error(std::string(who) + ": " + what);
-        return HARE_E_INVALID;
-    };
-    if (int rc = hist_check_shape(who, K, n_bins, B, channels)) return rc;
-    if (r.n_win < 0 || r.n_win > kMaxReduceWindows) return bad("n_win out of range (0 .. 16)");
-    if (r.n_lev < 0 || r.n_lev > kMaxReduceLevels) return bad("n_lev out of range (0 .. 32)");
-    if (r.n_win + r.n_lev < 1) return bad("nothing to compute: n_win and n_lev are both 0");
-    if ((r.n_win > 0 && !r.win) || (r.n_lev > 0 && !r.levels)) return bad("null win / levels");
-    for (int32_t j = 0; j < r.n_win; ++j)
-        if (r.win[2 * j] < 0 || r.win[2 * j] > r.win[2 * j + 1] || r.win[2 * j + 1] > n_bins)
-            return bad("window " + std::to_string(j) + " is not 0 <= lo <= hi <= n_bins");
-    return HARE_OK;
-}
-
-int reduce_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist,
-                   const void* d_weight, const ReduceSpec& r, void* d_sums, void* d_cross, hipStream_t st)
-{
-    if (!s.module || !s.module->hist_reduce) {
-        set_error("hare_hist_reduce missing from code object");
-        return HARE_E_STATE;
-    }
-    ReduceArgs a;
-    memset(&a, 0, sizeof a);
-    a.hist = (const unsigned long long*)d_hist;
-    a.weight = (const uint32_t*)d_weight;
-    a.sums = (unsigned long long*)d_sums;
-    a.cross = (int32_t*)d_cross;
-    a.n_bins = n_bins;
-    a.bands = B;
-    a.channels = channels;
-    a.n_win = r.n_win;
-    a.n_lev = r.n_lev;
-    for (int32_t j = 0; j < 2 * r.n_win; ++j) a.win[j] = r.win[j];
-    for (int32_t l = 0; l < r.n_lev; ++l) a.levels[l] = r.levels[l];
-    void* args[] = {&a};
-    return launch(H, s.module->hist_reduce, (unsigned)K, 256, 0, st, args);          // a workgroup per receiver
-}
-
-// what hare_hist_reduce_device and hare_hist_reduce check of their buffers, device or host: none null that is used, no output on another buffer
-static int reduce_check_buffers(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const void* hist, const void* weight,
-                                const ReduceSpec& r, const void* sums, const void* cross)
-{
-    if (!hist || (r.n_win > 0 && !sums) || (r.n_lev > 0 && !cross)) {
-        set_error(std::string(who) + ": null histogram / sums / crossings");
-        return HARE_E_INVALID;
-    }
-    const size_t KB = (size_t)K * (size_t)B;
-    const struct { const void* p; size_t bytes; } bufs[] = {{sums, KB * (size_t)r.n_win * 4 * sizeof(uint64_t)},
-                                                            {cross, KB * (size_t)r.n_lev * sizeof(int32_t)},
-                                                            {hist, KB * (size_t)n_bins * (size_t)channels * sizeof(uint64_t)},
-                                                            {weight, (size_t)n_bins * (size_t)B * sizeof(uint32_t)}};
-    for (size_t x = 0; x < 2; ++x)
-        for (size_t y = x + 1; y < 4; ++y)
-            if (ranges_overlap(bufs[x].p, bufs[x].bytes, bufs[y].p, bufs[y].bytes)) {
-                set_error(std::string(who) + ": sums and crossings must not overlap each other, the histogram or the weights");
-                return HARE_E_INVALID;
-            }
-    return HARE_OK;
-}
-
-// ---- the projection of a histogram (include/hare_hip.h, "receivers", "Projection"; the kernel: project.hip)
-// everything hare_hist_project_device and hare_hist_project check before anything runs, in the header's order; buffers device or host
-static int project_check(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const void* hist, const void* weight, int32_t J,
-                         const void* coef, const void* proj)
-{
-    auto bad = [&](const std::string& what) {
-        set_error(std::string(who) + ": " + what);
-        return HARE_E_INVALID;
-    };
-    if (int rc = hist_check_shape(who, K, n_bins, B, channels)) return rc;
-    if (J < 1 || J > kMaxProjectVectors) return bad("J out of range (1 .. 32)");
-    if (!hist || !coef || !proj) return bad("null histogram / coefficients / output");
-    const size_t proj_bytes = (size_t)K * (size_t)B * (size_t)J * 2 * sizeof(uint64_t);
-    const struct { const void* p; size_t bytes; } in[] = {{hist, (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels * sizeof(uint64_t)},
-                                                          {weight, (size_t)n_bins * (size_t)B * sizeof(uint32_t)},
-                                                          {coef, (size_t)J * (size_t)n_bins * sizeof(int32_t)}};
-    for (const auto& b : in)
-        if (ranges_overlap(proj, proj_bytes, b.p, b.bytes)) return bad("the output must not overlap the histogram, the weights or the coefficients");
-    return HARE_OK;
-}
-
-static int project_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist,
-                           const void* d_weight, int32_t J, const void* d_coef, void* d_proj, hipStream_t st)
-{
-    if (!s.module || !s.module->hist_project) {
-        set_error("hare_hist_project missing from code object");
-        return HARE_E_STATE;
-    }
-    ProjectArgs a;
-    memset(&a, 0, sizeof a);
-    a.hist = (const unsigned long long*)d_hist;
-    a.weight = (const uint32_t*)d_weight;
-    a.coef = (const int32_t*)d_coef;
-    a.proj = (unsigned long long*)d_proj;
-    a.n_bins = n_bins;
-    a.bands = B;
-    a.channels = channels;
-    a.n_vec = J;
-    void* args[] = {&a};
-    return launch(H, s.module->hist_project, (unsigned)K, 256, 0, st, args);         // a workgroup per receiver
-}
-
-// ---- the rendering of a histogram (include/hare_hip.h, "receivers", "Rendering"; the kernel: render.hip)
-// everything hare_hist_render_device and hare_hist_render check before anything runs, in the header's order; buffers device or host
-static int render_check(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const void* hist, const void* weight,
-                        int32_t frac_bits, int32_t M, int32_t T, const void* taps, const void* out)
-{
-    auto bad = [&](const std::string& what) {
-        set_error(std::string(who) + ": " + what);
-        return HARE_E_INVALID;
-    };
-    if (int rc = hist_check_shape(who, K, n_bins, B, channels)) return rc;
-    if (M < 1 || M > kMaxRenderBin) return bad("M out of range (1 .. 1024)");
-    if (T < 1 || T > kMaxRenderTaps) return bad("T out of range (1 .. 1024)");
-    if (frac_bits < 0 || frac_bits > 62) return bad("frac_bits out of range (0 .. 62)");
-    if ((unsigned __int128)K * (unsigned)channels * (unsigned)n_bins * (unsigned)M > ((size_t)1 << 28)) return bad("K x channels x n_bins x M exceeds 2^28");
-    if (!hist || !taps || !out) return bad("null histogram / taps / output");
-    const size_t out_bytes = (size_t)K * (size_t)channels * (size_t)n_bins * (size_t)M * sizeof(double);
-    const struct { const void* p; size_t bytes; } in[] = {{hist, (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels * sizeof(uint64_t)},
-                                                          {weight, (size_t)n_bins * (size_t)B * sizeof(uint32_t)},
-                                                          {taps, (size_t)B * (size_t)T * sizeof(double)}};
-    for (const auto& b : in)
-        if (ranges_overlap(out, out_bytes, b.p, b.bytes)) return bad("the output must not overlap the histogram, the weights or the taps");
-    return HARE_OK;
-}
-
-// The tile of hare_hist_render (render.hip): whole bins, as many as keep the B x S filtered samples near 32 KiB and the gains within
-// 16 KiB -- one bin where a bin alone is more.  LDS: taps, samples, gains, a, sign mask: at most 8 * (8192 + 8192 + 2048 + 256 + 35) bytes
-static unsigned render_plan(RenderArgs& a)
-{
-    const int32_t B = a.bands, C = a.channels;
-    a.tile_bins = std::max<int32_t>(1, std::min<int32_t>({(4096 / B) / a.M, 2048 / (B * C), a.n_bins}));
-    a.tiles = (a.n_bins + a.tile_bins - 1) / a.tile_bins;
-    const int32_t S = a.tile_bins * a.M;
-    a.sign_words = ((S + a.T + kRenderRun + 62) >> 6) + 2;
-    return (unsigned)(sizeof(double) * (size_t)(B * a.T + B * S + a.tile_bins * B * C + a.tile_bins * B + a.sign_words));
-}
-
-static int render_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist,
-                          const void* d_weight, int32_t frac_bits, int32_t M, int32_t T, const void* d_taps, uint64_t seed, void* d_out, hipStream_t st)
-{
-    if (!s.module || !s.module->hist_render) {
-        set_error("hare_hist_render missing from code object");
-        return HARE_E_STATE;
-    }
-    RenderArgs a;
-    memset(&a, 0, sizeof a);
-    a.hist = (const unsigned long long*)d_hist;
-    a.weight = (const uint32_t*)d_weight;
-    a.taps = (const double*)d_taps;
-    a.out = (double*)d_out;
-    a.seed = seed;
-    a.n_bins = n_bins;
-    a.bands = B;
-    a.channels = channels;
-    a.frac_bits = frac_bits;
-    a.M = M;
-    a.T = T;
-    const unsigned lds = render_plan(a);
-    void* args[] = {&a};
-    return launch(H, s.module->hist_render, (unsigned)K * (unsigned)a.tiles, kRenderThreads, lds, st, args);      // K x n_bins <= 2^27 workgroups
-}
-
 // hare_scene_set_absorption / _scattering behind their own checks of top_index and B: P x B coefficients in [0, 1] become Model[top]'s
 // table `mine` (`name` in the messages), with the B of the topology's other table where it has one
 static int set_band_table(Scene& s, const char* who, const char* name, std::vector<Scene::BandTable>& mine, const std::vector<Scene::BandTable>& other,
@@ -872,15 +691,10 @@ static int deposit_buffers_check(const char* who, const Scene& s, int32_t top, u
         return HARE_E_INVALID;
     }
     const size_t K = std::max<size_t>(1, s.rcv.size() / 4);
-    const struct { const void* p; size_t bytes; } bufs[] = {{d_work, work_bytes},
-                                                            {d_hist, receive_hist_words(s, top, n_bins, flags, 1) * sizeof(uint64_t)},
-                                                            {d_det, K * 2 * sizeof(uint64_t)}};
-    for (size_t x = 0; x < 3; ++x)
-        for (size_t y = x + 1; y < 3; ++y)
-            if (ranges_overlap(bufs[x].p, bufs[x].bytes, bufs[y].p, bufs[y].bytes)) {
-                set_error(std::string(who) + ": work array, histogram and detections must not overlap");
-                return HARE_E_INVALID;
-            }
+    if (spans_overlap({{d_work, work_bytes}, {d_hist, receive_hist_words(s, top, n_bins, flags, 1) * sizeof(uint64_t)}, {d_det, K * 2 * sizeof(uint64_t)}}, 3)) {
+        set_error(std::string(who) + ": work array, histogram and detections must not overlap");
+        return HARE_E_INVALID;
+    }
     return HARE_OK;
 }
 
@@ -888,19 +702,12 @@ static int deposit_buffers_check(const char* who, const Scene& s, int32_t top, u
 template <class Enqueue>
 static int deposit_call_run(Scene& s, const char* who, Enqueue enqueue)
 {
-    GUARD_BEGIN
-    const HipApi* H = api_or_err();
-    if (!H) return HARE_E_NODEVICE;
-    DeviceGuard dev_guard(H, s.device);
-    if (!s.module) {
-        int rc = ensure_device(s, H);
-        if (rc) return rc;
-    }
-    if (int rc = source_ready(s, H, who)) return rc;
-    if (int rc = upload_polys(s, H)) return rc;
-    if (int rc = receive_ready(s, H, who)) return rc;
-    return enqueue(H);
-    GUARD_END
+    return device_call(s, [&](const HipApi* H) -> int {
+        if (int rc = source_ready(s, H, who)) return rc;
+        if (int rc = upload_polys(s, H)) return rc;
+        if (int rc = receive_ready(s, H, who)) return rc;
+        return enqueue(H);
+    });
 }
 
 extern "C" {
@@ -1084,17 +891,10 @@ int hare_emit_device(hare_scene* s, int64_t n, int64_t first_ray, void* d_rays, 
             return HARE_E_INVALID;
         }
     }
-    GUARD_BEGIN
-    const HipApi* H = api_or_err();
-    if (!H) return HARE_E_NODEVICE;
-    DeviceGuard dev_guard(H, s->device);
-    if (!s->module) {
-        int rc = ensure_device(*s, H);
-        if (rc) return rc;
-    }
-    if (int rc = source_ready(*s, H, "hare_emit_device")) return rc;
-    return emit_source(*s, H, n, first_ray, d_rays, d_state, (hipStream_t)stream);
-    GUARD_END
+    return device_call(*s, [&](const HipApi* H) -> int {
+        if (int rc = source_ready(*s, H, "hare_emit_device")) return rc;
+        return emit_source(*s, H, n, first_ray, d_rays, d_state, (hipStream_t)stream);
+    });
 }
 
 int hare_direct_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
@@ -1144,211 +944,6 @@ int hare_image2_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n
     });
 }
 
-int hare_hist_reduce_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
-                            int32_t n_win, const int32_t* win, int32_t n_lev, const uint32_t* levels, void* d_sums, void* d_cross, void* stream)
-{
-    if (!s) {
-        set_error("null scene");
-        return HARE_E_INVALID;
-    }
-    ReduceSpec r;
-    r.n_win = n_win;
-    r.win = win;
-    r.n_lev = n_lev;
-    r.levels = levels;
-    if (int rc = reduce_check_spec("hare_hist_reduce_device", K, n_bins, B, channels, r)) return rc;
-    if (int rc = reduce_check_buffers("hare_hist_reduce_device", K, n_bins, B, channels, d_hist, d_weight, r, d_sums, d_cross)) return rc;
-    GUARD_BEGIN
-    const HipApi* H = api_or_err();
-    if (!H) return HARE_E_NODEVICE;
-    DeviceGuard dev_guard(H, s->device);
-    if (!s->module) {
-        int rc = ensure_device(*s, H);
-        if (rc) return rc;
-    }
-    return reduce_enqueue(*s, H, K, n_bins, B, channels, d_hist, d_weight, r, d_sums, d_cross, (hipStream_t)stream);
-    GUARD_END
-}
-
-int hare_hist_reduce(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t* hist, const uint32_t* weight,
-                     int32_t n_win, const int32_t* win, int32_t n_lev, const uint32_t* levels, uint64_t* sums, int32_t* cross)
-{
-    if (!s) {
-        set_error("null scene");
-        return HARE_E_INVALID;
-    }
-    ReduceSpec r;
-    r.weight = weight;
-    r.n_win = n_win;
-    r.win = win;
-    r.n_lev = n_lev;
-    r.levels = levels;
-    if (int rc = reduce_check_spec("hare_hist_reduce", K, n_bins, B, channels, r)) return rc;
-    if (int rc = reduce_check_buffers("hare_hist_reduce", K, n_bins, B, channels, hist, weight, r, sums, cross)) return rc;
-    GUARD_BEGIN
-    const HipApi* H = api_or_err();
-    if (!H) return HARE_E_NODEVICE;
-    DeviceGuard dev_guard(H, s->device);
-    if (!s->module) {
-        int rc = ensure_device(*s, H);
-        if (rc) return rc;
-    }
-    // one device block: histogram, sums, crossings, weights (each from a 16-byte boundary); up, reduce, down, one synchronisation
-    const size_t KB = (size_t)K * (size_t)B;
-    const size_t hist_bytes = KB * (size_t)n_bins * (size_t)channels * sizeof(uint64_t), sums_bytes = KB * (size_t)n_win * 4 * sizeof(uint64_t);
-    const size_t cross_bytes = (KB * (size_t)n_lev * sizeof(int32_t) + 15) & ~(size_t)15, weight_bytes = (size_t)n_bins * (size_t)B * sizeof(uint32_t);
-    void* block = nullptr;
-    HIP_TRY(H->Malloc(&block, hist_bytes + sums_bytes + cross_bytes + weight_bytes + 16));
-    char* const d_hist = (char*)block;
-    char* const d_sums = d_hist + hist_bytes;
-    char* const d_cross = d_sums + sums_bytes;
-    char* const d_weight = d_cross + cross_bytes;
-    auto run = [&]() -> int {
-        HIP_TRY(H->MemcpyAsync(d_hist, hist, hist_bytes, hipMemcpyHostToDevice, nullptr));
-        if (weight) HIP_TRY(H->MemcpyAsync(d_weight, weight, weight_bytes, hipMemcpyHostToDevice, nullptr));
-        if (int rc = reduce_enqueue(*s, H, K, n_bins, B, channels, d_hist, weight ? d_weight : nullptr, r, d_sums, d_cross, nullptr)) return rc;
-        if (n_win > 0) HIP_TRY(H->MemcpyAsync(sums, d_sums, sums_bytes, hipMemcpyDeviceToHost, nullptr));
-        if (n_lev > 0) HIP_TRY(H->MemcpyAsync(cross, d_cross, KB * (size_t)n_lev * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(H->StreamSynchronize(nullptr));
-        return HARE_OK;
-    };
-    const int rc = run();
-    if (rc != HARE_OK) (void)H->StreamSynchronize(nullptr);      // copies may still be in flight
-    dev_free(H, block);
-    return rc;
-    GUARD_END
-}
-
-int hare_hist_project_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
-                             int32_t J, const void* d_coef, void* d_proj, void* stream)
-{
-    if (!s) {
-        set_error("null scene");
-        return HARE_E_INVALID;
-    }
-    if (int rc = project_check("hare_hist_project_device", K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj)) return rc;
-    GUARD_BEGIN
-    const HipApi* H = api_or_err();
-    if (!H) return HARE_E_NODEVICE;
-    DeviceGuard dev_guard(H, s->device);
-    if (!s->module) {
-        int rc = ensure_device(*s, H);
-        if (rc) return rc;
-    }
-    return project_enqueue(*s, H, K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj, (hipStream_t)stream);
-    GUARD_END
-}
-
-int hare_hist_project(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t* hist, const uint32_t* weight,
-                      int32_t J, const int32_t* coef, uint64_t* proj)
-{
-    if (!s) {
-        set_error("null scene");
-        return HARE_E_INVALID;
-    }
-    if (int rc = project_check("hare_hist_project", K, n_bins, B, channels, hist, weight, J, coef, proj)) return rc;
-    GUARD_BEGIN
-    const HipApi* H = api_or_err();
-    if (!H) return HARE_E_NODEVICE;
-    DeviceGuard dev_guard(H, s->device);
-    if (!s->module) {
-        int rc = ensure_device(*s, H);
-        if (rc) return rc;
-    }
-    // one device block: histogram, output, coefficients, weights (the first two whole 8-byte words, then 4-byte words); up, project, down, one synchronisation
-    const size_t hist_bytes = (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels * sizeof(uint64_t);
-    const size_t proj_bytes = (size_t)K * (size_t)B * (size_t)J * 2 * sizeof(uint64_t);
-    const size_t coef_bytes = (size_t)J * (size_t)n_bins * sizeof(int32_t), weight_bytes = (size_t)n_bins * (size_t)B * sizeof(uint32_t);
-    void* block = nullptr;
-    HIP_TRY(H->Malloc(&block, hist_bytes + proj_bytes + coef_bytes + weight_bytes));
-    char* const d_hist = (char*)block;
-    char* const d_proj = d_hist + hist_bytes;
-    char* const d_coef = d_proj + proj_bytes;
-    char* const d_weight = d_coef + coef_bytes;
-    auto run = [&]() -> int {
-        HIP_TRY(H->MemcpyAsync(d_hist, hist, hist_bytes, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(H->MemcpyAsync(d_coef, coef, coef_bytes, hipMemcpyHostToDevice, nullptr));
-        if (weight) HIP_TRY(H->MemcpyAsync(d_weight, weight, weight_bytes, hipMemcpyHostToDevice, nullptr));
-        if (int rc = project_enqueue(*s, H, K, n_bins, B, channels, d_hist, weight ? d_weight : nullptr, J, d_coef, d_proj, nullptr)) return rc;
-        HIP_TRY(H->MemcpyAsync(proj, d_proj, proj_bytes, hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(H->StreamSynchronize(nullptr));
-        return HARE_OK;
-    };
-    const int rc = run();
-    if (rc != HARE_OK) (void)H->StreamSynchronize(nullptr);      // copies may still be in flight
-    dev_free(H, block);
-    return rc;
-    GUARD_END
-}
-
-int hare_hist_render_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
-                            int32_t frac_bits, int32_t M, int32_t T, const void* d_taps, uint64_t seed, void* d_out, void* stream)
-{
-    if (!s) {
-        set_error("null scene");
-        return HARE_E_INVALID;
-    }
-    if (int rc = render_check("hare_hist_render_device", K, n_bins, B, channels, d_hist, d_weight, frac_bits, M, T, d_taps, d_out)) return rc;
-    GUARD_BEGIN
-    const HipApi* H = api_or_err();
-    if (!H) return HARE_E_NODEVICE;
-    DeviceGuard dev_guard(H, s->device);
-    if (!s->module) {
-        int rc = ensure_device(*s, H);
-        if (rc) return rc;
-    }
-    return render_enqueue(*s, H, K, n_bins, B, channels, d_hist, d_weight, frac_bits, M, T, d_taps, seed, d_out, (hipStream_t)stream);
-    GUARD_END
-}
-
-int hare_hist_render(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t* hist, const uint32_t* weight,
-                     int32_t frac_bits, int32_t M, int32_t T, const double* taps, uint64_t seed, double* out)
-{
-    if (!s) {
-        set_error("null scene");
-        return HARE_E_INVALID;
-    }
-    if (int rc = render_check("hare_hist_render", K, n_bins, B, channels, hist, weight, frac_bits, M, T, taps, out)) return rc;
-    for (size_t x = 0; x < (size_t)B * (size_t)T; ++x)
-        if (!std::isfinite(taps[x])) {
-            set_error("hare_hist_render: taps[" + std::to_string(x) + "] is not finite");
-            return HARE_E_INVALID;
-        }
-    GUARD_BEGIN
-    const HipApi* H = api_or_err();
-    if (!H) return HARE_E_NODEVICE;
-    DeviceGuard dev_guard(H, s->device);
-    if (!s->module) {
-        int rc = ensure_device(*s, H);
-        if (rc) return rc;
-    }
-    // one device block: output, histogram, taps, weights (sizes of whole 8-byte words: each stays aligned); up, render, down, one synchronisation
-    const size_t hist_bytes = (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels * sizeof(uint64_t);
-    const size_t out_bytes = (size_t)K * (size_t)channels * (size_t)n_bins * (size_t)M * sizeof(double);
-    const size_t taps_bytes = (size_t)B * (size_t)T * sizeof(double), weight_bytes = (size_t)n_bins * (size_t)B * sizeof(uint32_t);
-    void* block = nullptr;
-    HIP_TRY(H->Malloc(&block, out_bytes + hist_bytes + taps_bytes + weight_bytes + 16));
-    char* const d_out = (char*)block;
-    char* const d_hist = d_out + out_bytes;
-    char* const d_taps = d_hist + hist_bytes;
-    char* const d_weight = d_taps + taps_bytes;
-    auto run = [&]() -> int {
-        HIP_TRY(H->MemcpyAsync(d_hist, hist, hist_bytes, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(H->MemcpyAsync(d_taps, taps, taps_bytes, hipMemcpyHostToDevice, nullptr));
-        if (weight) HIP_TRY(H->MemcpyAsync(d_weight, weight, weight_bytes, hipMemcpyHostToDevice, nullptr));
-        if (int rc = render_enqueue(*s, H, K, n_bins, B, channels, d_hist, weight ? d_weight : nullptr, frac_bits, M, T, d_taps, seed, d_out, nullptr))
-            return rc;
-        HIP_TRY(H->MemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(H->StreamSynchronize(nullptr));
-        return HARE_OK;
-    };
-    const int rc = run();
-    if (rc != HARE_OK) (void)H->StreamSynchronize(nullptr);      // copies may still be in flight
-    dev_free(H, block);
-    return rc;
-    GUARD_END
-}
-
 int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n, void* d_rays, const void* d_excl1, const void* d_excl2,
                         int32_t bounces, uint32_t flags, int32_t n_bins, double bin_len, int32_t frac_bits, void* d_state, void* d_work,
                         void* d_events_last, void* d_hist, void* d_detections, void* d_counters, void* stream)
@@ -1389,25 +984,18 @@ int hare_receive_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t 
                     return HARE_E_INVALID;
                 }
     }
-    GUARD_BEGIN
-    const HipApi* H = api_or_err();
-    if (!H) return HARE_E_NODEVICE;
-    DeviceGuard dev_guard(H, s->device);
-    if (!s->module) {
-        int rc = ensure_device(*s, H);
-        if (rc) return rc;
-    }
-    if (int rc = upload_polys(*s, H)) return rc;
-    if (int rc = receive_ready(*s, H, "hare_receive_device")) return rc;
-    if (flags & (HARE_RECEIVE_DIRECT | HARE_RECEIVE_IMAGE))      // suppression only, but of the SOURCE's paths: hare_direct_device / hare_image_device deposit them
-        if (int rc = source_ready(*s, H, "hare_receive_device")) return rc;
-    if (n == 0) return HARE_OK;
-    ReceivePlan plan;
-    if (int rc = receive_plan(*s, top_index, flags, n, n_bins, bin_len, frac_bits, d_state, d_hist, d_detections, d_work, false, 0, plan)) return rc;
-    flags &= HARE_SHOOT_COUNT_WORK | HARE_SHOOT_SIMPLE_KERNEL;
-    return bounce_device_impl(*s, H, kind, top_index, n, d_rays, d_excl1, d_excl2, bounces, flags, d_work, nullptr, d_events_last, d_counters,
-                              nullptr, (hipStream_t)stream, &plan);
-    GUARD_END
+    return device_call(*s, [&](const HipApi* H) -> int {
+        if (int rc = upload_polys(*s, H)) return rc;
+        if (int rc = receive_ready(*s, H, "hare_receive_device")) return rc;
+        if (flags & (HARE_RECEIVE_DIRECT | HARE_RECEIVE_IMAGE))      // suppression only, but of the SOURCE's paths: hare_direct_device / hare_image_device deposit them
+            if (int rc = source_ready(*s, H, "hare_receive_device")) return rc;
+        if (n == 0) return HARE_OK;
+        ReceivePlan plan;
+        if (int rc = receive_plan(*s, top_index, flags, n, n_bins, bin_len, frac_bits, d_state, d_hist, d_detections, d_work, false, 0, plan)) return rc;
+        flags &= HARE_SHOOT_COUNT_WORK | HARE_SHOOT_SIMPLE_KERNEL;
+        return bounce_device_impl(*s, H, kind, top_index, n, d_rays, d_excl1, d_excl2, bounces, flags, d_work, nullptr, d_events_last, d_counters,
+                                  nullptr, (hipStream_t)stream, &plan);
+    });
 }
 
 }  // extern "C"

@@ -1,12 +1,10 @@
 // reduce.hip -- hare_hist_reduce: a receive histogram reduced, on the device, to what a receiver map's user reads from it (include/hare_hip.h,
 // "receivers", "Reduction"): per receiver and band the sums S0 = sum g and S1 = sum i * g over up to 16 bin windows, and the bins at which the
-// backward-integrated decay R(i) crosses up to 32 levels.  #included from kernels.hip.  Integer arithmetic only, 128 bits from 64-bit
-// pieces: the result is a function of the inputs, bit for bit (tests/reduce_ref.py restates it in Python integers).
-//
-// A workgroup of 256 threads owns a receiver: its n_bins x B (x channels) words are contiguous.  The block is read in TILES of
-// step = 256 / B bins = A = step * B words, thread t < A taking word t of each tile: consecutive lanes read consecutive words (8 B each; with
-// four channels every fourth word, the W channel -- the line is fetched either way), and a thread keeps ONE band, b = t % B, and the bin
-// t / B of every tile.  (256 - A <= 4 threads idle for B = 3, 5, 6, 7.)
+// backward-integrated decay R(i) crosses up to 32 levels.  #included from kernels.hip behind hist_block.h, which holds what this kernel
+// shares with hare_hist_project and hare_hist_render: the 128-bit pieces (U128, add128, ..., wave_scan), the weighting (weighted), a band's
+// total over the four waves (band_total) and the layout -- Block: a workgroup of 256 threads owns a receiver and reads its block in tiles of
+// step = 256 / B bins, a thread keeping ONE band, b = t % B, and the bin li = t / B of every tile.  Integer arithmetic only: the result is a
+// function of the inputs, bit for bit (tests/reduce_ref.py restates it in Python integers).
 //
 //   pass 1   T and the window sums.  A thread adds its words into T, S0[u], S1[u] (128 bits each) for four windows at a time -- a sweep
 //            over the block per four windows: one for the usual n_win <= 4, later sweeps read the 64 KiB or so from L2 -- four loads in
@@ -26,53 +24,6 @@
 // K = 1 with a huge n_bins runs on this one workgroup: a host-sized problem, and not what the kernel is for.
 namespace hare_reduce {
 
-struct U128 {
-    unsigned long long lo, hi;
-};
-__device__ __forceinline__ U128 make128(unsigned long long lo, unsigned long long hi = 0)
-{
-    U128 r;
-    r.lo = lo;
-    r.hi = hi;
-    return r;
-}
-__device__ __forceinline__ U128 add128(U128 a, U128 b)          // add with carry
-{
-    U128 r;
-    r.lo = a.lo + b.lo;
-    r.hi = a.hi + b.hi + (r.lo < a.lo ? 1ull : 0ull);
-    return r;
-}
-__device__ __forceinline__ U128 sub128(U128 a, U128 b)          // a >= b
-{
-    U128 r;
-    r.lo = a.lo - b.lo;
-    r.hi = a.hi - b.hi - (a.lo < b.lo ? 1ull : 0ull);
-    return r;
-}
-__device__ __forceinline__ bool lt128(U128 a, U128 b)
-{
-    return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo);
-}
-// x * m, 96 bits, from two 32 x 32 -> 64 multiply-adds
-__device__ __forceinline__ U128 mul_64x32(unsigned long long x, uint32_t m)
-{
-    const unsigned long long p0 = (x & 0xFFFFFFFFull) * m;
-    const unsigned long long p1 = (x >> 32) * m + (p0 >> 32);
-    return make128((p0 & 0xFFFFFFFFull) | (p1 << 32), p1 >> 32);
-}
-// Inclusive scan over the lanes of a wave that share a band: lane L receives the sum of lanes L, L - B, L - 2 B, ...
-__device__ __forceinline__ U128 wave_scan(U128 v, int B, int lane)
-{
-    for (int d = B; d < 64; d <<= 1) {
-        U128 o;
-        o.lo = __shfl_up(v.lo, (unsigned)d);
-        o.hi = __shfl_up(v.hi, (unsigned)d);
-        if (lane >= d) v = add128(v, o);
-    }
-    return v;
-}
-
 constexpr int kSweep = 4;                       // windows per sweep of pass 1
 constexpr int kQ = 1 + 2 * kSweep;              // T, then S0 and S1 per window
 
@@ -80,29 +31,24 @@ constexpr int kQ = 1 + 2 * kSweep;              // T, then S0 and S1 per window
 
 extern "C" __global__ __launch_bounds__(256) void hare_hist_reduce(ReduceArgs a)
 {
+    using namespace hare_hist;
     using namespace hare_reduce;
     __shared__ U128 s_tot[kQ][4][kMaxBands];    // per quantity, wave and band: the wave's total
     __shared__ U128 s_T[kMaxBands];
     __shared__ U128 s_pre[256];                 // pass 2: the tile's exclusive prefixes P(i), word order
 
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int B = a.bands, nb = a.n_bins, n_win = a.n_win, n_lev = a.n_lev;
-    const int step = 256 / B, A = step * B;
-    const int b = t % B, li = t / B;
-    const bool on = t < A;
-    const int tiles = (nb + step - 1) / step;
-    const size_t ch = (size_t)a.channels;
-    const unsigned long long* const h = a.hist + (size_t)blockIdx.x * (size_t)nb * (size_t)B * ch;
-    const uint32_t* const weight = a.weight;
+    const int n_win = a.n_win, n_lev = a.n_lev;
+    const Block k = block_of(a.hist, a.weight, a.n_bins, a.bands, a.channels);
+    const int B = k.B, nb = k.nb, step = k.step, b = k.b, li = k.li, tiles = k.tiles;
+    const bool on = k.on;
 
     // g(k, i, b) of this thread's band; 0 past the end and for an idle thread
     auto g_at = [&](int i) -> unsigned long long {
         if (!on || i >= nb) return 0ull;
         const int e = i * B + b;
-        const unsigned long long hv = h[(size_t)e * ch];
-        if (!weight) return hv;
-        const unsigned long long w = weight[e];
-        return (hv >> 32) * w + (((hv & 0xFFFFFFFFull) * w) >> 32);          // floor(hv * w / 2^32)
+        const unsigned long long hv = k.h[(size_t)e * k.ch];
+        return k.weight ? weighted(hv, k.weight[e]) : hv;
     };
 
     // ---- pass 1
@@ -150,10 +96,9 @@ extern "C" __global__ __launch_bounds__(256) void hare_hist_reduce(ReduceArgs a)
             }
         }
         __syncthreads();
-        if (want_T && t < B) s_T[t] = add128(add128(s_tot[0][0][t], s_tot[0][1][t]), add128(s_tot[0][2][t], s_tot[0][3][t]));
+        if (want_T && t < B) s_T[t] = band_total(s_tot[0], t);
         if (t < kSweep * B && j0 + li < n_win) {                               // thread (u, b) = (li, b): window j0 + u of band b
-            const U128 s0 = add128(add128(s_tot[1 + 2 * li][0][b], s_tot[1 + 2 * li][1][b]), add128(s_tot[1 + 2 * li][2][b], s_tot[1 + 2 * li][3][b]));
-            const U128 s1 = add128(add128(s_tot[2 + 2 * li][0][b], s_tot[2 + 2 * li][1][b]), add128(s_tot[2 + 2 * li][2][b], s_tot[2 + 2 * li][3][b]));
+            const U128 s0 = band_total(s_tot[1 + 2 * li], b), s1 = band_total(s_tot[2 + 2 * li], b);
             unsigned long long* out = a.sums + (((size_t)blockIdx.x * (size_t)B + (size_t)b) * (size_t)n_win + (size_t)(j0 + li)) * 4;
             out[0] = s0.lo;
             out[1] = s0.hi;

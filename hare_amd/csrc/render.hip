@@ -126,10 +126,7 @@ extern "C" __global__ __launch_bounds__(kRenderThreads, 4) void hare_hist_render
         for (int j = 1; j < M; ++j) p = p + yy[j] * yy[j];
         const size_t e = (size_t)(i0 + il) * (size_t)B + (size_t)b;
         unsigned long long g = a.hist[((size_t)k * (size_t)nb * (size_t)B + e) * (size_t)C];
-        if (a.weight) {
-            const unsigned long long w = a.weight[e];
-            g = (g >> 32) * w + (((g & 0xFFFFFFFFull) * w) >> 32);          // floor(h * w / 2^32)
-        }
+        if (a.weight) g = hare_hist::weighted(g, a.weight[e]);
         const double en = ldexp((double)g, -a.frac_bits);
         s_a[x] = (p > 0.0 && en > 0.0) ? sqrt(en / p) : 0.0;
     }

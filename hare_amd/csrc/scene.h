@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <atomic>
 #include <condition_variable>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -489,7 +490,7 @@ int image_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t 
 // paths found.  Source, receivers and tables must be on the device
 int image2_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                    int32_t frac_bits, int64_t max_cands, int64_t max_paths, void* d_work, void* d_hist, void* d_det, hipStream_t st);
-// The reduction of a receive histogram (receive.cpp; include/hare_hip.h, "receivers", "Reduction").  ReduceSpec: what the caller asks for,
+// The reduction of a receive histogram (hist.cpp; include/hare_hip.h, "receivers", "Reduction").  ReduceSpec: what the caller asks for,
 // host pointers (weight: n_bins x B, nullable).  reduce_check_spec: the checks that need no buffer (HARE_E_INVALID); reduce_enqueue:
 // hare_hist_reduce on the stream, device buffers, win and levels read here
 struct ReduceSpec {
@@ -540,6 +541,12 @@ int build_kdtree(Scene& s, int32_t max_depth, int32_t max_polys);
 int32_t octree_levels(const OctreeHost& o);   // device_scene.cpp
 
 // host helpers
+// a call's buffers, device or host alike: one of the first n_out (its outputs) shares a byte with another of the list; null never overlaps (launch.cpp)
+struct Span {
+    const void* p;
+    size_t bytes;
+};
+bool spans_overlap(std::initializer_list<Span> v, size_t n_out);
 void polygon_normals(const double* verts, const int32_t* nverts, int32_t P, double* out);
 void topology_bounds(const double* verts, const int32_t* nverts, int32_t P, double mn[3], double mx[3]);
 int topology_ingest(const double* soup, const int32_t* nverts, int32_t P, double* verts_out, int32_t* corner_vertex,

@@ -248,6 +248,15 @@ def _reduce_spec(reduce, n_bins: int, B: int):
     return w, 0 if win is None else win.shape[0], win, 0 if lev is None else lev.shape[0], lev
 
 
+def _hist_shape(hist):
+    """A histogram as the receive calls return it, for hist_reduce, hist_project and hist_render: (hist, K, n_bins, B, channels), hist
+    contiguous uint64 [K, n_bins, B] (channels = 1) or [K, n_bins, B, C] (channels = C = 4, 9 or 16)."""
+    hist = np.ascontiguousarray(hist, np.uint64)
+    if hist.ndim not in (3, 4) or (hist.ndim == 4 and hist.shape[3] not in (4, 9, 16)):
+        raise ValueError("hist must be uint64 [K, n_bins, B] or [K, n_bins, B, C], C = 4, 9 or 16")
+    return (hist,) + hist.shape[:3] + (hist.shape[3] if hist.ndim == 4 else 1,)
+
+
 class Spatial_Partition:
     """Hare.Geometry.Spatial_Partition (Spatial_Partition.cs:27-35) over a native scene."""
 
@@ -710,13 +719,10 @@ class Spatial_Partition:
         calls return it, reduced on this partition's device (include/hare_hip.h, "receivers", "Reduction").  windows: [(lo, hi), ...] bin
         ranges; levels: uint32 fractions (decay_levels); weight: uint32 [n_bins, B] (air_weights) or None.  Returns (sums [K, B, n_win, 4]
         uint64 -- S0 lo, S0 hi, S1 lo, S1 hi --, cross [K, B, n_lev] int32)."""
-        hist = np.ascontiguousarray(hist, np.uint64)
-        if hist.ndim not in (3, 4) or (hist.ndim == 4 and hist.shape[3] not in (4, 9, 16)):
-            raise ValueError("hist must be uint64 [K, n_bins, B] or [K, n_bins, B, C], C = 4, 9 or 16")
-        K, nb, B = hist.shape[:3]
+        hist, K, nb, B, channels = _hist_shape(hist)
         w, n_win, win, n_lev, lev = _reduce_spec(dict(windows=windows, levels=levels, weight=weight), nb, B)
         sums, cross = np.zeros((K, B, n_win, 4), np.uint64), np.zeros((K, B, n_lev), np.int32)
-        check(lib.hare_hist_reduce(self._h, K, nb, B, hist.shape[3] if hist.ndim == 4 else 1, ptr(hist), ptr(w), n_win, ptr(win), n_lev, ptr(lev),
+        check(lib.hare_hist_reduce(self._h, K, nb, B, channels, ptr(hist), ptr(w), n_win, ptr(win), n_lev, ptr(lev),
                                    ptr(sums), ptr(cross)))
         return sums, cross
 
@@ -735,14 +741,11 @@ class Spatial_Partition:
         "receivers", "Projection"): the exact signed sums over the bins of coef[j, i] * g[k, i, b].  weight: uint32 [n_bins, B] (air_weights)
         or None.  Returns uint64 [K, B, J, 2], the (lo, hi) words of the 128-bit two's-complement sums, or with as_int an object array
         [K, B, J] of Python integers (proj_to_int)."""
-        hist = np.ascontiguousarray(hist, np.uint64)
-        if hist.ndim not in (3, 4) or (hist.ndim == 4 and hist.shape[3] not in (4, 9, 16)):
-            raise ValueError("hist must be uint64 [K, n_bins, B] or [K, n_bins, B, C], C = 4, 9 or 16")
-        K, nb, B = hist.shape[:3]
+        hist, K, nb, B, channels = _hist_shape(hist)
         coef = _project_coef(coef, nb)
         w, *_ = _reduce_spec(dict(weight=weight), nb, B)
         proj = np.zeros((K, B, coef.shape[0], 2), np.uint64)
-        check(lib.hare_hist_project(self._h, K, nb, B, hist.shape[3] if hist.ndim == 4 else 1, ptr(hist), ptr(w), coef.shape[0], ptr(coef),
+        check(lib.hare_hist_project(self._h, K, nb, B, channels, ptr(hist), ptr(w), coef.shape[0], ptr(coef),
                                     ptr(proj)))
         return proj_to_int(proj) if as_int else proj
 
@@ -758,11 +761,7 @@ class Spatial_Partition:
         """hare_hist_render: a histogram [K, n_bins, B] or [K, n_bins, B, C] (C = 4, 9 or 16) of uint64, as the receive calls return it,
         rendered on this partition's device to impulse responses (include/hare_hip.h, "receivers", "Rendering"): M samples per bin, taps
         [B, T] float64 (band_taps), seed uint64, weight uint32 [n_bins, B] (air_weights) or None.  Returns float64 [K, channels, n_bins * M]."""
-        hist = np.ascontiguousarray(hist, np.uint64)
-        if hist.ndim not in (3, 4) or (hist.ndim == 4 and hist.shape[3] not in (4, 9, 16)):
-            raise ValueError("hist must be uint64 [K, n_bins, B] or [K, n_bins, B, C], C = 4, 9 or 16")
-        K, nb, B = hist.shape[:3]
-        channels = hist.shape[3] if hist.ndim == 4 else 1
+        hist, K, nb, B, channels = _hist_shape(hist)
         taps = np.ascontiguousarray(taps, np.float64)
         if taps.ndim != 2 or taps.shape[0] != B:
             raise ValueError("taps must be float64 [B, T] = [%d, T]" % B)

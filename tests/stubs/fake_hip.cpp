@@ -7,6 +7,8 @@
 // buffers (real ones named through fake_hip_name_host_range; FAKE_HIP_BUFFERS: name=hex address, ... ; each 2^40 bytes) or to the live allocations, numbered in the order they were made (a0,
 // a1, ...).  Events and streams are numbered the same way (e0 ...; s0 is the null stream).  hipMemsetAsync, hipMemcpyAsync, hipStreamWaitEvent
 // and hipEventRecord are logged in order.  The stub never dereferences a pointer it did not allocate (host sources of uploads apart).
+// For the hare_hist_* kernels the line holds their buffers and counts.  fake_hip_log_enable(2) also logs, for a test that counts them, every
+// hipMalloc (`malloc a3 bytes=...`), hipFree (`free a3`) and hipStreamSynchronize (`sync s0`).
 // Built with g++ alone: no HIP header, the runtime's enums are ints at the ABI.
 #include <stdint.h>
 #include <stdio.h>
@@ -35,7 +37,7 @@ struct HostRange { std::string name; uintptr_t base; size_t bytes; };
 std::vector<HostRange> g_host;            // the caller's real buffers (fake_hip_name_host_range)
 std::set<std::string> g_names;            // interned kernel names: a hipFunction_t is the address of one
 std::string g_log;
-bool g_log_on = true;
+int g_log_on = 1;                         // 0: nothing; 1: launches, copies, memsets, events; 2: allocations, frees and synchronisations too
 uintptr_t g_next_handle = 0x1000;
 constexpr uintptr_t kRegionBytes = (uintptr_t)1 << 40;
 constexpr size_t kBigAlloc = (size_t)1 << 20;
@@ -144,6 +146,24 @@ std::string decode(const KdArgs& a)
     F(polys); F(quads); F(nodes); F(items); F(n_nodes); F(max_depth); F(cull); F(cf); F(tight); F(tight_mid); F(tight_rad); F(dnodes);
     return o + " }";
 }
+std::string decode(const ReduceArgs& a)
+{
+    std::string o = "reduce{";
+    F(hist); F(weight); F(sums); F(cross); F(n_bins); F(bands); F(channels); F(n_win); F(n_lev);
+    return o + " }";
+}
+std::string decode(const ProjectArgs& a)
+{
+    std::string o = "project{";
+    F(hist); F(weight); F(coef); F(proj); F(n_bins); F(bands); F(channels); F(n_vec);
+    return o + " }";
+}
+std::string decode(const RenderArgs& a)
+{
+    std::string o = "render{";
+    F(hist); F(weight); F(taps); F(out); F(n_bins); F(bands); F(channels); F(frac_bits); F(M); F(T); F(tile_bins); F(tiles); F(sign_words);
+    return o + " }";
+}
 std::string decode(const ShootIO& a)
 {
     std::string o = "io{";
@@ -155,9 +175,9 @@ std::string decode(const ShootIO& a)
 }
 #undef F
 
-void log_line(const std::string& s)
+void log_line(const std::string& s, int level = 1)
 {
-    if (g_log_on) { g_log += s; g_log += '\n'; }
+    if (g_log_on >= level) { g_log += s; g_log += '\n'; }
 }
 
 bool starts(const std::string& s, const char* p) { return s.compare(0, strlen(p), p) == 0; }
@@ -169,7 +189,7 @@ extern "C" {
 // ---- what the test reads (the same shared object, opened a second time with ctypes)
 const char* fake_hip_log(void) { std::lock_guard<std::mutex> lk(g_mu); static std::string copy; copy = g_log; return copy.c_str(); }
 void fake_hip_log_clear(void) { std::lock_guard<std::mutex> lk(g_mu); g_log.clear(); }
-void fake_hip_log_enable(int on) { std::lock_guard<std::mutex> lk(g_mu); g_log_on = on != 0; }
+void fake_hip_log_enable(int on) { std::lock_guard<std::mutex> lk(g_mu); g_log_on = on; }
 long long fake_hip_live_allocations(void) { std::lock_guard<std::mutex> lk(g_mu); return (long long)g_allocs.size(); }
 // a real host buffer of the caller's: pointers into [base, base + bytes) print as name+offset (a null name forgets every range)
 void fake_hip_name_host_range(const char* name, const void* base, size_t bytes)
@@ -197,6 +217,7 @@ int hipMalloc(void** p, size_t n)
     if (!m || m == (char*)MAP_FAILED) { *p = nullptr; return 2; }
     std::lock_guard<std::mutex> lk(g_mu);
     g_allocs.push_back({m, n});
+    log_line("malloc a" + std::to_string(g_allocs.size() - 1) + " bytes=" + std::to_string(n), 2);
     *p = m;
     return 0;
 }
@@ -206,6 +227,7 @@ int hipFree(void* p)
     std::lock_guard<std::mutex> lk(g_mu);
     for (size_t k = 0; k < g_allocs.size(); ++k)
         if (g_allocs[k].base == p) {
+            log_line("free a" + std::to_string(k), 2);
             if (g_allocs[k].size >= kBigAlloc) munmap(p, g_allocs[k].size);
             else free(p);
             g_allocs.erase(g_allocs.begin() + (long)k);
@@ -265,7 +287,12 @@ int hipStreamDestroy(void* s)
     g_streams.erase(std::remove(g_streams.begin(), g_streams.end(), s), g_streams.end());
     return 0;
 }
-int hipStreamSynchronize(void*) { return 0; }
+int hipStreamSynchronize(void* st)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    log_line("sync " + handle_name(g_streams, st, 's'), 2);
+    return 0;
+}
 int hipDeviceSynchronize(void) { return 0; }
 int hipStreamIsCapturing(void*, int* status) { *status = 0; return 0; }
 int hipModuleLoadData(void** m, const void*) { *m = (void*)(uintptr_t)0x10; return 0; }
@@ -302,6 +329,9 @@ int hipModuleLaunchKernel(void* f, unsigned gx, unsigned gy, unsigned gz, unsign
         o += " " + decode(*(const ShootIO*)args[1]);
         if (*name == "hare_octree_pool") o += " scratch=" + ptr_name(*(void**)args[2]) + " stride=" + std::to_string(*(unsigned*)args[3]);
     }
+    if (*name == "hare_hist_reduce") o += " " + decode(*(const ReduceArgs*)args[0]);
+    if (*name == "hare_hist_project") o += " " + decode(*(const ProjectArgs*)args[0]);
+    if (*name == "hare_hist_render") o += " " + decode(*(const RenderArgs*)args[0]);
     log_line(o);
     return 0;
 }

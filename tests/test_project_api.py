@@ -53,8 +53,13 @@ OVERLAPS = [dict(proj=A0), dict(proj=A0 + 120), dict(hist=A0 + 131072 + 88), dic
 REFUSED = SHAPE + VECTORS + NULLS + OVERLAPS
 
 
+def case_id(kw):
+    """A case's name; an address as its offset in the arena, so that the name is the same in every process"""
+    return ",".join(f"{k}=A0+{v - A0}" if isinstance(v, int) and v >= A0 else f"{k}={v}" for k, v in kw.items())[:50]
+
+
 @pytest.mark.parametrize("dev", (False, True), ids=("host", "device"))
-@pytest.mark.parametrize("kw", REFUSED, ids=lambda kw: ",".join(f"{k}={v}" for k, v in kw.items())[:50])
+@pytest.mark.parametrize("kw", REFUSED, ids=case_id)
 def test_every_refusal_is_invalid_and_names_the_call(grid, kw, dev):
     rc, msg = call(grid, dev, **kw)
     assert rc == capi.HARE_E_INVALID, (kw, rc, msg)
