@@ -8,7 +8,10 @@ occluders, mapped by x -> A x + t with A = R diag(s), R a rotation from a unit q
 the placed receivers mapped along.  Two sets.  edge_cases(): fixed and named, each with the class it is there for (`why`);
 tests/test_path_cases.py asserts on the CPU that each holds it.  sweep_case(seed): one case drawn from a seed over the whole parameter
 space (tools/fuzz_paths.py runs them by the thousand).  digest(result) is the SHA-256 that tests/golden/path_reference_digests.json pins
-(tests/test_path_cases.py)."""
+(tests/test_path_cases.py).  A directional case carries an ambisonic `order` (1, 2 or 3: 4, 9 or 16 channels); ambi_edge_cases() and
+ambi_sweep_case(seed) at the end are the two sets again at orders 2 and 3 (tests/test_gpu_path_ambi.py), pinned in
+tests/golden/path_ambi_reference_digests.json."""
+import contextlib
 import dataclasses
 import functools
 import hashlib
@@ -19,6 +22,7 @@ import numpy as np
 
 import hare_amd.scenes as scenes
 from oracle import pyoracle as po
+from tests import ambi_ref
 from tests import direct_ref as dr
 from tests import image2_ref as i2
 from tests import image_ref as ir
@@ -63,6 +67,7 @@ class PathCase:
     scene: str = ""                      # for describe() only
     why: str = ""                        # an edge case's class
     marks: dict = dataclasses.field(default_factory=dict)        # what the CPU test needs to find the class again (receiver and polygon numbers)
+    order: int = 1                       # the ambisonic order of a directional case: 1, 2 or 3 (4, 9 or 16 channels)
 
     @property
     def K(self):
@@ -82,12 +87,12 @@ class PathCase:
 
     @property
     def shape(self):
-        return (self.K, self.n_bins, self.B, 4) if self.directional else (self.K, self.n_bins, self.B)
+        return (self.K, self.n_bins, self.B, ambi_ref.CHANNELS[self.order]) if self.directional else (self.K, self.n_bins, self.B)
 
     def describe(self):
         return (f"{self.name}: {self.scene} P={self.P} {' '.join(str(x) for x in self.partition)} K={self.K}{' map' if self.map else ''} B={self.B} "
                 f"R={self.R} tables={self.tables} frac_bits={self.frac_bits} n_bins={self.n_bins} bin_len={self.bin_len!r}"
-                f"{' directional' if self.directional else ''} n_weight={self.n_weight} orders={'+'.join(self.orders)} "
+                f"{f' directional order={self.order}' if self.directional else ''} n_weight={self.n_weight} orders={'+'.join(self.orders)} "
                 f"image_cull={self.image_cull} image2_prune={self.image2_prune} pos={self.pos.tolist()!r}")
 
     def without(self, **fields):
@@ -107,24 +112,29 @@ _KEPT = {}
 
 def reference(case, nthreads=16, keep=False):
     """What the library must return for the case, per order it runs: {"direct": dict(hist, det, seen, tallies), "image": the same and
-    pairs, "image2": the same and cands, paths}, each onto zeros.  keep: kept under the case's name and served again (the fixed set,
-    whose tests share it and leave it unchanged)."""
+    pairs, "image2": the same and cands, paths}, each onto zeros.  At order 2 or 3 each path order runs inside its own
+    tests.ambi_ref.higher_order (an Extra collects every deposit made inside it) and the channels 4 .. C - 1 are joined behind the four.
+    keep: kept under the case's name and served again (the fixed set, whose tests share it and leave it unchanged)."""
     if keep and case.name in _KEPT:
         return _KEPT[case.name]
     _, o, normals = oracle_of(case)
     src = (case.pos, case.power, case.frame, case.R, case.gain)
     tail = (case.centers, case.radii, case.n_weight, case.n_bins, case.bin_len, case.frac_bits)
     out = {}
+    high = case.directional and case.order > 1
     for order in case.orders:
-        hist, det, seen, tallies = np.zeros(case.shape, np.uint64), np.zeros((case.K, 2), np.uint64), {}, {}
+        hist, det, seen, tallies = np.zeros(case.shape[:3] + (4,) if high else case.shape, np.uint64), np.zeros((case.K, 2), np.uint64), {}, {}
         res = dict(hist=hist, det=det, seen=seen, tallies=tallies)
-        if order == "direct":
-            dr.direct(o, *src, *tail, hist, det, seen, tallies, nthreads)
-        elif order == "image":
-            res["pairs"] = ir.image(o, case.verts, case.nverts, normals, *src, case.alpha, case.sigma, *tail, hist, det, seen, tallies, nthreads)
-        else:
-            res["cands"], res["paths"] = i2.image2(o, case.verts, case.nverts, normals, *src, case.alpha, case.sigma, *tail, hist, det, seen,
-                                                   tallies, nthreads)
+        with (ambi_ref.higher_order(case.order) if high else contextlib.nullcontext()) as extra:
+            if order == "direct":
+                dr.direct(o, *src, *tail, hist, det, seen, tallies, nthreads)
+            elif order == "image":
+                res["pairs"] = ir.image(o, case.verts, case.nverts, normals, *src, case.alpha, case.sigma, *tail, hist, det, seen, tallies, nthreads)
+            else:
+                res["cands"], res["paths"] = i2.image2(o, case.verts, case.nverts, normals, *src, case.alpha, case.sigma, *tail, hist, det, seen,
+                                                       tallies, nthreads)
+        if high:
+            res["hist"] = ambi_ref.join(hist, extra)
         out[order] = res
     if keep:
         _KEPT[case.name] = out
@@ -619,3 +629,159 @@ def sweep_case(seed):
                 tables=("none", "alpha", "alpha+sigma")[int(rng.integers(0, 3))], frac_bits=int(rng.integers(0, 63)), n_bins=n_bins, bin_len=bin_len,
                 directional=directional, n_weight=(1, 4097, 2 ** 40)[int(rng.integers(0, 3))], orders=orders, seed=int(seed),
                 image_cull=int(rng.integers(0, 2)), image2_prune=int(rng.integers(0, 2)), scene=f"{kind}+{n_occ}")
+
+
+# ---- the higher orders: nine and sixteen channels (tests/test_gpu_path_ambi.py)
+@functools.lru_cache(maxsize=None)
+def pinned_ambi_digests():
+    """tests/golden/path_ambi_reference_digests.json: digest() of every ambi edge case ("edge/" + name) and, for the ambi sweep's seeds
+    ("sweep/" 0 .. N - 1), dict(digest, higher: whether channels 4 .. C - 1 hold a non-zero word in some order)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "path_ambi_reference_digests.json")) as f:
+        return json.load(f)
+
+
+def higher_nonzero(out):
+    return bool(any(res["hist"][..., 4:].any() for res in out.values()))
+
+
+AXIS_SIZE = (10.0, 7.0, 4.0)
+
+
+def axis_box(name, order, *, frac_bits=40, power=None, why=""):
+    """The 12-triangle shoebox UNMAPPED (A the identity, every coordinate dyadic), the source at (3, 2, 1), and receivers of radius 1/8 on
+    the lattice of whole metres inside: the vectors from S, from the six S' and from the S'' to them have whole components, among them
+    (a, 0, 0), (a, a, 0) and (a, a, a) in every sign and axis -- arrivals along the axes, the face diagonals and the space diagonals, their
+    components 0, +-1, +-sqrt(1/2) and +-sqrt(1/3) as the division by dist leaves them -- and whole layers of receivers at the height of
+    the source and of its images behind the walls, where az == 0 and so Y6 == -0.5 exactly.  Receiver 0 is (5, 4, 1): its direct path
+    arrives along (-1, -1, 0) / sqrt(2)."""
+    v, nv, size, pos, _ = base_scene(("box", 1))
+    m = Mapped(v, nv, np.eye(3), np.zeros(3))
+    c = [(5.0, 4.0, 1.0)] + [(x, y, z) for x in (1.0, 3.0, 5.0, 7.0) for y in (1.0, 2.0, 4.0, 6.0) for z in (1.0, 2.0, 3.0) if (x, y, z) not in ((5.0, 4.0, 1.0), (3.0, 2.0, 1.0))]
+    case = make(name, m, V8, pos, np.array(c), np.full(len(c), 0.125), B=3, tables="none", frac_bits=frac_bits, n_bins=64, bin_len=0.5, directional=True,
+                scene="box1 unmapped", why=why, order=order)
+    return case if power is None else case.without(power=np.asarray(power, np.float64))
+
+
+def tie_powers(frac_bits, targets=(1.0, 3.0, 5.0)):
+    """power [3] with m_b = (power_b * fw) * 2^frac_bits EXACTLY 1, 3 and 5 on the direct path of axis_box's receiver 0 (no table, no
+    reflectance: the deposit's products with 1.0 are exact): the quotient, moved by units in the last place until the product is the
+    target.  m_b * Y6 is then -0.5, -1.5 and -2.5, ties of the rint, and rint(m_b) 1, 3 and 5."""
+    case = axis_box("probe", 3)
+    fw = dr.share(case.radii[0] * case.radii[0], d2_of(case.centers[0], case.pos)) * np.float64(case.n_weight)
+    out = []
+    for t in targets:
+        p = np.float64(t) / (fw * np.float64(2.0 ** frac_bits))
+        for _ in range(64):
+            got = (p * fw) * np.float64(2.0 ** frac_bits)
+            if got == t:
+                break
+            p = np.nextafter(p, np.inf if got < t else -np.inf)
+        assert (p * fw) * np.float64(2.0 ** frac_bits) == t, (t, p)
+        out.append(p)
+    return np.array(out)
+
+
+def drum_room(n_side=64, radius=4.0, height=3.0):
+    """A prism over a regular n_side-gon: n_side wall quadrilaterals, each in a plane of its own, a floor and a ceiling of n_side triangles
+    each about the axis.  From a source and receivers near the axis every wall reflects a first-order path and every (wall, floor),
+    (floor, wall), (wall, ceiling), (ceiling, wall) pair a second-order one -- the 6 planes of a shoebox give 6 and about 30, however
+    finely they are tessellated."""
+    a = 2.0 * np.pi * np.arange(n_side + 1) / n_side
+    ring = np.stack([radius + radius * np.cos(a), radius + radius * np.sin(a)], axis=1)
+    v, nv = np.zeros((3 * n_side, 4, 3)), np.full(3 * n_side, 3, np.int32)
+    for i in range(n_side):
+        (x0, y0), (x1, y1) = ring[i], ring[i + 1]
+        v[i] = [(x0, y0, 0.0), (x1, y1, 0.0), (x1, y1, height), (x0, y0, height)]
+        v[n_side + i, :3] = [(radius, radius, 0.0), (x0, y0, 0.0), (x1, y1, 0.0)]
+        v[2 * n_side + i, :3] = [(radius, radius, height), (x0, y0, height), (x1, y1, height)]
+    nv[:n_side] = 4
+    return v, nv, (2.0 * radius, 2.0 * radius, height)
+
+
+def one_word_case():
+    """Every path of a receiver into ONE bin (n_bins = 1, bin_len 1000): each of its B x 16 words is the wrapped sum of one atomic per
+    path -- more than 50 first-order and 200 second-order paths per receiver in the drum room, rotated by a drawn quaternion and scaled
+    by 1.3 on every axis (a map that keeps angles, so that the walls go on reflecting towards the axis)."""
+    rng = np.random.default_rng(7090)
+    v, nv, size = drum_room()
+    m = Mapped(v, nv, quaternion_rotation(rng.normal(size=4)) * 1.3)
+    mid = np.asarray(size) / 2
+    c = m(mid + np.array([(0.15, 0.05, 0.1), (-0.1, 0.125, -0.2), (0.05, -0.15, 0.25), (-0.125, -0.1, -0.05)]))
+    return make("one-word-o3", m, V8, m(mid + np.array((0.075, -0.05, 0.15))), c, np.full(4, 0.1 * m.radius_scale), B=3, tables="alpha", frac_bits=40,
+                n_bins=1, bin_len=1000.0, directional=True, scene="drum64", why="many paths of a receiver in one word", order=3)
+
+
+def wide_cases():
+    """B = 8 at order 3, 128 words per deposit: K = 255 and 256 linear and 257 as a map with the first two orders; K = 8 with the second
+    order at P = 256."""
+    out = []
+    for j, K in enumerate((255, 256, 257)):
+        m, size, pos, placed, rng = _box(2, 90 + j, extra=6, partition=PARTITIONS[j])
+        c, r = receivers_in(rng, m, size, K, placed)
+        out.append(make(f"wide-K{K}-o3", m, PARTITIONS[j], pos, c, r, B=8, R=(0, 4, 1)[j], tables=("alpha", "alpha+sigma", "none")[j], n_bins=32, bin_len=1.0,
+                        directional=True, orders=("direct", "image"), seed=j, scene="box2+soup", why="128 words per deposit, K about a block of 256", order=3))
+    m, size, pos, placed, rng = _box(4, 31, 256 - 192, partition=O48, walls_last=True)
+    c, r = receivers_in(rng, m, size, 8, placed)
+    out.append(make("wide-P256-K8-second-o3", m, O48, pos, c, r, B=8, tables="alpha", n_bins=64, bin_len=1.0, directional=True, orders=("image2",),
+                    pair=("image2_prune",), scene="box4+soup", why="128 words per deposit, P a tile of 256 second polygons", order=3))
+    return out
+
+
+def partition_cases3():
+    out = []
+    for j, part in enumerate(PARTITIONS):
+        m, size, pos, placed, rng = _box(2, 95 + j, extra=8, partition=part)
+        c, r = receivers_in(rng, m, size, 8, placed)
+        out.append(make(f"{part[0]}-o3", m, part, pos, c, r, B=3, R=(4, 0, 1)[j], tables="alpha+sigma", bin_len=0.5, directional=True, seed=j,
+                        scene="box2+soup", why=f"order 3 under the {part[0]} partition, with occluders", order=3))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def ambi_edge_cases():
+    """The fixed cases of the nine- and sixteen-channel forms: every directional case of edge_cases() again at order 2 and 3 (name +
+    "-o2" / "-o3"; the option pairs run through variants() as before); arrivals along the axes and diagonals (axis_box); ties of the
+    signed words and the clamp; the widest word block; many paths in one word; every partition."""
+    out = [c.without(name=f"{c.name}-o{o}", order=o, marks=dict(c.marks, base=c.name)) for c in edge_cases() if c.directional for o in (2, 3)]
+    for o in (2, 3):
+        out.append(axis_box(f"arrivals-o{o}", o, why="arrivals along the axes, the face diagonals and the space diagonals; az == 0"))
+        for fb in (0, 1):
+            out.append(axis_box(f"ties-f{fb}-o{o}", o, frac_bits=fb, power=tie_powers(fb), why="m = 1, 3, 5 with Y6 == -0.5: the signed words' ties"))
+        out.append(axis_box(f"clamp-f62-o{o}", o, frac_bits=62, power=np.full(3, 2.0 ** 20), why="m == 2^63: every signed channel at the +-2^62 clamp"))
+    out += wide_cases() + [one_word_case()] + partition_cases3()
+    names = [c.name for c in out]
+    assert len(set(names)) == len(names)
+    return tuple(out)
+
+
+AMBI_KBC_MAX = 8192                      # K x B x C of an ambi sweep case: the reference makes B x (C - 1) numpy adds per path and a receiver has some
+                                         # six first-order paths, so the slowest seeds stay at a few seconds (K = 64 at B = 8, C = 16; the wide
+                                         # cases of ambi_edge_cases() run K = 255 .. 257 there)
+
+
+def ambi_sweep_case(seed):
+    """sweep_case(seed), directional, at an order drawn from a generator of its own (the base draw is untouched): 2 or 3.  Three rules,
+    each a function of the base case alone; no seed is skipped or redrawn.
+    K is cut to AMBI_KBC_MAX / (B C) receivers (the first ones: the placed receivers stay).
+    To stay within WORDS_MAX words per order at 9 or 16 channels n_bins is halved (rounded up) and bin_len doubled until
+    K x n_bins x B x C fits: the histogram covers the base seed's time span (one bin more where n_bins was odd), so every path the base
+    seed bins is binned here.
+    A quarter of the base seeds draw a histogram that ends before the NEAREST receiver's direct distance |c - S|, which no path of any
+    order undercuts: every arrival is counted as unbinned and the histogram stays zero on all channels, whatever frac_bits is.  Those
+    seeds alone get bin_len doubled until the histogram reaches past the FARTHEST receiver's direct distance; a histogram that bins
+    anything keeps its span, short ones with unbinned arrivals included.  frac_bits stays the base seed's: with that rule
+    tests/test_path_cases.py finds the channels 4 .. C - 1 all zero in fewer than 10 of 100 seeds (low frac_bits rounding every m * Y
+    to 0), so the draw needed no change."""
+    base = sweep_case(seed)
+    order = int(np.random.default_rng(0xA3B20000 + int(seed)).integers(2, 4))
+    C = ambi_ref.CHANNELS[order]
+    K = max(1, min(base.K, AMBI_KBC_MAX // (base.B * C)))
+    centers, radii = np.ascontiguousarray(base.centers[:K]), base.radii[:K]
+    n_bins, bin_len = base.n_bins, base.bin_len
+    while K * n_bins * base.B * C > WORDS_MAX:
+        n_bins, bin_len = (n_bins + 1) // 2, bin_len * 2.0
+    d = np.sqrt(((centers - base.pos[None]) ** 2).sum(axis=1))
+    if n_bins * bin_len < d.min():
+        while n_bins * bin_len <= d.max():
+            bin_len *= 2.0
+    return base.without(name=f"ambi-sweep-{seed}", directional=True, order=order, centers=centers, radii=radii, n_bins=n_bins, bin_len=bin_len)

@@ -1,5 +1,6 @@
-"""The device side of the source paths' differential tests (tests/test_gpu_path_{edges,sweep}.py, tools/fuzz_paths.py): a
-tests.path_cases.PathCase set up in the library and run through direct_device, Image_device and Image2_device for the orders it names --
+"""The device side of the source paths' differential tests (tests/test_gpu_path_{edges,sweep,ambi}.py, tools/fuzz_paths.py): a
+tests.path_cases.PathCase set up in the library and run through direct_device, Image_device and Image2_device for the orders it names, at
+the ambisonic order it names (one, four, nine or sixteen channels: every size here follows from case.shape) --
 onto random non-zero words, with guard bytes behind every buffer and lists of exactly the counts the reference found -- and compared with
 what tests.path_cases.reference returns for it.  torch and the GPU are touched in check_case alone: the module imports on a host without
 one."""
@@ -75,13 +76,13 @@ def check_case(case, want):
         w = want[order]
         if order == "direct":
             got = run_order(torch, g, case, order, H.Voxel_Grid.direct_work_bytes(K),
-                            lambda dw, dh, dd: g.direct_device(*tail, dw, dh, dd, directional=case.directional))
+                            lambda dw, dh, dd: g.direct_device(*tail, dw, dh, dd, directional=case.directional, order=case.order))
             if isinstance(got, str):
                 return got
         elif order == "image":
             M = max(1, w["pairs"])                                      # a list of exactly the pairs there are
             got = run_order(torch, g, case, order, H.Voxel_Grid.image_work_bytes(K, P, M),
-                            lambda dw, dh, dd: g.Image_device(*tail, M, dw, dh, dd, directional=case.directional))
+                            lambda dw, dh, dd: g.Image_device(*tail, M, dw, dh, dd, directional=case.directional, order=case.order))
             if isinstance(got, str):
                 return got
             work = got[2]
@@ -95,7 +96,7 @@ def check_case(case, want):
         else:
             C, M = max(1, w["cands"]), max(1, w["paths"])
             got = run_order(torch, g, case, order, H.Voxel_Grid.image2_work_bytes(P, C, M),
-                            lambda dw, dh, dd: g.Image2_device(*tail, C, M, dw, dh, dd, directional=case.directional))
+                            lambda dw, dh, dd: g.Image2_device(*tail, C, M, dw, dh, dd, directional=case.directional, order=case.order))
             if isinstance(got, str):
                 return got
             work = got[2]

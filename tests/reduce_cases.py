@@ -82,12 +82,12 @@ class Case:
 
 @lru_cache(maxsize=None)
 def inputs(case):
-    """(hist [K, n_bins, B(, 4)] uint64, weight [n_bins, B] uint32 or None), from the case's seed."""
+    """(hist [K, n_bins, B(, C)] uint64 with C = 4, 9 or 16, weight [n_bins, B] uint32 or None), from the case's seed."""
     rng = np.random.default_rng(1000 + case.index)
-    shape = (case.K, case.n_bins, case.B) + ((4,) if case.channels == 4 else ())
+    shape = (case.K, case.n_bins, case.B) + ((case.channels,) if case.channels > 1 else ())
     hist = words(case.word, shape, rng)
-    if case.channels == 4:
-        hist[..., 1:] = rng.integers(0, 1 << 64, hist[..., 1:].shape, dtype=np.uint64)      # X, Y, Z: never read
+    if case.channels > 1:
+        hist[..., 1:] = rng.integers(0, 1 << 64, hist[..., 1:].shape, dtype=np.uint64)      # the channels 1 .. C - 1: never read
     wk = case.weight_kind
     weight = None if wk == "none" else (np.zeros((case.n_bins, case.B), np.uint32) if wk == "zero" else
                                         np.full((case.n_bins, case.B), MAX32, np.uint32) if wk == "ones" else
@@ -105,3 +105,7 @@ COVER = [Case(i, *s) for i, s in enumerate(shapes())]
 # every word class with every weight at one shape that has idle threads (B = 3), a partial last tile and several tiles
 CLASSES = [Case(100 + 4 * a + b, 300, 3, 3, 1 + 3 * (a % 2), word=w, win=3 if (a + b) % 2 else 2, lev=3, weight=x)
            for a, w in enumerate(WORDS) for b, x in enumerate(WEIGHTS)]
+# the strides 9 and 16 of the higher orders' histograms (channel 0 of a word block of C): n_bins below a tile, one past 256 and several
+# tiles; B with idle threads and full; words that differ from bin to bin, so that a read at another stride gives other sums
+STRIDES = [Case(200 + 6 * a + 2 * b + c, n, (3, 8)[(a + b + c) % 2], 3, C, word=("full", "decay")[(b + c) % 2], win=2, lev=3, weight=("none", "random")[c])
+           for a, C in enumerate((9, 16)) for b, n in enumerate((63, 257, 1000)) for c in range(2)]

@@ -21,7 +21,7 @@ def _words(x):
 
 
 def reduce_direct(hist, windows=(), levels=(), weight=None):
-    """The definition as the header states it.  hist: uint64 [K, n_bins, B] or [K, n_bins, B, 4]; windows: (lo, hi) bin pairs; levels:
+    """The definition as the header states it.  hist: uint64 [K, n_bins, B] or [K, n_bins, B, C] (C = 4, 9 or 16: channel 0 is read); windows: (lo, hi) bin pairs; levels:
     uint32 fractions in units of 2^-32; weight: uint32 [n_bins, B] or None.  Returns (sums uint64 [K, B, n_win, 4], cross int32
     [K, B, n_lev])."""
     (K, n_bins, B), h, windows, levels, w = _inputs(hist, windows, levels, weight)

@@ -1,13 +1,13 @@
 """hare_hist_reduce on the MI355X (include/hare_hip.h, "receivers", "Reduction"): the device call on torch tensors and the host call
 return, byte for byte, what the integer restatement (tests/reduce_ref.py) computes -- over a pairwise cover of the shapes at the
-kernel's tile, wave and carry edges, every word class with every kind of weights, the window and level sets of
-tests/reduce_cases.py.  The device call allocates nothing, frees nothing and waits for nothing, and two runs give the same bytes."""
+kernel's tile, wave and carry edges, every word class with every kind of weights, histograms of nine and sixteen channels (the higher
+orders' strides), the window and level sets of tests/reduce_cases.py.  The device call allocates nothing, frees nothing and waits for nothing, and two runs give the same bytes."""
 import numpy as np
 import pytest
 
 import hare_amd as H
 from tests.receive_harness import CALL_COUNTERS, same_bits
-from tests.reduce_cases import CLASSES, COVER, inputs, reference
+from tests.reduce_cases import CLASSES, COVER, STRIDES, inputs, reference
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +60,11 @@ def test_shapes_at_the_tile_wave_and_carry_edges(grid, case):
 
 @pytest.mark.parametrize("case", CLASSES, ids=lambda c: c.id)
 def test_every_word_class_with_every_weight(grid, case):
+    check(grid, case)
+
+
+@pytest.mark.parametrize("case", STRIDES, ids=lambda c: c.id)
+def test_channel_0_is_read_at_the_strides_of_nine_and_sixteen_channels(grid, case):
     check(grid, case)
 
 

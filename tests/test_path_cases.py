@@ -3,13 +3,20 @@ every edge case holds the class it names -- counted from `seen`, the tallies and
 through at least one order it runs; over the N seeds each order runs in at least a third and finds a free path in at least half of
 those; every partition and both values of each option occur.  tests/golden/path_reference_digests.json holds tests.path_cases.digest of
 every edge case and sweep seed, so that a later edit of tests/direct_ref.py, tests/image_ref.py or tests/image2_ref.py cannot move the
-target unnoticed.  A digest that changes on purpose is a change of the specification: regenerate the file and say so."""
+target unnoticed.  A digest that changes on purpose is a change of the specification: regenerate the file and say so.
+The cases at ambisonic orders 2 and 3 (tests.path_cases.ambi_edge_cases, ambi_sweep_case; tests/test_gpu_path_ambi.py) follow below in the
+same way, pinned in tests/golden/path_ambi_reference_digests.json: each class is found again in the deposits the reference makes (m and
+the arrival vector of each, read where they are handed over) or in the words it returns, and at most a tenth of the sweep's seeds leave the
+channels 4 .. C - 1 all zero."""
 import numpy as np
 import pytest
 
+from tests import ambi_ref
 from tests import image2_ref as i2
 from tests import image_ref as ir
 from tests import path_cases as pc
+from tests.receive_ref import magnitude
+from tests.test_gpu_path_ambi import N as AMBI_N
 from tests.test_gpu_path_sweep import N
 
 EDGES = {c.name: c for c in pc.edge_cases()}
@@ -258,3 +265,189 @@ def test_the_sweep_covers_the_orders_the_partitions_and_the_options(sweep):
     assert {c.tables for c in cases} == {"none", "alpha", "alpha+sigma"} and {c.R for c in cases} == {0, 1, 4}
     assert any(c.map and c.K > 256 for c in cases) and any(c.K == 1 for c in cases) and {c.n_weight for c in cases} == {1, 4097, 2 ** 40}
     assert any(np.abs(c.verts[:, :3]).max() > 500 for c in cases) and any(c.verts[:, :3].min() == 0.0 for c in cases)
+
+
+# ---- the higher orders (tests/test_gpu_path_ambi.py): tests.path_cases.ambi_edge_cases() and ambi_sweep_case(seed)
+AMBI = {c.name: c for c in pc.ambi_edge_cases()}
+RERUNS = [n for n, c in AMBI.items() if "base" in c.marks]
+TWO62 = 2.0 ** 62
+
+
+def aref(name):
+    return pc.reference(AMBI[name], keep=True)
+
+
+def deposits_of(case, orders=None):
+    """Every deposit the reference makes for the case, per path order: rows of (k, bin, m [B], the arrival vector (x, y, z)) -- read where
+    tests.ambi_ref.higher_order hands them to tests.ambi_ref.deposit."""
+    real, log = ambi_ref.deposit, {}
+
+    def spy(extra, hist, k, bins, v, frac_bits, arrival, counts=None, tallies=None):
+        rows.append((int(k), int(bins[0]), magnitude(v, frac_bits)[:, 0], tuple(float(x[0]) for x in arrival())))
+        real(extra, hist, k, bins, v, frac_bits, arrival, counts, tallies)
+    ambi_ref.deposit = spy
+    try:
+        for o in orders or case.orders:
+            rows = log[o] = []
+            pc.reference(case.without(orders=(o,)))
+    finally:
+        ambi_ref.deposit = real
+    return log
+
+
+def test_the_ambi_file_holds_exactly_the_cases():
+    assert set(pc.pinned_ambi_digests()) == {"edge/" + n for n in AMBI} | {f"sweep/{s}" for s in range(AMBI_N)}
+
+
+@pytest.mark.parametrize("name", list(AMBI))
+def test_ambi_edge_case_gives_the_pinned_result_on_c_channels(name):
+    case, out = AMBI[name], aref(name)
+    assert case.directional and case.order in (2, 3) and case.why
+    for res in out.values():
+        assert res["hist"].shape == case.shape == (case.K, case.n_bins, case.B, ambi_ref.CHANNELS[case.order])
+    assert pc.higher_nonzero(out), case.describe()
+    assert pc.digest(out) == pc.pinned_ambi_digests()["edge/" + name], case.describe()
+
+
+@pytest.mark.parametrize("name", RERUNS)
+def test_the_order_changes_nothing_but_the_higher_channels(name):
+    """A rerun of a directional edge case: the four channels, det, the counts and what the searches saw are the base case's; the
+    case still stands in its oblique room, so the arrivals are oblique; the higher channels of every order it runs hold words."""
+    case, out, base = AMBI[name], aref(name), ref(AMBI[name].marks["base"])
+    assert EDGES[case.marks["base"]].directional and case.pair == EDGES[case.marks["base"]].pair and set(out) == set(base)
+    for o, res in out.items():
+        assert (res["hist"][..., :4] == base[o]["hist"]).all() and (res["det"] == base[o]["det"]).all() and res["hist"][..., 4:].any()
+        assert res["tallies"] == base[o]["tallies"]
+        for key in ("pairs", "cands", "paths"):
+            assert res.get(key) == base[o].get(key)
+        for key in ("k", "p", "q", "binned", "eligible", "occluded"):
+            assert (key in res["seen"]) == (key in base[o]["seen"]) and (key not in res["seen"] or (res["seen"][key] == base[o]["seen"][key]).all())
+    if name.startswith("rr-edges"):
+        rows = deposits_of(case)
+        assert all(min(abs(c) for c in a) > 1e-3 for o in rows for _, _, _, a in rows[o]) and all(rows[o] for o in pc.ORDERS)
+
+
+def test_the_arrivals_run_along_the_axes_and_the_diagonals():
+    """Per path order: an arrival along every axis, a face diagonal in every coordinate plane and a space diagonal, in both signs; the
+    components are 0, +-1 and what the division leaves of sqrt(1/2) and sqrt(1/3); with az == 0, Y6 == -0.5 exactly."""
+    case = AMBI["arrivals-o3"]
+    assert (case.verts == np.round(case.verts * 8) / 8).all() and AMBI["arrivals-o2"].centers.tobytes() == case.centers.tobytes()
+    rows = deposits_of(case)
+    for o in pc.ORDERS:
+        a = np.array([r[3] for r in rows[o]])
+        zero, mag = a == 0.0, np.abs(a)
+        axial = {(int(np.argmax(m)), float(x[np.argmax(m)])) for x, m, z in zip(a, mag, zero) if z.sum() == 2}
+        assert axial >= ({(i, s) for i in range(3) for s in (1.0, -1.0)} if o != "direct" else {(0, 1.0), (0, -1.0), (1, -1.0), (2, -1.0)}), (o, axial)
+        face = {(int(np.argmax(z)), tuple(np.sign(x[~z]))) for x, m, z in zip(a, mag, zero) if z.sum() == 1 and len(set(m[~z])) == 1}
+        assert {f[0] for f in face} == {0, 1, 2} and len(face) >= 6, (o, face)
+        space = [x for x, m, z in zip(a, mag, zero) if z.sum() == 0 and len(set(m)) == 1]
+        assert len({tuple(np.sign(x)) for x in space}) >= 2, o
+        assert all(abs(abs(x[0]) - np.sqrt(1 / 3)) < 1e-15 for x in space)
+        assert all(abs(m[~z][0] - np.sqrt(0.5)) < 1e-15 for m, z in zip(mag, zero) if z.sum() == 1 and len(set(m[~z])) == 1)
+        level = a[a[:, 2] == 0.0]
+        assert len(level) >= 8 and all(ambi_ref.harmonics(*x)[2] == -0.5 for x in level), o
+
+
+@pytest.mark.parametrize("fb", (0, 1))
+@pytest.mark.parametrize("order", (2, 3))
+def test_the_signed_words_meet_ties(order, fb):
+    """Receiver 0's direct path: m is 1, 3 and 5 exactly, az == 0, so m * Y6 is -0.5, -1.5 and -2.5, and the word is the tie rounded to
+    even: -0, -2, -2.  The words are read back from the reference: nothing else lands in that bin of receiver 0."""
+    case = AMBI[f"ties-f{fb}-o{order}"]
+    assert case.frac_bits == fb and case.centers.tobytes() == AMBI["arrivals-o3"].centers.tobytes()
+    (k, bin_, m, a), = [r for r in deposits_of(case, ("direct",))["direct"] if r[0] == 0]
+    y6 = ambi_ref.harmonics(*a)[2]
+    assert m.tolist() == [1.0, 3.0, 5.0] and a[2] == 0.0 and y6 == -0.5 and (m * y6).tolist() == [-0.5, -1.5, -2.5]
+    words = aref(case.name)["direct"]["hist"][0, bin_]
+    assert words[:, 0].tolist() == [1, 3, 5] and words[:, 6].view(np.int64).tolist() == [0, -2, -2]
+    assert aref(case.name)["direct"]["tallies"]["ties"] == 0            # m itself is whole: the ties are the signed words' own
+    x = m[:, None] * np.array(a)[None, :2]                              # X and Y of the same deposit: m / sqrt(2), no tie, not whole
+    assert (words[:, 1:3].view(np.int64) == np.rint(x)).all() and (x != np.rint(x)).all()
+
+
+@pytest.mark.parametrize("order", (2, 3))
+def test_every_signed_channel_stands_at_the_clamp(order):
+    case = AMBI[f"clamp-f62-o{order}"]
+    rows = deposits_of(case)
+    C = ambi_ref.CHANNELS[order]
+    hit = np.zeros((2, C), bool)
+    n = 0
+    for o in pc.ORDERS:
+        assert aref(case.name)[o]["tallies"]["saturated"] == 3 * len(rows[o]) > 0          # every add at m == 2^63
+        for _, _, m, a in rows[o]:
+            w = m[0] * np.array(list(a) + ambi_ref.harmonics(*a, order=order))
+            hit[0, 1:] |= w >= TWO62
+            hit[1, 1:] |= w <= -TWO62                       # Y6 >= -0.5: it reaches -2^62 and no further
+            n += 1
+    assert hit[:, 1:].all(), (order, np.argwhere(~hit[:, 1:]))           # every channel 1 .. C - 1, at +2^62 and at -2^62
+    h = np.concatenate([aref(case.name)[o]["hist"].reshape(-1, C) for o in pc.ORDERS])
+    lone = h[h[:, 0] == np.uint64(1 << 63)]                              # words of a single deposit
+    assert len(lone) and ((lone[:, 1:].view(np.int64) == 1 << 62) | (lone[:, 1:].view(np.int64) == -(1 << 62))).any(axis=0).all()
+
+
+@pytest.mark.parametrize("name", [n for n in AMBI if n.startswith("wide-")])
+def test_the_wide_cases_add_128_words_per_deposit(name):
+    case, out = AMBI[name], aref(name)
+    assert case.B == 8 and case.order == 3 and case.shape[2] * case.shape[3] == 128
+    if "second" in name:
+        s = out["image2"]["seen"]
+        assert case.P == 256 and case.K == 8 and case.orders == ("image2",) and (s["binned"] & ~s["occ"].any(axis=1)).sum() > 50
+    else:
+        K = int(name.split("-")[1][1:])
+        assert case.K == K and case.map == (K > 256) and case.orders == ("direct", "image")
+        assert out["image"]["hist"][K - 1, ..., 4:].any() and out["direct"]["hist"][K - 2:, ..., 4:].any()
+    for res in out.values():
+        assert (res["hist"] != 0).any(axis=(0, 1))[case.power > 0].all() and (case.power > 0).sum() >= 7        # every word of the block, somewhere (one band has no power)
+
+
+def test_many_paths_of_a_receiver_land_in_one_word():
+    case, out = AMBI["one-word-o3"], aref("one-word-o3")
+    assert case.n_bins == 1 and case.order == 3
+    s1, s2 = out["image"]["seen"], out["image2"]["seen"]
+    first = np.bincount(s1["k"][s1["binned"]], minlength=case.K)
+    second = np.bincount(s2["k"][s2["binned"]], minlength=case.K)
+    assert first.min() >= 50 and second.min() >= 200, (first, second)
+    assert (out["image"]["det"][:, 0] == first).all() and (out["image2"]["det"][:, 0] == second).all() and not out["image2"]["det"][:, 1].any()
+    signed = ambi_ref.signed(out["image2"]["hist"])
+    assert (signed < 0).any() and (signed > 0).any()                     # sums of both signs: words that wrap as uint64
+
+
+@pytest.mark.parametrize("kind", ("voxel", "octree", "kdtree"))
+def test_order_3_runs_under_every_partition_with_occluders(kind):
+    case, out = AMBI[f"{kind}-o3"], aref(f"{kind}-o3")
+    assert case.partition[0] == kind and case.order == 3 and case.P > 48 and set(out) == set(pc.ORDERS)
+    normals = pc.oracle_of(case)[2]
+    assert (np.abs(normals[:48]) > 1e-3).all()                           # an oblique room
+    assert out["image"]["seen"]["occ_rcv"].any() or out["image"]["seen"]["occ_src"].any() or out["image2"]["seen"]["occ"].any()
+    assert all(res["det"][:, 0].sum() > 0 and res["hist"][..., 4:].any() for res in out.values())
+
+
+@pytest.fixture(scope="module")
+def ambi_sweep():
+    rows = []
+    for seed in range(AMBI_N):
+        case = pc.ambi_sweep_case(seed)
+        out = pc.reference(case)
+        rows.append((case, sum(int(r["det"].sum()) for r in out.values()), pc.digest(out), pc.higher_nonzero(out)))
+    return rows
+
+
+def test_every_ambi_sweep_seed_is_its_base_seed_widened_and_gives_the_pinned_result(ambi_sweep):
+    for seed, (case, det, dig, higher) in enumerate(ambi_sweep):
+        base = pc.sweep_case(seed)
+        assert case.directional and case.order in (2, 3) and det > 0, case.describe()
+        assert int(np.prod(case.shape)) <= pc.WORDS_MAX and case.K * case.B * case.shape[3] <= max(pc.AMBI_KBC_MAX, case.B * case.shape[3])
+        assert case.n_bins * case.bin_len >= base.n_bins * base.bin_len and case.centers.tobytes() == base.centers[:case.K].tobytes()
+        for f in ("partition", "frac_bits", "n_weight", "orders", "image_cull", "image2_prune", "R", "map"):
+            assert getattr(case, f) == getattr(base, f), (seed, f)
+        assert case.verts.tobytes() == base.verts.tobytes() and case.pos.tobytes() == base.pos.tobytes() and case.power.tobytes() == base.power.tobytes()
+        assert dict(digest=dig, higher=higher) == pc.pinned_ambi_digests()[f"sweep/{seed}"], case.describe()
+
+
+def test_the_ambi_sweep_is_not_vacuous_in_the_higher_channels(ambi_sweep):
+    """At most 10 of 100 seeds leave the channels 4 .. C - 1 all zero (nothing binned, or a low frac_bits that rounds every m * Y to 0)."""
+    zero = [seed for seed, row in enumerate(ambi_sweep) if not row[3]]
+    assert 10 * len(zero) <= AMBI_N, zero
+    assert {row[0].order for row in ambi_sweep} == {2, 3}
+    for order in pc.ORDERS:
+        assert sum(1 for row in ambi_sweep if order in row[0].orders and row[3]) >= AMBI_N // 4, order
