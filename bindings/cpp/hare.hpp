@@ -377,6 +377,24 @@ public:
     {
         check(hare_hist_render_device(scene_, K, n_bins, B, channels, d_hist, d_weight, frac_bits, M, T, d_taps, seed, d_out, stream));
     }
+    // hare_convolve (include/hare_hip.h, "receivers", "Convolution"): the R rows of N doubles in ir -- the rows HistRender writes, R = K x
+    // channels -- each convolved in the time domain with the one signal x; the samples n0 .. n0 + n_out - 1 of the N + L - 1 of the full
+    // convolution into out, R x n_out.  n_out < 0: everything from n0 on
+    void Convolve(const std::vector<double>& ir, int64_t R, const std::vector<double>& x, std::vector<double>& out, int64_t n0 = 0, int64_t n_out = -1)
+    {
+        if (R < 1 || ir.empty() || ir.size() % (size_t)R != 0) throw std::invalid_argument("Convolve: ir must hold R x N values");
+        if (x.empty()) throw std::invalid_argument("Convolve: x must hold the signal");
+        const int64_t N = (int64_t)(ir.size() / (size_t)R), L = (int64_t)x.size();
+        if (n_out < 0) n_out = N + L - 1 - n0;
+        if (n0 < 0 || n_out < 1 || n0 + n_out > N + L - 1) throw std::invalid_argument("Convolve: the window must lie within the N + L - 1 samples");
+        out.assign((size_t)R * (size_t)n_out, 0.0);
+        check(hare_convolve(scene_, R, N, ir.data(), L, x.data(), n0, n_out, out.data()));
+    }
+    // hare_convolve_device on device pointers and a hipStream_t: d_y (R x n_out doubles) written.  Stream-ordered.
+    void ConvolveDevice(int64_t R, int64_t N, const void* d_ir, int64_t L, const void* d_x, int64_t n0, int64_t n_out, void* d_y, void* stream = nullptr)
+    {
+        check(hare_convolve_device(scene_, R, N, d_ir, L, d_x, n0, n_out, d_y, stream));
+    }
     // Receive / ReceiveSource with the histogram reduced on the device (hare_receive_batch_reduced / hare_receive_source_reduced): sums and
     // cross as HistReduce gives them on the histogram Receive returns; the histogram itself never comes down
     uint64_t ReceiveReduced(const std::vector<hare_ray>& rays, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,

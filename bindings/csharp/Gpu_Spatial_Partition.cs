@@ -432,6 +432,18 @@ namespace Hare
                 HareHip.Check(HareHip.hare_hist_render(scenes[0], K, n_bins, B, channels, hist, weight, frac_bits, M, taps.Length / B, taps, seed, result));
             }
 
+            /// <summary>hare_convolve: the R rows of N doubles in ir (the rows HistRender writes: R = K x channels) each convolved with the one
+            /// signal x on the first scene's device, FP64 in the time domain (include/hare_hip.h, "Convolution"); the samples n0 ..
+            /// n0 + n_out - 1 of the N + L - 1 of the full convolution into result, R x n_out doubles.</summary>
+            public void Convolve(double[] ir, long R, long N, double[] x, long n0, long n_out, double[] result)
+            {
+                if (R < 1 || N < 1 || ir == null || ir.LongLength < R * N) throw new ArgumentException("ir must hold R x N values");
+                if (x == null || x.Length == 0) throw new ArgumentException("x must hold the signal");
+                if (n0 < 0 || n_out < 1 || n0 + n_out > N + x.LongLength - 1) throw new ArgumentException("the window must lie within the N + L - 1 samples");
+                if (result == null || result.LongLength < R * n_out) throw new ArgumentException("result must hold R x n_out values");
+                HareHip.Check(HareHip.hare_convolve(scenes[0], R, N, ir, x.LongLength, x, n0, n_out, result));
+            }
+
             /// <summary>min(2^32 - 1, floor(10^(dB / 10) * 2^32)): a level of the reduction from decibels (dB at most 0).</summary>
             public static uint DecayLevel(double dB)
             {

@@ -312,6 +312,13 @@ namespace Hare
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_hist_render(IntPtr scene, int K, int n_bins, int B, int channels, [In] ulong[] hist, [In] uint[] weight,
                                                       int frac_bits, int M, int T, [In] double[] taps, ulong seed, [Out] double[] result);
+            // the convolution of rendered responses with a dry signal on the device (include/hare_hip.h, "receivers", "Convolution")
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_convolve_device(IntPtr scene, long R, long N, IntPtr d_ir, long L, IntPtr d_x, long n0, long n_out,
+                                                          IntPtr d_y, IntPtr stream);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_convolve(IntPtr scene, long R, long N, [In] double[] ir, long L, [In] double[] x, long n0, long n_out,
+                                                   [Out] double[] y);
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_receive_batch_reduced(IntPtr scene, int kind, int top_index, long n, [In] hare_ray[] rays, int[] excl1,
                                                                 int[] excl2, int bounces, uint flags, int n_bins, double bin_len, int frac_bits,

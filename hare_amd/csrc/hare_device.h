@@ -717,6 +717,28 @@ struct RenderArgs {
     int32_t sign_words;               // 64-bit words of the tile's sign mask, pad included
 };
 
+// hare_convolve (convolve.hip): R rows of N doubles, each convolved in the time domain with one signal of L doubles, a window of the full
+// convolution written (include/hare_hip.h, "receivers", "Convolution").  A workgroup owns one row and kConvolveTile consecutive outputs,
+// kConvolveRun to a lane; the taps go by in chunks of kConvolveChunk staged in LDS, blocks of kConvolveBlock to a wave (convolve_plan,
+// hist.cpp, sizes the grid and the dynamic LDS)
+constexpr int kConvolveThreads = 256;
+constexpr int kConvolveRun = 8;            // consecutive outputs a lane accumulates
+constexpr int kConvolveTile = 2048;        // outputs per workgroup: kConvolveThreads * kConvolveRun
+constexpr int kConvolveChunk = 256;        // taps staged in LDS at once
+constexpr int kConvolveBlock = 32;         // taps a wave takes in one piece, guarded or not as a whole
+// LDS doubles: the chunk's taps, then the kConvolveTile + kConvolveChunk - 1 signal samples the chunk meets, a pad word after every 8
+constexpr int kConvolveLdsDoubles = kConvolveChunk + 9 * ((kConvolveTile + kConvolveChunk + 7) / 8);
+struct ConvolveArgs {
+    const double* ir;                 // R x N
+    const double* x;                  // L
+    double* y;                        // R x n_out; each word written once
+    int32_t N;                        // 1 .. 2^24
+    int32_t L;                        // 1 .. 2^28
+    int32_t n0;                       // first output sample; n0 + n_out <= N + L - 1 < 2^29
+    int32_t n_out;
+    int32_t tiles;                    // workgroups per row: ceil(n_out / kConvolveTile)
+};
+
 #if defined(__HIPCC__)
 // Every kernel argument as a scalar of its OWN (round 6).  The compiler fetches the 720-byte argument block in tuples of 8 and 16 SGPRs and,
 // short of SGPRs in these kernels, spills and reloads them AS tuples: a block that needs the rays' pointer reloaded sixteen registers to get

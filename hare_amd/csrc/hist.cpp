@@ -1,6 +1,6 @@
 // hist.cpp -- what runs on a receive histogram once it is on the device (include/hare_hip.h, "receivers"): the reduction (hare_hist_reduce
-// / _device; the kernel: reduce.hip), the projection (hare_hist_project / _device; project.hip) and the rendering (hare_hist_render /
-// _device; render.hip).  A call is its own check and its own enqueue; what the calls share is the device prelude (device_call, launch.h),
+// / _device; the kernel: reduce.hip), the projection (hare_hist_project / _device; project.hip), the rendering (hare_hist_render /
+// _device; render.hip) and, on the rendered rows, the convolution with a dry signal (hare_convolve / _device; convolve.hip).  A call is its own check and its own enqueue; what the calls share is the device prelude (device_call, launch.h),
 // the overlap test (spans_overlap, scene.h), one byte count per buffer, used by the check and by the staging, and the staging of the
 // host-buffer calls (staged_run).  reduce_check_spec and reduce_enqueue also serve hare_receive_*_reduced (bounce.cpp).
 // Product code; nothing from oracle/.
@@ -259,6 +259,61 @@ int render_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, i
     return launch(H, s.module->hist_render, (unsigned)K * (unsigned)a.tiles, kRenderThreads, lds, st, args);      // K x n_bins <= 2^27 workgroups
 }
 
+// ---- the convolution (include/hare_hip.h, "receivers", "Convolution"; the kernel: convolve.hip)
+struct ConvolveBytes {
+    size_t ir, x, y;
+};
+
+// everything both convolve calls check before anything runs, in the header's order; buffers device or host
+int convolve_check(const char* who, int64_t R, int64_t N, const void* ir, int64_t L, const void* x, int64_t n0, int64_t n_out, const void* y,
+                   ConvolveBytes& z)
+{
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    if (R < 1 || R > ((int64_t)1 << 20)) return bad("R out of range (1 .. 2^20)");
+    if (N < 1 || N > ((int64_t)1 << 24)) return bad("N out of range (1 .. 2^24)");
+    if (L < 1 || L > ((int64_t)1 << 28)) return bad("L out of range (1 .. 2^28)");
+    if (n0 < 0 || n_out < 1 || n0 > N + L - 1 || n_out > N + L - 1 - n0) return bad("the window is not 0 <= n0, 1 <= n_out, n0 + n_out <= N + L - 1");
+    if (R * n_out > ((int64_t)1 << 28)) return bad("R x n_out exceeds 2^28");
+    if ((unsigned __int128)(R * n_out) * (unsigned __int128)std::min(N, L) > (unsigned __int128)HARE_CONVOLVE_MAX_TERMS)
+        return bad("R x n_out x min(N, L) exceeds the work cap HARE_CONVOLVE_MAX_TERMS: split the output window");
+    if (!ir || !x || !y) return bad("null ir / x / y");
+    z = {(size_t)R * (size_t)N * sizeof(double), (size_t)L * sizeof(double), (size_t)R * (size_t)n_out * sizeof(double)};
+    if (spans_overlap({{y, z.y}, {ir, z.ir}, {x, z.x}}, 1)) return bad("y must not overlap ir or x");
+    return HARE_OK;
+}
+
+// The launch of hare_convolve (convolve.hip): a workgroup per row and tile of kConvolveTile outputs; LDS: a chunk of taps and the padded
+// segment of x it meets, the same for every shape
+unsigned convolve_plan(ConvolveArgs& a)
+{
+    a.tiles = (a.n_out + kConvolveTile - 1) / kConvolveTile;
+    return (unsigned)(sizeof(double) * (size_t)kConvolveLdsDoubles);
+}
+
+int convolve_enqueue(const Scene& s, const HipApi* H, int64_t R, int64_t N, const void* d_ir, int64_t L, const void* d_x, int64_t n0, int64_t n_out,
+                     void* d_y, hipStream_t st)
+{
+    if (!s.module || !s.module->convolve) {
+        set_error("hare_convolve missing from code object");
+        return HARE_E_STATE;
+    }
+    ConvolveArgs a;
+    memset(&a, 0, sizeof a);
+    a.ir = (const double*)d_ir;
+    a.x = (const double*)d_x;
+    a.y = (double*)d_y;
+    a.N = (int32_t)N;
+    a.L = (int32_t)L;
+    a.n0 = (int32_t)n0;
+    a.n_out = (int32_t)n_out;
+    const unsigned lds = convolve_plan(a);
+    void* args[] = {&a};
+    return launch(H, s.module->convolve, (unsigned)R * (unsigned)a.tiles, kConvolveThreads, lds, st, args);      // R x tiles <= 2^20 + 2^17 workgroups
+}
+
 }  // namespace
 
 }  // namespace hare
@@ -344,6 +399,26 @@ int hare_hist_render(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_
         return staged_run(H, parts, [&](void* const* d) {
             return render_enqueue(*s, H, K, n_bins, B, channels, d[1], d[3], frac_bits, M, T, d[2], seed, d[0], nullptr);
         });
+    });
+}
+
+int hare_convolve_device(hare_scene* s, int64_t R, int64_t N, const void* d_ir, int64_t L, const void* d_x, int64_t n0, int64_t n_out, void* d_y,
+                         void* stream)
+{
+    if (!s) return null_scene();
+    ConvolveBytes z;
+    if (int rc = convolve_check("hare_convolve_device", R, N, d_ir, L, d_x, n0, n_out, d_y, z)) return rc;
+    return device_call(*s, [&](const HipApi* H) { return convolve_enqueue(*s, H, R, N, d_ir, L, d_x, n0, n_out, d_y, (hipStream_t)stream); });
+}
+
+int hare_convolve(hare_scene* s, int64_t R, int64_t N, const double* ir, int64_t L, const double* x, int64_t n0, int64_t n_out, double* y)
+{
+    if (!s) return null_scene();
+    ConvolveBytes z;
+    if (int rc = convolve_check("hare_convolve", R, N, ir, L, x, n0, n_out, y, z)) return rc;
+    return device_call(*s, [&](const HipApi* H) {
+        const StagePart parts[] = {{z.y, nullptr, y}, {z.ir, ir, nullptr}, {z.x, x, nullptr}};
+        return staged_run(H, parts, [&](void* const* d) { return convolve_enqueue(*s, H, R, N, d[1], L, d[2], n0, n_out, d[0], nullptr); });
     });
 }
 

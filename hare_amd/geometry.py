@@ -779,6 +779,30 @@ class Spatial_Partition:
         check(lib.hare_hist_render_device(self._h, int(K), int(n_bins), int(B), int(channels), d_hist or None, d_weight or None, int(frac_bits),
                                           int(M), int(T), d_taps or None, int(seed) & 0xFFFFFFFFFFFFFFFF, d_out or None, stream or None))
 
+    def convolve(self, ir, x, n0: int = 0, n_out=None):
+        """hare_convolve: the rows of ir -- float64 [R, N], or [K, C, N] as hist_render returns it (row k * C + ch) -- each convolved on
+        this partition's device with the one signal x, float64 [L] (include/hare_hip.h, "receivers", "Convolution"): FP64 in the time
+        domain, every output one sequential sum over its taps.  The window [n0, n0 + n_out) of the N + L - 1 samples of the full convolution
+        is computed; n_out None: everything from n0 on.  Returns float64 [R, n_out]."""
+        ir, x = np.ascontiguousarray(ir, np.float64), np.ascontiguousarray(x, np.float64)
+        if ir.ndim not in (2, 3) or ir.size == 0:
+            raise ValueError("ir must be float64 [R, N] or [K, C, N], not empty")
+        if x.ndim != 1 or x.size == 0:
+            raise ValueError("x must be float64 [L], not empty")
+        ir = ir.reshape(-1, ir.shape[-1])
+        R, N, L = ir.shape[0], ir.shape[1], x.shape[0]
+        n0 = int(n0)
+        n_out = N + L - 1 - n0 if n_out is None else int(n_out)
+        y = np.zeros((R, max(0, n_out)), np.float64)
+        check(lib.hare_convolve(self._h, R, N, ptr(ir), L, ptr(x), n0, n_out, ptr(y)))
+        return y
+
+    def convolve_device(self, R: int, N: int, d_ir: int, L: int, d_x: int, n0: int, n_out: int, d_y: int, stream: int = 0):
+        """hare_convolve_device on raw device addresses + a hipStream_t: d_ir (R x N float64, e.g. hist_render_device's d_out with
+        R = K x channels), d_x (L float64), d_y (R x n_out float64) written.  Stream-ordered: no allocation, no free, no wait."""
+        check(lib.hare_convolve_device(self._h, int(R), int(N), d_ir or None, int(L), d_x or None, int(n0), int(n_out), d_y or None,
+                                       stream or None))
+
     @staticmethod
     def direct_work_bytes(K: int) -> int:
         """Bytes of direct_device's d_work for K receivers: HARE_DIRECT_WORK_BYTES(K)."""

@@ -950,6 +950,29 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * histogram of their own with the _device calls and renders only the rest here; rendering impulses is not part of this call.  The
  * sequential order of y, p and z is part of the definition: parallelism is over (k, b, n) and (k, b, i), never inside a sum.
  *
+ * Convolution (hare_convolve_device, hare_convolve).  What is listened to is not the response but a sound in the room: a dry signal
+ * convolved with the response of every receiver channel.  This is that last step, in the time domain, on the device, so that the chain stays
+ * a pure function of its inputs to the end.  Inputs: ir, R rows of N doubles -- exactly the rows "Rendering" writes (R = K * channels,
+ * N = n_bins * M, row r = k * channels + ch), though the call does not care where they came from; x, ONE signal of L doubles shared by all
+ * rows; and an output window [n0, n0 + n_out) of the N + L - 1 samples of the full convolution.  Output: y[r * n_out + (n - n0)], doubles,
+ * every word written once.  All arithmetic is FP64 without contraction -- the product is rounded, then the add -- in exactly this order:
+ *
+ *   t_lo = max(0, n - (L - 1));   t_hi = min(N - 1, n)
+ *   acc = +0.0;   for t = t_lo .. t_hi ascending:   acc = acc + ir[r*N + t] * x[n - t]
+ *   y(r, n) = acc
+ *
+ * Terms outside [t_lo, t_hi] are SKIPPED, not formed against a zero: a value of ir or x that is not finite reaches exactly the outputs
+ * whose range holds it.  Parallelism is over (r, n), never inside a sum, so a split of a job over output windows, or of its rows over
+ * several calls or GPUs, is byte-identical to the one call; there is no sharded variant and no mixing between rows (no decode matrix).
+ * Infinities, signed zeros and denormals follow IEEE 754 to the bit; the accumulator starts at +0.0 and is therefore never -0.0.  A NaN
+ * output is "some NaN": its sign and payload are not defined (the one place where a comparison with a host is not byte for byte).  An FFT
+ * would take fewer operations and has no statable order of its sums: not offered.
+ * Limits (HARE_E_INVALID): 1 <= R <= 2^20, 1 <= N <= 2^24, 1 <= L <= 2^28; 0 <= n0, 1 <= n_out, n0 + n_out <= N + L - 1;
+ * R * n_out <= 2^28 (the render call's output cap); and R * n_out * min(N, L) <= HARE_CONVOLVE_MAX_TERMS, an upper bound of the terms of
+ * one call: the devices are shared and one launch is not to run for many seconds.  The cap, 2^44, is the largest power of two whose launch
+ * stays under two seconds at the rate measured on an MI355X, 1.39e13 terms per second: 1.26 s ("Convolution"); a larger job
+ * is cut into output windows by the caller.
+ *
  * Setters: single-caller, like the build calls.  They validate, keep a host copy, and upload it when a device is present (as a build
  * pushes its partition; on a GPU-less host the copy goes up with the first receive call).  No receive call allocates for them.
  *   hare_scene_set_receivers    replaces the receivers: centers K x 3, radii K.  HARE_E_INVALID for K outside 1..256, a non-finite
@@ -1112,6 +1135,19 @@ HARE_API int hare_hist_render_device(hare_scene *s, int32_t K, int32_t n_bins, i
 HARE_API int hare_hist_render(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t *hist,
                               const uint32_t *weight /* nullable */, int32_t frac_bits, int32_t M, int32_t T, const double *taps,
                               uint64_t seed, double *out);
+/* The convolution of rows with a signal ("receivers", "Convolution" above) on DEVICE buffers: one launch, stream-ordered like
+ * hare_hist_render_device -- no allocation, no free, no wait.  d_ir (R x N doubles), d_x (L doubles); d_y (R x n_out doubles) is WRITTEN,
+ * every word once.  Behind hare_hist_render_device on the same stream, with d_ir its d_out, R = K x channels and N = n_bins x M, it convolves
+ * the responses that call rendered.  Checked before anything runs (HARE_E_INVALID), in this order: 1 <= R <= 2^20, 1 <= N <= 2^24,
+ * 1 <= L <= 2^28; n0 >= 0, n_out >= 1, n0 + n_out <= N + L - 1; R x n_out <= 2^28; R x n_out x min(N, L) <= HARE_CONVOLVE_MAX_TERMS; null
+ * buffers; y overlapping ir or x.  Then HARE_E_NODEVICE, then HARE_E_STATE (the kernel is missing from the code object).  The scene names
+ * the device; its geometry is not read. */
+#define HARE_CONVOLVE_MAX_TERMS ((int64_t)1 << 44)
+HARE_API int hare_convolve_device(hare_scene *s, int64_t R, int64_t N, const void *d_ir, int64_t L, const void *d_x, int64_t n0,
+                                  int64_t n_out, void *d_y, void *stream);
+/* The same from host buffers: one allocation, upload, convolve, download, one synchronisation. */
+HARE_API int hare_convolve(hare_scene *s, int64_t R, int64_t N, const double *ir, int64_t L, const double *x, int64_t n0, int64_t n_out,
+                           double *y);
 /* hare_receive_batch / hare_receive_source with `hist` replaced by the reduction's arguments: the loop runs as in the parent call, the
  * histogram stays on the device, the reduction is enqueued behind the last cast on the same stream, and sums, crossings, detections,
  * state and counters come down -- never the histogram.  K and B are the scene's; channels is 4 with HARE_RECEIVE_DIRECTIONAL (9, 16 with the order flags), else 1.
