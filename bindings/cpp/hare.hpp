@@ -395,6 +395,26 @@ public:
     {
         check(hare_convolve_device(scene_, R, N, d_ir, L, d_x, n0, n_out, d_y, stream));
     }
+    // hare_decode (include/hare_hip.h, "receivers", "Decoding"): the K x C rows of N doubles in in -- the rows HistRender writes, C =
+    // channels -- decoded through the O x C filters of T doubles in h (h[(o*C + c)*T + t]): output (k, o) sums over all c the row (k, c)
+    // filtered by h[o, c].  The samples n0 .. n0 + n_out - 1 of the N + T - 1 into out, K x O x n_out.  n_out < 0: everything from n0 on
+    void Decode(const std::vector<double>& in, int64_t K, int64_t C, const std::vector<double>& h, int64_t O, std::vector<double>& out, int64_t n0 = 0,
+                int64_t n_out = -1)
+    {
+        if (K < 1 || C < 1 || in.empty() || in.size() % (size_t)(K * C) != 0) throw std::invalid_argument("Decode: in must hold K x C x N values");
+        if (O < 1 || h.empty() || h.size() % (size_t)(O * C) != 0) throw std::invalid_argument("Decode: h must hold O x C x T values");
+        const int64_t N = (int64_t)(in.size() / (size_t)(K * C)), T = (int64_t)(h.size() / (size_t)(O * C));
+        if (n_out < 0) n_out = N + T - 1 - n0;
+        if (n0 < 0 || n_out < 1 || n0 + n_out > N + T - 1) throw std::invalid_argument("Decode: the window must lie within the N + T - 1 samples");
+        out.assign((size_t)(K * O) * (size_t)n_out, 0.0);
+        check(hare_decode(scene_, K, C, N, in.data(), O, T, h.data(), n0, n_out, out.data()));
+    }
+    // hare_decode_device on device pointers and a hipStream_t: d_y (K x O x n_out doubles) written.  Stream-ordered.
+    void DecodeDevice(int64_t K, int64_t C, int64_t N, const void* d_in, int64_t O, int64_t T, const void* d_h, int64_t n0, int64_t n_out, void* d_y,
+                      void* stream = nullptr)
+    {
+        check(hare_decode_device(scene_, K, C, N, d_in, O, T, d_h, n0, n_out, d_y, stream));
+    }
     // Receive / ReceiveSource with the histogram reduced on the device (hare_receive_batch_reduced / hare_receive_source_reduced): sums and
     // cross as HistReduce gives them on the histogram Receive returns; the histogram itself never comes down
     uint64_t ReceiveReduced(const std::vector<hare_ray>& rays, int top_index, int bounces, int n_bins, double bin_len, int frac_bits,

@@ -444,6 +444,19 @@ namespace Hare
                 HareHip.Check(HareHip.hare_convolve(scenes[0], R, N, ir, x.LongLength, x, n0, n_out, result));
             }
 
+            /// <summary>hare_decode: the K x C rows of N doubles in input (the rows HistRender writes: C = channels) decoded on the first scene's
+            /// device through the O x C filters of T doubles in h (h[(o*C + c)*T + t]), FP64 in the time domain, every output one sequential sum
+            /// over the channels and, within a channel, over the taps (include/hare_hip.h, "Decoding"); the samples n0 .. n0 + n_out - 1 of the
+            /// N + T - 1 into result, K x O x n_out doubles.</summary>
+            public void Decode(double[] input, long K, long C, long N, double[] h, long O, long T, long n0, long n_out, double[] result)
+            {
+                if (K < 1 || C < 1 || N < 1 || input == null || input.LongLength < K * C * N) throw new ArgumentException("input must hold K x C x N values");
+                if (O < 1 || T < 1 || h == null || h.LongLength < O * C * T) throw new ArgumentException("h must hold O x C x T values");
+                if (n0 < 0 || n_out < 1 || n0 + n_out > N + T - 1) throw new ArgumentException("the window must lie within the N + T - 1 samples");
+                if (result == null || result.LongLength < K * O * n_out) throw new ArgumentException("result must hold K x O x n_out values");
+                HareHip.Check(HareHip.hare_decode(scenes[0], K, C, N, input, O, T, h, n0, n_out, result));
+            }
+
             /// <summary>min(2^32 - 1, floor(10^(dB / 10) * 2^32)): a level of the reduction from decibels (dB at most 0).</summary>
             public static uint DecayLevel(double dB)
             {

@@ -319,6 +319,13 @@ namespace Hare
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_convolve(IntPtr scene, long R, long N, [In] double[] ir, long L, [In] double[] x, long n0, long n_out,
                                                    [Out] double[] y);
+            // the decoding of rendered responses through a matrix of FIR filters on the device (include/hare_hip.h, "receivers", "Decoding")
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_decode_device(IntPtr scene, long K, long C, long N, IntPtr d_in, long O, long T, IntPtr d_h, long n0,
+                                                        long n_out, IntPtr d_y, IntPtr stream);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_decode(IntPtr scene, long K, long C, long N, [In] double[] input, long O, long T, [In] double[] h, long n0,
+                                                 long n_out, [Out] double[] y);
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_receive_batch_reduced(IntPtr scene, int kind, int top_index, long n, [In] hare_ray[] rays, int[] excl1,
                                                                 int[] excl2, int bounces, uint flags, int n_bins, double bin_len, int frac_bits,

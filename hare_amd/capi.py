@@ -27,6 +27,7 @@ RECEIVE_IMAGE2 = 65536              # the same calls, only with RECEIVE_IMAGE: s
 RECEIVE_ORDER2 = 131072             # wherever RECEIVE_DIRECTIONAL is accepted, only with it: nine channels per histogram word ("Higher orders")
 RECEIVE_ORDER3 = 1048576            # the same, sixteen channels; not together with RECEIVE_ORDER2
 ORDER_CHANNELS = {1: 4, 2: 9, 3: 16}        # channels of a directional histogram by ambisonic order
+DECODE_MAX_TERMS = 1 << 42          # HARE_DECODE_MAX_TERMS: hare_decode*'s bound on K x O x n_out x C x min(N, T) (include/hare_hip.h, "Decoding")
 
 
 def channel_flags(directional, order: int = 1) -> int:
@@ -142,6 +143,8 @@ SYMBOLS = {
     "hare_hist_render": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, C.c_uint64, _vp]),
     "hare_convolve_device": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "hare_convolve": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp]),
+    "hare_decode_device": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "hare_decode": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "hare_receive_batch_reduced": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _i32, _u32, _i32, C.c_double, _i32, _vp, _vp,
                                              _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "hare_receive_source_reduced": (C.c_int, [_vp, _i32, _i32, _i64, _i64, _i32, _u32, _i32, C.c_double, _i32, _vp,

@@ -739,6 +739,29 @@ struct ConvolveArgs {
     int32_t tiles;                    // workgroups per row: ceil(n_out / kConvolveTile)
 };
 
+// hare_decode (decode.hip): K x C rows of N doubles decoded to K x O rows through O x C filters of T doubles, a window of the N + T - 1
+// samples written (include/hare_hip.h, "receivers", "Decoding").  The convolution's tile: a workgroup owns one (k, o) and kDecodeTile
+// consecutive outputs, kDecodeRun to a lane; per input channel the filter's taps go by in chunks of kDecodeChunk staged in LDS with the padded
+// samples of in[k, c] they meet, blocks of kDecodeBlock to a wave (decode_plan, hist.cpp, sizes the grid and the dynamic LDS)
+constexpr int kDecodeThreads = kConvolveThreads;
+constexpr int kDecodeRun = kConvolveRun;
+constexpr int kDecodeTile = kConvolveTile;
+constexpr int kDecodeChunk = kConvolveChunk;
+constexpr int kDecodeBlock = kConvolveBlock;
+constexpr int kDecodeLdsDoubles = kConvolveLdsDoubles;          // the chunk's taps of h[o, c], then the padded samples of in[k, c]
+struct DecodeArgs {
+    const double* in;                 // K x C x N
+    const double* h;                  // O x C x T
+    double* y;                        // K x O x n_out; each word written once
+    int32_t C;                        // 1 .. 64
+    int32_t O;                        // 1 .. 64
+    int32_t N;                        // 1 .. 2^24
+    int32_t T;                        // 1 .. 2^16
+    int32_t n0;                       // first output sample; n0 + n_out <= N + T - 1 < 2^25
+    int32_t n_out;
+    int32_t tiles;                    // workgroups per (k, o): ceil(n_out / kDecodeTile)
+};
+
 #if defined(__HIPCC__)
 // Every kernel argument as a scalar of its OWN (round 6).  The compiler fetches the 720-byte argument block in tuples of 8 and 16 SGPRs and,
 // short of SGPRs in these kernels, spills and reloads them AS tuples: a block that needs the rays' pointer reloaded sixteen registers to get

@@ -1,6 +1,7 @@
 // hist.cpp -- what runs on a receive histogram once it is on the device (include/hare_hip.h, "receivers"): the reduction (hare_hist_reduce
 // / _device; the kernel: reduce.hip), the projection (hare_hist_project / _device; project.hip), the rendering (hare_hist_render /
-// _device; render.hip) and, on the rendered rows, the convolution with a dry signal (hare_convolve / _device; convolve.hip).  A call is its own check and its own enqueue; what the calls share is the device prelude (device_call, launch.h),
+// _device; render.hip) and, on the rendered rows, the convolution with a dry signal (hare_convolve / _device; convolve.hip) and the
+// decoding through a matrix of FIR filters (hare_decode / _device; decode.hip).  A call is its own check and its own enqueue; what the calls share is the device prelude (device_call, launch.h),
 // the overlap test (spans_overlap, scene.h), one byte count per buffer, used by the check and by the staging, and the staging of the
 // host-buffer calls (staged_run).  reduce_check_spec and reduce_enqueue also serve hare_receive_*_reduced (bounce.cpp).
 // Product code; nothing from oracle/.
@@ -314,6 +315,66 @@ int convolve_enqueue(const Scene& s, const HipApi* H, int64_t R, int64_t N, cons
     return launch(H, s.module->convolve, (unsigned)R * (unsigned)a.tiles, kConvolveThreads, lds, st, args);      // R x tiles <= 2^20 + 2^17 workgroups
 }
 
+// ---- the decoding (include/hare_hip.h, "receivers", "Decoding"; the kernel: decode.hip)
+struct DecodeBytes {
+    size_t in, h, y;
+};
+
+// everything both decode calls check before anything runs, in the header's order; buffers device or host
+int decode_check(const char* who, int64_t K, int64_t C, int64_t N, const void* in, int64_t O, int64_t T, const void* h, int64_t n0, int64_t n_out,
+                 const void* y, DecodeBytes& z)
+{
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    if (K < 1 || K > 65536) return bad("K out of range (1 .. 65536)");
+    if (C < 1 || C > 64) return bad("C out of range (1 .. 64)");
+    if (O < 1 || O > 64) return bad("O out of range (1 .. 64)");
+    if (N < 1 || N > ((int64_t)1 << 24)) return bad("N out of range (1 .. 2^24)");
+    if (T < 1 || T > ((int64_t)1 << 16)) return bad("T out of range (1 .. 2^16)");
+    if (n0 < 0 || n_out < 1 || n0 > N + T - 1 || n_out > N + T - 1 - n0) return bad("the window is not 0 <= n0, 1 <= n_out, n0 + n_out <= N + T - 1");
+    if (K * C * N > ((int64_t)1 << 28)) return bad("K x C x N exceeds 2^28");
+    if (K * O * n_out > ((int64_t)1 << 28)) return bad("K x O x n_out exceeds 2^28");
+    if ((unsigned __int128)(K * O * n_out) * (unsigned __int128)(C * std::min(N, T)) > (unsigned __int128)HARE_DECODE_MAX_TERMS)
+        return bad("K x O x n_out x C x min(N, T) exceeds the work cap HARE_DECODE_MAX_TERMS: split the output window");
+    if (!in || !h || !y) return bad("null in / h / y");
+    z = {(size_t)(K * C * N) * sizeof(double), (size_t)(O * C * T) * sizeof(double), (size_t)(K * O * n_out) * sizeof(double)};
+    if (spans_overlap({{y, z.y}, {in, z.in}, {h, z.h}}, 1)) return bad("y must not overlap in or h");
+    return HARE_OK;
+}
+
+// The launch of hare_decode (decode.hip): a workgroup per (k, o) and tile of kDecodeTile outputs; LDS: a chunk of a filter's taps and the
+// padded segment of in[k, c] it meets, the same for every shape
+unsigned decode_plan(DecodeArgs& a)
+{
+    a.tiles = (a.n_out + kDecodeTile - 1) / kDecodeTile;
+    return (unsigned)(sizeof(double) * (size_t)kDecodeLdsDoubles);
+}
+
+int decode_enqueue(const Scene& s, const HipApi* H, int64_t K, int64_t C, int64_t N, const void* d_in, int64_t O, int64_t T, const void* d_h, int64_t n0,
+                   int64_t n_out, void* d_y, hipStream_t st)
+{
+    if (!s.module || !s.module->decode) {
+        set_error("hare_decode missing from code object");
+        return HARE_E_STATE;
+    }
+    DecodeArgs a;
+    memset(&a, 0, sizeof a);
+    a.in = (const double*)d_in;
+    a.h = (const double*)d_h;
+    a.y = (double*)d_y;
+    a.C = (int32_t)C;
+    a.O = (int32_t)O;
+    a.N = (int32_t)N;
+    a.T = (int32_t)T;
+    a.n0 = (int32_t)n0;
+    a.n_out = (int32_t)n_out;
+    const unsigned lds = decode_plan(a);
+    void* args[] = {&a};
+    return launch(H, s.module->decode, (unsigned)(K * O) * (unsigned)a.tiles, kDecodeThreads, lds, st, args);      // K x O x tiles <= 2^22 + 2^17 workgroups
+}
+
 }  // namespace
 
 }  // namespace hare
@@ -419,6 +480,27 @@ int hare_convolve(hare_scene* s, int64_t R, int64_t N, const double* ir, int64_t
     return device_call(*s, [&](const HipApi* H) {
         const StagePart parts[] = {{z.y, nullptr, y}, {z.ir, ir, nullptr}, {z.x, x, nullptr}};
         return staged_run(H, parts, [&](void* const* d) { return convolve_enqueue(*s, H, R, N, d[1], L, d[2], n0, n_out, d[0], nullptr); });
+    });
+}
+
+int hare_decode_device(hare_scene* s, int64_t K, int64_t C, int64_t N, const void* d_in, int64_t O, int64_t T, const void* d_h, int64_t n0,
+                       int64_t n_out, void* d_y, void* stream)
+{
+    if (!s) return null_scene();
+    DecodeBytes z;
+    if (int rc = decode_check("hare_decode_device", K, C, N, d_in, O, T, d_h, n0, n_out, d_y, z)) return rc;
+    return device_call(*s, [&](const HipApi* H) { return decode_enqueue(*s, H, K, C, N, d_in, O, T, d_h, n0, n_out, d_y, (hipStream_t)stream); });
+}
+
+int hare_decode(hare_scene* s, int64_t K, int64_t C, int64_t N, const double* in, int64_t O, int64_t T, const double* h, int64_t n0, int64_t n_out,
+                double* y)
+{
+    if (!s) return null_scene();
+    DecodeBytes z;
+    if (int rc = decode_check("hare_decode", K, C, N, in, O, T, h, n0, n_out, y, z)) return rc;
+    return device_call(*s, [&](const HipApi* H) {
+        const StagePart parts[] = {{z.y, nullptr, y}, {z.in, in, nullptr}, {z.h, h, nullptr}};
+        return staged_run(H, parts, [&](void* const* d) { return decode_enqueue(*s, H, K, C, N, d[1], O, T, d[2], n0, n_out, d[0], nullptr); });
     });
 }
 

@@ -803,6 +803,32 @@ class Spatial_Partition:
         check(lib.hare_convolve_device(self._h, int(R), int(N), d_ir or None, int(L), d_x or None, int(n0), int(n_out), d_y or None,
                                        stream or None))
 
+    def decode(self, in_, h, n0: int = 0, n_out=None):
+        """hare_decode: the rows of in_ -- float64 [K, C, N], as hist_render returns it: ambisonic channels per receiver -- decoded on this
+        partition's device through the matrix of FIR filters h, float64 [O, C, T] (include/hare_hip.h, "receivers", "Decoding"): output
+        (k, o) is the sum over all channels c of in_[k, c] filtered by h[o, c], FP64 in the time domain, every output one sequential sum
+        over c and, within c, over the taps.  The window [n0, n0 + n_out) of the N + T - 1 samples is computed; n_out None: everything
+        from n0 on.  Returns float64 [K, O, n_out].  hare_amd.decoders builds h for loudspeakers and for a caller's HRIR set."""
+        in_, h = np.ascontiguousarray(in_, np.float64), np.ascontiguousarray(h, np.float64)
+        if in_.ndim != 3 or in_.size == 0:
+            raise ValueError("in_ must be float64 [K, C, N], not empty")
+        if h.ndim != 3 or h.size == 0:
+            raise ValueError("h must be float64 [O, C, T], not empty")
+        if h.shape[1] != in_.shape[1]:
+            raise ValueError("h [O, C, T] must have the C of in_ [K, C, N]")
+        (K, Cn, N), (O, _, T) = in_.shape, h.shape
+        n0 = int(n0)
+        n_out = N + T - 1 - n0 if n_out is None else int(n_out)
+        y = np.zeros((K, O, max(0, n_out)), np.float64)
+        check(lib.hare_decode(self._h, K, Cn, N, ptr(in_), O, T, ptr(h), n0, n_out, ptr(y)))
+        return y
+
+    def decode_device(self, K: int, C: int, N: int, d_in: int, O: int, T: int, d_h: int, n0: int, n_out: int, d_y: int, stream: int = 0):
+        """hare_decode_device on raw device addresses + a hipStream_t: d_in (K x C x N float64, e.g. hist_render_device's d_out with
+        C = channels), d_h (O x C x T float64), d_y (K x O x n_out float64) written.  Stream-ordered: no allocation, no free, no wait."""
+        check(lib.hare_decode_device(self._h, int(K), int(C), int(N), d_in or None, int(O), int(T), d_h or None, int(n0), int(n_out),
+                                     d_y or None, stream or None))
+
     @staticmethod
     def direct_work_bytes(K: int) -> int:
         """Bytes of direct_device's d_work for K receivers: HARE_DIRECT_WORK_BYTES(K)."""

@@ -963,7 +963,8 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  *
  * Terms outside [t_lo, t_hi] are SKIPPED, not formed against a zero: a value of ir or x that is not finite reaches exactly the outputs
  * whose range holds it.  Parallelism is over (r, n), never inside a sum, so a split of a job over output windows, or of its rows over
- * several calls or GPUs, is byte-identical to the one call; there is no sharded variant and no mixing between rows (no decode matrix).
+ * several calls or GPUs, is byte-identical to the one call; there is no sharded variant and no mixing between rows (a decode matrix is another call's
+ * business: "Decoding" below).
  * Infinities, signed zeros and denormals follow IEEE 754 to the bit; the accumulator starts at +0.0 and is therefore never -0.0.  A NaN
  * output is "some NaN": its sign and payload are not defined (the one place where a comparison with a host is not byte for byte).  An FFT
  * would take fewer operations and has no statable order of its sums: not offered.
@@ -972,6 +973,34 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * one call: the devices are shared and one launch is not to run for many seconds.  The cap, 2^44, is the largest power of two whose launch
  * stays under two seconds at the rate measured on an MI355X, 1.39e13 terms per second: 1.26 s ("Convolution"); a larger job
  * is cut into output windows by the caller.
+ *
+ * Decoding (hare_decode_device, hare_decode).  The rows of a directional receiver are ambisonic channels -- W X Y Z, then ACN 4..15 in SN3D
+ * -- and nobody plays those back: they are decoded to ears or to loudspeakers, every output channel a sum over ALL input channels of that
+ * channel filtered by a short FIR of its own (HRIR-derived for binaural, one gain each for a loudspeaker matrix, a few taps for a virtual
+ * microphone).  This is the mixing between rows that "Convolution" leaves out.  Inputs: in, K x C rows of N doubles, row k * C + c --
+ * exactly the rows "Rendering" writes (C = channels, N = n_bins * M), or equally the rows "Convolution" writes with a full window; h,
+ * O x C filters of T doubles, h[(o*C + c)*T + t], shared by all receivers; and an output window [n0, n0 + n_out) of the N + T - 1 samples.
+ * Output: y[(k*O + o)*n_out + (n - n0)], doubles, every word written once.  All arithmetic is FP64 without contraction -- the product is
+ * rounded, then the add -- in exactly this order:
+ *
+ *   t_lo = max(0, n - (N - 1));   t_hi = min(T - 1, n)
+ *   acc = +0.0
+ *   for c = 0 .. C-1 ascending:   for t = t_lo .. t_hi ascending:   acc = acc + h[(o*C + c)*T + t] * in[(k*C + c)*N + (n - t)]
+ *   y(k, o, n) = acc
+ *
+ * ONE accumulator runs through all channels: this is neither C convolutions added afterwards nor a sum with t outside and c inside.  The
+ * rules of "Convolution" hold: terms outside [t_lo, t_hi] are SKIPPED, never formed against a zero, so a value of in or h that is not
+ * finite reaches exactly the outputs whose range holds it; the accumulator starts at +0.0 and is never -0.0; a NaN output is "some NaN";
+ * parallelism is over (k, o, n), never inside a sum, so a job cut over output windows, over outputs o (rows of h) or over receivers k (rows
+ * of in) is the one call byte for byte, and there is no sharded variant.  With C = O = 1 the call IS hare_convolve with ir = h (R = 1,
+ * its N this T) and x = in[k] (its L this N), bit for bit.  Helpers that build h (a sampling decoder, virtual
+ * loudspeakers through a caller's HRIR set) are host code of the bindings (hare_amd/decoders.py); no HRIR data is shipped.
+ * Limits (HARE_E_INVALID): 1 <= K <= 65 536, 1 <= C <= 64, 1 <= O <= 64; 1 <= N <= 2^24, 1 <= T <= 2^16; 0 <= n0, 1 <= n_out,
+ * n0 + n_out <= N + T - 1; K * C * N <= 2^28 and K * O * n_out <= 2^28; and K * O * n_out * C * min(N, T) <= HARE_DECODE_MAX_TERMS, an
+ * upper bound of the terms of one call, a constant of its own: the instruction mix is the convolution's, and so is the reason for the cap.
+ * The cap, 2^42, is the largest power of two whose launch stays under two seconds at the rate measured on an MI355X for 16 third-order
+ * receivers decoded to two ears through 512 taps, 4.31e12 terms per second: 1.02 s ("Decoding"); a larger job is cut into
+ * output windows by the caller.
  *
  * Setters: single-caller, like the build calls.  They validate, keep a host copy, and upload it when a device is present (as a build
  * pushes its partition; on a GPU-less host the copy goes up with the first receive call).  No receive call allocates for them.
@@ -1148,6 +1177,20 @@ HARE_API int hare_convolve_device(hare_scene *s, int64_t R, int64_t N, const voi
 /* The same from host buffers: one allocation, upload, convolve, download, one synchronisation. */
 HARE_API int hare_convolve(hare_scene *s, int64_t R, int64_t N, const double *ir, int64_t L, const double *x, int64_t n0, int64_t n_out,
                            double *y);
+/* The decoding of rows through a matrix of FIR filters ("receivers", "Decoding" above) on DEVICE buffers: one launch, stream-ordered like
+ * hare_convolve_device -- no allocation, no free, no wait.  d_in (K x C x N doubles), d_h (O x C x T doubles); d_y (K x O x n_out doubles)
+ * is WRITTEN, every word once.  Behind hare_hist_render_device on the same stream, with d_in its d_out, C = channels and N = n_bins x M, it
+ * decodes the responses that call rendered; hare_convolve_device may follow on d_y with R = K x O.  Checked before anything runs
+ * (HARE_E_INVALID), in this order: 1 <= K <= 65 536, 1 <= C <= 64, 1 <= O <= 64; 1 <= N <= 2^24, 1 <= T <= 2^16; n0 >= 0, n_out >= 1,
+ * n0 + n_out <= N + T - 1; K x C x N <= 2^28 and K x O x n_out <= 2^28; K x O x n_out x C x min(N, T) <= HARE_DECODE_MAX_TERMS; null
+ * buffers; y overlapping in or h.  Then HARE_E_NODEVICE, then HARE_E_STATE (the kernel is missing from the code object).  The scene names
+ * the device; its geometry is not read. */
+#define HARE_DECODE_MAX_TERMS ((int64_t)1 << 42)
+HARE_API int hare_decode_device(hare_scene *s, int64_t K, int64_t C, int64_t N, const void *d_in, int64_t O, int64_t T, const void *d_h,
+                                int64_t n0, int64_t n_out, void *d_y, void *stream);
+/* The same from host buffers: one allocation, upload, decode, download, one synchronisation. */
+HARE_API int hare_decode(hare_scene *s, int64_t K, int64_t C, int64_t N, const double *in, int64_t O, int64_t T, const double *h, int64_t n0,
+                         int64_t n_out, double *y);
 /* hare_receive_batch / hare_receive_source with `hist` replaced by the reduction's arguments: the loop runs as in the parent call, the
  * histogram stays on the device, the reduction is enqueued behind the last cast on the same stream, and sums, crossings, detections,
  * state and counters come down -- never the histogram.  K and B are the scene's; channels is 4 with HARE_RECEIVE_DIRECTIONAL (9, 16 with the order flags), else 1.
