@@ -377,6 +377,48 @@ public:
     {
         check(hare_hist_render_device(scene_, K, n_bins, B, channels, d_hist, d_weight, frac_bits, M, T, d_taps, seed, d_out, stream));
     }
+    // hare_hist_impulses (include/hare_hip.h, "receivers", "Impulses"): a PER-SAMPLE histogram (SourcePaths with bin_len = c / fs;
+    // K x n_bins x B x channels) turned into pressure rows, every non-empty (bin, band) an impulse of amplitude sqrt(energy) through that
+    // band's row of taps (B x T).  The samples n0 .. n0 + n_out - 1 of the n_bins + T - 1; n_out < 0: everything from n0 on.  add false:
+    // out becomes K x channels x n_out.  add true: out holds K x channels rows of equal length >= n_out (e.g. what HistRender wrote) and the
+    // impulses are added onto the first n_out samples of each
+    void HistImpulses(const std::vector<uint64_t>& hist, int K, int n_bins, int B, int channels, int frac_bits, const std::vector<double>& taps,
+                      std::vector<double>& out, int64_t n0 = 0, int64_t n_out = -1, bool add = false, const std::vector<uint32_t>& weight = {})
+    {
+        if (K < 1 || n_bins < 1 || B < 1 || channels < 1 || hist.size() != (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels)
+            throw std::invalid_argument("HistImpulses: hist must hold K x n_bins x B x channels values");
+        if (taps.empty() || taps.size() % (size_t)B != 0) throw std::invalid_argument("HistImpulses: taps must hold B x T values");
+        if (!weight.empty() && weight.size() != (size_t)n_bins * (size_t)B) throw std::invalid_argument("HistImpulses: weight must hold n_bins x B values (or none)");
+        const int32_t T = (int32_t)(taps.size() / (size_t)B);
+        if (n_out < 0) n_out = (int64_t)n_bins + T - 1 - n0;
+        if (n0 < 0 || n_out < 1 || n0 + n_out > (int64_t)n_bins + T - 1) throw std::invalid_argument("HistImpulses: the window must lie within the n_bins + T - 1 samples");
+        const size_t rows = (size_t)K * (size_t)channels;
+        if (!add) out.assign(rows * (size_t)n_out, 0.0);
+        if (out.empty() || out.size() % rows != 0 || out.size() / rows < (size_t)n_out)
+            throw std::invalid_argument("HistImpulses: out must hold K x channels rows of at least n_out values");
+        check(hare_hist_impulses(scene_, K, n_bins, B, channels, hist.data(), weight.empty() ? nullptr : weight.data(), frac_bits, T, taps.data(), n0, n_out,
+                                 (int64_t)(out.size() / rows), add ? 1 : 0, out.data()));
+    }
+    // hare_hist_impulses_device on device pointers and a hipStream_t: the first n_out doubles of every row of d_out (K x channels x out_stride)
+    // written, or added onto.  Stream-ordered.
+    void HistImpulsesDevice(int K, int n_bins, int B, int channels, const void* d_hist, int frac_bits, int T, const void* d_taps, int64_t n0, int64_t n_out,
+                            int64_t out_stride, bool add, void* d_out, const void* d_weight = nullptr, void* stream = nullptr)
+    {
+        check(hare_hist_impulses_device(scene_, K, n_bins, B, channels, d_hist, d_weight, frac_bits, T, d_taps, n0, n_out, out_stride, add ? 1 : 0, d_out, stream));
+    }
+    // hare_source_paths: the direct sound (direct) and the image sources of the first (image) and second order (image2, only with image) of the
+    // scene's source alone, each standing for n_weight rays, into a zeroed histogram: K x n_bins x B (x 4, 9, 16 with directional and order)
+    void SourcePaths(int top_index, int64_t n_weight, int n_bins, double bin_len, int frac_bits, std::vector<uint64_t>& hist, std::vector<uint64_t>& detections,
+                     int K, int B, bool directional = false, int order = 1, bool direct = true, bool image = true, bool image2 = true)
+    {
+        const uint32_t flags = (directional ? HARE_RECEIVE_DIRECTIONAL | (order == 2 ? HARE_RECEIVE_ORDER2 : order == 3 ? HARE_RECEIVE_ORDER3 : 0u) : 0u) |
+                               (direct ? HARE_RECEIVE_DIRECT : 0u) | (image ? HARE_RECEIVE_IMAGE : 0u) | (image2 ? HARE_RECEIVE_IMAGE2 : 0u);
+        const size_t channels = directional ? (order == 3 ? 16 : order == 2 ? 9 : 4) : 1;
+        if (K < 1 || B < 1 || n_bins < 1) throw std::invalid_argument("SourcePaths: K, B and n_bins must be >= 1");
+        hist.assign((size_t)K * (size_t)n_bins * (size_t)B * channels, 0);
+        detections.assign((size_t)K * 2, 0);
+        check(hare_source_paths(scene_, kind_, top_index, n_weight, flags, n_bins, bin_len, frac_bits, hist.data(), detections.data()));
+    }
     // hare_convolve (include/hare_hip.h, "receivers", "Convolution"): the R rows of N doubles in ir -- the rows HistRender writes, R = K x
     // channels -- each convolved in the time domain with the one signal x; the samples n0 .. n0 + n_out - 1 of the N + L - 1 of the full
     // convolution into out, R x n_out.  n_out < 0: everything from n0 on

@@ -432,6 +432,30 @@ namespace Hare
                 HareHip.Check(HareHip.hare_hist_render(scenes[0], K, n_bins, B, channels, hist, weight, frac_bits, M, taps.Length / B, taps, seed, result));
             }
 
+            /// <summary>hare_hist_impulses on a per-sample histogram (SourcePaths with bin_len = c / fs): every non-empty (bin, band) an impulse of
+            /// amplitude sqrt(energy) through that band's row of taps (B x T), the samples n0 .. n0 + n_out - 1 of the n_bins + T - 1 into the
+            /// first n_out values of every row of result, K x channels rows of out_stride doubles; add: onto what the rows hold
+            /// (include/hare_hip.h, "Impulses").</summary>
+            public void HistImpulses(ulong[] hist, int K, int n_bins, int B, int channels, uint[] weight, int frac_bits, double[] taps, long n0, long n_out,
+                                     long out_stride, bool add, double[] result)
+            {
+                if (hist == null || hist.LongLength < (long)K * n_bins * B * channels) throw new ArgumentException("hist must hold K x n_bins x B x channels values");
+                if (B < 1 || taps == null || taps.Length == 0 || taps.Length % B != 0) throw new ArgumentException("taps must hold B x T values");
+                if (weight != null && weight.LongLength != (long)n_bins * B) throw new ArgumentException("weight must hold n_bins x B values (or be null)");
+                if (out_stride < n_out || result == null || result.LongLength < (long)K * channels * out_stride) throw new ArgumentException("result must hold K x channels x out_stride values, out_stride >= n_out");
+                HareHip.Check(HareHip.hare_hist_impulses(scenes[0], K, n_bins, B, channels, hist, weight, frac_bits, taps.Length / B, taps, n0, n_out, out_stride,
+                                                         add ? 1 : 0, result));
+            }
+
+            /// <summary>hare_source_paths: the direct sound and the first- and second-order image sources of the first scene's source alone, each
+            /// standing for n_weight rays, into hist (zeroed by the call) and detections; flags: a non-empty subset of HARE_RECEIVE_DIRECT |
+            /// HARE_RECEIVE_IMAGE | HARE_RECEIVE_IMAGE2 plus the directional and order flags (include/hare_hip.h, "Impulses").</summary>
+            public void SourcePaths(int kind, int top_index, long n_weight, uint flags, int n_bins, double bin_len, int frac_bits, ulong[] hist, ulong[] detections)
+            {
+                if (hist == null || detections == null) throw new ArgumentException("hist and detections must be given");
+                HareHip.Check(HareHip.hare_source_paths(scenes[0], kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, hist, detections));
+            }
+
             /// <summary>hare_convolve: the R rows of N doubles in ir (the rows HistRender writes: R = K x channels) each convolved with the one
             /// signal x on the first scene's device, FP64 in the time domain (include/hare_hip.h, "Convolution"); the samples n0 ..
             /// n0 + n_out - 1 of the N + L - 1 of the full convolution into result, R x n_out doubles.</summary>

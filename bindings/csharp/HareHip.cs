@@ -312,6 +312,19 @@ namespace Hare
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_hist_render(IntPtr scene, int K, int n_bins, int B, int channels, [In] ulong[] hist, [In] uint[] weight,
                                                       int frac_bits, int M, int T, [In] double[] taps, ulong seed, [Out] double[] result);
+            // a per-sample histogram turned into pressure rows, an impulse per non-empty (bin, band) (include/hare_hip.h, "receivers", "Impulses")
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_hist_impulses_device(IntPtr scene, int K, int n_bins, int B, int channels, IntPtr d_hist, IntPtr d_weight,
+                                                               int frac_bits, int T, IntPtr d_taps, long n0, long n_out, long out_stride, int add,
+                                                               IntPtr d_out, IntPtr stream);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_hist_impulses(IntPtr scene, int K, int n_bins, int B, int channels, [In] ulong[] hist, [In] uint[] weight,
+                                                        int frac_bits, int T, [In] double[] taps, long n0, long n_out, long out_stride, int add,
+                                                        [In, Out] double[] result);
+            // the direct sound and the image sources of the scene's source alone, from host buffers (include/hare_hip.h, "receivers", "Impulses")
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_source_paths(IntPtr scene, int kind, int top_index, long n_weight, uint flags, int n_bins, double bin_len,
+                                                       int frac_bits, [Out] ulong[] hist, [Out] ulong[] detections);
             // the convolution of rendered responses with a dry signal on the device (include/hare_hip.h, "receivers", "Convolution")
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_convolve_device(IntPtr scene, long R, long N, IntPtr d_ir, long L, IntPtr d_x, long n0, long n_out,

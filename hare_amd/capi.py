@@ -141,6 +141,9 @@ SYMBOLS = {
     "hare_hist_project": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "hare_hist_render_device": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, C.c_uint64, _vp, _vp]),
     "hare_hist_render": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, C.c_uint64, _vp]),
+    "hare_hist_impulses_device": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "hare_hist_impulses": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _i64, _i64, _i32, _vp]),
+    "hare_source_paths": (C.c_int, [_vp, _i32, _i32, _i64, _u32, _i32, C.c_double, _i32, _vp, _vp]),
     "hare_convolve_device": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "hare_convolve": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp]),
     "hare_decode_device": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),

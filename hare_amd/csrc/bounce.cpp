@@ -653,6 +653,98 @@ int hare_receive_source_sharded(hare_scene* const* scenes, int32_t n_scenes, int
 
 }  // extern "C"
 
+// hare_source_paths: the deterministic paths from the scene's source alone -- the direct sound and the image sources of the first and the
+// second order -- deposited into a zeroed histogram from host buffers (include/hare_hip.h, "receivers", "Impulses").  What receive_on_scene
+// enqueues ahead of cast 0, in its order and through the same three plans, and nothing of the loop: the histogram and the detections are
+// zeroed, direct_enqueue / image_enqueue / image2_enqueue run on the context's stream with scratch sized from the scene's options, the
+// histogram, the detections and the found-counts come down, one synchronisation
+static int source_paths_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags,
+                                 int32_t n_bins, double bin_len, int32_t frac_bits, uint64_t* hist, uint64_t* det)
+{
+    Scene::BounceBuf& b = c.bounce;
+    const size_t K = s.rcv.size() / 4, P = (size_t)s.topos[(size_t)top].P;
+    const size_t hist_words = receive_hist_words(s, top, n_bins, flags), hist_bytes = (hist_words + 2 * K) * sizeof(uint64_t);
+    const bool direct = (flags & HARE_RECEIVE_DIRECT) != 0, image = (flags & HARE_RECEIVE_IMAGE) != 0, image2 = (flags & HARE_RECEIVE_IMAGE2) != 0;
+    const int64_t image_pairs = s.opt.image_max_pairs, image2_cands = s.opt.image2_max_cands, image2_paths = s.opt.image2_max_paths;
+    if (int rc = grow(H, b.hist, b.hist_cap, hist_bytes)) return rc;
+    if (int rc = grow(H, b.direct, b.direct_cap, direct ? (size_t)HARE_DIRECT_WORK_BYTES(K) : 0)) return rc;
+    if (int rc = grow(H, b.image, b.image_cap, image ? (size_t)HARE_IMAGE_WORK_BYTES(K, P, image_pairs) : 0)) return rc;
+    if (int rc = grow(H, b.image2, b.image2_cap, image2 ? (size_t)HARE_IMAGE2_WORK_BYTES(P, image2_cands, image2_paths) : 0)) return rc;
+    if (!c.st[0]) HIP_TRY(H->StreamCreate(&c.st[0]));
+    hipStream_t st = c.st[0];
+    uint64_t* const d_hist = (uint64_t*)b.hist;
+    uint64_t* const d_det = d_hist + hist_words;
+    HIP_TRY(H->MemsetAsync(b.hist, 0, hist_bytes, st));
+    if (direct)
+        if (int rc = direct_enqueue(s, H, kind, top, n_weight, flags, n_bins, bin_len, frac_bits, b.direct, d_hist, d_det, st)) return rc;
+    if (image)
+        if (int rc = image_enqueue(s, H, kind, top, n_weight, flags, n_bins, bin_len, frac_bits, image_pairs, b.image, d_hist, d_det, st)) return rc;
+    if (image2)
+        if (int rc = image2_enqueue(s, H, kind, top, n_weight, flags, n_bins, bin_len, frac_bits, image2_cands, image2_paths, b.image2, d_hist, d_det, st))
+            return rc;
+    HIP_TRY(H->MemcpyAsync(hist, d_hist, hist_words * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(H->MemcpyAsync(det, d_det, 2 * K * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    uint64_t image_found = 0;       // the last downloads, so that no return lies between them and the wait
+    if (image) HIP_TRY(H->MemcpyAsync(&image_found, b.image, sizeof image_found, hipMemcpyDeviceToHost, st));
+    uint64_t image2_found[2] = {0, 0};
+    if (image2) HIP_TRY(H->MemcpyAsync(image2_found, b.image2, sizeof image2_found, hipMemcpyDeviceToHost, st));
+    HIP_TRY(H->StreamSynchronize(st));
+    const std::string who = "hare_source_paths";
+    if (image2_found[0] > (uint64_t)image2_cands || image2_found[1] > (uint64_t)image2_paths) {      // receive_on_scene's messages
+        set_error(who + ": the scene yields " + std::to_string(image2_found[0]) + " second-order candidates and " +
+                  (image2_found[0] > (uint64_t)image2_cands ? std::string("an unknown number of") : std::to_string(image2_found[1])) +
+                  " paths, \"image2_max_cands\" is " + std::to_string(image2_cands) + " and \"image2_max_paths\" " + std::to_string(image2_paths) +
+                  " (needed: " + std::to_string(image2_found[0]) + ", " + std::to_string(image2_found[1]) + ")");
+        return HARE_E_NOMEM;
+    }
+    if (image_found > (uint64_t)image_pairs) {
+        set_error(who + ": the scene yields " + std::to_string(image_found) + " image-source pairs, \"image_max_pairs\" is " +
+                  std::to_string(image_pairs) + " (needed: " + std::to_string(image_found) + ")");
+        return HARE_E_NOMEM;
+    }
+    return HARE_OK;
+}
+
+extern "C" int hare_source_paths(hare_scene* s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                                 int32_t frac_bits, uint64_t* hist, uint64_t* detections)
+{
+    const char* const who = "hare_source_paths";
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    const uint32_t paths = HARE_RECEIVE_DIRECT | HARE_RECEIVE_IMAGE | HARE_RECEIVE_IMAGE2;
+    if (flags & ~(paths | kReceiveChannelFlags))
+        return bad("flags other than HARE_RECEIVE_DIRECT / _IMAGE / _IMAGE2 and the directional and order flags");
+    if (!(flags & paths)) return bad("nothing to deposit: none of HARE_RECEIVE_DIRECT / _IMAGE / _IMAGE2");
+    if (int rc = receive_check_args(who, *s, flags, kind, top_index, 0, 1, n_bins, bin_len, frac_bits)) return rc;      // the order flags, _IMAGE2 without _IMAGE
+    if (n_weight < 1 || n_weight > ((int64_t)1 << 53)) return bad("n_weight out of range (1 .. 2^53)");
+    if (s->src.set && s->src.B != scene_bands(*s, top_index))
+        return bad("the source has " + std::to_string(s->src.B) + " bands, the topology " + std::to_string(scene_bands(*s, top_index)));
+    if (!hist || !detections) return bad("null histogram / detections");
+    const size_t K1 = std::max<size_t>(1, s->rcv.size() / 4);
+    if (spans_overlap({{hist, receive_hist_words(*s, top_index, n_bins, flags, 1) * sizeof(uint64_t)}, {detections, K1 * 2 * sizeof(uint64_t)}}, 2))
+        return bad("histogram and detections must not overlap");
+    GUARD_BEGIN
+    DeviceGuard dev_guard(hip_api(nullptr), s->device);
+    const HipApi* H = nullptr;
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (int rc = ensure_device(*s, H)) return rc;
+    if (int rc = source_ready(*s, H, who)) return rc;
+    if (int rc = upload_polys(*s, H)) return rc;
+    if (int rc = receive_ready(*s, H, who)) return rc;
+    const CtxLease lease(*s, lk, [](const Scene::BatchCtx&) { return true; });       // (releases lk)
+    Scene::BatchCtx* const c = lease.get();
+    const int rc = source_paths_on_scene(*s, H, *c, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, hist, detections);
+    if (rc != HARE_OK && c->st[0]) (void)H->StreamSynchronize(c->st[0]);          // copies into the caller's buffers may still be in flight
+    return rc;
+    GUARD_END
+}
+
 // hare_receive_batch / hare_receive_source with the histogram reduced on the device (include/hare_hip.h, "receivers", "Reduction")
 static ReduceSpec reduce_spec(const uint32_t* weight, int32_t n_win, const int32_t* win, int32_t n_lev, const uint32_t* levels)
 {

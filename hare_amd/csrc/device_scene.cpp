@@ -117,6 +117,7 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_hist_project", &m->hist_project},
         {"hare_convolve", &m->convolve},
         {"hare_decode", &m->decode},
+        {"hare_hist_impulses", &m->hist_impulses},
         {"hare_direct_emit", &m->direct_emit},
         {"hare_image_mirror", &m->image_mirror},
         {"hare_image_pairs", &m->image_pairs},

@@ -762,6 +762,34 @@ struct DecodeArgs {
     int32_t tiles;                    // workgroups per (k, o): ceil(n_out / kDecodeTile)
 };
 
+// hare_hist_impulses (impulses.hip): a per-sample receive histogram turned into pressure rows, every non-empty (bin, band) an impulse of
+// amplitude sqrt(energy) through that band's FIR (include/hare_hip.h, "receivers", "Impulses").  A workgroup owns one receiver and
+// kImpulseTile consecutive outputs of ALL channels, an output to a lane; per band the bins that reach the tile go by in chunks of
+// kImpulseChunk, a bin to a thread, the chunk's entries compacted in ascending bin order into an LDS list (impulses_plan, hist.cpp, sizes
+// the grid and the dynamic LDS)
+constexpr int kImpulseThreads = 256;
+constexpr int kImpulseTile = kImpulseThreads;       // outputs per workgroup
+constexpr int kImpulseChunk = kImpulseThreads;      // bins scanned at once: the list's capacity
+// LDS bytes behind the bands x T taps: per list slot the gains of every channel, the amplitude and the W word (8 bytes each) and the bin
+// (4 bytes), then the waves' entry counts
+constexpr int impulse_list_bytes(int channels) { return kImpulseChunk * (8 * (channels + 2) + 4) + 4 * (kImpulseThreads / 64); }
+struct ImpulseArgs {
+    const unsigned long long* hist;   // K x n_bins x bands x channels words
+    const uint32_t* weight;           // n_bins x bands, units of 2^-32 (null: none)
+    const double* taps;               // bands x T
+    double* out;                      // K x channels x out_stride; the first n_out words of a row written (add: read, then written)
+    long long out_stride;             // doubles between rows, >= n_out
+    int32_t n_bins;
+    int32_t bands;                    // 1 .. kMaxBands
+    int32_t channels;                 // 1, 4, 9 or 16
+    int32_t frac_bits;
+    int32_t T;                        // 1 .. kMaxRenderTaps
+    int32_t n0;                       // first output sample; n0 + n_out <= n_bins + T - 1 < 2^27 + 2^10
+    int32_t n_out;
+    int32_t add;                      // 0: out = z; 1: out = out + z
+    int32_t tiles;                    // workgroups per receiver: ceil(n_out / kImpulseTile)
+};
+
 #if defined(__HIPCC__)
 // Every kernel argument as a scalar of its OWN (round 6).  The compiler fetches the 720-byte argument block in tuples of 8 and 16 SGPRs and,
 // short of SGPRs in these kernels, spills and reloads them AS tuples: a block that needs the rays' pointer reloaded sixteen registers to get

@@ -1,6 +1,6 @@
 // hist.cpp -- what runs on a receive histogram once it is on the device (include/hare_hip.h, "receivers"): the reduction (hare_hist_reduce
 // / _device; the kernel: reduce.hip), the projection (hare_hist_project / _device; project.hip), the rendering (hare_hist_render /
-// _device; render.hip) and, on the rendered rows, the convolution with a dry signal (hare_convolve / _device; convolve.hip) and the
+// _device; render.hip), the impulses of a per-sample histogram (hare_hist_impulses / _device; impulses.hip) and, on the rendered rows, the convolution with a dry signal (hare_convolve / _device; convolve.hip) and the
 // decoding through a matrix of FIR filters (hare_decode / _device; decode.hip).  A call is its own check and its own enqueue; what the calls share is the device prelude (device_call, launch.h),
 // the overlap test (spans_overlap, scene.h), one byte count per buffer, used by the check and by the staging, and the staging of the
 // host-buffer calls (staged_run).  reduce_check_spec and reduce_enqueue also serve hare_receive_*_reduced (bounce.cpp).
@@ -260,6 +260,71 @@ int render_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, i
     return launch(H, s.module->hist_render, (unsigned)K * (unsigned)a.tiles, kRenderThreads, lds, st, args);      // K x n_bins <= 2^27 workgroups
 }
 
+// ---- the impulses (include/hare_hip.h, "receivers", "Impulses"; the kernel: impulses.hip)
+struct ImpulseBytes {
+    size_t hist, weight, taps, out;
+};
+
+// everything both impulse calls check before anything runs, in the header's order; buffers device or host
+int impulses_check(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const void* hist, const void* weight, int32_t frac_bits,
+                   int32_t T, const void* taps, int64_t n0, int64_t n_out, int64_t out_stride, int32_t add, const void* out, ImpulseBytes& z)
+{
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    if (int rc = hist_check_shape(who, K, n_bins, B, channels)) return rc;
+    if (T < 1 || T > kMaxRenderTaps) return bad("T out of range (1 .. 1024)");
+    if (frac_bits < 0 || frac_bits > 62) return bad("frac_bits out of range (0 .. 62)");
+    const int64_t total = (int64_t)n_bins + T - 1;
+    if (n0 < 0 || n_out < 1 || n0 > total || n_out > total - n0) return bad("the window is not 0 <= n0, 1 <= n_out, n0 + n_out <= n_bins + T - 1");
+    if (out_stride < n_out) return bad("out_stride must be >= n_out");
+    if ((unsigned __int128)K * (unsigned)channels * (unsigned __int128)out_stride > ((size_t)1 << 28)) return bad("K x channels x out_stride exceeds 2^28");
+    if (add != 0 && add != 1) return bad("add must be 0 or 1");
+    if (!hist || !taps || !out) return bad("null histogram / taps / output");
+    z = {hist_bytes(K, n_bins, B, channels), weight_bytes(n_bins, B), (size_t)B * (size_t)T * sizeof(double),
+         (size_t)K * (size_t)channels * (size_t)out_stride * sizeof(double)};
+    if (spans_overlap({{out, z.out}, {hist, z.hist}, {weight, z.weight}, {taps, z.taps}}, 1))
+        return bad("the output must not overlap the histogram, the weights or the taps");
+    return HARE_OK;
+}
+
+// The launch of hare_hist_impulses (impulses.hip): a workgroup per receiver and tile of kImpulseTile outputs, all channels; LDS: the taps,
+// then the list of one chunk's entries: at most 8 * 8192 + 256 * (8 * 18 + 4) + 16 = 103 440 bytes
+unsigned impulses_plan(ImpulseArgs& a)
+{
+    a.tiles = (a.n_out + kImpulseTile - 1) / kImpulseTile;
+    return (unsigned)(sizeof(double) * (size_t)(a.bands * a.T) + (size_t)impulse_list_bytes(a.channels));
+}
+
+int impulses_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
+                     int32_t frac_bits, int32_t T, const void* d_taps, int64_t n0, int64_t n_out, int64_t out_stride, int32_t add, void* d_out,
+                     hipStream_t st)
+{
+    if (!s.module || !s.module->hist_impulses) {
+        set_error("hare_hist_impulses missing from code object");
+        return HARE_E_STATE;
+    }
+    ImpulseArgs a;
+    memset(&a, 0, sizeof a);
+    a.hist = (const unsigned long long*)d_hist;
+    a.weight = (const uint32_t*)d_weight;
+    a.taps = (const double*)d_taps;
+    a.out = (double*)d_out;
+    a.out_stride = out_stride;
+    a.n_bins = n_bins;
+    a.bands = B;
+    a.channels = channels;
+    a.frac_bits = frac_bits;
+    a.T = T;
+    a.n0 = (int32_t)n0;
+    a.n_out = (int32_t)n_out;
+    a.add = add;
+    const unsigned lds = impulses_plan(a);
+    void* args[] = {&a};
+    return launch(H, s.module->hist_impulses, (unsigned)K * (unsigned)a.tiles, kImpulseThreads, lds, st, args);      // K x tiles <= 2^20 + 2^16 workgroups
+}
+
 // ---- the convolution (include/hare_hip.h, "receivers", "Convolution"; the kernel: convolve.hip)
 struct ConvolveBytes {
     size_t ir, x, y;
@@ -459,6 +524,43 @@ int hare_hist_render(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_
         const StagePart parts[] = {{z.out, nullptr, out}, {z.hist, hist, nullptr}, {z.taps, taps, nullptr}, {weight ? z.weight : 0, weight, nullptr}};
         return staged_run(H, parts, [&](void* const* d) {
             return render_enqueue(*s, H, K, n_bins, B, channels, d[1], d[3], frac_bits, M, T, d[2], seed, d[0], nullptr);
+        });
+    });
+}
+
+int hare_hist_impulses_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist, const void* d_weight,
+                              int32_t frac_bits, int32_t T, const void* d_taps, int64_t n0, int64_t n_out, int64_t out_stride, int32_t add, void* d_out,
+                              void* stream)
+{
+    if (!s) return null_scene();
+    ImpulseBytes z;
+    if (int rc = impulses_check("hare_hist_impulses_device", K, n_bins, B, channels, d_hist, d_weight, frac_bits, T, d_taps, n0, n_out, out_stride, add,
+                                d_out, z))
+        return rc;
+    return device_call(*s, [&](const HipApi* H) {
+        return impulses_enqueue(*s, H, K, n_bins, B, channels, d_hist, d_weight, frac_bits, T, d_taps, n0, n_out, out_stride, add, d_out,
+                                (hipStream_t)stream);
+    });
+}
+
+int hare_hist_impulses(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t* hist, const uint32_t* weight,
+                       int32_t frac_bits, int32_t T, const double* taps, int64_t n0, int64_t n_out, int64_t out_stride, int32_t add, double* out)
+{
+    if (!s) return null_scene();
+    ImpulseBytes z;
+    if (int rc = impulses_check("hare_hist_impulses", K, n_bins, B, channels, hist, weight, frac_bits, T, taps, n0, n_out, out_stride, add, out, z))
+        return rc;
+    for (size_t x = 0; x < (size_t)B * (size_t)T; ++x)
+        if (!std::isfinite(taps[x])) {
+            set_error("hare_hist_impulses: taps[" + std::to_string(x) + "] is not finite");
+            return HARE_E_INVALID;
+        }
+    // out goes up first where the device must see it: the rows it adds onto, and the words between n_out and out_stride, which come down as they went up
+    const bool up = add == 1 || out_stride > n_out;
+    return device_call(*s, [&](const HipApi* H) {
+        const StagePart parts[] = {{z.out, up ? out : nullptr, out}, {z.hist, hist, nullptr}, {z.taps, taps, nullptr}, {weight ? z.weight : 0, weight, nullptr}};
+        return staged_run(H, parts, [&](void* const* d) {
+            return impulses_enqueue(*s, H, K, n_bins, B, channels, d[1], d[3], frac_bits, T, d[2], n0, n_out, out_stride, add, d[0], nullptr);
         });
     });
 }

@@ -21,6 +21,7 @@
 //   hare_image2_mirror / _cands / _paths / _deposit  second-order image sources: candidates polygons x polygons, paths receivers x candidates (image2.hip)
 //   hare_hist_reduce            a receive histogram reduced to window sums and decay crossings per receiver and band (reduce.hip)
 //   hare_hist_render            a receive histogram rendered to impulse responses per receiver and channel: shaped band noise (render.hip)
+//   hare_hist_impulses          a per-sample receive histogram turned into pressure rows: an impulse per non-empty (bin, band) through the band's FIR (impulses.hip)
 //   hare_convolve               rows of doubles convolved with one signal in the time domain: FP64, one sequential sum per output (convolve.hip)
 //   hare_decode                 rows of doubles decoded through a matrix of FIR filters: FP64, one sequential sum per output over channels and taps (decode.hip)
 //   hare_hist_project           a receive histogram projected onto up to 32 integer vectors over the bins, exact 128-bit sums (project.hip)
@@ -1968,6 +1969,7 @@ __global__ __launch_bounds__(256) void hare_occlusion(const XEventRec* ev, const
 #include "hist_block.h"        // U128, weighted, band_total, Block: what the three kernels on a histogram share; no kernel
 #include "reduce.hip"          // hare_hist_reduce: window sums and decay crossings of a receive histogram (hare_hist_reduce_device)
 #include "render.hip"          // hare_hist_render: a receive histogram rendered to impulse responses, shaped band noise (hare_hist_render_device)
+#include "impulses.hip"        // hare_hist_impulses: a per-sample histogram to pressure rows, an impulse per entry through its band's FIR, stated sum order (hare_hist_impulses_device)
 #include "convolve.hip"        // hare_convolve: rows of doubles convolved with one signal in the time domain, FP64, stated sum order (hare_convolve_device)
 #include "decode.hip"          // hare_decode: K x C rows decoded to K x O through O x C FIR filters, the convolution's tile, stated sum order (hare_decode_device)
 #include "project.hip"         // hare_hist_project: a receive histogram projected onto integer vectors over the bins (hare_hist_project_device)

@@ -138,6 +138,7 @@ struct DeviceModule {
     hipFunction_t hist_project = nullptr;                                  // project.hip
     hipFunction_t convolve = nullptr;                                      // convolve.hip
     hipFunction_t decode = nullptr;                                        // decode.hip
+    hipFunction_t hist_impulses = nullptr;                                 // impulses.hip
     hipFunction_t direct_emit = nullptr, direct_deposit[4] = {};           // direct.hip ([channel form])
     hipFunction_t image_mirror = nullptr, image_pairs = nullptr, image_deposit[4] = {};   // image.hip ([channel form])
     hipFunction_t image2_mirror = nullptr, image2_cands = nullptr, image2_paths = nullptr, image2_deposit[4] = {};   // image2.hip ([channel form])

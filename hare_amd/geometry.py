@@ -204,6 +204,17 @@ def band_taps(fs: float, edges, T: int):
     return np.ascontiguousarray([steps[b + 1] - steps[b] for b in range(len(edges) + 1)])
 
 
+def unit_energy_taps(taps):
+    """taps float64 [B, T] with every band's row scaled to unit energy (the sum of its squares 1): an impulse of hist_impulses then puts
+    the histogram's energy e into its band, as hist_render's noise does over a bin.  A row of zeros stays as it is.  A host convenience
+    that produces data: whatever taps the caller passes are the definition's."""
+    taps = np.array(taps, np.float64, ndmin=2)
+    if taps.ndim != 2 or not np.isfinite(taps).all():
+        raise ValueError("taps must be finite float64 [B, T]")
+    norm = np.sqrt((taps * taps).sum(axis=1, keepdims=True))
+    return np.ascontiguousarray(taps / np.where(norm > 0, norm, 1.0))
+
+
 def sums_to_float(sums):
     """The sums of a reduction [..., 4] (S0 lo, S0 hi, S1 lo, S1 hi; uint64) as float64 (S0, S1): rounded, for the ratios a caller forms."""
     s = np.asarray(sums).astype(np.float64)
@@ -778,6 +789,54 @@ class Spatial_Partition:
         wait."""
         check(lib.hare_hist_render_device(self._h, int(K), int(n_bins), int(B), int(channels), d_hist or None, d_weight or None, int(frac_bits),
                                           int(M), int(T), d_taps or None, int(seed) & 0xFFFFFFFFFFFFFFFF, d_out or None, stream or None))
+
+    def hist_impulses(self, hist, taps, frac_bits: int, n0: int = 0, n_out=None, weight=None, out=None):
+        """hare_hist_impulses: a PER-SAMPLE histogram [K, n_bins, B] or [K, n_bins, B, C] (C = 4, 9 or 16) of uint64 -- Source_paths with
+        bin_len = c / fs -- turned on this partition's device into pressure rows (include/hare_hip.h, "receivers", "Impulses"): every
+        non-empty (bin, band) an impulse of amplitude sqrt(energy) through that band's row of taps [B, T] float64, weighted per channel by
+        the rendering's ratio.  The window [n0, n0 + n_out) of the n_bins + T - 1 samples is computed; n_out None: everything from n0 on.
+        weight uint32 [n_bins, B] (air_weights) or None.  out None: returns a new float64 [K, channels, n_out].  out given, float64
+        [K, channels, stride] C-contiguous with stride >= n_out: the impulses are ADDED onto its first n_out samples per row (add = 1; e.g.
+        what hist_render returned), the rest is left as it is, and out is returned."""
+        hist, K, nb, B, channels = _hist_shape(hist)
+        taps = np.ascontiguousarray(taps, np.float64)
+        if taps.ndim != 2 or taps.shape[0] != B or taps.shape[1] < 1:
+            raise ValueError("taps must be float64 [B, T] = [%d, T]" % B)
+        w, *_ = _reduce_spec(dict(weight=weight), nb, B)
+        T, n0 = taps.shape[1], int(n0)
+        n_out = nb + T - 1 - n0 if n_out is None else int(n_out)
+        add = 0 if out is None else 1
+        if out is None:
+            out = np.zeros((K, channels, max(0, n_out)), np.float64)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.flags.writeable
+                  and out.ndim == 3 and out.shape[:2] == (K, channels)):
+            raise ValueError("out must be a writeable C-contiguous float64 [K, channels, stride] = [%d, %d, stride]" % (K, channels))
+        check(lib.hare_hist_impulses(self._h, K, nb, B, channels, ptr(hist), ptr(w), int(frac_bits), T, ptr(taps), n0, n_out, out.shape[2], add,
+                                     ptr(out)))
+        return out
+
+    def hist_impulses_device(self, K: int, n_bins: int, B: int, channels: int, d_hist: int, frac_bits: int, T: int, d_taps: int, n0: int,
+                             n_out: int, out_stride: int, add: int, d_out: int, d_weight: int = 0, stream: int = 0):
+        """hare_hist_impulses_device on raw device addresses + a hipStream_t: d_hist as direct_device / image_device / image2_device
+        accumulate it with a bin of one sample, d_taps (B x T float64), d_out (K x channels x out_stride float64): the first n_out words of
+        each row written (add 0) or added onto (add 1).  d_weight (n_bins x B uint32) or 0.  Stream-ordered: no allocation, no free, no wait."""
+        check(lib.hare_hist_impulses_device(self._h, int(K), int(n_bins), int(B), int(channels), d_hist or None, d_weight or None, int(frac_bits),
+                                            int(T), d_taps or None, int(n0), int(n_out), int(out_stride), int(add), d_out or None, stream or None))
+
+    def Source_paths(self, n_weight: int, n_bins: int, bin_len: float, frac_bits: int = 40, top_index: int = 0, directional: bool = False,
+                     direct: bool = True, image: bool = True, image2: bool = True, *, order: int = 1):
+        """hare_source_paths: the deterministic paths of the scene's source alone -- the direct sound (direct), the first-order image sources
+        (image) and the second-order ones (image2, only with image) -- deposited into a zeroed histogram, each standing for n_weight rays:
+        what Receive_source deposits ahead of cast 0 under the same flags, and nothing of the loop.  With bin_len = c / fs the histogram is
+        what hist_impulses takes.  Returns (hist uint64 [K, n_bins, B] or [K, n_bins, B, C], detections uint64 [K, 2])."""
+        shape = self._receive_shape(top_index, n_bins, bool(directional), order=order)
+        K = max(shape[0], 0)
+        hist, det = np.zeros((K,) + shape[1:], np.uint64), np.zeros((K, 2), np.uint64)
+        flags = (capi.channel_flags(directional, order) | (capi.RECEIVE_DIRECT if direct else 0) | (capi.RECEIVE_IMAGE if image else 0) |
+                 (capi.RECEIVE_IMAGE2 if image2 else 0))
+        check(lib.hare_source_paths(self._h, self._kind, int(top_index), int(n_weight), flags, int(n_bins), float(bin_len), int(frac_bits),
+                                    ptr(hist), ptr(det)))
+        return hist, det
 
     def convolve(self, ir, x, n0: int = 0, n_out=None):
         """hare_convolve: the rows of ir -- float64 [R, N], or [K, C, N] as hist_render returns it (row k * C + ch) -- each convolved on

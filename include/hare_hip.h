@@ -947,8 +947,38 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * channels of a receiver share one noise sequence, so direction is carried by the gains; receivers are decorrelated through k.  r_ch is
  * the energy-weighted mean of the SN3D harmonic in that bin.  The gain is constant across a bin (no interpolation).  Deterministic early
  * paths are better rendered as impulses than as noise: a caller who wants that deposits the direct sound and the image sources into a
- * histogram of their own with the _device calls and renders only the rest here; rendering impulses is not part of this call.  The
+ * histogram of their own with the _device calls and renders only the rest here; rendering impulses is not part of this call
+ * ("Impulses" below).  The
  * sequential order of y, p and z is part of the definition: parallelism is over (k, b, n) and (k, b, i), never inside a sum.
+ *
+ * Impulses (hare_hist_impulses_device, hare_hist_impulses, hare_source_paths).  The direct sound and the specular reflections of the first
+ * and second order are the arrivals the ear locates; rendered as noise they become bursts a bin long with a random polarity.  The three
+ * deposit calls accept any n_bins and bin_len: with a bin of ONE output sample (bin_len = c / fs) they deposit every path into the sample
+ * it arrives in, as exact integers, whatever the order, the directional channels included.  This call turns such a per-sample histogram
+ * into pressure rows: every non-empty (bin, band) becomes an impulse of amplitude sqrt(energy), positive, filtered by that band's FIR and
+ * weighted per channel by the rendering's ratio; optionally added onto rows "Rendering" wrote (the noise tail), which makes the hybrid
+ * response.  Inputs: a histogram as in "Reduction" (K x n_bins x B entries of `channels` 1, 4, 9 or 16 words), the optional weight of
+ * "Reduction" (n_bins x B uint32), frac_bits, taps (B x T doubles, 1 <= T <= 1024), a window [n0, n0 + n_out) of the n_bins + T - 1
+ * samples of the full result, out_stride >= n_out (doubles between the rows of out), and add, 0 or 1.  Output: out[(k * channels + ch) *
+ * out_stride + (n - n0)], doubles.  All floating-point work is FP64 without contraction, in exactly this order:
+ *
+ *   per (k, i, b):  hW = hist[..+0];  g = hW, or the weighted word of "Reduction";  an ENTRY exists iff g != 0
+ *   e = ldexp((double)g, -frac_bits);  a = sqrt(e)                            uint64 -> double, round to nearest even
+ *   r_0 = 1.0;  for ch >= 1:  r_ch = (double)(int64)hist[..+ch] / (double)hW   (hW != 0 follows from g != 0);   gain_ch = a * r_ch
+ *   out(k,ch,n): z = +0.0
+ *     for b = 0 .. B-1 ascending:  for i = max(0, n - (T-1)) .. min(n_bins - 1, n) ascending:
+ *       if (k, i, b) is an entry:  z = z + (gain_ch(k,i,b) * taps[b*T + (n - i)])       product rounded, then the add
+ *   out[..] = z  (add == 0),  or  out[..] + z, one add  (add == 1)
+ *
+ * Bins without an entry and taps out of range contribute NO term: they are skipped, not multiplied by zero, for the reason "Convolution"
+ * gives -- a tap that is not finite reaches exactly the outputs an entry carries it to, and the sparse sum is the dense one bit for bit.
+ * The words from n_out to out_stride of a row are never touched.  A NaN output is "some NaN", as elsewhere.  Parallelism is over (k, n),
+ * never inside a sum: a job cut over windows or over receivers is the one call byte for byte.  Two paths in one sample and band add as
+ * energies (sqrt(e1 + e2)), not as pressures.  The energy an impulse puts into band b is e * sum_t taps[b][t]^2, so calibration against
+ * the noise rendering is a matter of the taps (bindings: hare_amd.unit_energy_taps scales each band's row to unit energy; a convenience
+ * outside this contract).  With taps whose bands telescope to a delay of D samples (hare_amd.band_taps: D = (T - 1) / 2), n0 = D aligns
+ * output sample n with bin n.  hare_source_paths runs the three deposits alone, from the host: what hare_receive_source deposits ahead of
+ * cast 0 under HARE_RECEIVE_DIRECT / _IMAGE / _IMAGE2 and nothing of the loop, word for word.
  *
  * Convolution (hare_convolve_device, hare_convolve).  What is listened to is not the response but a sound in the room: a dry signal
  * convolved with the response of every receiver channel.  This is that last step, in the time domain, on the device, so that the chain stays
@@ -1164,6 +1194,35 @@ HARE_API int hare_hist_render_device(hare_scene *s, int32_t K, int32_t n_bins, i
 HARE_API int hare_hist_render(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t *hist,
                               const uint32_t *weight /* nullable */, int32_t frac_bits, int32_t M, int32_t T, const double *taps,
                               uint64_t seed, double *out);
+/* A per-sample histogram turned into pressure rows ("receivers", "Impulses" above) on DEVICE buffers: one launch, stream-ordered like
+ * hare_hist_render_device -- no allocation, no free, no wait.  d_taps (B x T doubles) is a device buffer of the caller's; d_weight
+ * nullable; of d_out (K x channels x out_stride doubles) the first n_out words of every row are WRITTEN (add == 0) or read and written
+ * (add == 1), the rest never touched.  Behind hare_direct_device / hare_image_device / hare_image2_device on the same stream it renders
+ * the paths those calls deposited; behind hare_hist_render_device, with add == 1 and out_stride that call's n_bins x M, it adds them onto
+ * the noise rows; hare_decode_device may follow with N = out_stride.  Checked before anything runs (HARE_E_INVALID), in this order:
+ * 1 <= K <= 65 536, n_bins >= 1, 1 <= B <= 8, channels 1, 4, 9 or 16, K x n_bins x B x channels <= 2^27; 1 <= T <= 1024;
+ * 0 <= frac_bits <= 62; n0 >= 0, n_out >= 1, n0 + n_out <= n_bins + T - 1; out_stride >= n_out; K x channels x out_stride <= 2^28; add 0
+ * or 1; null buffers; out overlapping the histogram, the weights or the taps.  Then HARE_E_NODEVICE, then HARE_E_STATE.  The scene names
+ * the device; its geometry is not read. */
+HARE_API int hare_hist_impulses_device(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void *d_hist,
+                                       const void *d_weight /* nullable */, int32_t frac_bits, int32_t T, const void *d_taps, int64_t n0,
+                                       int64_t n_out, int64_t out_stride, int32_t add, void *d_out, void *stream);
+/* The same from host buffers: one allocation, upload, launch, download, one synchronisation.  out goes up first where the device must
+ * see it: with add == 1, and with out_stride > n_out (the words between come down as they went up).  Also HARE_E_INVALID: a tap that is
+ * not finite. */
+HARE_API int hare_hist_impulses(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t *hist,
+                                const uint32_t *weight /* nullable */, int32_t frac_bits, int32_t T, const double *taps, int64_t n0,
+                                int64_t n_out, int64_t out_stride, int32_t add, double *out);
+/* The deterministic paths of the scene's source alone, from host buffers ("receivers", "Impulses" above): flags is a non-empty subset of
+ * HARE_RECEIVE_DIRECT | HARE_RECEIVE_IMAGE | HARE_RECEIVE_IMAGE2 (_IMAGE2 only with _IMAGE) plus HARE_RECEIVE_DIRECTIONAL and the order
+ * flags; anything else is HARE_E_INVALID, like 1 <= n_weight <= 2^53 and the receive calls' checks of kind, top_index, n_bins, bin_len,
+ * frac_bits and the histogram's size.  A batch context is leased, the histogram zeroed, the three deposits enqueued as hare_receive_source
+ * enqueues them (scratch sized from the scene options "image_max_pairs", "image2_max_cands", "image2_max_paths"), histogram, detections and
+ * found-counts downloaded, one synchronisation.  An overflow of a list is HARE_E_NOMEM with hare_receive_source's message.  hist
+ * (K x n_bins x B x channels uint64) and detections (K x 2 uint64) are WRITTEN.  With bin_len = c / fs the histogram is what
+ * hare_hist_impulses takes.  HARE_E_STATE when no source or no receivers are set. */
+HARE_API int hare_source_paths(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags, int32_t n_bins,
+                               double bin_len, int32_t frac_bits, uint64_t *hist, uint64_t *detections);
 /* The convolution of rows with a signal ("receivers", "Convolution" above) on DEVICE buffers: one launch, stream-ordered like
  * hare_hist_render_device -- no allocation, no free, no wait.  d_ir (R x N doubles), d_x (L doubles); d_y (R x n_out doubles) is WRITTEN,
  * every word once.  Behind hare_hist_render_device on the same stream, with d_ir its d_out, R = K x channels and N = n_bins x M, it convolves
