@@ -357,6 +357,27 @@ public:
     {
         check(hare_hist_project_device(scene_, K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj, stream));
     }
+    // hare_hist_project_channels (include/hare_hip.h, "receivers", "Directional projection"): HistProject for every channel of hist, the
+    // channels after W read as two's-complement int64.  proj: K x B x J x channels x 2, the lo and hi words of the exact 128-bit sums
+    void HistProjectChannels(const std::vector<uint64_t>& hist, int K, int n_bins, int B, int channels, const std::vector<int32_t>& coef,
+                             std::vector<uint64_t>& proj, const std::vector<uint32_t>& weight = {})
+    {
+        if (K < 0 || n_bins < 1 || B < 0 || channels < 0 || hist.size() != (size_t)K * (size_t)n_bins * (size_t)B * (size_t)channels)
+            throw std::invalid_argument("HistProjectChannels: hist must hold K x n_bins x B x channels values");
+        if (coef.empty() || coef.size() % (size_t)n_bins != 0) throw std::invalid_argument("HistProjectChannels: coef must hold J x n_bins values");
+        if (!weight.empty() && weight.size() != (size_t)n_bins * (size_t)B)
+            throw std::invalid_argument("HistProjectChannels: weight must hold n_bins x B values (or none)");
+        const size_t J = coef.size() / (size_t)n_bins;
+        proj.assign((size_t)K * (size_t)B * J * (size_t)channels * 2, 0);
+        check(hare_hist_project_channels(scene_, K, n_bins, B, channels, hist.data(), weight.empty() ? nullptr : weight.data(), (int32_t)J,
+                                         coef.data(), proj.data()));
+    }
+    // hare_hist_project_channels_device on device pointers and a hipStream_t: d_proj (K x B x J x channels x 2 uint64) written.  Stream-ordered.
+    void HistProjectChannelsDevice(int K, int n_bins, int B, int channels, const void* d_hist, int J, const void* d_coef, void* d_proj,
+                                   const void* d_weight = nullptr, void* stream = nullptr)
+    {
+        check(hare_hist_project_channels_device(scene_, K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj, stream));
+    }
     // hare_hist_render (include/hare_hip.h, "receivers", "Rendering"): hist as Receive returns it (K x n_bins x B x channels), rendered to
     // impulse responses of M samples per bin -- noise from `seed`, filtered per band by taps (B x T), shaped by the histogram.  out:
     // K x channels x (n_bins * M).  weight: n_bins x B in units of 2^-32 (AirWeights), or empty: none

@@ -305,6 +305,13 @@ namespace Hare
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_hist_project(IntPtr scene, int K, int n_bins, int B, int channels, [In] ulong[] hist, [In] uint[] weight,
                                                        int J, [In] int[] coef, [Out] ulong[] proj);
+            // the projection of every channel of a histogram, signed words (include/hare_hip.h, "receivers", "Directional projection")
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_hist_project_channels_device(IntPtr scene, int K, int n_bins, int B, int channels, IntPtr d_hist,
+                                                                       IntPtr d_weight, int J, IntPtr d_coef, IntPtr d_proj, IntPtr stream);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_hist_project_channels(IntPtr scene, int K, int n_bins, int B, int channels, [In] ulong[] hist,
+                                                                [In] uint[] weight, int J, [In] int[] coef, [Out] ulong[] proj);
             // the rendering of a histogram to impulse responses on the device (include/hare_hip.h, "receivers", "Rendering")
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_hist_render_device(IntPtr scene, int K, int n_bins, int B, int channels, IntPtr d_hist, IntPtr d_weight,

@@ -10,10 +10,11 @@ from .capi import HareError, device_count  # noqa: F401
 from .geometry import KDTree, Octree, Ray, Spatial_Partition, Topology, Voxel_Grid, X_Event  # noqa: F401
 from .geometry import air_weights, band_taps, decay_levels, proj_to_int, sums_to_float, unit_energy_taps  # noqa: F401
 from . import sti  # noqa: F401
+from . import spatial  # noqa: F401
 from . import decoders  # noqa: F401
 from . import scenes  # noqa: F401
 
 __all__ = ["Ray", "X_Event", "Topology", "Spatial_Partition", "Voxel_Grid", "Octree", "KDTree",
            "HareError", "device_count", "scenes", "capi", "air_weights", "band_taps", "decay_levels", "proj_to_int", "sums_to_float",
            "unit_energy_taps",
-           "sti", "decoders"]
+           "sti", "spatial", "decoders"]

@@ -115,6 +115,7 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_hist_reduce", &m->hist_reduce},
         {"hare_hist_render", &m->hist_render},
         {"hare_hist_project", &m->hist_project},
+        {"hare_hist_project_channels", &m->hist_project_channels},
         {"hare_convolve", &m->convolve},
         {"hare_decode", &m->decode},
         {"hare_hist_impulses", &m->hist_impulses},

@@ -679,7 +679,8 @@ struct ReduceArgs {
 };
 
 // hare_hist_project (project.hip): a receive histogram projected onto caller-supplied integer vectors over the bins, per receiver and band
-// (include/hare_hip.h, "receivers", "Projection").  Everything but the four buffers by value
+// (include/hare_hip.h, "receivers", "Projection").  Everything but the four buffers by value.  hare_hist_project_channels
+// (project_channels.hip, "Directional projection") takes the same arguments: it reads every channel and writes K x bands x n_vec x channels x 2 words
 constexpr int kMaxProjectVectors = 32;
 constexpr int kProjectGroup = 8;           // vectors a sweep over the receiver's block carries (project.hip)
 struct ProjectArgs {

@@ -1,5 +1,5 @@
 // hist.cpp -- what runs on a receive histogram once it is on the device (include/hare_hip.h, "receivers"): the reduction (hare_hist_reduce
-// / _device; the kernel: reduce.hip), the projection (hare_hist_project / _device; project.hip), the rendering (hare_hist_render /
+// / _device; the kernel: reduce.hip), the projection (hare_hist_project / _device; project.hip) and its directional form (hare_hist_project_channels / _device; project_channels.hip), the rendering (hare_hist_render /
 // _device; render.hip), the impulses of a per-sample histogram (hare_hist_impulses / _device; impulses.hip) and, on the rendered rows, the convolution with a dry signal (hare_convolve / _device; convolve.hip) and the
 // decoding through a matrix of FIR filters (hare_decode / _device; decode.hip).  A call is its own check and its own enqueue; what the calls share is the device prelude (device_call, launch.h),
 // the overlap test (spans_overlap, scene.h), one byte count per buffer, used by the check and by the staging, and the staging of the
@@ -158,9 +158,10 @@ struct ProjectBytes {
     size_t hist, weight, coef, proj;
 };
 
-// everything both project calls check before anything runs, in the header's order; buffers device or host
+// everything the project calls check before anything runs, in the header's order; buffers device or host.  out_channels: 1 for the
+// projection of W, `channels` for the directional projection, whose output holds every channel
 int project_check(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t channels, const void* hist, const void* weight, int32_t J,
-                  const void* coef, const void* proj, ProjectBytes& z)
+                  const void* coef, const void* proj, int32_t out_channels, ProjectBytes& z)
 {
     auto bad = [&](const std::string& what) {
         set_error(std::string(who) + ": " + what);
@@ -170,7 +171,7 @@ int project_check(const char* who, int64_t K, int32_t n_bins, int32_t B, int32_t
     if (J < 1 || J > kMaxProjectVectors) return bad("J out of range (1 .. 32)");
     if (!hist || !coef || !proj) return bad("null histogram / coefficients / output");
     z = {hist_bytes(K, n_bins, B, channels), weight_bytes(n_bins, B), (size_t)J * (size_t)n_bins * sizeof(int32_t),
-         (size_t)K * (size_t)B * (size_t)J * 2 * sizeof(uint64_t)};
+         (size_t)K * (size_t)B * (size_t)J * (size_t)out_channels * 2 * sizeof(uint64_t)};
     if (spans_overlap({{proj, z.proj}, {hist, z.hist}, {weight, z.weight}, {coef, z.coef}}, 1))
         return bad("the output must not overlap the histogram, the weights or the coefficients");
     return HARE_OK;
@@ -195,6 +196,29 @@ int project_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, 
     a.n_vec = J;
     void* args[] = {&a};
     return launch(H, s.module->hist_project, (unsigned)K, 256, 0, st, args);         // a workgroup per receiver
+}
+
+// ---- the directional projection (include/hare_hip.h, "receivers", "Directional projection"; the kernel: project_channels.hip): the
+// projection's checks (project_check with out_channels = channels) and one launch with the projection's arguments
+int project_channels_enqueue(const Scene& s, const HipApi* H, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist,
+                             const void* d_weight, int32_t J, const void* d_coef, void* d_proj, hipStream_t st)
+{
+    if (!s.module || !s.module->hist_project_channels) {
+        set_error("hare_hist_project_channels missing from code object");
+        return HARE_E_STATE;
+    }
+    ProjectArgs a;
+    memset(&a, 0, sizeof a);
+    a.hist = (const unsigned long long*)d_hist;
+    a.weight = (const uint32_t*)d_weight;
+    a.coef = (const int32_t*)d_coef;
+    a.proj = (unsigned long long*)d_proj;
+    a.n_bins = n_bins;
+    a.bands = B;
+    a.channels = channels;
+    a.n_vec = J;
+    void* args[] = {&a};
+    return launch(H, s.module->hist_project_channels, (unsigned)K, 256, 0, st, args);         // a workgroup per receiver
 }
 
 // ---- the rendering (include/hare_hip.h, "receivers", "Rendering"; the kernel: render.hip)
@@ -480,7 +504,7 @@ int hare_hist_project_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B
 {
     if (!s) return null_scene();
     ProjectBytes z;
-    if (int rc = project_check("hare_hist_project_device", K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj, z)) return rc;
+    if (int rc = project_check("hare_hist_project_device", K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj, 1, z)) return rc;
     return device_call(*s, [&](const HipApi* H) {
         return project_enqueue(*s, H, K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj, (hipStream_t)stream);
     });
@@ -491,10 +515,35 @@ int hare_hist_project(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32
 {
     if (!s) return null_scene();
     ProjectBytes z;
-    if (int rc = project_check("hare_hist_project", K, n_bins, B, channels, hist, weight, J, coef, proj, z)) return rc;
+    if (int rc = project_check("hare_hist_project", K, n_bins, B, channels, hist, weight, J, coef, proj, 1, z)) return rc;
     return device_call(*s, [&](const HipApi* H) {
         const StagePart parts[] = {{z.hist, hist, nullptr}, {z.proj, nullptr, proj}, {z.coef, coef, nullptr}, {weight ? z.weight : 0, weight, nullptr}};
         return staged_run(H, parts, [&](void* const* d) { return project_enqueue(*s, H, K, n_bins, B, channels, d[0], d[3], J, d[2], d[1], nullptr); });
+    });
+}
+
+int hare_hist_project_channels_device(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void* d_hist,
+                                      const void* d_weight, int32_t J, const void* d_coef, void* d_proj, void* stream)
+{
+    if (!s) return null_scene();
+    ProjectBytes z;
+    if (int rc = project_check("hare_hist_project_channels_device", K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj, channels, z)) return rc;
+    return device_call(*s, [&](const HipApi* H) {
+        return project_channels_enqueue(*s, H, K, n_bins, B, channels, d_hist, d_weight, J, d_coef, d_proj, (hipStream_t)stream);
+    });
+}
+
+int hare_hist_project_channels(hare_scene* s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t* hist,
+                               const uint32_t* weight, int32_t J, const int32_t* coef, uint64_t* proj)
+{
+    if (!s) return null_scene();
+    ProjectBytes z;
+    if (int rc = project_check("hare_hist_project_channels", K, n_bins, B, channels, hist, weight, J, coef, proj, channels, z)) return rc;
+    return device_call(*s, [&](const HipApi* H) {
+        const StagePart parts[] = {{z.hist, hist, nullptr}, {z.proj, nullptr, proj}, {z.coef, coef, nullptr}, {weight ? z.weight : 0, weight, nullptr}};
+        return staged_run(H, parts, [&](void* const* d) {
+            return project_channels_enqueue(*s, H, K, n_bins, B, channels, d[0], d[3], J, d[2], d[1], nullptr);
+        });
     });
 }
 

@@ -25,6 +25,7 @@
 //   hare_convolve               rows of doubles convolved with one signal in the time domain: FP64, one sequential sum per output (convolve.hip)
 //   hare_decode                 rows of doubles decoded through a matrix of FIR filters: FP64, one sequential sum per output over channels and taps (decode.hip)
 //   hare_hist_project           a receive histogram projected onto up to 32 integer vectors over the bins, exact 128-bit sums (project.hip)
+//   hare_hist_project_channels  the same for every channel of a directional histogram: signed words, a thread per band and channel (project_channels.hip)
 //   hare_cull_audit             tests only: FP32 cull vs exact test on every ray x polygon pair
 //   hare_vb_*, hare_scan_*, hare_ob_*  Voxel_Grid / Octree construction (build_kernels.hip, included at the end)
 //
@@ -1973,6 +1974,7 @@ __global__ __launch_bounds__(256) void hare_occlusion(const XEventRec* ev, const
 #include "convolve.hip"        // hare_convolve: rows of doubles convolved with one signal in the time domain, FP64, stated sum order (hare_convolve_device)
 #include "decode.hip"          // hare_decode: K x C rows decoded to K x O through O x C FIR filters, the convolution's tile, stated sum order (hare_decode_device)
 #include "project.hip"         // hare_hist_project: a receive histogram projected onto integer vectors over the bins (hare_hist_project_device)
+#include "project_channels.hip"  // hare_hist_project_channels: the same for every channel of a directional histogram, signed words (hare_hist_project_channels_device)
 #include "voxel_pool.hip"
 #include "octree_pool.hip"
 #include "octree_group.hip"

@@ -136,6 +136,7 @@ struct DeviceModule {
     hipFunction_t hist_reduce = nullptr;                                   // reduce.hip
     hipFunction_t hist_render = nullptr;                                   // render.hip
     hipFunction_t hist_project = nullptr;                                  // project.hip
+    hipFunction_t hist_project_channels = nullptr;                         // project_channels.hip
     hipFunction_t convolve = nullptr;                                      // convolve.hip
     hipFunction_t decode = nullptr;                                        // decode.hip
     hipFunction_t hist_impulses = nullptr;                                 // impulses.hip

@@ -768,6 +768,28 @@ class Spatial_Partition:
         check(lib.hare_hist_project_device(self._h, int(K), int(n_bins), int(B), int(channels), d_hist or None, d_weight or None, int(J),
                                            d_coef or None, d_proj or None, stream or None))
 
+    def hist_project_channels(self, hist, coef, weight=None, as_int: bool = False):
+        """hare_hist_project_channels: hist_project for EVERY channel of a histogram [K, n_bins, B] or [K, n_bins, B, C] (C = 4, 9 or 16) of
+        uint64 (include/hare_hip.h, "receivers", "Directional projection"): channel 0 unsigned, the channels after it two's-complement
+        int64, weighted with a floor towards minus infinity.  coef: int32 [J, n_bins], 1 <= J <= 32; weight: uint32 [n_bins, B]
+        (air_weights) or None.  Returns uint64 [K, B, J, C, 2], the (lo, hi) words of the exact 128-bit two's-complement sums over the bins
+        of coef[j, i] * g[k, i, b, ch], or with as_int an object array [K, B, J, C] of Python integers (proj_to_int).  hare_amd.spatial
+        turns them into the intensity vector, the second moments and the lateral fraction."""
+        hist, K, nb, B, channels = _hist_shape(hist)
+        coef = _project_coef(coef, nb)
+        w, *_ = _reduce_spec(dict(weight=weight), nb, B)
+        proj = np.zeros((K, B, coef.shape[0], channels, 2), np.uint64)
+        check(lib.hare_hist_project_channels(self._h, K, nb, B, channels, ptr(hist), ptr(w), coef.shape[0], ptr(coef), ptr(proj)))
+        return proj_to_int(proj) if as_int else proj
+
+    def hist_project_channels_device(self, K: int, n_bins: int, B: int, channels: int, d_hist: int, J: int, d_coef: int, d_proj: int,
+                                     d_weight: int = 0, stream: int = 0):
+        """hare_hist_project_channels_device on raw device addresses + a hipStream_t: d_hist as receive_device accumulates it, d_coef
+        (J x n_bins int32), d_proj (K x B x J x channels x 2 uint64) written, d_weight (n_bins x B uint32) or 0.  Stream-ordered: no
+        allocation, no free, no wait, no upload."""
+        check(lib.hare_hist_project_channels_device(self._h, int(K), int(n_bins), int(B), int(channels), d_hist or None, d_weight or None,
+                                                    int(J), d_coef or None, d_proj or None, stream or None))
+
     def hist_render(self, hist, taps, M: int, frac_bits: int, seed: int = 0, weight=None):
         """hare_hist_render: a histogram [K, n_bins, B] or [K, n_bins, B, C] (C = 4, 9 or 16) of uint64, as the receive calls return it,
         rendered on this partition's device to impulse responses (include/hare_hip.h, "receivers", "Rendering"): M samples per bin, taps

@@ -923,6 +923,37 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * the sum of the shards' projections is exactly the projection of the summed histogram; with weights each shard's floor() is taken on its
  * own words, so g of the shards sums to at most one unit per bin, band and shard less than g of the summed histogram.
  *
+ * Directional projection (hare_hist_project_channels_device, hare_hist_project_channels).  The projection reads W and drops the direction
+ * a directional histogram recorded.  This call projects EVERY channel, so that the spatial parameters -- the intensity vector, the lateral
+ * energy fraction LF, the late lateral level, a modulation transfer function per direction -- are formed where a map's histogram lies.
+ * Inputs: exactly those of "Projection" -- the histogram (K x n_bins x B entries of `channels` 1, 4, 9 or 16 words, channel innermost), the
+ * optional weight (n_bins x B uint32, units of 2^-32) and coef (J x n_bins int32, vector-major, 1 <= J <= 32, every int32 value legal).
+ * Word 0 of an entry is the unsigned W word, as in "Reduction"; the words ch >= 1 are read as two's-complement int64, as the receive loop
+ * wrote them ("Directional", "Higher orders"):
+ *
+ *   h(k, i, b, ch) = hist[((k * n_bins + i) * B + b) * channels + ch]                     ch = 0: uint64;  ch >= 1: (int64)
+ *   g(k, i, b, ch) = weight ? floor(h * weight[i * B + b] / 2^32) : h
+ *                    floor towards minus infinity for a negative h: (h * w) >> 32 on unbounded integers; h = -1, w = 1 gives -1, not 0
+ *   proj[(((k * B + b) * J + j) * channels + ch) * 2 + 0 .. 1] = lo, hi of   sum over i of  (int128) c_j[i] * g(k, i, b, ch)
+ *
+ * the exact signed sum as a 128-bit two's-complement integer, lo then hi.  Nothing wraps: |c| <= 2^31, |g| < 2^64 and
+ * n_bins x channels <= 2^27 give |P| < 2^122.  Consequences: the column ch = 0 is hare_hist_project's result bit for bit; with
+ * channels = 1 the call IS hare_hist_project; with weight NULL the result is additive over shards, as 128-bit integers: the sum of the
+ * shards' projections is exactly the projection of the summed histogram; with weights each shard's floor() is taken on its own words, so g
+ * of the shards sums to at most one unit per bin, band, channel and shard less than g of the summed histogram.
+ * What the caller does with it.  With 0 / 1 window vectors as c (and any other vector: an MTF table gives a modulation transfer function
+ * per channel), per receiver, band and window, writing W, X, ... Y8 for the projections of the channels 0 .. 8:
+ *   the intensity vector  I = (X, Y, Z) / W, the energy-weighted mean arrival direction, and 1 - |I| a diffuseness figure;
+ *   the energy-weighted second moments of the arrival vector a, from the order-2 channels, with the SN3D polynomials of "Higher orders"
+ *   and x^2 + y^2 + z^2 = 1:   zz = (2 Y6 + W) / 3;   xx - yy = 2 Y8 / sqrt(3), xx + yy = W - zz;   xy = Y4 / sqrt(3),
+ *   yz = Y5 / sqrt(3),  xz = Y7 / sqrt(3)  -- hence the energy-weighted (a . u)^2 = u^T M u for any unit axis u;
+ *   the early lateral energy fraction LF = M_uu(early window, 5 .. 80 ms) / W(0 .. 80 ms), u the axis through the listener's ears, and the
+ *   late lateral level from M_uu(80 ms .. end) against a reference energy.
+ * frac_bits cancels in every ratio; each rint of a deposit moved a signed word by at most 1/2, so none of these is exact, unlike the sums
+ * they are formed from.  LFC, the |cos| form of the lateral fraction, is not a polynomial of the arrival vector: it cannot be formed
+ * from these channels and is not offered.  One workgroup projects one receiver, as in "Reduction".  There is no sharded variant and no
+ * _projected receive call: a device caller enqueues hare_hist_project_channels_device behind hare_receive_device on the same stream.
+ *
  * Rendering (hare_hist_render_device, hare_hist_render).  The other thing wanted from a histogram is a pressure impulse response to listen
  * to: band-filtered noise shaped by the energy envelope, weighted per channel by the direction the histogram recorded -- the usual
  * rendering of the late part of a ray-traced response.  A pure function of the histogram, a seed and a filter table, formed on the device.
@@ -1181,6 +1212,19 @@ HARE_API int hare_hist_project_device(hare_scene *s, int32_t K, int32_t n_bins, 
 /* The same from host buffers: one allocation, upload, project, download, one synchronisation. */
 HARE_API int hare_hist_project(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t *hist,
                                const uint32_t *weight /* nullable */, int32_t J, const int32_t *coef, uint64_t *proj);
+/* The projection of every channel of a histogram ("receivers", "Directional projection" above) on DEVICE buffers: one launch,
+ * stream-ordered like hare_hist_project_device -- no allocation, no free, no wait, no upload.  d_coef (J x n_bins int32) is a device buffer
+ * of the caller's; d_weight nullable; d_proj (K x B x J x channels x 2 uint64) is WRITTEN, every word once.  Checked before anything runs
+ * (HARE_E_INVALID), in this order, as hare_hist_project_device checks: 1 <= K <= 65 536, n_bins >= 1, 1 <= B <= 8, channels 1, 4, 9 or
+ * 16, K x n_bins x B x channels <= 2^27; 1 <= J <= 32; null buffers; proj overlapping the histogram, the weights or the coefficients.
+ * Then HARE_E_NODEVICE, then HARE_E_STATE.  The scene names the device; its geometry is not read.  Behind hare_receive_device on the same
+ * stream it projects the histogram that call accumulated. */
+HARE_API int hare_hist_project_channels_device(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const void *d_hist,
+                                               const void *d_weight /* nullable */, int32_t J, const void *d_coef, void *d_proj,
+                                               void *stream);
+/* The same from host buffers: one allocation, upload, project, download, one synchronisation. */
+HARE_API int hare_hist_project_channels(hare_scene *s, int32_t K, int32_t n_bins, int32_t B, int32_t channels, const uint64_t *hist,
+                                        const uint32_t *weight /* nullable */, int32_t J, const int32_t *coef, uint64_t *proj);
 /* The rendering of a histogram ("receivers", "Rendering" above) on DEVICE buffers: one launch, stream-ordered like hare_shoot_device -- no
  * allocation, no free, no wait.  d_taps (B x T doubles) is a device buffer of the caller's: the call has nothing to upload.  d_weight
  * nullable; d_out (K x channels x n_bins x M doubles) is WRITTEN, every word once.  Checked before anything runs (HARE_E_INVALID), in this
