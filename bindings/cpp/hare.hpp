@@ -440,6 +440,39 @@ public:
         detections.assign((size_t)K * 2, 0);
         check(hare_source_paths(scene_, kind_, top_index, n_weight, flags, n_bins, bin_len, frac_bits, hist.data(), detections.data()));
     }
+    // first-order edge diffraction (include/hare_hip.h, "receivers", "Edge diffraction (first order)").  SetEdges: the diffracting edges of
+    // Model[top_index] -- ends E x 6 (a, b), faces E x 2 (the polygons that meet in the edge, -1 for none), inv_lambda f_b / c per band; all
+    // empty removes the table.  DiffractPaths: one diffracted path per (edge, receiver) pair whose receiver the source does not see, Maekawa's
+    // 1 / (3 + 20 N), into a zeroed histogram K x n_bins x B (x 4, 9, 16 with directional and order); returns the pairs found
+    // (std::runtime_error, HARE_E_NOMEM, when the scene yields more than max_pairs).  Add it to SourcePaths' histogram word by word.
+    // DiffractDevice: the same ACCUMULATED on device pointers and a hipStream_t; d_work holds DiffractWorkBytes(K, max_pairs) bytes
+    void SetEdges(int top_index, const std::vector<double>& ends, const std::vector<int32_t>& faces, const std::vector<double>& inv_lambda)
+    {
+        if (ends.size() % 6 != 0 || faces.size() * 3 != ends.size()) throw std::invalid_argument("SetEdges: ends must hold E x 6 values and faces E x 2");
+        const bool none = ends.empty();
+        check(hare_scene_set_edges(scene_, top_index, (int32_t)(ends.size() / 6), none ? nullptr : ends.data(), none ? nullptr : faces.data(),
+                                   (int32_t)inv_lambda.size(), inv_lambda.empty() ? nullptr : inv_lambda.data()));
+    }
+    uint64_t DiffractPaths(int top_index, int64_t n_weight, int n_bins, double bin_len, int frac_bits, double max_detour, int64_t max_pairs,
+                           std::vector<uint64_t>& hist, std::vector<uint64_t>& detections, int K, int B, bool directional = false, int order = 1)
+    {
+        const uint32_t flags = directional ? HARE_RECEIVE_DIRECTIONAL | (order == 2 ? HARE_RECEIVE_ORDER2 : order == 3 ? HARE_RECEIVE_ORDER3 : 0u) : 0u;
+        const size_t channels = directional ? (order == 3 ? 16 : order == 2 ? 9 : 4) : 1;
+        if (K < 1 || B < 1 || n_bins < 1) throw std::invalid_argument("DiffractPaths: K, B and n_bins must be >= 1");
+        hist.assign((size_t)K * (size_t)n_bins * (size_t)B * channels, 0);
+        detections.assign((size_t)K * 2, 0);
+        uint64_t found = 0;
+        check(hare_diffract_paths(scene_, kind_, top_index, n_weight, flags, n_bins, bin_len, frac_bits, max_detour, max_pairs, hist.data(),
+                                  detections.data(), &found));
+        return found;
+    }
+    static int64_t DiffractWorkBytes(int64_t K, int64_t max_pairs) { return HARE_DIFFRACT_WORK_BYTES(K, max_pairs); }
+    void DiffractDevice(int top_index, int64_t n_weight, int n_bins, double bin_len, int frac_bits, double max_detour, int64_t max_pairs, void* d_work,
+                        void* d_hist, void* d_detections, bool directional = false, void* stream = nullptr)
+    {
+        check(hare_diffract_device(scene_, kind_, top_index, n_weight, directional ? HARE_RECEIVE_DIRECTIONAL : 0u, n_bins, bin_len, frac_bits,
+                                   max_detour, max_pairs, d_work, d_hist, d_detections, stream));
+    }
     // hare_convolve (include/hare_hip.h, "receivers", "Convolution"): the R rows of N doubles in ir -- the rows HistRender writes, R = K x
     // channels -- each convolved in the time domain with the one signal x; the samples n0 .. n0 + n_out - 1 of the N + L - 1 of the full
     // convolution into out, R x n_out.  n_out < 0: everything from n0 on

@@ -290,6 +290,19 @@ namespace Hare
             public static extern int hare_image2_device(IntPtr scene, int kind, int top_index, long n_weight, uint flags, int n_bins, double bin_len,
                                                         int frac_bits, long max_cands, long max_paths, IntPtr d_work, IntPtr d_hist, IntPtr d_detections,
                                                         IntPtr stream);
+            // first-order edge diffraction ("Edge diffraction (first order)"): the edge table of a topology (ends E x 6, faces E x 2, inv_lambda B),
+            // the deposit on device buffers (d_work: 256 + 68 K + 144 max_pairs bytes) and the same from host buffers (found: one word, nullable)
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_scene_set_edges(IntPtr scene, int top_index, int E, [In] double[] ends, [In] int[] faces, int B,
+                                                          [In] double[] inv_lambda);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_diffract_device(IntPtr scene, int kind, int top_index, long n_weight, uint flags, int n_bins, double bin_len,
+                                                          int frac_bits, double max_detour, long max_pairs, IntPtr d_work, IntPtr d_hist,
+                                                          IntPtr d_detections, IntPtr stream);
+            [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+            public static extern int hare_diffract_paths(IntPtr scene, int kind, int top_index, long n_weight, uint flags, int n_bins, double bin_len,
+                                                         int frac_bits, double max_detour, long max_pairs, [Out] ulong[] hist, [Out] ulong[] detections,
+                                                         [Out] ulong[] found);
             // the reduction of a histogram on the device (include/hare_hip.h, "receivers", "Reduction")
             [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
             public static extern int hare_hist_reduce_device(IntPtr scene, int K, int n_bins, int B, int channels, IntPtr d_hist, IntPtr d_weight,

@@ -13,6 +13,7 @@ from . import sti  # noqa: F401
 from . import spatial  # noqa: F401
 from . import decoders  # noqa: F401
 from . import scenes  # noqa: F401
+from . import edges  # noqa: F401
 
 __all__ = ["Ray", "X_Event", "Topology", "Spatial_Partition", "Voxel_Grid", "Octree", "KDTree",
            "HareError", "device_count", "scenes", "capi", "air_weights", "band_taps", "decay_levels", "proj_to_int", "sums_to_float",

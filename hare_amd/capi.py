@@ -133,6 +133,9 @@ SYMBOLS = {
     "hare_direct_device": (C.c_int, [_vp, _i32, _i32, _i64, _u32, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "hare_image_device": (C.c_int, [_vp, _i32, _i32, _i64, _u32, _i32, C.c_double, _i32, _i64, _vp, _vp, _vp, _vp]),
     "hare_image2_device": (C.c_int, [_vp, _i32, _i32, _i64, _u32, _i32, C.c_double, _i32, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "hare_scene_set_edges": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "hare_diffract_device": (C.c_int, [_vp, _i32, _i32, _i64, _u32, _i32, C.c_double, _i32, C.c_double, _i64, _vp, _vp, _vp, _vp]),
+    "hare_diffract_paths": (C.c_int, [_vp, _i32, _i32, _i64, _u32, _i32, C.c_double, _i32, C.c_double, _i64, _vp, _vp, _vp]),
     "hare_receive_source": (C.c_int, [_vp, _i32, _i32, _i64, _i64, _i32, _u32, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "hare_receive_source_sharded": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i64, _i32, _u32, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "hare_hist_reduce_device": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),

@@ -875,6 +875,20 @@ int hare_scene_get_option(const hare_scene* s, const char* name, int64_t* value)
         *value = scene_bands(*s, (int32_t)top);
         return HARE_OK;
     }
+    if (strcmp(name, "edges") == 0) {                 // hare_scene_set_edges: E of topology 0 (0: no table)
+        *value = scene_edges(*s, 0);
+        return HARE_OK;
+    }
+    if (strncmp(name, "edges:", 6) == 0) {            // ... of topology <top>
+        char* end = nullptr;
+        const long top = strtol(name + 6, &end, 10);
+        if (end == name + 6 || *end != '\0' || top < 0 || top >= (long)s->topos.size()) {
+            set_error(std::string("hare_scene_get_option: bad topology in ") + name);
+            return HARE_E_INVALID;
+        }
+        *value = scene_edges(*s, (int32_t)top);
+        return HARE_OK;
+    }
     if (strcmp(name, "scatter_seed") == 0) {
         *value = (int64_t)s->opt.scatter_seed;
         return HARE_OK;

@@ -41,7 +41,7 @@ void free_bounce_buffers(const HipApi* H, Scene& s)
         Scene::BounceBuf& b = c.bounce;
         if (b.copy_st) { (void)H->StreamSynchronize(b.copy_st); (void)H->StreamDestroy(b.copy_st); b.copy_st = nullptr; }
         for (void** p : {&b.rays[0], &b.rays[1], &b.excl[0], &b.excl[1], &b.excl2, &b.idx[0], &b.idx[1], &b.ev[0], &b.ev[1], &b.full,
-                         &b.tiles, &b.ctr, &b.state, &b.hist, &b.rain, &b.red, &b.direct, &b.image, &b.image2, &b.spec2})
+                         &b.tiles, &b.ctr, &b.state, &b.hist, &b.rain, &b.red, &b.direct, &b.image, &b.image2, &b.diffract, &b.spec2})
             dev_free(H, *p);
         b.cap = 0;
         b.ctr_cap = 0;
@@ -52,6 +52,7 @@ void free_bounce_buffers(const HipApi* H, Scene& s)
         b.direct_cap = 0;
         b.image_cap = 0;
         b.image2_cap = 0;
+        b.diffract_cap = 0;
         b.spec2_cap = 0;
     }
 }
@@ -740,6 +741,70 @@ extern "C" int hare_source_paths(hare_scene* s, int32_t kind, int32_t top_index,
     const CtxLease lease(*s, lk, [](const Scene::BatchCtx&) { return true; });       // (releases lk)
     Scene::BatchCtx* const c = lease.get();
     const int rc = source_paths_on_scene(*s, H, *c, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, hist, detections);
+    if (rc != HARE_OK && c->st[0]) (void)H->StreamSynchronize(c->st[0]);          // copies into the caller's buffers may still be in flight
+    return rc;
+    GUARD_END
+}
+
+// hare_diffract_paths: first-order edge diffraction from host buffers (include/hare_hip.h, "receivers", "Edge diffraction (first order)"),
+// built as hare_source_paths is: the histogram and the detections zeroed on a leased context's stream, diffract_enqueue, the three downloads,
+// one synchronisation
+static int diffract_paths_on_scene(Scene& s, const HipApi* H, Scene::BatchCtx& c, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags,
+                                   int32_t n_bins, double bin_len, int32_t frac_bits, double max_detour, int64_t max_pairs, uint64_t* hist,
+                                   uint64_t* det, uint64_t* found)
+{
+    Scene::BounceBuf& b = c.bounce;
+    const size_t K = s.rcv.size() / 4;
+    const size_t hist_words = receive_hist_words(s, top, n_bins, flags), hist_bytes = (hist_words + 2 * K) * sizeof(uint64_t);
+    if (int rc = grow(H, b.hist, b.hist_cap, hist_bytes)) return rc;
+    if (int rc = grow(H, b.diffract, b.diffract_cap, (size_t)HARE_DIFFRACT_WORK_BYTES(K, max_pairs))) return rc;
+    if (!c.st[0]) HIP_TRY(H->StreamCreate(&c.st[0]));
+    hipStream_t st = c.st[0];
+    uint64_t* const d_hist = (uint64_t*)b.hist;
+    uint64_t* const d_det = d_hist + hist_words;
+    HIP_TRY(H->MemsetAsync(b.hist, 0, hist_bytes, st));
+    if (int rc = diffract_enqueue(s, H, kind, top, n_weight, flags, n_bins, bin_len, frac_bits, max_detour, max_pairs, b.diffract, d_hist, d_det, st))
+        return rc;
+    HIP_TRY(H->MemcpyAsync(hist, d_hist, hist_words * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(H->MemcpyAsync(det, d_det, 2 * K * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    uint64_t pairs = 0;             // the last download, so that no return lies between it and the wait
+    HIP_TRY(H->MemcpyAsync(&pairs, b.diffract, sizeof pairs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(H->StreamSynchronize(st));
+    if (found) *found = pairs;
+    if (pairs > (uint64_t)max_pairs) {
+        set_error("hare_diffract_paths: the scene yields " + std::to_string(pairs) + " edge-receiver pairs, max_pairs is " + std::to_string(max_pairs) +
+                  " (needed: " + std::to_string(pairs) + ")");
+        return HARE_E_NOMEM;
+    }
+    return HARE_OK;
+}
+
+extern "C" int hare_diffract_paths(hare_scene* s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                                   int32_t frac_bits, double max_detour, int64_t max_pairs, uint64_t* hist, uint64_t* detections, uint64_t* found)
+{
+    const char* const who = "hare_diffract_paths";
+    if (int rc = diffract_call_check(who, s, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, max_detour, max_pairs)) return rc;
+    auto bad = [&](const std::string& what) {
+        set_error(std::string(who) + ": " + what);
+        return HARE_E_INVALID;
+    };
+    if (!hist || !detections) return bad("null histogram / detections");
+    const size_t K1 = std::max<size_t>(1, s->rcv.size() / 4);
+    if (spans_overlap({{hist, receive_hist_words(*s, top_index, n_bins, flags, 1) * sizeof(uint64_t)}, {detections, K1 * 2 * sizeof(uint64_t)}, {found, sizeof(uint64_t)}}, 3))
+        return bad("histogram, detections and found must not overlap");
+    GUARD_BEGIN
+    DeviceGuard dev_guard(hip_api(nullptr), s->device);
+    const HipApi* H = nullptr;
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (int rc = ensure_device(*s, H)) return rc;
+    if (int rc = source_ready(*s, H, who)) return rc;
+    if (int rc = upload_polys(*s, H)) return rc;
+    if (int rc = receive_ready(*s, H, who)) return rc;
+    if (int rc = diffract_ready(*s, H, top_index, who)) return rc;
+    const CtxLease lease(*s, lk, [](const Scene::BatchCtx&) { return true; });       // (releases lk)
+    Scene::BatchCtx* const c = lease.get();
+    const int rc = diffract_paths_on_scene(*s, H, *c, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, max_detour, max_pairs, hist,
+                                           detections, found);
     if (rc != HARE_OK && c->st[0]) (void)H->StreamSynchronize(c->st[0]);          // copies into the caller's buffers may still be in flight
     return rc;
     GUARD_END

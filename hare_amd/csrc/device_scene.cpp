@@ -125,6 +125,8 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
         {"hare_image2_mirror", &m->image2_mirror},
         {"hare_image2_cands", &m->image2_cands},
         {"hare_image2_paths", &m->image2_paths},
+        {"hare_diffract_emit", &m->diffract_emit},
+        {"hare_diffract_pairs", &m->diffract_pairs},
     };
     for (auto& t : table) {
         hipError_t e = H->ModuleGetFunction(t.fn, m->mod, t.name);
@@ -132,12 +134,12 @@ int get_module(const HipApi* H, int device, const DeviceModule** out)
     }
     for (int i = 0; i < DeviceModule::kFamilies * 4; ++i)          // the voxel families, member by member
         if (H->ModuleGetFunction(&m->voxel[0][0][0] + i, m->mod, (&kVoxelKernelNames[0][0][0])[i]) != hipSuccess) (&m->voxel[0][0][0])[i] = nullptr;
-    // the kernels with a form per channel count (scene.h: kChannelSuffix): the receive step's five, the rain and the three deposits
-    const char* const channel_names[9] = {"hare_receive_reflect", "hare_receive_scatter", "hare_receive_scatter_rain", "hare_receive_reflect_map",
+    // the kernels with a form per channel count (scene.h: kChannelSuffix): the receive step's five, the rain and the four deposits
+    const char* const channel_names[10] = {"hare_receive_reflect", "hare_receive_scatter", "hare_receive_scatter_rain", "hare_receive_reflect_map",
                                           "hare_receive_scatter_map", "hare_rain_step", "hare_direct_deposit", "hare_image_deposit",
-                                          "hare_image2_deposit"};
-    hipFunction_t* const channel_fns[4] = {m->rain_step, m->direct_deposit, m->image_deposit, m->image2_deposit};
-    for (int f = 0; f < 9; ++f)
+                                          "hare_image2_deposit", "hare_diffract_deposit"};
+    hipFunction_t* const channel_fns[5] = {m->rain_step, m->direct_deposit, m->image_deposit, m->image2_deposit, m->diffract_deposit};
+    for (int f = 0; f < 10; ++f)
         for (int dir = 0; dir < 4; ++dir) {
             hipFunction_t* fn = f < 5 ? &m->receive[f][dir] : &channel_fns[f - 5][dir];
             if (H->ModuleGetFunction(fn, m->mod, (std::string(channel_names[f]) + kChannelSuffix[dir]).c_str()) != hipSuccess) *fn = nullptr;

@@ -660,6 +660,25 @@ struct Image2Args {
     int32_t prune;             // scene option "image2_prune"
 };
 
+// hare_diffract_emit / _pairs / _deposit[_dir] (diffract.hip): first-order edge diffraction (include/hare_hip.h, "receivers", "Edge
+// diffraction (first order)").  The shadow slots are ONE run of n_rcv + 2 max_pairs: slot k < n_rcv is receiver k's direct ray (as
+// hare_direct_emit writes it), slots n_rcv + 2 i and n_rcv + 2 i + 1 are pair i's legs apex -> center and apex -> source, t_max 1.0, both
+// faces of the edge as the two exclusion words.  The emission writes the direct rays, marks every pair slot -2 and zeroes *count; the pair
+// search (a lane per edge, the receivers streamed) appends the accepted pairs with their (k, j) in pair_kj; the flags-only occlusion kernels
+// answer the whole run; the deposit (a lane per pair) adds the words of the pairs whose receiver's direct ray is blocked and whose legs are free
+struct DiffractArgs {
+    DepositArgs d;             // S = n_rcv + 2 max_pairs
+    const double* ends;        // n_edges x 6: a, b
+    const int32_t* faces;      // n_edges x 2: the polygons that meet in the edge, -1 for none
+    unsigned long long* count; // the work block's first word: pairs found (may exceed max_pairs: then nothing is deposited)
+    int32_t* sexcl2;           // S second exclusion words (poly_origin2)
+    int32_t* pair_kj;          // 2 max_pairs: k, j per pair
+    long long max_pairs;
+    double max_detour;
+    double inv_lambda[kMaxBands];      // f_b / c per band, by value as DepositArgs::power
+    int32_t n_edges;
+};
+
 // hare_hist_reduce (reduce.hip): a receive histogram reduced to window sums and decay-level crossings per receiver and band
 // (include/hare_hip.h, "receivers", "Reduction").  Windows, levels and counts by value (276 of the struct's 312 bytes): no upload
 constexpr int kMaxReduceWindows = 16;

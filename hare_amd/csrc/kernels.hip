@@ -19,6 +19,7 @@
 //   hare_direct_emit / _deposit the direct sound: one visibility query and one deposit per receiver (direct.hip)
 //   hare_image_mirror / _pairs / _deposit  first-order image sources: the pair search receivers x polygons and its deposit (image.hip)
 //   hare_image2_mirror / _cands / _paths / _deposit  second-order image sources: candidates polygons x polygons, paths receivers x candidates (image2.hip)
+//   hare_diffract_emit / _pairs / _deposit  first-order edge diffraction: the pair search edges x receivers and its deposit (diffract.hip)
 //   hare_hist_reduce            a receive histogram reduced to window sums and decay crossings per receiver and band (reduce.hip)
 //   hare_hist_render            a receive histogram rendered to impulse responses per receiver and channel: shaped band noise (render.hip)
 //   hare_hist_impulses          a per-sample receive histogram turned into pressure rows: an impulse per non-empty (bin, band) through the band's FIR (impulses.hip)
@@ -1967,6 +1968,7 @@ __global__ __launch_bounds__(256) void hare_occlusion(const XEventRec* ev, const
 #include "direct.hip"          // hare_direct_emit / hare_direct_deposit[_dir]: the direct sound, a lane per receiver (hare_direct_device, HARE_RECEIVE_DIRECT)
 #include "image.hip"           // hare_image_mirror / _pairs / _deposit[_dir]: first-order image sources (hare_image_device, HARE_RECEIVE_IMAGE)
 #include "image2.hip"          // hare_image2_mirror / _cands / _paths / _deposit[_dir]: second-order image sources (hare_image2_device, HARE_RECEIVE_IMAGE2)
+#include "diffract.hip"        // hare_diffract_emit / _pairs / _deposit[_dir]: first-order edge diffraction, the pair search edges x receivers (hare_diffract_device)
 #include "hist_block.h"        // U128, weighted, band_total, Block: what the three kernels on a histogram share; no kernel
 #include "reduce.hip"          // hare_hist_reduce: window sums and decay crossings of a receive histogram (hare_hist_reduce_device)
 #include "render.hip"          // hare_hist_render: a receive histogram rendered to impulse responses, shaped band noise (hare_hist_render_device)

@@ -2,8 +2,9 @@
 // and its per-cast step (receive_plan, receive_step: what bounce_device_impl, launch.cpp, runs between its casts) and hare_receive_device
 // (include/hare_hip.h, "receivers"; the kernels: receive.hip); the point source (hare_scene_set_source, hare_emit_device; the kernel:
 // source.hip); the direct sound (direct_enqueue, hare_direct_device; the kernels: direct.hip); first-order image sources (image_enqueue,
-// hare_image_device; the kernels: image.hip) and second-order ones (image2_enqueue, hare_image2_device; the kernels: image2.hip).  The three
-// plans fill what their kernels share through deposit_fill and image_scene_fill, and the three calls check and prepare through
+// hare_image_device; the kernels: image.hip) and second-order ones (image2_enqueue, hare_image2_device; the kernels: image2.hip); first-order edge
+// diffraction (hare_scene_set_edges, diffract_enqueue, hare_diffract_device; the kernels: diffract.hip).  The
+// plans fill what their kernels share through deposit_fill and image_scene_fill, and the calls check and prepare through
 // deposit_call_check, deposit_buffers_check and deposit_call_run.  The host-buffer calls hare_receive_batch / _sharded and
 // hare_receive_source / _sharded are in bounce.cpp, beside the loop they share with hare_bounce_batch; what post-processes a histogram
 // (hare_hist_reduce, _project, _render) is in hist.cpp.
@@ -71,6 +72,10 @@ void free_receivers(const HipApi* H, Scene& s)
     dev_free(H, s.rmap.d_start);
     dev_free(H, s.rmap.d_items);
     dev_free(H, s.src.d_gain);
+    for (Scene::EdgeTable& t : s.edges) {
+        dev_free(H, t.d_ends);
+        dev_free(H, t.d_faces);
+    }
     for (std::vector<Scene::BandTable>* tables : {&s.alpha, &s.sigma})
         for (Scene::BandTable& t : *tables) dev_free(H, t.dev);
 }
@@ -528,6 +533,78 @@ int image2_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t
     return launch(H, m->image2_deposit[dir], (unsigned)((M + 255) / 256), 256, 0, st, args);
 }
 
+// ---- first-order edge diffraction (include/hare_hip.h, "receivers", "Edge diffraction (first order)"; the kernels: diffract.hip)
+int64_t scene_edges(const Scene& s, int32_t top)
+{
+    return (top >= 0 && (size_t)top < s.edges.size()) ? (int64_t)(s.edges[(size_t)top].ends.size() / 6) : 0;
+}
+
+static int upload_edges(Scene::EdgeTable& t, const HipApi* H)
+{
+    if (t.ends.empty() || t.on_device) return HARE_OK;
+    if (int rc = upload(H, &t.d_ends, t.ends.data(), t.ends.size() * sizeof(double))) return rc;
+    if (int rc = upload(H, &t.d_faces, t.faces.data(), t.faces.size() * sizeof(int32_t))) return rc;
+    t.on_device = true;
+    return HARE_OK;
+}
+
+// After the device checks: an edge table set for the topology, and on the device (uploads only what a setter run without a device left behind)
+int diffract_ready(Scene& s, const HipApi* H, int32_t top, const char* who)
+{
+    if (scene_edges(s, top) == 0) {
+        set_error(std::string(who) + ": no edges set (hare_scene_set_edges)");
+        return HARE_E_STATE;
+    }
+    return upload_edges(s.edges[(size_t)top], H);
+}
+
+// The scratch of a deposit, from d_work (a 16-byte boundary): 256 bytes whose first word is the pair count; then ONE run of K + 2 max_pairs
+// shadow slots, array by array -- the rays (48 B), t_max (8 B), poly_origin1, poly_origin2 and the occlusion flags (4 B each): 68 bytes a
+// slot -- and the pairs' k and j (8 B): 256 + 68 K + 144 max_pairs = HARE_DIFFRACT_WORK_BYTES
+int diffract_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                     int32_t frac_bits, double max_detour, int64_t max_pairs, void* d_work, void* d_hist, void* d_det, hipStream_t st)
+{
+    const int dir = receive_channel_form(flags);
+    const DeviceModule* const m = s.module;
+    if (!m || !m->diffract_emit || !m->diffract_pairs || !m->diffract_deposit[dir]) {
+        set_error("hare_diffract_emit / hare_diffract_pairs / hare_diffract_deposit missing from code object");
+        return HARE_E_STATE;
+    }
+    const Scene::EdgeTable& t = s.edges[(size_t)top];
+    const int64_t K = (int64_t)(s.rcv.size() / 4), E = scene_edges(s, top), M = max_pairs, S = K + 2 * M;
+    DiffractArgs a;
+    memset((void*)&a, 0, sizeof a);
+    DepositArgs& d = a.d;
+    char* const w = (char*)d_work;
+    a.count = (unsigned long long*)w;
+    d.srays = (RayRec*)(w + 256);
+    d.stmax = (double*)(d.srays + S);
+    d.sexcl = (int32_t*)(d.stmax + S);
+    a.sexcl2 = d.sexcl + S;
+    int32_t* const occ = a.sexcl2 + S;
+    d.socc = occ;
+    a.pair_kj = occ + S;
+    a.ends = (const double*)t.d_ends;
+    a.faces = (const int32_t*)t.d_faces;
+    a.max_pairs = M;
+    a.max_detour = max_detour;
+    memcpy(a.inv_lambda, t.inv_lambda, sizeof a.inv_lambda);
+    a.n_edges = (int32_t)E;
+    if (!deposit_fill(d, s, n_weight, n_bins, bin_len, frac_bits, d_hist, d_det) || !a.ends || !a.faces) {
+        set_error("edge diffraction: receivers, edges or directivity table not on the device");
+        return HARE_E_STATE;
+    }
+    void* args[] = {&a};
+    if (int rc = launch(H, m->diffract_emit, (unsigned)std::min<int64_t>((S + 255) / 256, 4096), 256, 0, st, args)) return rc;
+    {
+        // hare_diffract_pairs: (edge blocks) x (receiver tiles of 256): E <= 2^20 edges are 4 096 blocks, K <= 65 536 receivers 256 tiles
+        const unsigned gx = (unsigned)((E + 255) / 256), gy = (unsigned)((K + 255) / 256);
+        HIP_TRY(H->ModuleLaunchKernel(m->diffract_pairs, gx, gy, 1, 256, 1, 1, 0, st, args, nullptr));
+    }
+    if (int rc = shoot_device_impl(s, H, kind, top, S, d.srays, d.sexcl, a.sexcl2, HARE_SHOOT_RETIRED_RAYS, nullptr, nullptr, st, d.stmax, occ)) return rc;
+    return launch(H, m->diffract_deposit[dir], (unsigned)((M + 255) / 256), 256, 0, st, args);
+}
+
 // hare_scene_set_absorption / _scattering behind their own checks of top_index and B: P x B coefficients in [0, 1] become Model[top]'s
 // table `mine` (`name` in the messages), with the B of the topology's other table where it has one
 static int set_band_table(Scene& s, const char* who, const char* name, std::vector<Scene::BandTable>& mine, const std::vector<Scene::BandTable>& other,
@@ -661,7 +738,7 @@ using namespace hare;
 // ---- what hare_direct_device, hare_image_device and hare_image2_device share (the calls themselves are below).  Their checks fire in
 // this order: deposit_call_check, the call's own list lengths, deposit_buffers_check -- all HARE_E_INVALID, ahead of the device.
 // The scene, the weight and the numbers; flags comes back masked to what these calls read
-static int deposit_call_check(const char* who, const hare_scene* s, int32_t kind, int32_t top, int64_t n_weight, uint32_t& flags, int32_t n_bins,
+static int deposit_call_check(const char* who, const Scene* s, int32_t kind, int32_t top, int64_t n_weight, uint32_t& flags, int32_t n_bins,
                               double bin_len, int32_t frac_bits)
 {
     if (!s) {
@@ -677,6 +754,27 @@ static int deposit_call_check(const char* who, const hare_scene* s, int32_t kind
     if (int rc = receive_check_args(who, *s, flags, kind, top, 0, 1, n_bins, bin_len, frac_bits)) return rc;
     if (s->src.set && s->src.B != scene_bands(*s, top)) {
         set_error(std::string(who) + ": the source has " + std::to_string(s->src.B) + " bands, the topology " + std::to_string(scene_bands(*s, top)));
+        return HARE_E_INVALID;
+    }
+    return HARE_OK;
+}
+
+// hare_image_device's checks in its order, then the detour and the edge table's band count
+int hare::diffract_call_check(const char* who, const Scene* s, int32_t kind, int32_t top, int64_t n_weight, uint32_t& flags, int32_t n_bins,
+                              double bin_len, int32_t frac_bits, double max_detour, int64_t max_pairs)
+{
+    if (int rc = deposit_call_check(who, s, kind, top, n_weight, flags, n_bins, bin_len, frac_bits)) return rc;
+    if (max_pairs < 1 || max_pairs > ((int64_t)1 << 26)) {
+        set_error(std::string(who) + ": max_pairs out of range (1 .. 2^26)");
+        return HARE_E_INVALID;
+    }
+    if (!(max_detour >= 0)) {
+        set_error(std::string(who) + ": max_detour must be >= 0 (+inf: no limit)");
+        return HARE_E_INVALID;
+    }
+    if (s->src.set && scene_edges(*s, top) > 0 && s->src.B != s->edges[(size_t)top].B) {
+        set_error(std::string(who) + ": the source has " + std::to_string(s->src.B) + " bands, the edge table " +
+                  std::to_string(s->edges[(size_t)top].B));
         return HARE_E_INVALID;
     }
     return HARE_OK;
@@ -869,6 +967,67 @@ int hare_scene_set_source(hare_scene* s, const double pos[3], int32_t B, const d
     GUARD_END
 }
 
+int hare_scene_set_edges(hare_scene* s, int32_t top_index, int32_t E, const double* ends, const int32_t* faces, int32_t B, const double* inv_lambda)
+{
+    if (!s) {
+        set_error("null scene");
+        return HARE_E_INVALID;
+    }
+    auto bad = [&](const std::string& what) {
+        set_error("hare_scene_set_edges: " + what);
+        return HARE_E_INVALID;
+    };
+    if (top_index < 0 || top_index >= (int32_t)s->topos.size()) return bad("bad top_index");
+    if (E == 0 && !ends && !faces) {                 // removal
+        if (scene_edges(*s, top_index) == 0) return HARE_OK;
+        Scene::EdgeTable& t = s->edges[(size_t)top_index];
+        t.ends.clear();
+        t.faces.clear();
+        t.B = 0;
+        t.on_device = false;
+        const HipApi* H = (t.d_ends || t.d_faces) ? hip_api(nullptr) : nullptr;
+        if (H) {
+            DeviceGuard dev_guard(H, s->device);
+            dev_free(H, t.d_ends);
+            dev_free(H, t.d_faces);
+        }
+        return HARE_OK;
+    }
+    if (E < 1 || E > (1 << 20)) return bad("E out of range (1 .. 2^20; 0 with null arrays removes the table)");
+    if (!ends || !faces) return bad("null ends / faces");
+    const int64_t P = s->topos[(size_t)top_index].P;
+    for (int32_t j = 0; j < E; ++j) {
+        const double* const a = ends + 6 * (size_t)j;
+        for (int c = 0; c < 6; ++c)
+            if (!std::isfinite(a[c])) return bad("edge " + std::to_string(j) + " has a non-finite end");
+        const double ex = a[3] - a[0], ey = a[4] - a[1], ez = a[5] - a[2];
+        const double ee = (ex * ex + ey * ey) + ez * ez;
+        if (!(ee > 0 && std::isfinite(ee))) return bad("edge " + std::to_string(j) + " has no length (a == b), or one whose square overflows");
+    }
+    for (size_t k = 0; k < 2 * (size_t)E; ++k)
+        if (faces[k] < -1 || faces[k] >= P) return bad("faces[" + std::to_string(k) + "] outside -1 .. P - 1");
+    if (B < 1 || B > kMaxBands) return bad("bands out of range (1 .. 8)");
+    if (!inv_lambda) return bad("null inv_lambda");
+    for (int32_t b = 0; b < B; ++b)
+        if (!(inv_lambda[b] >= 0 && std::isfinite(inv_lambda[b]))) return bad("inv_lambda[" + std::to_string(b) + "] must be finite and >= 0");
+    GUARD_BEGIN
+    std::vector<double> e(ends, ends + 6 * (size_t)E);
+    std::vector<int32_t> f(faces, faces + 2 * (size_t)E);
+    if (s->edges.size() < s->topos.size()) s->edges.resize(s->topos.size());
+    Scene::EdgeTable& t = s->edges[(size_t)top_index];
+    t.ends.swap(e);
+    t.faces.swap(f);
+    t.B = B;
+    for (int32_t b = 0; b < kMaxBands; ++b) t.inv_lambda[b] = b < B ? inv_lambda[b] : 0.0;
+    t.on_device = false;
+    const HipApi* H = nullptr;
+    if (!device_present(H)) return HARE_OK;          // GPU-less: the table goes up with the first diffraction call
+    DeviceGuard dev_guard(H, s->device);
+    if (int rc = ensure_device(*s, H)) return rc;
+    return upload_edges(t, H);
+    GUARD_END
+}
+
 int hare_emit_device(hare_scene* s, int64_t n, int64_t first_ray, void* d_rays, void* d_state, void* stream)
 {
     if (!s) {
@@ -941,6 +1100,21 @@ int hare_image2_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n
     return deposit_call_run(*s, who, [&](const HipApi* H) {
         return image2_enqueue(*s, H, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, max_cands, max_paths, d_work, d_hist, d_detections,
                               (hipStream_t)stream);
+    });
+}
+
+int hare_diffract_device(hare_scene* s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                         int32_t frac_bits, double max_detour, int64_t max_pairs, void* d_work, void* d_hist, void* d_detections, void* stream)
+{
+    const char* const who = "hare_diffract_device";
+    if (int rc = diffract_call_check(who, s, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, max_detour, max_pairs)) return rc;
+    const size_t K = std::max<size_t>(1, s->rcv.size() / 4);
+    if (int rc = deposit_buffers_check(who, *s, top_index, flags, n_bins, d_work, (size_t)HARE_DIFFRACT_WORK_BYTES(K, max_pairs), true, d_hist, d_detections))
+        return rc;
+    return deposit_call_run(*s, who, [&](const HipApi* H) -> int {
+        if (int rc = diffract_ready(*s, H, top_index, who)) return rc;
+        return diffract_enqueue(*s, H, kind, top_index, n_weight, flags, n_bins, bin_len, frac_bits, max_detour, max_pairs, d_work, d_hist,
+                                d_detections, (hipStream_t)stream);
     });
 }
 

@@ -143,6 +143,7 @@ struct DeviceModule {
     hipFunction_t direct_emit = nullptr, direct_deposit[4] = {};           // direct.hip ([channel form])
     hipFunction_t image_mirror = nullptr, image_pairs = nullptr, image_deposit[4] = {};   // image.hip ([channel form])
     hipFunction_t image2_mirror = nullptr, image2_cands = nullptr, image2_paths = nullptr, image2_deposit[4] = {};   // image2.hip ([channel form])
+    hipFunction_t diffract_emit = nullptr, diffract_pairs = nullptr, diffract_deposit[4] = {};   // diffract.hip ([channel form])
     hipFunction_t octree_occl = nullptr, octree_occl_any = nullptr;
     hipFunction_t events_pack_slim = nullptr;
     hipFunction_t block_occ = nullptr;                                     // build_kernels.hip: hare_block_occ
@@ -271,8 +272,9 @@ struct Scene {
         void* direct = nullptr;         // hare_receive_source* with HARE_RECEIVE_DIRECT: hare_direct_device's scratch, HARE_DIRECT_WORK_BYTES(K)
         void* image = nullptr;          // hare_receive_source* with HARE_RECEIVE_IMAGE: hare_image_device's scratch, HARE_IMAGE_WORK_BYTES(K, P, "image_max_pairs"), grown on demand
         void* image2 = nullptr;         // ... with HARE_RECEIVE_IMAGE2: hare_image2_device's scratch, HARE_IMAGE2_WORK_BYTES(P, "image2_max_cands", "image2_max_paths"), grown on demand
+        void* diffract = nullptr;       // hare_diffract_paths: hare_diffract_device's scratch, HARE_DIFFRACT_WORK_BYTES(K, max_pairs), grown on demand
         void* spec2 = nullptr;          // ... on a topology with a scattering table: the loop's byte per ray (ReceiveArgs::spec2)
-        size_t state_cap = 0, hist_cap = 0, rain_cap = 0, red_cap = 0, direct_cap = 0, image_cap = 0, image2_cap = 0, spec2_cap = 0;     // bytes
+        size_t state_cap = 0, hist_cap = 0, rain_cap = 0, red_cap = 0, direct_cap = 0, image_cap = 0, image2_cap = 0, diffract_cap = 0, spec2_cap = 0;     // bytes
         int64_t cap = 0;
         int32_t ctr_cap = 0;
         hipStream_t copy_st = nullptr;
@@ -349,6 +351,16 @@ struct Scene {
         bool same_as(const Source& o) const;     // what the sharded call compares
     };
     Source src;
+    // the diffracting edges of a topology (hare_scene_set_edges, receive.cpp): kept and uploaded as the receivers are
+    struct EdgeTable {
+        std::vector<double> ends;                // E x 6: a, b (empty: no table)
+        std::vector<int32_t> faces;              // E x 2
+        int32_t B = 0;
+        double inv_lambda[kMaxBands] = {};
+        void *d_ends = nullptr, *d_faces = nullptr;
+        bool on_device = false;
+    };
+    std::vector<EdgeTable> edges;                // per topology, sized by the first hare_scene_set_edges
 };
 // One of the scene's staging contexts, held for a host-buffer call: concurrent callers (Pachyderm's worker threads) run side by side, each
 // on a context of its own.  Constructed with s.mu held through `lk`: waits for a free context, prefers a free one that `fits` (already
@@ -494,6 +506,19 @@ int image_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t 
 // paths found.  Source, receivers and tables must be on the device
 int image2_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
                    int32_t frac_bits, int64_t max_cands, int64_t max_paths, void* d_work, void* d_hist, void* d_det, hipStream_t st);
+// first-order edge diffraction (receive.cpp; include/hare_hip.h, "receivers", "Edge diffraction (first order)").  scene_edges: E of Model[top]'s
+// edge table (0: none).  diffract_ready: a table is set for `top` (HARE_E_STATE) and on the device.  diffract_enqueue: hare_diffract_emit,
+// hare_diffract_pairs, ONE flags-only occlusion query of K + 2 * max_pairs slots and hare_diffract_deposit[_dir] on the stream; d_work:
+// HARE_DIFFRACT_WORK_BYTES(K, max_pairs) of scratch from a 16-byte boundary, its first word the number of pairs found.  Source and receivers
+// must be on the device
+int64_t scene_edges(const Scene& s, int32_t top);
+int diffract_ready(Scene& s, const HipApi* H, int32_t top, const char* who);
+int diffract_enqueue(Scene& s, const HipApi* H, int32_t kind, int32_t top, int64_t n_weight, uint32_t flags, int32_t n_bins, double bin_len,
+                     int32_t frac_bits, double max_detour, int64_t max_pairs, void* d_work, void* d_hist, void* d_det, hipStream_t st);
+// what hare_diffract_device and hare_diffract_paths check ahead of their buffers, in hare_image_device's order (HARE_E_INVALID); flags
+// comes back masked to the channel flags
+int diffract_call_check(const char* who, const Scene* s, int32_t kind, int32_t top, int64_t n_weight, uint32_t& flags, int32_t n_bins,
+                        double bin_len, int32_t frac_bits, double max_detour, int64_t max_pairs);
 // The reduction of a receive histogram (hist.cpp; include/hare_hip.h, "receivers", "Reduction").  ReduceSpec: what the caller asks for,
 // host pointers (weight: n_bins x B, nullable).  reduce_check_spec: the checks that need no buffer (HARE_E_INVALID); reduce_enqueue:
 // hare_hist_reduce on the stream, device buffers, win and levels read here

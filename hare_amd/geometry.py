@@ -554,6 +554,22 @@ class Spatial_Partition:
         check(lib.hare_scene_set_source(self._h, ptr(p), int(B), ptr(w), ptr(f), 0 if g is None else g.shape[1], ptr(g)))
         return self
 
+    def set_edges(self, ends, faces, inv_lambda, top_index: int = 0):
+        """hare_scene_set_edges: the diffracting edges of Model[top_index] (include/hare_hip.h, "receivers", "Edge diffraction (first
+        order)").  ends [E, 2, 3] (or [E, 6]): a and b of every edge; faces int32 [E, 2]: the polygons that meet in it, -1 for none;
+        inv_lambda [B]: f_b / c per band (hare_amd.edges.band_inv_lambda).  hare_amd.edges.find_edges proposes ends and faces from a
+        topology.  ends None removes the table."""
+        if ends is None:
+            check(lib.hare_scene_set_edges(self._h, int(top_index), 0, None, None, 0, None))
+            return self
+        e = np.ascontiguousarray(ends, np.float64).reshape(-1, 6)
+        f = np.ascontiguousarray(faces, np.int32).reshape(-1, 2)
+        w = np.ascontiguousarray(inv_lambda, np.float64).reshape(-1)
+        if f.shape[0] != e.shape[0]:
+            raise ValueError("one pair of faces per edge")
+        check(lib.hare_scene_set_edges(self._h, int(top_index), e.shape[0], ptr(e), ptr(f), w.shape[0], ptr(w)))
+        return self
+
     def emit_device(self, n: int, d_rays: int, d_state: int, first_ray: int = 0, stream: int = 0):
         """hare_emit_device on raw device addresses + a hipStream_t: the source's rays first_ray .. first_ray + n - 1 into d_rays (n x 48 B)
         and their state into d_state ((1 + B) x n doubles, B = get_option("source_bands")).  Stream-ordered."""
@@ -960,6 +976,40 @@ class Spatial_Partition:
         check(lib.hare_image2_device(self._h, self._kind, int(top_index), int(n_weight), capi.channel_flags(directional, order),
                                      int(n_bins), float(bin_len), int(frac_bits), int(max_cands), int(max_paths), d_work or None, d_hist or None,
                                      d_detections or None, stream or None))
+
+    @staticmethod
+    def diffract_work_bytes(K: int, max_pairs: int) -> int:
+        """Bytes of diffract_device's d_work for K receivers and a list of max_pairs pairs: HARE_DIFFRACT_WORK_BYTES(K, max_pairs)."""
+        return 256 + 68 * int(K) + 144 * int(max_pairs)
+
+    def diffract_device(self, n_weight: int, n_bins: int, bin_len: float, frac_bits: int, max_pairs: int, d_work: int, d_hist: int,
+                        d_detections: int, max_detour: float = float("inf"), top_index: int = 0, directional: bool = False, stream: int = 0, *,
+                        order: int = 1):
+        """hare_diffract_device on raw device addresses + a hipStream_t: first-order edge diffraction of the scene's source over the edges
+        of set_edges (include/hare_hip.h, "Edge diffraction (first order)") -- the pair search edges x receivers, two shadow rays per
+        accepted pair and one deposit per pair whose receiver the source does not see and whose legs are free, standing for n_weight
+        source rays -- accumulated into d_hist and d_detections (shaped as direct_device's); d_work holds
+        diffract_work_bytes(K, max_pairs) bytes on a 16-byte boundary and its first uint64 receives the number of pairs found (more than
+        max_pairs: nothing was deposited).  Stream-ordered: no allocation, no free, no wait."""
+        check(lib.hare_diffract_device(self._h, self._kind, int(top_index), int(n_weight), capi.channel_flags(directional, order),
+                                       int(n_bins), float(bin_len), int(frac_bits), float(max_detour), int(max_pairs), d_work or None,
+                                       d_hist or None, d_detections or None, stream or None))
+
+    def Diffract_paths(self, n_weight: int, n_bins: int, bin_len: float, max_pairs: int, frac_bits: int = 40, max_detour: float = float("inf"),
+                       top_index: int = 0, directional: bool = False, *, order: int = 1):
+        """hare_diffract_paths: the same from the host, into a zeroed histogram.  Returns (hist uint64 [K, n_bins, B] or [K, n_bins, B, C],
+        detections uint64 [K, 2], pairs found); a HareError with HARE_E_NOMEM, the count in its message and in its `found`, when the scene
+        yields more than max_pairs pairs.  Add it to Source_paths' or a receive call's histogram as wrapping uint64 words."""
+        shape = self._receive_shape(top_index, n_bins, bool(directional), order=order)
+        K = max(shape[0], 0)
+        hist, det, found = np.zeros((K,) + shape[1:], np.uint64), np.zeros((K, 2), np.uint64), np.zeros(1, np.uint64)
+        try:
+            check(lib.hare_diffract_paths(self._h, self._kind, int(top_index), int(n_weight), capi.channel_flags(directional, order), int(n_bins),
+                                          float(bin_len), int(frac_bits), float(max_detour), int(max_pairs), ptr(hist), ptr(det), ptr(found)))
+        except capi.HareError as e:
+            e.found = int(found[0])
+            raise
+        return hist, det, int(found[0])
 
     @staticmethod
     def receive_work_bytes(n: int, rain: bool = False, image2: bool = False) -> int:

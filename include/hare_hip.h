@@ -261,6 +261,7 @@ HARE_API int hare_scene_set_option(hare_scene *s, const char *name, int64_t valu
  *   "receivers", "bands"    K of hare_scene_set_receivers (0: none set) and B of topology 0's absorption / scattering tables (1: none);
  *   "bands:<top>"           B of topology <top> (e.g. "bands:1"; HARE_E_INVALID for a topology the scene does not have)
  *   "source", "source_bands", "source_res"   1 when hare_scene_set_source has set a source (0: none), its B and its table's R (0: no table)
+ *   "edges", "edges:<top>"  E of hare_scene_set_edges for topology 0 and for topology <top> (0: no table)
  * No reference counterpart: Hare has no device memory to account for. */
 HARE_API int hare_scene_get_option(const hare_scene *s, const char *name, int64_t *value);
 
@@ -817,6 +818,52 @@ HARE_API int hare_bounce_batch_sharded(hare_scene *const *scenes, int32_t n_scen
  * margins of 1e-9 of the coordinates' size.  Non-finite values, a pyramid wider than a right angle and coordinates whose squares overflow
  * take every pair.  The filter never decides a result: histogram, detections and the path count are the same with 0 and 1.
  *
+ * Edge diffraction (first order) (hare_scene_set_edges; hare_diffract_device, hare_diffract_paths).  A receiver that the source cannot see
+ * gets nothing from the direct sound, and a barrier, a balcony front or a column would cast a hard acoustic shadow.  The engineering remedy
+ * is ONE diffracted path over each edge, source -> apex on the edge -> receiver, attenuated by Maekawa's thin-screen rule.  The edges are
+ * the caller's: hare_scene_set_edges takes, per topology, E segments a -> b with the two polygons that meet in each (faces, numbered as
+ * poly_origin1 numbers polygon p; -1 for none: a free edge of a screen) and inv_lambda[b] = f_b / c in 1/m for the table's B bands.  The
+ * library detects no edges.  All arithmetic is FP64 with no contraction, in this order; sqrt and / are the correctly rounded ones; every
+ * comparison with a NaN is false; dot(x, y) = (x0*y0 + x1*y1) + x2*y2.  S = pos, power[b] and gain_b are the scene's source; c and rr are
+ * receiver k as stored; W = (double)n_weight; edge j is a, b with e = b - a (per component).
+ * Per receiver k, exactly the shadow ray and the eligibility of "Direct sound":
+ *
+ *   v = c - S;  d2 = (vx*vx + vy*vy) + vz*vz;  eligible iff d2 > rr
+ *   blocked_k = hare_occluded(origin S, direction v, no exclusion, t_max = 1.0)
+ *
+ * Per pair (j, k) with k eligible, in any order (integer sums are order-free):
+ *
+ *   ee = dot(e, e);  ts = dot(S - a, e) / ee;  tr = dot(c - a, e) / ee          the feet of S and c on the edge's line
+ *   ps = S - (a + e*ts)  per component;  hs = sqrt(dot(ps, ps));  pr, hr likewise from c and tr
+ *   hsum = hs + hr;  t = (ts*hr + tr*hs) / hsum                                  the apex of the shortest path over the line
+ *   A = a + e*t;  u = A - S;  w = c - A;  ls2 = dot(u, u);  lr2 = dot(w, w)
+ *   ls = sqrt(ls2);  lr = sqrt(lr2);  delta = (ls + lr) - sqrt(d2)               the detour
+ *   accepted  iff  hsum > 0 && t > 0 && t < 1 && ls2 > 0 && lr2 > rr && delta > 0 && delta <= max_detour
+ *   occluded = hare_occluded(origin A, direction w,     poly_origin1 = faces[2j], poly_origin2 = faces[2j+1], t_max = 1.0)
+ *           || hare_occluded(origin A, direction S - A, poly_origin1 = faces[2j], poly_origin2 = faces[2j+1], t_max = 1.0)
+ *   if accepted && blocked_k && !occluded:
+ *     q  = ls / lr;  S* = (A.x - wx*q, A.y - wy*q, A.z - wz*q)                   the source unfolded about the apex onto the receiver's leg
+ *     the deposit of "Image sources (first order)" with S* in S' 's place: v* = c - S*, d2* = dot(v*, v*), dist = sqrt(d2*),
+ *     y = rr / d2*, f = (0.5 * y) / (1.0 + sqrt(1.0 - y)), xb = dist / bin_len, a = -(v* / dist), detections as there, and
+ *     g_b = gain_b(u)                                        "Source"'s lookup, not normalised; 1.0 without a table
+ *     r_b = 1.0 / (3.0 + 20.0 * ((2.0 * delta) * inv_lambda[b]))
+ *     m_b = (((power[b] * g_b) * r_b) * (f * W)) * 2^frac_bits                   then quantised exactly as the direct deposit's m_b
+ *
+ * The deposit stores no detour: it forms u, ls, lr, d2 and delta again from the stored apex A and the stored w by the operations above, so
+ * it sees the bits the search saw.
+ * What this is and is not.  r_b is Maekawa's ENERGY attenuation for a thin screen, 1 / (3 + 20 N) with the Fresnel number
+ * N = 2 delta / lambda_b: a 5 dB step (1/3) at the shadow boundary, falling with frequency and detour.  A receiver the source sees gets no
+ * diffracted path at all: the direct sound covers it, so across the shadow boundary the energy steps from the direct sound's to a third of
+ * it.  "Blocked" is a blocked CENTER ray, as in "Direct sound".  One edge per path: no path over two edges (a thick barrier's far edge), no
+ * reflection before or behind the edge.  S* lies on the line from c through A, ls beyond A, so the arrival direction is
+ * the apex's and the path length |c - S*| is ls + lr up to the rounding of the operations stated.  Both faces are excluded on both legs,
+ * so a wedge's own faces do not block the legs that leave along them; walls and other obstacles do.
+ * The pair list.  Accepted pairs go to a list of max_pairs records.  If the scene yields more, the deposit adds NOTHING at all (the count is
+ * order-free, so this outcome is deterministic); hare_diffract_paths then returns HARE_E_NOMEM with the count in *found.
+ * Where it goes.  No receive call takes a diffraction flag and hare_source_paths is unchanged: a caller adds the histogram of
+ * hare_diffract_paths to that of hare_source_paths or of a receive call as wrapping uint64 words (or runs hare_diffract_device onto the same
+ * device histogram), with the same n_weight, bin_len and frac_bits.  With bin_len = c / fs it is what hare_hist_impulses takes.
+ *
  * The histogram is fixed point in uint64: integer sums do not depend on the order of the adds, so the result is bit-identical from
  * run to run, between the one-device and the sharded call, and against a restatement on the host.  (r*r is formed once, when the
  * receivers are set: the same FP64 product.)
@@ -1156,6 +1203,35 @@ HARE_API int hare_image_device(hare_scene *s, int32_t kind, int32_t top_index, i
 HARE_API int hare_image2_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL, _ORDER2, _ORDER3 only */,
                                 int32_t n_bins, double bin_len, int32_t frac_bits, int64_t max_cands, int64_t max_paths, void *d_work,
                                 void *d_hist, void *d_detections, void *stream);
+/* The diffracting edges of Model[top_index] ("receivers", "Edge diffraction (first order)"): a setter like those above.  ends: E x 6 (a, b);
+ * faces: E x 2, the polygons that meet in each edge, -1 for none; inv_lambda: B values f_b / c.  Checked in this order (HARE_E_INVALID; a
+ * refused call changes nothing): top_index; E within 1 .. 2^20 and no array null (E = 0 with ends and faces NULL removes the table); every
+ * end finite; a != b (the FP64 dot(e, e) > 0 and finite); every face within -1 .. P - 1; B within 1 .. 8; every inv_lambda finite and >= 0.
+ * "edges" / "edges:<top>" read E back. */
+HARE_API int hare_scene_set_edges(hare_scene *s, int32_t top_index, int32_t E, const double *ends /* E x 6: a, b */,
+                                  const int32_t *faces /* E x 2 */, int32_t B, const double *inv_lambda /* B */);
+/* First-order edge diffraction on DEVICE buffers ("receivers", "Edge diffraction (first order)"): one direct visibility query per receiver,
+ * the pair search edges x receivers, two shadow rays per accepted pair -- ONE occlusion query for all of them -- and one deposit per pair
+ * whose receiver the source does not see and whose legs are free, from the scene's source, standing for n_weight source rays.
+ * Stream-ordered like hare_direct_device: no allocation, no free, no wait.  d_hist and d_detections are ACCUMULATED, shaped as
+ * hare_direct_device's.  d_work is scratch of HARE_DIFFRACT_WORK_BYTES(K, max_pairs) bytes on a 16-byte boundary: a 256-byte head whose
+ * first 8-byte word receives the number of pairs found; the K direct shadow rays with t_max, two exclusion words and a flag each; the list
+ * of max_pairs records (two shadow rays, two t_max, 2 x 2 exclusion words, two flags, k and j; the detour is re-formed, not stored), in
+ * unspecified order.  If more than max_pairs pairs are found nothing is deposited; the caller reads the count from the first word behind
+ * the stream.  Checked as hare_image_device checks, in its order (1 <= max_pairs <= 2^26 in its place), then max_detour not NaN and >= 0
+ * (+inf: no limit), then a source whose B is not the edge table's, then the buffers (HARE_E_INVALID); then HARE_E_NODEVICE; then
+ * HARE_E_STATE: no source, no receivers, no edges for top_index, or the partition not built. */
+#define HARE_DIFFRACT_WORK_BYTES(K, max_pairs) (256 + 68 * (int64_t)(K) + 144 * (int64_t)(max_pairs))
+HARE_API int hare_diffract_device(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL, _ORDER2, _ORDER3 only */,
+                                  int32_t n_bins, double bin_len, int32_t frac_bits, double max_detour, int64_t max_pairs, void *d_work,
+                                  void *d_hist, void *d_detections, void *stream);
+/* The same from host buffers, built as hare_source_paths is: a batch context leased, histogram and detections zeroed, one enqueue, the
+ * downloads, one synchronisation.  hist and detections are WRITTEN; found (nullable) receives the number of pairs found.  More pairs than
+ * max_pairs: HARE_E_NOMEM, hist and detections all zero, the count in *found and in hare_last_error().  Checks and their order as
+ * hare_diffract_device's, with hist and detections in the buffers' place. */
+HARE_API int hare_diffract_paths(hare_scene *s, int32_t kind, int32_t top_index, int64_t n_weight, uint32_t flags /* HARE_RECEIVE_DIRECTIONAL, _ORDER2, _ORDER3 only */,
+                                 int32_t n_bins, double bin_len, int32_t frac_bits, double max_detour, int64_t max_pairs, uint64_t *hist,
+                                 uint64_t *detections, uint64_t *found /* nullable */);
 /* The same from host buffers (threading and staging as hare_bounce_batch's last-cast-only path: one enqueue, one synchronisation; no
  * events are downloaded).  state_in nullable (every ray starts at L = 0, E = 1); state_out nullable ((1 + B) x n, as d_state).
  * hist (K x n_bins x B, x 4 with HARE_RECEIVE_DIRECTIONAL, x 9 / x 16 with the order flags) and detections (2 K) are WRITTEN, not accumulated; ctr nullable: counters summed over the casts.  flags as
